@@ -13,7 +13,9 @@ per GPU, index replicated); the only exchange is one RCCL all-reduce of the Incr
 kernel_path_mreads / _ms_per_step, the per-kernel ms and fractions, valu_issue_* (wave-instructions against the issue ceiling),
 and the rates of the legs below (memo_mreads, sub1_mreads, mixed99_mreads, host_fed_mreads, cli_e2e_mreads ...).
 
-Beside `value` the same JSON line carries, at N=1:
+A plain run (no --full) sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, `config` and the
+`roofline` of that step.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).  With --full the same
+JSON line also carries, at N=1:
   kernel_path   the `value` ctx on reads with 1 % substitutions
   memo_tier     configs[2] on the library's DEFAULT ctx (memo on: error-free window-sized reads are its keys -- a table look-up)
   robustness    the default ctx on reads the memo cannot answer: 1 % substitutions per base; 99 % random reads
@@ -26,7 +28,7 @@ Beside `value` the same JSON line carries, at N=1:
   cli_e2e       build/groot-hip align: FASTQ file -> BAM file + GFAs, the whole process
   cpu_baseline  the oracle (CPU restatement of the reference path) as one process per granted CPU
 
-  python bench.py --gpus 1 --steps 200 --warmup 5
+  python bench.py --gpus 1 --steps 200 --warmup 5 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 """
@@ -498,6 +500,39 @@ def cli_e2e(index, d_seq, n_reads, bam_level):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT = 64 << 20       # bytes of all --dump-outputs files together
+DUMP_TRAVS = 1 << 18        # traversal records kept when the step made more: a fixed, seeded sample
+DUMP_SEED = 0x67726F6F74
+
+
+def dump_outputs(out_dir, counts, travs, masks, call_counts):
+    """--dump-outputs: what a caller of the timed path holds after the last step, as float64 .npy files (every value is an integer
+    below 2**53, so the conversion is exact), for comparing two builds output by output on the same arguments:
+      counts.npy       [11]                  the step's counts, in the field order of device.Counts
+      call_counts.npy  [n_windows]           the IncrementSubPath call-count table (summed over the timed steps and the ranks)
+      trav_index.npy   [S]                   which of the step's traversal records follow: all of them, or a sorted seeded sample
+      travs.npy        [S, 6]                read_id, graph_id, node, offset, ord, flags of those records
+      trav_paths.npy   [S, 2 * path_words]   their path sets, every 64-bit word as its low and high 32-bit halves"""
+    from groot_amd import device
+
+    out = {"counts": np.array([counts[n] for n, _ in device.Counts._fields_], dtype=np.float64),
+           "call_counts": np.asarray(call_counts).view(np.uint32).astype(np.float64)}
+    n, pw = len(travs), masks.shape[1]
+    row_bytes = 8 * (1 + 6 + 2 * pw)
+    cap = min(DUMP_TRAVS, (DUMP_LIMIT - sum(a.nbytes for a in out.values())) // row_bytes)
+    keep = np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False)) if n > cap else np.arange(n)
+    t = travs[keep]
+    m = masks[keep]
+    out["trav_index"] = keep.astype(np.float64)
+    out["travs"] = np.stack([t[f] for f in ("read_id", "graph_id", "node", "offset", "ord", "flags")], axis=1).astype(np.float64)
+    out["trav_paths"] = np.stack([m & 0xFFFFFFFF, m >> 32], axis=2).reshape(len(keep), 2 * pw).astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 COMPACT_LIMIT = 8000     # the driver keeps an 8 KB tail of stdout and parses the last line; round 5's 20 KB line did not parse
 
@@ -579,11 +614,15 @@ def emit(full):
     print(compact_line(full), flush=True)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every leg (kernel_path, lean_first, memo_tier, robustness, thresholds, mixed, host_fed, "
+                         "cli_e2e, cpu_baseline; the --no-* options below drop single ones); without it only the headline is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/*.npy (dump_outputs)")
     ap.add_argument("--reads", type=int, default=10_000_000, help="reads per GPU per step")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target wall time of the all-cores CPU baseline run")
     ap.add_argument("--no-cpu", action="store_true")
@@ -600,7 +639,17 @@ def main():
     ap.add_argument("--no-align", action="store_true", help="diagnostic: --noAlign mode (weights only, no BAM records)")
     ap.add_argument("--background", type=float, default=0.0,
                     help="diagnostic: fraction of reads replaced by uniform random ACGT (metagenome-like input, SURVEY 8d)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does only what `value` and `ms_per_step` need: no leg, and neither the CLI nor the oracle is built
+        args.no_legs = args.no_host_fed = args.no_cli = args.no_cpu = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
 
@@ -736,6 +785,13 @@ def main():
         dist.all_gather(allr, mine)
         per_rank = [[float(x[0].item()), float(x[1].item())] for x in allr]
         log("rank %d: %.3f ms per step, all-reduce of the call counts %.3f ms" % (rank, t_steps / args.steps * 1e3, t_reduce * 1e3))
+
+    if rank == 0 and args.dump_outputs:
+        # (before any leg: kernel_path submits other batches through the same ctx)
+        travs, masks = al.travs()
+        dump_outputs(args.dump_outputs, counts, travs, masks, d_att.cpu().numpy())
+        del travs, masks
+        log("outputs of the last timed step written to", args.dump_outputs)
 
     if rank == 0:
         total_reads = world * R * args.steps

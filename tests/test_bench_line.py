@@ -99,3 +99,50 @@ def test_emit_prints_the_compact_line_last_and_keeps_the_full_object(tmp_path, m
     for f in (tmp_path / "bench_full.json", tmp_path / "gpurun_out" / "bench_full.json"):
         assert json.load(open(f))["roofline"]["kernels"]          # the per-kernel blocks live in the full object
     assert "kernels" in err.getvalue()
+
+
+def test_a_plain_run_is_the_headline_only():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert plain.no_legs and plain.no_host_fed and plain.no_cli and plain.no_cpu
+    full = bench.parse_args(["--full", "--no-cpu", "--dump-outputs", "out"])
+    assert full.full and full.dump_outputs == "out" and full.no_cpu
+    assert not (full.no_legs or full.no_host_fed or full.no_cli)
+    with pytest.raises(SystemExit), redirect_stderr(io.StringIO()):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_keeps_a_seeded_sample_exactly(tmp_path):
+    import numpy as np
+
+    from groot_amd import device
+
+    n, pw = 300_000, 3
+    rng = np.random.default_rng(1)
+    travs = np.zeros(n, dtype=device.TRAV_DTYPE)
+    for f in ("read_id", "graph_id", "node", "offset"):
+        travs[f] = rng.integers(0, 1 << 32, n, dtype=np.uint32)
+    travs["ord"] = rng.integers(0, 1 << 16, n, dtype=np.uint16)
+    travs["flags"] = rng.integers(0, 16, n, dtype=np.uint8)
+    masks = rng.integers(0, 1 << 64, (n, pw), dtype=np.uint64, endpoint=False)
+    counts = {name: i * 1000 + 7 for i, (name, _) in enumerate(device.Counts._fields_)}
+    table = rng.integers(-(1 << 31), 1 << 31, 322_333, dtype=np.int32)       # uint32 counts as a torch int32 tensor holds them
+    runs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), counts, travs, masks, table)
+        runs.append({f[:-4]: np.load(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))})
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= bench.DUMP_LIMIT
+    a, b = runs
+    assert set(a) == {"counts", "call_counts", "trav_index", "travs", "trav_paths"}
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k
+    assert list(a["counts"]) == list(counts.values())
+    assert np.array_equal(a["call_counts"], table.view(np.uint32).astype(np.float64))
+    keep = a["trav_index"].astype(np.int64)
+    assert len(keep) == bench.DUMP_TRAVS and np.all(np.diff(keep) > 0) and keep[-1] < n
+    assert np.array_equal(a["travs"][:, 0], travs["read_id"][keep]) and np.array_equal(a["travs"][:, 5], travs["flags"][keep])
+    halves = a["trav_paths"].astype(np.uint64).reshape(len(keep), pw, 2)
+    assert np.array_equal(halves[:, :, 0] | (halves[:, :, 1] << np.uint64(32)), masks[keep])
+    # a step with fewer records keeps all of them
+    small = bench.dump_outputs(str(tmp_path / "c"), counts, travs[:1000], masks[:1000], table)
+    assert np.array_equal(small["trav_index"], np.arange(1000))

@@ -242,7 +242,7 @@ def test_bench_multi_rank_code_path(argannot_index, tmp_path):
     # every rank's own step time and its all-reduce time are on the line, so that a scaling run can be read rank by rank
     assert len(line["per_rank"]["ms_per_step"]) == 2 and len(line["per_rank"]["allreduce_ms"]) == 2 and min(line["per_rank"]["ms_per_step"]) > 0
     assert line["roofline"]["allreduce_ms_max"] >= 0 and line["roofline"]["rank_ms_per_step_max"] >= line["roofline"]["rank_ms_per_step_min"]
-    one = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--reads", "300000", "--no-cpu",
+    one = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--reads", "300000", "--no-cpu",
                           "--leg-steps", "2", "--mixed-reads", "30000", "--mixed-cli-reads", "5000", "--host-fed-seconds", "0.3"],
                          cwd=REPO, capture_output=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -271,6 +271,37 @@ def test_bench_multi_rank_code_path(argannot_index, tmp_path):
         assert isinstance(rf.get(k), float) and rf[k] > 0, (k, rf.get(k))
     assert single["memo_tier"]["walked_reads"] < 0.05 * 300000 and single["kernel_path"]["substitutions_1pct"]["value"] > 0
     assert single["cli_e2e"].get("value", 0) > 0 and single["cli_e2e"]["reads"] == 300000, single["cli_e2e"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(argannot_index, tmp_path):
+    """bench.py without --full: the headline only (no leg on the line), --steps timed steps, and --dump-outputs writes the last step's
+    outputs -- the same on every run with the same inputs; the call-count table, summed over the timed steps, scales with --steps"""
+    import json
+    import sys
+
+    dumps = {}
+    for steps in (2, 4):
+        d = tmp_path / ("s%d" % steps)
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", "1", "--reads", "300000",
+                            "--dump-outputs", str(d)], cwd=REPO, capture_output=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        compact = json.loads(r.stdout.decode().strip().splitlines()[-1])
+        assert compact["steps"] == steps and compact["ms_per_step"] > 0 and compact["value"] > 0 and "cpu_baseline" not in compact
+        assert "leg_errors" not in compact and "memo_mreads" not in compact["roofline"] and "host_fed_mreads" not in compact["roofline"]
+        full = json.load(open(os.path.join(REPO, "bench_full.json")))
+        assert full["steps"] == steps and not {"kernel_path", "memo_tier", "thresholds", "mixed", "host_fed", "cli_e2e"} & set(full)
+        dumps[steps] = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= 64 << 20
+        assert all(a.dtype == np.float64 for a in dumps[steps].values())
+        c = dict(zip((n for n, _ in device.Counts._fields_), dumps[steps]["counts"]))
+        assert c["received"] == 300000 and c == {k: full["config"]["per_step_counts"][k] for k in c}
+        assert len(dumps[steps]["travs"]) == min(c["travs"], 1 << 18) > 0
+    a, b = dumps[2], dumps[4]
+    assert set(a) == {"counts", "call_counts", "trav_index", "travs", "trav_paths"} == set(b)
+    for k in ("counts", "trav_index", "travs", "trav_paths"):
+        assert np.array_equal(a[k], b[k]), k
+    assert a["call_counts"].sum() > 0 and np.array_equal(2 * a["call_counts"], b["call_counts"])
 
 
 @pytest.mark.gpu
