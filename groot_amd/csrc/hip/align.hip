@@ -30,4 +30,13 @@ void launch_align_lean(uint32_t pw, const LeanArgs &a, dim3 grid, hipStream_t st
     else hipLaunchKernelGGL((align_lean_kernel<3, 8>), grid, dim3(kBlock), lds, st, a);
 }
 
+void launch_align_path(uint32_t pw, const LeanArgs &a, dim3 grid, hipStream_t st)
+{
+    if (pw != 3) return;
+    const size_t lds = (size_t)kBlock * a.lds_stride_dw * 4;
+    if (a.max_len <= 128) hipLaunchKernelGGL((align_path_kernel<3, 4>), grid, dim3(kBlock), lds, st, a);
+    else if (a.max_len <= 160) hipLaunchKernelGGL((align_path_kernel<3, 5>), grid, dim3(kBlock), lds, st, a);
+    else hipLaunchKernelGGL((align_path_kernel<3, 8>), grid, dim3(kBlock), lds, st, a);
+}
+
 } // namespace groot

@@ -39,6 +39,7 @@ struct DeviceCounters {
     unsigned int seeded_reads;  // reads with at least one seed whose alignment is not tabulated: the align stage's share of the processing order (they sort first)
     unsigned int tab_reads;     // reads the signature kernel answered from the outcome table
     unsigned int lean_reads;    // reads align_lean_kernel finished
+    unsigned int path_reads;    // reads align_path_kernel finished
     unsigned long long dbg[192]; // work counters (only with -DGROOT_WORK_COUNTERS): [e] wave iterations with event e, [32+e] lanes with it,
                                  // [64+b] lanes finishing their read b*2 iterations into the round, [128+b] rounds of that length
 };
@@ -360,6 +361,14 @@ struct LeanArgs {
     uint32_t *ovf_cnt;
     uint32_t ovf_cap;
     DeviceCounters *ctr;
+    // align_path_kernel only (kernels_path.hpp; built at open: build_path_tables)
+    const uint4 *path_node;        // [n_nodes][2] {text offset of the node's first base on its lowest path with a text, the node's index on it, end of that
+                                   // path's text, its node list in path_nodes; its sparse table in path_tab, its node count, 0, 0}; kEmpty: on no such path
+    const uint32_t *path_text;     // every path's text, 2 bits per base, 16 to a dword (+ slack for 17 dwords from any base)
+    const uint32_t *path_tag;      // likewise: bit 0 a node starts here; bit 1 with bit 0 the boundary is flagged, without it the base is an 'N'
+    const uint32_t *path_nodes;    // per path, its nodes in order (global node indices)
+    const uint64_t *path_tab;      // per path, the sparse table of its nodes' path sets, PW words per entry
+    uint4 *hold;                   // [n_reads][kPathHold][3] by slot: traversals with ord >= 1 until the read finishes
 };
 
 // LDS dwords per lane: 2 zero dwords, the read at 16 bases per dword (one strand at a time), 2 zero dwords, 7 dwords of the current window's record,

@@ -23,6 +23,7 @@
 #include "../common/cpus.hpp"
 #include "../common/view_check.hpp"
 #include "kernels_misc.hpp"
+#include "kernels_path.hpp"
 #include "launch.hpp"
 
 using namespace groot;
@@ -74,7 +75,7 @@ template <class T> struct PinBuf {
 // compare the tiers with each other and with the CPU checker); TEST_SMALL_BUFFERS starts every growable buffer and list too small, so that
 // a test batch walks the grow-and-redo and the fall-back paths; OPEN_STATS prints where groot_hip_open spent its time.
 struct Knobs {
-    bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false;
+    bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false;
     static Knobs read()
     {
         Knobs k;
@@ -82,7 +83,8 @@ struct Knobs {
         k.no_sig = getenv("GROOT_NO_SIG") != nullptr;                     k.force_rccl = getenv("GROOT_FORCE_RCCL") != nullptr;
         k.small_buffers = getenv("GROOT_TEST_SMALL_BUFFERS") != nullptr;  k.open_stats = getenv("GROOT_OPEN_STATS") != nullptr;
         k.poison = getenv("GROOT_TEST_POISON") != nullptr;
-        k.lean = getenv("GROOT_LEAN") != nullptr;                         // the align stage WITH its first pass (kernels_lean.hpp; off by default: DESIGN.md section 3)
+        k.lean = getenv("GROOT_LEAN") != nullptr;                         // the node-by-node first pass (kernels_lean.hpp) instead of the path-text one
+        k.no_path = getenv("GROOT_NO_PATH_PASS") != nullptr;              // no first pass: align_kernel alone
         return k;
     }
 };
@@ -101,6 +103,9 @@ struct Slot {
     bool sig_used = false;                 // the signature kernel ran in front of the full-width kernel for this batch
     uint32_t packed_q = 0;                 // SeedArgs::packed_q of the batch's signature kernel (0: it left no codes)
     bool lean_used = false;                // align_lean_kernel ran in front of align_kernel for this batch
+    bool path_used = false;                // align_path_kernel ran in front of align_kernel for this batch
+    uint32_t path_reads = 0;               // ... and finished this many reads
+    float path_ms = 0;                     // ... in this time (profiling on: the pass + its stream compaction)
     bool one_len = false;                  // the reads are known to have max_len bases each, or the caller said so (submit_device with max_len)
     uint64_t n_bases = 0, n_exc = 0;
     enum Input { IN_ASCII, IN_PACKED, IN_PACKED16, IN_DEVICE } input = IN_ASCII;
@@ -193,7 +198,11 @@ struct groot_ctx {
     DevBuf<uint4> cn_pre2;
     DevBuf<uint8_t> win_ok;
     DevBuf<uint4> lean_stk;                // LeanArgs::stk (align stream)
-    bool lean = false;
+    bool lean = false;                     // the first pass is align_lean_kernel (GROOT_LEAN=1)
+    bool path = false;                     // the first pass is align_path_kernel (the default; pw == 3)
+    DevBuf<uint4> path_node, path_hold;    // LeanArgs::path_* (kernels_path.hpp)
+    DevBuf<uint32_t> path_text, path_tag, path_nodes;
+    DevBuf<uint64_t> path_tab;
     DevBuf<WinRec> win_rec;
     DevBuf<ExactEntry> exact;
     DevBuf<SigEntry> sig;                  // sketch_sig_kernel: signature index + window texts (absent: that kernel is not used)
@@ -378,6 +387,109 @@ uint32_t round_pw(uint32_t pw)
     for (uint32_t c : {3u, 11u})   // NodeRec<3> = 64 B, NodeRec<11> = 128 B
         if (pw <= c) return c;
     return 0;
+}
+
+// ---- the first pass against path text (kernels_path.hpp): what it reads, built from the view at open ----
+struct PathTables {
+    std::vector<uint4> node;           // LeanArgs::path_node, two per node
+    std::vector<uint32_t> text, tag;   // LeanArgs::path_text / path_tag
+    std::vector<uint32_t> nodes;       // LeanArgs::path_nodes
+    std::vector<uint64_t> tab;         // LeanArgs::path_tab (three words per entry)
+    uint32_t n_text_paths = 0;
+    size_t n_bases = 0;
+};
+// false: the paths' texts hold 2^31 bases or more (the kernel addresses them with 32-bit bit offsets): no first pass against path text
+static bool build_path_tables(const groot_index_view *v, PathTables &pt)
+{
+    auto code_of = [](uint8_t b) -> int { return b == 'A' ? 0 : b == 'C' ? 1 : b == 'T' ? 2 : b == 'G' ? 3 : -1; };
+    auto nlen = [&](uint32_t n) { return v->node_seq_off[n + 1] - v->node_seq_off[n]; };
+    std::vector<uint32_t> gnode(v->n_nodes, 0);
+    for (uint32_t g = 0; g < v->n_graphs; g++)
+        for (uint32_t n = v->graph_node_off[g]; n < v->graph_node_off[g + 1]; n++) gnode[n] = g;
+    // flag[n]: the DFS's step out of node n is not decided by the read's next base alone -- more than four OutEdges (the node records
+    // hold four), two non-empty neighbours with the same first base, a neighbour that starts with an 'N'
+    std::vector<uint8_t> flag(v->n_nodes, 0);
+    for (uint32_t n = 0; n < v->n_nodes; n++) {
+        const uint32_t e0 = v->node_edge_off[n], deg = v->node_edge_off[n + 1] - e0;
+        uint32_t seen = 0;
+        bool f = deg > 4;
+        for (uint32_t e = 0; e < deg && !f; e++) {
+            const uint32_t ch = v->edges[e0 + e];
+            if (nlen(ch) == 0) continue;                   // never entered (dfsRecursive returns at once)
+            const int cd = code_of(v->bases[v->node_seq_off[ch]]);
+            if (cd < 0 || (seen >> cd) & 1u) f = true;
+            else seen |= 1u << cd;
+        }
+        flag[n] = f;
+    }
+    auto has_edge = [&](uint32_t a, uint32_t b) {
+        for (uint32_t e = v->node_edge_off[a]; e < v->node_edge_off[a + 1]; e++)
+            if (v->edges[e] == b) return true;
+        return false;
+    };
+    // every path's nodes by position; a path has a text when its nodes are non-empty, follow each other without gap or overlap, and are
+    // joined by OutEdges -- then its text is exactly what the DFS spells along it
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> pl(v->n_paths);
+    for (uint32_t n = 0; n < v->n_nodes; n++)
+        for (uint32_t i = v->node_np_off[n]; i < v->node_np_off[n + 1]; i++) {
+            const uint32_t gp = v->graph_path_off[gnode[n]] + v->np_path[i];
+            if (gp < v->n_paths) pl[gp].push_back({v->np_pos[i], n});
+        }
+    std::vector<uint8_t> ok(v->n_paths, 0);
+    size_t total = 0;
+    for (uint32_t p = 0; p < v->n_paths; p++) {
+        auto &L = pl[p];
+        std::sort(L.begin(), L.end());
+        bool good = !L.empty();
+        for (size_t i = 0; good && i < L.size(); i++) {
+            if (nlen(L[i].second) == 0) good = false;
+            else if (i + 1 < L.size() && ((uint64_t)L[i].first + nlen(L[i].second) != L[i + 1].first || !has_edge(L[i].second, L[i + 1].second))) good = false;
+        }
+        if (!good) continue;
+        ok[p] = 1;
+        pt.n_text_paths++;
+        total += (uint64_t)L.back().first + nlen(L.back().second) - L.front().first;
+    }
+    pt.n_bases = total;
+    if (total + 512 >= (1ull << 31)) return false;
+    pt.text.assign(total / 16 + 20, 0);
+    pt.tag.assign(total / 16 + 20, 0);
+    pt.node.assign((size_t)v->n_nodes * 2, make_uint4(kEmpty, 0, 0, 0));
+    const uint32_t pw = std::min<uint32_t>(v->path_words, 3);
+    size_t at = 0;
+    for (uint32_t p = 0; p < v->n_paths; p++) {
+        if (!ok[p]) continue;
+        const auto &L = pl[p];
+        const uint32_t n = (uint32_t)L.size(), nbase = (uint32_t)pt.nodes.size(), tbase = (uint32_t)(pt.tab.size() / 3);
+        const uint32_t tend = (uint32_t)(at + (L.back().first + nlen(L.back().second) - L.front().first));
+        uint32_t levels = 1;
+        while ((2ull << (levels - 1)) <= n) levels++;
+        pt.tab.resize(pt.tab.size() + (size_t)3 * levels * n, 0);
+        uint64_t *T = pt.tab.data() + (size_t)3 * tbase;
+        for (uint32_t i = 0; i < n; i++)
+            for (uint32_t w = 0; w < pw; w++) T[(size_t)3 * i + w] = v->node_mask[(size_t)L[i].second * v->path_words + w];
+        for (uint32_t k = 1; k < levels; k++)
+            for (uint32_t i = 0; i + (1u << k) <= n; i++)
+                for (uint32_t w = 0; w < 3; w++)
+                    T[(size_t)3 * ((size_t)k * n + i) + w] = T[(size_t)3 * ((size_t)(k - 1) * n + i) + w] & T[(size_t)3 * ((size_t)(k - 1) * n + i + (1u << (k - 1))) + w];
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t nd = L[i].second, s0 = v->node_seq_off[nd], len = nlen(nd);
+            if (pt.node[2 * (size_t)nd].x == kEmpty) {          // the node's lowest path with a text
+                pt.node[2 * (size_t)nd] = make_uint4((uint32_t)at, i, tend, nbase);
+                pt.node[2 * (size_t)nd + 1] = make_uint4(tbase, n, 0, 0);
+            }
+            pt.nodes.push_back(nd);
+            for (uint32_t j = 0; j < len; j++, at++) {
+                const int cd = code_of(v->bases[s0 + j]);
+                const uint32_t tg = j == 0 ? 1u | ((i > 0 && flag[L[i - 1].second]) ? 2u : 0u) : (cd < 0 ? 2u : 0u);
+                pt.text[at >> 4] |= (uint32_t)(cd < 0 ? 0 : cd) << (2 * (at & 15));
+                pt.tag[at >> 4] |= tg << (2 * (at & 15));
+            }
+        }
+    }
+    if (pt.nodes.empty()) pt.nodes.push_back(0);
+    if (pt.tab.empty()) pt.tab.assign(3, 0);
+    return true;
 }
 
 template <int PW> void build_node_records(const groot_index_view *v, std::vector<unsigned char> &out)
@@ -590,7 +702,7 @@ static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
         a.list_stride_dw = list_lds_stride(stride_dw);
         HIP_TRY(c, hipMemsetAsync(c->todo_count.p, 0, sizeof(uint32_t), c->stream));
         // (the reads it decides it also leaves as 2-bit codes for the first pass of the align stage)
-        if (c->lean && !c->tab_capture && w->packed.p) { a.packed = w->packed.p; a.packed_q = s->max_len <= 128 ? 2u : 4u; }
+        if ((c->lean || c->path) && !c->tab_capture && w->packed.p) { a.packed = w->packed.p; a.packed_q = s->max_len <= 128 ? 2u : 4u; }
         s->packed_q = a.packed ? a.packed_q : 0;
         launch_sig(c->s, a, s->max_len, c->stream);
         HIP_TRY(c, hipGetLastError());
@@ -704,7 +816,10 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
     else if (c->dfs_frac >= kSparseBelow && c->dfs_frac < 0.6 && !s->mixed_len && blocks >= 4) blocks /= 2;
     // (the first pass takes most reads: what it left in the latest batch sizes the persistent grid of the second -- a wavefront per 64 reads left,
     // at least one workgroup per CU; the registers it does not hold go to the next batch's hashing kernels)
-    if (c->lean && !c->tab_capture && c->lean_left_frac < 0.25) {
+    // (only when a first pass runs for THIS batch: long-read and sparse batches keep the whole grid)
+    s->lean_used = c->lean && !c->tab_capture && s->n_reads && s->max_len <= kLeanMaxLen && c->dfs_frac >= 0.02;
+    s->path_used = c->path && !c->tab_capture && s->n_reads && s->max_len <= kLeanMaxLen && c->dfs_frac >= 0.02;
+    if ((s->lean_used || s->path_used) && c->lean_left_frac < 0.25) {
         uint32_t want = (uint32_t)(c->lean_left_frac * 1.25 * (double)s->n_reads / 64.0 / (kBlock / 64)) + 1u;
         blocks = std::max(1u, std::min(blocks, std::max(want, c->n_cu)));
     }
@@ -743,8 +858,7 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
     // (GROOT_LEAN=1: every batch that has reads to walk.  Measured, DESIGN.md section 3: alone on the chip the two passes take 2.2 + 0.7 ms where align_kernel
     // takes 3.0 on configs[2]; beside the next batch's hashing kernels the step is between 1.5 % shorter and 8 % longer from box to box, and batches of
     // mixed lengths or of reads with errors are slower -- hence off by default.)
-    s->lean_used = c->lean && !c->tab_capture && s->n_reads && s->max_len <= kLeanMaxLen && c->dfs_frac >= 0.02;
-    if (s->lean_used) {
+    if (s->lean_used || s->path_used) {
         LeanArgs l{};
         l.nodes = c->lean_nodes.p; l.ext = c->lean_ext.p; l.bases2 = c->bases2.p; l.cn_pre2 = c->cn_pre2.p; l.win_ok = c->win_ok.p;
         l.win_rec = c->dix.win_rec; l.node_l2b = c->dix.node_l2b; l.q_row = c->q_row.p;
@@ -759,7 +873,11 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
         // workgroups for the reads expected to have seeds (the latest batch says how many: they come first in the processing order); the slots
         // beyond them, if the batch has more, go to align_kernel like the flagged ones
         const uint32_t lean_blocks = std::min<uint32_t>((s->n_reads + kBlock - 1) / kBlock, (uint32_t)(c->dfs_frac * 1.05 * (double)s->n_reads / kBlock) + 64u);
-        launch_align_lean(c->pw, l, dim3(lean_blocks), c->astream);
+        if (s->path_used) {
+            l.path_node = c->path_node.p; l.path_text = c->path_text.p; l.path_tag = c->path_tag.p; l.path_nodes = c->path_nodes.p; l.path_tab = c->path_tab.p;
+            l.hold = c->path_hold.p;
+            launch_align_path(c->pw, l, dim3(lean_blocks), c->astream);
+        } else launch_align_lean(c->pw, l, dim3(lean_blocks), c->astream);
         HIP_TRY(c, hipGetLastError());
         size_t tb = 0;
         rocprim::counting_iterator<uint32_t> ids(0u);
@@ -1139,7 +1257,7 @@ static int finish_counters(groot_ctx *c, Slot *s)
             merged.flags = keep | again.flags;
             merged.q_rows = again.q_rows;
             merged.mask_words = again.mask_words;
-            merged.todo_reads = again.todo_reads; merged.tab_reads = again.tab_reads; merged.lean_reads = again.lean_reads;
+            merged.todo_reads = again.todo_reads; merged.tab_reads = again.tab_reads; merged.lean_reads = again.lean_reads; merged.path_reads = again.path_reads;
             h = merged;
         } else h = again;
     }
@@ -1151,6 +1269,7 @@ static int finish_counters(groot_ctx *c, Slot *s)
     o.full_sketch_reads = (s->sig_used || s->text_used) ? h.todo_reads : s->n_reads;
     o.walked_reads = h.seeded_reads;
     o.lean_reads = h.lean_reads;
+    s->path_reads = s->path_used ? h.path_reads : 0;
     if (s->status == GROOT_OK) {
         char buf[256];
         if (h.flags & kFlagLongRead) { s->status = GROOT_E_NOSPACE; snprintf(buf, sizeof buf, "a read is longer than max_read_len=%u", c->prm.max_read_len); s->status_msg = buf; }
@@ -1190,6 +1309,9 @@ static int finish_counters(groot_ctx *c, Slot *s)
                 (double)h.dbg[144] / nw, (double)h.dbg[145] / nw, (double)h.dbg[146] / nw, (double)h.dbg[147] / nw, (double)h.dbg[149] / nw / 100.0, (double)h.dbg[150] / nw / 100.0);
         fprintf(stderr, "[groot lean] finished without an alignment %llu; left to align_kernel: seeds > 4: %llu, byte > T / length: %llu, byte other than ACGT: %llu, window with an N: %llu, node with an N: %llu, N ahead: %llu, three neighbours: %llu, third pending: %llu, too many steps: %llu\n",
                 h.dbg[160], h.dbg[161], h.dbg[163], h.dbg[164], h.dbg[165], h.dbg[166], h.dbg[167], h.dbg[168], h.dbg[169], h.dbg[170]);
+        if (s->path_used)
+            fprintf(stderr, "[groot path] left to align_kernel: node on no path with a text %llu, event on the start base %llu, more than %u records %llu; segments ended: empty path set %llu, read's end %llu, end of the path's text %llu, flagged boundary %llu, jump %llu\n",
+                    h.dbg[171], h.dbg[172], kPathHold + 1, h.dbg[173], h.dbg[176], h.dbg[177], h.dbg[178], h.dbg[179], h.dbg[180]);
     }
 #elif defined(GROOT_WORK_COUNTERS)
     for (int e = 0; e < 32; e++)
@@ -1215,7 +1337,10 @@ static int finish_counters(groot_ctx *c, Slot *s)
     // the records were copied out by copy_out_kernel right behind the kernels; after a redo they are fetched again here
     if (s->n_reads) c->trav_per_read = (double)s->n_trav / (double)s->n_reads;
     if (s->n_reads && !c->tab_capture) c->dfs_frac = (double)h.seeded_reads / (double)s->n_reads;
-    if (s->n_reads && !c->tab_capture && s->lean_used) c->lean_left_frac = (double)(h.seeded_reads - std::min(h.seeded_reads, h.lean_reads)) / (double)s->n_reads;
+    if (s->n_reads && !c->tab_capture && (s->lean_used || s->path_used)) {
+        const uint32_t first = s->path_used ? h.path_reads : h.lean_reads;
+        c->lean_left_frac = (double)(h.seeded_reads - std::min(h.seeded_reads, first)) / (double)s->n_reads;
+    }
     if (s->n_reads && (s->sig_used || s->text_used)) c->todo_frac = (double)h.todo_reads / (double)s->n_reads;
     if (s->n_reads && !c->tab_capture && c->dix.text_tab) {
         c->text_hit_frac = s->text_used ? 1.0 - (double)h.todo_reads / (double)s->n_reads : (double)h.tab_reads / (double)s->n_reads;
@@ -1281,8 +1406,9 @@ static int collect_impl(groot_ctx *c, Slot **out)
         (void)hipEventElapsedTime(&s->ms.first_seed_kernel, s->ev[7], s->ev[8]);
         (void)hipEventElapsedTime(&s->ms.order_kernel, s->ev[9], s->ev[10]);
         (void)hipEventElapsedTime(&s->ms.list_pass, s->ev[8], s->ev[12]);
-        s->ms.lean_pass = 0;
+        s->ms.lean_pass = 0; s->path_ms = 0;
         if (s->lean_used) (void)hipEventElapsedTime(&s->ms.lean_pass, s->ev[11], s->ev[13]);
+        if (s->path_used) (void)hipEventElapsedTime(&s->path_ms, s->ev[11], s->ev[13]);
         (void)hipEventElapsedTime(&s->ms.wall, s->ev[1], s->ev[5]);
         if (!c->prm.results_on_device) (void)hipEventElapsedTime(&s->ms.d2h, s->ev_d2h0, s->ev_d2h);
     }
@@ -2122,7 +2248,21 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
     }
     // ---- first pass of the align stage (kernels_lean.hpp): everything at 2 bits per base ----
     c->lean = c->pw == 3 && c->kn.lean && !c->prm.no_exact_align;
-    if (c->lean) {
+    c->path = c->pw == 3 && !c->kn.lean && !c->kn.no_path && !c->prm.no_exact_align;
+    PathTables pt;
+    if (c->path) c->path = build_path_tables(v, pt);
+    if (c->path) {
+        HIP_TRY(c, upload(c->path_node, pt.node.data(), pt.node.size()));
+        HIP_TRY(c, upload(c->path_text, pt.text.data(), pt.text.size()));
+        HIP_TRY(c, upload(c->path_tag, pt.tag.data(), pt.tag.size()));
+        HIP_TRY(c, upload(c->path_nodes, pt.nodes.data(), pt.nodes.size()));
+        HIP_TRY(c, upload(c->path_tab, pt.tab.data(), pt.tab.size()));
+        if (c->kn.open_stats)
+            fprintf(stderr, "[groot open] path tables: %u of %u paths with a text, %zu bases; node records %.2f MB, text + tags %.2f MB, node lists %.2f MB, sparse tables %.2f MB\n",
+                    pt.n_text_paths, v->n_paths, pt.n_bases, pt.node.size() * 16 / 1e6, (pt.text.size() + pt.tag.size()) * 4 / 1e6, pt.nodes.size() * 4 / 1e6, pt.tab.size() * 8 / 1e6);
+        pt = PathTables();
+    }
+    if (c->lean || c->path) {
         auto code_of = [](uint8_t b) -> int { return b == 'A' ? 0 : b == 'C' ? 1 : b == 'T' ? 2 : b == 'G' ? 3 : -1; };
         std::vector<uint32_t> b2((size_t)(v->n_bases + 15) / 16 + 20, 0);
         for (uint64_t i = 0; i < v->n_bases; i++) {
@@ -2464,7 +2604,7 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
         HIP_TRY(c, w.read_rec.alloc(R));
         HIP_TRY(c, w.perm.alloc(R));
         HIP_TRY(c, w.perm_count.alloc(4));
-        if (c->lean) {
+        if (c->lean || c->path) {
             HIP_TRY(c, w.perm2.alloc(R));
             HIP_TRY(c, w.perm2_count.alloc(4));
             HIP_TRY(c, w.defer.alloc(R));
@@ -2480,7 +2620,8 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
         HIP_TRY(c, hipMemset(w.vcount.p, 0, 4 * sizeof(uint32_t)));
     }
     HIP_TRY(c, c->trav_off.alloc(R));
-    if (c->lean) HIP_TRY(c, c->lean_stk.alloc((size_t)R * 4));
+    if (c->lean || c->path) HIP_TRY(c, c->lean_stk.alloc((size_t)R * 4));
+    if (c->path) HIP_TRY(c, c->path_hold.alloc((size_t)R * 3 * kPathHold));
     HIP_TRY(c, c->ovf_cnt.alloc(kOvfShards + 2));
     if (int rc = alloc_ovf(c, c->kn.small_buffers ? 2u : std::max<uint32_t>(256, R / kOvfShards / 4))) return rc;
     // the align kernel is persistent: exactly the workgroups that are resident at once (GROOT_ALIGN_WAVES per SIMD = per CU)
@@ -3019,6 +3160,16 @@ int groot_hip_stage_ms(groot_ctx *c, groot_stage_ms *out)
     if (!c || !out) return GROOT_E_INVALID;
     if (c->waited) *out = c->waited->ms;
     else memset(out, 0, sizeof *out);
+    return GROOT_OK;
+}
+
+int groot_hip_path_pass_stats(groot_ctx *c, uint32_t *ran, uint64_t *reads, float *ms)
+{
+    if (!c || !ran || !reads || !ms) return GROOT_E_INVALID;
+    const Slot *s = c->waited;
+    *ran = s && s->path_used ? 1u : 0u;
+    *reads = *ran ? s->path_reads : 0;
+    *ms = *ran ? s->path_ms : 0.0f;
     return GROOT_OK;
 }
 

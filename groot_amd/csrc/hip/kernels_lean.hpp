@@ -1,6 +1,7 @@
 #pragma once
 
 #include "kernels_common.hpp"
+#include "kernels_path.hpp"
 
 namespace groot {
 
@@ -56,9 +57,11 @@ __device__ __forceinline__ uint64_t lean_bits64(const uint32_t *wp, uint32_t bit
     return lean_funnel(q[0], q[1], q[2], bit & 31u);
 }
 
+// The body of both first passes: PATH = false walks node by node (align_lean_kernel), PATH = true compares the read against the text of
+// one path at a time (align_path_kernel, kernels_path.hpp).  Staging, the hierarchy, the graphMinion loop and the commit are shared.
 // NCH: 64-bit pieces a node comparison looks at (reads of up to 32 * NCH bases)
-template <int PW, int NCH>
-__global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs a)
+template <int PW, int NCH, bool PATH>
+__device__ __forceinline__ void first_pass_body(const LeanArgs &a)
 {
     static_assert(PW == 3, "LeanNode holds three path words");
     static_assert(NCH >= 1 && NCH <= 8, "LeanExt holds bases [32, 256)");
@@ -189,6 +192,40 @@ __global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs
     uint64_t cur64 = 0, m0 = 0, m1 = 0, m2 = 0;
     uint32_t emitted = 0, sp = 0; // traversals of this AlignRead call; pending neighbours on the read's stack
     uint4 *stk = a.stk + (size_t)slot * 4;
+    // PATH: the segment's place in its path's text -- global text offset, end of the path's text, the node's index on the path, the
+    // path's node list and sparse table, its node count; pn_need: `cur` is a node start whose path record is still to be fetched
+    uint32_t t = 0, tend = 0, idx = 0, nbase = 0, tbase = 0, pnn = 0;
+    bool pn_need = false;
+    uint4 *hold = PATH ? a.hold + (size_t)slot * (3 * kPathHold) : nullptr;
+    // a traversal (alignment.go:229-236 -> processTraversal): ord 0 goes to the read's own slot; PATH keeps ord >= 1 in `hold` until the read
+    // is known to finish here (a read left to align_kernel leaves nothing in the overflow lists), the node walk appends them at once
+    auto emit = [&]() {
+        groot_trav t_;
+        t_.read_id = a.first_read_id + r; t_.graph_id = g; t_.node = node0; t_.offset = noff0;
+        t_.ord = (uint16_t)ord;
+        t_.flags = (uint8_t)((rc ? GROOT_TRAV_RC : 0u) | (level == 3u ? GROOT_TRAV_START_CLIP : level == 4u ? GROOT_TRAV_END_CLIP : 0u) | (emitted == 0u ? GROOT_TRAV_FIRST : 0u));
+        t_.reserved = 0;
+        if (ord == 0u) {
+            a.trav_first[r] = t_;
+            a.mask_first[(size_t)r * PW] = m0; a.mask_first[(size_t)r * PW + 1] = m1; a.mask_first[(size_t)r * PW + 2] = m2;
+        } else if (PATH) {
+            if (ord > kPathHold) { st = ST_DEFER; LEAN_WHY(13); return; }
+            uint4 *h = hold + 3u * (ord - 1u);
+            h[0] = make_uint4(g, node0, noff0, (uint32_t)t_.ord | ((uint32_t)t_.flags << 16));
+            h[1] = make_uint4((uint32_t)m0, (uint32_t)(m0 >> 32), (uint32_t)m1, (uint32_t)(m1 >> 32));
+            h[2] = make_uint4((uint32_t)m2, (uint32_t)(m2 >> 32), 0u, 0u);
+        } else {
+            const uint32_t shard = blockIdx.x & (kOvfShards - 1);
+            const uint32_t at = atomicAdd(&a.ovf_cnt[shard], 1u);
+            if (at < a.ovf_cap) {
+                const size_t o = (size_t)shard * a.ovf_cap + at;
+                a.ovf_trav[o] = t_;
+                a.ovf_mask[o * PW] = m0; a.ovf_mask[o * PW + 1] = m1; a.ovf_mask[o * PW + 2] = m2;
+            } else atomicOr(&a.ctr->flags, kFlagOvfOverflow);
+        }
+        ord++; emitted++;
+        alns += (uint32_t)(__popcll(m0) + __popcll(m1) + __popcll(m2));
+    };
 
     // verdict of the seed stage on the read's FIRST seed window, current orientation: bit 0 levels 1-2, bit 1 level 3, bit 2 level 4
     auto verdict = [&](uint32_t bit) -> bool { return si == 1u && (((vbits >> (rc ? 3 : 0)) >> bit) & 1u); };
@@ -242,6 +279,14 @@ __global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs
 #define LEAN_EV(i, pred) do { const unsigned long long b__ = __ballot(pred); if (b__) { lw[i]++; lw[(i) + 4] += (unsigned long long)__popcll(b__); } } while (0)
 #else
 #define LEAN_EV(i, pred) ((void)0)
+#endif
+#if defined(GROOT_WORK_COUNTERS) && GROOT_WORK_COUNTERS == 4
+    // PATH, dbg[176..180]: segments that ended with an empty path set / at the read's end / at the end of the path's text / at a flagged
+    // boundary / at a mismatch on a node's first base (the jump)
+    uint32_t stops[5] = {0, 0, 0, 0, 0};
+#define LEAN_STOP(i) (stops[i]++)
+#else
+#define LEAN_STOP(i) ((void)0)
 #endif
 #ifdef GROOT_LEAN_PROBE      // (tools: 1 = every read is left to align_kernel right after staging: what the prologue costs)
     if (GROOT_LEAN_PROBE == 1 && st <= ST_SEED) st = ST_DEFER;
@@ -307,7 +352,12 @@ __global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs
                 if (j < n) { have = true; c_node = W[W_SEED]; c_off = from + j; c_s0 = s0; c_len = slen; }
                 pos = level == 1u ? (j < n ? c_off + 1u : pos + n) : 1u;
             }
-            if (have) {
+            if (have && PATH) {
+                node0 = c_node; noff0 = c_off; cur = c_node; coff = c_off; dist = 0;
+                m0 = m1 = m2 = ~0ull;
+                pn_need = true;
+                st = ST_WALK;
+            } else if (have) {
                 node0 = c_node; noff0 = c_off; cur = c_node; cur_s0 = c_s0; coff = c_off; dist = 0;
                 cur_long = c_len > 32u;
                 cur64 = chunk(0);
@@ -315,7 +365,82 @@ __global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs
                 st = ST_WALK;
             } else if (pos >= lim) st = ST_ADV;
         }
-        if (st == ST_WALK) {
+        if (PATH && st == ST_WALK) {
+            // ---- one segment of the walk: the read against a path's text (kernels_path.hpp) ----
+            bool over = false;
+            if (pn_need) {                                         // the node's path record: its lowest path with a text, where the node sits on it
+                const uint4 *pq = a.path_node + 2u * cur;
+                const uint4 p0 = pq[0], p1 = pq[1];
+                if (p0.x == kEmpty) { st = ST_DEFER; LEAN_WHY(11); }
+                else { t = p0.x + coff; idx = p0.y; tend = p0.z; nbase = p0.w; tbase = p1.x; pnn = p1.y; pn_need = false; }
+            }
+            if (st == ST_WALK) {
+                const PathStop ps = path_segment<NCH>(a.path_text, a.path_tag, t, min(eff - dist, tend - t), [&](uint32_t d) { return chunk(dist + d); });
+                if (ps.e == 0u) { st = ST_DEFER; LEAN_WHY(12); }   // (the start base was compared before a segment starts: not met)
+                else if (ps.e != kEmpty && !ps.at_start) over = true;      // a mismatch inside a node: dfsRecursive returns false (:216-221)
+                else {
+                    // matched up to `stop`; the nodes [idx, last] of the path were spelt in full or up to the read's end
+                    const uint32_t stop = ps.e == kEmpty ? ps.n : ps.e, last = idx + ps.ns;
+                    const bool step = ps.e != kEmpty || dist + ps.n < eff;     // else the read ends here
+                    uint32_t prev = 0, nextn = kEmpty;
+                    if (step) { prev = a.path_nodes[nbase + last]; if (last + 1u < pnn) nextn = a.path_nodes[nbase + last + 1u]; }
+                    uint64_t r0, r1, r2;
+                    path_range_and<PW>(a.path_tab, tbase, pnn, idx, last, r0, r1, r2);
+                    m0 &= r0; m1 &= r1; m2 &= r2;
+                    dist += stop;
+                    // processTraversal keeps the paths present in every node of the walk: an empty set ends the branch (no record)
+                    if ((m0 | m1 | m2) == 0ull) { over = true; LEAN_STOP(0); }
+                    else if (!step) { emit(); over = true; LEAN_STOP(1); }
+                    else {
+                        // the end of node `prev`: dfsRecursive's neighbour loop (:242-252) -- at a flagged boundary, at a mismatch on the first base
+                        // of the path's next node (the one neighbour with the read's base, if any: the jump), at the end of the path's text
+                        const uint4 *q = reinterpret_cast<const uint4 *>(a.nodes + prev);
+                        const uint4 q0 = q[0], q1 = q[1];
+                        const uint32_t dk = q0.z, deg = dk & 7u;
+                        LEAN_STOP(ps.e == kEmpty ? 2 : ps.flagged ? 3 : 4);
+                        if (deg == 0u) { emit(); over = true; }    // :229-236 a sink: the overhang is reported
+                        else if (deg > 4u) { st = ST_DEFER; LEAN_WHY(8); }
+                        else {
+                            const uint32_t nextb = (uint32_t)chunk(dist) & 3u;
+                            const uint32_t ed[4] = {q1.x, q1.y, q1.z, q1.w};
+                            uint32_t hits = 0, pick = 0, alt = 0;
+                            bool wild = false;
+#pragma unroll
+                            for (int e = 0; e < 4; e++) {
+                                const uint32_t code = (dk >> (8 + 4 * e)) & 15u;
+                                if ((uint32_t)e < deg) {
+                                    wild |= code == 4u;
+                                    if (code == nextb) { if (hits == 0u) pick = ed[e]; else alt = ed[e]; hits++; }
+                                }
+                            }
+                            if (wild || hits > 2u || (hits == 2u && sp == 2u)) { st = ST_DEFER; LEAN_WHY(wild ? 7 : hits > 2u ? 8 : 9); }
+                            else if (hits == 0u) over = true;
+                            else {
+                                if (hits == 2u) {                  // the second neighbour stays pending
+                                    stk[2 * sp] = make_uint4(alt, dist, (uint32_t)m0, (uint32_t)(m0 >> 32));
+                                    stk[2 * sp + 1] = make_uint4((uint32_t)m1, (uint32_t)(m1 >> 32), (uint32_t)m2, (uint32_t)(m2 >> 32));
+                                    sp++;
+                                }
+                                if (pick == nextn) { t += stop; idx = last + 1u; }     // on along the same path's text
+                                else { cur = pick; coff = 0; pn_need = true; }
+                            }
+                        }
+                    }
+                }
+            }
+            if (over && st == ST_WALK) {
+                if (sp) {                                          // resume at the newest pending neighbour
+                    sp--;
+                    const uint4 h0 = stk[2 * sp], h1 = stk[2 * sp + 1];
+                    cur = h0.x; coff = 0; dist = h0.y; pn_need = true;
+                    m0 = (uint64_t)h0.z | ((uint64_t)h0.w << 32);
+                    m1 = (uint64_t)h1.x | ((uint64_t)h1.y << 32);
+                    m2 = (uint64_t)h1.z | ((uint64_t)h1.w << 32);
+                } else if (emitted) { done_graph = g; st = ST_SEED; }
+                else st = pos >= lim ? ST_ADV : ST_GEN;
+            }
+        }
+        if (!PATH && st == ST_WALK) {
             // ---- one node of the walk (dfsRecursive, alignment.go:196-254) ----
             // everything the step may need is asked for at once: the record; for a walk that starts inside its node the graph bases from
             // `bases2`, else the extension of a long node; for a start position at offset <= 10 its 8-mer set
@@ -364,27 +489,7 @@ __global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs
                     const bool any = (m0 | m1 | m2) != 0ull;
                     const uint32_t deg = dk & 7u;
                     if (dist == eff || deg == 0u) {               // :229-236 report the traversal
-                        if (any) {
-                            groot_trav t;
-                            t.read_id = a.first_read_id + r; t.graph_id = g; t.node = node0; t.offset = noff0;
-                            t.ord = (uint16_t)ord;
-                            t.flags = (uint8_t)((rc ? GROOT_TRAV_RC : 0u) | (level == 3u ? GROOT_TRAV_START_CLIP : level == 4u ? GROOT_TRAV_END_CLIP : 0u) | (emitted == 0u ? GROOT_TRAV_FIRST : 0u));
-                            t.reserved = 0;
-                            if (ord == 0u) {
-                                a.trav_first[r] = t;
-                                a.mask_first[(size_t)r * PW] = m0; a.mask_first[(size_t)r * PW + 1] = m1; a.mask_first[(size_t)r * PW + 2] = m2;
-                            } else {
-                                const uint32_t shard = blockIdx.x & (kOvfShards - 1);
-                                const uint32_t at = atomicAdd(&a.ovf_cnt[shard], 1u);
-                                if (at < a.ovf_cap) {
-                                    const size_t o = (size_t)shard * a.ovf_cap + at;
-                                    a.ovf_trav[o] = t;
-                                    a.ovf_mask[o * PW] = m0; a.ovf_mask[o * PW + 1] = m1; a.ovf_mask[o * PW + 2] = m2;
-                                } else atomicOr(&a.ctr->flags, kFlagOvfOverflow);
-                            }
-                            ord++; emitted++;
-                            alns += (uint32_t)(__popcll(m0) + __popcll(m1) + __popcll(m2));
-                        }
+                        if (any) emit();
                         over = true;
                     } else if (!any) over = true;                 // no path left: descendants cannot yield ids
                     else {
@@ -447,6 +552,12 @@ __global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs
         if (b && (threadIdx.x & 63) == 0) atomicAdd(&a.ctr->dbg[160 + y], (unsigned long long)__popcll(b));
     }
     { const unsigned long long b = __ballot(st == ST_DONE && !ord); if (b && (threadIdx.x & 63) == 0) atomicAdd(&a.ctr->dbg[160], (unsigned long long)__popcll(b)); }
+    for (uint32_t y = 11; y <= 13; y++) {
+        const unsigned long long b = __ballot(st == ST_DEFER && why == y);
+        if (b && (threadIdx.x & 63) == 0) atomicAdd(&a.ctr->dbg[160 + y], (unsigned long long)__popcll(b));
+    }
+    if (PATH)
+        for (int i = 0; i < 5; i++) if (stops[i]) atomicAdd(&a.ctr->dbg[176 + i], (unsigned long long)stops[i]);
 #endif
     // ---- what the read leaves behind ----
     const bool fin = st == ST_DONE;
@@ -454,6 +565,22 @@ __global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs
     unsigned long long n_alns = 0, mapped = 0, multimapped = 0;
     if (fin) {
         a.trav_cnt[r] = ord;
+        if (PATH)                                                 // the held records (ord >= 1) go to the overflow lists now
+            for (uint32_t o = 1; o < ord; o++) {
+                const uint4 h0 = hold[3 * (o - 1)], h1 = hold[3 * (o - 1) + 1], h2 = hold[3 * (o - 1) + 2];
+                groot_trav t_;
+                t_.read_id = a.first_read_id + r; t_.graph_id = h0.x; t_.node = h0.y; t_.offset = h0.z;
+                t_.ord = (uint16_t)(h0.w & 0xFFFFu); t_.flags = (uint8_t)(h0.w >> 16); t_.reserved = 0;
+                const uint32_t shard = blockIdx.x & (kOvfShards - 1);
+                const uint32_t at = atomicAdd(&a.ovf_cnt[shard], 1u);
+                if (at < a.ovf_cap) {
+                    const size_t q = (size_t)shard * a.ovf_cap + at;
+                    a.ovf_trav[q] = t_;
+                    a.ovf_mask[q * PW] = (uint64_t)h1.x | ((uint64_t)h1.y << 32);
+                    a.ovf_mask[q * PW + 1] = (uint64_t)h1.z | ((uint64_t)h1.w << 32);
+                    a.ovf_mask[q * PW + 2] = (uint64_t)h2.x | ((uint64_t)h2.y << 32);
+                } else atomicOr(&a.ctr->flags, kFlagOvfOverflow);
+            }
         mapped = 1;                                               // boss.go:195-200
         multimapped = n_graphs > 1u ? 1 : 0;
         n_alns = alns;
@@ -485,8 +612,17 @@ __global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs
         if (n_alns) atomicAdd(&a.ctr->alignments, n_alns);
         if (a.update_weights && mapped) atomicAdd(&a.ctr->mapped, mapped);
         if (a.update_weights && multimapped) atomicAdd(&a.ctr->multimapped, multimapped);
-        if (mapped) atomicAdd(&a.ctr->lean_reads, (unsigned int)mapped);
+        if (mapped) atomicAdd(PATH ? &a.ctr->path_reads : &a.ctr->lean_reads, (unsigned int)mapped);
     }
+#undef LEAN_WHY
+#undef LEAN_EV
+#undef LEAN_STOP
 }
+
+template <int PW, int NCH>
+__global__ __launch_bounds__(kBlock, kLeanWaves) void align_lean_kernel(LeanArgs a) { first_pass_body<PW, NCH, false>(a); }
+// the default first pass: walks compared against path text (kernels_path.hpp)
+template <int PW, int NCH>
+__global__ __launch_bounds__(kBlock, kPathWaves) void align_path_kernel(LeanArgs a) { first_pass_body<PW, NCH, true>(a); }
 
 } // namespace groot

@@ -289,6 +289,12 @@ class Aligner:
         self._check(lib().groot_hip_stage_ms(self._h, C.byref(m)))
         return {n: float(getattr(m, n)) for n, _ in StageMs._fields_}
 
+    def path_pass_stats(self):
+        """the waited batch's first pass against path text: {"ran": bool, "reads": reads it finished, "ms": its time (profiling on, else 0)}"""
+        ran, reads, ms = C.c_uint32(), C.c_uint64(), C.c_float()
+        self._check(lib().groot_hip_path_pass_stats(self._h, C.byref(ran), C.byref(reads), C.byref(ms)))
+        return {"ran": bool(ran.value), "reads": int(reads.value), "ms": float(ms.value)}
+
     # ---- weights ------------------------------------------------------------------------------
     def attempts_shape(self):
         nq, nw = C.c_uint32(), C.c_uint32()

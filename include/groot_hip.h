@@ -250,6 +250,10 @@ int groot_hip_read_seeds(groot_ctx *ctx, groot_seed *out, uint64_t cap, uint64_t
 int groot_hip_read_sketches(groot_ctx *ctx, uint64_t *out /* [cap_reads*sketch_size] */, uint64_t cap_reads,
                             uint64_t *n_reads);
 int groot_hip_stage_ms(groot_ctx *ctx, groot_stage_ms *out);
+/* the waited batch's first pass against path text (align_path_kernel, the default first pass of the align stage): ran = 1 when it ran,
+ * reads = the reads it finished (the rest of the walked reads went to align_kernel), ms = its time with the stream compaction behind
+ * it (profiling on, else 0).  groot_counts.lean_reads stays 0 on this path. */
+int groot_hip_path_pass_stats(groot_ctx *ctx, uint32_t *ran, uint64_t *reads, float *ms);
 
 /* ---- IncrementSubPath call counts ---------------------------------------------------------------------------------
  * Accumulated over every batch since open/reset in a table [rows][n_windows] of uint32, one row per kmerCount
