@@ -7,22 +7,26 @@ import os
 import numpy as np
 import pytest
 
+import oracle_check
 from conftest import DATA, digest
 from groot_amd import device, host, synth
 from oracle import oracle_py as O
 
 pytestmark = pytest.mark.gpu
 
-@pytest.fixture(autouse=True, params=["align_kernel", "lean_first"])
+@pytest.fixture(autouse=True, params=["path_first", "align_kernel", "lean_first"])
 def align_stage(request, monkeypatch):
-    """every test of this module twice: the align stage as shipped (align_kernel alone), and with its first pass in front (GROOT_LEAN=1,
-    kernels_lean.hpp) -- the results must not depend on it"""
+    """every test of this module three times: the align stage as shipped (its first pass against path text in front of align_kernel,
+    kernels_path.hpp), align_kernel alone (GROOT_NO_PATH_PASS=1) and the node-by-node first pass in front (GROOT_LEAN=1, kernels_lean.hpp)
+    -- the results must not depend on it"""
+    for v in ("GROOT_NO_PATH_PASS", "GROOT_LEAN"):
+        monkeypatch.delenv(v, raising=False)
     if request.param == "lean_first":
         if request.node.name.startswith("test_kernel_path_at_benchmark_size") or "background" in request.node.name:
             pytest.skip("compares the two itself / not about the align stage")
         monkeypatch.setenv("GROOT_LEAN", "1")
-    else:
-        monkeypatch.delenv("GROOT_LEAN", raising=False)
+    elif request.param == "align_kernel":
+        monkeypatch.setenv("GROOT_NO_PATH_PASS", "1")
     return request.param
 
 
@@ -52,29 +56,21 @@ def run_both(index, seq, off, threshold=0.99, no_align=False, first=0, **kw):
                         max_batch_reads=max(1024, len(off) - 1), **kw)
     al.submit(seq, off, first_read_id=first)
     counts = al.wait()
+    # the shipped stage: a batch of reads of up to 256 bases that has reads to walk goes through the first pass against path text (an index
+    # of up to 192 paths per graph, alignment on)
+    if os.environ.get("GROOT_NO_PATH_PASS") is None and os.environ.get("GROOT_LEAN") is None and not no_align \
+            and index.view.path_words <= 3 and len(off) > 1 and int(np.max(np.diff(off))) <= 256 and counts["walked_reads"]:
+        assert al.path_pass_stats()["ran"], (counts["walked_reads"], al.path_pass_stats())
     run = O.Run(index, threshold, no_align)
     run.batch(seq, off, first_read_id=first)
     return al, counts, run
 
 
 def assert_same(al, counts, run, index):
-    oc = run.counts()
-    for k in ("received", "mapped", "multimapped", "alignments", "seeds", "revcomp_panics"):
-        assert counts[k] == oc[k], (k, counts[k], oc[k])
     if KEEP_SKETCHES:
         assert np.array_equal(al.sketches(), run.sketches())
         assert counts["full_sketch_reads"] == counts["received"]
-    assert np.array_equal(al.seeds(), run.seeds().astype(device.SEED_DTYPE))
-    got, exp = al.alns(), run.alns()
-    assert len(got) == len(exp)
-    for f in exp.dtype.names:
-        assert np.array_equal(got[f], exp[f]), f
-    att, oatt = al.attempts(), run.attempts()
-    assert np.array_equal(att[: oatt.shape[0]], oatt) and not att[oatt.shape[0]:].any()
-    kf, kt = device.weights(index, att)
-    okf, okt = run.weights(order=1)
-    assert np.array_equal(kf, okf) and np.array_equal(kt, okt)
-    return got
+    return oracle_check.assert_same(counts, oracle_check.device_results(al, index), run)
 
 
 def pack(reads):
