@@ -7,7 +7,8 @@
 //        graphDir, the reference's log lines in --log (default groot.log)
 //
 // Extra flags: --gpu <id> (device) or --gpus <N> (reads shard over N GPUs), --batch <reads> (reads per device batch),
-// --maxReadLen, --bam <file> (Info.Sketch.BAMout), --bamLevel, --stats <json>; index: --writeGob.
+// --maxReadLen, --bam <file> (Info.Sketch.BAMout), --bamLevel, --stats <json>, --report <file> [--covCutoff --lowCov --noBam]
+// (the `report` of the run from coverage counted on the GPU, with or without a BAM); index: --writeGob.
 // The align hot path runs only on the GPU: no device -> error, never a CPU fallback.
 #include <algorithm>
 #include <atomic>
@@ -64,9 +65,9 @@ void logf(const char *fmt, ...)
 }
 
 struct Args {
-    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file;
+    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out;
     double cov_cutoff = 0.97;
-    bool low_cov = false;
+    bool low_cov = false, no_bam = false;
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
     bool gpu_given = false, write_gob = false;
@@ -101,7 +102,9 @@ void usage()
             "  groot-hip align -i <indexDir> -f <fastq>[,<fastq>...] [-t 0.99] [-c 1.0] [-g <graphDir>] [--noAlign] [-p N] [--log F]\n"
             "                  [--gpu 0 | --gpus N] [--batch 1048576] [--maxReadLen 512] [--bam out.bam] [--bamLevel -2..9] [--stats f.json]\n"
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
-            "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated)\n"
+            "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--noBam]]\n"
+            "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
+            "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all)\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--log F]      (BAM from stdin unless --bamFile)\n",
             groot_host_version());
 }
@@ -134,7 +137,9 @@ Args parse(int argc, char **argv)
         else if (f == "--maxSketchSpan") a.max_span = (uint32_t)atoi(v().c_str());
         else if (f == "-f" || f == "--fastq") { for (auto &x : split(v(), ',')) a.fastq.push_back(x); }
         else if (f == "-t" || f == "--contThresh") a.threshold = atof(v().c_str());
-        else if (a.cmd == "report" && (f == "-c" || f == "--covCutoff")) a.cov_cutoff = atof(v().c_str());
+        else if ((a.cmd == "report" && (f == "-c" || f == "--covCutoff")) || (a.cmd == "align" && f == "--covCutoff")) a.cov_cutoff = atof(v().c_str());
+        else if (a.cmd == "align" && f == "--report") a.report_out = v();
+        else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
         else if (f == "--bamFile") a.bam_file = v();
         else if (f == "--lowCov") a.low_cov = true;
         else if (f == "-c" || f == "--minKmerCov") a.min_kmer_cov = atof(v().c_str());
@@ -330,6 +335,11 @@ int run_align(const Args &a)   // cmd/align.go:54-163
 {
     if (a.index_dir.empty()) { puts("please specify a directory with the index files (--indexDir)"); return 1; }
     if (a.fasta) { fprintf(stderr, "--fasta is an experimental reference feature that is not supported\n"); return 1; }
+    const bool want_report = !a.report_out.empty();
+    if (want_report && a.no_align) { fprintf(stderr, "--report needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
+    if (want_report && a.cov_cutoff > 1.0) { fprintf(stderr, "supplied coverage cutoff exceeds 1.0 (100%%): %g\n", a.cov_cutoff); return 1; }   // cmd/report.go:95-97
+    if (a.no_bam && !want_report) { fprintf(stderr, "--noBam without --report would leave no output of the alignments\n"); return 1; }
+    if (a.no_bam && !a.bam_out.empty()) { fprintf(stderr, "--noBam and --bam contradict each other\n"); return 1; }
     start_logging(a);
     auto t0 = std::chrono::steady_clock::now();
     logf("i am groot (version %s)", groot_host_version());
@@ -469,7 +479,22 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         prm.max_batch_bases = (uint64_t)a.batch * std::min<uint32_t>(max_read_len, 512);
         prm.pipeline_depth = depth;
         prm.memo_budget_mb = memo_budget;
+        prm.results_on_device = a.no_bam ? 1 : 0;   // (no BAM: the records stay in HBM, nothing crosses PCIe but the counters)
         return prm;
+    };
+    // --report: every ctx counts records and pileups on the device (groot_hip_coverage_*); what a ctx has counted is added here before
+    // it closes (grow_ctx) and at the end of the stream
+    uint64_t cov_slots = 0;
+    for (uint32_t p = 0; p < v.n_paths; p++) cov_slots += v.path_len[p];
+    std::vector<uint64_t> cov_records(want_report ? v.n_paths : 0), cov_depth(want_report ? cov_slots : 0);
+    std::mutex cov_mu;
+    auto cov_harvest = [&](groot_ctx *ctx) -> int {
+        std::vector<uint64_t> r(v.n_paths), d(cov_slots);
+        if (int rc = groot_hip_coverage_export(ctx, r.data(), d.data())) return rc;
+        std::lock_guard<std::mutex> lk(cov_mu);
+        for (size_t i = 0; i < r.size(); i++) cov_records[i] += r[i];
+        for (size_t i = 0; i < d.size(); i++) cov_depth[i] += d[i];
+        return 0;
     };
     for (int d : devices) {
         std::unique_ptr<Gpu> g(new Gpu());
@@ -486,6 +511,8 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             });
         for (auto &t : th) t.join();
         for (auto &e : errs) if (!e.empty()) die("%s", e.c_str());
+        if (want_report)
+            for (auto &g : gpus) if (groot_hip_coverage_enable(g->ctx, 1)) die("%s", groot_hip_last_error(g->ctx));
     }
     logf("\tcontainment threshold: %.2f", a.threshold);
     if (a.no_align) logf("\tprevent exact alignments and using approximated mapping only");
@@ -497,7 +524,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     const double load_s = seconds_since(t0);
 
     groot_bam *bam = nullptr;
-    if (!a.no_align && groot_bam_open(a.bam_out.empty() ? nullptr : a.bam_out.c_str(), &v, nullptr, &bam)) die("%s", groot_host_last_error());
+    if (!a.no_align && !a.no_bam && groot_bam_open(a.bam_out.empty() ? nullptr : a.bam_out.c_str(), &v, nullptr, &bam)) die("%s", groot_host_last_error());
     if (bam) { groot_bam_set_threads(bam, cores); if (groot_bam_set_level(bam, a.bam_level)) die("%s", groot_host_last_error()); }
 
     logf("now streaming reads...");
@@ -541,6 +568,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                 if (groot_hip_attempts_export(g.ctx, nullptr, nullptr, 0, &n_rows, &nw)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 std::vector<uint32_t> qv(n_rows), cnt((size_t)n_rows * nw);
                 if (n_rows && groot_hip_attempts_export(g.ctx, qv.data(), cnt.data(), n_rows, &n_rows, &nw)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+                if (want_report && cov_harvest(g.ctx)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 groot_hip_close(g.ctx);
                 g.ctx = nullptr;
                 g.max_read_len = std::min<uint32_t>(65535, need + need / 2);
@@ -548,6 +576,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                 logf("\tread of %u bases: reopening the GPU context for reads up to %u bases", need, g.max_read_len);
                 if (groot_hip_open_flags(&g.ctx, g.device, &v, &prm, GROOT_OPEN_BACKGROUND)) { fail_with(groot_hip_last_error(nullptr)); return false; }
                 if (n_rows && groot_hip_attempts_import(g.ctx, qv.data(), cnt.data(), n_rows)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+                if (want_report && groot_hip_coverage_enable(g.ctx, 1)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 return true;
             };
             while (!failed) {
@@ -643,6 +672,17 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     logf("\tnumber of reads sketched: %llu", (unsigned long long)received);                      // sketch.go:321
     const uint64_t bam_bytes = bam ? groot_bam_bytes_written(bam) : 0;
     if (bam && groot_bam_close(bam)) die("%s", groot_host_last_error());
+    if (want_report) {
+        // every batch has been collected: what each ctx counted is final (it is switched off, so a ctx reopened below starts without it)
+        for (auto &g : gpus) {
+            if (cov_harvest(g->ctx) || groot_hip_coverage_enable(g->ctx, 0)) die("%s", groot_hip_last_error(g->ctx));
+        }
+        uint64_t n_rep = 0;
+        if (groot_host_report_coverage(&v, cov_records.data(), cov_depth.data(), a.cov_cutoff, a.low_cov ? 1 : 0, a.report_out.c_str(), &n_rep))
+            die("%s", groot_host_last_error());
+        logf("\treport: %llu ARG(s) written to %s (coverage cutoff %.2f%s)", (unsigned long long)n_rep, a.report_out.c_str(), a.low_cov ? 0.97 : a.cov_cutoff,
+             a.low_cov ? ", --lowCov" : "");
+    }
     const double stream_s = seconds_since(t_stream);
     auto t_post = std::chrono::steady_clock::now();
 

@@ -22,6 +22,7 @@
 
 #include "../common/cpus.hpp"
 #include "../common/view_check.hpp"
+#include "kernels_cov.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_path.hpp"
 #include "launch.hpp"
@@ -287,6 +288,16 @@ struct groot_ctx {
     uint32_t *attempts_ptr = nullptr;      // own buffer or the caller's (groot_hip_attempts_layout)
     uint32_t att_cap = 0;                  // rows the table can hold
     bool att_external = false;
+    // report coverage (groot_hip_coverage_*, kernels_cov.hpp): off until enabled, then cov_count_kernel runs behind every batch's
+    // order stage.  The host keeps the position tables from open (a few MB); the device holds them and the counters only while on.
+    bool cov_on = false;
+    std::vector<uint32_t> h_cov_np_off, h_cov_gpo, h_cov_len;
+    std::vector<uint2> h_cov_np;
+    std::vector<uint64_t> h_cov_base;      // first slot of every path, + the total
+    DevBuf<uint32_t> cov_np_off, cov_gpo, cov_len;
+    DevBuf<uint2> cov_np;
+    DevBuf<uint64_t> cov_base;
+    DevBuf<unsigned long long> cov_starts, cov_ends;
 };
 
 // A ctx drives four HIP streams at once -- seed stage, align + order stage, copy-in, copy-out -- beside whatever the host process
@@ -982,6 +993,15 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
     if (int rc = launch_order_stage(c, s, update_weights)) return rc;
     if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[5], c->astream));
     HIP_TRY(c, hipEventRecord(w->ev_free, c->astream));
+    if (c->cov_on) {   // (reads the slot's records and read offsets only: the next batch's seed stage need not wait for it)
+        CovArgs ca{};
+        ca.trav = s->d_trav.p; ca.mask = s->d_mask.p; ca.seq_off = s->off(); ca.ctr = s->d_ctr.p;
+        ca.node_np_off = c->cov_np_off.p; ca.np = c->cov_np.p; ca.graph_path_off = c->cov_gpo.p; ca.path_len = c->cov_len.p; ca.slot_base = c->cov_base.p;
+        ca.starts = c->cov_starts.p; ca.ends = c->cov_ends.p;
+        ca.cap = s->trav_cap; ca.pw = c->pw_view; ca.first_read_id = s->first_read_id;
+        hipLaunchKernelGGL(cov_count_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->astream, ca);
+        HIP_TRY(c, hipGetLastError());
+    }
     w->used = true;
     w->owner = s;
     w->ticket = s->ticket;
@@ -2402,6 +2422,14 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
     c->h_node_graph.resize(v->n_nodes);
     for (uint32_t g = 0; g < v->n_graphs; g++)
         for (uint32_t nd = v->graph_node_off[g]; nd < v->graph_node_off[g + 1]; nd++) c->h_node_graph[nd] = g;
+    // (a view without graphs -- the sketch engine of `index --gpu` -- may carry no offset arrays at all)
+    if (v->node_np_off) c->h_cov_np_off.assign(v->node_np_off, v->node_np_off + v->n_nodes + 1); else c->h_cov_np_off.assign(v->n_nodes + 1, 0);
+    if (v->graph_path_off) c->h_cov_gpo.assign(v->graph_path_off, v->graph_path_off + v->n_graphs + 1); else c->h_cov_gpo.assign(v->n_graphs + 1, 0);
+    c->h_cov_len.assign(v->path_len, v->path_len + v->n_paths);
+    c->h_cov_np.resize(v->n_np);
+    for (uint64_t j = 0; j < v->n_np; j++) c->h_cov_np[j] = make_uint2(v->np_path[j], v->np_pos[j]);
+    c->h_cov_base.assign(v->n_paths + 1, 0);
+    for (uint32_t p = 0; p < v->n_paths; p++) c->h_cov_base[p + 1] = c->h_cov_base[p] + v->path_len[p] + 1;
     c->packed_travs = !c->prm.results_on_device && c->prm.max_batch_reads <= (1u << 24);
     {   // windows are numbered graph by graph (canonical seed order): the last window of every graph
         std::vector<uint32_t> end(v->n_graphs, 0);
@@ -3292,6 +3320,69 @@ int groot_hip_attempts_reset(groot_ctx *c)
     if (!c) return GROOT_E_INVALID;
     if (int rc = drain(c)) return rc;
     if (c->att_cap) HIP_TRY(c, hipMemset(c->attempts_ptr, 0, (size_t)c->att_cap * c->n_windows * sizeof(uint32_t)));
+    return GROOT_OK;
+}
+
+// ---- report coverage (kernels_cov.hpp) ------------------------------------------------------------------------------
+int groot_hip_coverage_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "coverage can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!on) {
+        for (auto *b : {&c->cov_np_off, &c->cov_gpo, &c->cov_len}) b->release();
+        c->cov_np.release(); c->cov_base.release(); c->cov_starts.release(); c->cov_ends.release();
+        c->cov_on = false;
+        return GROOT_OK;
+    }
+    if (c->cov_on) return GROOT_OK;
+    const uint64_t slots = c->h_cov_base.back();
+    HIP_TRY(c, upload(c->cov_np_off, c->h_cov_np_off.data(), c->h_cov_np_off.size()));
+    HIP_TRY(c, upload(c->cov_gpo, c->h_cov_gpo.data(), c->h_cov_gpo.size()));
+    HIP_TRY(c, upload(c->cov_len, c->h_cov_len.data(), c->h_cov_len.size()));
+    HIP_TRY(c, upload(c->cov_np, c->h_cov_np.data(), c->h_cov_np.size()));
+    HIP_TRY(c, upload(c->cov_base, c->h_cov_base.data(), c->h_cov_base.size()));
+    HIP_TRY(c, c->cov_starts.alloc(slots));
+    HIP_TRY(c, c->cov_ends.alloc(slots));
+    HIP_TRY(c, hipMemset(c->cov_starts.p, 0, std::max<uint64_t>(slots, 1) * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->cov_ends.p, 0, std::max<uint64_t>(slots, 1) * sizeof(unsigned long long)));
+    c->cov_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_coverage_export(groot_ctx *c, uint64_t *records, uint64_t *depth)
+{
+    if (!c || (!c->h_cov_len.empty() && (!records || !depth))) return GROOT_E_INVALID;
+    if (!c->cov_on) return fail(c, GROOT_E_STATE, "coverage is not enabled (groot_hip_coverage_enable)");
+    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo, if they need one)
+    const uint64_t slots = c->h_cov_base.back();
+    std::vector<uint64_t> st(slots), en(slots);
+    if (slots) {
+        HIP_TRY(c, hipMemcpy(st.data(), c->cov_starts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(en.data(), c->cov_ends.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    uint64_t at = 0;
+    for (size_t p = 0; p < c->h_cov_len.size(); p++) {
+        const uint64_t b = c->h_cov_base[p], len = c->h_cov_len[p];
+        uint64_t n = 0, d = 0;
+        for (uint64_t i = 0; i < len; i++) {
+            n += st[b + i];
+            d += st[b + i] - en[b + i];
+            depth[at++] = d;
+        }
+        records[p] = n + st[b + len];
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_coverage_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->cov_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    const uint64_t slots = std::max<uint64_t>(c->h_cov_base.back(), 1);
+    HIP_TRY(c, hipMemset(c->cov_starts.p, 0, slots * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->cov_ends.p, 0, slots * sizeof(unsigned long long)));
     return GROOT_OK;
 }
 

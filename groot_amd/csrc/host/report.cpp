@@ -124,12 +124,50 @@ std::string cigar_clean(const std::vector<uint8_t> &covered, bool &internal_d)
     return cigar;
 }
 
+// cmd/report.go:95-97 and :119-122
+int check_cutoff(double &cov_cutoff, int low_cov)
+{
+    if (cov_cutoff > 1.0) return set_error(GROOT_E_INVALID, "supplied coverage cutoff exceeds 1.0 (100%%): %g", cov_cutoff);
+    if (low_cov) cov_cutoff = 0.97;
+    return GROOT_OK;
+}
+
+// reporting.go:128-160: the lines of the report from per-reference record counts and pileups, in reference order.  covered(r, i) =
+// base i of reference r has a non-zero pileup; has_pileup(r) = reference r got a pileup (of its length).  name_len NULL = C strings.
+template <class Covered, class HasPileup>
+int write_report(uint32_t n_ref, const char *const *names, const uint32_t *name_len, const uint32_t *lens, const uint64_t *count,
+                 Covered covered_at, HasPileup has_pileup, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported)
+{
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
+    uint64_t reported = 0;
+    std::vector<uint8_t> cov;
+    for (uint32_t r = 0; r < n_ref; r++) {
+        if (!count[r] || !has_pileup(r)) continue;
+        const size_t len = lens[r];
+        size_t covered = 0;
+        cov.resize(len);
+        for (size_t i = 0; i < len; i++) { cov[i] = covered_at(r, i) ? 1 : 0; covered += cov[i]; }
+        if ((double)covered / (double)len < cov_cutoff) continue;         // reporting.go:130-131
+        bool internal_d = false;
+        const std::string cigar = cigar_clean(cov, internal_d);
+        if (internal_d && low_cov) continue;                               // reporting.go:151-153
+        const char *name = names[r];
+        size_t nl = name_len ? name_len[r] : strlen(name);
+        if (nl && name[0] == '*') { name++; nl--; }                         // cluster representative marker (:135-137)
+        fprintf(out, "%.*s\t%llu\t%u\t%s\n", (int)nl, name, (unsigned long long)count[r], lens[r], cigar.c_str());
+        reported++;
+    }
+    if (out_path) fclose(out); else fflush(out);
+    if (n_reported) *n_reported = reported;
+    return GROOT_OK;
+}
+
 } // namespace
 
 extern "C" int groot_host_report(const char *bam_path, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported)
 {
-    if (cov_cutoff > 1.0) return set_error(GROOT_E_INVALID, "supplied coverage cutoff exceeds 1.0 (100%%): %g", cov_cutoff);   // cmd/report.go:95-97
-    if (low_cov) cov_cutoff = 0.97;                                                                                            // cmd/report.go:119-122
+    if (int rc = check_cutoff(cov_cutoff, low_cov)) return rc;
     BgzfIn in;
     if (!in.open(bam_path)) return set_error(GROOT_E_IO, "could not open BAM file %s", bam_path);
     uint8_t b4[4];
@@ -183,25 +221,29 @@ extern "C" int groot_host_report(const char *bam_path, double cov_cutoff, int lo
         if (end > pl.size() - 1) end = pl.size() - 1;
         for (uint64_t i = (uint64_t)pos; i <= end; i++) pl[i]++;
     }
-    FILE *out = out_path ? fopen(out_path, "w") : stdout;
-    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
-    uint64_t reported = 0;
-    for (uint32_t r = 0; r < n_ref; r++) {
-        if (!count[r] || pileup[r].empty()) continue;
-        const auto &pl = pileup[r];
-        size_t covered = 0;
-        std::vector<uint8_t> cov(pl.size());
-        for (size_t i = 0; i < pl.size(); i++) { cov[i] = pl[i] != 0; covered += cov[i]; }
-        if ((double)covered / (double)pl.size() < cov_cutoff) continue;     // reporting.go:130-131
-        bool internal_d = false;
-        const std::string cigar = cigar_clean(cov, internal_d);
-        if (internal_d && low_cov) continue;                                 // reporting.go:151-153
-        const char *name = names[r].c_str();
-        if (name[0] == '*') name++;                                         // cluster representative marker (:135-137)
-        fprintf(out, "%s\t%llu\t%u\t%s\n", name, (unsigned long long)count[r], lens[r], cigar.c_str());
-        reported++;
+    std::vector<const char *> name_ptr(n_ref);
+    for (uint32_t r = 0; r < n_ref; r++) name_ptr[r] = names[r].c_str();
+    return write_report(n_ref, name_ptr.data(), nullptr, lens.data(), count.data(),
+                        [&](uint32_t r, size_t i) { return pileup[r][i] != 0; }, [&](uint32_t r) { return !pileup[r].empty(); },
+                        cov_cutoff, low_cov, out_path, n_reported);
+}
+
+extern "C" int groot_host_report_coverage(const groot_index_view *ix, const uint64_t *records, const uint64_t *depth, double cov_cutoff,
+                                          int low_cov, const char *out_path, uint64_t *n_reported)
+{
+    if (!ix || (ix->n_paths && (!records || !depth))) return set_error(GROOT_E_INVALID, "null argument");
+    if (int rc = check_cutoff(cov_cutoff, low_cov)) return rc;
+    const uint32_t n = ix->n_paths;
+    std::vector<uint64_t> base(n + 1, 0);
+    for (uint32_t p = 0; p < n; p++) base[p + 1] = base[p] + ix->path_len[p];
+    std::vector<const char *> name_ptr(n);
+    std::vector<uint32_t> name_len(n);
+    for (uint32_t p = 0; p < n; p++) {
+        name_ptr[p] = ix->path_names + ix->path_name_off[p];
+        name_len[p] = ix->path_name_off[p + 1] - ix->path_name_off[p];
     }
-    if (out_path) fclose(out); else fflush(out);
-    if (n_reported) *n_reported = reported;
-    return GROOT_OK;
+    // a reference with records has a pileup of its length (reporting.go:100-103); one of length 0 is not reported
+    return write_report(n, name_ptr.data(), name_len.data(), ix->path_len, records,
+                        [&](uint32_t p, size_t i) { return depth[base[p] + i] != 0; }, [&](uint32_t p) { return ix->path_len[p] != 0; },
+                        cov_cutoff, low_cov, out_path, n_reported);
 }

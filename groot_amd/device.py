@@ -338,6 +338,23 @@ class Aligner:
     def attempts_reset(self):
         self._check(lib().groot_hip_attempts_reset(self._h))
 
+    # ---- report coverage (groot_hip_coverage_*) ------------------------------------------------
+    def coverage_enable(self, on=True):
+        """count records and pileups of every batch from now on (only while nothing is in flight)"""
+        self._check(lib().groot_hip_coverage_enable(self._h, C.c_int(1 if on else 0)))
+
+    def coverage(self):
+        """(records[n_paths], depth[sum of path_len]) as uint64 over every batch since enable / reset: the inputs of
+        host.report_coverage.  Waits for everything in flight."""
+        v = self.index.view
+        records = np.zeros(v.n_paths, dtype=np.uint64)
+        depth = np.zeros(int(self.index.arrays["path_len"].astype(np.uint64).sum()), dtype=np.uint64)
+        self._check(lib().groot_hip_coverage_export(self._h, _ffi.as_ptr(records, C.c_uint64), _ffi.as_ptr(depth, C.c_uint64)))
+        return records, depth
+
+    def coverage_reset(self):
+        self._check(lib().groot_hip_coverage_reset(self._h))
+
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):
         seq = np.ascontiguousarray(seq_concat, dtype=np.uint8)

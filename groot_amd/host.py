@@ -370,6 +370,33 @@ def report(bam_path, cov_cutoff=0.97, low_cov=False, out_path=None):
     return [(r[0], int(r[1]), int(r[2]), r[3]) for r in rows]
 
 
+def report_coverage(index, records, depth, cov_cutoff=0.97, low_cov=False, out_path=None):
+    """the report of `report` from counts instead of a BAM (groot_host_report_coverage): records[n_paths] and depth[sum of
+    path_len] as uint64, e.g. device.Aligner.coverage(); same rows as `report` on the BAM whose records they count"""
+    import tempfile
+
+    v = index.view
+    records = np.ascontiguousarray(records, dtype=np.uint64)
+    depth = np.ascontiguousarray(depth, dtype=np.uint64)
+    if records.shape != (v.n_paths,) or depth.shape != (int(index.arrays["path_len"].astype(np.uint64).sum()),):
+        raise ValueError("records / depth do not match the index")
+    tmp = None
+    if out_path is None:
+        fd, tmp = tempfile.mkstemp(suffix=".report")
+        os.close(fd)
+    n = C.c_uint64(0)
+    try:
+        _check(lib().groot_host_report_coverage(C.byref(v), _ffi.as_ptr(records, C.c_uint64), _ffi.as_ptr(depth, C.c_uint64),
+                                                C.c_double(cov_cutoff), C.c_int(1 if low_cov else 0), (out_path or tmp).encode(),
+                                                C.byref(n)))
+        rows = [ln.rstrip("\n").split("\t") for ln in open(out_path or tmp)]
+    finally:
+        if tmp:
+            os.unlink(tmp)
+    assert len(rows) == n.value
+    return [(r[0], int(r[1]), int(r[2]), r[3]) for r in rows]
+
+
 def save_gfa(index, graph, kmer_freq, path_kept, node_removed, total_kmers, file_name, timestamp=None):
     """GrootGraph.SaveGraphAsGFA (src/graph/graphio.go:19-112); returns True if a file was written"""
     kf = np.ascontiguousarray(kmer_freq, dtype=np.float64)

@@ -282,6 +282,23 @@ int groot_hip_attempts_allreduce(groot_ctx *const *ctxs, int n_ctx);
 int groot_hip_attempts_shape(groot_ctx *ctx, uint32_t *n_q, uint32_t *n_windows);
 int groot_hip_attempts_read(groot_ctx *ctx, uint32_t *out, uint64_t n_elems);
 
+/* ---- report coverage ------------------------------------------------------------------------------------------------
+ * What `groot report` reads back from the BAM of `groot align` (src/reporting/reporting.go:100-127), accumulated on the device
+ * batch by batch behind the order stage, so that `align | report` needs no BAM.  Per global path p (BAM header order):
+ * records[p] = the records AlignRead emits on p (alignment.go:113-156: one per path of a traversal's path set, secondary ones
+ * included) and the pileup depth[i] = the records covering base i, a record at Pos with the M op of M = read length - clips
+ * covering [Pos, min(Pos + M, path_len - 1)] -- both ends included, reporting.go:104-127.  groot_host_report_coverage turns
+ * them into the report.  Off by default: then nothing is launched and no device memory is taken.
+ * A batch is counted once: a pass the ctx redoes at collect (groot_hip_redo_status) counts in its redo only, and a batch that
+ * fails with GROOT_E_NOSPACE (a read longer than max_read_len, more than 65535 traversals for one read) is not counted. */
+/* Switch on (zeroed counters; 16 bytes per path base of HBM) or off (freed).  Only while nothing is in flight. */
+int groot_hip_coverage_enable(groot_ctx *ctx, int on);
+/* records[n_paths], depth[sum of path_len] with path p at sum_{q<p} path_len[q].  Waits for everything in flight (redoing what
+ * needs a redo); counts every batch submitted so far.  GROOT_E_STATE when coverage is off. */
+int groot_hip_coverage_export(groot_ctx *ctx, uint64_t *records, uint64_t *depth);
+/* Zeroes the counters (after waiting for everything in flight).  No-op when coverage is off. */
+int groot_hip_coverage_reset(groot_ctx *ctx);
+
 /* Fine-grained mirror of Sequence.RunMinHash(k, s, false, nil) (seqio.go:40-68) for a batch of
  * sequences in host memory: out[i*s .. (i+1)*s) = KHF sketch of sequence i.  Only while nothing is in flight. */
 int groot_hip_sketch(groot_ctx *ctx, const uint8_t *seq_concat, const uint64_t *seq_off, uint32_t n, uint64_t *out);

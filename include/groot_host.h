@@ -259,6 +259,12 @@ int groot_host_pack_reads(const uint8_t *seq_concat, uint64_t n_bases, uint8_t *
  * covered fraction is >= cov_cutoff, written to out_path (NULL = stdout) in BAM header order; low_cov != 0 uses the
  * cutoff 0.97 and drops references with internal uncovered stretches (cmd/report.go:119-122, reporting.go:151-153). */
 int groot_host_report(const char *bam_path, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported);
+/* The same report from counts instead of a BAM: records[p] = records on global path p, depth = the pileup of every path, path p
+ * at sum_{q<p} path_len[q] (path_len[p] entries), as groot_hip_coverage_export hands them out.  A record of path p at Pos with
+ * an M op of length M adds 1 to depth[Pos .. min(Pos + M, path_len[p] - 1)], both ends included (reporting.go:104-127).
+ * Byte for byte the output groot_host_report writes for the BAM whose records give these counts. */
+int groot_host_report_coverage(const groot_index_view *idx, const uint64_t *records, const uint64_t *depth, double cov_cutoff,
+                               int low_cov, const char *out_path, uint64_t *n_reported);
 
 #ifdef __cplusplus
 }
