@@ -8,7 +8,10 @@
 //
 // Extra flags: --gpu <id> (device) or --gpus <N> (reads shard over N GPUs), --batch <reads> (reads per device batch),
 // --maxReadLen, --bam <file> (Info.Sketch.BAMout), --bamLevel, --stats <json>, --report <file> [--covCutoff --lowCov --noBam]
-// (the `report` of the run from coverage counted on the GPU, with or without a BAM); index: --writeGob.
+// (the `report` of the run from coverage counted on the GPU, with or without a BAM) [--sharedReads <file>] (for every pair of
+// reported ARGs, the reads with records on both, counted on the GPU; needs --report); index: --writeGob.
+// report: --sharedReads <file> writes the same pairs from the BAM, a read being one QNAME (the device counts input reads: the two
+// agree whenever read names are unique).
 // The align hot path runs only on the GPU: no device -> error, never a CPU fallback.
 #include <algorithm>
 #include <atomic>
@@ -65,7 +68,7 @@ void logf(const char *fmt, ...)
 }
 
 struct Args {
-    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out;
+    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out;
     double cov_cutoff = 0.97;
     bool low_cov = false, no_bam = false;
     std::vector<std::string> fastq;
@@ -102,10 +105,11 @@ void usage()
             "  groot-hip align -i <indexDir> -f <fastq>[,<fastq>...] [-t 0.99] [-c 1.0] [-g <graphDir>] [--noAlign] [-p N] [--log F]\n"
             "                  [--gpu 0 | --gpus N] [--batch 1048576] [--maxReadLen 512] [--bam out.bam] [--bamLevel -2..9] [--stats f.json]\n"
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
-            "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--noBam]]\n"
+            "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--noBam] [--sharedReads s.tsv]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
-            "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all)\n"
-            "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--log F]      (BAM from stdin unless --bamFile)\n",
+            "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all;\n"
+            "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common)\n"
+            "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--log F]   (BAM from stdin unless --bamFile)\n",
             groot_host_version());
 }
 
@@ -139,6 +143,7 @@ Args parse(int argc, char **argv)
         else if (f == "-t" || f == "--contThresh") a.threshold = atof(v().c_str());
         else if ((a.cmd == "report" && (f == "-c" || f == "--covCutoff")) || (a.cmd == "align" && f == "--covCutoff")) a.cov_cutoff = atof(v().c_str());
         else if (a.cmd == "align" && f == "--report") a.report_out = v();
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--sharedReads") a.shared_out = v();
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
         else if (f == "--bamFile") a.bam_file = v();
         else if (f == "--lowCov") a.low_cov = true;
@@ -338,6 +343,8 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     const bool want_report = !a.report_out.empty();
     if (want_report && a.no_align) { fprintf(stderr, "--report needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
     if (want_report && a.cov_cutoff > 1.0) { fprintf(stderr, "supplied coverage cutoff exceeds 1.0 (100%%): %g\n", a.cov_cutoff); return 1; }   // cmd/report.go:95-97
+    const bool want_shared = !a.shared_out.empty();
+    if (want_shared && !want_report) { fprintf(stderr, "--sharedReads lists pairs of reported ARGs: it needs --report\n"); return 1; }
     if (a.no_bam && !want_report) { fprintf(stderr, "--noBam without --report would leave no output of the alignments\n"); return 1; }
     if (a.no_bam && !a.bam_out.empty()) { fprintf(stderr, "--noBam and --bam contradict each other\n"); return 1; }
     start_logging(a);
@@ -488,13 +495,31 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     for (uint32_t p = 0; p < v.n_paths; p++) cov_slots += v.path_len[p];
     std::vector<uint64_t> cov_records(want_report ? v.n_paths : 0), cov_depth(want_report ? cov_slots : 0);
     std::mutex cov_mu;
+    std::vector<uint32_t> sh_a, sh_b;
+    std::vector<uint64_t> sh_n;
     auto cov_harvest = [&](groot_ctx *ctx) -> int {
         std::vector<uint64_t> r(v.n_paths), d(cov_slots);
         if (int rc = groot_hip_coverage_export(ctx, r.data(), d.data())) return rc;
         std::lock_guard<std::mutex> lk(cov_mu);
         for (size_t i = 0; i < r.size(); i++) cov_records[i] += r[i];
         for (size_t i = 0; i < d.size(); i++) cov_depth[i] += d[i];
+        if (!want_shared) return 0;
+        // --sharedReads: the ctx's nonzero pairs, appended (a read goes to one ctx only: the sums are exact, groot_host_shared_from_counts
+        // adds up repeated pairs)
+        uint64_t n = 0, m = 0;
+        if (int rc = groot_hip_shared_export(ctx, nullptr, nullptr, nullptr, 0, &n)) return rc;
+        std::vector<uint32_t> pa(n), pb(n);
+        std::vector<uint64_t> cnt(n);
+        if (n)
+            if (int rc = groot_hip_shared_export(ctx, pa.data(), pb.data(), cnt.data(), n, &m)) return rc;
+        sh_a.insert(sh_a.end(), pa.begin(), pa.end());
+        sh_b.insert(sh_b.end(), pb.begin(), pb.end());
+        sh_n.insert(sh_n.end(), cnt.begin(), cnt.end());
         return 0;
+    };
+    auto cov_enable = [&](groot_ctx *ctx, int on) -> int {
+        if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
+        return want_shared ? groot_hip_shared_enable(ctx, on) : 0;
     };
     for (int d : devices) {
         std::unique_ptr<Gpu> g(new Gpu());
@@ -512,7 +537,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         for (auto &t : th) t.join();
         for (auto &e : errs) if (!e.empty()) die("%s", e.c_str());
         if (want_report)
-            for (auto &g : gpus) if (groot_hip_coverage_enable(g->ctx, 1)) die("%s", groot_hip_last_error(g->ctx));
+            for (auto &g : gpus) if (cov_enable(g->ctx, 1)) die("%s", groot_hip_last_error(g->ctx));
     }
     logf("\tcontainment threshold: %.2f", a.threshold);
     if (a.no_align) logf("\tprevent exact alignments and using approximated mapping only");
@@ -576,7 +601,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                 logf("\tread of %u bases: reopening the GPU context for reads up to %u bases", need, g.max_read_len);
                 if (groot_hip_open_flags(&g.ctx, g.device, &v, &prm, GROOT_OPEN_BACKGROUND)) { fail_with(groot_hip_last_error(nullptr)); return false; }
                 if (n_rows && groot_hip_attempts_import(g.ctx, qv.data(), cnt.data(), n_rows)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
-                if (want_report && groot_hip_coverage_enable(g.ctx, 1)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+                if (want_report && cov_enable(g.ctx, 1)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 return true;
             };
             while (!failed) {
@@ -675,13 +700,20 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     if (want_report) {
         // every batch has been collected: what each ctx counted is final (it is switched off, so a ctx reopened below starts without it)
         for (auto &g : gpus) {
-            if (cov_harvest(g->ctx) || groot_hip_coverage_enable(g->ctx, 0)) die("%s", groot_hip_last_error(g->ctx));
+            if (cov_harvest(g->ctx) || cov_enable(g->ctx, 0)) die("%s", groot_hip_last_error(g->ctx));
         }
         uint64_t n_rep = 0;
         if (groot_host_report_coverage(&v, cov_records.data(), cov_depth.data(), a.cov_cutoff, a.low_cov ? 1 : 0, a.report_out.c_str(), &n_rep))
             die("%s", groot_host_last_error());
         logf("\treport: %llu ARG(s) written to %s (coverage cutoff %.2f%s)", (unsigned long long)n_rep, a.report_out.c_str(), a.low_cov ? 0.97 : a.cov_cutoff,
              a.low_cov ? ", --lowCov" : "");
+        if (want_shared) {
+            uint64_t n_lines = 0;
+            if (groot_host_shared_from_counts(&v, cov_records.data(), cov_depth.data(), a.cov_cutoff, a.low_cov ? 1 : 0, sh_a.size(), sh_a.data(), sh_b.data(),
+                                              sh_n.data(), a.shared_out.c_str(), &n_lines))
+                die("%s", groot_host_last_error());
+            logf("\tshared reads: %llu pair(s) of reported ARGs written to %s", (unsigned long long)n_lines, a.shared_out.c_str());
+        }
     }
     const double stream_s = seconds_since(t_stream);
     auto t_post = std::chrono::steady_clock::now();
@@ -809,9 +841,12 @@ int run_report(const Args &a)
     if (a.cov_cutoff > 1.0) die("supplied coverage cutoff exceeds 1.0 (100%%): %g", a.cov_cutoff);
     logf("\tcoverage cutoff: %.2f", a.cov_cutoff);
     logf("\tprocessors: %d", a.proc);
-    uint64_t n = 0;
-    if (groot_host_report(a.bam_file.empty() ? nullptr : a.bam_file.c_str(), a.cov_cutoff, a.low_cov ? 1 : 0, nullptr, &n))
+    uint64_t n = 0, n_lines = 0;
+    const char *bam = a.bam_file.empty() ? nullptr : a.bam_file.c_str();
+    if (a.shared_out.empty() ? groot_host_report(bam, a.cov_cutoff, a.low_cov ? 1 : 0, nullptr, &n)
+                             : groot_host_report_shared(bam, a.cov_cutoff, a.low_cov ? 1 : 0, nullptr, a.shared_out.c_str(), &n, &n_lines))
         die("%s", groot_host_last_error());
+    if (!a.shared_out.empty()) logf("\tshared reads: %llu pair(s) of reported ARGs written to %s", (unsigned long long)n_lines, a.shared_out.c_str());
     logf("finished");
     return 0;
 }

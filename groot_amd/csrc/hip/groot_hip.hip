@@ -25,6 +25,7 @@
 #include "kernels_cov.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_path.hpp"
+#include "kernels_shared.hpp"
 #include "launch.hpp"
 
 using namespace groot;
@@ -76,7 +77,8 @@ template <class T> struct PinBuf {
 // compare the tiers with each other and with the CPU checker); TEST_SMALL_BUFFERS starts every growable buffer and list too small, so that
 // a test batch walks the grow-and-redo and the fall-back paths; OPEN_STATS prints where groot_hip_open spent its time.
 struct Knobs {
-    bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false;
+    bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false,
+         shared_slow = false;
     static Knobs read()
     {
         Knobs k;
@@ -86,6 +88,7 @@ struct Knobs {
         k.poison = getenv("GROOT_TEST_POISON") != nullptr;
         k.lean = getenv("GROOT_LEAN") != nullptr;                         // the node-by-node first pass (kernels_lean.hpp) instead of the path-text one
         k.no_path = getenv("GROOT_NO_PATH_PASS") != nullptr;              // no first pass: align_kernel alone
+        k.shared_slow = getenv("GROOT_TEST_SHARED_SLOW") != nullptr;      // shared reads: every read in more than one graph takes the slow path
         return k;
     }
 };
@@ -298,6 +301,13 @@ struct groot_ctx {
     DevBuf<uint2> cov_np;
     DevBuf<uint64_t> cov_base;
     DevBuf<unsigned long long> cov_starts, cov_ends;
+    // shared reads (groot_hip_shared_*, kernels_shared.hpp): off until enabled, then four kernels behind every batch's order stage count,
+    // for every pair of paths a <= b, the reads with records on both.  Nothing on the device while off.
+    bool sh_on = false;
+    uint32_t sh_tab_cap = 0;               // slots of the set table: a power of two >= 2 max_batch_reads
+    DevBuf<uint32_t> sh_gpo, sh_set_graph, sh_tab_rep, sh_tab_cnt, sh_slow, sh_batch;
+    DevBuf<uint64_t> sh_set_mask;
+    DevBuf<unsigned long long> sh_tri, sh_stats;
 };
 
 // A ctx drives four HIP streams at once -- seed stage, align + order stage, copy-in, copy-out -- beside whatever the host process
@@ -1000,6 +1010,23 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
         ca.starts = c->cov_starts.p; ca.ends = c->cov_ends.p;
         ca.cap = s->trav_cap; ca.pw = c->pw_view; ca.first_read_id = s->first_read_id;
         hipLaunchKernelGGL(cov_count_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->astream, ca);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (c->sh_on) {    // (the same: slot data and the ctx's own buffers, in align-stream order)
+        SharedArgs sa{};
+        sa.trav = s->d_trav.p; sa.mask = s->d_mask.p; sa.ctr = s->d_ctr.p; sa.graph_path_off = c->sh_gpo.p;
+        sa.set_graph = c->sh_set_graph.p; sa.set_mask = c->sh_set_mask.p; sa.tab_rep = c->sh_tab_rep.p; sa.tab_cnt = c->sh_tab_cnt.p;
+        sa.slow = c->sh_slow.p; sa.batch = c->sh_batch.p; sa.tri = c->sh_tri.p; sa.stats = c->sh_stats.p;
+        sa.cap = s->trav_cap; sa.pw = c->pw_view; sa.first_read_id = s->first_read_id; sa.n_paths = (uint32_t)c->h_cov_len.size();
+        sa.max_segs = c->kn.shared_slow ? 1u : kSharedSegs;
+        uint32_t tab = 1;                  // this batch's part of the table: >= 2 n_reads slots
+        while (tab < 2u * std::max<uint32_t>(s->n_reads, 1u)) tab <<= 1;
+        sa.tab_mask = tab - 1;
+        const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
+        hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->astream, sa);
+        hipLaunchKernelGGL(shared_insert_kernel, g, dim3(kBlock), 0, c->astream, sa);
+        hipLaunchKernelGGL(shared_slow_kernel, dim3(256), dim3(kBlock), 0, c->astream, sa);
+        hipLaunchKernelGGL(shared_expand_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->astream, sa, tab);
         HIP_TRY(c, hipGetLastError());
     }
     w->used = true;
@@ -3383,6 +3410,92 @@ int groot_hip_coverage_reset(groot_ctx *c)
     const uint64_t slots = std::max<uint64_t>(c->h_cov_base.back(), 1);
     HIP_TRY(c, hipMemset(c->cov_starts.p, 0, slots * sizeof(unsigned long long)));
     HIP_TRY(c, hipMemset(c->cov_ends.p, 0, slots * sizeof(unsigned long long)));
+    return GROOT_OK;
+}
+
+// ---- shared reads (kernels_shared.hpp) -------------------------------------------------------------------------------
+static uint64_t shared_tri_size(uint64_t n_paths) { return n_paths * (n_paths + 1) / 2; }
+
+int groot_hip_shared_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "shared reads can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!on) {
+        for (auto *b : {&c->sh_gpo, &c->sh_set_graph, &c->sh_tab_rep, &c->sh_tab_cnt, &c->sh_slow, &c->sh_batch}) b->release();
+        c->sh_set_mask.release(); c->sh_tri.release(); c->sh_stats.release();
+        c->sh_on = false;
+        return GROOT_OK;
+    }
+    if (c->sh_on) return GROOT_OK;
+    const uint64_t n_paths = c->h_cov_len.size(), tri = shared_tri_size(n_paths);
+    if (tri * sizeof(uint64_t) > GROOT_SHARED_MAX_BYTES)
+        return fail(c, GROOT_E_UNSUPPORTED, "shared reads: %llu paths need a %llu MiB pair table, above the bound of %llu MiB", (unsigned long long)n_paths,
+                    (unsigned long long)(tri * sizeof(uint64_t) >> 20), (unsigned long long)(GROOT_SHARED_MAX_BYTES >> 20));
+    const uint32_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    uint64_t tab = 1;
+    while (tab < 2ull * R) tab <<= 1;
+    if (tab > (1ull << 31)) return fail(c, GROOT_E_UNSUPPORTED, "shared reads: max_batch_reads=%u is above 2^30", R);
+    c->sh_tab_cap = (uint32_t)tab;
+    auto undo = [&](int rc) { groot_hip_shared_enable(c, 0); return rc; };
+    hipError_t e = upload(c->sh_gpo, c->h_cov_gpo.data(), c->h_cov_gpo.size());
+    if (e == hipSuccess) e = c->sh_set_graph.alloc((size_t)R * kSharedSegs);
+    if (e == hipSuccess) e = c->sh_set_mask.alloc((size_t)R * kSharedSegs * std::max<uint32_t>(c->pw_view, 1u));
+    if (e == hipSuccess) e = c->sh_tab_rep.alloc(tab);
+    if (e == hipSuccess) e = c->sh_tab_cnt.alloc(tab);
+    if (e == hipSuccess) e = c->sh_slow.alloc(R);
+    if (e == hipSuccess) e = c->sh_batch.alloc(3);
+    if (e == hipSuccess) e = c->sh_tri.alloc(tri);
+    if (e == hipSuccess) e = c->sh_stats.alloc(3);
+    if (e == hipSuccess) e = hipMemset(c->sh_tab_rep.p, 0xFF, tab * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->sh_tab_cnt.p, 0, tab * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->sh_batch.p, 0, 3 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->sh_tri.p, 0, std::max<uint64_t>(tri, 1) * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, 3 * sizeof(unsigned long long));
+    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "shared reads: %s", hipGetErrorString(e)));
+    c->sh_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_shared_export(groot_ctx *c, uint32_t *pa, uint32_t *pb, uint64_t *count, uint64_t cap, uint64_t *n_pairs)
+{
+    if (!c || !n_pairs || (cap && (!pa || !pb || !count))) return GROOT_E_INVALID;
+    if (!c->sh_on) return fail(c, GROOT_E_STATE, "shared reads are not enabled (groot_hip_shared_enable)");
+    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo, if they need one)
+    const uint64_t P = c->h_cov_len.size(), tri = shared_tri_size(P);
+    std::vector<uint64_t> t(tri);
+    if (tri) HIP_TRY(c, hipMemcpy(t.data(), c->sh_tri.p, tri * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t n = 0, i = 0;
+    for (uint64_t x = 0; x < P; x++)
+        for (uint64_t y = x; y < P; y++, i++) {
+            if (!t[i]) continue;
+            if (n < cap) { pa[n] = (uint32_t)x; pb[n] = (uint32_t)y; count[n] = t[i]; }
+            n++;
+        }
+    *n_pairs = n;
+    return GROOT_OK;
+}
+
+int groot_hip_shared_stats(groot_ctx *c, uint64_t *reads, uint64_t *distinct_sets, uint64_t *slow_reads)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->sh_on) return fail(c, GROOT_E_STATE, "shared reads are not enabled (groot_hip_shared_enable)");
+    if (int rc = drain(c)) return rc;
+    uint64_t st[3];
+    HIP_TRY(c, hipMemcpy(st, c->sh_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    if (reads) *reads = st[0];
+    if (distinct_sets) *distinct_sets = st[1];
+    if (slow_reads) *slow_reads = st[2];
+    return GROOT_OK;
+}
+
+int groot_hip_shared_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->sh_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemset(c->sh_tri.p, 0, std::max<uint64_t>(shared_tri_size(c->h_cov_len.size()), 1) * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->sh_stats.p, 0, 3 * sizeof(unsigned long long)));
     return GROOT_OK;
 }
 

@@ -8,8 +8,11 @@
 // a loop variable shared between goroutines, reporting.go:149).
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstring>
+#include <map>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "host_common.hpp"
@@ -134,12 +137,15 @@ int check_cutoff(double &cov_cutoff, int low_cov)
 
 // reporting.go:128-160: the lines of the report from per-reference record counts and pileups, in reference order.  covered(r, i) =
 // base i of reference r has a non-zero pileup; has_pileup(r) = reference r got a pileup (of its length).  name_len NULL = C strings.
+// reported: NULL, or set to 1 for every reference written.
 template <class Covered, class HasPileup>
 int write_report(uint32_t n_ref, const char *const *names, const uint32_t *name_len, const uint32_t *lens, const uint64_t *count,
-                 Covered covered_at, HasPileup has_pileup, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported)
+                 Covered covered_at, HasPileup has_pileup, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported,
+                 std::vector<uint8_t> *reported_refs = nullptr, bool emit = true)
 {
-    FILE *out = out_path ? fopen(out_path, "w") : stdout;
-    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
+    if (reported_refs) reported_refs->assign(n_ref, 0);
+    FILE *out = !emit ? nullptr : out_path ? fopen(out_path, "w") : stdout;
+    if (emit && !out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
     uint64_t reported = 0;
     std::vector<uint8_t> cov;
     for (uint32_t r = 0; r < n_ref; r++) {
@@ -155,17 +161,51 @@ int write_report(uint32_t n_ref, const char *const *names, const uint32_t *name_
         const char *name = names[r];
         size_t nl = name_len ? name_len[r] : strlen(name);
         if (nl && name[0] == '*') { name++; nl--; }                         // cluster representative marker (:135-137)
-        fprintf(out, "%.*s\t%llu\t%u\t%s\n", (int)nl, name, (unsigned long long)count[r], lens[r], cigar.c_str());
+        if (out) fprintf(out, "%.*s\t%llu\t%u\t%s\n", (int)nl, name, (unsigned long long)count[r], lens[r], cigar.c_str());
         reported++;
+        if (reported_refs) (*reported_refs)[r] = 1;
+    }
+    if (out && out_path) fclose(out); else if (out) fflush(out);
+    if (n_reported) *n_reported = reported;
+    return GROOT_OK;
+}
+
+// The shared-reads file: "nameA \t nameB \t n" for every pair (a, b), a <= b, of reported references with n != 0, ascending by (a, b),
+// names as the report prints them.  pairs = (a, b, n) sorted by (a, b), a pair at most once.
+struct SharedPair {
+    uint32_t a, b;
+    uint64_t n;
+};
+
+int write_shared(const char *const *names, const uint32_t *name_len, const std::vector<uint8_t> &reported, const std::vector<SharedPair> &pairs,
+                 const char *out_path, uint64_t *n_lines)
+{
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
+    auto name = [&](uint32_t r, size_t &nl) {
+        const char *nm = names[r];
+        nl = name_len ? name_len[r] : strlen(nm);
+        if (nl && nm[0] == '*') { nm++; nl--; }                             // as the report prints it
+        return nm;
+    };
+    uint64_t lines = 0;
+    for (const SharedPair &p : pairs) {
+        if (!p.n || !reported[p.a] || !reported[p.b]) continue;
+        size_t la, lb;
+        const char *na = name(p.a, la), *nb = name(p.b, lb);
+        fprintf(out, "%.*s\t%.*s\t%llu\n", (int)la, na, (int)lb, nb, (unsigned long long)p.n);
+        lines++;
     }
     if (out_path) fclose(out); else fflush(out);
-    if (n_reported) *n_reported = reported;
+    if (n_lines) *n_lines = lines;
     return GROOT_OK;
 }
 
 } // namespace
 
-extern "C" int groot_host_report(const char *bam_path, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported)
+// `groot report` on a BAM; with shared_out, also the shared-reads file: S(read) = the references with a counted record of that QNAME
+static int report_bam(const char *bam_path, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported, const char *shared_out,
+                      uint64_t *n_lines)
 {
     if (int rc = check_cutoff(cov_cutoff, low_cov)) return rc;
     BgzfIn in;
@@ -191,6 +231,12 @@ extern "C" int groot_host_report(const char *bam_path, double cov_cutoff, int lo
     std::vector<std::vector<uint32_t>> pileup(n_ref);
     std::vector<uint64_t> count(n_ref, 0);
     std::vector<uint8_t> rec;
+    // shared reads: reads are numbered by QNAME in order of first appearance (the reference interleaves the records of several
+    // reads, so adjacency does not delimit a read); every counted record adds (read, reference)
+    const bool shared = shared_out != nullptr;
+    std::unordered_map<std::string, uint32_t> read_of;
+    std::vector<uint64_t> read_ref;
+    std::string qname;
     for (;;) {
         bool clean = false;
         if (!in.read(b4, 4, &clean)) {
@@ -216,6 +262,11 @@ extern "C" int groot_host_report(const char *bam_path, double cov_cutoff, int lo
         auto &pl = pileup[ref_id];
         if (pl.empty()) pl.assign(lens[ref_id], 0);
         count[ref_id]++;
+        if (shared) {
+            qname.assign((const char *)rec.data() + 32, l_read_name ? l_read_name - 1 : 0);   // (NUL-terminated)
+            const uint32_t rd = read_of.emplace(qname, (uint32_t)read_of.size()).first->second;
+            read_ref.push_back((uint64_t)rd << 32 | (uint32_t)ref_id);
+        }
         if (pl.empty()) continue;
         uint64_t end = (uint64_t)pos + ref_len;
         if (end > pl.size() - 1) end = pl.size() - 1;
@@ -223,13 +274,61 @@ extern "C" int groot_host_report(const char *bam_path, double cov_cutoff, int lo
     }
     std::vector<const char *> name_ptr(n_ref);
     for (uint32_t r = 0; r < n_ref; r++) name_ptr[r] = names[r].c_str();
-    return write_report(n_ref, name_ptr.data(), nullptr, lens.data(), count.data(),
-                        [&](uint32_t r, size_t i) { return pileup[r][i] != 0; }, [&](uint32_t r) { return !pileup[r].empty(); },
-                        cov_cutoff, low_cov, out_path, n_reported);
+    std::vector<uint8_t> reported;
+    if (int rc = write_report(n_ref, name_ptr.data(), nullptr, lens.data(), count.data(),
+                              [&](uint32_t r, size_t i) { return pileup[r][i] != 0; }, [&](uint32_t r) { return !pileup[r].empty(); },
+                              cov_cutoff, low_cov, out_path, n_reported, &reported))
+        return rc;
+    if (!shared) return GROOT_OK;
+    // S(read) restricted to the reported references, then every pair of it counted once per read
+    pileup.clear();
+    read_ref.erase(std::remove_if(read_ref.begin(), read_ref.end(), [&](uint64_t x) { return !reported[(uint32_t)x]; }), read_ref.end());
+    std::sort(read_ref.begin(), read_ref.end());
+    read_ref.erase(std::unique(read_ref.begin(), read_ref.end()), read_ref.end());
+    // counters: a dense triangle over the reported references (rank order = header order) up to 1 GiB of them, else a map
+    std::vector<uint32_t> rank(n_ref, 0), ref_of;
+    for (uint32_t r = 0; r < n_ref; r++)
+        if (reported[r]) { rank[r] = (uint32_t)ref_of.size(); ref_of.push_back(r); }
+    const uint64_t R = ref_of.size(), tri = R * (R + 1) / 2;
+    const bool dense = tri <= (1ull << 27);
+    std::vector<uint64_t> dcnt(dense ? tri : 0);
+    std::map<std::pair<uint32_t, uint32_t>, uint64_t> mcnt;
+    for (size_t i = 0; i < read_ref.size();) {
+        size_t j = i;
+        while (j < read_ref.size() && read_ref[j] >> 32 == read_ref[i] >> 32) j++;
+        for (size_t x = i; x < j; x++)
+            for (size_t y = x; y < j; y++) {
+                const uint64_t a = rank[(uint32_t)read_ref[x]], b = rank[(uint32_t)read_ref[y]];
+                if (dense) dcnt[a * R - a * (a - 1) / 2 + (b - a)]++;
+                else mcnt[{(uint32_t)a, (uint32_t)b}]++;
+            }
+        i = j;
+    }
+    std::vector<SharedPair> pairs;
+    if (dense) {
+        uint64_t k = 0;
+        for (uint64_t a = 0; a < R; a++)
+            for (uint64_t b = a; b < R; b++, k++)
+                if (dcnt[k]) pairs.push_back({ref_of[a], ref_of[b], dcnt[k]});
+    } else
+        for (const auto &kv : mcnt) pairs.push_back({ref_of[kv.first.first], ref_of[kv.first.second], kv.second});
+    return write_shared(name_ptr.data(), nullptr, reported, pairs, shared_out, n_lines);
 }
 
-extern "C" int groot_host_report_coverage(const groot_index_view *ix, const uint64_t *records, const uint64_t *depth, double cov_cutoff,
-                                          int low_cov, const char *out_path, uint64_t *n_reported)
+extern "C" int groot_host_report(const char *bam_path, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported)
+{
+    return report_bam(bam_path, cov_cutoff, low_cov, out_path, n_reported, nullptr, nullptr);
+}
+
+extern "C" int groot_host_report_shared(const char *bam_path, double cov_cutoff, int low_cov, const char *report_out, const char *shared_out,
+                                        uint64_t *n_reported, uint64_t *n_lines)
+{
+    if (!shared_out) return set_error(GROOT_E_INVALID, "null argument");
+    return report_bam(bam_path, cov_cutoff, low_cov, report_out, n_reported, shared_out, n_lines);
+}
+
+static int report_counts(const groot_index_view *ix, const uint64_t *records, const uint64_t *depth, double cov_cutoff, int low_cov,
+                         const char *out_path, uint64_t *n_reported, std::vector<uint8_t> *reported, bool emit = true)
 {
     if (!ix || (ix->n_paths && (!records || !depth))) return set_error(GROOT_E_INVALID, "null argument");
     if (int rc = check_cutoff(cov_cutoff, low_cov)) return rc;
@@ -245,5 +344,42 @@ extern "C" int groot_host_report_coverage(const groot_index_view *ix, const uint
     // a reference with records has a pileup of its length (reporting.go:100-103); one of length 0 is not reported
     return write_report(n, name_ptr.data(), name_len.data(), ix->path_len, records,
                         [&](uint32_t p, size_t i) { return depth[base[p] + i] != 0; }, [&](uint32_t p) { return ix->path_len[p] != 0; },
-                        cov_cutoff, low_cov, out_path, n_reported);
+                        cov_cutoff, low_cov, out_path, n_reported, reported, emit);
+}
+
+extern "C" int groot_host_report_coverage(const groot_index_view *ix, const uint64_t *records, const uint64_t *depth, double cov_cutoff,
+                                          int low_cov, const char *out_path, uint64_t *n_reported)
+{
+    return report_counts(ix, records, depth, cov_cutoff, low_cov, out_path, n_reported, nullptr);
+}
+
+extern "C" int groot_host_shared_from_counts(const groot_index_view *ix, const uint64_t *records, const uint64_t *depth, double cov_cutoff,
+                                             int low_cov, uint64_t n_pairs, const uint32_t *pa, const uint32_t *pb, const uint64_t *count,
+                                             const char *out_path, uint64_t *n_lines)
+{
+    if (!ix || (n_pairs && (!pa || !pb || !count))) return set_error(GROOT_E_INVALID, "null argument");
+    const uint32_t n = ix->n_paths;
+    std::vector<SharedPair> pairs(n_pairs);
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        if (pa[i] > pb[i] || pb[i] >= n) return set_error(GROOT_E_INVALID, "pair %llu = (%u, %u) is not a <= b < %u", (unsigned long long)i, pa[i], pb[i], n);
+        pairs[i] = {pa[i], pb[i], count[i]};
+    }
+    // the reported set: the report's own tail, written nowhere
+    std::vector<uint8_t> reported;
+    if (int rc = report_counts(ix, records, depth, cov_cutoff, low_cov, nullptr, nullptr, &reported, false)) return rc;
+    // in any order, a pair given more than once (the lists of several contexts) is summed
+    std::sort(pairs.begin(), pairs.end(), [](const SharedPair &x, const SharedPair &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+    size_t m = 0;
+    for (size_t i = 0; i < pairs.size(); i++) {
+        if (m && pairs[m - 1].a == pairs[i].a && pairs[m - 1].b == pairs[i].b) pairs[m - 1].n += pairs[i].n;
+        else pairs[m++] = pairs[i];
+    }
+    pairs.resize(m);
+    std::vector<const char *> name_ptr(n);
+    std::vector<uint32_t> name_len(n);
+    for (uint32_t p = 0; p < n; p++) {
+        name_ptr[p] = ix->path_names + ix->path_name_off[p];
+        name_len[p] = ix->path_name_off[p + 1] - ix->path_name_off[p];
+    }
+    return write_shared(name_ptr.data(), name_len.data(), reported, pairs, out_path, n_lines);
 }

@@ -355,6 +355,35 @@ class Aligner:
     def coverage_reset(self):
         self._check(lib().groot_hip_coverage_reset(self._h))
 
+    # ---- shared reads (groot_hip_shared_*) --------------------------------------------------------
+    def shared_enable(self, on=True):
+        """count, for every pair of paths a <= b, the reads with records on both, from now on (only while nothing is in flight)"""
+        self._check(lib().groot_hip_shared_enable(self._h, C.c_int(1 if on else 0)))
+
+    def shared(self):
+        """(a, b, count) of every nonzero pair since enable / reset, ascending by (a, b): uint32, uint32, uint64 arrays; the pair
+        input of host.shared_from_counts.  Waits for everything in flight."""
+        n = C.c_uint64(0)
+        self._check(lib().groot_hip_shared_export(self._h, None, None, None, C.c_uint64(0), C.byref(n)))
+        a = np.zeros(n.value, dtype=np.uint32)
+        b = np.zeros(n.value, dtype=np.uint32)
+        cnt = np.zeros(n.value, dtype=np.uint64)
+        if n.value:
+            m = C.c_uint64(0)
+            self._check(lib().groot_hip_shared_export(self._h, _ffi.as_ptr(a, C.c_uint32), _ffi.as_ptr(b, C.c_uint32), _ffi.as_ptr(cnt, C.c_uint64),
+                                                      C.c_uint64(n.value), C.byref(m)))
+            assert m.value == n.value
+        return a, b, cnt
+
+    def shared_stats(self):
+        """{"reads", "distinct_sets", "slow_reads"} since enable / reset (groot_hip_shared_stats)"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        self._check(lib().groot_hip_shared_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("reads", "distinct_sets", "slow_reads"), (x.value for x in v)))
+
+    def shared_reset(self):
+        self._check(lib().groot_hip_shared_reset(self._h))
+
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):
         seq = np.ascontiguousarray(seq_concat, dtype=np.uint8)

@@ -397,6 +397,70 @@ def report_coverage(index, records, depth, cov_cutoff=0.97, low_cov=False, out_p
     return [(r[0], int(r[1]), int(r[2]), r[3]) for r in rows]
 
 
+def _shared_rows(path):
+    rows = [ln.rstrip("\n").split("\t") for ln in open(path)]
+    return [(r[0], r[1], int(r[2])) for r in rows]
+
+
+def shared_from_counts(index, records, depth, pa, pb, count, cov_cutoff=0.97, low_cov=False, out_path=None):
+    """the shared-reads lines (groot_host_shared_from_counts) for the references report_coverage(index, records, depth, ...) reports:
+    [(nameA, nameB, reads)]; pa / pb / count as device.Aligner.shared() gives them (any order, repeated pairs summed)"""
+    import tempfile
+
+    v = index.view
+    records = np.ascontiguousarray(records, dtype=np.uint64)
+    depth = np.ascontiguousarray(depth, dtype=np.uint64)
+    pa = np.ascontiguousarray(pa, dtype=np.uint32)
+    pb = np.ascontiguousarray(pb, dtype=np.uint32)
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    if records.shape != (v.n_paths,) or depth.shape != (int(index.arrays["path_len"].astype(np.uint64).sum()),):
+        raise ValueError("records / depth do not match the index")
+    if not (len(pa) == len(pb) == len(count)):
+        raise ValueError("pa / pb / count differ in length")
+    tmp = None
+    if out_path is None:
+        fd, tmp = tempfile.mkstemp(suffix=".shared")
+        os.close(fd)
+    n = C.c_uint64(0)
+    try:
+        _check(lib().groot_host_shared_from_counts(C.byref(v), _ffi.as_ptr(records, C.c_uint64), _ffi.as_ptr(depth, C.c_uint64), C.c_double(cov_cutoff),
+                                                   C.c_int(1 if low_cov else 0), C.c_uint64(len(pa)), _ffi.as_ptr(pa, C.c_uint32),
+                                                   _ffi.as_ptr(pb, C.c_uint32), _ffi.as_ptr(count, C.c_uint64), (out_path or tmp).encode(),
+                                                   C.byref(n)))
+        rows = _shared_rows(out_path or tmp)
+    finally:
+        if tmp:
+            os.unlink(tmp)
+    assert len(rows) == n.value
+    return rows
+
+
+def report_shared(bam_path, cov_cutoff=0.97, low_cov=False, report_out=None, shared_out=None):
+    """one pass over a BAM (groot_host_report_shared): (the rows of report(), the shared-reads rows [(nameA, nameB, reads)]), a read
+    being one QNAME"""
+    import tempfile
+
+    tmps = []
+    paths = []
+    for p in (report_out, shared_out):
+        if p is None:
+            fd, p = tempfile.mkstemp(suffix=".tsv")
+            os.close(fd)
+            tmps.append(p)
+        paths.append(p)
+    nr, nl = C.c_uint64(0), C.c_uint64(0)
+    try:
+        _check(lib().groot_host_report_shared(bam_path.encode(), C.c_double(cov_cutoff), C.c_int(1 if low_cov else 0), paths[0].encode(),
+                                              paths[1].encode(), C.byref(nr), C.byref(nl)))
+        rep = [ln.rstrip("\n").split("\t") for ln in open(paths[0])]
+        sh = _shared_rows(paths[1])
+    finally:
+        for p in tmps:
+            os.unlink(p)
+    assert len(rep) == nr.value and len(sh) == nl.value
+    return [(r[0], int(r[1]), int(r[2]), r[3]) for r in rep], sh
+
+
 def save_gfa(index, graph, kmer_freq, path_kept, node_removed, total_kmers, file_name, timestamp=None):
     """GrootGraph.SaveGraphAsGFA (src/graph/graphio.go:19-112); returns True if a file was written"""
     kf = np.ascontiguousarray(kmer_freq, dtype=np.float64)

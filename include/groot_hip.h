@@ -299,6 +299,28 @@ int groot_hip_coverage_export(groot_ctx *ctx, uint64_t *records, uint64_t *depth
 /* Zeroes the counters (after waiting for everything in flight).  No-op when coverage is off. */
 int groot_hip_coverage_reset(groot_ctx *ctx);
 
+/* ---- shared reads ---------------------------------------------------------------------------------------------------
+ * Which reads two references share (the multimapper check of the reference tutorial, without a BAM).  For a read r let S(r) be
+ * the set of global paths (BAM references) that carry at least one record of r -- the records groot_host_expand_alns emits and
+ * `report` counts: every traversal, both strands, primary and secondary.  For paths a <= b in BAM header order,
+ * shared[a][b] = |{r : a in S(r) and b in S(r)}|; shared[a][a] is the number of distinct reads on a.  A read is one input read of
+ * the batch (one FASTQ record); groot_host_report_shared, which works from a BAM, groups records by QNAME instead, so the two
+ * agree whenever read names are unique.  Accumulated on the device batch by batch behind the order stage (kernels_shared.hpp);
+ * counted once exactly as coverage is (a redone pass counts in its redo only, a batch that fails with GROOT_E_NOSPACE not at all).
+ * Off by default: then nothing is launched and no device memory is taken. */
+#define GROOT_SHARED_MAX_BYTES (1ull << 30)   /* bound of the pair table: n_paths (n_paths + 1) / 2 u64 counters */
+/* Switch on (zeroed counters: the pair table, plus ~(36 + 32 path_words) bytes per read of max_batch_reads) or off (freed).  Only
+ * while nothing is in flight.  GROOT_E_UNSUPPORTED when the pair table would exceed GROOT_SHARED_MAX_BYTES (16 383 paths). */
+int groot_hip_shared_enable(groot_ctx *ctx, int on);
+/* The nonzero pairs, ascending by (a, b): *n_pairs = their number; the first min(cap, *n_pairs) are written to pa / pb / count (call
+ * with cap = 0 to size the arrays).  Waits for everything in flight (redoing what needs a redo).  GROOT_E_STATE when off. */
+int groot_hip_shared_export(groot_ctx *ctx, uint32_t *pa, uint32_t *pb, uint64_t *count, uint64_t cap, uint64_t *n_pairs);
+/* Zeroes the counters (after waiting for everything in flight).  No-op when off. */
+int groot_hip_shared_reset(groot_ctx *ctx);
+/* Diagnostics since enable / reset: reads with at least one record, distinct path sets summed over batches (one table slot each),
+ * reads whose records lie in more than 4 graphs (counted by the slower wave-per-read kernel).  GROOT_E_STATE when off. */
+int groot_hip_shared_stats(groot_ctx *ctx, uint64_t *reads, uint64_t *distinct_sets, uint64_t *slow_reads);
+
 /* Fine-grained mirror of Sequence.RunMinHash(k, s, false, nil) (seqio.go:40-68) for a batch of
  * sequences in host memory: out[i*s .. (i+1)*s) = KHF sketch of sequence i.  Only while nothing is in flight. */
 int groot_hip_sketch(groot_ctx *ctx, const uint8_t *seq_concat, const uint64_t *seq_off, uint32_t n, uint64_t *out);

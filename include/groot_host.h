@@ -265,6 +265,20 @@ int groot_host_report(const char *bam_path, double cov_cutoff, int low_cov, cons
  * Byte for byte the output groot_host_report writes for the BAM whose records give these counts. */
 int groot_host_report_coverage(const groot_index_view *idx, const uint64_t *records, const uint64_t *depth, double cov_cutoff,
                                int low_cov, const char *out_path, uint64_t *n_reported);
+/* Shared reads (the definition is at groot_hip_shared_enable in groot_hip.h): the file of "nameA \t nameB \t n" lines, one for every
+ * pair a <= b of REPORTED references with n != 0 reads in common -- a = b included, n then being the distinct reads on a --
+ * ascending by (a, b) in BAM header order, names as the report's first column prints them (the '*' stripped).  Empty when nothing is
+ * reported.  The reported references are the lines groot_host_report_coverage writes for records / depth under the same cutoff and
+ * low_cov.  The n_pairs triples (pa[i], pb[i], count[i]), pa <= pb < n_paths, come from groot_hip_shared_export, in any order; a pair
+ * given more than once (the lists of several contexts) is summed.  out_path NULL = stdout; *n_lines = lines written. */
+int groot_host_shared_from_counts(const groot_index_view *idx, const uint64_t *records, const uint64_t *depth, double cov_cutoff,
+                                  int low_cov, uint64_t n_pairs, const uint32_t *pa, const uint32_t *pb, const uint64_t *count,
+                                  const char *out_path, uint64_t *n_lines);
+/* One pass over a BAM: the report, byte for byte what groot_host_report writes (report_out NULL = stdout), and the shared-reads file
+ * above (shared_out, required).  Here a read is one QNAME: the records of a name are grouped wherever they lie in the BAM (the
+ * reference's writer interleaves the records of different reads), so the device counts and these agree whenever read names are unique. */
+int groot_host_report_shared(const char *bam_path, double cov_cutoff, int low_cov, const char *report_out, const char *shared_out,
+                             uint64_t *n_reported, uint64_t *n_lines);
 
 #ifdef __cplusplus
 }
