@@ -12,6 +12,8 @@
 // reported ARGs, the reads with records on both, counted on the GPU; needs --report); index: --writeGob.
 // report: --sharedReads <file> writes the same pairs from the BAM, a read being one QNAME (the device counts input reads: the two
 // agree whenever read names are unique).
+// align / report: --abundance <file> [--abundanceMin 1.0]: per ARG the reads an EM over equivalence classes (distinct read sets,
+// counted on the GPU under align, from the BAM by QNAME under report) assigns to it.
 // The align hot path runs only on the GPU: no device -> error, never a CPU fallback.
 #include <algorithm>
 #include <atomic>
@@ -68,8 +70,8 @@ void logf(const char *fmt, ...)
 }
 
 struct Args {
-    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out;
-    double cov_cutoff = 0.97;
+    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out, abundance_out;
+    double cov_cutoff = 0.97, abundance_min = 1.0;
     bool low_cov = false, no_bam = false;
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
@@ -105,11 +107,13 @@ void usage()
             "  groot-hip align -i <indexDir> -f <fastq>[,<fastq>...] [-t 0.99] [-c 1.0] [-g <graphDir>] [--noAlign] [-p N] [--log F]\n"
             "                  [--gpu 0 | --gpus N] [--batch 1048576] [--maxReadLen 512] [--bam out.bam] [--bamLevel -2..9] [--stats f.json]\n"
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
-            "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--noBam] [--sharedReads s.tsv]]\n"
+            "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0]] [--noBam]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
-            "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all;\n"
-            "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common)\n"
-            "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--log F]   (BAM from stdin unless --bamFile)\n",
+            "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
+            "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
+            "                   --abundance: `name reads em_reads fraction` per ARG with em_reads >= --abundanceMin, by EM over the reads' path sets)\n"
+            "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
+            "                  (BAM from stdin unless --bamFile)\n",
             groot_host_version());
 }
 
@@ -144,6 +148,8 @@ Args parse(int argc, char **argv)
         else if ((a.cmd == "report" && (f == "-c" || f == "--covCutoff")) || (a.cmd == "align" && f == "--covCutoff")) a.cov_cutoff = atof(v().c_str());
         else if (a.cmd == "align" && f == "--report") a.report_out = v();
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--sharedReads") a.shared_out = v();
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--abundance") a.abundance_out = v();
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--abundanceMin") a.abundance_min = atof(v().c_str());
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
         else if (f == "--bamFile") a.bam_file = v();
         else if (f == "--lowCov") a.low_cov = true;
@@ -345,7 +351,9 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     if (want_report && a.cov_cutoff > 1.0) { fprintf(stderr, "supplied coverage cutoff exceeds 1.0 (100%%): %g\n", a.cov_cutoff); return 1; }   // cmd/report.go:95-97
     const bool want_shared = !a.shared_out.empty();
     if (want_shared && !want_report) { fprintf(stderr, "--sharedReads lists pairs of reported ARGs: it needs --report\n"); return 1; }
-    if (a.no_bam && !want_report) { fprintf(stderr, "--noBam without --report would leave no output of the alignments\n"); return 1; }
+    const bool want_ab = !a.abundance_out.empty();
+    if (want_ab && a.no_align) { fprintf(stderr, "--abundance needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
+    if (a.no_bam && !want_report && !want_ab) { fprintf(stderr, "--noBam without --report would leave no output of the alignments\n"); return 1; }
     if (a.no_bam && !a.bam_out.empty()) { fprintf(stderr, "--noBam and --bam contradict each other\n"); return 1; }
     start_logging(a);
     auto t0 = std::chrono::steady_clock::now();
@@ -497,7 +505,23 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     std::mutex cov_mu;
     std::vector<uint32_t> sh_a, sh_b;
     std::vector<uint64_t> sh_n;
+    std::vector<uint64_t> ec_off{0}, ec_cnt;     // --abundance: the ECs of every ctx, appended (CSR)
+    std::vector<uint32_t> ec_ids;
     auto cov_harvest = [&](groot_ctx *ctx) -> int {
+        if (want_ab) {
+            uint64_t ne = 0, ni = 0, me = 0, mi = 0;
+            if (int rc = groot_hip_ec_export(ctx, nullptr, nullptr, nullptr, 0, 0, &ne, &ni)) return rc;
+            std::vector<uint64_t> off(ne + 1), cnt(ne);
+            std::vector<uint32_t> ids(ni);
+            if (ne)
+                if (int rc = groot_hip_ec_export(ctx, off.data(), ids.data(), cnt.data(), ne, ni, &me, &mi)) return rc;
+            std::lock_guard<std::mutex> lk(cov_mu);
+            const uint64_t base = ec_ids.size();
+            for (uint64_t e = 0; e < ne; e++) ec_off.push_back(base + off[e + 1]);
+            ec_ids.insert(ec_ids.end(), ids.begin(), ids.end());
+            ec_cnt.insert(ec_cnt.end(), cnt.begin(), cnt.end());
+        }
+        if (!want_report) return 0;
         std::vector<uint64_t> r(v.n_paths), d(cov_slots);
         if (int rc = groot_hip_coverage_export(ctx, r.data(), d.data())) return rc;
         std::lock_guard<std::mutex> lk(cov_mu);
@@ -518,8 +542,11 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         return 0;
     };
     auto cov_enable = [&](groot_ctx *ctx, int on) -> int {
-        if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
-        return want_shared ? groot_hip_shared_enable(ctx, on) : 0;
+        if (want_report)
+            if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
+        if (want_shared)
+            if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
+        return want_ab ? groot_hip_ec_enable(ctx, on) : 0;
     };
     for (int d : devices) {
         std::unique_ptr<Gpu> g(new Gpu());
@@ -536,7 +563,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             });
         for (auto &t : th) t.join();
         for (auto &e : errs) if (!e.empty()) die("%s", e.c_str());
-        if (want_report)
+        if (want_report || want_ab)
             for (auto &g : gpus) if (cov_enable(g->ctx, 1)) die("%s", groot_hip_last_error(g->ctx));
     }
     logf("\tcontainment threshold: %.2f", a.threshold);
@@ -593,7 +620,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                 if (groot_hip_attempts_export(g.ctx, nullptr, nullptr, 0, &n_rows, &nw)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 std::vector<uint32_t> qv(n_rows), cnt((size_t)n_rows * nw);
                 if (n_rows && groot_hip_attempts_export(g.ctx, qv.data(), cnt.data(), n_rows, &n_rows, &nw)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
-                if (want_report && cov_harvest(g.ctx)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+                if ((want_report || want_ab) && cov_harvest(g.ctx)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 groot_hip_close(g.ctx);
                 g.ctx = nullptr;
                 g.max_read_len = std::min<uint32_t>(65535, need + need / 2);
@@ -601,7 +628,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                 logf("\tread of %u bases: reopening the GPU context for reads up to %u bases", need, g.max_read_len);
                 if (groot_hip_open_flags(&g.ctx, g.device, &v, &prm, GROOT_OPEN_BACKGROUND)) { fail_with(groot_hip_last_error(nullptr)); return false; }
                 if (n_rows && groot_hip_attempts_import(g.ctx, qv.data(), cnt.data(), n_rows)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
-                if (want_report && cov_enable(g.ctx, 1)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+                if ((want_report || want_ab) && cov_enable(g.ctx, 1)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 return true;
             };
             while (!failed) {
@@ -697,11 +724,23 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     logf("\tnumber of reads sketched: %llu", (unsigned long long)received);                      // sketch.go:321
     const uint64_t bam_bytes = bam ? groot_bam_bytes_written(bam) : 0;
     if (bam && groot_bam_close(bam)) die("%s", groot_host_last_error());
-    if (want_report) {
+    if (want_report || want_ab) {
         // every batch has been collected: what each ctx counted is final (it is switched off, so a ctx reopened below starts without it)
         for (auto &g : gpus) {
             if (cov_harvest(g->ctx) || cov_enable(g->ctx, 0)) die("%s", groot_hip_last_error(g->ctx));
         }
+    }
+    if (want_ab) {
+        uint64_t n_lines = 0;
+        uint32_t iters = 0;
+        auto t_em = std::chrono::steady_clock::now();
+        if (groot_host_abundance_from_ecs(&v, ec_cnt.size(), ec_off.data(), ec_ids.data(), ec_cnt.data(), a.abundance_min, a.abundance_out.c_str(), &n_lines,
+                                          &iters))
+            die("%s", groot_host_last_error());
+        logf("\tabundance: %llu equivalence class(es), EM of %u iteration(s) in %.3f s, %llu ARG(s) with at least %g reads written to %s",
+             (unsigned long long)ec_cnt.size(), iters, seconds_since(t_em), (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
+    }
+    if (want_report) {
         uint64_t n_rep = 0;
         if (groot_host_report_coverage(&v, cov_records.data(), cov_depth.data(), a.cov_cutoff, a.low_cov ? 1 : 0, a.report_out.c_str(), &n_rep))
             die("%s", groot_host_last_error());
@@ -843,10 +882,29 @@ int run_report(const Args &a)
     logf("\tprocessors: %d", a.proc);
     uint64_t n = 0, n_lines = 0;
     const char *bam = a.bam_file.empty() ? nullptr : a.bam_file.c_str();
+    // --abundance reads the BAM a second time: a BAM on stdin is spooled to a temporary file first
+    std::string spool;
+    if (!bam && !a.abundance_out.empty()) {
+        const char *td = getenv("TMPDIR");
+        spool = std::string(td && *td ? td : "/tmp") + "/groot-report-XXXXXX";
+        const int fd = mkstemp(&spool[0]);
+        FILE *f = fd < 0 ? nullptr : fdopen(fd, "wb");
+        if (!f) die("cannot create a temporary file for the BAM on stdin");
+        std::vector<char> buf(1 << 20);
+        for (size_t k; (k = fread(buf.data(), 1, buf.size(), stdin)) > 0;)
+            if (fwrite(buf.data(), 1, k, f) != k) { fclose(f); unlink(spool.c_str()); die("cannot write %s", spool.c_str()); }
+        fclose(f);
+        bam = spool.c_str();
+    }
     if (a.shared_out.empty() ? groot_host_report(bam, a.cov_cutoff, a.low_cov ? 1 : 0, nullptr, &n)
                              : groot_host_report_shared(bam, a.cov_cutoff, a.low_cov ? 1 : 0, nullptr, a.shared_out.c_str(), &n, &n_lines))
         die("%s", groot_host_last_error());
     if (!a.shared_out.empty()) logf("\tshared reads: %llu pair(s) of reported ARGs written to %s", (unsigned long long)n_lines, a.shared_out.c_str());
+    if (!a.abundance_out.empty()) {
+        if (groot_host_report_abundance(bam, a.abundance_min, a.abundance_out.c_str(), &n_lines)) die("%s", groot_host_last_error());
+        logf("\tabundance: %llu ARG(s) with at least %g reads written to %s", (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
+    }
+    if (!spool.empty()) unlink(spool.c_str());
     logf("finished");
     return 0;
 }

@@ -14,6 +14,7 @@
 #include <atomic>
 #include <chrono>
 #include <deque>
+#include <map>
 #include <memory>
 #include <numeric>
 #include <string>
@@ -23,6 +24,7 @@
 #include "../common/cpus.hpp"
 #include "../common/view_check.hpp"
 #include "kernels_cov.hpp"
+#include "kernels_ec.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_path.hpp"
 #include "kernels_shared.hpp"
@@ -43,6 +45,7 @@ template <class T> struct DevBuf {
         return hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
     }
     hipError_t reserve(size_t count) { return count <= n && p ? hipSuccess : alloc(count); }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); }
     void release()
     {
         if (p) (void)hipFree(p);
@@ -79,6 +82,7 @@ template <class T> struct PinBuf {
 struct Knobs {
     bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false,
          shared_slow = false;
+    uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
     static Knobs read()
     {
         Knobs k;
@@ -89,6 +93,7 @@ struct Knobs {
         k.lean = getenv("GROOT_LEAN") != nullptr;                         // the node-by-node first pass (kernels_lean.hpp) instead of the path-text one
         k.no_path = getenv("GROOT_NO_PATH_PASS") != nullptr;              // no first pass: align_kernel alone
         k.shared_slow = getenv("GROOT_TEST_SHARED_SLOW") != nullptr;      // shared reads: every read in more than one graph takes the slow path
+        if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         return k;
     }
 };
@@ -150,6 +155,8 @@ struct Slot {
     int status = GROOT_OK;
     std::string status_msg;
     groot_stage_ms ms{};
+    DevBuf<uint32_t> d_ec_slow;            // equivalence classes: the batch's slow-path reads (ec_merge_kernel), read at collect
+    PinBuf<uint32_t> h_ec;                 // [0] their number, [1] the table's fill behind this batch's merge
     const uint8_t *seq() const { return input == IN_DEVICE ? ext_seq : d_seq.p; }
     const uint64_t *off() const { return input == IN_DEVICE ? ext_off : d_off.p; }
 };
@@ -308,6 +315,16 @@ struct groot_ctx {
     DevBuf<uint32_t> sh_gpo, sh_set_graph, sh_tab_rep, sh_tab_cnt, sh_slow, sh_batch;
     DevBuf<uint64_t> sh_set_mask;
     DevBuf<unsigned long long> sh_tri, sh_stats;
+    // equivalence classes (groot_hip_ec_*, kernels_ec.hpp): the gather and insert kernels of shared reads run while either is on, and
+    // ec_merge_kernel folds each batch's distinct sets into a run-wide table; slow-path reads are folded on the host at collect
+    bool ec_on = false;
+    uint32_t ec_cap = 0, ec_epoch = 0;     // slots (a power of two) / epoch of the newest launch on the table
+    DevBuf<uint32_t> ec_claim, ec_graph, ec_fill;
+    DevBuf<uint64_t> ec_mask;
+    DevBuf<unsigned long long> ec_cnt;
+    uint64_t ec_fill_known = 0;            // the fill read back at the newest collect
+    uint64_t ec_grows = 0, ec_slow_reads = 0;
+    std::map<std::vector<uint32_t>, uint64_t> ec_host;   // the exact S(r) of slow-path reads -> reads
 };
 
 // A ctx drives four HIP streams at once -- seed stage, align + order stage, copy-in, copy-out -- beside whatever the host process
@@ -972,6 +989,110 @@ static int launch_order_stage(groot_ctx *c, Slot *s, bool update_weights)
     return GROOT_OK;
 }
 
+// ---- equivalence classes (kernels_ec.hpp) ----
+static EcTable ec_table(const groot_ctx *c)
+{
+    return EcTable{c->ec_claim.p, c->ec_graph.p, c->ec_mask.p, c->ec_cnt.p, c->ec_cap - 1};
+}
+
+// the table's buffers for cap slots, free
+static hipError_t ec_alloc(groot_ctx *c, uint32_t cap, DevBuf<uint32_t> &claim, DevBuf<uint32_t> &graph, DevBuf<uint64_t> &mask, DevBuf<unsigned long long> &cnt,
+                           hipStream_t st)
+{
+    const size_t pw = std::max<uint32_t>(c->pw_view, 1u);
+    hipError_t e = claim.alloc(cap);
+    if (e == hipSuccess) e = graph.alloc((size_t)cap * kSharedSegs);
+    if (e == hipSuccess) e = mask.alloc((size_t)cap * kSharedSegs * pw);
+    if (e == hipSuccess) e = cnt.alloc(cap);
+    if (e == hipSuccess) e = hipMemsetAsync(claim.p, 0, (size_t)cap * sizeof(uint32_t), st);
+    return e;
+}
+
+// Before a batch's merge: each batch adds at most n_reads keys, so the table must keep >= 2 x (the fill read back at the newest
+// collect + n_reads of every batch launched and not collected, this one included) slots -- else it doubles, rehashed in align-stream
+// order.  (Growth is rare -- a handful of times per run -- so the old buffers are freed behind a wait for the align stream.)
+static int ec_reserve(groot_ctx *c, Slot *s)
+{
+    uint64_t pending = s->n_reads;
+    for (Slot *x : c->inflight)
+        if (x != s && x->state == Slot::IN_FLIGHT) pending += x->n_reads;
+    const uint64_t need = 2 * (c->ec_fill_known + pending);
+    if (c->ec_cap >= need) return GROOT_OK;
+    uint64_t cap = c->ec_cap;
+    while (cap < need) cap *= 2;
+    if (cap > (1ull << 31)) return fail(c, GROOT_E_NOSPACE, "equivalence classes: the table would need %llu slots", (unsigned long long)cap);
+    DevBuf<uint32_t> claim, graph;
+    DevBuf<uint64_t> mask;
+    DevBuf<unsigned long long> cnt;
+    hipError_t e = ec_alloc(c, (uint32_t)cap, claim, graph, mask, cnt, c->astream);
+    if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "equivalence classes: growing the table to %llu slots: %s", (unsigned long long)cap, hipGetErrorString(e));
+    const EcTable from = ec_table(c), to{claim.p, graph.p, mask.p, cnt.p, (uint32_t)cap - 1};
+    hipLaunchKernelGGL(ec_rehash_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->astream,
+                       from, c->ec_cap, to, std::max<uint32_t>(c->pw_view, 1u), ++c->ec_epoch);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->astream));
+    c->ec_claim.swap(claim); c->ec_graph.swap(graph); c->ec_mask.swap(mask); c->ec_cnt.swap(cnt);
+    c->ec_cap = (uint32_t)cap;
+    c->ec_grows++;
+    return GROOT_OK;
+}
+
+// S(r) of the records trav[0..n) (one read): global path IDs, ascending, each once
+static void ec_set_of(const groot_ctx *c, const groot_trav *trav, const uint64_t *mask, size_t n, std::vector<uint32_t> &ids)
+{
+    const uint32_t pw = c->pw_view, n_paths = (uint32_t)c->h_cov_len.size();
+    ids.clear();
+    for (size_t t = 0; t < n; t++)
+        for (uint32_t w = 0; w < pw; w++)
+            for (uint64_t m = mask[t * pw + w]; m; m &= m - 1) {
+                const uint64_t id = (uint64_t)c->h_cov_gpo[trav[t].graph_id] + w * 64 + (uint32_t)__builtin_ctzll(m);
+                if (id < n_paths) ids.push_back((uint32_t)id);
+            }
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+}
+
+// At collect, while slot s still owns its records: the table's fill, and the exact S(r) of the batch's slow-path reads into ec_host.
+// refetch: the copies enqueue made are stale (the batch was redone).
+static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
+{
+    if (refetch) {
+        HIP_TRY(c, hipMemcpy(s->h_ec.p, s->d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(s->h_ec.p + 1, c->ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    const uint32_t n_slow = s->h_ec.p[0];
+    c->ec_fill_known = std::max<uint64_t>(c->ec_fill_known, s->h_ec.p[1]);
+    if (!n_slow) return GROOT_OK;
+    std::vector<uint32_t> span(2 * (size_t)n_slow);
+    HIP_TRY(c, hipMemcpy(span.data(), s->d_ec_slow.p + 1, span.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t pw = c->pw_view;
+    // few reads: their records one by one; many (GROOT_TEST_SHARED_SLOW): the range that holds them all in one copy
+    uint32_t lo = ~0u, hi = 0;
+    for (uint32_t i = 0; i < n_slow; i++) { lo = std::min(lo, span[2 * i]); hi = std::max(hi, span[2 * i + 1]); }
+    const bool whole = n_slow > 32;
+    std::vector<groot_trav> tr;
+    std::vector<uint64_t> mk;
+    if (whole) {
+        tr.resize(hi - lo); mk.resize((size_t)(hi - lo) * pw);
+        HIP_TRY(c, hipMemcpy(tr.data(), s->d_trav.p + lo, tr.size() * sizeof(groot_trav), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)lo * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    std::vector<uint32_t> ids;
+    for (uint32_t i = 0; i < n_slow; i++) {
+        const uint32_t t0 = span[2 * i], t1 = span[2 * i + 1];
+        if (!whole) {
+            tr.resize(t1 - t0); mk.resize((size_t)(t1 - t0) * pw);
+            HIP_TRY(c, hipMemcpy(tr.data(), s->d_trav.p + t0, tr.size() * sizeof(groot_trav), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)t0 * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        }
+        const size_t o = whole ? t0 - lo : 0;
+        ec_set_of(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids);
+        if (!ids.empty()) c->ec_host[ids]++;
+    }
+    c->ec_slow_reads += n_slow;
+    return GROOT_OK;
+}
+
 // sketch+seed -> schedule (compute stream) | align -> order (align stream) for the batch of slot s
 static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
 {
@@ -1012,20 +1133,28 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
         hipLaunchKernelGGL(cov_count_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->astream, ca);
         HIP_TRY(c, hipGetLastError());
     }
-    if (c->sh_on) {    // (the same: slot data and the ctx's own buffers, in align-stream order)
+    if (c->sh_on || c->ec_on) {    // (the same: slot data and the ctx's own buffers, in align-stream order)
         SharedArgs sa{};
         sa.trav = s->d_trav.p; sa.mask = s->d_mask.p; sa.ctr = s->d_ctr.p; sa.graph_path_off = c->sh_gpo.p;
         sa.set_graph = c->sh_set_graph.p; sa.set_mask = c->sh_set_mask.p; sa.tab_rep = c->sh_tab_rep.p; sa.tab_cnt = c->sh_tab_cnt.p;
         sa.slow = c->sh_slow.p; sa.batch = c->sh_batch.p; sa.tri = c->sh_tri.p; sa.stats = c->sh_stats.p;
         sa.cap = s->trav_cap; sa.pw = c->pw_view; sa.first_read_id = s->first_read_id; sa.n_paths = (uint32_t)c->h_cov_len.size();
         sa.max_segs = c->kn.shared_slow ? 1u : kSharedSegs;
+        sa.pairs = c->sh_on;
         uint32_t tab = 1;                  // this batch's part of the table: >= 2 n_reads slots
         while (tab < 2u * std::max<uint32_t>(s->n_reads, 1u)) tab <<= 1;
         sa.tab_mask = tab - 1;
         const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
         hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->astream, sa);
         hipLaunchKernelGGL(shared_insert_kernel, g, dim3(kBlock), 0, c->astream, sa);
-        hipLaunchKernelGGL(shared_slow_kernel, dim3(256), dim3(kBlock), 0, c->astream, sa);
+        if (c->sh_on) hipLaunchKernelGGL(shared_slow_kernel, dim3(256), dim3(kBlock), 0, c->astream, sa);
+        if (c->ec_on) {
+            if (int rc = ec_reserve(c, s)) return rc;
+            HIP_TRY(c, s->d_ec_slow.reserve(1 + 2 * (size_t)c->prm.max_batch_reads));
+            HIP_TRY(c, s->h_ec.reserve(2));
+            hipLaunchKernelGGL(ec_merge_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->astream, sa, ec_table(c),
+                               tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p);
+        }
         hipLaunchKernelGGL(shared_expand_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->astream, sa, tab);
         HIP_TRY(c, hipGetLastError());
     }
@@ -1209,6 +1338,10 @@ static int enqueue(groot_ctx *c, Slot *s)
         HIP_TRY(c, hipMemcpyAsync(s->h_ckpt.p, s->d_ckpt.p, ((size_t)s->copied / 256 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
         if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev_d2h, c->d2h_stream));
     }
+    if (c->ec_on) {    // (ahead of the counters: there when they are)
+        HIP_TRY(c, hipMemcpyAsync(s->h_ec.p, s->d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+        HIP_TRY(c, hipMemcpyAsync(s->h_ec.p + 1, c->ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    }
     HIP_TRY(c, hipMemcpyAsync(s->h_ctr.p, s->d_ctr.p, sizeof(DeviceCounters), hipMemcpyDeviceToHost, c->d2h_stream));
     HIP_TRY(c, hipEventRecord(s->ev_ctr, c->d2h_stream));
     s->state = Slot::IN_FLIGHT;
@@ -1309,6 +1442,9 @@ static int finish_counters(groot_ctx *c, Slot *s)
         } else h = again;
     }
     s->n_trav = s->n_reads ? h.n_trav : 0;
+    if (c->ec_on && s->n_reads) {
+        if (int rc = ec_collect(c, s, redone)) return rc;
+    }
     groot_counts &o = s->counts;
     o.received = s->n_reads;              // boss.go:194 receivedReads++ for every read
     o.mapped = h.mapped; o.multimapped = h.multimapped; o.alignments = h.alignments; o.seeds = h.seeds;
@@ -3416,28 +3552,18 @@ int groot_hip_coverage_reset(groot_ctx *c)
 // ---- shared reads (kernels_shared.hpp) -------------------------------------------------------------------------------
 static uint64_t shared_tri_size(uint64_t n_paths) { return n_paths * (n_paths + 1) / 2; }
 
-int groot_hip_shared_enable(groot_ctx *c, int on)
+// the per-batch buffers shared reads and equivalence classes both use (allocated while either is on)
+static void sh_common_release(groot_ctx *c)
 {
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "shared reads can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!on) {
-        for (auto *b : {&c->sh_gpo, &c->sh_set_graph, &c->sh_tab_rep, &c->sh_tab_cnt, &c->sh_slow, &c->sh_batch}) b->release();
-        c->sh_set_mask.release(); c->sh_tri.release(); c->sh_stats.release();
-        c->sh_on = false;
-        return GROOT_OK;
-    }
-    if (c->sh_on) return GROOT_OK;
-    const uint64_t n_paths = c->h_cov_len.size(), tri = shared_tri_size(n_paths);
-    if (tri * sizeof(uint64_t) > GROOT_SHARED_MAX_BYTES)
-        return fail(c, GROOT_E_UNSUPPORTED, "shared reads: %llu paths need a %llu MiB pair table, above the bound of %llu MiB", (unsigned long long)n_paths,
-                    (unsigned long long)(tri * sizeof(uint64_t) >> 20), (unsigned long long)(GROOT_SHARED_MAX_BYTES >> 20));
+    for (auto *b : {&c->sh_gpo, &c->sh_set_graph, &c->sh_tab_rep, &c->sh_tab_cnt, &c->sh_slow, &c->sh_batch}) b->release();
+    c->sh_set_mask.release(); c->sh_stats.release();
+}
+
+static hipError_t sh_common_alloc(groot_ctx *c)
+{
+    if (c->sh_on || c->ec_on) return hipSuccess;
     const uint32_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-    uint64_t tab = 1;
-    while (tab < 2ull * R) tab <<= 1;
-    if (tab > (1ull << 31)) return fail(c, GROOT_E_UNSUPPORTED, "shared reads: max_batch_reads=%u is above 2^30", R);
-    c->sh_tab_cap = (uint32_t)tab;
-    auto undo = [&](int rc) { groot_hip_shared_enable(c, 0); return rc; };
+    const uint64_t tab = c->sh_tab_cap;
     hipError_t e = upload(c->sh_gpo, c->h_cov_gpo.data(), c->h_cov_gpo.size());
     if (e == hipSuccess) e = c->sh_set_graph.alloc((size_t)R * kSharedSegs);
     if (e == hipSuccess) e = c->sh_set_mask.alloc((size_t)R * kSharedSegs * std::max<uint32_t>(c->pw_view, 1u));
@@ -3445,11 +3571,45 @@ int groot_hip_shared_enable(groot_ctx *c, int on)
     if (e == hipSuccess) e = c->sh_tab_cnt.alloc(tab);
     if (e == hipSuccess) e = c->sh_slow.alloc(R);
     if (e == hipSuccess) e = c->sh_batch.alloc(3);
-    if (e == hipSuccess) e = c->sh_tri.alloc(tri);
     if (e == hipSuccess) e = c->sh_stats.alloc(3);
     if (e == hipSuccess) e = hipMemset(c->sh_tab_rep.p, 0xFF, tab * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(c->sh_tab_cnt.p, 0, tab * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(c->sh_batch.p, 0, 3 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, 3 * sizeof(unsigned long long));
+    return e;
+}
+
+static int sh_table_size(groot_ctx *c, const char *what)
+{
+    const uint32_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    uint64_t tab = 1;
+    while (tab < 2ull * R) tab <<= 1;
+    if (tab > (1ull << 31)) return fail(c, GROOT_E_UNSUPPORTED, "%s: max_batch_reads=%u is above 2^30", what, R);
+    c->sh_tab_cap = (uint32_t)tab;
+    return GROOT_OK;
+}
+
+int groot_hip_shared_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "shared reads can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!on) {
+        c->sh_tri.release();
+        c->sh_on = false;
+        if (!c->ec_on) sh_common_release(c);
+        return GROOT_OK;
+    }
+    if (c->sh_on) return GROOT_OK;
+    const uint64_t n_paths = c->h_cov_len.size(), tri = shared_tri_size(n_paths);
+    if (tri * sizeof(uint64_t) > GROOT_SHARED_MAX_BYTES)
+        return fail(c, GROOT_E_UNSUPPORTED, "shared reads: %llu paths need a %llu MiB pair table, above the bound of %llu MiB", (unsigned long long)n_paths,
+                    (unsigned long long)(tri * sizeof(uint64_t) >> 20), (unsigned long long)(GROOT_SHARED_MAX_BYTES >> 20));
+    if (!c->ec_on)
+        if (int rc = sh_table_size(c, "shared reads")) return rc;
+    auto undo = [&](int rc) { c->sh_on = true; groot_hip_shared_enable(c, 0); return rc; };
+    hipError_t e = sh_common_alloc(c);
+    if (e == hipSuccess) e = c->sh_tri.alloc(tri);
     if (e == hipSuccess) e = hipMemset(c->sh_tri.p, 0, std::max<uint64_t>(tri, 1) * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, 3 * sizeof(unsigned long long));
     if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "shared reads: %s", hipGetErrorString(e)));
@@ -3496,6 +3656,138 @@ int groot_hip_shared_reset(groot_ctx *c)
     if (int rc = drain(c)) return rc;
     HIP_TRY(c, hipMemset(c->sh_tri.p, 0, std::max<uint64_t>(shared_tri_size(c->h_cov_len.size()), 1) * sizeof(unsigned long long)));
     HIP_TRY(c, hipMemset(c->sh_stats.p, 0, 3 * sizeof(unsigned long long)));
+    return GROOT_OK;
+}
+
+// ---- equivalence classes (kernels_ec.hpp) ---------------------------------------------------------------------------
+int groot_hip_ec_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "equivalence classes can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!on) {
+        for (auto *b : {&c->ec_claim, &c->ec_graph, &c->ec_fill}) b->release();
+        c->ec_mask.release(); c->ec_cnt.release();
+        c->ec_host.clear();
+        c->ec_on = false;
+        c->ec_cap = 0;
+        if (!c->sh_on) sh_common_release(c);
+        return GROOT_OK;
+    }
+    if (c->ec_on) return GROOT_OK;
+    if (!c->sh_on)
+        if (int rc = sh_table_size(c, "equivalence classes")) return rc;
+    uint32_t cap = 1;
+    while (cap < (c->kn.ec_slots ? std::max<uint32_t>(c->kn.ec_slots, 2u) : (1u << 16))) cap <<= 1;
+    auto undo = [&](int rc) { c->ec_on = true; groot_hip_ec_enable(c, 0); return rc; };
+    hipError_t e = sh_common_alloc(c);
+    if (e == hipSuccess) e = ec_alloc(c, cap, c->ec_claim, c->ec_graph, c->ec_mask, c->ec_cnt, c->astream);
+    if (e == hipSuccess) e = c->ec_fill.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(c->ec_fill.p, 0, sizeof(uint32_t), c->astream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->astream);
+    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "equivalence classes: %s", hipGetErrorString(e)));
+    c->ec_cap = cap;
+    c->ec_fill_known = c->ec_grows = c->ec_slow_reads = 0;
+    c->ec_host.clear();
+    c->ec_on = true;
+    return GROOT_OK;
+}
+
+// the device table and the host map merged: S -> reads, in canonical order (lexicographic on the ascending ID lists)
+static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &out)
+{
+    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo and their slow-path reads)
+    uint32_t fill = 0;
+    HIP_TRY(c, hipMemcpy(&fill, c->ec_fill.p, sizeof fill, hipMemcpyDeviceToHost));
+    out = c->ec_host;
+    if (!fill) return GROOT_OK;
+    const uint32_t pw = std::max<uint32_t>(c->pw_view, 1u);
+    DevBuf<uint32_t> g, n;
+    DevBuf<uint64_t> m;
+    DevBuf<unsigned long long> cnt;
+    HIP_TRY(c, g.alloc((size_t)fill * kSharedSegs));
+    HIP_TRY(c, m.alloc((size_t)fill * kSharedSegs * pw));
+    HIP_TRY(c, cnt.alloc(fill));
+    HIP_TRY(c, n.alloc(1));
+    HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->astream));
+    hipLaunchKernelGGL(ec_export_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->astream,
+                       ec_table(c), c->ec_cap, pw, g.p, m.p, cnt.p, n.p, fill);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->astream));
+    uint32_t got = 0;
+    HIP_TRY(c, hipMemcpy(&got, n.p, sizeof got, hipMemcpyDeviceToHost));
+    if (got != fill) return fail(c, GROOT_E_DEVICE, "equivalence classes: %u keys in a table that counted %u", got, fill);
+    std::vector<uint32_t> hg((size_t)fill * kSharedSegs);
+    std::vector<uint64_t> hm((size_t)fill * kSharedSegs * pw), hc(fill);
+    HIP_TRY(c, hipMemcpy(hg.data(), g.p, hg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hm.data(), m.p, hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hc.data(), cnt.p, hc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::vector<groot_trav> tr;
+    std::vector<uint64_t> mk;
+    std::vector<uint32_t> ids;
+    for (uint32_t i = 0; i < fill; i++) {
+        // a key = one pseudo-record per segment: (graph, OR of its path sets)
+        tr.clear(); mk.clear();
+        for (uint32_t k = 0; k < kSharedSegs && hg[(size_t)i * kSharedSegs + k] != kSharedEmpty; k++) {
+            groot_trav t{};
+            t.graph_id = hg[(size_t)i * kSharedSegs + k];
+            tr.push_back(t);
+            for (uint32_t w = 0; w < pw; w++) mk.push_back(hm[((size_t)i * kSharedSegs + k) * pw + w]);
+        }
+        ec_set_of(c, tr.data(), mk.data(), tr.size(), ids);
+        if (!ids.empty() && hc[i]) out[ids] += hc[i];
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_ec_export(groot_ctx *c, uint64_t *off, uint32_t *ids, uint64_t *count, uint64_t cap_ec, uint64_t cap_ids, uint64_t *n_ec, uint64_t *n_ids)
+{
+    if (!c || !n_ec || !n_ids || (cap_ec && (!off || !count)) || (cap_ids && !ids)) return GROOT_E_INVALID;
+    if (!c->ec_on) return fail(c, GROOT_E_STATE, "equivalence classes are not enabled (groot_hip_ec_enable)");
+    std::map<std::vector<uint32_t>, uint64_t> m;
+    if (int rc = ec_gather(c, m)) return rc;
+    uint64_t ni = 0;
+    for (const auto &kv : m) ni += kv.first.size();
+    *n_ec = m.size();
+    *n_ids = ni;
+    if (!cap_ec && !cap_ids) return GROOT_OK;
+    if (cap_ec < m.size() || cap_ids < ni)
+        return fail(c, GROOT_E_NOSPACE, "equivalence classes: room for %llu classes / %llu IDs, %llu / %llu needed", (unsigned long long)cap_ec,
+                    (unsigned long long)cap_ids, (unsigned long long)m.size(), (unsigned long long)ni);
+    uint64_t e = 0, at = 0;
+    off[0] = 0;
+    for (const auto &kv : m) {
+        for (uint32_t x : kv.first) ids[at++] = x;
+        count[e] = kv.second;
+        off[++e] = at;
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_ec_stats(groot_ctx *c, uint64_t *reads, uint64_t *distinct, uint64_t *slow_reads, uint64_t *grows)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ec_on) return fail(c, GROOT_E_STATE, "equivalence classes are not enabled (groot_hip_ec_enable)");
+    std::map<std::vector<uint32_t>, uint64_t> m;
+    if (int rc = ec_gather(c, m)) return rc;
+    uint64_t r = 0;
+    for (const auto &kv : m) r += kv.second;
+    if (reads) *reads = r;
+    if (distinct) *distinct = m.size();
+    if (slow_reads) *slow_reads = c->ec_slow_reads;
+    if (grows) *grows = c->ec_grows;
+    return GROOT_OK;
+}
+
+int groot_hip_ec_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ec_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemset(c->ec_claim.p, 0, (size_t)c->ec_cap * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(c->ec_fill.p, 0, sizeof(uint32_t)));
+    c->ec_fill_known = c->ec_grows = c->ec_slow_reads = 0;
+    c->ec_host.clear();
     return GROOT_OK;
 }
 

@@ -15,6 +15,8 @@
 //                          Different sets with one hash probe on: a collision costs a probe, never a wrong count.
 //   shared_slow_kernel     one wave per listed read: the exact set from its traversals, 1 added to every pair (a, b), a <= b.
 //   shared_expand_kernel   one thread per table slot: count added to every pair of the owner's set, then the slot is cleared.
+// With equivalence classes on (kernels_ec.hpp) gather and insert run too, and ec_merge_kernel between insert and expand; with shared
+// reads off, expand only clears the table.
 // So the triangle sees one u64 atomic per (distinct set, pair) and per (slow read, pair), not one per (read, pair).
 // Every kernel reads the pass's status word first: a pass collect redoes, or a batch that fails with NOSPACE, is not counted.
 #pragma once
@@ -42,6 +44,7 @@ struct SharedArgs {
     unsigned long long *stats;     // [3] totals of `batch` since enable / reset
     uint32_t cap, pw, first_read_id, n_paths, tab_mask;
     uint32_t max_segs;             // graphs per read on the fast path: kSharedSegs (1 under GROOT_TEST_SHARED_SLOW)
+    uint32_t pairs;                // shared reads are on: expand adds to the triangle (else it only clears the table: equivalence classes)
 };
 
 __device__ __forceinline__ bool shared_live(const SharedArgs &a) { return !(a.ctr->flags & kCovSkipFlags); }
@@ -210,7 +213,7 @@ __global__ __launch_bounds__(kBlock) void shared_expand_kernel(SharedArgs a, uin
         const unsigned long long c = a.tab_cnt[slot];
         const uint32_t *sg = a.set_graph + (size_t)r * kSharedSegs;
         const uint64_t *m = a.set_mask + (size_t)r * kSharedSegs * a.pw;
-        for (uint32_t i = 0; i < kSharedSegs && sg[i] != kSharedEmpty; i++) {
+        for (uint32_t i = 0; a.pairs && i < kSharedSegs && sg[i] != kSharedEmpty; i++) {
             const uint64_t gi = a.graph_path_off[sg[i]];
             for (uint32_t wa = 0; wa < a.pw; wa++) {
                 for (uint64_t ma = m[i * a.pw + wa]; ma; ma &= ma - 1) {

@@ -9,6 +9,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <string>
@@ -204,8 +205,9 @@ int write_shared(const char *const *names, const uint32_t *name_len, const std::
 } // namespace
 
 // `groot report` on a BAM; with shared_out, also the shared-reads file: S(read) = the references with a counted record of that QNAME
+// read_sets: instead of any output, the (read << 32 | reference) pairs of the counted records, sorted and unique, and the header's names
 static int report_bam(const char *bam_path, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported, const char *shared_out,
-                      uint64_t *n_lines)
+                      uint64_t *n_lines, std::vector<uint64_t> *read_sets = nullptr, std::vector<std::string> *names_out = nullptr)
 {
     if (int rc = check_cutoff(cov_cutoff, low_cov)) return rc;
     BgzfIn in;
@@ -233,7 +235,7 @@ static int report_bam(const char *bam_path, double cov_cutoff, int low_cov, cons
     std::vector<uint8_t> rec;
     // shared reads: reads are numbered by QNAME in order of first appearance (the reference interleaves the records of several
     // reads, so adjacency does not delimit a read); every counted record adds (read, reference)
-    const bool shared = shared_out != nullptr;
+    const bool shared = shared_out != nullptr || read_sets != nullptr;
     std::unordered_map<std::string, uint32_t> read_of;
     std::vector<uint64_t> read_ref;
     std::string qname;
@@ -271,6 +273,13 @@ static int report_bam(const char *bam_path, double cov_cutoff, int low_cov, cons
         uint64_t end = (uint64_t)pos + ref_len;
         if (end > pl.size() - 1) end = pl.size() - 1;
         for (uint64_t i = (uint64_t)pos; i <= end; i++) pl[i]++;
+    }
+    if (read_sets) {
+        std::sort(read_ref.begin(), read_ref.end());
+        read_ref.erase(std::unique(read_ref.begin(), read_ref.end()), read_ref.end());
+        *read_sets = std::move(read_ref);
+        *names_out = std::move(names);
+        return GROOT_OK;
     }
     std::vector<const char *> name_ptr(n_ref);
     for (uint32_t r = 0; r < n_ref; r++) name_ptr[r] = names[r].c_str();
@@ -382,4 +391,138 @@ extern "C" int groot_host_shared_from_counts(const groot_index_view *ix, const u
         name_len[p] = ix->path_name_off[p + 1] - ix->path_name_off[p];
     }
     return write_shared(name_ptr.data(), name_len.data(), reported, pairs, out_path, n_lines);
+}
+
+// ---- abundance: EM over equivalence classes ---------------------------------------------------------------------------------
+// src/em/em.go NewEM / Run / Return (lines 29-158), restated in double precision without FMA contraction (the library is built
+// without -march), over ECs in canonical order: the reference iterates a Go map, so its sums are not reproducible.
+extern "C" int groot_host_em(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t min_iter,
+                             uint32_t max_iter, double *alpha_out, uint32_t *iterations)
+{
+    if ((n_ec && (!off || !count)) || (n_paths && !alpha_out)) return set_error(GROOT_E_INVALID, "null argument");
+    if (max_iter < min_iter)                                                                     // em.go:31-33
+        return set_error(GROOT_E_INVALID, "number of EM iterations (%u) must be greater than minimum iterations (%u)", max_iter, min_iter);
+    if (max_iter < 1) return set_error(GROOT_E_INVALID, "no EM iterations were ran");           // em.go:153-155
+    for (uint64_t e = 0; e < n_ec; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
+        for (uint64_t i = off[e]; i < off[e + 1]; i++)
+            if (ids[i] >= n_paths) return set_error(GROOT_E_INVALID, "EC %llu holds path %u of %u", (unsigned long long)e, ids[i], n_paths);
+    }
+    const double tolerance = std::nextafter(1.0, 2.0) - 1.0;
+    const double alpha_limit = 1e-7, alpha_change = 1e-2, alpha_change_limit = 1e-2;
+    std::vector<double> alpha(n_paths, 1.0 / (double)n_paths), next(n_paths, 0.0);
+    bool final_round = false;
+    uint32_t it = 0;
+    for (it = 0; it < max_iter; it++) {
+        for (uint64_t e = 0; e < n_ec; e++) {
+            const double c = (double)count[e];
+            if (c == 0) continue;
+            double denom = 0.0;
+            for (uint64_t i = off[e]; i < off[e + 1]; i++) denom += alpha[ids[i]];
+            if (denom < tolerance) continue;
+            const double norm = c / denom;
+            for (uint64_t i = off[e]; i < off[e + 1]; i++) next[ids[i]] += alpha[ids[i]] * norm;
+        }
+        uint32_t changed = 0;
+        for (uint32_t p = 0; p < n_paths; p++) {
+            if (next[p] > alpha_change_limit && std::fabs(next[p] - alpha[p]) / next[p] > alpha_change) changed++;
+            alpha[p] = next[p];
+            next[p] = 0.0;
+        }
+        const bool stop = changed == 0 && it > min_iter;
+        if (final_round) break;
+        if (stop) {                        // one more round after this one, from alpha with its tiny values zeroed
+            final_round = true;
+            for (uint32_t p = 0; p < n_paths; p++)
+                if (alpha[p] < alpha_limit / 10.0) alpha[p] = 0.0;
+        }
+    }
+    std::copy(alpha.begin(), alpha.end(), alpha_out);
+    if (iterations) *iterations = it;
+    return GROOT_OK;
+}
+
+namespace {
+
+using EcMap = std::map<std::vector<uint32_t>, uint64_t>;   // canonical order
+
+// the abundance file of the ECs in m (paths [0, n_paths), names as the report prints them)
+int write_abundance(uint32_t n_paths, const char *const *names, const uint32_t *name_len, const EcMap &m, double min_reads, const char *out_path,
+                    uint64_t *n_lines, uint32_t *iterations)
+{
+    std::vector<uint64_t> off{0}, count;
+    std::vector<uint32_t> ids;
+    std::vector<uint64_t> reads(n_paths, 0);
+    for (const auto &kv : m) {
+        for (uint32_t p : kv.first) { ids.push_back(p); reads[p] += kv.second; }
+        off.push_back(ids.size());
+        count.push_back(kv.second);
+    }
+    std::vector<double> alpha(n_paths);
+    uint32_t it = 0;
+    if (int rc = groot_host_em(n_paths, m.size(), off.data(), ids.data(), count.data(), GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER, alpha.data(), &it)) return rc;
+    if (iterations) *iterations = it;
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
+    double sum = 0.0;
+    for (uint32_t p = 0; p < n_paths; p++) sum += alpha[p];
+    uint64_t lines = 0;
+    for (uint32_t p = 0; p < n_paths && !m.empty(); p++) {
+        if (!(alpha[p] >= min_reads)) continue;
+        const char *nm = names[p];
+        size_t nl = name_len ? name_len[p] : strlen(nm);
+        if (nl && nm[0] == '*') { nm++; nl--; }
+        fprintf(out, "%.*s\t%llu\t%.2f\t%.6f\n", (int)nl, nm, (unsigned long long)reads[p], alpha[p], sum > 0 ? alpha[p] / sum : 0.0);
+        lines++;
+    }
+    if (out_path) fclose(out); else fflush(out);
+    if (n_lines) *n_lines = lines;
+    return GROOT_OK;
+}
+
+} // namespace
+
+extern "C" int groot_host_abundance_from_ecs(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                             double min_reads, const char *out_path, uint64_t *n_lines, uint32_t *iterations)
+{
+    if (!ix || (n_ec && (!off || !count))) return set_error(GROOT_E_INVALID, "null argument");
+    const uint32_t n = ix->n_paths;
+    EcMap m;
+    std::vector<uint32_t> v;
+    for (uint64_t e = 0; e < n_ec; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
+        v.assign(ids + off[e], ids + off[e + 1]);
+        for (uint32_t p : v)
+            if (p >= n) return set_error(GROOT_E_INVALID, "EC %llu holds path %u of %u", (unsigned long long)e, p, n);
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        if (!v.empty() && count[e]) m[v] += count[e];          // (the lists of several contexts: repeats summed)
+    }
+    std::vector<const char *> name_ptr(n);
+    std::vector<uint32_t> name_len(n);
+    for (uint32_t p = 0; p < n; p++) {
+        name_ptr[p] = ix->path_names + ix->path_name_off[p];
+        name_len[p] = ix->path_name_off[p + 1] - ix->path_name_off[p];
+    }
+    return write_abundance(n, name_ptr.data(), name_len.data(), m, min_reads, out_path, n_lines, iterations);
+}
+
+extern "C" int groot_host_report_abundance(const char *bam_path, double min_reads, const char *out_path, uint64_t *n_lines)
+{
+    std::vector<uint64_t> read_ref;
+    std::vector<std::string> names;
+    if (int rc = report_bam(bam_path, 0.97, 0, nullptr, nullptr, nullptr, nullptr, &read_ref, &names)) return rc;
+    // S(read): the references of one QNAME's records (read_ref is sorted by read, then reference)
+    EcMap m;
+    std::vector<uint32_t> v;
+    for (size_t i = 0; i < read_ref.size();) {
+        size_t j = i;
+        v.clear();
+        while (j < read_ref.size() && read_ref[j] >> 32 == read_ref[i] >> 32) v.push_back((uint32_t)read_ref[j++]);
+        m[v]++;
+        i = j;
+    }
+    std::vector<const char *> name_ptr(names.size());
+    for (size_t r = 0; r < names.size(); r++) name_ptr[r] = names[r].c_str();
+    return write_abundance((uint32_t)names.size(), name_ptr.data(), nullptr, m, min_reads, out_path, n_lines, nullptr);
 }

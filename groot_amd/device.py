@@ -384,6 +384,36 @@ class Aligner:
     def shared_reset(self):
         self._check(lib().groot_hip_shared_reset(self._h))
 
+    # ---- equivalence classes (groot_hip_ec_*) -----------------------------------------------------
+    def ec_enable(self, on=True):
+        """count the reads of every distinct S(r) (equivalence class) from now on (only while nothing is in flight)"""
+        self._check(lib().groot_hip_ec_enable(self._h, C.c_int(1 if on else 0)))
+
+    def ecs(self):
+        """(off uint64[n_ec + 1], ids uint32, count uint64[n_ec]) of every EC since enable / reset in canonical order (lexicographic
+        on the ascending path-ID lists), EC i = ids[off[i]:off[i + 1]]: the input of host.abundance_from_ecs.  Waits for everything
+        in flight."""
+        ne, ni = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().groot_hip_ec_export(self._h, None, None, None, C.c_uint64(0), C.c_uint64(0), C.byref(ne), C.byref(ni)))
+        off = np.zeros(ne.value + 1, dtype=np.uint64)
+        ids = np.zeros(ni.value, dtype=np.uint32)
+        cnt = np.zeros(ne.value, dtype=np.uint64)
+        if ne.value:
+            me, mi = C.c_uint64(0), C.c_uint64(0)
+            self._check(lib().groot_hip_ec_export(self._h, _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32), _ffi.as_ptr(cnt, C.c_uint64),
+                                                  C.c_uint64(ne.value), C.c_uint64(ni.value), C.byref(me), C.byref(mi)))
+            assert (me.value, mi.value) == (ne.value, ni.value)
+        return off, ids, cnt
+
+    def ec_stats(self):
+        """{"reads", "distinct", "slow_reads", "grows"} since enable / reset (groot_hip_ec_stats)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._check(lib().groot_hip_ec_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("reads", "distinct", "slow_reads", "grows"), (x.value for x in v)))
+
+    def ec_reset(self):
+        self._check(lib().groot_hip_ec_reset(self._h))
+
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):
         seq = np.ascontiguousarray(seq_concat, dtype=np.uint8)

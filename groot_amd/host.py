@@ -461,6 +461,75 @@ def report_shared(bam_path, cov_cutoff=0.97, low_cov=False, report_out=None, sha
     return [(r[0], int(r[1]), int(r[2]), r[3]) for r in rep], sh
 
 
+EM_MIN_ITER, EM_MAX_ITER = 50, 10000        # GROOT_EM_MIN_ITER / GROOT_EM_MAX_ITER
+
+
+def em(n_paths, off, ids, count, min_iter=EM_MIN_ITER, max_iter=EM_MAX_ITER):
+    """groot_host_em: src/em/em.go over the ECs (CSR off / ids / count) in the order given -> (alpha float64[n_paths], iterations)"""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    if len(off) != len(count) + 1:
+        raise ValueError("off must have one entry more than count")
+    alpha = np.zeros(n_paths, dtype=np.float64)
+    it = C.c_uint32(0)
+    _check(lib().groot_host_em(C.c_uint32(n_paths), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                               _ffi.as_ptr(count, C.c_uint64), C.c_uint32(min_iter), C.c_uint32(max_iter), _ffi.as_ptr(alpha, C.c_double),
+                               C.byref(it)))
+    return alpha, it.value
+
+
+def _abundance_rows(path):
+    rows = [ln.rstrip("\n").split("\t") for ln in open(path)]
+    return [(r[0], int(r[1]), float(r[2]), float(r[3])) for r in rows]
+
+
+def abundance_from_ecs(index, off, ids, count, min_reads=1.0, out_path=None):
+    """the abundance lines (groot_host_abundance_from_ecs) of ECs as device.Aligner.ecs() gives them (any order, repeats summed):
+    [(name, reads, em_reads, fraction)]"""
+    import tempfile
+
+    v = index.view
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    if len(off) != len(count) + 1:
+        raise ValueError("off must have one entry more than count")
+    tmp = None
+    if out_path is None:
+        fd, tmp = tempfile.mkstemp(suffix=".abundance")
+        os.close(fd)
+    n = C.c_uint64(0)
+    try:
+        _check(lib().groot_host_abundance_from_ecs(C.byref(v), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                                   _ffi.as_ptr(count, C.c_uint64), C.c_double(min_reads), (out_path or tmp).encode(), C.byref(n), None))
+        rows = _abundance_rows(out_path or tmp)
+    finally:
+        if tmp:
+            os.unlink(tmp)
+    assert len(rows) == n.value
+    return rows
+
+
+def report_abundance(bam_path, min_reads=1.0, out_path=None):
+    """the abundance lines from a BAM (groot_host_report_abundance), a read being one QNAME: [(name, reads, em_reads, fraction)]"""
+    import tempfile
+
+    tmp = None
+    if out_path is None:
+        fd, tmp = tempfile.mkstemp(suffix=".abundance")
+        os.close(fd)
+    n = C.c_uint64(0)
+    try:
+        _check(lib().groot_host_report_abundance(bam_path.encode(), C.c_double(min_reads), (out_path or tmp).encode(), C.byref(n)))
+        rows = _abundance_rows(out_path or tmp)
+    finally:
+        if tmp:
+            os.unlink(tmp)
+    assert len(rows) == n.value
+    return rows
+
+
 def save_gfa(index, graph, kmer_freq, path_kept, node_removed, total_kmers, file_name, timestamp=None):
     """GrootGraph.SaveGraphAsGFA (src/graph/graphio.go:19-112); returns True if a file was written"""
     kf = np.ascontiguousarray(kmer_freq, dtype=np.float64)

@@ -321,6 +321,28 @@ int groot_hip_shared_reset(groot_ctx *ctx);
  * reads whose records lie in more than 4 graphs (counted by the slower wave-per-read kernel).  GROOT_E_STATE when off. */
 int groot_hip_shared_stats(groot_ctx *ctx, uint64_t *reads, uint64_t *distinct_sets, uint64_t *slow_reads);
 
+/* ---- equivalence classes -------------------------------------------------------------------------------------------
+ * The input of an abundance estimate by EM (groot_host_em).  S(r) is exactly the S(r) of shared reads above: the set of global paths
+ * (BAM header order) that carry at least one record of input read r -- every traversal, both strands, primary and secondary.  Reads
+ * with no record are in no class.  An equivalence class (EC) is a distinct non-empty S(r), written as its global path IDs in
+ * ascending order; count(EC) is the number of reads r with that S(r).  Canonical EC order: lexicographic on the ascending ID lists.
+ * Accumulated over the run (kernels_ec.hpp): each batch's distinct sets are folded into a run-wide table in HBM that grows as needed;
+ * reads in more than 4 graphs are folded in exactly on the host when their batch is collected.  Counted once exactly as coverage is.
+ * Off by default: then nothing is launched and no device memory is taken. */
+/* Switch on (an empty table; the per-read buffers of shared reads, shared with it when both are on) or off (freed).  Only while
+ * nothing is in flight. */
+int groot_hip_ec_enable(groot_ctx *ctx, int on);
+/* The ECs since enable / reset in canonical order, as CSR: EC i is ids[off[i] .. off[i+1]), count[i] its reads.  *n_ec / *n_ids =
+ * their sizes; call with cap_ec = cap_ids = 0 to get them, then with off[cap_ec + 1], ids[cap_ids], count[cap_ec] (GROOT_E_NOSPACE
+ * when they are too small).  Waits for everything in flight (redoing what needs a redo).  GROOT_E_STATE when off. */
+int groot_hip_ec_export(groot_ctx *ctx, uint64_t *off, uint32_t *ids, uint64_t *count, uint64_t cap_ec, uint64_t cap_ids, uint64_t *n_ec,
+                        uint64_t *n_ids);
+/* Empties the table (after waiting for everything in flight).  No-op when off. */
+int groot_hip_ec_reset(groot_ctx *ctx);
+/* Since enable / reset: reads in an EC (the sum of the counts), distinct ECs, reads folded in on the host (in more than 4 graphs, or
+ * in more than one under GROOT_TEST_SHARED_SLOW), times the table grew.  Waits for everything in flight.  GROOT_E_STATE when off. */
+int groot_hip_ec_stats(groot_ctx *ctx, uint64_t *reads, uint64_t *distinct, uint64_t *slow_reads, uint64_t *grows);
+
 /* Fine-grained mirror of Sequence.RunMinHash(k, s, false, nil) (seqio.go:40-68) for a batch of
  * sequences in host memory: out[i*s .. (i+1)*s) = KHF sketch of sequence i.  Only while nothing is in flight. */
 int groot_hip_sketch(groot_ctx *ctx, const uint8_t *seq_concat, const uint64_t *seq_off, uint32_t n, uint64_t *out);

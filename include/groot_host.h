@@ -280,6 +280,30 @@ int groot_host_shared_from_counts(const groot_index_view *idx, const uint64_t *r
 int groot_host_report_shared(const char *bam_path, double cov_cutoff, int low_cov, const char *report_out, const char *shared_out,
                              uint64_t *n_reported, uint64_t *n_lines);
 
+/* ---- abundance by EM over equivalence classes ----------------------------------------------------------------------
+ * ECs as defined at groot_hip_ec_enable in groot_hip.h (distinct non-empty S(r), ascending path IDs, in CSR form: EC i is
+ * ids[off[i] .. off[i+1]) with count[i] reads).  groot_host_em restates src/em/em.go NewEM / Run / Return (lines 29-158) in double
+ * precision over n_paths paths, visiting the ECs in the order given (canonical order: lexicographic on the ID lists; the reference
+ * iterates a Go map): alpha starts at 1/n_paths; an EC with count 0, or whose denominator (the sum of alpha over it) is below 2^-52,
+ * is skipped; next[p] += alpha[p] * (count / denom); a path has changed when next > 1e-2 and |next - alpha| / next > 1e-2; when no path
+ * changed and the iteration index is above min_iter, alpha below 1e-7 / 10 is zeroed and one more round runs.  alpha_out[n_paths] =
+ * the estimated reads of each path; *iterations = the rounds run (max_iter when it never settled).  GROOT_E_INVALID when
+ * max_iter < min_iter or max_iter = 0 (the reference's errors), or an ID is >= n_paths. */
+#define GROOT_EM_MIN_ITER 50      /* the reference's defaults (1_pipeline_test.go:49-54) */
+#define GROOT_EM_MAX_ITER 10000
+int groot_host_em(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t min_iter,
+                  uint32_t max_iter, double *alpha_out, uint32_t *iterations);
+/* The abundance file: "name \t reads \t em_reads \t fraction" for every path with alpha >= min_reads, in BAM header order; name as the
+ * report prints it ('*' stripped), reads = the distinct reads with a record on the path (the diagonal of shared reads), em_reads =
+ * alpha ("%.2f"), fraction = alpha / sum(alpha) ("%.6f").  Empty when there are no ECs.  The ECs come in any order, IDs in any order,
+ * repeats summed (the lists of several contexts or GPUs); they are canonicalised, then groot_host_em runs with GROOT_EM_MIN_ITER /
+ * GROOT_EM_MAX_ITER.  out_path NULL = stdout; *n_lines = lines written; iterations (may be NULL) = the EM's rounds. */
+int groot_host_abundance_from_ecs(const groot_index_view *idx, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                  double min_reads, const char *out_path, uint64_t *n_lines, uint32_t *iterations);
+/* The same file from a BAM, a read being one QNAME (its records grouped wherever they lie, as groot_host_report_shared does): byte for
+ * byte what the device path writes whenever read names are unique. */
+int groot_host_report_abundance(const char *bam_path, double min_reads, const char *out_path, uint64_t *n_lines);
+
 #ifdef __cplusplus
 }
 #endif
