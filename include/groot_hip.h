@@ -290,7 +290,8 @@ int groot_hip_attempts_read(groot_ctx *ctx, uint32_t *out, uint64_t n_elems);
  * covering [Pos, min(Pos + M, path_len - 1)] -- both ends included, reporting.go:104-127.  groot_host_report_coverage turns
  * them into the report.  Off by default: then nothing is launched and no device memory is taken.
  * A batch is counted once: a pass the ctx redoes at collect (groot_hip_redo_status) counts in its redo only, and a batch that
- * fails with GROOT_E_NOSPACE (a read longer than max_read_len, more than 65535 traversals for one read) is not counted. */
+ * fails with GROOT_E_NOSPACE (a read longer than max_read_len, more than 65535 traversals for one read) is not counted.  A batch
+ * that fails with GROOT_E_SHORT_READ or GROOT_E_REVCOMP is counted whole: the records of its other reads, which remain readable. */
 /* Switch on (zeroed counters; 16 bytes per path base of HBM) or off (freed).  Only while nothing is in flight. */
 int groot_hip_coverage_enable(groot_ctx *ctx, int on);
 /* records[n_paths], depth[sum of path_len] with path p at sum_{q<p} path_len[q].  Waits for everything in flight (redoing what
@@ -306,7 +307,8 @@ int groot_hip_coverage_reset(groot_ctx *ctx);
  * shared[a][b] = |{r : a in S(r) and b in S(r)}|; shared[a][a] is the number of distinct reads on a.  A read is one input read of
  * the batch (one FASTQ record); groot_host_report_shared, which works from a BAM, groups records by QNAME instead, so the two
  * agree whenever read names are unique.  Accumulated on the device batch by batch behind the order stage (kernels_shared.hpp);
- * counted once exactly as coverage is (a redone pass counts in its redo only, a batch that fails with GROOT_E_NOSPACE not at all).
+ * counted once exactly as coverage is (a redone pass counts in its redo only, a batch that fails with GROOT_E_NOSPACE not at all, one
+ * that fails with GROOT_E_SHORT_READ or GROOT_E_REVCOMP whole: the records of its other reads).
  * Off by default: then nothing is launched and no device memory is taken. */
 #define GROOT_SHARED_MAX_BYTES (1ull << 30)   /* bound of the pair table: n_paths (n_paths + 1) / 2 u64 counters */
 /* Switch on (zeroed counters: the pair table, plus ~(36 + 32 path_words) bytes per read of max_batch_reads) or off (freed).  Only
@@ -327,7 +329,8 @@ int groot_hip_shared_stats(groot_ctx *ctx, uint64_t *reads, uint64_t *distinct_s
  * with no record are in no class.  An equivalence class (EC) is a distinct non-empty S(r), written as its global path IDs in
  * ascending order; count(EC) is the number of reads r with that S(r).  Canonical EC order: lexicographic on the ascending ID lists.
  * Accumulated over the run (kernels_ec.hpp): each batch's distinct sets are folded into a run-wide table in HBM that grows as needed;
- * reads in more than 4 graphs are folded in exactly on the host when their batch is collected.  Counted once exactly as coverage is.
+ * reads in more than 4 graphs are folded in exactly on the host when their batch is collected.  Counted once exactly as coverage is:
+ * a batch that fails with GROOT_E_NOSPACE not at all, one that fails with GROOT_E_SHORT_READ or GROOT_E_REVCOMP whole.
  * Off by default: then nothing is launched and no device memory is taken. */
 /* Switch on (an empty table; the per-read buffers of shared reads, shared with it when both are on) or off (freed).  Only while
  * nothing is in flight. */

@@ -258,6 +258,8 @@ def test_device_ecs_equal_the_records(which, stage, memo, rod, small_index, arga
 def test_slow_path_and_wide_sets(argannot_index, hip_lib, monkeypatch, slow):
     """reads in several graphs and reads with wide sets; under GROOT_TEST_SHARED_SLOW every read in more than one graph is folded in
     on the host from its records"""
+    # (arg-annot reads lie in at most three graphs: without the switch no read is slow here.  Reads in more than four graphs, with sets
+    # of several hundred paths, are in test_counter_edges.py)
     from groot_amd import synth
 
     _stage(monkeypatch, "path_first")
