@@ -73,6 +73,8 @@ struct Args {
     std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out, abundance_out;
     double cov_cutoff = 0.97, abundance_min = 1.0;
     bool low_cov = false, no_bam = false;
+    uint32_t bootstraps = 0;               // --bootstraps: replicates behind the four bootstrap columns of --abundance (0 = none)
+    uint64_t boot_seed = 1;
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
     bool gpu_given = false, write_gob = false;
@@ -108,12 +110,16 @@ void usage()
             "                  [--gpu 0 | --gpus N] [--batch 1048576] [--maxReadLen 512] [--bam out.bam] [--bamLevel -2..9] [--stats f.json]\n"
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
             "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0]] [--noBam]\n"
+            "                  [--bootstraps B [--bootSeed 1]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
-            "                   --abundance: `name reads em_reads fraction` per ARG with em_reads >= --abundanceMin, by EM over the reads' path sets)\n"
+            "                   --abundance: `name reads em_reads fraction` per ARG with em_reads >= --abundanceMin, by EM over the reads' path sets;\n"
+            "                   --bootstraps: with --abundance, four more columns `boot_mean boot_sd boot_lo boot_hi` from B replicates of the reads\n"
+            "                   resampled with replacement (--bootSeed), each with its own EM, drawn and fitted on the GPU)\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
-            "                  (BAM from stdin unless --bamFile)\n",
+            "                  [--bootstraps B [--bootSeed 1]] [-p N]\n"
+            "                  (BAM from stdin unless --bamFile; --bootstraps: the same columns as align writes, computed on -p host threads)\n",
             groot_host_version());
 }
 
@@ -150,6 +156,8 @@ Args parse(int argc, char **argv)
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--sharedReads") a.shared_out = v();
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--abundance") a.abundance_out = v();
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--abundanceMin") a.abundance_min = atof(v().c_str());
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootstraps") a.bootstraps = (uint32_t)std::max(0l, atol(v().c_str()));
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootSeed") a.boot_seed = strtoull(v().c_str(), nullptr, 10);
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
         else if (f == "--bamFile") a.bam_file = v();
         else if (f == "--lowCov") a.low_cov = true;
@@ -353,6 +361,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     if (want_shared && !want_report) { fprintf(stderr, "--sharedReads lists pairs of reported ARGs: it needs --report\n"); return 1; }
     const bool want_ab = !a.abundance_out.empty();
     if (want_ab && a.no_align) { fprintf(stderr, "--abundance needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
+    if (a.bootstraps && !want_ab) { fprintf(stderr, "--bootstraps adds columns to the abundance file: it needs --abundance\n"); return 1; }
     if (a.no_bam && !want_report && !want_ab) { fprintf(stderr, "--noBam without --report would leave no output of the alignments\n"); return 1; }
     if (a.no_bam && !a.bam_out.empty()) { fprintf(stderr, "--noBam and --bam contradict each other\n"); return 1; }
     start_logging(a);
@@ -734,8 +743,27 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         uint64_t n_lines = 0;
         uint32_t iters = 0;
         auto t_em = std::chrono::steady_clock::now();
-        if (groot_host_abundance_from_ecs(&v, ec_cnt.size(), ec_off.data(), ec_ids.data(), ec_cnt.data(), a.abundance_min, a.abundance_out.c_str(), &n_lines,
-                                          &iters))
+        std::vector<double> boot_alpha;
+        if (a.bootstraps) {
+            // the replicates: drawn and fitted on the run's first GPU, over the merged ECs in canonical order
+            auto t_boot = std::chrono::steady_clock::now();
+            std::vector<uint64_t> c_off(ec_cnt.size() + 1), c_cnt(ec_cnt.size());
+            std::vector<uint32_t> c_ids(ec_ids.size()), its(a.bootstraps);
+            uint64_t n_can = 0;
+            if (groot_host_ecs_canonical(v.n_paths, ec_cnt.size(), ec_off.data(), ec_ids.data(), ec_cnt.data(), c_off.data(), c_ids.data(), c_cnt.data(), &n_can))
+                die("%s", groot_host_last_error());
+            boot_alpha.resize((size_t)a.bootstraps * v.n_paths);
+            if (groot_hip_em_bootstrap(gpus[0]->device, v.n_paths, n_can, c_off.data(), c_ids.data(), c_cnt.data(), a.bootstraps, a.boot_seed, 0, GROOT_EM_MIN_ITER,
+                                       GROOT_EM_MAX_ITER, nullptr, boot_alpha.data(), its.data()))
+                die("%s", groot_hip_last_error(nullptr));
+            logf("\tbootstrap: %u replicate(s) of %llu equivalence class(es) on GPU %d (seed %llu), EM of %u to %u iteration(s), %.3f s", a.bootstraps,
+                 (unsigned long long)n_can, gpus[0]->device, (unsigned long long)a.boot_seed, *std::min_element(its.begin(), its.end()),
+                 *std::max_element(its.begin(), its.end()), seconds_since(t_boot));
+        }
+        if (a.bootstraps ? groot_host_abundance_boot_from_ecs(&v, ec_cnt.size(), ec_off.data(), ec_ids.data(), ec_cnt.data(), a.abundance_min, a.bootstraps,
+                                                              a.boot_seed, boot_alpha.data(), 1, a.abundance_out.c_str(), &n_lines, &iters)
+                         : groot_host_abundance_from_ecs(&v, ec_cnt.size(), ec_off.data(), ec_ids.data(), ec_cnt.data(), a.abundance_min, a.abundance_out.c_str(),
+                                                         &n_lines, &iters))
             die("%s", groot_host_last_error());
         logf("\tabundance: %llu equivalence class(es), EM of %u iteration(s) in %.3f s, %llu ARG(s) with at least %g reads written to %s",
              (unsigned long long)ec_cnt.size(), iters, seconds_since(t_em), (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
@@ -878,6 +906,7 @@ int run_report(const Args &a)
         logf("\tBAM file: %s", a.bam_file.c_str());
     }
     if (a.cov_cutoff > 1.0) die("supplied coverage cutoff exceeds 1.0 (100%%): %g", a.cov_cutoff);
+    if (a.bootstraps && a.abundance_out.empty()) die("--bootstraps adds columns to the abundance file: it needs --abundance");
     logf("\tcoverage cutoff: %.2f", a.cov_cutoff);
     logf("\tprocessors: %d", a.proc);
     uint64_t n = 0, n_lines = 0;
@@ -901,7 +930,11 @@ int run_report(const Args &a)
         die("%s", groot_host_last_error());
     if (!a.shared_out.empty()) logf("\tshared reads: %llu pair(s) of reported ARGs written to %s", (unsigned long long)n_lines, a.shared_out.c_str());
     if (!a.abundance_out.empty()) {
-        if (groot_host_report_abundance(bam, a.abundance_min, a.abundance_out.c_str(), &n_lines)) die("%s", groot_host_last_error());
+        if (a.bootstraps ? groot_host_report_abundance_boot(bam, a.abundance_min, a.bootstraps, a.boot_seed, (uint32_t)std::max(1, a.proc),
+                                                            a.abundance_out.c_str(), &n_lines)
+                         : groot_host_report_abundance(bam, a.abundance_min, a.abundance_out.c_str(), &n_lines))
+            die("%s", groot_host_last_error());
+        if (a.bootstraps) logf("\tbootstrap: %u replicate(s) on %d host thread(s) (seed %llu)", a.bootstraps, std::max(1, a.proc), (unsigned long long)a.boot_seed);
         logf("\tabundance: %llu ARG(s) with at least %g reads written to %s", (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
     }
     if (!spool.empty()) unlink(spool.c_str());

@@ -23,6 +23,7 @@
 
 #include "../common/cpus.hpp"
 #include "../common/view_check.hpp"
+#include "kernels_boot.hpp"
 #include "kernels_cov.hpp"
 #include "kernels_ec.hpp"
 #include "kernels_misc.hpp"
@@ -3788,6 +3789,127 @@ int groot_hip_ec_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ec_fill.p, 0, sizeof(uint32_t)));
     c->ec_fill_known = c->ec_grows = c->ec_slow_reads = 0;
     c->ec_host.clear();
+    return GROOT_OK;
+}
+
+// ---- bootstrap replicates of the abundance EM (kernels_boot.hpp; the contract is in groot_host.h) ---------------------------
+namespace {
+struct DeviceGuard {         // the calling thread's current device, put back on return
+    int prev = -1;
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
+};
+constexpr size_t kBootChunkBytes = 256u << 20;      // device memory of one chunk of replicates (counts + alpha)
+constexpr uint32_t kBootDrawGroups = 2048;          // workgroups of one boot_resample_kernel launch, about
+} // namespace
+
+int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_boot,
+                           uint64_t seed, uint64_t n_draws, uint32_t min_iter, uint32_t max_iter, uint64_t *boot_count, double *alpha, uint32_t *iterations)
+{
+    if ((n_ec && (!off || !count)) || (n_paths && !alpha)) return fail(nullptr, GROOT_E_INVALID, "null argument");
+    if (n_boot == 0) return fail(nullptr, GROOT_E_INVALID, "no bootstrap replicates");
+    if (max_iter < min_iter)
+        return fail(nullptr, GROOT_E_INVALID, "number of EM iterations (%u) must be greater than minimum iterations (%u)", max_iter, min_iter);
+    if (max_iter < 1) return fail(nullptr, GROOT_E_INVALID, "no EM iterations were ran");
+    if (n_ec >= 0xFFFFFFFFull || (n_ec && off[n_ec] >= 0xFFFFFFFFull))
+        return fail(nullptr, GROOT_E_UNSUPPORTED, "bootstrap on the device: 2^32 ECs or path IDs and more");
+    const uint32_t ne = (uint32_t)n_ec;
+    std::vector<uint64_t> cum((size_t)ne + 1, 0);
+    std::vector<uint32_t> ec_off((size_t)ne + 1, 0), path_off((size_t)n_paths + 1, 0);
+    for (uint32_t e = 0; e < ne; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return fail(nullptr, GROOT_E_INVALID, "EC %u: bad offsets", e);
+        for (uint64_t i = off[e]; i < off[e + 1]; i++) {
+            if (ids[i] >= n_paths) return fail(nullptr, GROOT_E_INVALID, "EC %u holds path %u of %u", e, ids[i], n_paths);
+            path_off[ids[i] + 1]++;
+        }
+        ec_off[e + 1] = ec_off[e] + (uint32_t)(off[e + 1] - off[e]);
+        cum[e + 1] = cum[e] + count[e];
+        if (cum[e + 1] < cum[e]) return fail(nullptr, GROOT_E_INVALID, "the EC counts sum to 2^64 or more");
+    }
+    const uint64_t total = cum[ne];
+    if (ne && total == 0) return fail(nullptr, GROOT_E_INVALID, "bootstrap over ECs without reads");
+    if (n_draws == 0) n_draws = total;
+    // path -> EC, CSR: the ECs are visited in order, so every path's list ascends (an ID an EC names twice is listed twice, as the host adds it twice)
+    const uint32_t nnz = ec_off[ne];
+    for (uint32_t p = 0; p < n_paths; p++) path_off[p + 1] += path_off[p];
+    std::vector<uint32_t> ec_ids(std::max<uint32_t>(nnz, 1u)), path_ecs(std::max<uint32_t>(nnz, 1u)), at(path_off.begin(), path_off.end() - 1);
+    for (uint32_t e = 0; e < ne; e++)
+        for (uint64_t i = off[e]; i < off[e + 1]; i++) {
+            ec_ids[ec_off[e] + (i - off[e])] = ids[i];
+            path_ecs[at[ids[i]]++] = e;
+        }
+
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(nullptr, GROOT_E_DEVICE, "no HIP device");
+    if (device < 0 || device >= n_dev) return fail(nullptr, GROOT_E_DEVICE, "device %d of %d", device, n_dev);
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    HIP_TRY(nullptr, hipSetDevice(device));
+    int lds_max = 0, n_cu = 0;
+    HIP_TRY(nullptr, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    HIP_TRY(nullptr, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+    n_cu = std::max(n_cu, 1);
+    StreamGuard sg;
+    HIP_TRY(nullptr, hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    hipStream_t st = sg.s;
+
+    const size_t per_rep = ((size_t)ne + n_paths) * 8;
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)n_boot, (size_t)65535, kBootChunkBytes / std::max<size_t>(per_rep, 1)}));
+    DevBuf<uint64_t> d_cum;
+    DevBuf<uint32_t> d_ec_off, d_ec_ids, d_path_off, d_path_ecs, d_it;
+    DevBuf<unsigned long long> d_cnt;
+    DevBuf<double> d_alpha, d_scratch;
+    HIP_TRY(nullptr, d_cum.alloc(cum.size()));
+    HIP_TRY(nullptr, d_ec_off.alloc(ec_off.size()));
+    HIP_TRY(nullptr, d_ec_ids.alloc(ec_ids.size()));
+    HIP_TRY(nullptr, d_path_off.alloc(path_off.size()));
+    HIP_TRY(nullptr, d_path_ecs.alloc(path_ecs.size()));
+    HIP_TRY(nullptr, d_cnt.alloc((size_t)chunk * ne));
+    HIP_TRY(nullptr, d_alpha.alloc((size_t)chunk * n_paths));
+    HIP_TRY(nullptr, d_it.alloc(chunk));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_cum.p, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_ec_off.p, ec_off.data(), ec_off.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_ec_ids.p, ec_ids.data(), ec_ids.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_path_off.p, path_off.data(), path_off.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_path_ecs.p, path_ecs.data(), path_ecs.size() * 4, hipMemcpyHostToDevice, st));
+
+    // LDS or global memory: the cumulative table and the histogram of the draws; alpha and norm of the EM
+    const size_t draw_lds = ((size_t)ne + 1) * 8 + (size_t)ne * 4, em_lds = per_rep;
+    const bool draw_in_lds = draw_lds <= (size_t)lds_max, em_in_lds = em_lds <= (size_t)lds_max;
+    if (draw_in_lds && draw_lds > 48 * 1024)
+        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_resample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)draw_lds));
+    if (em_in_lds && em_lds > 48 * 1024)
+        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_em_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
+    const uint32_t em_grid = std::min<uint32_t>(chunk, (uint32_t)n_cu);
+    if (!em_in_lds) HIP_TRY(nullptr, d_scratch.alloc((size_t)em_grid * ((size_t)ne + n_paths)));
+
+    constexpr uint64_t kChunkDraws = (uint64_t)kBootDrawBlock * kBootDrawsPerThread;
+    const uint64_t draw_chunks = (n_draws + kChunkDraws - 1) / kChunkDraws;
+    for (uint32_t b0 = 0; b0 < n_boot; b0 += chunk) {
+        const uint32_t nb = std::min(chunk, n_boot - b0);
+        if (ne) {
+            HIP_TRY(nullptr, hipMemsetAsync(d_cnt.p, 0, (size_t)nb * ne * 8, st));
+            if (draw_chunks) {
+                BootDrawArgs da{d_cum.p, d_cnt.p, total, n_draws, seed, ne, b0};
+                const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(draw_chunks, (kBootDrawGroups + nb - 1) / nb)), nb);
+                if (draw_in_lds) hipLaunchKernelGGL(boot_resample_kernel<true>, grid, dim3(kBootDrawBlock), draw_lds, st, da);
+                else hipLaunchKernelGGL(boot_resample_kernel<false>, grid, dim3(kBootDrawBlock), 0, st, da);
+                HIP_TRY(nullptr, hipGetLastError());
+            }
+        }
+        BootEmArgs ea{d_ec_off.p, d_ec_ids.p, d_path_off.p, d_path_ecs.p, d_cnt.p, d_alpha.p, d_it.p, d_scratch.p, 1.0 / (double)n_paths, n_paths, ne, nb, min_iter, max_iter};
+        const dim3 grid(std::min<uint32_t>(nb, em_grid));
+        if (em_in_lds) hipLaunchKernelGGL(boot_em_kernel<true>, grid, dim3(kBootEmBlock), em_lds, st, ea);
+        else hipLaunchKernelGGL(boot_em_kernel<false>, grid, dim3(kBootEmBlock), 0, st, ea);
+        HIP_TRY(nullptr, hipGetLastError());
+        if (boot_count && ne) HIP_TRY(nullptr, hipMemcpyAsync(boot_count + (size_t)b0 * ne, d_cnt.p, (size_t)nb * ne * 8, hipMemcpyDeviceToHost, st));
+        if (n_paths) HIP_TRY(nullptr, hipMemcpyAsync(alpha + (size_t)b0 * n_paths, d_alpha.p, (size_t)nb * n_paths * 8, hipMemcpyDeviceToHost, st));
+        if (iterations) HIP_TRY(nullptr, hipMemcpyAsync(iterations + b0, d_it.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(nullptr, hipStreamSynchronize(st));
+    }
     return GROOT_OK;
 }
 

@@ -11,8 +11,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <atomic>
 #include <map>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -442,13 +444,87 @@ extern "C" int groot_host_em(uint32_t n_paths, uint64_t n_ec, const uint64_t *of
     return GROOT_OK;
 }
 
+// ---- bootstrap over the ECs (groot_host.h: resampling by splitmix64, the EM above per replicate) ---------------------------
+extern "C" int groot_host_em_bootstrap(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_boot,
+                                       uint64_t seed, uint64_t n_draws, uint32_t min_iter, uint32_t max_iter, uint32_t threads, uint64_t *boot_count,
+                                       double *alpha, uint32_t *iterations)
+{
+    if ((n_ec && (!off || !count)) || (n_paths && !alpha)) return set_error(GROOT_E_INVALID, "null argument");
+    if (n_boot == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
+    if (max_iter < min_iter)
+        return set_error(GROOT_E_INVALID, "number of EM iterations (%u) must be greater than minimum iterations (%u)", max_iter, min_iter);
+    if (max_iter < 1) return set_error(GROOT_E_INVALID, "no EM iterations were ran");
+    std::vector<uint64_t> cum(n_ec + 1, 0);
+    for (uint64_t e = 0; e < n_ec; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
+        for (uint64_t i = off[e]; i < off[e + 1]; i++)
+            if (ids[i] >= n_paths) return set_error(GROOT_E_INVALID, "EC %llu holds path %u of %u", (unsigned long long)e, ids[i], n_paths);
+        cum[e + 1] = cum[e] + count[e];
+        if (cum[e + 1] < cum[e]) return set_error(GROOT_E_INVALID, "the EC counts sum to 2^64 or more");
+    }
+    const uint64_t total = cum[n_ec];
+    if (n_ec && total == 0) return set_error(GROOT_E_INVALID, "bootstrap over ECs without reads");
+    if (n_draws == 0) n_draws = total;
+    std::atomic<uint32_t> next_b{0};
+    std::atomic<int> failed{0};
+    auto work = [&]() {
+        std::vector<uint64_t> own(boot_count ? 0 : n_ec);
+        for (uint32_t b; (b = next_b.fetch_add(1)) < n_boot;) {
+            uint64_t *bc = boot_count ? boot_count + (size_t)b * n_ec : own.data();
+            std::fill(bc, bc + n_ec, 0);
+            const uint64_t base = (uint64_t)b * n_draws;
+            for (uint64_t j = 0; n_ec && j < n_draws; j++) {
+                uint64_t z = seed + (base + j + 1) * 0x9E3779B97F4A7C15ull;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                z = z ^ (z >> 31);
+                const uint64_t t = (uint64_t)(((unsigned __int128)z * total) >> 64);
+                bc[(std::upper_bound(cum.begin(), cum.end(), t) - cum.begin()) - 1]++;     // cum[e] <= t < cum[e + 1]
+            }
+            if (groot_host_em(n_paths, n_ec, off, ids, bc, min_iter, max_iter, alpha + (size_t)b * n_paths, iterations ? iterations + b : nullptr))
+                failed = 1;
+        }
+    };
+    const uint32_t nt = std::max(1u, std::min(threads, n_boot));
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < nt; t++) pool.emplace_back(work);
+    work();
+    for (auto &t : pool) t.join();
+    if (failed) return set_error(GROOT_E_INVALID, "the EM of a bootstrap replicate failed");
+    return GROOT_OK;
+}
+
 namespace {
 
 using EcMap = std::map<std::vector<uint32_t>, uint64_t>;   // canonical order
 
-// the abundance file of the ECs in m (paths [0, n_paths), names as the report prints them)
+// the bootstrap columns of the abundance file: n replicates, from ready-made alpha[n][n_paths] or computed here over `threads`
+struct Boot {
+    uint32_t n = 0;
+    uint64_t seed = 1;
+    const double *alpha = nullptr;
+    uint32_t threads = 1;
+};
+
+// ECs in any order, IDs in any order, repeats summed -> the canonical map (IDs ascending and unique, empty and count-0 ECs dropped)
+int canonical_ecs(uint32_t n, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, EcMap &m)
+{
+    std::vector<uint32_t> v;
+    for (uint64_t e = 0; e < n_ec; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
+        v.assign(ids + off[e], ids + off[e + 1]);
+        for (uint32_t p : v)
+            if (p >= n) return set_error(GROOT_E_INVALID, "EC %llu holds path %u of %u", (unsigned long long)e, p, n);
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        if (!v.empty() && count[e]) m[v] += count[e];          // (the lists of several contexts: repeats summed)
+    }
+    return GROOT_OK;
+}
+
+// the abundance file of the ECs in m (paths [0, n_paths), names as the report prints them); with boot, its four columns more
 int write_abundance(uint32_t n_paths, const char *const *names, const uint32_t *name_len, const EcMap &m, double min_reads, const char *out_path,
-                    uint64_t *n_lines, uint32_t *iterations)
+                    uint64_t *n_lines, uint32_t *iterations, const Boot *boot = nullptr)
 {
     std::vector<uint64_t> off{0}, count;
     std::vector<uint32_t> ids;
@@ -462,17 +538,40 @@ int write_abundance(uint32_t n_paths, const char *const *names, const uint32_t *
     uint32_t it = 0;
     if (int rc = groot_host_em(n_paths, m.size(), off.data(), ids.data(), count.data(), GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER, alpha.data(), &it)) return rc;
     if (iterations) *iterations = it;
+    const uint32_t B = boot ? boot->n : 0;
+    std::vector<double> own;
+    const double *ba = B ? boot->alpha : nullptr;
+    if (B && !ba && !m.empty()) {
+        own.resize((size_t)B * n_paths);
+        if (int rc = groot_host_em_bootstrap(n_paths, m.size(), off.data(), ids.data(), count.data(), B, boot->seed, 0, GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER,
+                                             boot->threads, nullptr, own.data(), nullptr))
+            return rc;
+        ba = own.data();
+    }
     FILE *out = out_path ? fopen(out_path, "w") : stdout;
     if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
     double sum = 0.0;
     for (uint32_t p = 0; p < n_paths; p++) sum += alpha[p];
     uint64_t lines = 0;
+    std::vector<double> x(B);
     for (uint32_t p = 0; p < n_paths && !m.empty(); p++) {
         if (!(alpha[p] >= min_reads)) continue;
         const char *nm = names[p];
         size_t nl = name_len ? name_len[p] : strlen(nm);
         if (nl && nm[0] == '*') { nm++; nl--; }
-        fprintf(out, "%.*s\t%llu\t%.2f\t%.6f\n", (int)nl, nm, (unsigned long long)reads[p], alpha[p], sum > 0 ? alpha[p] / sum : 0.0);
+        fprintf(out, "%.*s\t%llu\t%.2f\t%.6f", (int)nl, nm, (unsigned long long)reads[p], alpha[p], sum > 0 ? alpha[p] / sum : 0.0);
+        if (B) {
+            // groot_host.h: mean and sd with the sums in replicate order, the interval from the sorted replicates
+            double s = 0.0, s2 = 0.0;
+            for (uint32_t b = 0; b < B; b++) { x[b] = ba[(size_t)b * n_paths + p]; s += x[b]; }
+            const double mean = s / (double)B;
+            for (uint32_t b = 0; b < B; b++) { const double d = x[b] - mean; s2 += d * d; }
+            const double sd = B > 1 ? std::sqrt(s2 / (double)(B - 1)) : 0.0;
+            std::sort(x.begin(), x.end());
+            const uint32_t q = (uint32_t)((25ull * (B - 1)) / 1000);
+            fprintf(out, "\t%.2f\t%.2f\t%.2f\t%.2f", mean, sd, x[q], x[B - 1 - q]);
+        }
+        fputc('\n', out);
         lines++;
     }
     if (out_path) fclose(out); else fflush(out);
@@ -480,34 +579,23 @@ int write_abundance(uint32_t n_paths, const char *const *names, const uint32_t *
     return GROOT_OK;
 }
 
-} // namespace
-
-extern "C" int groot_host_abundance_from_ecs(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
-                                             double min_reads, const char *out_path, uint64_t *n_lines, uint32_t *iterations)
+int abundance_from_ecs(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, double min_reads,
+                       const char *out_path, uint64_t *n_lines, uint32_t *iterations, const Boot *boot)
 {
     if (!ix || (n_ec && (!off || !count))) return set_error(GROOT_E_INVALID, "null argument");
     const uint32_t n = ix->n_paths;
     EcMap m;
-    std::vector<uint32_t> v;
-    for (uint64_t e = 0; e < n_ec; e++) {
-        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
-        v.assign(ids + off[e], ids + off[e + 1]);
-        for (uint32_t p : v)
-            if (p >= n) return set_error(GROOT_E_INVALID, "EC %llu holds path %u of %u", (unsigned long long)e, p, n);
-        std::sort(v.begin(), v.end());
-        v.erase(std::unique(v.begin(), v.end()), v.end());
-        if (!v.empty() && count[e]) m[v] += count[e];          // (the lists of several contexts: repeats summed)
-    }
+    if (int rc = canonical_ecs(n, n_ec, off, ids, count, m)) return rc;
     std::vector<const char *> name_ptr(n);
     std::vector<uint32_t> name_len(n);
     for (uint32_t p = 0; p < n; p++) {
         name_ptr[p] = ix->path_names + ix->path_name_off[p];
         name_len[p] = ix->path_name_off[p + 1] - ix->path_name_off[p];
     }
-    return write_abundance(n, name_ptr.data(), name_len.data(), m, min_reads, out_path, n_lines, iterations);
+    return write_abundance(n, name_ptr.data(), name_len.data(), m, min_reads, out_path, n_lines, iterations, boot);
 }
 
-extern "C" int groot_host_report_abundance(const char *bam_path, double min_reads, const char *out_path, uint64_t *n_lines)
+int report_abundance(const char *bam_path, double min_reads, const char *out_path, uint64_t *n_lines, const Boot *boot)
 {
     std::vector<uint64_t> read_ref;
     std::vector<std::string> names;
@@ -524,5 +612,52 @@ extern "C" int groot_host_report_abundance(const char *bam_path, double min_read
     }
     std::vector<const char *> name_ptr(names.size());
     for (size_t r = 0; r < names.size(); r++) name_ptr[r] = names[r].c_str();
-    return write_abundance((uint32_t)names.size(), name_ptr.data(), nullptr, m, min_reads, out_path, n_lines, nullptr);
+    return write_abundance((uint32_t)names.size(), name_ptr.data(), nullptr, m, min_reads, out_path, n_lines, nullptr, boot);
+}
+
+} // namespace
+
+extern "C" int groot_host_ecs_canonical(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint64_t *out_off,
+                                        uint32_t *out_ids, uint64_t *out_count, uint64_t *n_out)
+{
+    if ((n_ec && (!off || !count || !out_count)) || !out_off || !n_out) return set_error(GROOT_E_INVALID, "null argument");
+    EcMap m;
+    if (int rc = canonical_ecs(n_paths, n_ec, off, ids, count, m)) return rc;
+    uint64_t e = 0, at = 0;
+    out_off[0] = 0;
+    for (const auto &kv : m) {
+        for (uint32_t p : kv.first) out_ids[at++] = p;
+        out_count[e] = kv.second;
+        out_off[++e] = at;
+    }
+    *n_out = e;
+    return GROOT_OK;
+}
+
+extern "C" int groot_host_abundance_from_ecs(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                             double min_reads, const char *out_path, uint64_t *n_lines, uint32_t *iterations)
+{
+    return abundance_from_ecs(ix, n_ec, off, ids, count, min_reads, out_path, n_lines, iterations, nullptr);
+}
+
+extern "C" int groot_host_abundance_boot_from_ecs(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                                  double min_reads, uint32_t n_boot, uint64_t seed, const double *boot_alpha, uint32_t threads,
+                                                  const char *out_path, uint64_t *n_lines, uint32_t *iterations)
+{
+    if (n_boot == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
+    const Boot boot{n_boot, seed, boot_alpha, threads};
+    return abundance_from_ecs(ix, n_ec, off, ids, count, min_reads, out_path, n_lines, iterations, &boot);
+}
+
+extern "C" int groot_host_report_abundance(const char *bam_path, double min_reads, const char *out_path, uint64_t *n_lines)
+{
+    return report_abundance(bam_path, min_reads, out_path, n_lines, nullptr);
+}
+
+extern "C" int groot_host_report_abundance_boot(const char *bam_path, double min_reads, uint32_t n_boot, uint64_t seed, uint32_t threads,
+                                                const char *out_path, uint64_t *n_lines)
+{
+    if (n_boot == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
+    const Boot boot{n_boot, seed, nullptr, threads};
+    return report_abundance(bam_path, min_reads, out_path, n_lines, &boot);
 }

@@ -110,6 +110,25 @@ def expand_alns(index, travs, masks):
     return out
 
 
+def em_bootstrap(n_paths, off, ids, count, n_boot, seed=1, n_draws=0, min_iter=host.EM_MIN_ITER, max_iter=host.EM_MAX_ITER, device=0):
+    """groot_hip_em_bootstrap: host.em_bootstrap on the device, bit for bit ->
+    (boot_count uint64[n_boot, n_ec], alpha float64[n_boot, n_paths], iterations uint32[n_boot])"""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    if len(off) != len(count) + 1:
+        raise ValueError("off must have one entry more than count")
+    bc = np.zeros((n_boot, len(count)), dtype=np.uint64)
+    alpha = np.zeros((n_boot, n_paths), dtype=np.float64)
+    its = np.zeros(n_boot, dtype=np.uint32)
+    rc = lib().groot_hip_em_bootstrap(C.c_int(device), C.c_uint32(n_paths), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                      _ffi.as_ptr(count, C.c_uint64), C.c_uint32(n_boot), C.c_uint64(seed), C.c_uint64(n_draws), C.c_uint32(min_iter),
+                                      C.c_uint32(max_iter), _ffi.as_ptr(bc, C.c_uint64), _ffi.as_ptr(alpha, C.c_double), _ffi.as_ptr(its, C.c_uint32))
+    if rc < 0:
+        raise GrootError(rc, lib().groot_hip_last_error(None).decode(errors="replace"))
+    return bc, alpha, its
+
+
 class Aligner:
     """One groot_ctx: the replacement for theBoss.mapReads (src/pipeline/boss.go:108-242) on one GPU."""
 

@@ -530,6 +530,97 @@ def report_abundance(bam_path, min_reads=1.0, out_path=None):
     return rows
 
 
+def _ec_arrays(off, ids, count):
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    if len(off) != len(count) + 1:
+        raise ValueError("off must have one entry more than count")
+    return off, ids, count
+
+
+def em_bootstrap(n_paths, off, ids, count, n_boot, seed=1, n_draws=0, min_iter=EM_MIN_ITER, max_iter=EM_MAX_ITER, threads=1):
+    """groot_host_em_bootstrap: n_boot resampled replicates of the ECs (splitmix64 draws, include/groot_host.h), the EM on each ->
+    (boot_count uint64[n_boot, n_ec], alpha float64[n_boot, n_paths], iterations uint32[n_boot])"""
+    off, ids, count = _ec_arrays(off, ids, count)
+    bc = np.zeros((n_boot, len(count)), dtype=np.uint64)
+    alpha = np.zeros((n_boot, n_paths), dtype=np.float64)
+    its = np.zeros(n_boot, dtype=np.uint32)
+    _check(lib().groot_host_em_bootstrap(C.c_uint32(n_paths), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                         _ffi.as_ptr(count, C.c_uint64), C.c_uint32(n_boot), C.c_uint64(seed), C.c_uint64(n_draws), C.c_uint32(min_iter),
+                                         C.c_uint32(max_iter), C.c_uint32(threads), _ffi.as_ptr(bc, C.c_uint64), _ffi.as_ptr(alpha, C.c_double),
+                                         _ffi.as_ptr(its, C.c_uint32)))
+    return bc, alpha, its
+
+
+def ecs_canonical(n_paths, off, ids, count):
+    """groot_host_ecs_canonical: ECs in any order, repeats summed -> (off, ids, count) in canonical order"""
+    off, ids, count = _ec_arrays(off, ids, count)
+    o = np.zeros(len(count) + 1, dtype=np.uint64)
+    i = np.zeros(max(len(ids), 1), dtype=np.uint32)
+    c = np.zeros(max(len(count), 1), dtype=np.uint64)
+    n = C.c_uint64(0)
+    _check(lib().groot_host_ecs_canonical(C.c_uint32(n_paths), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                          _ffi.as_ptr(count, C.c_uint64), _ffi.as_ptr(o, C.c_uint64), _ffi.as_ptr(i, C.c_uint32), _ffi.as_ptr(c, C.c_uint64),
+                                          C.byref(n)))
+    return o[:n.value + 1].copy(), i[:int(o[n.value])].copy(), c[:n.value].copy()
+
+
+def _abundance_boot_rows(path):
+    rows = [ln.rstrip("\n").split("\t") for ln in open(path)]
+    return [(r[0], int(r[1])) + tuple(float(x) for x in r[2:]) for r in rows]
+
+
+def abundance_boot_from_ecs(index, off, ids, count, n_boot, seed=1, boot_alpha=None, threads=1, min_reads=1.0, out_path=None):
+    """groot_host_abundance_boot_from_ecs: the abundance lines with the bootstrap columns, from ready-made boot_alpha[n_boot, n_paths]
+    (device.em_bootstrap over ecs_canonical) or computed on `threads` host threads:
+    [(name, reads, em_reads, fraction, boot_mean, boot_sd, boot_lo, boot_hi)]"""
+    import tempfile
+
+    v = index.view
+    off, ids, count = _ec_arrays(off, ids, count)
+    if boot_alpha is not None:
+        boot_alpha = np.ascontiguousarray(boot_alpha, dtype=np.float64)
+        if boot_alpha.shape != (n_boot, v.n_paths):
+            raise ValueError("boot_alpha must be [n_boot, n_paths]")
+    tmp = None
+    if out_path is None:
+        fd, tmp = tempfile.mkstemp(suffix=".abundance")
+        os.close(fd)
+    n = C.c_uint64(0)
+    try:
+        _check(lib().groot_host_abundance_boot_from_ecs(C.byref(v), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                                        _ffi.as_ptr(count, C.c_uint64), C.c_double(min_reads), C.c_uint32(n_boot), C.c_uint64(seed),
+                                                        _ffi.as_ptr(boot_alpha, C.c_double) if boot_alpha is not None else None, C.c_uint32(threads),
+                                                        (out_path or tmp).encode(), C.byref(n), None))
+        rows = _abundance_boot_rows(out_path or tmp)
+    finally:
+        if tmp:
+            os.unlink(tmp)
+    assert len(rows) == n.value
+    return rows
+
+
+def report_abundance_boot(bam_path, n_boot, seed=1, threads=1, min_reads=1.0, out_path=None):
+    """groot_host_report_abundance_boot: the abundance lines of a BAM with the bootstrap columns"""
+    import tempfile
+
+    tmp = None
+    if out_path is None:
+        fd, tmp = tempfile.mkstemp(suffix=".abundance")
+        os.close(fd)
+    n = C.c_uint64(0)
+    try:
+        _check(lib().groot_host_report_abundance_boot(bam_path.encode(), C.c_double(min_reads), C.c_uint32(n_boot), C.c_uint64(seed), C.c_uint32(threads),
+                                                      (out_path or tmp).encode(), C.byref(n)))
+        rows = _abundance_boot_rows(out_path or tmp)
+    finally:
+        if tmp:
+            os.unlink(tmp)
+    assert len(rows) == n.value
+    return rows
+
+
 def save_gfa(index, graph, kmer_freq, path_kept, node_removed, total_kmers, file_name, timestamp=None):
     """GrootGraph.SaveGraphAsGFA (src/graph/graphio.go:19-112); returns True if a file was written"""
     kf = np.ascontiguousarray(kmer_freq, dtype=np.float64)

@@ -346,6 +346,25 @@ int groot_hip_ec_reset(groot_ctx *ctx);
  * in more than one under GROOT_TEST_SHARED_SLOW), times the table grew.  Waits for everything in flight.  GROOT_E_STATE when off. */
 int groot_hip_ec_stats(groot_ctx *ctx, uint64_t *reads, uint64_t *distinct, uint64_t *slow_reads, uint64_t *grows);
 
+/* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
+ * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
+ * the device, bit for bit in boot_count, alpha and iterations.  Quoted from there: draw j (0 <= j < n_draws; n_draws = 0 means N, the sum
+ * of count) of replicate b, modulo 2^64,
+ *     z = seed + (b * n_draws + j + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31);  t = high 64 bits of z * N;
+ *     boot_count[b][e] += 1 for the EC e with cum[e] <= t < cum[e+1]   (cum = the running sum of count; count 0 is never drawn),
+ * then alpha[b] = groot_host_em(n_paths, n_ec, off, ids, boot_count[b], min_iter, max_iter), iterations[b] its rounds.
+ * Needs no ctx: it runs on the device with that ordinal, on a stream and in buffers of its own that are freed on return, and may be
+ * called while ctxs have batches in flight.  The replicates are processed in chunks that bound the device memory taken; the draws
+ * are one kernel (a thread per draw), the EM runs one workgroup per replicate, as many at a time as the device has compute units
+ * (kernels_boot.hpp).  ECs in the order given (canonical order for the abundance file: groot_host_ecs_canonical).
+ * boot_count[n_boot][n_ec] and iterations[n_boot] may be NULL; alpha[n_boot][n_paths].  GROOT_E_INVALID as groot_host_em_bootstrap
+ * (n_boot = 0; N = 0 with n_ec > 0; the EM's errors), GROOT_E_UNSUPPORTED at 2^32 - 1 ECs or listed IDs and more, GROOT_E_DEVICE
+ * without that HIP device; the message is groot_hip_last_error(NULL). */
+int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                           uint32_t n_boot, uint64_t seed, uint64_t n_draws, uint32_t min_iter, uint32_t max_iter, uint64_t *boot_count,
+                           double *alpha, uint32_t *iterations);
+
 /* Fine-grained mirror of Sequence.RunMinHash(k, s, false, nil) (seqio.go:40-68) for a batch of
  * sequences in host memory: out[i*s .. (i+1)*s) = KHF sketch of sequence i.  Only while nothing is in flight. */
 int groot_hip_sketch(groot_ctx *ctx, const uint8_t *seq_concat, const uint64_t *seq_off, uint32_t n, uint64_t *out);

@@ -304,6 +304,48 @@ int groot_host_abundance_from_ecs(const groot_index_view *idx, uint64_t n_ec, co
  * byte what the device path writes whenever read names are unique. */
 int groot_host_report_abundance(const char *bam_path, double min_reads, const char *out_path, uint64_t *n_lines);
 
+/* ---- bootstrap intervals of the abundance estimate ----------------------------------------------------------------
+ * Input: ECs in canonical order as CSR (n_ec, off, ids, count over n_paths paths), N = the sum of count; n_boot = B replicates, a
+ * 64-bit seed, n_draws draws per replicate (0 means N).
+ * Resampling: cum[0] = 0, cum[e+1] = cum[e] + count[e].  Draw j (0 <= j < n_draws) of replicate b, all arithmetic modulo 2^64:
+ *     z = seed + (b * n_draws + j + 1) * 0x9E3779B97F4A7C15
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z =  z ^ (z >> 31)
+ *     t = high 64 bits of the 128-bit product z * N          (0 <= t < N)
+ *     e = the EC with cum[e] <= t < cum[e+1]                 (an EC with count 0 is never drawn)
+ *     boot_count[b][e] += 1
+ * Only integers are involved: boot_count depends on (seed, b, n_draws, count) alone, not on the order of the draws or the number of
+ * threads; the first three replicates of a run with B = 7 are the run with B = 3.
+ * EM per replicate: alpha_b = groot_host_em(n_paths, n_ec, off, ids, boot_count[b], min_iter, max_iter), bit for bit, with its own
+ * iteration count.  With n_ec = 0 every replicate is the EM of no ECs.
+ * GROOT_E_INVALID: n_boot = 0; N = 0 with n_ec > 0; the errors of groot_host_em.
+ * Statistics per path p over x_b = alpha_b[p], b = 0 .. B-1, in double precision without FMA contraction, sums in order of b:
+ * boot_mean = (sum x_b) / B; boot_sd = sqrt(sum (x_b - boot_mean)^2 / (B - 1)), 0 when B = 1; with v = the x_b sorted ascending and
+ * q = (25 * (B - 1)) / 1000 in integer arithmetic, boot_lo = v[q], boot_hi = v[B - 1 - q] (B = 100: v[2] and v[97]).
+ * File: every line of the abundance file gets four more tab-separated columns, all "%.2f":
+ * name \t reads \t em_reads \t fraction \t boot_mean \t boot_sd \t boot_lo \t boot_hi; the lines, their order and their first four
+ * columns are those of the file without bootstraps. */
+/* The contract above on the host, the replicates spread over `threads` (0 = 1).  boot_count[n_boot][n_ec] (may be NULL),
+ * alpha[n_boot][n_paths], iterations[n_boot] (may be NULL).  groot_hip_em_bootstrap computes the same bits on the device. */
+int groot_host_em_bootstrap(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_boot,
+                            uint64_t seed, uint64_t n_draws, uint32_t min_iter, uint32_t max_iter, uint32_t threads, uint64_t *boot_count,
+                            double *alpha, uint32_t *iterations);
+/* The canonicalisation the abundance writers apply: ECs in any order, IDs in any order, repeats summed -> canonical order, IDs ascending
+ * and unique, empty and count-0 ECs dropped.  out_off[n_ec + 1], out_ids[off[n_ec]], out_count[n_ec] (the input's sizes always
+ * suffice); *n_out = the canonical ECs. */
+int groot_host_ecs_canonical(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint64_t *out_off,
+                             uint32_t *out_ids, uint64_t *out_count, uint64_t *n_out);
+/* groot_host_abundance_from_ecs with the bootstrap columns: boot_alpha[n_boot][n_paths] = the replicates' alpha over the canonical ECs
+ * (groot_host_ecs_canonical) with n_draws = 0 and GROOT_EM_MIN_ITER / GROOT_EM_MAX_ITER, as groot_hip_em_bootstrap returns them; NULL =
+ * computed here with groot_host_em_bootstrap(seed, threads). */
+int groot_host_abundance_boot_from_ecs(const groot_index_view *idx, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                       double min_reads, uint32_t n_boot, uint64_t seed, const double *boot_alpha, uint32_t threads,
+                                       const char *out_path, uint64_t *n_lines, uint32_t *iterations);
+/* groot_host_report_abundance with the bootstrap columns, the replicates computed on `threads` host threads. */
+int groot_host_report_abundance_boot(const char *bam_path, double min_reads, uint32_t n_boot, uint64_t seed, uint32_t threads, const char *out_path,
+                                     uint64_t *n_lines);
+
 #ifdef __cplusplus
 }
 #endif
