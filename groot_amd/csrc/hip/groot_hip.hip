@@ -82,7 +82,7 @@ template <class T> struct PinBuf {
 // a test batch walks the grow-and-redo and the fall-back paths; OPEN_STATS prints where groot_hip_open spent its time.
 struct Knobs {
     bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false,
-         shared_slow = false;
+         shared_slow = false, serial_tail = false;
     uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
     static Knobs read()
     {
@@ -94,6 +94,7 @@ struct Knobs {
         k.lean = getenv("GROOT_LEAN") != nullptr;                         // the node-by-node first pass (kernels_lean.hpp) instead of the path-text one
         k.no_path = getenv("GROOT_NO_PATH_PASS") != nullptr;              // no first pass: align_kernel alone
         k.shared_slow = getenv("GROOT_TEST_SHARED_SLOW") != nullptr;      // shared reads: every read in more than one graph takes the slow path
+        k.serial_tail = getenv("GROOT_SERIAL_TAIL") != nullptr;           // the tail of the align stage stays on the walk stream (no tail stream: the A/B baseline)
         if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         return k;
     }
@@ -149,6 +150,7 @@ struct Slot {
     uint64_t n_mask_bytes = 0, copied_bytes = 0;
     bool host_results = false;             // the traversal records of this batch are in h_trav / h_mask
     hipEvent_t ev_seed = nullptr;          // behind the batch's seed stage on the compute stream: its align stage waits for it
+    hipEvent_t ev_walk = nullptr;          // behind the batch's first pass and its compaction on the walk stream: its tail waits for it
     hipEvent_t ev_h2d0 = nullptr, ev_h2d = nullptr, ev_compute = nullptr, ev_ctr = nullptr, ev_d2h0 = nullptr, ev_d2h = nullptr;
     hipEvent_t ev[14]{};                   // [7..8] around the first seed kernel, [9..10] around order_first_kernel, [11] start of the align stage (align stream), [12] behind the list pass
                                            // [0..6] stage boundaries on the compute stream (profiling)
@@ -173,7 +175,12 @@ struct WorkSet {
     DevBuf<uint32_t> vcount;                             // [0] items, [1] split reads of the batch
     DevBuf<groot_trav> trav_first;
     DevBuf<uint64_t> mask_first, sketches;
-    hipEvent_t ev_free = nullptr;          // on the align stream behind the order stage of the batch that used the set last
+    // records beyond a read's first (both passes of the align stage append, order_ovf_kernel reads): per set, since the first pass of batch b+1
+    // (walk stream) runs beside align_kernel and the order stage of batch b (tail stream); groot_ctx::ovf_cap slots per shard
+    DevBuf<groot_trav> ovf_trav;
+    DevBuf<uint64_t> ovf_mask;
+    DevBuf<uint32_t> ovf_cnt;
+    hipEvent_t ev_free = nullptr;          // on the tail stream behind the order stage of the batch that used the set last
     bool used = false;
     Slot *owner = nullptr;                 // whose seeds / sketches the set holds
     uint64_t ticket = 0;
@@ -187,8 +194,10 @@ struct groot_ctx {
     uint32_t s = 0, k = 0, max_k = 0, l_max = 0, pw_view = 0, pw = 0, n_windows = 0, max_q = 0, band_hash_bits = 0;
     hipEvent_t h2d_last = nullptr;         // the copy-in of the newest host-fed batch (its slot's event)
     Slot *newest = nullptr;                // the newest submitted batch (groot_hip_redo_status)
-    hipEvent_t last_compute = nullptr;     // behind the order stage of the newest batch (groot_hip_stream_join)
-    hipStream_t own_stream = nullptr, stream = nullptr, astream = nullptr, h2d_stream = nullptr, d2h_stream = nullptr;   // stream: seed stage (the caller's, if given); astream: align + order stage
+    hipEvent_t last_compute = nullptr;     // behind the order stage of the newest batch, on the tail stream (groot_hip_stream_join)
+    // stream: seed stage (the caller's, if given); astream: the walk stream (first pass of the align stage + the compaction of what it left);
+    // tstream: the tail stream (align_kernel, order stage, host-copy and counting kernels) -- astream itself under GROOT_SERIAL_TAIL=1
+    hipStream_t own_stream = nullptr, stream = nullptr, astream = nullptr, tstream = nullptr, own_tstream = nullptr, h2d_stream = nullptr, d2h_stream = nullptr;
     bool profiling = false;
 
     // index in HBM
@@ -276,7 +285,7 @@ struct groot_ctx {
     WorkSet ws[2];
     uint32_t next_set = 0;
 
-    // shared work buffers: used on ONE of the two streams only, inside one stage
+    // shared work buffers: used on ONE of the three streams only, inside one stage
     uint32_t seed_slots = 0;
     DevBuf<uint32_t> sort_key, sort_key_out, perm_in, todo_list, todo_count;   // seed stage
     DevBuf<uint32_t> long_list, long_count;              // SeedArgs::long_list (seed stage)
@@ -287,10 +296,9 @@ struct groot_ctx {
     DevBuf<uint64_t> lsh_sketch;
     DevBuf<char> sort_tmp, in_tmp;         // rocprim scratch of the seed stage / of the input decoding (compute stream)
     uint32_t ovf_cap = 0;
-    DevBuf<groot_trav> ovf_trav;           // align + order stage
-    DevBuf<uint64_t> ovf_mask;
-    DevBuf<uint32_t> trav_off, ovf_cnt;
-    DevBuf<char> scan_tmp;                 // rocprim scratch of the order stage (align stream)
+    DevBuf<uint32_t> trav_off;             // order stage (tail stream)
+    DevBuf<char> scan_tmp;                 // rocprim scratch of the order stage (tail stream)
+    DevBuf<char> sel_tmp;                  // rocprim scratch of the compaction behind the first pass (walk stream)
     // DFS stacks
     uint32_t align_threads = 0, stk_depth = 0;
     DevBuf<uint64_t> stk_hdr, stk_mask;
@@ -328,8 +336,8 @@ struct groot_ctx {
     std::map<std::vector<uint32_t>, uint64_t> ec_host;   // the exact S(r) of slow-path reads -> reads
 };
 
-// A ctx drives four HIP streams at once -- seed stage, align + order stage, copy-in, copy-out -- beside whatever the host process
-// uses itself.  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share one
+// A ctx drives five HIP streams at once -- seed stage, walk (first pass of the align stage), tail (align_kernel + order stage), copy-in,
+// copy-out -- beside whatever the host process uses itself.  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share one
 // run one after the other: with a fifth stream in the process the copy-in and the copy-out of neighbouring batches took turns
 // (host-fed rate 1 355 -> 717 Mreads/s).  Ask for eight before the runtime reads the setting (first HIP call of the process); a
 // value the user has set stands.
@@ -598,8 +606,10 @@ static int alloc_trav(groot_ctx *c, Slot *s, uint32_t cap)
 static int alloc_ovf(groot_ctx *c, uint32_t cap_per_shard)
 {
     c->ovf_cap = cap_per_shard;
-    HIP_TRY(c, c->ovf_trav.alloc((size_t)kOvfShards * cap_per_shard));
-    HIP_TRY(c, c->ovf_mask.alloc((size_t)kOvfShards * cap_per_shard * c->pw));
+    for (WorkSet &w : c->ws) {
+        HIP_TRY(c, w.ovf_trav.alloc((size_t)kOvfShards * cap_per_shard));
+        HIP_TRY(c, w.ovf_mask.alloc((size_t)kOvfShards * cap_per_shard * c->pw));
+    }
     return GROOT_OK;
 }
 
@@ -836,9 +846,9 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
     a.trav_first = w->trav_first.p;
     a.mask_first = w->mask_first.p;
     a.trav_cnt = w->trav_cnt.p;
-    a.ovf_trav = c->ovf_trav.p;
-    a.ovf_mask = c->ovf_mask.p;
-    a.ovf_cnt = c->ovf_cnt.p;
+    a.ovf_trav = w->ovf_trav.p;
+    a.ovf_mask = w->ovf_mask.p;
+    a.ovf_cnt = w->ovf_cnt.p;
     a.ovf_cap = c->ovf_cap;
     if (c->vcap) { a.vitem = w->vitem.p; a.vcount = w->vcount.p; a.vcap = c->vcap; }
     a.stk_hdr = c->stk_hdr.p;
@@ -856,8 +866,7 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
     // (the first pass takes most reads: what it left in the latest batch sizes the persistent grid of the second -- a wavefront per 64 reads left,
     // at least one workgroup per CU; the registers it does not hold go to the next batch's hashing kernels)
     // (only when a first pass runs for THIS batch: long-read and sparse batches keep the whole grid)
-    s->lean_used = c->lean && !c->tab_capture && s->n_reads && s->max_len <= kLeanMaxLen && c->dfs_frac >= 0.02;
-    s->path_used = c->path && !c->tab_capture && s->n_reads && s->max_len <= kLeanMaxLen && c->dfs_frac >= 0.02;
+    // (s->lean_used / s->path_used: run_batch_async decided them, and with them the stream the stage starts on)
     if ((s->lean_used || s->path_used) && c->lean_left_frac < 0.25) {
         uint32_t want = (uint32_t)(c->lean_left_frac * 1.25 * (double)s->n_reads / 64.0 / (kBlock / 64)) + 1u;
         blocks = std::max(1u, std::min(blocks, std::max(want, c->n_cu)));
@@ -872,7 +881,7 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
     }
     if (c->tab_capture) {
         a.incr_cnt = c->incr_cnt.p; a.incr_win = c->incr_win.p; a.incr_cap = c->incr_cap;
-        HIP_TRY(c, hipMemsetAsync(c->incr_cnt.p, 0, (size_t)s->n_reads * sizeof(uint32_t), c->astream));
+        HIP_TRY(c, hipMemsetAsync(c->incr_cnt.p, 0, (size_t)s->n_reads * sizeof(uint32_t), c->tstream));   // (no first pass while capturing: the whole stage is on the tail stream)
     }
     a.head_lanes = s->mixed_len ? 16u : 0u;              // (8: best at 2 M reads before the items of split reads took the head; 16: 2.9 / 5.2 ms at 2 M / 8 M reads, 8 gave 3.05 / 5.6)
     // (round 5: 48 when fewer than six reads in ten are walked -- reads with errors: some align at once, some fail through the hierarchy, and lanes that
@@ -890,14 +899,19 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
     if (const char *e = getenv("GROOT_DEV_ROUND")) a.round_lanes = (uint32_t)atoi(e);   // instrumented builds only (tools/slow_reads_probe.py: one read per round)
 #endif
     a.ctr = s->d_ctr.p;
-    HIP_TRY(c, hipMemsetAsync(c->ovf_cnt.p, 0, (kOvfShards + 2) * sizeof(uint32_t), c->astream));   // + the two chunk cursors
+    // Walk stream: the first pass and the compaction of what it left.  Tail stream: align_kernel and everything behind it -- the tail of batch b runs
+    // beside the first pass of batch b+1.  A batch without a first pass has no walk part: its whole stage goes on the tail stream, so that the
+    // persistent align_kernel launches (they share the DFS stacks) stay in order with one another.
+    const bool first_pass = s->lean_used || s->path_used;
+    hipStream_t walk = first_pass ? c->astream : c->tstream;
+    HIP_TRY(c, hipMemsetAsync(w->ovf_cnt.p, 0, (kOvfShards + 2) * sizeof(uint32_t), walk));   // + the two chunk cursors
     // First pass (kernels_lean.hpp): a thread per read in processing order finishes the reads of one seed window whose walks never branch;
     // the slots it leaves are flagged, a stream compaction keeps them in processing order, and align_kernel takes that list.
     const uint32_t lean_stride = lean_stride_dw(s->max_len);
     // (GROOT_LEAN=1: every batch that has reads to walk.  Measured, DESIGN.md section 3: alone on the chip the two passes take 2.2 + 0.7 ms where align_kernel
     // takes 3.0 on configs[2]; beside the next batch's hashing kernels the step is between 1.5 % shorter and 8 % longer from box to box, and batches of
     // mixed lengths or of reads with errors are slower -- hence off by default.)
-    if (s->lean_used || s->path_used) {
+    if (first_pass) {
         LeanArgs l{};
         l.nodes = c->lean_nodes.p; l.ext = c->lean_ext.p; l.bases2 = c->bases2.p; l.cn_pre2 = c->cn_pre2.p; l.win_ok = c->win_ok.p;
         l.win_rec = c->dix.win_rec; l.node_l2b = c->dix.node_l2b; l.q_row = c->q_row.p;
@@ -908,7 +922,7 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
         l.attempts = c->attempts_ptr;
         l.trav_first = w->trav_first.p; l.mask_first = w->mask_first.p; l.trav_cnt = w->trav_cnt.p;
         l.defer = w->defer.p; l.ctr = s->d_ctr.p;
-        l.stk = c->lean_stk.p; l.ovf_trav = c->ovf_trav.p; l.ovf_mask = c->ovf_mask.p; l.ovf_cnt = c->ovf_cnt.p; l.ovf_cap = c->ovf_cap;
+        l.stk = c->lean_stk.p; l.ovf_trav = w->ovf_trav.p; l.ovf_mask = w->ovf_mask.p; l.ovf_cnt = w->ovf_cnt.p; l.ovf_cap = c->ovf_cap;
         // workgroups for the reads expected to have seeds (the latest batch says how many: they come first in the processing order); the slots
         // beyond them, if the batch has more, go to align_kernel like the flagged ones
         const uint32_t lean_blocks = std::min<uint32_t>((s->n_reads + kBlock - 1) / kBlock, (uint32_t)(c->dfs_frac * 1.05 * (double)s->n_reads / kBlock) + 64u);
@@ -922,16 +936,20 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
         rocprim::counting_iterator<uint32_t> ids(0u);
         auto flags = rocprim::make_transform_iterator(ids, LeanLeft{w->defer.p, s->d_ctr.p, lean_blocks * (uint32_t)kBlock});
         HIP_TRY(c, rocprim::select(nullptr, tb, w->perm.p, flags, w->perm2.p, w->perm2_count.p, (size_t)s->n_reads, c->astream));
-        if (tb > c->scan_tmp.n) {
+        if (tb > c->sel_tmp.n) {           // (only the walk stream uses it)
             HIP_TRY(c, hipStreamSynchronize(c->astream));
-            HIP_TRY(c, c->scan_tmp.alloc(tb + tb / 4));
+            HIP_TRY(c, c->sel_tmp.alloc(tb + tb / 4));
         }
-        HIP_TRY(c, rocprim::select(c->scan_tmp.p, tb, w->perm.p, flags, w->perm2.p, w->perm2_count.p, (size_t)s->n_reads, c->astream));
+        HIP_TRY(c, rocprim::select(c->sel_tmp.p, tb, w->perm.p, flags, w->perm2.p, w->perm2_count.p, (size_t)s->n_reads, c->astream));
         a.perm = w->perm2.p;
         a.n_perm = w->perm2_count.p;
         if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[13], c->astream));
+        if (c->tstream != c->astream) {
+            HIP_TRY(c, hipEventRecord(s->ev_walk, c->astream));
+            HIP_TRY(c, hipStreamWaitEvent(c->tstream, s->ev_walk, 0));
+        }
     }
-    launch_align(c->pw, a, dim3(blocks), c->astream);
+    launch_align(c->pw, a, dim3(blocks), c->tstream);
     HIP_TRY(c, hipGetLastError());
     return GROOT_OK;
 }
@@ -943,15 +961,15 @@ static int launch_order_stage(groot_ctx *c, Slot *s, bool update_weights)
     const uint32_t n = s->n_reads;
     size_t tmp_bytes = 0;
     // split reads: their items' counts become the read's count, every item learns where its records go in the read's run
-    if (c->vcap) hipLaunchKernelGGL(split_fix_kernel, dim3(256), dim3(kBlock), 0, c->astream, w->split_list.p, w->vcount.p, w->vitem.p, w->trav_cnt.p, n, s->d_ctr.p,
+    if (c->vcap) hipLaunchKernelGGL(split_fix_kernel, dim3(256), dim3(kBlock), 0, c->tstream, w->split_list.p, w->vcount.p, w->vitem.p, w->trav_cnt.p, n, s->d_ctr.p,
                                     w->trav_first.p, w->mask_first.p, c->pw, s->first_read_id);
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_bytes, w->trav_cnt.p, c->trav_off.p, 0u, n, rocprim::plus<uint32_t>(), c->astream));
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_bytes, w->trav_cnt.p, c->trav_off.p, 0u, n, rocprim::plus<uint32_t>(), c->tstream));
     if (tmp_bytes > c->scan_tmp.n) {
-        HIP_TRY(c, hipStreamSynchronize(c->astream));
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
         HIP_TRY(c, c->scan_tmp.alloc(tmp_bytes + tmp_bytes / 4));
     }
-    HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tmp_bytes, w->trav_cnt.p, c->trav_off.p, 0u, n, rocprim::plus<uint32_t>(), c->astream));
-    hipLaunchKernelGGL(order_total_kernel, dim3(1), dim3(1), 0, c->astream, c->trav_off.p, w->trav_cnt.p, n, s->d_ctr.p);
+    HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tmp_bytes, w->trav_cnt.p, c->trav_off.p, 0u, n, rocprim::plus<uint32_t>(), c->tstream));
+    hipLaunchKernelGGL(order_total_kernel, dim3(1), dim3(1), 0, c->tstream, c->trav_off.p, w->trav_cnt.p, n, s->d_ctr.p);
     OrderTabArgs ot{};
     if (c->dix.out_tab) {
         ot.tab_idx = w->tab_idx.p; ot.out_tab = c->dix.out_tab; ot.stride_q = c->dix.out_stride_q; ot.first_read_id = s->first_read_id;
@@ -959,32 +977,32 @@ static int launch_order_stage(groot_ctx *c, Slot *s, bool update_weights)
         ot.attempts = c->attempts_ptr; ot.q_row = c->q_row.p;
         ot.q_tab = c->dix.w - c->k + 1; ot.n_windows = c->n_windows;
     }
-    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[9], c->astream));
-    hipLaunchKernelGGL(order_first_kernel, dim3(std::min<uint32_t>((n + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->astream, w->trav_first.p,
+    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[9], c->tstream));
+    hipLaunchKernelGGL(order_first_kernel, dim3(std::min<uint32_t>((n + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->tstream, w->trav_first.p,
                        w->mask_first.p, c->trav_off.p, w->trav_cnt.p, n, s->d_trav.p, s->d_mask.p, s->trav_cap, c->pw,
                        c->pw_view, s->d_ctr.p, ot);
-    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[10], c->astream));
-    if (c->vcap) hipLaunchKernelGGL(order_split_kernel, dim3(std::min<uint32_t>((c->vcap + kBlock - 1) / kBlock, 256u)), dim3(kBlock), 0, c->astream, w->vitem.p, w->vcount.p, c->vcap, w->trav_cnt.p,
+    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[10], c->tstream));
+    if (c->vcap) hipLaunchKernelGGL(order_split_kernel, dim3(std::min<uint32_t>((c->vcap + kBlock - 1) / kBlock, 256u)), dim3(kBlock), 0, c->tstream, w->vitem.p, w->vcount.p, c->vcap, w->trav_cnt.p,
                                     c->trav_off.p, w->trav_first.p, w->mask_first.p, n, s->first_read_id, s->d_trav.p, s->d_mask.p, s->trav_cap, c->pw, c->pw_view, s->d_ctr.p);
-    hipLaunchKernelGGL(order_ovf_kernel, dim3((c->ovf_cap + kBlock - 1) / kBlock, kOvfShards), dim3(kBlock), 0, c->astream,
-                       c->ovf_trav.p, c->ovf_mask.p, c->ovf_cnt.p, c->ovf_cap, c->trav_off.p, s->first_read_id, s->d_trav.p,
+    hipLaunchKernelGGL(order_ovf_kernel, dim3((c->ovf_cap + kBlock - 1) / kBlock, kOvfShards), dim3(kBlock), 0, c->tstream,
+                       w->ovf_trav.p, w->ovf_mask.p, w->ovf_cnt.p, c->ovf_cap, c->trav_off.p, s->first_read_id, s->d_trav.p,
                        s->d_mask.p, s->trav_cap, c->pw, c->pw_view, s->d_ctr.p, w->vitem.p, n);
     HIP_TRY(c, hipGetLastError());
     if (!c->prm.results_on_device) {
         // compact path sets for the copy-out (kernels.hpp): words per traversal, their exclusive scan, the copy
         const dim3 g((s->trav_cap + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(mask_words_kernel, g, dim3(kBlock), 0, c->astream, s->d_trav.p, s->d_ctr.p, s->trav_cap, c->graph_words.p, (uint32_t)c->h_graph_words.size(),
+        hipLaunchKernelGGL(mask_words_kernel, g, dim3(kBlock), 0, c->tstream, s->d_trav.p, s->d_ctr.p, s->trav_cap, c->graph_words.p, (uint32_t)c->h_graph_words.size(),
                            s->d_mwords.p);
         size_t tb = 0;
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tb, s->d_mwords.p, s->d_moff.p, 0u, s->trav_cap, rocprim::plus<uint32_t>(), c->astream));
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tb, s->d_mwords.p, s->d_moff.p, 0u, s->trav_cap, rocprim::plus<uint32_t>(), c->tstream));
         if (tb > c->scan_tmp.n) {
-            HIP_TRY(c, hipStreamSynchronize(c->astream));
+            HIP_TRY(c, hipStreamSynchronize(c->tstream));
             HIP_TRY(c, c->scan_tmp.alloc(tb + tb / 4));
         }
-        HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tb, s->d_mwords.p, s->d_moff.p, 0u, s->trav_cap, rocprim::plus<uint32_t>(), c->astream));
-        hipLaunchKernelGGL(mask_compact_kernel, g, dim3(kBlock), 0, c->astream, s->d_trav.p, s->d_mask.p, c->pw_view, s->d_ctr.p, s->trav_cap,
+        HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tb, s->d_mwords.p, s->d_moff.p, 0u, s->trav_cap, rocprim::plus<uint32_t>(), c->tstream));
+        hipLaunchKernelGGL(mask_compact_kernel, g, dim3(kBlock), 0, c->tstream, s->d_trav.p, s->d_mask.p, c->pw_view, s->d_ctr.p, s->trav_cap,
                            c->graph_words.p, (uint32_t)c->h_graph_words.size(), s->d_moff.p, s->d_cmask.p, s->d_ckpt.p);
-        if (c->packed_travs) hipLaunchKernelGGL(trav_pack_kernel, g, dim3(kBlock), 0, c->astream, s->d_trav.p, s->d_ctr.p, s->trav_cap, s->first_read_id, s->d_ctrav.p);
+        if (c->packed_travs) hipLaunchKernelGGL(trav_pack_kernel, g, dim3(kBlock), 0, c->tstream, s->d_trav.p, s->d_ctr.p, s->trav_cap, s->first_read_id, s->d_ctrav.p);
         HIP_TRY(c, hipGetLastError());
     }
     return GROOT_OK;
@@ -1010,8 +1028,8 @@ static hipError_t ec_alloc(groot_ctx *c, uint32_t cap, DevBuf<uint32_t> &claim, 
 }
 
 // Before a batch's merge: each batch adds at most n_reads keys, so the table must keep >= 2 x (the fill read back at the newest
-// collect + n_reads of every batch launched and not collected, this one included) slots -- else it doubles, rehashed in align-stream
-// order.  (Growth is rare -- a handful of times per run -- so the old buffers are freed behind a wait for the align stream.)
+// collect + n_reads of every batch launched and not collected, this one included) slots -- else it doubles, rehashed in tail-stream
+// order.  (Growth is rare -- a handful of times per run -- so the old buffers are freed behind a wait for the tail stream.)
 static int ec_reserve(groot_ctx *c, Slot *s)
 {
     uint64_t pending = s->n_reads;
@@ -1025,13 +1043,13 @@ static int ec_reserve(groot_ctx *c, Slot *s)
     DevBuf<uint32_t> claim, graph;
     DevBuf<uint64_t> mask;
     DevBuf<unsigned long long> cnt;
-    hipError_t e = ec_alloc(c, (uint32_t)cap, claim, graph, mask, cnt, c->astream);
+    hipError_t e = ec_alloc(c, (uint32_t)cap, claim, graph, mask, cnt, c->tstream);
     if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "equivalence classes: growing the table to %llu slots: %s", (unsigned long long)cap, hipGetErrorString(e));
     const EcTable from = ec_table(c), to{claim.p, graph.p, mask.p, cnt.p, (uint32_t)cap - 1};
-    hipLaunchKernelGGL(ec_rehash_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->astream,
+    hipLaunchKernelGGL(ec_rehash_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
                        from, c->ec_cap, to, std::max<uint32_t>(c->pw_view, 1u), ++c->ec_epoch);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->astream));
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
     c->ec_claim.swap(claim); c->ec_graph.swap(graph); c->ec_mask.swap(mask); c->ec_cnt.swap(cnt);
     c->ec_cap = (uint32_t)cap;
     c->ec_grows++;
@@ -1117,24 +1135,28 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
     if (int rc = launch_seed_stage(c, s, update_weights)) return rc;
     if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[3], c->stream));
     HIP_TRY(c, hipEventRecord(s->ev_seed, c->stream));
-    // align stream: graph walk and ordering, beside the seed stage of the next batch
-    HIP_TRY(c, hipStreamWaitEvent(c->astream, s->ev_seed, 0));
-    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[11], c->astream));
+    // walk + tail streams: graph walk and ordering, beside the seed stage of the next batch.  The stage starts on the walk stream when a first
+    // pass runs for this batch (launch_align_stage moves to the tail stream behind it), on the tail stream otherwise.
+    s->lean_used = c->lean && !c->tab_capture && s->n_reads && s->max_len <= kLeanMaxLen && c->dfs_frac >= 0.02;
+    s->path_used = c->path && !c->tab_capture && s->n_reads && s->max_len <= kLeanMaxLen && c->dfs_frac >= 0.02;
+    hipStream_t start = s->lean_used || s->path_used ? c->astream : c->tstream;
+    HIP_TRY(c, hipStreamWaitEvent(start, s->ev_seed, 0));
+    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[11], start));
     if (int rc = launch_align_stage(c, s, update_weights)) return rc;
-    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[4], c->astream));
+    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[4], c->tstream));
     if (int rc = launch_order_stage(c, s, update_weights)) return rc;
-    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[5], c->astream));
-    HIP_TRY(c, hipEventRecord(w->ev_free, c->astream));
+    if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[5], c->tstream));
+    HIP_TRY(c, hipEventRecord(w->ev_free, c->tstream));
     if (c->cov_on) {   // (reads the slot's records and read offsets only: the next batch's seed stage need not wait for it)
         CovArgs ca{};
         ca.trav = s->d_trav.p; ca.mask = s->d_mask.p; ca.seq_off = s->off(); ca.ctr = s->d_ctr.p;
         ca.node_np_off = c->cov_np_off.p; ca.np = c->cov_np.p; ca.graph_path_off = c->cov_gpo.p; ca.path_len = c->cov_len.p; ca.slot_base = c->cov_base.p;
         ca.starts = c->cov_starts.p; ca.ends = c->cov_ends.p;
         ca.cap = s->trav_cap; ca.pw = c->pw_view; ca.first_read_id = s->first_read_id;
-        hipLaunchKernelGGL(cov_count_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->astream, ca);
+        hipLaunchKernelGGL(cov_count_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream, ca);
         HIP_TRY(c, hipGetLastError());
     }
-    if (c->sh_on || c->ec_on) {    // (the same: slot data and the ctx's own buffers, in align-stream order)
+    if (c->sh_on || c->ec_on) {    // (the same: slot data and the ctx's own buffers, in tail-stream order)
         SharedArgs sa{};
         sa.trav = s->d_trav.p; sa.mask = s->d_mask.p; sa.ctr = s->d_ctr.p; sa.graph_path_off = c->sh_gpo.p;
         sa.set_graph = c->sh_set_graph.p; sa.set_mask = c->sh_set_mask.p; sa.tab_rep = c->sh_tab_rep.p; sa.tab_cnt = c->sh_tab_cnt.p;
@@ -1146,17 +1168,17 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
         while (tab < 2u * std::max<uint32_t>(s->n_reads, 1u)) tab <<= 1;
         sa.tab_mask = tab - 1;
         const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
-        hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->astream, sa);
-        hipLaunchKernelGGL(shared_insert_kernel, g, dim3(kBlock), 0, c->astream, sa);
-        if (c->sh_on) hipLaunchKernelGGL(shared_slow_kernel, dim3(256), dim3(kBlock), 0, c->astream, sa);
+        hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->tstream, sa);
+        hipLaunchKernelGGL(shared_insert_kernel, g, dim3(kBlock), 0, c->tstream, sa);
+        if (c->sh_on) hipLaunchKernelGGL(shared_slow_kernel, dim3(256), dim3(kBlock), 0, c->tstream, sa);
         if (c->ec_on) {
             if (int rc = ec_reserve(c, s)) return rc;
             HIP_TRY(c, s->d_ec_slow.reserve(1 + 2 * (size_t)c->prm.max_batch_reads));
             HIP_TRY(c, s->h_ec.reserve(2));
-            hipLaunchKernelGGL(ec_merge_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->astream, sa, ec_table(c),
+            hipLaunchKernelGGL(ec_merge_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->tstream, sa, ec_table(c),
                                tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p);
         }
-        hipLaunchKernelGGL(shared_expand_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->astream, sa, tab);
+        hipLaunchKernelGGL(shared_expand_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->tstream, sa, tab);
         HIP_TRY(c, hipGetLastError());
     }
     w->used = true;
@@ -1248,6 +1270,7 @@ static int enqueue(groot_ctx *c, Slot *s)
     memset(&s->counts, 0, sizeof s->counts);
     memset(&s->ms, 0, sizeof s->ms);
     s->ticket = c->next_ticket++;
+    s->lean_used = s->path_used = false; s->path_reads = 0;   // (an empty batch runs no stage: not what the slot's last batch left)
     if (s->n_reads == 0) {      // nothing to run: completes at once
         memset(s->h_ctr.p, 0, sizeof(DeviceCounters));
         HIP_TRY(c, hipEventRecord(s->ev_ctr, c->d2h_stream));
@@ -1315,7 +1338,7 @@ static int enqueue(groot_ctx *c, Slot *s)
     s->set = c->next_set;
     c->next_set ^= 1u;
     if (int rc = run_batch_async(c, s, true)) return rc;
-    HIP_TRY(c, hipEventRecord(s->ev_compute, c->astream));
+    HIP_TRY(c, hipEventRecord(s->ev_compute, c->tstream));
     c->last_compute = s->ev_compute;
     c->newest = s;
     // Copy-out on its own stream with no host in between.  The record count is only known on the device, and asking for it
@@ -1392,8 +1415,8 @@ static int finish_counters(groot_ctx *c, Slot *s)
 {
     DeviceCounters &h = *s->h_ctr.p;
     auto refetch = [&](DeviceCounters &dst) -> int {
-        HIP_TRY(c, hipMemcpyAsync(s->h_ctr.p, s->d_ctr.p, sizeof(DeviceCounters), hipMemcpyDeviceToHost, c->astream));
-        HIP_TRY(c, hipStreamSynchronize(c->astream));
+        HIP_TRY(c, hipMemcpyAsync(s->h_ctr.p, s->d_ctr.p, sizeof(DeviceCounters), hipMemcpyDeviceToHost, c->tstream));
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
         dst = *s->h_ctr.p;
         return GROOT_OK;
     };
@@ -1409,6 +1432,7 @@ static int finish_counters(groot_ctx *c, Slot *s)
         // after any other overflow the weights and read counters of the first pass stand and only records are re-made.
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->astream));
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
         bool redo_weights = !have_first;
         if (fl & (kFlagSeedOverflow | kFlagQOverflow)) {
             if (fl & kFlagSeedOverflow) { if (int rc = alloc_seed_slots(c, h.max_seeds + 4)) return rc; }
@@ -1609,6 +1633,7 @@ static int drain(groot_ctx *c)     // everything submitted has finished on the d
     if (!c->inflight.empty()) { if (int rc = progress(c, c->inflight.back())) return rc; }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->astream));
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
     HIP_TRY(c, hipStreamSynchronize(c->d2h_stream));
     return GROOT_OK;
 }
@@ -1653,10 +1678,11 @@ void groot_hip_close(groot_ctx *ctx)
     if (ctx->bg_stream) { (void)hipStreamSynchronize(ctx->bg_stream); (void)hipStreamDestroy(ctx->bg_stream); }
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->astream) (void)hipStreamSynchronize(ctx->astream);
+    if (ctx->tstream) (void)hipStreamSynchronize(ctx->tstream);
     if (ctx->h2d_stream) (void)hipStreamSynchronize(ctx->h2d_stream);
     if (ctx->d2h_stream) (void)hipStreamSynchronize(ctx->d2h_stream);
     for (auto &s : ctx->slots) {
-        for (hipEvent_t e : {s->ev_seed, s->ev_h2d0, s->ev_h2d, s->ev_compute, s->ev_ctr, s->ev_d2h0, s->ev_d2h})
+        for (hipEvent_t e : {s->ev_seed, s->ev_walk, s->ev_h2d0, s->ev_h2d, s->ev_compute, s->ev_ctr, s->ev_d2h0, s->ev_d2h})
             if (e) (void)hipEventDestroy(e);
         for (auto &e : s->ev)
             if (e) (void)hipEventDestroy(e);
@@ -1666,6 +1692,7 @@ void groot_hip_close(groot_ctx *ctx)
         if (w.ev_free) (void)hipEventDestroy(w.ev_free);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     if (ctx->astream) (void)hipStreamDestroy(ctx->astream);
+    if (ctx->own_tstream) (void)hipStreamDestroy(ctx->own_tstream);
     if (ctx->h2d_stream) (void)hipStreamDestroy(ctx->h2d_stream);
     if (ctx->d2h_stream) (void)hipStreamDestroy(ctx->d2h_stream);
     delete ctx;
@@ -2398,6 +2425,14 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         if (hipStreamCreateWithPriority(&c->astream, hipStreamNonBlocking, lo) != hipSuccess)
             HIP_TRY(c, hipStreamCreateWithFlags(&c->astream, hipStreamNonBlocking));
+        // the tail stream, at the same priority: the tail of batch b beside the first pass of batch b+1 (GROOT_SERIAL_TAIL=1: one stream for both, as
+        // before the split -- every "tail stream" below is then the walk stream)
+        if (c->kn.serial_tail) c->tstream = c->astream;
+        else {
+            if (hipStreamCreateWithPriority(&c->own_tstream, hipStreamNonBlocking, lo) != hipSuccess)
+                HIP_TRY(c, hipStreamCreateWithFlags(&c->own_tstream, hipStreamNonBlocking));
+            c->tstream = c->own_tstream;
+        }
     }
     for (WorkSet &w : c->ws) HIP_TRY(c, hipEventCreateWithFlags(&w.ev_free, hipEventDisableTiming));
     HIP_TRY(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
@@ -2406,7 +2441,7 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
     c->build_dix = &c->dix; c->build_stream = c->stream;
     for (uint32_t i = 0; i < c->prm.pipeline_depth; i++) {
         std::unique_ptr<Slot> s(new Slot());
-        for (hipEvent_t *e : {&s->ev_seed, &s->ev_h2d0, &s->ev_h2d, &s->ev_compute, &s->ev_ctr, &s->ev_d2h0, &s->ev_d2h}) HIP_TRY(c, hipEventCreate(e));
+        for (hipEvent_t *e : {&s->ev_seed, &s->ev_walk, &s->ev_h2d0, &s->ev_h2d, &s->ev_compute, &s->ev_ctr, &s->ev_d2h0, &s->ev_d2h}) HIP_TRY(c, hipEventCreate(e));
         for (auto &e : s->ev) HIP_TRY(c, hipEventCreate(&e));
         c->slots.push_back(std::move(s));
     }
@@ -2814,7 +2849,7 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
     HIP_TRY(c, c->trav_off.alloc(R));
     if (c->lean || c->path) HIP_TRY(c, c->lean_stk.alloc((size_t)R * 4));
     if (c->path) HIP_TRY(c, c->path_hold.alloc((size_t)R * 3 * kPathHold));
-    HIP_TRY(c, c->ovf_cnt.alloc(kOvfShards + 2));
+    for (WorkSet &w : c->ws) HIP_TRY(c, w.ovf_cnt.alloc(kOvfShards + 2));
     if (int rc = alloc_ovf(c, c->kn.small_buffers ? 2u : std::max<uint32_t>(256, R / kOvfShards / 4))) return rc;
     // the align kernel is persistent: exactly the workgroups that are resident at once (GROOT_ALIGN_WAVES per SIMD = per CU)
     int n_cu = 256;
@@ -3682,10 +3717,10 @@ int groot_hip_ec_enable(groot_ctx *c, int on)
     while (cap < (c->kn.ec_slots ? std::max<uint32_t>(c->kn.ec_slots, 2u) : (1u << 16))) cap <<= 1;
     auto undo = [&](int rc) { c->ec_on = true; groot_hip_ec_enable(c, 0); return rc; };
     hipError_t e = sh_common_alloc(c);
-    if (e == hipSuccess) e = ec_alloc(c, cap, c->ec_claim, c->ec_graph, c->ec_mask, c->ec_cnt, c->astream);
+    if (e == hipSuccess) e = ec_alloc(c, cap, c->ec_claim, c->ec_graph, c->ec_mask, c->ec_cnt, c->tstream);
     if (e == hipSuccess) e = c->ec_fill.alloc(1);
-    if (e == hipSuccess) e = hipMemsetAsync(c->ec_fill.p, 0, sizeof(uint32_t), c->astream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->astream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->ec_fill.p, 0, sizeof(uint32_t), c->tstream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->tstream);
     if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "equivalence classes: %s", hipGetErrorString(e)));
     c->ec_cap = cap;
     c->ec_fill_known = c->ec_grows = c->ec_slow_reads = 0;
@@ -3710,11 +3745,11 @@ static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &ou
     HIP_TRY(c, m.alloc((size_t)fill * kSharedSegs * pw));
     HIP_TRY(c, cnt.alloc(fill));
     HIP_TRY(c, n.alloc(1));
-    HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->astream));
-    hipLaunchKernelGGL(ec_export_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->astream,
+    HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->tstream));
+    hipLaunchKernelGGL(ec_export_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
                        ec_table(c), c->ec_cap, pw, g.p, m.p, cnt.p, n.p, fill);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->astream));
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
     uint32_t got = 0;
     HIP_TRY(c, hipMemcpy(&got, n.p, sizeof got, hipMemcpyDeviceToHost));
     if (got != fill) return fail(c, GROOT_E_DEVICE, "equivalence classes: %u keys in a table that counted %u", got, fill);
