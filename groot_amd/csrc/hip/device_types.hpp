@@ -284,7 +284,8 @@ struct AlignArgs {
     uint32_t *trav_cnt;          // [n_reads] traversals emitted for read r
     groot_trav *ovf_trav;        // [kOvfShards][ovf_cap]
     uint64_t *ovf_mask;          // [kOvfShards*ovf_cap*pw]
-    uint32_t *ovf_cnt;           // [kOvfShards] list lengths, then [kOvfShards], [kOvfShards+1] = cursors over the sorted slots (align_kernel)
+    uint32_t *ovf_cnt;           // [kOvfShards] list lengths, then [kOvfShards], [kOvfShards+1] = cursors over the sorted slots (align_kernel),
+                                 // then [kOvfShards+2] = length of the list the first pass left (LeanArgs::left_cnt)
     uint32_t ovf_cap;
     // DFS stacks: entry d of thread t lives at [d*n_threads + t]
     uint64_t *stk_hdr;
@@ -303,7 +304,11 @@ struct AlignArgs {
     const uint4 *vitem;
     const uint32_t *vcount;
     uint32_t vcap;
-    const uint32_t *n_perm;      // entries of perm when it is the list the first pass left (align_lean_kernel + stream compaction); null: DeviceCounters::seeded_reads
+    const uint32_t *n_perm;      // entries of perm when it is the list the first pass left (LeanArgs::left, LeanArgs::left_cnt); null: DeviceCounters::seeded_reads
+    // behind a first pass whose grid was narrower than the reads with seeds: slots [rest_lo, seeded_reads) of the processing order `rest`
+    // follow the list (slot *n_perm + i is rest[rest_lo + i]); without a first pass rest is null
+    const uint32_t *rest;
+    uint32_t rest_lo;
     uint32_t refill;             // waiting lanes that make a wavefront take new reads: 64 (all of them) for batches of one read length, 32 for mixed ones
     DeviceCounters *ctr;
 };
@@ -354,7 +359,8 @@ struct LeanArgs {
     groot_trav *trav_first;
     uint64_t *mask_first;
     uint32_t *trav_cnt;
-    uint8_t *defer;                // [n_reads] by slot: 1 = left to align_kernel
+    uint32_t *left;                // [n_reads] the reads left to align_kernel, in the order the wavefronts finished (AlignArgs::perm of the second pass)
+    uint32_t *left_cnt;            // their number: ovf_cnt[kOvfShards + 2], cleared with the overflow lists' lengths
     uint4 *stk;                    // [n_reads][2][2] by slot: pending neighbours of the walk {node | long << 31, dist, path set}
     groot_trav *ovf_trav;          // AlignArgs::ovf_* (traversals with ord >= 1)
     uint64_t *ovf_mask;

@@ -116,7 +116,7 @@ struct Slot {
     bool lean_used = false;                // align_lean_kernel ran in front of align_kernel for this batch
     bool path_used = false;                // align_path_kernel ran in front of align_kernel for this batch
     uint32_t path_reads = 0;               // ... and finished this many reads
-    float path_ms = 0;                     // ... in this time (profiling on: the pass + its stream compaction)
+    float path_ms = 0;                     // ... in this time (profiling on: the pass, which also appends the list of the reads it leaves)
     bool one_len = false;                  // the reads are known to have max_len bases each, or the caller said so (submit_device with max_len)
     uint64_t n_bases = 0, n_exc = 0;
     enum Input { IN_ASCII, IN_PACKED, IN_PACKED16, IN_DEVICE } input = IN_ASCII;
@@ -150,7 +150,7 @@ struct Slot {
     uint64_t n_mask_bytes = 0, copied_bytes = 0;
     bool host_results = false;             // the traversal records of this batch are in h_trav / h_mask
     hipEvent_t ev_seed = nullptr;          // behind the batch's seed stage on the compute stream: its align stage waits for it
-    hipEvent_t ev_walk = nullptr;          // behind the batch's first pass and its compaction on the walk stream: its tail waits for it
+    hipEvent_t ev_walk = nullptr;          // behind the batch's first pass (which appends the list of the reads it leaves) on the walk stream: its tail waits for it
     hipEvent_t ev_h2d0 = nullptr, ev_h2d = nullptr, ev_compute = nullptr, ev_ctr = nullptr, ev_d2h0 = nullptr, ev_d2h = nullptr;
     hipEvent_t ev[14]{};                   // [7..8] around the first seed kernel, [9..10] around order_first_kernel, [11] start of the align stage (align stream), [12] behind the list pass
                                            // [0..6] stage boundaries on the compute stream (profiling)
@@ -167,8 +167,7 @@ struct Slot {
 // One of the two sets of buffers a batch's seed stage fills for its align and order stages (groot_ctx::ws)
 struct WorkSet {
     DevBuf<uint32_t> seed_count, seed_win, perm, perm_count, trav_cnt, tab_idx;
-    DevBuf<uint32_t> perm2, perm2_count;                 // the slots align_lean_kernel left, in processing order, and how many
-    DevBuf<uint8_t> defer;                               // LeanArgs::defer
+    DevBuf<uint32_t> perm2;                              // the reads the first pass left (LeanArgs::left); their number is ovf_cnt[kOvfShards + 2]
     DevBuf<uint4> packed;                                // SeedArgs::packed
     DevBuf<ReadRec> read_rec;
     DevBuf<uint4> vitem, split_list;                     // AlignArgs::vitem, sort_seed_lists_kernel
@@ -195,7 +194,7 @@ struct groot_ctx {
     hipEvent_t h2d_last = nullptr;         // the copy-in of the newest host-fed batch (its slot's event)
     Slot *newest = nullptr;                // the newest submitted batch (groot_hip_redo_status)
     hipEvent_t last_compute = nullptr;     // behind the order stage of the newest batch, on the tail stream (groot_hip_stream_join)
-    // stream: seed stage (the caller's, if given); astream: the walk stream (first pass of the align stage + the compaction of what it left);
+    // stream: seed stage (the caller's, if given); astream: the walk stream (first pass of the align stage, which appends the list of what it leaves);
     // tstream: the tail stream (align_kernel, order stage, host-copy and counting kernels) -- astream itself under GROOT_SERIAL_TAIL=1
     hipStream_t own_stream = nullptr, stream = nullptr, astream = nullptr, tstream = nullptr, own_tstream = nullptr, h2d_stream = nullptr, d2h_stream = nullptr;
     bool profiling = false;
@@ -298,7 +297,6 @@ struct groot_ctx {
     uint32_t ovf_cap = 0;
     DevBuf<uint32_t> trav_off;             // order stage (tail stream)
     DevBuf<char> scan_tmp;                 // rocprim scratch of the order stage (tail stream)
-    DevBuf<char> sel_tmp;                  // rocprim scratch of the compaction behind the first pass (walk stream)
     // DFS stacks
     uint32_t align_threads = 0, stk_depth = 0;
     DevBuf<uint64_t> stk_hdr, stk_mask;
@@ -653,6 +651,30 @@ static uint32_t list_lds_stride(uint32_t stride_dw)
 #ifndef GROOT_SORTLIST_BLOCKS
 #define GROOT_SORTLIST_BLOCKS 16384
 #endif
+// The processing-order sort runs beside the previous batch's first pass, whose 256-thread workgroups hold the whole register file of every CU.
+// rocprim's default onesweep for gfx950 (1 024 threads, 16 items) needs four free wavefront places on every SIMD of a CU at once, which happens
+// only when the first pass runs dry: the sort waited for it.  256-thread workgroups (one wavefront per SIMD) fit the hole one retiring first-pass
+// workgroup leaves.  Same digits (8 bits), same stable ranking: perm is bit-identical.  
+// Which rocprim algorithm a batch of n reads takes under this configuration: n <= 1 024 the single-block sort (256 x 4, rocprim's default), n <= GROOT_SORT_MERGE_LIMIT
+// rocprim's merge sort (default configuration), above it the onesweep configured here.  rocprim's own limit is 2^20; 2 048 = two blocks of the single sort,
+// so that every batch that needs more than a handful of workgroups gets the kernels that fit beside the first pass, and so that the suite reaches them
+// with small batches (tests/test_order_handoff.py).  All three are stable sorts of the same bits.  List-mode batches (few reads walked) are not sorted at all.
+#ifndef GROOT_SORT_ITEMS
+#define GROOT_SORT_ITEMS 16
+#endif
+#ifndef GROOT_SORT_MERGE_LIMIT
+#define GROOT_SORT_MERGE_LIMIT 2048
+#endif
+using OrderSortConfig = rocprim::radix_sort_config<
+    rocprim::default_config, rocprim::default_config,
+    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<256, GROOT_SORT_ITEMS>, rocprim::kernel_config<256, GROOT_SORT_ITEMS>, 8,
+                                        rocprim::block_radix_rank_algorithm::match>,
+    GROOT_SORT_MERGE_LIMIT>;
+
+// a batch of one read length of which fewer than six reads in ten (but not next to none) are walked, by the latest finished batch: reads with errors --
+// the exact ones seed, the others do not.  The hashing kernels of the next batch are the longer stage there.
+static bool error_batch(const groot_ctx *c, const Slot *s) { return c->dfs_frac >= kSparseBelow && c->dfs_frac < 0.6 && !s->mixed_len; }
+
 static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
 {
     WorkSet *w = &c->ws[s->set];
@@ -805,25 +827,23 @@ static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
     size_t tmp_bytes = 0;
     // keys are (window << 2 | class) below 2^end_bit, or 0xFFFFFFFF for reads without seeds: sorting the low
     // end_bit bits keeps those last as long as bit end_bit-1.. are all ones for them, which they are
-    HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, c->sort_key.p, c->sort_key_out.p, c->perm_in.p, w->perm.p, s->n_reads, begin_bit,
-                                         end_bit, c->stream));
+    // (batches of one read length of which fewer than six reads in ten are walked -- reads with errors: the previous batch's first pass is the shorter
+    // stage there and the sort does not wait for it; the small blocks cost 0.1 ms alone and 3 % of that workload's rate, so it keeps rocprim's default)
+    const bool small_blocks = !error_batch(c, s);
+    auto sort = [&](void *tmp) {
+        return small_blocks ? rocprim::radix_sort_pairs<OrderSortConfig>(tmp, tmp_bytes, c->sort_key.p, c->sort_key_out.p, c->perm_in.p, w->perm.p, s->n_reads,
+                                                                         begin_bit, end_bit, c->stream)
+                            : rocprim::radix_sort_pairs(tmp, tmp_bytes, c->sort_key.p, c->sort_key_out.p, c->perm_in.p, w->perm.p, s->n_reads, begin_bit, end_bit,
+                                                        c->stream);
+    };
+    HIP_TRY(c, sort(nullptr));
     if (tmp_bytes > c->sort_tmp.n) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, c->sort_tmp.alloc(tmp_bytes + tmp_bytes / 4));
     }
-    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, c->sort_key.p, c->sort_key_out.p, c->perm_in.p, w->perm.p,
-                                         s->n_reads, begin_bit, end_bit, c->stream));
+    HIP_TRY(c, sort(c->sort_tmp.p));
     return GROOT_OK;
 }
-
-// which slots of the processing order does align_kernel take after the first pass?  Those the first pass flagged, and those it did not get to
-// (its grid is sized by the latest batch: slots beyond it)
-struct LeanLeft {
-    const uint8_t *defer;
-    const DeviceCounters *ctr;
-    uint32_t lean_slots;
-    __device__ uint8_t operator()(uint32_t i) const { return i < ctr->seeded_reads && (i >= lean_slots || defer[i]) ? 1 : 0; }
-};
 
 static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
 {
@@ -862,7 +882,7 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
     // (round 5: when fewer than six reads in ten need the walk -- reads with errors: the exact ones seed, the others do not -- the hashing kernels of the
     // next batch are the longer stage, and a persistent grid of two workgroups per CU leaves them half the registers: configs[2] with 1 % substitutions
     // 2 345 -> 2 680 Mreads/s; no difference on mixed-length batches; on error-free reads, where every read is walked, the full grid is 4 % faster)
-    else if (c->dfs_frac >= kSparseBelow && c->dfs_frac < 0.6 && !s->mixed_len && blocks >= 4) blocks /= 2;
+    else if (error_batch(c, s) && blocks >= 4) blocks /= 2;
     // (the first pass takes most reads: what it left in the latest batch sizes the persistent grid of the second -- a wavefront per 64 reads left,
     // at least one workgroup per CU; the registers it does not hold go to the next batch's hashing kernels)
     // (only when a first pass runs for THIS batch: long-read and sparse batches keep the whole grid)
@@ -894,19 +914,19 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
 #define GROOT_REFILL_MIXED 2      // mixed read lengths: a lane that has finished takes its next read at once -- no rounds (2 / 8 / 16 / 32 / 48: 1 258 / 1 253 / 1 249 / 1 208 /
                                   // 1 172 Mreads/s at t = 0.99 on 8 M reads of 75..150 bases, 694 / 678 / 680 / 676 / 653 at t = 0.90; batches of 2 M: 850-890 -> 912)
 #endif
-    a.refill = s->mixed_len ? (uint32_t)GROOT_REFILL_MIXED : (c->dfs_frac >= kSparseBelow && c->dfs_frac < 0.6 ? (uint32_t)GROOT_REFILL_ERR : 64u);                   // reads of many lengths finish their walks far apart (tools/mixed_probe.py)
+    a.refill = s->mixed_len ? (uint32_t)GROOT_REFILL_MIXED : (error_batch(c, s) ? (uint32_t)GROOT_REFILL_ERR : 64u);                   // reads of many lengths finish their walks far apart (tools/mixed_probe.py)
 #ifdef GROOT_WORK_COUNTERS
     if (const char *e = getenv("GROOT_DEV_ROUND")) a.round_lanes = (uint32_t)atoi(e);   // instrumented builds only (tools/slow_reads_probe.py: one read per round)
 #endif
     a.ctr = s->d_ctr.p;
-    // Walk stream: the first pass and the compaction of what it left.  Tail stream: align_kernel and everything behind it -- the tail of batch b runs
+    // Walk stream: the first pass, which appends the list of what it leaves.  Tail stream: align_kernel and everything behind it -- the tail of batch b runs
     // beside the first pass of batch b+1.  A batch without a first pass has no walk part: its whole stage goes on the tail stream, so that the
     // persistent align_kernel launches (they share the DFS stacks) stay in order with one another.
     const bool first_pass = s->lean_used || s->path_used;
     hipStream_t walk = first_pass ? c->astream : c->tstream;
-    HIP_TRY(c, hipMemsetAsync(w->ovf_cnt.p, 0, (kOvfShards + 2) * sizeof(uint32_t), walk));   // + the two chunk cursors
+    HIP_TRY(c, hipMemsetAsync(w->ovf_cnt.p, 0, (kOvfShards + 3) * sizeof(uint32_t), walk));   // + the two chunk cursors + the length of the first pass's list
     // First pass (kernels_lean.hpp): a thread per read in processing order finishes the reads of one seed window whose walks never branch;
-    // the slots it leaves are flagged, a stream compaction keeps them in processing order, and align_kernel takes that list.
+    // the reads it leaves it appends to a list (a wavefront at a time, in the order the wavefronts finish), and align_kernel takes that list.
     const uint32_t lean_stride = lean_stride_dw(s->max_len);
     // (GROOT_LEAN=1: every batch that has reads to walk.  Measured, DESIGN.md section 3: alone on the chip the two passes take 2.2 + 0.7 ms where align_kernel
     // takes 3.0 on configs[2]; beside the next batch's hashing kernels the step is between 1.5 % shorter and 8 % longer from box to box, and batches of
@@ -921,10 +941,10 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
         l.lds_stride_dw = lean_stride; l.max_len = s->max_len;
         l.attempts = c->attempts_ptr;
         l.trav_first = w->trav_first.p; l.mask_first = w->mask_first.p; l.trav_cnt = w->trav_cnt.p;
-        l.defer = w->defer.p; l.ctr = s->d_ctr.p;
+        l.left = w->perm2.p; l.left_cnt = w->ovf_cnt.p + kOvfShards + 2; l.ctr = s->d_ctr.p;
         l.stk = c->lean_stk.p; l.ovf_trav = w->ovf_trav.p; l.ovf_mask = w->ovf_mask.p; l.ovf_cnt = w->ovf_cnt.p; l.ovf_cap = c->ovf_cap;
         // workgroups for the reads expected to have seeds (the latest batch says how many: they come first in the processing order); the slots
-        // beyond them, if the batch has more, go to align_kernel like the flagged ones
+        // beyond them, if the batch has more, go to align_kernel behind the list (AlignArgs::rest: addressed in place, not copied)
         const uint32_t lean_blocks = std::min<uint32_t>((s->n_reads + kBlock - 1) / kBlock, (uint32_t)(c->dfs_frac * 1.05 * (double)s->n_reads / kBlock) + 64u);
         if (s->path_used) {
             l.path_node = c->path_node.p; l.path_text = c->path_text.p; l.path_tag = c->path_tag.p; l.path_nodes = c->path_nodes.p; l.path_tab = c->path_tab.p;
@@ -932,17 +952,10 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
             launch_align_path(c->pw, l, dim3(lean_blocks), c->astream);
         } else launch_align_lean(c->pw, l, dim3(lean_blocks), c->astream);
         HIP_TRY(c, hipGetLastError());
-        size_t tb = 0;
-        rocprim::counting_iterator<uint32_t> ids(0u);
-        auto flags = rocprim::make_transform_iterator(ids, LeanLeft{w->defer.p, s->d_ctr.p, lean_blocks * (uint32_t)kBlock});
-        HIP_TRY(c, rocprim::select(nullptr, tb, w->perm.p, flags, w->perm2.p, w->perm2_count.p, (size_t)s->n_reads, c->astream));
-        if (tb > c->sel_tmp.n) {           // (only the walk stream uses it)
-            HIP_TRY(c, hipStreamSynchronize(c->astream));
-            HIP_TRY(c, c->sel_tmp.alloc(tb + tb / 4));
-        }
-        HIP_TRY(c, rocprim::select(c->sel_tmp.p, tb, w->perm.p, flags, w->perm2.p, w->perm2_count.p, (size_t)s->n_reads, c->astream));
         a.perm = w->perm2.p;
-        a.n_perm = w->perm2_count.p;
+        a.n_perm = l.left_cnt;
+        a.rest = w->perm.p;
+        a.rest_lo = lean_blocks * (uint32_t)kBlock;
         if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[13], c->astream));
         if (c->tstream != c->astream) {
             HIP_TRY(c, hipEventRecord(s->ev_walk, c->astream));
@@ -2833,8 +2846,6 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
         HIP_TRY(c, w.perm_count.alloc(4));
         if (c->lean || c->path) {
             HIP_TRY(c, w.perm2.alloc(R));
-            HIP_TRY(c, w.perm2_count.alloc(4));
-            HIP_TRY(c, w.defer.alloc(R));
             HIP_TRY(c, w.packed.alloc((size_t)R * (c->prm.max_read_len <= 128 ? 2 : 4)));
         }
         if (c->prm.keep_sketches) HIP_TRY(c, w.sketches.alloc((size_t)R * s));
@@ -2849,7 +2860,7 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
     HIP_TRY(c, c->trav_off.alloc(R));
     if (c->lean || c->path) HIP_TRY(c, c->lean_stk.alloc((size_t)R * 4));
     if (c->path) HIP_TRY(c, c->path_hold.alloc((size_t)R * 3 * kPathHold));
-    for (WorkSet &w : c->ws) HIP_TRY(c, w.ovf_cnt.alloc(kOvfShards + 2));
+    for (WorkSet &w : c->ws) HIP_TRY(c, w.ovf_cnt.alloc(kOvfShards + 3));
     if (int rc = alloc_ovf(c, c->kn.small_buffers ? 2u : std::max<uint32_t>(256, R / kOvfShards / 4))) return rc;
     // the align kernel is persistent: exactly the workgroups that are resident at once (GROOT_ALIGN_WAVES per SIMD = per CU)
     int n_cu = 256;

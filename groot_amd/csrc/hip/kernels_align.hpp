@@ -129,7 +129,11 @@ __global__ __launch_bounds__(kBlock, PW > 3 ? kAlignWavesWide : kAlignWaves) voi
     // reads without seeds sort last and have nothing to do here (the seed stage zeroed their traversal counts)
     // (items of split reads come first: slot j < nv is AlignArgs::vitem[j], slot nv + i is position i of the processing order)
     const uint32_t nv = a.vitem ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)*a.vcount), a.vcap) : 0u;
-    const uint32_t n_todo = nv + (a.perm ? min(a.n_reads, (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.n_perm ? *a.n_perm : a.ctr->seeded_reads))) : a.n_reads);   // (scalar: it bounds every refill)
+    // (behind a first pass: the list it left, then the slots of the processing order its grid did not reach)
+    const uint32_t n_seeded = min(a.n_reads, (uint32_t)__builtin_amdgcn_readfirstlane((int)a.ctr->seeded_reads));
+    const uint32_t n_list = a.n_perm ? min(a.n_reads, (uint32_t)__builtin_amdgcn_readfirstlane((int)*a.n_perm)) : n_seeded;
+    const uint32_t n_rest = a.rest && n_seeded > a.rest_lo ? n_seeded - a.rest_lo : 0u;
+    const uint32_t n_todo = nv + (a.perm ? min(a.n_reads, n_list + n_rest) : a.n_reads);   // (scalar: it bounds every refill)
     // Lanes per round.  A round lasts as long as its slowest read, so when there are fewer reads than 64 per resident wavefront
     // (most of the batch was answered from the outcome table: what is left are the hard reads) the rounds are made smaller
     // and spread over all wavefronts: the launch then ends with the slowest read instead of the slowest sum of rounds.
@@ -528,7 +532,7 @@ __global__ __launch_bounds__(kBlock, PW > 3 ? kAlignWavesWide : kAlignWaves) voi
                     if (r == kEmpty) { phase = PH_WAIT; continue; }   // (found no room: its read is handled whole)
                 } else {
                     const uint32_t so = slot - nv;
-                    r = a.perm ? a.perm[so] : so;              // reads in (first seed window, orientation) order
+                    r = !a.perm ? so : so < n_list ? a.perm[so] : a.rest[a.rest_lo + (so - n_list)];   // reads in (first seed window, orientation) order
                 }
                 uint4 ra, rb;                                     // one 32-byte record per read
                 load32(a.read_rec + r, ra, rb);                  // (gathering the records into processing order first costs more than this dependent trip)

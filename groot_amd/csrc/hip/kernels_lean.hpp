@@ -22,8 +22,8 @@ namespace groot {
 //     a node where two neighbours take the next base (dfsRecursive comes back to the second: alignment.go:242-252) leaves the second
 //     on a stack of two entries per read in HBM;
 //   * whatever does not fit -- more than four seed windows, a byte other than ACGT, an 'N' in the graph, three neighbours that take
-//     the next base, a third pending neighbour -- is left to align_kernel: the read's slot is flagged, a stream compaction keeps the
-//     flagged slots in processing order, and align_kernel handles the read from scratch.  What the first pass has written for such a
+//     the next base, a third pending neighbour -- is left to align_kernel: the pass appends the read to a list (a wavefront at a
+//     time, in the order the wavefronts finish), and align_kernel handles the read from scratch.  What the first pass has written for such a
 //     read by then are traversal records that align_kernel writes again, bit for bit, to the same places (ord 0: the read's own
 //     slot; ord >= 1: the overflow list, placed by (read, ord)); everything that counts -- IncrementSubPath calls, mapped /
 //     multimapped / alignments -- is kept in registers until the read is finished here.
@@ -561,7 +561,21 @@ __device__ __forceinline__ void first_pass_body(const LeanArgs &a)
 #endif
     // ---- what the read leaves behind ----
     const bool fin = st == ST_DONE;
-    if (slot < n_todo) a.defer[slot] = st == ST_DEFER ? 1 : 0;   // (slots from n_todo on hold reads without seeds: LeanLeft)
+    // the reads left to align_kernel go on its list: one atomic per wavefront, the lanes write their reads behind one another.  The list's order
+    // is the order in which the wavefronts get here, so it differs from run to run; no output does (order_ovf_kernel places records by (read, ord),
+    // everything else is per read or a sum).  (slots from n_todo on hold reads without seeds: nobody's business)
+    {
+        const bool left = st == ST_DEFER && slot < n_todo;
+        const unsigned long long lb = __ballot(left);
+        if (lb) {
+            const unsigned lane_ = threadIdx.x & 63u;
+            const int first = __ffsll(lb) - 1;
+            uint32_t at = 0;
+            if ((int)lane_ == first) at = atomicAdd(a.left_cnt, (uint32_t)__popcll(lb));
+            at = __shfl(at, first);
+            if (left) a.left[at + (uint32_t)__popcll(lb & ((1ull << lane_) - 1ull))] = r;
+        }
+    }
     unsigned long long n_alns = 0, mapped = 0, multimapped = 0;
     if (fin) {
         a.trav_cnt[r] = ord;
