@@ -222,6 +222,28 @@ func (c *Ctx) Close() {
 	}
 }
 
+// PairsEnable switches paired-end counting on or off: reads 2i and 2i+1 of every batch are then the mates of one fragment, and
+// shared reads and equivalence classes count units (include/groot_hip.h, "paired-end reads").  Nothing may be in flight.
+func (c *Ctx) PairsEnable(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.groot_hip_pairs_enable(c.h, v); rc != 0 {
+		return c.err("groot_hip_pairs_enable")
+	}
+	return nil
+}
+
+// PairsStats returns the fragments counted as joined, split and single since PairsEnable or the last reset of a counter
+func (c *Ctx) PairsStats() (joined, split, single uint64, err error) {
+	var j, s, o C.uint64_t
+	if rc := C.groot_hip_pairs_stats(c.h, &j, &s, &o); rc != 0 {
+		return 0, 0, 0, c.err("groot_hip_pairs_stats")
+	}
+	return uint64(j), uint64(s), uint64(o), nil
+}
+
 func (c *Ctx) err(what string) error {
 	return fmt.Errorf("%s: %s", what, C.GoString(C.groot_hip_last_error(c.h)))
 }

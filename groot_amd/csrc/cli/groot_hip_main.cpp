@@ -73,6 +73,7 @@ struct Args {
     std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out, abundance_out;
     double cov_cutoff = 0.97, abundance_min = 1.0;
     bool low_cov = false, no_bam = false;
+    bool paired = false, interleaved = false;   // --paired / --interleaved: the FASTQ input is fragments (groot_reads_open_paired, groot_hip_pairs_enable)
     uint32_t bootstraps = 0;               // --bootstraps: replicates behind the four bootstrap columns of --abundance (0 = none)
     uint64_t boot_seed = 1;
     std::vector<std::string> fastq;
@@ -110,13 +111,16 @@ void usage()
             "                  [--gpu 0 | --gpus N] [--batch 1048576] [--maxReadLen 512] [--bam out.bam] [--bamLevel -2..9] [--stats f.json]\n"
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
             "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0]] [--noBam]\n"
-            "                  [--bootstraps B [--bootSeed 1]]\n"
+            "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
             "                   --abundance: `name reads em_reads fraction` per ARG with em_reads >= --abundanceMin, by EM over the reads' path sets;\n"
             "                   --bootstraps: with --abundance, four more columns `boot_mean boot_sd boot_lo boot_hi` from B replicates of the reads\n"
-            "                   resampled with replacement (--bootSeed), each with its own EM, drawn and fitted on the GPU)\n"
+            "                   resampled with replacement (--bootSeed), each with its own EM, drawn and fitted on the GPU;\n"
+            "                   --paired: the -f files are R1,R2[,R1b,R2b...], first with second, third with fourth; --interleaved: the mates alternate in\n"
+            "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
+            "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
             "                  [--bootstraps B [--bootSeed 1]] [-p N]\n"
             "                  (BAM from stdin unless --bamFile; --bootstraps: the same columns as align writes, computed on -p host threads)\n",
@@ -159,6 +163,8 @@ Args parse(int argc, char **argv)
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootstraps") a.bootstraps = (uint32_t)std::max(0l, atol(v().c_str()));
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootSeed") a.boot_seed = strtoull(v().c_str(), nullptr, 10);
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--paired") a.paired = true;
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--interleaved") a.interleaved = true;
         else if (f == "--bamFile") a.bam_file = v();
         else if (f == "--lowCov") a.low_cov = true;
         else if (f == "-c" || f == "--minKmerCov") a.min_kmer_cov = atof(v().c_str());
@@ -364,6 +370,16 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     if (a.bootstraps && !want_ab) { fprintf(stderr, "--bootstraps adds columns to the abundance file: it needs --abundance\n"); return 1; }
     if (a.no_bam && !want_report && !want_ab) { fprintf(stderr, "--noBam without --report would leave no output of the alignments\n"); return 1; }
     if (a.no_bam && !a.bam_out.empty()) { fprintf(stderr, "--noBam and --bam contradict each other\n"); return 1; }
+    if (a.paired && a.interleaved) { fprintf(stderr, "--paired and --interleaved contradict each other: the mates come in two files or in one\n"); return 1; }
+    const bool frags = a.paired || a.interleaved;
+    if (frags && !want_shared && !want_ab) {
+        fprintf(stderr, "%s changes what --sharedReads and --abundance count, and nothing else: it needs one of them\n", a.paired ? "--paired" : "--interleaved");
+        return 1;
+    }
+    if (a.paired && (a.fastq.empty() || a.fastq.size() % 2)) {
+        fprintf(stderr, "--paired takes the -f files two at a time (R1,R2[,R1b,R2b...]): %zu file(s) given\n", a.fastq.size());
+        return 1;
+    }
     start_logging(a);
     auto t0 = std::chrono::steady_clock::now();
     logf("i am groot (version %s)", groot_host_version());
@@ -408,7 +424,13 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     std::vector<const char *> files;
     for (auto &f : a.fastq) files.push_back(f.c_str());
     groot_reads *reads = nullptr;
-    if (groot_reads_open(files.empty() ? nullptr : files.data(), (uint32_t)files.size(), cores, a.block_bytes, a.batch, max_batch_bases, &reads))
+    if (frags) {
+        std::vector<const char *> f1, f2;       // --paired: first with second, third with fourth; --interleaved: one stream, no second list
+        for (size_t i = 0; i < files.size(); i++) (a.paired && (i & 1) ? f2 : f1).push_back(files[i]);
+        if (groot_reads_open_paired(f1.empty() ? nullptr : f1.data(), (uint32_t)f1.size(), f2.empty() ? nullptr : f2.data(), (uint32_t)f2.size(), cores, a.block_bytes,
+                                    a.batch, max_batch_bases, &reads))
+            die("%s", groot_host_last_error());
+    } else if (groot_reads_open(files.empty() ? nullptr : files.data(), (uint32_t)files.size(), cores, a.block_bytes, a.batch, max_batch_bases, &reads))
         die("%s", groot_host_last_error());
     std::vector<std::unique_ptr<Gpu>> gpus;
     std::atomic<bool> gpus_ready{false};
@@ -516,7 +538,14 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     std::vector<uint64_t> sh_n;
     std::vector<uint64_t> ec_off{0}, ec_cnt;     // --abundance: the ECs of every ctx, appended (CSR)
     std::vector<uint32_t> ec_ids;
+    uint64_t fr_joined = 0, fr_split = 0, fr_single = 0;     // --paired / --interleaved: fragments per class, summed over the ctxs
     auto cov_harvest = [&](groot_ctx *ctx) -> int {
+        if (frags) {
+            uint64_t j = 0, sp = 0, si = 0;
+            if (int rc = groot_hip_pairs_stats(ctx, &j, &sp, &si)) return rc;
+            std::lock_guard<std::mutex> lk(cov_mu);
+            fr_joined += j; fr_split += sp; fr_single += si;
+        }
         if (want_ab) {
             uint64_t ne = 0, ni = 0, me = 0, mi = 0;
             if (int rc = groot_hip_ec_export(ctx, nullptr, nullptr, nullptr, 0, 0, &ne, &ni)) return rc;
@@ -551,6 +580,8 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         return 0;
     };
     auto cov_enable = [&](groot_ctx *ctx, int on) -> int {
+        if (frags)
+            if (int rc = groot_hip_pairs_enable(ctx, on)) return rc;
         if (want_report)
             if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
         if (want_shared)
@@ -739,6 +770,9 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             if (cov_harvest(g->ctx) || cov_enable(g->ctx, 0)) die("%s", groot_hip_last_error(g->ctx));
         }
     }
+    if (frags)
+        logf("\tpaired-end input: %llu fragment(s), %llu joined, %llu split, %llu single", (unsigned long long)(received / 2), (unsigned long long)fr_joined,
+             (unsigned long long)fr_split, (unsigned long long)fr_single);
     if (want_ab) {
         uint64_t n_lines = 0;
         uint32_t iters = 0;
@@ -894,6 +928,11 @@ int run_align(const Args &a)   // cmd/align.go:54-163
 // cmd/report.go:104-129
 int run_report(const Args &a)
 {
+    if (a.paired || a.interleaved) {
+        fprintf(stderr, "report cannot pair the records of a BAM: it carries no mate flags, and mates with equal QNAMEs cannot be told apart -- use "
+                        "`align --paired` (or --interleaved) with --sharedReads / --abundance\n");
+        return 1;
+    }
     start_logging(a);
     logf("i am groot (version %s)", groot_host_version());
     logf("starting the report subcommand");

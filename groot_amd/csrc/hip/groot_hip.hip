@@ -14,6 +14,7 @@
 #include <atomic>
 #include <chrono>
 #include <deque>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <numeric>
@@ -325,6 +326,7 @@ struct groot_ctx {
     // equivalence classes (groot_hip_ec_*, kernels_ec.hpp): the gather and insert kernels of shared reads run while either is on, and
     // ec_merge_kernel folds each batch's distinct sets into a run-wide table; slow-path reads are folded on the host at collect
     bool ec_on = false;
+    bool pairs_on = false;                 // groot_hip_pairs_enable: reads 2i, 2i+1 of a batch are one fragment (the kPaired kernels of kernels_shared.hpp)
     uint32_t ec_cap = 0, ec_epoch = 0;     // slots (a power of two) / epoch of the newest launch on the table
     DevBuf<uint32_t> ec_claim, ec_graph, ec_fill;
     DevBuf<uint64_t> ec_mask;
@@ -1095,12 +1097,15 @@ static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
     const uint32_t n_slow = s->h_ec.p[0];
     c->ec_fill_known = std::max<uint64_t>(c->ec_fill_known, s->h_ec.p[1]);
     if (!n_slow) return GROOT_OK;
-    std::vector<uint32_t> span(2 * (size_t)n_slow);
+    // per unit (first, end) traversal; in paired mode (first, end of the even mate's records, end): the unit is a fragment, and its
+    // set the intersection of the two mates' sets, when the middle differs from the end
+    const size_t sw = c->pairs_on ? 3 : 2;
+    std::vector<uint32_t> span(sw * (size_t)n_slow);
     HIP_TRY(c, hipMemcpy(span.data(), s->d_ec_slow.p + 1, span.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     const uint32_t pw = c->pw_view;
     // few reads: their records one by one; many (GROOT_TEST_SHARED_SLOW): the range that holds them all in one copy
     uint32_t lo = ~0u, hi = 0;
-    for (uint32_t i = 0; i < n_slow; i++) { lo = std::min(lo, span[2 * i]); hi = std::max(hi, span[2 * i + 1]); }
+    for (uint32_t i = 0; i < n_slow; i++) { lo = std::min(lo, span[sw * i]); hi = std::max(hi, span[sw * i + sw - 1]); }
     const bool whole = n_slow > 32;
     std::vector<groot_trav> tr;
     std::vector<uint64_t> mk;
@@ -1109,16 +1114,23 @@ static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
         HIP_TRY(c, hipMemcpy(tr.data(), s->d_trav.p + lo, tr.size() * sizeof(groot_trav), hipMemcpyDeviceToHost));
         HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)lo * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
-    std::vector<uint32_t> ids;
+    std::vector<uint32_t> ids, ids_a, ids_b;
     for (uint32_t i = 0; i < n_slow; i++) {
-        const uint32_t t0 = span[2 * i], t1 = span[2 * i + 1];
+        const uint32_t t0 = span[sw * i], tm = span[sw * i + sw - 2], t1 = span[sw * i + sw - 1];
         if (!whole) {
             tr.resize(t1 - t0); mk.resize((size_t)(t1 - t0) * pw);
             HIP_TRY(c, hipMemcpy(tr.data(), s->d_trav.p + t0, tr.size() * sizeof(groot_trav), hipMemcpyDeviceToHost));
             HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)t0 * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
         }
         const size_t o = whole ? t0 - lo : 0;
-        ec_set_of(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids);
+        if (c->pairs_on && tm != t1) {
+            ec_set_of(c, tr.data() + o, mk.data() + o * pw, tm - t0, ids_a);
+            ec_set_of(c, tr.data() + o + (tm - t0), mk.data() + (o + (tm - t0)) * pw, t1 - tm, ids_b);
+            ids.clear();
+            std::set_intersection(ids_a.begin(), ids_a.end(), ids_b.begin(), ids_b.end(), std::back_inserter(ids));
+        } else {
+            ec_set_of(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids);
+        }
         if (!ids.empty()) c->ec_host[ids]++;
     }
     c->ec_slow_reads += n_slow;
@@ -1177,21 +1189,28 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
         sa.cap = s->trav_cap; sa.pw = c->pw_view; sa.first_read_id = s->first_read_id; sa.n_paths = (uint32_t)c->h_cov_len.size();
         sa.max_segs = c->kn.shared_slow ? 1u : kSharedSegs;
         sa.pairs = c->sh_on;
+        sa.slow_cap = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
         uint32_t tab = 1;                  // this batch's part of the table: >= 2 n_reads slots
         while (tab < 2u * std::max<uint32_t>(s->n_reads, 1u)) tab <<= 1;
         sa.tab_mask = tab - 1;
         const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
-        hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->tstream, sa);
+        const bool paired = c->pairs_on;
+        if (paired) hipLaunchKernelGGL(shared_gather_paired_kernel, g, dim3(kBlock), 0, c->tstream, sa);
+        else hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->tstream, sa);
         hipLaunchKernelGGL(shared_insert_kernel, g, dim3(kBlock), 0, c->tstream, sa);
-        if (c->sh_on) hipLaunchKernelGGL(shared_slow_kernel, dim3(256), dim3(kBlock), 0, c->tstream, sa);
+        if (c->sh_on && paired) hipLaunchKernelGGL(shared_slow_kernel<true>, dim3(256), dim3(kBlock), 0, c->tstream, sa);
+        else if (c->sh_on) hipLaunchKernelGGL(shared_slow_kernel<false>, dim3(256), dim3(kBlock), 0, c->tstream, sa);
         if (c->ec_on) {
             if (int rc = ec_reserve(c, s)) return rc;
-            HIP_TRY(c, s->d_ec_slow.reserve(1 + 2 * (size_t)c->prm.max_batch_reads));
+            HIP_TRY(c, s->d_ec_slow.reserve(1 + (paired ? 3 : 2) * (size_t)c->prm.max_batch_reads));
             HIP_TRY(c, s->h_ec.reserve(2));
-            hipLaunchKernelGGL(ec_merge_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->tstream, sa, ec_table(c),
-                               tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p);
+            const dim3 gm(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u));
+            if (paired) hipLaunchKernelGGL(ec_merge_kernel<true>, gm, dim3(kBlock), 0, c->tstream, sa, ec_table(c), tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p);
+            else hipLaunchKernelGGL(ec_merge_kernel<false>, gm, dim3(kBlock), 0, c->tstream, sa, ec_table(c), tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p);
         }
-        hipLaunchKernelGGL(shared_expand_kernel, dim3(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u)), dim3(kBlock), 0, c->tstream, sa, tab);
+        const dim3 ge(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u));
+        if (paired) hipLaunchKernelGGL(shared_expand_kernel<true>, ge, dim3(kBlock), 0, c->tstream, sa, tab);
+        else hipLaunchKernelGGL(shared_expand_kernel<false>, ge, dim3(kBlock), 0, c->tstream, sa, tab);
         HIP_TRY(c, hipGetLastError());
     }
     w->used = true;
@@ -3105,9 +3124,17 @@ static int check_exceptions(groot_ctx *c, const uint64_t *exc_pos, uint64_t n_ex
     return GROOT_OK;
 }
 
+// paired mode: a batch is whole fragments (checked by every submit before anything else is touched)
+static int pairs_check(groot_ctx *c, uint32_t n_reads)
+{
+    if (c->pairs_on && (n_reads & 1)) return fail(c, GROOT_E_INVALID, "pairing is on: a batch of %u reads is not whole fragments", n_reads);
+    return GROOT_OK;
+}
+
 int groot_hip_submit(groot_ctx *c, const uint8_t *seq_concat, const uint64_t *seq_off, uint32_t n_reads, uint32_t first_read_id)
 {
     if (!c) return GROOT_E_INVALID;
+    if (int rc = pairs_check(c, n_reads)) return rc;
     if (n_reads && (!seq_concat || !seq_off)) return fail(c, GROOT_E_INVALID, "null read buffers");
     uint32_t max_len = 0, min_len = 0;
     if (n_reads) { if (int rc = check_offsets(c, seq_off, n_reads, &max_len, &min_len)) return rc; }
@@ -3129,6 +3156,7 @@ int groot_hip_submit_packed(groot_ctx *c, const uint8_t *packed, const uint64_t 
                             const uint64_t *exc_pos, const uint8_t *exc_byte, uint64_t n_exc)
 {
     if (!c) return GROOT_E_INVALID;
+    if (int rc = pairs_check(c, n_reads)) return rc;
     if (n_reads && (!packed || !seq_off)) return fail(c, GROOT_E_INVALID, "null read buffers");
     if (n_exc && (!exc_pos || !exc_byte)) return fail(c, GROOT_E_INVALID, "null exception list");
     uint32_t max_len = 0, min_len = 0;
@@ -3155,6 +3183,7 @@ int groot_hip_submit_packed16(groot_ctx *c, const uint8_t *packed, const uint16_
                               const uint64_t *exc_pos, const uint8_t *exc_byte, uint64_t n_exc)
 {
     if (!c) return GROOT_E_INVALID;
+    if (int rc = pairs_check(c, n_reads)) return rc;
     if (n_reads && (!packed || !seq_len)) return fail(c, GROOT_E_INVALID, "null read buffers");
     if (n_exc && (!exc_pos || !exc_byte)) return fail(c, GROOT_E_INVALID, "null exception list");
     uint64_t total = 0;
@@ -3206,6 +3235,7 @@ int groot_hip_submit_acquired(groot_ctx *c, uint64_t ticket, uint32_t n_reads, u
     if (!c) return GROOT_E_INVALID;
     Slot *s = slot_by_ticket(c, ticket, Slot::ACQUIRED);
     if (!s) return fail(c, GROOT_E_STATE, "ticket %llu is not an acquired batch", (unsigned long long)ticket);
+    if (int rc = pairs_check(c, n_reads)) return rc;     // (the batch stays acquired)
     if (n_reads > c->prm.max_batch_reads) return fail(c, GROOT_E_NOSPACE, "batch of %u reads exceeds max_batch_reads=%u", n_reads, c->prm.max_batch_reads);
     if (n_exc > s->h_exc_pos.n) return fail(c, GROOT_E_NOSPACE, "more exceptions than the acquired buffers hold");
     uint64_t total = 0;
@@ -3227,6 +3257,7 @@ int groot_hip_submit_device(groot_ctx *c, const void *d_seq, const void *d_seq_o
                             uint32_t max_len)
 {
     if (!c) return GROOT_E_INVALID;
+    if (int rc = pairs_check(c, n_reads)) return rc;
     if (n_reads && (!d_seq || !d_seq_off)) return fail(c, GROOT_E_INVALID, "null device buffers");
     if (((uintptr_t)d_seq & 15) != 0) return fail(c, GROOT_E_INVALID, "d_seq must be 16-byte aligned");
     Slot *s = nullptr;
@@ -3617,12 +3648,12 @@ static hipError_t sh_common_alloc(groot_ctx *c)
     if (e == hipSuccess) e = c->sh_tab_rep.alloc(tab);
     if (e == hipSuccess) e = c->sh_tab_cnt.alloc(tab);
     if (e == hipSuccess) e = c->sh_slow.alloc(R);
-    if (e == hipSuccess) e = c->sh_batch.alloc(3);
-    if (e == hipSuccess) e = c->sh_stats.alloc(3);
+    if (e == hipSuccess) e = c->sh_batch.alloc(kSharedBatch);
+    if (e == hipSuccess) e = c->sh_stats.alloc(kSharedStats);
     if (e == hipSuccess) e = hipMemset(c->sh_tab_rep.p, 0xFF, tab * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(c->sh_tab_cnt.p, 0, tab * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(c->sh_batch.p, 0, 3 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, 3 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(c->sh_batch.p, 0, kSharedBatch * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, kSharedStats * sizeof(unsigned long long));
     return e;
 }
 
@@ -3658,7 +3689,7 @@ int groot_hip_shared_enable(groot_ctx *c, int on)
     hipError_t e = sh_common_alloc(c);
     if (e == hipSuccess) e = c->sh_tri.alloc(tri);
     if (e == hipSuccess) e = hipMemset(c->sh_tri.p, 0, std::max<uint64_t>(tri, 1) * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, 3 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, kSharedStats * sizeof(unsigned long long));
     if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "shared reads: %s", hipGetErrorString(e)));
     c->sh_on = true;
     return GROOT_OK;
@@ -3702,7 +3733,7 @@ int groot_hip_shared_reset(groot_ctx *c)
     if (!c->sh_on) return GROOT_OK;
     if (int rc = drain(c)) return rc;
     HIP_TRY(c, hipMemset(c->sh_tri.p, 0, std::max<uint64_t>(shared_tri_size(c->h_cov_len.size()), 1) * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(c->sh_stats.p, 0, 3 * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->sh_stats.p, 0, kSharedStats * sizeof(unsigned long long)));
     return GROOT_OK;
 }
 
@@ -3835,6 +3866,33 @@ int groot_hip_ec_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ec_fill.p, 0, sizeof(uint32_t)));
     c->ec_fill_known = c->ec_grows = c->ec_slow_reads = 0;
     c->ec_host.clear();
+    if (c->pairs_on) HIP_TRY(c, hipMemset(c->sh_stats.p + 3, 0, (kSharedStats - 3) * sizeof(unsigned long long)));
+    return GROOT_OK;
+}
+
+// ---- paired-end reads (the kPaired kernels of kernels_shared.hpp; the definition is in groot_hip.h) -------------------------
+int groot_hip_pairs_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "pairing can only be switched while nothing is in flight");
+    c->pairs_on = on != 0;
+    if (c->sh_on || c->ec_on) {     // (else there is nothing to zero: sh_common_alloc zeroes the counts when either comes on)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipMemset(c->sh_stats.p + 3, 0, (kSharedStats - 3) * sizeof(unsigned long long)));
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_pairs_stats(groot_ctx *c, uint64_t *joined, uint64_t *split, uint64_t *single)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->pairs_on) return fail(c, GROOT_E_STATE, "pairing is not enabled (groot_hip_pairs_enable)");
+    if (int rc = drain(c)) return rc;
+    uint64_t st[kSharedStats] = {};
+    if (c->sh_on || c->ec_on) HIP_TRY(c, hipMemcpy(st, c->sh_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    if (joined) *joined = st[3];
+    if (split) *split = st[4];
+    if (single) *single = st[5];
     return GROOT_OK;
 }
 

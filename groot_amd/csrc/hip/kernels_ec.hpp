@@ -12,6 +12,8 @@
 // align-stream order, by ec_rehash_kernel.  Slow-path reads (kernels_shared.hpp) are not in the table: ec_merge_kernel copies the
 // batch's slow list (first and end traversal of each read) into a buffer the slot owns, and the host folds those reads' exact sets
 // in at collect.  Every kernel reads the pass's status word first: a pass collect redoes is not counted.
+// In paired mode (kernels_shared.hpp) the rows are units and ec_merge_kernel<true> lists the slow-path units: a read, or a fragment
+// whose set is the intersection of its mates' sets (three words each, the host intersects).
 #pragma once
 
 #include "kernels_shared.hpp"
@@ -84,19 +86,37 @@ __device__ __forceinline__ void ec_add(const EcTable &t, const uint32_t *g, cons
 }
 
 // one thread per slot of the batch's set table (tab_size slots); block 0 also lists the batch's slow-path reads:
-// slow_out[0] = their number, then (first traversal, end traversal) per read
+// slow_out[0] = their number, then (first traversal, end traversal) per read.
+// kPaired: three words per slow-path unit, (first traversal, end of the even mate's records, end traversal); the middle word equals
+// the last for a read that is a unit by itself, and the host folds the intersection of the two ranges' sets otherwise.
+template <bool kPaired>
 __global__ __launch_bounds__(kBlock) void ec_merge_kernel(SharedArgs a, EcTable t, uint32_t tab_size, uint32_t epoch, uint32_t *fill, uint32_t *slow_out)
 {
     if (!shared_live(a)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) slow_out[0] = 0;
         return;
     }
-    const uint32_t n = min(a.ctr->n_trav, a.cap), n_slow = a.batch[2];
+    const uint32_t n = min(a.ctr->n_trav, a.cap), n_reads = a.batch[2], n_slow = n_reads + (kPaired ? a.batch[6] : 0u);
     if (blockIdx.x == 0 && threadIdx.x == 0) slow_out[0] = n_slow;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n_slow; i += gridDim.x * kBlock) {
+        if (kPaired && i >= n_reads) {
+            const uint32_t t0 = a.slow[a.slow_cap - 1 - (i - n_reads)];
+            uint32_t tm, t1;
+            frag_span(a, t0, n, tm, t1);
+            slow_out[1 + 3 * i] = t0;
+            slow_out[2 + 3 * i] = tm;
+            slow_out[3 + 3 * i] = t1;
+            continue;
+        }
         const uint32_t t0 = a.slow[i], rid = a.trav[t0].read_id;
         uint32_t t1 = t0 + 1;
         while (t1 < n && a.trav[t1].read_id == rid) t1++;
+        if (kPaired) {
+            slow_out[1 + 3 * i] = t0;
+            slow_out[2 + 3 * i] = t1;
+            slow_out[3 + 3 * i] = t1;
+            continue;
+        }
         slow_out[1 + 2 * i] = t0;
         slow_out[2 + 2 * i] = t1;
     }

@@ -19,6 +19,11 @@
 // reads off, expand only clears the table.
 // So the triangle sees one u64 atomic per (distinct set, pair) and per (slow read, pair), not one per (read, pair).
 // Every kernel reads the pass's status word first: a pass collect redoes, or a batch that fails with NOSPACE, is not counted.
+//
+// Paired mode (groot_hip_pairs_enable): shared_gather_paired_kernel takes the place of shared_gather_kernel and makes one row per
+// unit -- a fragment's two mates intersected, or either mate alone -- and the slow, merge and expand kernels run as their kPaired
+// instantiations, which also know the batch's slow fragments.  Insert, and everything that works on rows, is the same code either way;
+// with pairing off the launches are the ones above, compiled from the same text as before (kPaired = false drops every branch).
 #pragma once
 
 #include "kernels_common.hpp"
@@ -45,7 +50,12 @@ struct SharedArgs {
     uint32_t cap, pw, first_read_id, n_paths, tab_mask;
     uint32_t max_segs;             // graphs per read on the fast path: kSharedSegs (1 under GROOT_TEST_SHARED_SLOW)
     uint32_t pairs;                // shared reads are on: expand adds to the triangle (else it only clears the table: equivalence classes)
+    uint32_t slow_cap;             // paired mode: entries of `slow`; slow fragments are listed from its end down (batch[6] of them)
 };
+
+// `batch` and `stats` beyond [3], written in paired mode only (kPaired kernels): fragments joined, split, single; batch[6] = the
+// batch's slow-path fragments (into stats[2] with the slow-path reads)
+constexpr uint32_t kSharedStats = 6, kSharedBatch = 7;
 
 __device__ __forceinline__ bool shared_live(const SharedArgs &a) { return !(a.ctr->flags & kCovSkipFlags); }
 
@@ -135,6 +145,132 @@ __global__ __launch_bounds__(kBlock) void shared_gather_kernel(SharedArgs a)
     block_add(reads, &a.batch[0]);
 }
 
+// ---- paired mode (groot_hip_pairs_enable) ----------------------------------------------------------------------------
+// With pairing on, reads 2i and 2i+1 of a batch are the mates of fragment i (batch-relative: read_id - first_read_id).  With
+// A = S(r_2i), B = S(r_2i+1): joined (A n B not empty: one unit, A n B), split (both non-empty, A n B empty: two units, A and B),
+// single (one of them non-empty: one unit), none.  A fragment's records are contiguous, read 2i's before read 2i+1's, so one thread
+// owns a fragment -- the thread of its first traversal -- and nobody else writes either mate's row.  A joined unit goes to the even
+// mate's row; the odd mate's row gets kSharedEmpty as its first graph, which is what shared_insert_kernel skips at that read start.
+
+// t starts a fragment: its first traversal
+__device__ __forceinline__ bool frag_start(const SharedArgs &a, uint32_t t)
+{
+    return t == 0 || ((a.trav[t].read_id - a.first_read_id) >> 1) != ((a.trav[t - 1].read_id - a.first_read_id) >> 1);
+}
+
+// the fragment whose first traversal is t0: the even mate's records are [t0, tm), the odd mate's [tm, t1) (either may be empty, not both)
+__device__ __forceinline__ void frag_span(const SharedArgs &a, uint32_t t0, uint32_t n, uint32_t &tm, uint32_t &t1)
+{
+    const uint32_t even = a.first_read_id + ((a.trav[t0].read_id - a.first_read_id) & ~1u);
+    for (tm = t0; tm < n && a.trav[tm].read_id == even; tm++) {}
+    for (t1 = tm; t1 < n && a.trav[t1].read_id == even + 1; t1++) {}
+}
+
+// the end of the run of records of one graph that starts at s (records [s, lim) of one read)
+__device__ __forceinline__ uint32_t seg_end(const SharedArgs &a, uint32_t s, uint32_t lim)
+{
+    uint32_t e = s + 1;
+    while (e < lim && a.trav[e].graph_id == a.trav[s].graph_id) e++;
+    return e;
+}
+
+// word w of the OR of the path sets of records [s, e)
+__device__ __forceinline__ uint64_t seg_or(const SharedArgs &a, uint32_t s, uint32_t e, uint32_t w)
+{
+    uint64_t m = 0;
+    for (uint32_t t = s; t < e; t++) m |= a.mask[(size_t)t * a.pw + w];
+    return m;
+}
+
+// word w of the OR of the path sets of those records of [s, e) that lie in graph g (0 when there is none)
+__device__ __forceinline__ uint64_t graph_or(const SharedArgs &a, uint32_t s, uint32_t e, uint32_t g, uint32_t w)
+{
+    uint64_t m = 0;
+    for (uint32_t t = s; t < e; t++)
+        if (a.trav[t].graph_id == g) m |= a.mask[(size_t)t * a.pw + w];
+    return m;
+}
+
+// one read as a unit, as shared_gather_kernel does it: the row of read r from records [t0, t1), or the read on the slow list
+__device__ __forceinline__ void gather_read(const SharedArgs &a, uint32_t t0, uint32_t t1, uint32_t r)
+{
+    uint32_t segs = 0;
+    for (uint32_t s = t0; s < t1; s = seg_end(a, s, t1)) segs++;
+    uint32_t *sg = a.set_graph + (size_t)r * kSharedSegs;
+    if (segs > a.max_segs) {
+        sg[0] = kSharedEmpty;
+        a.slow[atomicAdd(&a.batch[2], 1u)] = t0;
+        return;
+    }
+    uint32_t k = 0;
+    for (uint32_t s = t0; s < t1; k++) {
+        const uint32_t e = seg_end(a, s, t1);
+        sg[k] = a.trav[s].graph_id;
+        for (uint32_t w = 0; w < a.pw; w++) a.set_mask[((size_t)r * kSharedSegs + k) * a.pw + w] = seg_or(a, s, e, w);
+        s = e;
+    }
+    for (; k < kSharedSegs; k++) sg[k] = kSharedEmpty;
+}
+
+// one thread per fragment.  The two mates' ascending segment lists are merged: graphs in common only, masks ANDed word by word,
+// segments whose AND is all zero dropped -- so the row is a canonical key (graphs ascend, no segment is empty, kSharedEmpty ends it).
+// The first max_segs segments of the intersection are written as they are met; a fragment is a slow-path unit only when the
+// intersection itself has more, whatever the mates have alone.
+__global__ __launch_bounds__(kBlock) void shared_gather_paired_kernel(SharedArgs a)
+{
+    if (!shared_live(a)) return;
+    const uint32_t n = min(a.ctr->n_trav, a.cap);
+    uint32_t units = 0, joined = 0, split = 0, single = 0;
+    for (uint32_t t0 = blockIdx.x * kBlock + threadIdx.x; t0 < n; t0 += gridDim.x * kBlock) {
+        if (!frag_start(a, t0)) continue;
+        uint32_t tm, t1;
+        frag_span(a, t0, n, tm, t1);
+        const uint32_t r0 = (a.trav[t0].read_id - a.first_read_id) & ~1u;     // the even mate's row; r0 + 1 the odd mate's
+        if (tm == t0 || t1 == tm) {     // "has records" is decided here, from the traversals: the other mate's row is stale and stays unread
+            gather_read(a, t0, t1, tm == t0 ? r0 + 1 : r0);
+            single++; units++;
+            continue;
+        }
+        uint32_t *sg = a.set_graph + (size_t)r0 * kSharedSegs;
+        uint32_t k = 0;
+        for (uint32_t sa = t0, sb = tm; sa < tm && sb < t1;) {
+            const uint32_t ga = a.trav[sa].graph_id, gb = a.trav[sb].graph_id;
+            if (ga < gb) { sa = seg_end(a, sa, tm); continue; }
+            if (gb < ga) { sb = seg_end(a, sb, t1); continue; }
+            const uint32_t ea = seg_end(a, sa, tm), eb = seg_end(a, sb, t1);
+            uint64_t any = 0;
+            for (uint32_t w = 0; w < a.pw; w++) {
+                const uint64_t m = seg_or(a, sa, ea, w) & seg_or(a, sb, eb, w);
+                any |= m;
+                if (k < a.max_segs) a.set_mask[((size_t)r0 * kSharedSegs + k) * a.pw + w] = m;     // (kept only if any: else segment k is written again)
+            }
+            if (any) {
+                if (k < a.max_segs) sg[k] = ga;
+                k++;
+            }
+            sa = ea; sb = eb;
+        }
+        if (k == 0) {                   // split: the two reads as today, each on its own path
+            gather_read(a, t0, tm, r0);
+            gather_read(a, tm, t1, r0 + 1);
+            split++; units += 2;
+            continue;
+        }
+        joined++; units++;
+        sg[kSharedSegs] = kSharedEmpty;     // the odd mate: a read start without a unit, and not on the slow list
+        if (k > a.max_segs) {
+            sg[0] = kSharedEmpty;
+            a.slow[a.slow_cap - 1 - atomicAdd(&a.batch[6], 1u)] = t0;
+            continue;
+        }
+        for (; k < kSharedSegs; k++) sg[k] = kSharedEmpty;
+    }
+    block_add(units, &a.batch[0]);
+    block_add(joined, &a.batch[3]);
+    block_add(split, &a.batch[4]);
+    block_add(single, &a.batch[5]);
+}
+
 __global__ __launch_bounds__(kBlock) void shared_insert_kernel(SharedArgs a)
 {
     if (!shared_live(a)) return;
@@ -159,19 +295,28 @@ __global__ __launch_bounds__(kBlock) void shared_insert_kernel(SharedArgs a)
 
 // one wave per slow-path read: S(r) = the concatenation, graph after graph (ascending), of the OR of each graph's path sets.  Lane l
 // takes the elements k = l, l + 64, ... of S(r) as a and adds 1 to (a, b) for every element b >= a.
+// kPaired: entries i >= batch[2] are the batch's slow fragments (listed from the end of `slow` down).  The wave walks the even mate's
+// segments, each ANDed with the odd mate's OR in the same graph: a graph the odd mate lacks, or an all-zero AND, has no element.
+template <bool kPaired>
 __global__ __launch_bounds__(kBlock) void shared_slow_kernel(SharedArgs a)
 {
     if (!shared_live(a)) return;
-    const uint32_t n = min(a.ctr->n_trav, a.cap), n_slow = a.batch[2];
+    const uint32_t n = min(a.ctr->n_trav, a.cap), n_reads = a.batch[2], n_slow = n_reads + (kPaired ? a.batch[6] : 0u);
     const uint32_t lane = threadIdx.x & 63, waves = gridDim.x * (kBlock / 64);
     for (uint32_t i = blockIdx.x * (kBlock / 64) + threadIdx.x / 64; i < n_slow; i += waves) {
-        const uint32_t t0 = a.slow[i], rid = a.trav[t0].read_id;
-        uint32_t t1 = t0 + 1;
-        while (t1 < n && a.trav[t1].read_id == rid) t1++;
+        const uint32_t t0 = a.slow[kPaired && i >= n_reads ? a.slow_cap - 1 - (i - n_reads) : i], rid = a.trav[t0].read_id;
+        uint32_t t1 = t0 + 1, m0 = 0, m1 = 0;      // [m0, m1): the odd mate's records, for a fragment
+        if (kPaired && i >= n_reads) {
+            frag_span(a, t0, n, t1, m1);
+            m0 = t1;
+        } else {
+            while (t1 < n && a.trav[t1].read_id == rid) t1++;
+        }
         // word w of the segment of graph starting at traversal s (traversals s..e-1 of one graph)
         auto seg_word = [&](uint32_t s, uint32_t e, uint32_t w) {
             uint64_t m = 0;
             for (uint32_t t = s; t < e; t++) m |= a.mask[(size_t)t * a.pw + w];
+            if (kPaired && m1 > m0) m &= graph_or(a, m0, m1, a.trav[s].graph_id, w);
             return m;
         };
         auto seg_end = [&](uint32_t s) {
@@ -204,6 +349,7 @@ __global__ __launch_bounds__(kBlock) void shared_slow_kernel(SharedArgs a)
     }
 }
 
+template <bool kPaired>
 __global__ __launch_bounds__(kBlock) void shared_expand_kernel(SharedArgs a, uint32_t tab_size)
 {
     if (!shared_live(a)) return;
@@ -235,9 +381,13 @@ __global__ __launch_bounds__(kBlock) void shared_expand_kernel(SharedArgs a, uin
         a.tab_cnt[slot] = 0;
     }
     // the batch's counters into the totals, and zeroed for the next batch (every kernel of this batch before this one has ended)
-    if (blockIdx.x == 0 && threadIdx.x < 3) {
+    if (blockIdx.x == 0 && threadIdx.x < (kPaired ? kSharedStats : 3u)) {
         a.stats[threadIdx.x] += a.batch[threadIdx.x];
         a.batch[threadIdx.x] = 0;
+        if (kPaired && threadIdx.x == 2) {     // slow units = slow reads + slow fragments
+            a.stats[2] += a.batch[6];
+            a.batch[6] = 0;
+        }
     }
 }
 

@@ -8,6 +8,9 @@
 // the records and packs the bases straight into the wire format of groot_hip_submit_packed16 -- all in parallel over
 // the block.  Lines from consecutive files form ONE stream (the four-line grouping carries across files), lines end at
 // "\n" or "\r\n" (bufio.ScanLines), a last line without terminator counts.
+// Paired-end input (groot_reads_open_paired): batches of whole fragments, read 2i from the first stream and 2i+1 from the second (two
+// file lists read in lockstep: a block's text is the first stream's stretch followed by the second's, and the records of the two
+// alternate by position), or from one stream that holds the mates alternately.  Mate names must agree.
 #include "host_common.hpp"
 
 #include <algorithm>
@@ -173,7 +176,11 @@ struct groot_reads_batch {
     uint32_t max_len = 0;
 };
 
+enum { kSingleEnd = 0, kInterleaved = 1, kTwoStreams = 2 };
+
 struct groot_reads {
+    int mode = kSingleEnd;
+    std::unique_ptr<groot_reads> mate;  // kTwoStreams: the second file list (its files, inputs and carry; everything else lives here)
     std::vector<std::string> files;     // empty = stdin
     unsigned n_threads = 1;
     size_t block_bytes = 0;
@@ -210,8 +217,20 @@ struct groot_reads {
     }
 };
 
+// the name two mates must share: up to the first whitespace, without a trailing /1 or /2
+static void mate_stem(const char *text, uint32_t &pos, uint32_t &len)
+{
+    pos++; len--;                                                  // the '@'
+    uint32_t l = 0;
+    while (l < len && text[pos + l] != ' ' && text[pos + l] != '\t') l++;
+    if (l >= 2 && text[pos + l - 2] == '/' && (text[pos + l - 1] == '1' || text[pos + l - 1] == '2')) l -= 2;
+    len = l;
+}
+
 // frames one raw block (carry + new text), parses it and appends its batches to r->ready
-static int parse_block(groot_reads *r, std::unique_ptr<RawBlock> blk, bool last_block)
+// kTwoStreams: the block is already framed (next_two): text[0, split) is the first stream's stretch and ends at a line end (so the
+// second stream's stretch, which follows, starts a line); `tail` is what the first stretch lost behind its last line end
+static int parse_block(groot_reads *r, std::unique_ptr<RawBlock> blk, bool last_block, size_t split = 0, const std::vector<char> *tail = nullptr)
 {
     // the partial record carried over goes in front of the new text
     if (!r->carry.empty()) {
@@ -284,10 +303,46 @@ static int parse_block(groot_reads *r, std::unique_ptr<RawBlock> blk, bool last_
         n_rec = rec_line.size() / 4;
         if (rec_line.empty()) rec_line.push_back(0);               // (non-empty = "regrouped")
     }
+    if (r->mode == kInterleaved && (n_rec & 1)) {                  // a fragment is never cut: its first mate waits for the next block
+        if (last_block) return set_error(GROOT_E_FORMAT, "interleaved FASTQ input holds an odd number of records (%llu)", (unsigned long long)(r->n_reads + n_rec));
+        n_rec--;
+    }
+    if (r->mode == kTwoStreams) {
+        // the records of each stretch (blank lines skipped as above), then the first min(R1, R2) of both, alternating
+        const size_t nl1 = (size_t)(std::lower_bound(nl.begin(), nl.end(), (uint32_t)split) - nl.begin());
+        std::vector<uint32_t> rec[2];
+        for (int st = 0; st < 2; st++) {
+            uint32_t field = 0, cur[4];
+            for (size_t li = st ? nl1 : 0; li < (st ? n_lines : nl1); li++) {
+                uint32_t p, l;
+                raw_line(li, p, l);
+                if (field < 3 && !l) continue;
+                cur[field++] = (uint32_t)li;
+                if (field == 4) { rec[st].insert(rec[st].end(), cur, cur + 4); field = 0; }
+            }
+        }
+        const size_t R1 = rec[0].size() / 4, R2 = rec[1].size() / 4, R = std::min(R1, R2);
+        if (last_block && R1 != R2)
+            return set_error(GROOT_E_FORMAT, "paired FASTQ input: the %s file list ends after %llu record(s), its partner has more", R1 < R2 ? "first" : "second",
+                             (unsigned long long)(r->n_reads / 2 + R));
+        rec_line.clear();
+        for (size_t i = 0; i < R; i++) {
+            rec_line.insert(rec_line.end(), rec[0].begin() + 4 * i, rec[0].begin() + 4 * i + 4);
+            rec_line.insert(rec_line.end(), rec[1].begin() + 4 * i, rec[1].begin() + 4 * i + 4);
+        }
+        n_rec = 2 * R;
+        const size_t cut1 = R ? (size_t)nl[rec[0][4 * R - 1]] + 1 : 0, cut2 = R ? (size_t)nl[rec[1][4 * R - 1]] + 1 : split;
+        if (!last_block) {
+            r->carry.assign(text + cut1, text + split);
+            if (tail) r->carry.insert(r->carry.end(), tail->begin(), tail->end());
+            r->mate->carry.assign(text + cut2, text + n);
+        }
+        if (rec_line.empty()) rec_line.push_back(0);
+    }
     const bool regrouped = !rec_line.empty();
     const size_t last_line = n_rec ? (regrouped ? (size_t)rec_line[4 * n_rec - 1] : 4 * n_rec - 1) : 0;
     const size_t cut = n_rec ? (size_t)nl[last_line] + 1 : 0;
-    if (!last_block) r->carry.assign(text + cut, text + n);       // lines of the next record (and a partial line): carried over
+    if (!last_block && r->mode != kTwoStreams) r->carry.assign(text + cut, text + n);       // lines of the next record (and a partial line): carried over
     // (at the end of all input a trailing partial record is dropped, as in FastqHandler.Run)
     if (!n_rec) return GROOT_OK;
     auto line = [&](size_t fi, uint32_t &pos, uint32_t &len) { raw_line(regrouped ? (size_t)rec_line[fi] : fi, pos, len); };
@@ -318,7 +373,28 @@ static int parse_block(groot_reads *r, std::unique_ptr<RawBlock> blk, bool last_
             if (task_err[t] == 1) return set_error(GROOT_E_FORMAT, "read ID in fastq file does not begin with @: %.*s", (int)std::min<uint32_t>(l, 200), text + p);
             return set_error(GROOT_E_UNSUPPORTED, "read longer than 65535 bases: %.*s", (int)std::min<uint32_t>(l, 200), text + p);
         }
+    if (r->mode != kSingleEnd) {       // mate names agree (after pass A: every ID line starts with '@')
+        const size_t P = n_rec / 2;
+        std::vector<size_t> bad(n_tasks, SIZE_MAX);
+        parallel_for(T, n_tasks, [&](size_t t) {
+            for (size_t i = P * t / n_tasks; i < P * (t + 1) / n_tasks; i++) {
+                uint32_t p1, l1, p2, l2;
+                line(8 * i, p1, l1); line(8 * i + 4, p2, l2);
+                mate_stem(text, p1, l1); mate_stem(text, p2, l2);
+                if (l1 != l2 || memcmp(text + p1, text + p2, l1)) { bad[t] = i; return; }
+            }
+        });
+        for (size_t t = 0; t < n_tasks; t++)
+            if (bad[t] != SIZE_MAX) {
+                uint32_t p1, l1, p2, l2;
+                line(8 * bad[t], p1, l1); line(8 * bad[t] + 4, p2, l2);
+                return set_error(GROOT_E_FORMAT, "paired FASTQ input: the mates of fragment %llu have different names: %.*s and %.*s",
+                                 (unsigned long long)(r->n_reads / 2 + bad[t] + 1), (int)std::min<uint32_t>(l1 - 1, 200), text + p1 + 1,
+                                 (int)std::min<uint32_t>(l2 - 1, 200), text + p2 + 1);
+            }
+    }
     // ---- cut the block into batches that fit the device ctx (reads and bases), then pass B per batch ----
+    const size_t unit = r->mode == kSingleEnd ? 1 : 2;             // records that stay together: a fragment is never cut
     std::shared_ptr<RawBlock> shared(blk.release());
     size_t rec0 = 0;
     while (rec0 < n_rec) {
@@ -327,15 +403,16 @@ static int parse_block(groot_reads *r, std::unique_ptr<RawBlock> blk, bool last_
         uint64_t bases = 0;
         {
             size_t i = rec0;
-            while (i < n_rec && (i - rec0) < r->max_batch_reads) {
-                uint32_t p, l;
+            while (i < n_rec && (i - rec0) + unit <= r->max_batch_reads) {
+                uint32_t p, l, l2 = 0;
                 line(4 * i + 1, p, l);
-                if (bases + l > r->max_batch_bases) break;
-                bases += l; i++;
+                if (unit == 2) line(4 * i + 5, p, l2);
+                if (bases + l + l2 > r->max_batch_bases) break;
+                bases += l + l2; i += unit;
             }
             rec1 = i;
         }
-        if (rec1 == rec0) return set_error(GROOT_E_NOSPACE, "a single read does not fit the batch (max_batch_bases=%llu)", (unsigned long long)r->max_batch_bases);
+        if (rec1 == rec0) return set_error(GROOT_E_NOSPACE, "a single %s does not fit the batch (max_batch_bases=%llu)", unit == 2 ? "fragment" : "read", (unsigned long long)r->max_batch_bases);
         const size_t m = rec1 - rec0;
         std::unique_ptr<groot_reads_batch> b(new groot_reads_batch());
         b->text = shared;
@@ -425,7 +502,87 @@ static int parse_block(groot_reads *r, std::unique_ptr<RawBlock> blk, bool last_
     return GROOT_OK;
 }
 
+// the next raw block of r's file list; *blk stays empty at its end
+static int pop_block(groot_reads *r, std::unique_ptr<RawBlock> *blk)
+{
+    while (!r->open.empty()) {
+        Source *s = r->open.front().get();
+        *blk = s->pop();
+        if (*blk) return GROOT_OK;
+        if (!s->err.empty()) return set_error(GROOT_E_IO, "%s", s->err.c_str());
+        s->shutdown();
+        r->open.pop_front();
+        r->open_more();
+    }
+    return GROOT_OK;
+}
+
+// kTwoStreams: one block of either list (a list whose carry has grown past a block waits for its partner), framed as one text
+static int next_two(groot_reads *r)
+{
+    groot_reads *m = r->mate.get();
+    std::unique_ptr<RawBlock> b1, b2;
+    const bool hold1 = r->carry.size() > r->block_bytes && !m->open.empty(), hold2 = m->carry.size() > r->block_bytes && !r->open.empty() && !hold1;
+    if (!hold1) { if (int rc = pop_block(r, &b1)) return rc; }
+    if (!hold2) { if (int rc = pop_block(m, &b2)) return rc; }
+    const bool last = r->open.empty() && m->open.empty();
+    if (last) r->input_done = true;
+    const size_t n1 = r->carry.size() + (b1 ? b1->end - b1->begin : 0), n2 = m->carry.size() + (b2 ? b2->end - b2->begin : 0);
+    std::unique_ptr<RawBlock> blk(new RawBlock());
+    blk->buf.resize(kHeadroom + n1 + n2 + 1);
+    char *dst = blk->buf.data() + kHeadroom;
+    if (!r->carry.empty()) memcpy(dst, r->carry.data(), r->carry.size());
+    if (b1) memcpy(dst + r->carry.size(), b1->buf.data() + b1->begin, b1->end - b1->begin);
+    size_t split = n1;                                             // the first stretch ends behind its last line end
+    while (split && dst[split - 1] != '\n') split--;
+    const std::vector<char> tail(dst + split, dst + n1);
+    if (!m->carry.empty()) memcpy(dst + split, m->carry.data(), m->carry.size());
+    if (b2) memcpy(dst + split + m->carry.size(), b2->buf.data() + b2->begin, b2->end - b2->begin);
+    blk->end = kHeadroom + split + n2;
+    r->carry.clear(); m->carry.clear();
+    if (blk->end == blk->begin) return GROOT_OK;
+    return parse_block(r, std::move(blk), last, split, &tail);
+}
+
+static int open_common(groot_reads *r, const char *const *files, uint32_t n_files, uint32_t n_threads, uint64_t block_bytes, uint32_t max_batch_reads,
+                       uint64_t max_batch_bases)
+{
+    for (uint32_t i = 0; i < n_files; i++) r->files.push_back(files[i]);
+    r->n_threads = n_threads ? n_threads : usable_cpus();
+    r->block_bytes = (size_t)std::min<uint64_t>(block_bytes ? block_bytes : (256ull << 20), r->mode == kTwoStreams ? 3ull << 29 : 3ull << 30);
+    r->max_batch_reads = max_batch_reads ? max_batch_reads : (1u << 20);
+    r->max_batch_bases = max_batch_bases ? max_batch_bases : (uint64_t)r->max_batch_reads * 256;
+    for (auto &f : r->files) {       // fail early on a missing file, like os.Open + misc.ErrorCheck
+        FILE *t = fopen(f.c_str(), "rb");
+        if (!t) return set_error(GROOT_E_IO, "cannot open %s", f.c_str());
+        fclose(t);
+    }
+    return GROOT_OK;
+}
+
 extern "C" {
+
+int groot_reads_open_paired(const char *const *files1, uint32_t n_files1, const char *const *files2, uint32_t n_files2, uint32_t n_threads,
+                            uint64_t block_bytes, uint32_t max_batch_reads, uint64_t max_batch_bases, groot_reads **out)
+{
+    if (!out || (n_files1 && !files1) || (n_files2 && !files2)) return set_error(GROOT_E_INVALID, "null argument");
+    if (n_files2 && n_files1 != n_files2) return set_error(GROOT_E_INVALID, "paired FASTQ input: %u file(s) of first mates, %u of second mates", n_files1, n_files2);
+    if (max_batch_reads == 1) return set_error(GROOT_E_INVALID, "paired FASTQ input: a batch of one read holds no fragment");
+    std::unique_ptr<groot_reads> r(new groot_reads());
+    r->mode = n_files2 ? kTwoStreams : kInterleaved;
+    if (int rc = open_common(r.get(), files1, n_files1, n_threads, block_bytes, max_batch_reads & ~1u, max_batch_bases)) return rc;
+    if (n_files2) {
+        r->mate.reset(new groot_reads());
+        r->mate->mode = kTwoStreams;
+        if (int rc = open_common(r->mate.get(), files2, n_files2, n_threads, r->block_bytes, max_batch_reads & ~1u, max_batch_bases)) return rc;
+        r->mate->open_more();
+        r->mate->started = true;
+    }
+    r->open_more();
+    r->started = true;
+    *out = r.release();
+    return GROOT_OK;
+}
 
 int groot_reads_open(const char *const *files, uint32_t n_files, uint32_t n_threads, uint64_t block_bytes, uint32_t max_batch_reads,
                      uint64_t max_batch_bases, groot_reads **out)
@@ -452,6 +609,8 @@ int groot_reads_next(groot_reads *r, groot_reads_batch **out)
 {
     if (!r || !out) return set_error(GROOT_E_INVALID, "null argument");
     *out = nullptr;
+    while (r->mode == kTwoStreams && r->ready.empty() && !r->input_done)
+        if (int rc = next_two(r)) return rc;
     while (r->ready.empty() && !r->input_done) {
         if (r->open.empty()) {
             // end of all input: what is left in the carry is whole lines of a last partial record, or nothing

@@ -433,6 +433,18 @@ class Aligner:
     def ec_reset(self):
         self._check(lib().groot_hip_ec_reset(self._h))
 
+    # ---- paired-end reads (groot_hip_pairs_*) ------------------------------------------------------
+    def pairs_enable(self, on=True):
+        """reads 2i and 2i+1 of every batch are the mates of one fragment: shared reads and equivalence classes count units
+        (include/groot_hip.h, "paired-end reads").  Only while nothing is in flight; a batch of an odd number of reads is then refused."""
+        self._check(lib().groot_hip_pairs_enable(self._h, C.c_int(1 if on else 0)))
+
+    def pairs_stats(self):
+        """{"joined", "split", "single"} fragments since enable / reset (groot_hip_pairs_stats)"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        self._check(lib().groot_hip_pairs_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("joined", "split", "single"), (x.value for x in v)))
+
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):
         seq = np.ascontiguousarray(seq_concat, dtype=np.uint8)

@@ -241,9 +241,17 @@ class ParallelReads:
     """groot_reads_*: parallel FASTQ ingest (reader thread per file, parse + 2-bit pack over all cores); batches carry the
     wire format of groot_hip_submit_packed16 and positions into the FASTQ text"""
 
-    def __init__(self, files, threads=0, block_bytes=0, max_batch_reads=0, max_batch_bases=0):
+    def __init__(self, files, threads=0, block_bytes=0, max_batch_reads=0, max_batch_bases=0, mates=None, interleaved=False):
+        """mates: the files of the second mates, read in lockstep with `files` (groot_reads_open_paired: batches of whole fragments,
+        read 2i from files, 2i+1 from mates); interleaved: `files` is one stream that holds the mates alternately"""
         self._h = C.c_void_p()
         arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
+        if mates is not None or interleaved:
+            m = [] if interleaved else list(mates)
+            arr2 = (C.c_char_p * len(m))(*[f.encode() for f in m])
+            _check(lib().groot_reads_open_paired(arr, C.c_uint32(len(files)), arr2, C.c_uint32(len(m)), C.c_uint32(threads), C.c_uint64(block_bytes),
+                                                 C.c_uint32(max_batch_reads), C.c_uint64(max_batch_bases), C.byref(self._h)))
+            return
         _check(lib().groot_reads_open(arr, C.c_uint32(len(files)), C.c_uint32(threads), C.c_uint64(block_bytes), C.c_uint32(max_batch_reads),
                                       C.c_uint64(max_batch_bases), C.byref(self._h)))
 

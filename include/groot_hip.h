@@ -346,6 +346,32 @@ int groot_hip_ec_reset(groot_ctx *ctx);
  * in more than one under GROOT_TEST_SHARED_SLOW), times the table grew.  Waits for everything in flight.  GROOT_E_STATE when off. */
 int groot_hip_ec_stats(groot_ctx *ctx, uint64_t *reads, uint64_t *distinct, uint64_t *slow_reads, uint64_t *grows);
 
+/* ---- paired-end reads -------------------------------------------------------------------------------------------------
+ * With pairing on, reads 2i and 2i+1 of a batch are the mates of fragment i.  The index is batch-relative: read_id - first_read_id;
+ * first_read_id may be odd.  Let A = S(r_2i) and B = S(r_2i+1), S(r) exactly as above.
+ *   joined:  A and B intersect.  The fragment is one unit with the set A n B.
+ *   split:   A and B are non-empty and do not intersect.  The fragment is two units, A and B, exactly as without pairing (mates on
+ *            different genes are evidence for both).
+ *   single:  exactly one of A, B is non-empty.  The fragment is one unit with that set.
+ *   none:    both are empty.  There is no unit.
+ * Everywhere shared reads and equivalence classes say "read", paired mode says "unit": shared[a][b] is the number of units whose set
+ * holds both a and b (the diagonal: the units on a); an EC is a distinct unit set and its count the units with that set; the `reads`
+ * fields of the shared and EC stats count units; bootstrap replicates draw units.  Coverage, records, call counts, weights, the BAM and
+ * every groot_counts field do not depend on pairing.
+ * The units are made on the device by a gather of their own (kernels_shared.hpp, shared_gather_paired_kernel): one thread per fragment
+ * intersects the two mates' per-graph path sets; the result does not depend on which path a unit takes (in at most 4 graphs or in
+ * more, GROOT_TEST_SHARED_SLOW, a redone batch, the pipeline depth, the first-pass variant).  Fragments whose mates lie in different
+ * batches are not supported.  Off by default: then every launch and every count is what it is without this section. */
+/* Switch on or off; takes effect on whichever of shared reads and equivalence classes are on, whichever is enabled first, and costs
+ * nothing (no launch, no memory) while both are off.  Zeroes the fragment counts.  Only while nothing is in flight (GROOT_E_STATE).
+ * While it is on, every submit call (groot_hip_submit, _packed, _packed16, _acquired, _device) of a batch with an odd number of
+ * reads fails with GROOT_E_INVALID before anything is enqueued; the ctx stays usable, and a batch of 0 reads is fine. */
+int groot_hip_pairs_enable(groot_ctx *ctx, int on);
+/* Fragments per class since groot_hip_pairs_enable, groot_hip_shared_reset or groot_hip_ec_reset (each zeroes them), counted once
+ * exactly as the counters are.  joined + 2 split + single = the `reads` of groot_hip_shared_stats = the `reads` of groot_hip_ec_stats.
+ * Waits for everything in flight.  GROOT_E_STATE when pairing is off. */
+int groot_hip_pairs_stats(groot_ctx *ctx, uint64_t *joined, uint64_t *split, uint64_t *single);
+
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
  * the device, bit for bit in boot_count, alpha and iterations.  Quoted from there: draw j (0 <= j < n_draws; n_draws = 0 means N, the sum

@@ -236,6 +236,15 @@ typedef struct groot_reads_view {
  * max_batch_reads reads (0 = 1<<20) and max_batch_bases bases (0 = 256 per read) */
 int groot_reads_open(const char *const *files, uint32_t n_files, uint32_t n_threads, uint64_t block_bytes, uint32_t max_batch_reads,
                      uint64_t max_batch_bases, groot_reads **out);
+/* Paired-end input: batches of whole fragments with the mates interleaved, read 2i from files1 and read 2i+1 from files2, the two lists
+ * read in lockstep (n_files2 == n_files1; the files of a list form one stream as above).  n_files2 == 0: files1 (or stdin) is ONE stream
+ * that holds the mates alternately -- the same batches.  n_reads of every batch is even: a fragment is never cut by max_batch_reads (an
+ * odd value is rounded down) or max_batch_bases.  Mate names must agree: the name runs up to the first whitespace and a trailing /1 or /2
+ * is removed before comparing; GROOT_E_FORMAT names the 1-based fragment number and both names.  GROOT_E_FORMAT too for a list that ends
+ * before its partner and for an interleaved stream with an odd number of records.  With two lists a batch's text is one stretch per
+ * stream (the record arrays hold positions: nothing is copied per read); the packed bases are in read order. */
+int groot_reads_open_paired(const char *const *files1, uint32_t n_files1, const char *const *files2, uint32_t n_files2, uint32_t n_threads,
+                            uint64_t block_bytes, uint32_t max_batch_reads, uint64_t max_batch_bases, groot_reads **out);
 int groot_reads_next(groot_reads *r, groot_reads_batch **out);   /* *out = NULL at the end of the input */
 void groot_reads_batch_view(const groot_reads_batch *b, groot_reads_view *view);
 void groot_reads_batch_free(groot_reads_batch *b);
