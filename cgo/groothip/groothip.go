@@ -222,6 +222,54 @@ func (c *Ctx) Close() {
 	}
 }
 
+// AcovEnable switches the assigned-coverage table on or off (include/groot_hip.h, "assigned coverage"): every record grouped by
+// (EC of its read, path, Pos, last).  Switching it on switches equivalence classes on.  Nothing may be in flight.
+func (c *Ctx) AcovEnable(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.groot_hip_acov_enable(c.h, v); rc != 0 {
+		return c.err("groot_hip_acov_enable")
+	}
+	return nil
+}
+
+// AcovExport returns the ctx's ECs (CSR, canonical order) and its table: tuples[4i..4i+4) = (EC index, path, Pos, last), n[i] records
+func (c *Ctx) AcovExport() (off []uint64, ids []uint32, count []uint64, tuples []uint32, n []uint64, err error) {
+	var ne, ni, nt C.uint64_t
+	if rc := C.groot_hip_acov_export(c.h, nil, nil, nil, nil, nil, 0, 0, 0, &ne, &ni, &nt); rc != 0 {
+		return nil, nil, nil, nil, nil, c.err("groot_hip_acov_export")
+	}
+	off = make([]uint64, uint64(ne)+1)
+	ids = make([]uint32, uint64(ni)+1)
+	count = make([]uint64, uint64(ne)+1)
+	tuples = make([]uint32, 4*uint64(nt)+4)
+	n = make([]uint64, uint64(nt)+1)
+	if rc := C.groot_hip_acov_export(c.h, (*C.uint64_t)(unsafe.Pointer(&off[0])), (*C.uint32_t)(unsafe.Pointer(&ids[0])), (*C.uint64_t)(unsafe.Pointer(&count[0])), (*C.uint32_t)(unsafe.Pointer(&tuples[0])), (*C.uint64_t)(unsafe.Pointer(&n[0])), ne, ni, nt, &ne, &ni, &nt); rc != 0 {
+		return nil, nil, nil, nil, nil, c.err("groot_hip_acov_export")
+	}
+	return off, ids[:ni], count[:ne], tuples[:4*uint64(nt)], n[:nt], nil
+}
+
+// AcovStats returns the records and distinct tuples in the table, its slots, the times it grew, the records grouped on the host
+// and the kernels launched for it since the ctx was opened
+func (c *Ctx) AcovStats() (records, tuples, slots, grows, slowRecords, launches uint64, err error) {
+	var r, t, s, g, sr, l C.uint64_t
+	if rc := C.groot_hip_acov_stats(c.h, &r, &t, &s, &g, &sr, &l); rc != 0 {
+		return 0, 0, 0, 0, 0, 0, c.err("groot_hip_acov_stats")
+	}
+	return uint64(r), uint64(t), uint64(s), uint64(g), uint64(sr), uint64(l), nil
+}
+
+// AcovReset empties the table (after waiting for everything in flight)
+func (c *Ctx) AcovReset() error {
+	if rc := C.groot_hip_acov_reset(c.h); rc != 0 {
+		return c.err("groot_hip_acov_reset")
+	}
+	return nil
+}
+
 // PairsEnable switches paired-end counting on or off: reads 2i and 2i+1 of every batch are then the mates of one fragment, and
 // shared reads and equivalence classes count units (include/groot_hip.h, "paired-end reads").  Nothing may be in flight.
 func (c *Ctx) PairsEnable(on bool) error {

@@ -70,8 +70,8 @@ void logf(const char *fmt, ...)
 }
 
 struct Args {
-    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out, abundance_out;
-    double cov_cutoff = 0.97, abundance_min = 1.0;
+    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out, abundance_out, calls_out;
+    double cov_cutoff = 0.97, abundance_min = 1.0, call_depth = 1.0;
     bool low_cov = false, no_bam = false;
     bool paired = false, interleaved = false;   // --paired / --interleaved: the FASTQ input is fragments (groot_reads_open_paired, groot_hip_pairs_enable)
     uint32_t bootstraps = 0;               // --bootstraps: replicates behind the four bootstrap columns of --abundance (0 = none)
@@ -111,18 +111,21 @@ void usage()
             "                  [--gpu 0 | --gpus N] [--batch 1048576] [--maxReadLen 512] [--bam out.bam] [--bamLevel -2..9] [--stats f.json]\n"
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
             "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0]] [--noBam]\n"
-            "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved]\n"
+            "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
             "                   --abundance: `name reads em_reads fraction` per ARG with em_reads >= --abundanceMin, by EM over the reads' path sets;\n"
             "                   --bootstraps: with --abundance, four more columns `boot_mean boot_sd boot_lo boot_hi` from B replicates of the reads\n"
             "                   resampled with replacement (--bootSeed), each with its own EM, drawn and fitted on the GPU;\n"
+            "                   --calls: with --abundance, per line of the abundance file `name em_reads length depth breadth cigar called`: the pileup of\n"
+            "                   the reads the EM assigns to the ARG (a record weighs its read's posterior on that ARG); a base is covered at depth >=\n"
+            "                   --callDepth, called = 1 at breadth >= --covCutoff;\n"
             "                   --paired: the -f files are R1,R2[,R1b,R2b...], first with second, third with fourth; --interleaved: the mates alternate in\n"
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
-            "                  [--bootstraps B [--bootSeed 1]] [-p N]\n"
+            "                  [--bootstraps B [--bootSeed 1]] [-p N] [--calls c.tsv [--callDepth 1.0]]\n"
             "                  (BAM from stdin unless --bamFile; --bootstraps: the same columns as align writes, computed on -p host threads)\n",
             groot_host_version());
 }
@@ -159,6 +162,8 @@ Args parse(int argc, char **argv)
         else if (a.cmd == "align" && f == "--report") a.report_out = v();
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--sharedReads") a.shared_out = v();
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--abundance") a.abundance_out = v();
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--calls") a.calls_out = v();
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--callDepth") a.call_depth = atof(v().c_str());
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--abundanceMin") a.abundance_min = atof(v().c_str());
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootstraps") a.bootstraps = (uint32_t)std::max(0l, atol(v().c_str()));
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootSeed") a.boot_seed = strtoull(v().c_str(), nullptr, 10);
@@ -368,6 +373,15 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     const bool want_ab = !a.abundance_out.empty();
     if (want_ab && a.no_align) { fprintf(stderr, "--abundance needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
     if (a.bootstraps && !want_ab) { fprintf(stderr, "--bootstraps adds columns to the abundance file: it needs --abundance\n"); return 1; }
+    const bool want_calls = !a.calls_out.empty();
+    if (want_calls && !want_ab) { fprintf(stderr, "--calls has a line per line of the abundance file: it needs --abundance\n"); return 1; }
+    if (want_calls && a.no_align) { fprintf(stderr, "--calls needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
+    if (want_calls && (a.paired || a.interleaved)) {
+        fprintf(stderr, "--calls cannot be combined with --paired / --interleaved yet: a fragment's set is the intersection of its mates' sets, and the records "
+                        "outside the intersection have no weight rule\n");
+        return 1;
+    }
+    if (want_calls && a.cov_cutoff > 1.0) { fprintf(stderr, "supplied coverage cutoff exceeds 1.0 (100%%): %g\n", a.cov_cutoff); return 1; }
     if (a.no_bam && !want_report && !want_ab) { fprintf(stderr, "--noBam without --report would leave no output of the alignments\n"); return 1; }
     if (a.no_bam && !a.bam_out.empty()) { fprintf(stderr, "--noBam and --bam contradict each other\n"); return 1; }
     if (a.paired && a.interleaved) { fprintf(stderr, "--paired and --interleaved contradict each other: the mates come in two files or in one\n"); return 1; }
@@ -539,6 +553,11 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     std::vector<uint64_t> ec_off{0}, ec_cnt;     // --abundance: the ECs of every ctx, appended (CSR)
     std::vector<uint32_t> ec_ids;
     uint64_t fr_joined = 0, fr_split = 0, fr_single = 0;     // --paired / --interleaved: fragments per class, summed over the ctxs
+    struct AcovExport {                          // --calls: every ctx's ECs and assigned-coverage table, as exported (groot_host_acov_merge)
+        std::vector<uint64_t> off, cnt, tn;
+        std::vector<uint32_t> ids, tuples;
+    };
+    std::vector<std::unique_ptr<AcovExport>> acov_exports;
     auto cov_harvest = [&](groot_ctx *ctx) -> int {
         if (frags) {
             uint64_t j = 0, sp = 0, si = 0;
@@ -546,7 +565,21 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             std::lock_guard<std::mutex> lk(cov_mu);
             fr_joined += j; fr_split += sp; fr_single += si;
         }
-        if (want_ab) {
+        if (want_calls) {
+            uint64_t ne = 0, ni = 0, nt = 0;
+            if (int rc = groot_hip_acov_export(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, &ne, &ni, &nt)) return rc;
+            std::unique_ptr<AcovExport> x(new AcovExport());
+            x->off.resize(ne + 1); x->cnt.resize(ne + 1); x->ids.resize(ni + 1); x->tuples.resize(4 * nt + 4); x->tn.resize(nt + 1);
+            if (ne || nt)
+                if (int rc = groot_hip_acov_export(ctx, x->off.data(), x->ids.data(), x->cnt.data(), x->tuples.data(), x->tn.data(), ne, ni, nt, &ne, &ni, &nt)) return rc;
+            x->cnt.resize(ne); x->ids.resize(ni); x->tuples.resize(4 * nt); x->tn.resize(nt);
+            std::lock_guard<std::mutex> lk(cov_mu);
+            const uint64_t base = ec_ids.size();
+            for (uint64_t e = 0; e < ne; e++) ec_off.push_back(base + x->off[e + 1]);
+            ec_ids.insert(ec_ids.end(), x->ids.begin(), x->ids.end());
+            ec_cnt.insert(ec_cnt.end(), x->cnt.begin(), x->cnt.end());
+            acov_exports.push_back(std::move(x));
+        } else if (want_ab) {
             uint64_t ne = 0, ni = 0, me = 0, mi = 0;
             if (int rc = groot_hip_ec_export(ctx, nullptr, nullptr, nullptr, 0, 0, &ne, &ni)) return rc;
             std::vector<uint64_t> off(ne + 1), cnt(ne);
@@ -586,7 +619,9 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
         if (want_shared)
             if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
-        return want_ab ? groot_hip_ec_enable(ctx, on) : 0;
+        if (want_calls && on)
+            if (int rc = groot_hip_acov_enable(ctx, 1)) return rc;
+        return want_ab ? groot_hip_ec_enable(ctx, on) : 0;     // (off: assigned coverage goes with it)
     };
     for (int d : devices) {
         std::unique_ptr<Gpu> g(new Gpu());
@@ -802,6 +837,30 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         logf("\tabundance: %llu equivalence class(es), EM of %u iteration(s) in %.3f s, %llu ARG(s) with at least %g reads written to %s",
              (unsigned long long)ec_cnt.size(), iters, seconds_since(t_em), (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
     }
+    if (want_calls) {
+        auto t_calls = std::chrono::steady_clock::now();
+        const size_t k = acov_exports.size();
+        std::vector<const uint64_t *> p_off(k), p_cnt(k), p_tn(k);
+        std::vector<const uint32_t *> p_ids(k), p_tup(k);
+        std::vector<uint64_t> n_ec(k), n_tp(k);
+        uint64_t s_ec = 0, s_ids = 0, s_tp = 0;
+        for (size_t i = 0; i < k; i++) {
+            const AcovExport &x = *acov_exports[i];
+            p_off[i] = x.off.data(); p_cnt[i] = x.cnt.data(); p_tn[i] = x.tn.data(); p_ids[i] = x.ids.data(); p_tup[i] = x.tuples.data();
+            n_ec[i] = x.cnt.size(); n_tp[i] = x.tn.size();
+            s_ec += x.cnt.size(); s_ids += x.ids.size(); s_tp += x.tn.size();
+        }
+        std::vector<uint64_t> m_off(s_ec + 1), m_cnt(s_ec + 1), m_tn(s_tp + 1);
+        std::vector<uint32_t> m_ids(s_ids + 1), m_tup(4 * s_tp + 4);
+        uint64_t m_ec = 0, m_tp = 0, n_lines = 0, n_called = 0;
+        if (groot_host_acov_merge(v.n_paths, (uint32_t)k, p_off.data(), p_ids.data(), p_cnt.data(), n_ec.data(), p_tup.data(), p_tn.data(), n_tp.data(), m_off.data(),
+                                  m_ids.data(), m_cnt.data(), m_tup.data(), m_tn.data(), &m_ec, &m_tp) ||
+            groot_host_calls_from_table(&v, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), nullptr, m_tp, m_tup.data(), m_tn.data(), a.abundance_min, a.call_depth,
+                                        a.cov_cutoff, a.calls_out.c_str(), &n_lines, &n_called))
+            die("%s", groot_host_last_error());
+        logf("\tcalls: %llu tuple(s) of (class, ARG, interval) from %zu context(s), %llu line(s), %llu called at depth >= %g over >= %.2f of the length, in %.3f s, written to %s",
+             (unsigned long long)m_tp, k, (unsigned long long)n_lines, (unsigned long long)n_called, a.call_depth, a.cov_cutoff, seconds_since(t_calls), a.calls_out.c_str());
+    }
     if (want_report) {
         uint64_t n_rep = 0;
         if (groot_host_report_coverage(&v, cov_records.data(), cov_depth.data(), a.cov_cutoff, a.low_cov ? 1 : 0, a.report_out.c_str(), &n_rep))
@@ -946,6 +1005,7 @@ int run_report(const Args &a)
     }
     if (a.cov_cutoff > 1.0) die("supplied coverage cutoff exceeds 1.0 (100%%): %g", a.cov_cutoff);
     if (a.bootstraps && a.abundance_out.empty()) die("--bootstraps adds columns to the abundance file: it needs --abundance");
+    if (!a.calls_out.empty() && a.abundance_out.empty()) die("--calls has a line per line of the abundance file: it needs --abundance");
     logf("\tcoverage cutoff: %.2f", a.cov_cutoff);
     logf("\tprocessors: %d", a.proc);
     uint64_t n = 0, n_lines = 0;
@@ -975,6 +1035,13 @@ int run_report(const Args &a)
             die("%s", groot_host_last_error());
         if (a.bootstraps) logf("\tbootstrap: %u replicate(s) on %d host thread(s) (seed %llu)", a.bootstraps, std::max(1, a.proc), (unsigned long long)a.boot_seed);
         logf("\tabundance: %llu ARG(s) with at least %g reads written to %s", (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
+    }
+    if (!a.calls_out.empty()) {
+        uint64_t n_called = 0, n_tuples = 0;
+        auto t_calls = std::chrono::steady_clock::now();
+        if (groot_host_report_calls(bam, a.abundance_min, a.call_depth, a.cov_cutoff, a.calls_out.c_str(), &n_lines, &n_called, &n_tuples)) die("%s", groot_host_last_error());
+        logf("\tcalls: %llu tuple(s) of (class, ARG, interval), %llu line(s), %llu called at depth >= %g over >= %.2f of the length, in %.3f s, written to %s",
+             (unsigned long long)n_tuples, (unsigned long long)n_lines, (unsigned long long)n_called, a.call_depth, a.cov_cutoff, seconds_since(t_calls), a.calls_out.c_str());
     }
     if (!spool.empty()) unlink(spool.c_str());
     logf("finished");

@@ -15,7 +15,9 @@
 #include <chrono>
 #include <deque>
 #include <iterator>
+#include <array>
 #include <map>
+#include <tuple>
 #include <memory>
 #include <numeric>
 #include <string>
@@ -27,6 +29,7 @@
 #include "kernels_boot.hpp"
 #include "kernels_cov.hpp"
 #include "kernels_ec.hpp"
+#include "kernels_acov.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_path.hpp"
 #include "kernels_shared.hpp"
@@ -85,6 +88,7 @@ struct Knobs {
     bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false,
          shared_slow = false, serial_tail = false;
     uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
+    uint32_t acov_slots = 0;               // GROOT_TEST_ACOV_SLOTS: initial slots of the assigned-coverage table (0 = the default)
     static Knobs read()
     {
         Knobs k;
@@ -97,6 +101,7 @@ struct Knobs {
         k.shared_slow = getenv("GROOT_TEST_SHARED_SLOW") != nullptr;      // shared reads: every read in more than one graph takes the slow path
         k.serial_tail = getenv("GROOT_SERIAL_TAIL") != nullptr;           // the tail of the align stage stays on the walk stream (no tail stream: the A/B baseline)
         if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
+        if (const char *e = getenv("GROOT_TEST_ACOV_SLOTS")) k.acov_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         return k;
     }
 };
@@ -160,7 +165,9 @@ struct Slot {
     std::string status_msg;
     groot_stage_ms ms{};
     DevBuf<uint32_t> d_ec_slow;            // equivalence classes: the batch's slow-path reads (ec_merge_kernel), read at collect
-    PinBuf<uint32_t> h_ec;                 // [0] their number, [1] the table's fill behind this batch's merge
+    PinBuf<uint32_t> h_ec;                 // [0] their number, [1] the table's fill behind this batch's merge; assigned coverage: [2] d_acov_state[0], [3] its table's fill
+    DevBuf<uint32_t> d_acov_ser;           // assigned coverage: the EC serial of every read of the batch (acov_serial_kernel); the counting kernels read it, also when collect repeats them
+    DevBuf<uint32_t> d_acov_state;         // [0] 1 = the batch's claim phase ran out of room (its add phase then did nothing), 2 = a key went missing
     const uint8_t *seq() const { return input == IN_DEVICE ? ext_seq : d_seq.p; }
     const uint64_t *off() const { return input == IN_DEVICE ? ext_off : d_off.p; }
 };
@@ -334,6 +341,17 @@ struct groot_ctx {
     uint64_t ec_fill_known = 0;            // the fill read back at the newest collect
     uint64_t ec_grows = 0, ec_slow_reads = 0;
     std::map<std::vector<uint32_t>, uint64_t> ec_host;   // the exact S(r) of slow-path reads -> reads
+    DevBuf<uint32_t> ec_serial;            // [ec_cap] the serial of every claimed slot (EcTable::serial)
+    // assigned coverage (groot_hip_acov_*, kernels_acov.hpp): the run's records grouped by (EC serial, path, Pos, last) in a run-wide
+    // open-addressing table; needs equivalence classes on.  Slow-path reads are grouped on the host at collect (ec_collect).
+    bool acov_on = false;
+    uint32_t acov_cap = 0;                 // slots (a power of two)
+    DevBuf<unsigned long long> acov_k0, acov_k1, acov_cnt;
+    DevBuf<uint32_t> acov_fill, acov_err, acov_tab_ser, acov_np_off, acov_len;
+    DevBuf<uint2> acov_np;
+    uint64_t acov_grows = 0, acov_slow_records = 0, acov_redone = 0;
+    uint64_t acov_launches = 0;            // kernels launched for it since open (stays put while it is off)
+    std::map<std::vector<uint32_t>, std::map<std::array<uint32_t, 3>, uint64_t>> acov_host;   // S(r) -> (path, Pos, last) -> records, of slow-path reads
 };
 
 // A ctx drives five HIP streams at once -- seed stage, walk (first pass of the align stage), tail (align_kernel + order stage), copy-in,
@@ -1026,18 +1044,19 @@ static int launch_order_stage(groot_ctx *c, Slot *s, bool update_weights)
 // ---- equivalence classes (kernels_ec.hpp) ----
 static EcTable ec_table(const groot_ctx *c)
 {
-    return EcTable{c->ec_claim.p, c->ec_graph.p, c->ec_mask.p, c->ec_cnt.p, c->ec_cap - 1};
+    return EcTable{c->ec_claim.p, c->ec_graph.p, c->ec_mask.p, c->ec_cnt.p, c->ec_serial.p, c->ec_cap - 1};
 }
 
 // the table's buffers for cap slots, free
 static hipError_t ec_alloc(groot_ctx *c, uint32_t cap, DevBuf<uint32_t> &claim, DevBuf<uint32_t> &graph, DevBuf<uint64_t> &mask, DevBuf<unsigned long long> &cnt,
-                           hipStream_t st)
+                           DevBuf<uint32_t> &serial, hipStream_t st)
 {
     const size_t pw = std::max<uint32_t>(c->pw_view, 1u);
     hipError_t e = claim.alloc(cap);
     if (e == hipSuccess) e = graph.alloc((size_t)cap * kSharedSegs);
     if (e == hipSuccess) e = mask.alloc((size_t)cap * kSharedSegs * pw);
     if (e == hipSuccess) e = cnt.alloc(cap);
+    if (e == hipSuccess) e = serial.alloc(cap);
     if (e == hipSuccess) e = hipMemsetAsync(claim.p, 0, (size_t)cap * sizeof(uint32_t), st);
     return e;
 }
@@ -1055,17 +1074,17 @@ static int ec_reserve(groot_ctx *c, Slot *s)
     uint64_t cap = c->ec_cap;
     while (cap < need) cap *= 2;
     if (cap > (1ull << 31)) return fail(c, GROOT_E_NOSPACE, "equivalence classes: the table would need %llu slots", (unsigned long long)cap);
-    DevBuf<uint32_t> claim, graph;
+    DevBuf<uint32_t> claim, graph, serial;
     DevBuf<uint64_t> mask;
     DevBuf<unsigned long long> cnt;
-    hipError_t e = ec_alloc(c, (uint32_t)cap, claim, graph, mask, cnt, c->tstream);
+    hipError_t e = ec_alloc(c, (uint32_t)cap, claim, graph, mask, cnt, serial, c->tstream);
     if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "equivalence classes: growing the table to %llu slots: %s", (unsigned long long)cap, hipGetErrorString(e));
-    const EcTable from = ec_table(c), to{claim.p, graph.p, mask.p, cnt.p, (uint32_t)cap - 1};
+    const EcTable from = ec_table(c), to{claim.p, graph.p, mask.p, cnt.p, serial.p, (uint32_t)cap - 1};
     hipLaunchKernelGGL(ec_rehash_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
                        from, c->ec_cap, to, std::max<uint32_t>(c->pw_view, 1u), ++c->ec_epoch);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->tstream));
-    c->ec_claim.swap(claim); c->ec_graph.swap(graph); c->ec_mask.swap(mask); c->ec_cnt.swap(cnt);
+    c->ec_claim.swap(claim); c->ec_graph.swap(graph); c->ec_mask.swap(mask); c->ec_cnt.swap(cnt); c->ec_serial.swap(serial);
     c->ec_cap = (uint32_t)cap;
     c->ec_grows++;
     return GROOT_OK;
@@ -1084,6 +1103,125 @@ static void ec_set_of(const groot_ctx *c, const groot_trav *trav, const uint64_t
             }
     std::sort(ids.begin(), ids.end());
     ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+}
+
+// ---- assigned coverage (kernels_acov.hpp) ----
+static AcovTable acov_table(const groot_ctx *c)
+{
+    return AcovTable{c->acov_k0.p, c->acov_k1.p, c->acov_cnt.p, c->acov_cap - 1};
+}
+
+// the table's buffers for cap slots, free (k0 = 0, k1 = all ones, no counts)
+static hipError_t acov_alloc(uint32_t cap, DevBuf<unsigned long long> &k0, DevBuf<unsigned long long> &k1, DevBuf<unsigned long long> &cnt, hipStream_t st)
+{
+    hipError_t e = k0.alloc(cap);
+    if (e == hipSuccess) e = k1.alloc(cap);
+    if (e == hipSuccess) e = cnt.alloc(cap);
+    if (e == hipSuccess) e = hipMemsetAsync(k0.p, 0, (size_t)cap * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(k1.p, 0xFF, (size_t)cap * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, (size_t)cap * sizeof(unsigned long long), st);
+    return e;
+}
+
+// the claim and the add phase of slot s's batch on the tail stream; both read nothing but what the slot owns and the ctx's tables
+static int acov_count(groot_ctx *c, Slot *s)
+{
+    AcovArgs a{};
+    a.trav = s->d_trav.p; a.mask = s->d_mask.p; a.seq_off = s->off(); a.ctr = s->d_ctr.p;
+    a.node_np_off = c->acov_np_off.p; a.np = c->acov_np.p; a.graph_path_off = c->sh_gpo.p; a.path_len = c->acov_len.p;
+    a.read_ser = s->d_acov_ser.p; a.state = s->d_acov_state.p; a.fill = c->acov_fill.p;
+    a.cap = s->trav_cap; a.pw = c->pw_view; a.first_read_id = s->first_read_id; a.n_paths = (uint32_t)c->h_cov_len.size();
+    const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
+    hipLaunchKernelGGL(acov_count_kernel<false>, g, dim3(kBlock), 0, c->tstream, a, acov_table(c));
+    hipLaunchKernelGGL(acov_count_kernel<true>, g, dim3(kBlock), 0, c->tstream, a, acov_table(c));
+    c->acov_launches += 2;
+    HIP_TRY(c, hipGetLastError());
+    return GROOT_OK;
+}
+
+// behind the batch's ec_merge_kernel and before shared_expand_kernel clears the per-batch table (tail stream)
+static int acov_launch(groot_ctx *c, Slot *s, const SharedArgs &sa)
+{
+    HIP_TRY(c, s->d_acov_ser.reserve(std::max<uint32_t>(c->prm.max_batch_reads, 1u)));
+    HIP_TRY(c, s->d_acov_state.reserve(1));
+    HIP_TRY(c, hipMemsetAsync(s->d_acov_state.p, 0, sizeof(uint32_t), c->tstream));
+    const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
+    hipLaunchKernelGGL(acov_serial_kernel, g, dim3(kBlock), 0, c->tstream, sa, c->acov_tab_ser.p, s->d_acov_ser.p);
+    c->acov_launches++;
+    return acov_count(c, s);
+}
+
+// `factor` times the slots, every key and count moved over; everything launched on the tail stream has ended when this returns
+static int acov_grow(groot_ctx *c, uint32_t factor)
+{
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
+    const uint64_t cap = (uint64_t)factor * c->acov_cap;
+    if (cap > (1ull << 31)) return fail(c, GROOT_E_NOSPACE, "assigned coverage: the table would need %llu slots", (unsigned long long)cap);
+    DevBuf<unsigned long long> k0, k1, cnt;
+    hipError_t e = acov_alloc((uint32_t)cap, k0, k1, cnt, c->tstream);
+    if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "assigned coverage: growing the table to %llu slots: %s", (unsigned long long)cap, hipGetErrorString(e));
+    const AcovTable to{k0.p, k1.p, cnt.p, (uint32_t)cap - 1};
+    hipLaunchKernelGGL(acov_rehash_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->acov_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
+                       acov_table(c), c->acov_cap, to, c->acov_err.p);
+    c->acov_launches++;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
+    uint32_t err = 0;
+    HIP_TRY(c, hipMemcpy(&err, c->acov_err.p, sizeof err, hipMemcpyDeviceToHost));
+    if (err) return fail(c, GROOT_E_DEVICE, "assigned coverage: a key did not fit the grown table");
+    c->acov_k0.swap(k0); c->acov_k1.swap(k1); c->acov_cnt.swap(cnt);
+    c->acov_cap = (uint32_t)cap;
+    c->acov_grows++;
+    return GROOT_OK;
+}
+
+// At collect, while slot s still owns its records and its reads' serials: a batch whose claim phase ran out of room added nothing;
+// the table grows fourfold and both phases run again until the claim goes through.  A table more than half full is doubled.
+// refetch: the copies enqueue made are stale (the batch was redone).
+static int acov_collect(groot_ctx *c, Slot *s, bool refetch)
+{
+    auto fetch = [&]() -> int {
+        HIP_TRY(c, hipMemcpy(s->h_ec.p + 2, s->d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(s->h_ec.p + 3, c->acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return GROOT_OK;
+    };
+    if (refetch)
+        if (int rc = fetch()) return rc;
+    for (;;) {
+        const uint32_t st = s->h_ec.p[2], fill = s->h_ec.p[3];
+        if (st > 1) return fail(c, GROOT_E_DEVICE, "assigned coverage: a claimed key was not found in the table");
+        if (!st && 2ull * fill <= c->acov_cap) return GROOT_OK;
+        if (int rc = acov_grow(c, st ? 4u : 2u)) return rc;
+        if (!st) continue;
+        HIP_TRY(c, hipMemsetAsync(s->d_acov_state.p, 0, sizeof(uint32_t), c->tstream));
+        if (int rc = acov_count(c, s)) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
+        c->acov_redone++;
+        if (int rc = fetch()) return rc;
+    }
+}
+
+// the records of one slow-path read (trav[0..n), its path sets, its S(r) = ids) into acov_host; m_len = the read's length
+static void acov_fold_host(groot_ctx *c, const groot_trav *trav, const uint64_t *mask, size_t n, const std::vector<uint32_t> &ids, uint64_t read_len)
+{
+    const uint32_t pw = c->pw_view, n_paths = (uint32_t)c->h_cov_len.size();
+    auto &tab = c->acov_host[ids];
+    for (size_t t = 0; t < n; t++) {
+        const groot_trav &tr = trav[t];
+        const uint64_t m = read_len - ((tr.flags & GROOT_TRAV_START_CLIP) ? 1u : 0u) - ((tr.flags & GROOT_TRAV_END_CLIP) ? 1u : 0u);
+        const uint32_t g0 = c->h_cov_gpo[tr.graph_id];
+        for (uint32_t j = c->h_cov_np_off[tr.node]; j < c->h_cov_np_off[tr.node + 1]; j++) {
+            const uint2 e = c->h_cov_np[j];
+            if (!((mask[t * pw + (e.x >> 6)] >> (e.x & 63)) & 1ull)) continue;
+            const uint32_t gp = g0 + e.x;
+            if (gp >= n_paths) continue;
+            const uint64_t len = c->h_cov_len[gp], pos = (uint64_t)e.y + tr.offset;
+            if (len == 0 || pos > 0xFFFFFFFEull) continue;
+            const uint64_t last = std::min<uint64_t>(pos + m, len - 1);
+            tab[{gp, (uint32_t)pos, (uint32_t)last}]++;
+            c->acov_slow_records++;
+        }
+    }
 }
 
 // At collect, while slot s still owns its records: the table's fill, and the exact S(r) of the batch's slow-path reads into ec_host.
@@ -1115,6 +1253,11 @@ static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
         HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)lo * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     std::vector<uint32_t> ids, ids_a, ids_b;
+    std::vector<uint64_t> offs;            // assigned coverage: the batch's read offsets (a record's M op is the read's length less its clips)
+    if (c->acov_on) {
+        offs.resize((size_t)s->n_reads + 1);
+        HIP_TRY(c, hipMemcpy(offs.data(), s->off(), offs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
     for (uint32_t i = 0; i < n_slow; i++) {
         const uint32_t t0 = span[sw * i], tm = span[sw * i + sw - 2], t1 = span[sw * i + sw - 1];
         if (!whole) {
@@ -1130,6 +1273,10 @@ static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
             std::set_intersection(ids_a.begin(), ids_a.end(), ids_b.begin(), ids_b.end(), std::back_inserter(ids));
         } else {
             ec_set_of(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids);
+        }
+        if (c->acov_on && !ids.empty() && t1 > t0) {
+            const uint32_t r = tr[o].read_id - s->first_read_id;
+            acov_fold_host(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids, offs[r + 1] - offs[r]);
         }
         if (!ids.empty()) c->ec_host[ids]++;
     }
@@ -1203,10 +1350,13 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
         if (c->ec_on) {
             if (int rc = ec_reserve(c, s)) return rc;
             HIP_TRY(c, s->d_ec_slow.reserve(1 + (paired ? 3 : 2) * (size_t)c->prm.max_batch_reads));
-            HIP_TRY(c, s->h_ec.reserve(2));
+            HIP_TRY(c, s->h_ec.reserve(4));
             const dim3 gm(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u));
-            if (paired) hipLaunchKernelGGL(ec_merge_kernel<true>, gm, dim3(kBlock), 0, c->tstream, sa, ec_table(c), tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p);
-            else hipLaunchKernelGGL(ec_merge_kernel<false>, gm, dim3(kBlock), 0, c->tstream, sa, ec_table(c), tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p);
+            if (paired) hipLaunchKernelGGL(ec_merge_kernel<true>, gm, dim3(kBlock), 0, c->tstream, sa, ec_table(c), tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p, nullptr);
+            else hipLaunchKernelGGL(ec_merge_kernel<false>, gm, dim3(kBlock), 0, c->tstream, sa, ec_table(c), tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p,
+                                    c->acov_on ? c->acov_tab_ser.p : nullptr);
+            if (c->acov_on)
+                if (int rc = acov_launch(c, s, sa)) return rc;
         }
         const dim3 ge(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u));
         if (paired) hipLaunchKernelGGL(shared_expand_kernel<true>, ge, dim3(kBlock), 0, c->tstream, sa, tab);
@@ -1397,6 +1547,10 @@ static int enqueue(groot_ctx *c, Slot *s)
     if (c->ec_on) {    // (ahead of the counters: there when they are)
         HIP_TRY(c, hipMemcpyAsync(s->h_ec.p, s->d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
         HIP_TRY(c, hipMemcpyAsync(s->h_ec.p + 1, c->ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+        if (c->acov_on) {
+            HIP_TRY(c, hipMemcpyAsync(s->h_ec.p + 2, s->d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+            HIP_TRY(c, hipMemcpyAsync(s->h_ec.p + 3, c->acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+        }
     }
     HIP_TRY(c, hipMemcpyAsync(s->h_ctr.p, s->d_ctr.p, sizeof(DeviceCounters), hipMemcpyDeviceToHost, c->d2h_stream));
     HIP_TRY(c, hipEventRecord(s->ev_ctr, c->d2h_stream));
@@ -1501,6 +1655,8 @@ static int finish_counters(groot_ctx *c, Slot *s)
     s->n_trav = s->n_reads ? h.n_trav : 0;
     if (c->ec_on && s->n_reads) {
         if (int rc = ec_collect(c, s, redone)) return rc;
+        if (c->acov_on)
+            if (int rc = acov_collect(c, s, redone)) return rc;
     }
     groot_counts &o = s->counts;
     o.received = s->n_reads;              // boss.go:194 receivedReads++ for every read
@@ -3744,7 +3900,9 @@ int groot_hip_ec_enable(groot_ctx *c, int on)
     if (!idle(c)) return fail(c, GROOT_E_STATE, "equivalence classes can only be switched while nothing is in flight");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!on) {
-        for (auto *b : {&c->ec_claim, &c->ec_graph, &c->ec_fill}) b->release();
+        if (c->acov_on)
+            if (int rc = groot_hip_acov_enable(c, 0)) return rc;     // (its tuples are keyed by this table's serials)
+        for (auto *b : {&c->ec_claim, &c->ec_graph, &c->ec_fill, &c->ec_serial}) b->release();
         c->ec_mask.release(); c->ec_cnt.release();
         c->ec_host.clear();
         c->ec_on = false;
@@ -3759,7 +3917,7 @@ int groot_hip_ec_enable(groot_ctx *c, int on)
     while (cap < (c->kn.ec_slots ? std::max<uint32_t>(c->kn.ec_slots, 2u) : (1u << 16))) cap <<= 1;
     auto undo = [&](int rc) { c->ec_on = true; groot_hip_ec_enable(c, 0); return rc; };
     hipError_t e = sh_common_alloc(c);
-    if (e == hipSuccess) e = ec_alloc(c, cap, c->ec_claim, c->ec_graph, c->ec_mask, c->ec_cnt, c->tstream);
+    if (e == hipSuccess) e = ec_alloc(c, cap, c->ec_claim, c->ec_graph, c->ec_mask, c->ec_cnt, c->ec_serial, c->tstream);
     if (e == hipSuccess) e = c->ec_fill.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(c->ec_fill.p, 0, sizeof(uint32_t), c->tstream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->tstream);
@@ -3772,7 +3930,8 @@ int groot_hip_ec_enable(groot_ctx *c, int on)
 }
 
 // the device table and the host map merged: S -> reads, in canonical order (lexicographic on the ascending ID lists)
-static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &out)
+// by_serial (optional): the ID list of every slot of the device table, by the slot's serial
+static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &out, std::vector<std::vector<uint32_t>> *by_serial = nullptr)
 {
     if (int rc = drain(c)) return rc;     // (the batches in flight through their redo and their slow-path reads)
     uint32_t fill = 0;
@@ -3780,16 +3939,17 @@ static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &ou
     out = c->ec_host;
     if (!fill) return GROOT_OK;
     const uint32_t pw = std::max<uint32_t>(c->pw_view, 1u);
-    DevBuf<uint32_t> g, n;
+    DevBuf<uint32_t> g, n, ser;
     DevBuf<uint64_t> m;
     DevBuf<unsigned long long> cnt;
+    HIP_TRY(c, ser.alloc(fill));
     HIP_TRY(c, g.alloc((size_t)fill * kSharedSegs));
     HIP_TRY(c, m.alloc((size_t)fill * kSharedSegs * pw));
     HIP_TRY(c, cnt.alloc(fill));
     HIP_TRY(c, n.alloc(1));
     HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->tstream));
     hipLaunchKernelGGL(ec_export_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
-                       ec_table(c), c->ec_cap, pw, g.p, m.p, cnt.p, n.p, fill);
+                       ec_table(c), c->ec_cap, pw, g.p, m.p, cnt.p, ser.p, n.p, fill);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->tstream));
     uint32_t got = 0;
@@ -3800,6 +3960,9 @@ static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &ou
     HIP_TRY(c, hipMemcpy(hg.data(), g.p, hg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(hm.data(), m.p, hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(hc.data(), cnt.p, hc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> hs(fill);
+    HIP_TRY(c, hipMemcpy(hs.data(), ser.p, hs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (by_serial) by_serial->assign(fill, {});
     std::vector<groot_trav> tr;
     std::vector<uint64_t> mk;
     std::vector<uint32_t> ids;
@@ -3814,6 +3977,7 @@ static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &ou
         }
         ec_set_of(c, tr.data(), mk.data(), tr.size(), ids);
         if (!ids.empty() && hc[i]) out[ids] += hc[i];
+        if (by_serial && hs[i] < fill) (*by_serial)[hs[i]] = ids;
     }
     return GROOT_OK;
 }
@@ -3867,6 +4031,177 @@ int groot_hip_ec_reset(groot_ctx *c)
     c->ec_fill_known = c->ec_grows = c->ec_slow_reads = 0;
     c->ec_host.clear();
     if (c->pairs_on) HIP_TRY(c, hipMemset(c->sh_stats.p + 3, 0, (kSharedStats - 3) * sizeof(unsigned long long)));
+    return groot_hip_acov_reset(c);     // (the serials start again: its tuples would name other classes)
+}
+
+// ---- assigned coverage (kernels_acov.hpp; the definition is in groot_hip.h) ------------------------------------------------
+int groot_hip_acov_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "assigned coverage can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!on) {
+        for (auto *b : {&c->acov_k0, &c->acov_k1, &c->acov_cnt}) b->release();
+        for (auto *b : {&c->acov_fill, &c->acov_err, &c->acov_tab_ser, &c->acov_np_off, &c->acov_len}) b->release();
+        c->acov_np.release();
+        c->acov_host.clear();
+        c->acov_on = false;
+        c->acov_cap = 0;
+        return GROOT_OK;
+    }
+    if (c->acov_on) return GROOT_OK;
+    if (c->pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "assigned coverage with paired-end units is not supported");
+    if (int rc = groot_hip_ec_enable(c, 1)) return rc;
+    uint32_t cap = 1;
+    while (cap < (c->kn.acov_slots ? std::max<uint32_t>(c->kn.acov_slots, 2u) : (1u << 20))) cap <<= 1;
+    auto undo = [&](int rc) { c->acov_on = true; groot_hip_acov_enable(c, 0); return rc; };
+    hipError_t e = acov_alloc(cap, c->acov_k0, c->acov_k1, c->acov_cnt, c->tstream);
+    if (e == hipSuccess) e = c->acov_fill.alloc(1);
+    if (e == hipSuccess) e = c->acov_err.alloc(1);
+    if (e == hipSuccess) e = c->acov_tab_ser.alloc(c->sh_tab_cap);
+    if (e == hipSuccess) e = hipMemsetAsync(c->acov_fill.p, 0, sizeof(uint32_t), c->tstream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->acov_err.p, 0, sizeof(uint32_t), c->tstream);
+    if (e == hipSuccess) e = upload(c->acov_np_off, c->h_cov_np_off.data(), c->h_cov_np_off.size());
+    if (e == hipSuccess) e = upload(c->acov_len, c->h_cov_len.data(), c->h_cov_len.size());
+    if (e == hipSuccess) e = upload(c->acov_np, c->h_cov_np.data(), c->h_cov_np.size());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->tstream);
+    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "assigned coverage: %s", hipGetErrorString(e)));
+    c->acov_cap = cap;
+    c->acov_grows = c->acov_slow_records = c->acov_redone = 0;
+    c->acov_host.clear();
+    c->acov_on = true;
+    return GROOT_OK;
+}
+
+namespace {
+struct AcovTuple {
+    uint32_t ec, path, pos, last;
+    uint64_t n;
+    bool operator<(const AcovTuple &o) const { return std::tie(ec, path, pos, last) < std::tie(o.ec, o.path, o.pos, o.last); }
+    bool same_key(const AcovTuple &o) const { return ec == o.ec && path == o.path && pos == o.pos && last == o.last; }
+};
+}
+
+// the ctx's ECs in canonical order and its tuples, EC = index into that list, ascending, equal keys of the device table and the host
+// map summed
+static int acov_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &ecs, std::vector<AcovTuple> &out)
+{
+    std::vector<std::vector<uint32_t>> by_serial;
+    if (int rc = ec_gather(c, ecs, &by_serial)) return rc;
+    out.clear();
+    std::map<std::vector<uint32_t>, uint32_t> index;
+    for (const auto &kv : ecs) { const uint32_t i = (uint32_t)index.size(); index[kv.first] = i; }
+    uint32_t fill = 0;
+    HIP_TRY(c, hipMemcpy(&fill, c->acov_fill.p, sizeof fill, hipMemcpyDeviceToHost));
+    if (fill) {
+        std::vector<uint32_t> ser_idx(by_serial.size(), ~0u);
+        for (size_t i = 0; i < by_serial.size(); i++) {
+            auto it = index.find(by_serial[i]);
+            if (it != index.end()) ser_idx[i] = it->second;
+        }
+        DevBuf<unsigned long long> key, cnt;
+        DevBuf<uint32_t> n;
+        HIP_TRY(c, key.alloc(2 * (size_t)fill));
+        HIP_TRY(c, cnt.alloc(fill));
+        HIP_TRY(c, n.alloc(1));
+        HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->tstream));
+        hipLaunchKernelGGL(acov_export_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->acov_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
+                           acov_table(c), c->acov_cap, key.p, cnt.p, n.p, fill);
+        c->acov_launches++;
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
+        uint32_t got = 0;
+        HIP_TRY(c, hipMemcpy(&got, n.p, sizeof got, hipMemcpyDeviceToHost));
+        if (got > fill) return fail(c, GROOT_E_DEVICE, "assigned coverage: %u tuples in a table that counted %u", got, fill);
+        std::vector<uint64_t> hk(2 * (size_t)got), hc(got);
+        if (got) {
+            HIP_TRY(c, hipMemcpy(hk.data(), key.p, hk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(hc.data(), cnt.p, hc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        }
+        out.reserve(got);
+        for (uint32_t i = 0; i < got; i++) {
+            const uint64_t ser = (hk[2 * (size_t)i] >> 32) - 1;
+            if (ser >= ser_idx.size() || ser_idx[ser] == ~0u) return fail(c, GROOT_E_DEVICE, "assigned coverage: a tuple names class %llu, which the table of classes does not hold", (unsigned long long)ser);
+            out.push_back(AcovTuple{ser_idx[ser], (uint32_t)hk[2 * (size_t)i], (uint32_t)(hk[2 * (size_t)i + 1] >> 32), (uint32_t)hk[2 * (size_t)i + 1], hc[i]});
+        }
+    }
+    for (const auto &kv : c->acov_host) {
+        auto it = index.find(kv.first);
+        if (it == index.end()) return fail(c, GROOT_E_DEVICE, "assigned coverage: the host map holds a class the table of classes does not");
+        for (const auto &t : kv.second) out.push_back(AcovTuple{it->second, t.first[0], t.first[1], t.first[2], t.second});
+    }
+    std::sort(out.begin(), out.end());
+    size_t w = 0;
+    for (size_t i = 0; i < out.size(); i++) {
+        if (w && out[w - 1].same_key(out[i])) out[w - 1].n += out[i].n;
+        else out[w++] = out[i];
+    }
+    out.resize(w);
+    return GROOT_OK;
+}
+
+int groot_hip_acov_export(groot_ctx *c, uint64_t *ec_off, uint32_t *ec_ids, uint64_t *ec_count, uint32_t *tuples, uint64_t *n, uint64_t cap_ec, uint64_t cap_ids,
+                          uint64_t cap_tuples, uint64_t *n_ec, uint64_t *n_ids, uint64_t *n_tuples)
+{
+    if (!c || !n_ec || !n_ids || !n_tuples || (cap_ec && (!ec_off || !ec_count)) || (cap_ids && !ec_ids) || (cap_tuples && (!tuples || !n))) return GROOT_E_INVALID;
+    if (!c->acov_on) return fail(c, GROOT_E_STATE, "assigned coverage is not enabled (groot_hip_acov_enable)");
+    std::map<std::vector<uint32_t>, uint64_t> m;
+    std::vector<AcovTuple> tp;
+    if (int rc = acov_gather(c, m, tp)) return rc;
+    uint64_t ni = 0;
+    for (const auto &kv : m) ni += kv.first.size();
+    *n_ec = m.size();
+    *n_ids = ni;
+    *n_tuples = tp.size();
+    if (!cap_ec && !cap_ids && !cap_tuples) return GROOT_OK;
+    if (cap_ec < m.size() || cap_ids < ni || cap_tuples < tp.size())
+        return fail(c, GROOT_E_NOSPACE, "assigned coverage: room for %llu classes / %llu IDs / %llu tuples, %llu / %llu / %llu needed", (unsigned long long)cap_ec,
+                    (unsigned long long)cap_ids, (unsigned long long)cap_tuples, (unsigned long long)m.size(), (unsigned long long)ni, (unsigned long long)tp.size());
+    uint64_t e = 0, at = 0;
+    if (ec_off) ec_off[0] = 0;
+    for (const auto &kv : m) {
+        for (uint32_t x : kv.first) ec_ids[at++] = x;
+        ec_count[e] = kv.second;
+        ec_off[++e] = at;
+    }
+    for (size_t i = 0; i < tp.size(); i++) {
+        tuples[4 * i] = tp[i].ec; tuples[4 * i + 1] = tp[i].path; tuples[4 * i + 2] = tp[i].pos; tuples[4 * i + 3] = tp[i].last;
+        n[i] = tp[i].n;
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_acov_stats(groot_ctx *c, uint64_t *records, uint64_t *tuples, uint64_t *slots, uint64_t *grows, uint64_t *slow_records, uint64_t *launches)
+{
+    if (!c) return GROOT_E_INVALID;
+    uint64_t r = 0, nt = 0;
+    if (c->acov_on) {
+        std::map<std::vector<uint32_t>, uint64_t> m;
+        std::vector<AcovTuple> tp;
+        if (int rc = acov_gather(c, m, tp)) return rc;
+        for (const auto &t : tp) r += t.n;
+        nt = tp.size();
+    }
+    if (records) *records = r;
+    if (tuples) *tuples = nt;
+    if (slots) *slots = c->acov_on ? c->acov_cap : 0;
+    if (grows) *grows = c->acov_on ? c->acov_grows : 0;
+    if (slow_records) *slow_records = c->acov_on ? c->acov_slow_records : 0;
+    if (launches) *launches = c->acov_launches;
+    return GROOT_OK;
+}
+
+int groot_hip_acov_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->acov_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemset(c->acov_k0.p, 0, (size_t)c->acov_cap * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->acov_k1.p, 0xFF, (size_t)c->acov_cap * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->acov_cnt.p, 0, (size_t)c->acov_cap * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->acov_fill.p, 0, sizeof(uint32_t)));
+    c->acov_grows = c->acov_slow_records = c->acov_redone = 0;
+    c->acov_host.clear();
     return GROOT_OK;
 }
 
@@ -3875,6 +4210,7 @@ int groot_hip_pairs_enable(groot_ctx *c, int on)
 {
     if (!c) return GROOT_E_INVALID;
     if (!idle(c)) return fail(c, GROOT_E_STATE, "pairing can only be switched while nothing is in flight");
+    if (on && c->acov_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assigned coverage are not supported");
     c->pairs_on = on != 0;
     if (c->sh_on || c->ec_on) {     // (else there is nothing to zero: sh_common_alloc zeroes the counts when either comes on)
         HIP_TRY(c, hipSetDevice(c->device));

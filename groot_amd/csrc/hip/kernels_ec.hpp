@@ -25,6 +25,7 @@ struct EcTable {
     uint32_t *graph;               // [cap * kSharedSegs]
     uint64_t *mask;                // [cap * kSharedSegs * pw]
     unsigned long long *cnt;       // [cap]
+    uint32_t *serial;              // [cap] the slot's serial number: the table's fill when it was claimed (kernels_acov.hpp keys its tuples by it)
     uint32_t cap_mask;             // cap - 1 (cap a power of two)
 };
 
@@ -56,9 +57,10 @@ __device__ __forceinline__ bool ec_same(const EcTable &t, uint32_t s, const uint
     return true;
 }
 
-// adds c to key (g, m): an older slot with the key, or the first free one (claimed with `epoch`); fill counts claimed slots
-__device__ __forceinline__ void ec_add(const EcTable &t, const uint32_t *g, const uint64_t *m, uint32_t pw, unsigned long long c, uint32_t epoch,
-                                       bool compare, uint32_t *fill)
+// adds c to key (g, m): an older slot with the key, or the first free one (claimed with `epoch`); fill counts claimed slots and
+// numbers them (a rehash has no fill and carries the serial `ser`).  Returns the slot's serial.
+__device__ __forceinline__ uint32_t ec_add(const EcTable &t, const uint32_t *g, const uint64_t *m, uint32_t pw, unsigned long long c, uint32_t epoch,
+                                           bool compare, uint32_t *fill, uint32_t ser)
 {
     // the host keeps at least half the slots free: the probe ends
     for (uint32_t s = (uint32_t)ec_hash(g, m, pw) & t.cap_mask;; s = (s + 1) & t.cap_mask) {
@@ -76,12 +78,13 @@ __device__ __forceinline__ void ec_add(const EcTable &t, const uint32_t *g, cons
                     for (uint32_t w = 0; w < pw; w++) t.mask[((size_t)s * kSharedSegs + k) * pw + w] = 0;
                 }
                 t.cnt[s] = c;
-                if (fill) atomicAdd(fill, 1u);
-                return;
+                if (fill) ser = atomicAdd(fill, 1u);
+                t.serial[s] = ser;
+                return ser;
             }
         }
         if (cur == epoch || !compare) continue;   // claimed by this launch: another key
-        if (ec_same(t, s, g, m, pw)) { atomicAdd(t.cnt + s, c); return; }
+        if (ec_same(t, s, g, m, pw)) { atomicAdd(t.cnt + s, c); return t.serial[s]; }
     }
 }
 
@@ -89,8 +92,10 @@ __device__ __forceinline__ void ec_add(const EcTable &t, const uint32_t *g, cons
 // slow_out[0] = their number, then (first traversal, end traversal) per read.
 // kPaired: three words per slow-path unit, (first traversal, end of the even mate's records, end traversal); the middle word equals
 // the last for a read that is a unit by itself, and the host folds the intersection of the two ranges' sets otherwise.
+// tab_ser (assigned coverage on, else null): [tab_size] the serial of every occupied slot's EC.
 template <bool kPaired>
-__global__ __launch_bounds__(kBlock) void ec_merge_kernel(SharedArgs a, EcTable t, uint32_t tab_size, uint32_t epoch, uint32_t *fill, uint32_t *slow_out)
+__global__ __launch_bounds__(kBlock) void ec_merge_kernel(SharedArgs a, EcTable t, uint32_t tab_size, uint32_t epoch, uint32_t *fill, uint32_t *slow_out,
+                                                          uint32_t *tab_ser)
 {
     if (!shared_live(a)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) slow_out[0] = 0;
@@ -123,7 +128,8 @@ __global__ __launch_bounds__(kBlock) void ec_merge_kernel(SharedArgs a, EcTable 
     for (uint32_t slot = blockIdx.x * kBlock + threadIdx.x; slot < tab_size; slot += gridDim.x * kBlock) {
         const uint32_t r = a.tab_rep[slot];
         if (r == kSharedEmpty) continue;
-        ec_add(t, a.set_graph + (size_t)r * kSharedSegs, a.set_mask + (size_t)r * kSharedSegs * a.pw, a.pw, a.tab_cnt[slot], epoch, true, fill);
+        const uint32_t ser = ec_add(t, a.set_graph + (size_t)r * kSharedSegs, a.set_mask + (size_t)r * kSharedSegs * a.pw, a.pw, a.tab_cnt[slot], epoch, true, fill, 0);
+        if (tab_ser) tab_ser[slot] = ser;
     }
 }
 
@@ -132,13 +138,13 @@ __global__ __launch_bounds__(kBlock) void ec_rehash_kernel(EcTable from, uint32_
 {
     for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < from_cap; s += gridDim.x * kBlock) {
         if (!from.claim[s]) continue;
-        ec_add(to, from.graph + (size_t)s * kSharedSegs, from.mask + (size_t)s * kSharedSegs * pw, pw, from.cnt[s], epoch, false, nullptr);
+        ec_add(to, from.graph + (size_t)s * kSharedSegs, from.mask + (size_t)s * kSharedSegs * pw, pw, from.cnt[s], epoch, false, nullptr, from.serial[s]);
     }
 }
 
 // the occupied slots, compacted (in no particular order) into out_* (room for cap_out keys); *n_out counts them
 __global__ __launch_bounds__(kBlock) void ec_export_kernel(EcTable t, uint32_t cap, uint32_t pw, uint32_t *out_graph, uint64_t *out_mask,
-                                                           unsigned long long *out_cnt, uint32_t *n_out, uint32_t cap_out)
+                                                           unsigned long long *out_cnt, uint32_t *out_ser, uint32_t *n_out, uint32_t cap_out)
 {
     for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < cap; s += gridDim.x * kBlock) {
         if (!t.claim[s]) continue;
@@ -147,6 +153,7 @@ __global__ __launch_bounds__(kBlock) void ec_export_kernel(EcTable t, uint32_t c
         for (uint32_t k = 0; k < kSharedSegs; k++) out_graph[(size_t)i * kSharedSegs + k] = t.graph[(size_t)s * kSharedSegs + k];
         for (uint32_t w = 0; w < kSharedSegs * pw; w++) out_mask[(size_t)i * kSharedSegs * pw + w] = t.mask[(size_t)s * kSharedSegs * pw + w];
         out_cnt[i] = t.cnt[s];
+        out_ser[i] = t.serial[s];
     }
 }
 

@@ -9,12 +9,14 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <atomic>
 #include <map>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -208,8 +210,11 @@ int write_shared(const char *const *names, const uint32_t *name_len, const std::
 
 // `groot report` on a BAM; with shared_out, also the shared-reads file: S(read) = the references with a counted record of that QNAME
 // read_sets: instead of any output, the (read << 32 | reference) pairs of the counted records, sorted and unique, and the header's names
+// recs (with read_sets): every counted record as (read, reference, Pos, last = min(Pos + reference bases of its CIGAR, length - 1)), in
+// file order; lens_out: the header's lengths
 static int report_bam(const char *bam_path, double cov_cutoff, int low_cov, const char *out_path, uint64_t *n_reported, const char *shared_out,
-                      uint64_t *n_lines, std::vector<uint64_t> *read_sets = nullptr, std::vector<std::string> *names_out = nullptr)
+                      uint64_t *n_lines, std::vector<uint64_t> *read_sets = nullptr, std::vector<std::string> *names_out = nullptr,
+                      std::vector<std::array<uint32_t, 4>> *recs = nullptr, std::vector<uint32_t> *lens_out = nullptr)
 {
     if (int rc = check_cutoff(cov_cutoff, low_cov)) return rc;
     BgzfIn in;
@@ -270,6 +275,10 @@ static int report_bam(const char *bam_path, double cov_cutoff, int low_cov, cons
             qname.assign((const char *)rec.data() + 32, l_read_name ? l_read_name - 1 : 0);   // (NUL-terminated)
             const uint32_t rd = read_of.emplace(qname, (uint32_t)read_of.size()).first->second;
             read_ref.push_back((uint64_t)rd << 32 | (uint32_t)ref_id);
+            if (recs && lens[ref_id]) {
+                const uint64_t last = std::min<uint64_t>((uint64_t)pos + ref_len, (uint64_t)lens[ref_id] - 1);
+                recs->push_back({rd, (uint32_t)ref_id, (uint32_t)pos, (uint32_t)last});
+            }
         }
         if (pl.empty()) continue;
         uint64_t end = (uint64_t)pos + ref_len;
@@ -281,6 +290,7 @@ static int report_bam(const char *bam_path, double cov_cutoff, int low_cov, cons
         read_ref.erase(std::unique(read_ref.begin(), read_ref.end()), read_ref.end());
         *read_sets = std::move(read_ref);
         *names_out = std::move(names);
+        if (lens_out) *lens_out = std::move(lens);
         return GROOT_OK;
     }
     std::vector<const char *> name_ptr(n_ref);
@@ -660,4 +670,270 @@ extern "C" int groot_host_report_abundance_boot(const char *bam_path, double min
     if (n_boot == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
     const Boot boot{n_boot, seed, nullptr, threads};
     return report_abundance(bam_path, min_reads, out_path, n_lines, &boot);
+}
+
+// ---- calls: the EM-weighted pileup per path (groot_host.h "assigned coverage") ------------------------------------------------
+namespace {
+
+struct Tuple {
+    uint32_t ec, path, pos, last;
+    uint64_t n;
+};
+bool tuple_less(const Tuple &a, const Tuple &b) { return std::tie(a.ec, a.path, a.pos, a.last) < std::tie(b.ec, b.path, b.pos, b.last); }
+
+// equal keys summed, ascending
+void tuples_canonical(std::vector<Tuple> &t)
+{
+    std::sort(t.begin(), t.end(), tuple_less);
+    size_t w = 0;
+    for (size_t i = 0; i < t.size(); i++) {
+        if (!t[i].n) continue;
+        if (w && !tuple_less(t[w - 1], t[i])) t[w - 1].n += t[i].n;
+        else t[w++] = t[i];
+    }
+    t.resize(w);
+}
+
+// the table checked and ordered by (path, EC, Pos, last): EC indices inside the list, the path an ID of its EC and inside the index
+int tuples_by_path(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn,
+                   std::vector<Tuple> &out)
+{
+    out.clear();
+    out.reserve(n_tuples);
+    for (uint64_t i = 0; i < n_tuples; i++) {
+        const Tuple t{tuples[4 * i], tuples[4 * i + 1], tuples[4 * i + 2], tuples[4 * i + 3], tn[i]};
+        if (t.ec >= n_ec) return set_error(GROOT_E_INVALID, "tuple %llu names EC %u of %llu", (unsigned long long)i, t.ec, (unsigned long long)n_ec);
+        if (t.path >= n_paths || !std::binary_search(ids + off[t.ec], ids + off[t.ec + 1], t.path))
+            return set_error(GROOT_E_INVALID, "tuple %llu: path %u is not in EC %u", (unsigned long long)i, t.path, t.ec);
+        out.push_back(t);
+    }
+    std::sort(out.begin(), out.end(), [](const Tuple &a, const Tuple &b) { return std::tie(a.path, a.ec, a.pos, a.last) < std::tie(b.path, b.ec, b.pos, b.last); });
+    return GROOT_OK;
+}
+
+// w(e, p): alpha[p] over the sum of alpha over e in ID order, 0.0 where the EM skips e
+double weight_of(const uint64_t *off, const uint32_t *ids, const double *alpha, uint32_t e, uint32_t p)
+{
+    const double tolerance = std::nextafter(1.0, 2.0) - 1.0;
+    double denom = 0.0;
+    for (uint64_t i = off[e]; i < off[e + 1]; i++) denom += alpha[ids[i]];
+    if (denom < tolerance) return 0.0;
+    return alpha[p] / denom;
+}
+
+// D_p of the tuples [lo, hi) of path p (ordered by EC): per EC an integer difference array, then the weighted sum in EC order
+void depth_of(const std::vector<Tuple> &t, size_t lo, size_t hi, const uint64_t *off, const uint32_t *ids, const double *alpha, uint32_t p, uint32_t len,
+              std::vector<double> &D, std::vector<int64_t> &diff)
+{
+    D.assign(len, 0.0);
+    for (size_t i = lo; i < hi;) {
+        size_t j = i;
+        diff.assign((size_t)len + 1, 0);
+        for (; j < hi && t[j].ec == t[i].ec; j++) {
+            if (t[j].pos >= len || t[j].last < t[j].pos) continue;           // (a record past its path covers nothing)
+            diff[t[j].pos] += (int64_t)t[j].n;
+            diff[std::min<uint64_t>((uint64_t)t[j].last, (uint64_t)len - 1) + 1] -= (int64_t)t[j].n;
+        }
+        const double w = weight_of(off, ids, alpha, t[i].ec, p);
+        int64_t d = 0;
+        for (uint32_t x = 0; x < len; x++) {
+            d += diff[x];
+            const double term = (double)d * w;
+            D[x] = D[x] + term;
+        }
+        i = j;
+    }
+}
+
+// the calls file: a line per line of the abundance file (alpha >= min_reads, header order)
+int write_calls(uint32_t n_paths, const char *const *names, const uint32_t *name_len, const uint32_t *lens, uint64_t n_ec, const uint64_t *off, const uint32_t *ids,
+                const uint64_t *count, const double *alpha_in, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads, double call_depth,
+                double cov_cutoff, const char *out_path, uint64_t *n_lines, uint64_t *n_called)
+{
+    if ((n_ec && (!off || !count)) || (n_tuples && (!tuples || !tn))) return set_error(GROOT_E_INVALID, "null argument");
+    if (cov_cutoff > 1.0) return set_error(GROOT_E_INVALID, "supplied coverage cutoff exceeds 1.0 (100%%): %g", cov_cutoff);
+    for (uint64_t e = 0; e < n_ec; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
+        for (uint64_t i = off[e]; i < off[e + 1]; i++)
+            if (ids[i] >= n_paths || (i > off[e] && ids[i] <= ids[i - 1])) return set_error(GROOT_E_INVALID, "EC %llu: its IDs do not ascend inside the index", (unsigned long long)e);
+    }
+    std::vector<double> own;
+    const double *alpha = alpha_in;
+    if (!alpha) {
+        own.resize(n_paths);
+        if (int rc = groot_host_em(n_paths, n_ec, off, ids, count, GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER, own.data(), nullptr)) return rc;
+        alpha = own.data();
+    }
+    std::vector<Tuple> t;
+    if (int rc = tuples_by_path(n_paths, n_ec, off, ids, n_tuples, tuples, tn, t)) return rc;
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
+    uint64_t lines = 0, called = 0;
+    std::vector<double> D;
+    std::vector<int64_t> diff;
+    std::vector<uint8_t> cov;
+    size_t at = 0;
+    for (uint32_t p = 0; p < n_paths && n_ec; p++) {
+        while (at < t.size() && t[at].path < p) at++;
+        size_t hi = at;
+        while (hi < t.size() && t[hi].path == p) hi++;
+        if (!(alpha[p] >= min_reads)) { at = hi; continue; }
+        const uint32_t len = lens[p];
+        depth_of(t, at, hi, off, ids, alpha, p, len, D, diff);
+        at = hi;
+        cov.resize(len);
+        size_t covered = 0;
+        double sum = 0.0;
+        for (uint32_t x = 0; x < len; x++) {
+            cov[x] = D[x] >= call_depth ? 1 : 0;
+            covered += cov[x];
+            sum += D[x];
+        }
+        const double breadth = len ? (double)covered / (double)len : 0.0, depth = len ? sum / (double)len : 0.0;
+        bool internal_d = false;
+        const std::string cigar = cigar_clean(cov, internal_d);
+        const int is_called = breadth >= cov_cutoff ? 1 : 0;
+        const char *nm = names[p];
+        size_t nl = name_len ? name_len[p] : strlen(nm);
+        if (nl && nm[0] == '*') { nm++; nl--; }
+        fprintf(out, "%.*s\t%.2f\t%u\t%.2f\t%.4f\t%s\t%d\n", (int)nl, nm, alpha[p], len, depth, breadth, cigar.c_str(), is_called);
+        lines++;
+        called += is_called;
+    }
+    if (out_path) fclose(out); else fflush(out);
+    if (n_lines) *n_lines = lines;
+    if (n_called) *n_called = called;
+    return GROOT_OK;
+}
+
+} // namespace
+
+extern "C" int groot_host_acov_merge(uint32_t n_paths, uint32_t n_ctx, const uint64_t *const *ec_off, const uint32_t *const *ec_ids, const uint64_t *const *ec_count,
+                                     const uint64_t *n_ec, const uint32_t *const *tuples, const uint64_t *const *tn, const uint64_t *n_tuples, uint64_t *out_off,
+                                     uint32_t *out_ids, uint64_t *out_count, uint32_t *out_tuples, uint64_t *out_tn, uint64_t *n_ec_out, uint64_t *n_tuples_out)
+{
+    if ((n_ctx && (!ec_off || !ec_ids || !ec_count || !n_ec || !tuples || !tn || !n_tuples)) || !out_off || !n_ec_out || !n_tuples_out)
+        return set_error(GROOT_E_INVALID, "null argument");
+    EcMap m;
+    for (uint32_t c = 0; c < n_ctx; c++)
+        if (int rc = canonical_ecs(n_paths, n_ec[c], ec_off[c], ec_ids[c], ec_count[c], m)) return rc;
+    std::map<std::vector<uint32_t>, uint32_t> index;
+    for (const auto &kv : m) { const uint32_t i = (uint32_t)index.size(); index[kv.first] = i; }
+    std::vector<Tuple> all;
+    std::vector<uint32_t> v, local;
+    for (uint32_t c = 0; c < n_ctx; c++) {
+        local.assign(n_ec[c], ~0u);
+        for (uint64_t e = 0; e < n_ec[c]; e++) {
+            v.assign(ec_ids[c] + ec_off[c][e], ec_ids[c] + ec_off[c][e + 1]);
+            std::sort(v.begin(), v.end());
+            v.erase(std::unique(v.begin(), v.end()), v.end());
+            auto it = index.find(v);
+            if (it != index.end()) local[e] = it->second;
+        }
+        for (uint64_t i = 0; i < n_tuples[c]; i++) {
+            const uint32_t e = tuples[c][4 * i];
+            if (e >= n_ec[c] || local[e] == ~0u) return set_error(GROOT_E_INVALID, "export %u, tuple %llu: EC %u is not in its list", c, (unsigned long long)i, e);
+            all.push_back(Tuple{local[e], tuples[c][4 * i + 1], tuples[c][4 * i + 2], tuples[c][4 * i + 3], tn[c][i]});
+        }
+    }
+    tuples_canonical(all);
+    uint64_t e = 0, at = 0;
+    out_off[0] = 0;
+    for (const auto &kv : m) {
+        for (uint32_t p : kv.first) out_ids[at++] = p;
+        out_count[e] = kv.second;
+        out_off[++e] = at;
+    }
+    for (size_t i = 0; i < all.size(); i++) {
+        out_tuples[4 * i] = all[i].ec; out_tuples[4 * i + 1] = all[i].path; out_tuples[4 * i + 2] = all[i].pos; out_tuples[4 * i + 3] = all[i].last;
+        out_tn[i] = all[i].n;
+    }
+    *n_ec_out = e;
+    *n_tuples_out = all.size();
+    return GROOT_OK;
+}
+
+extern "C" int groot_host_acov_depth(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const double *alpha, uint64_t n_tuples,
+                                     const uint32_t *tuples, const uint64_t *tn, uint32_t path, uint32_t path_len, double *depth)
+{
+    if ((n_ec && !off) || !alpha || (n_tuples && (!tuples || !tn)) || (path_len && !depth) || path >= n_paths) return set_error(GROOT_E_INVALID, "bad argument");
+    std::vector<Tuple> t;
+    if (int rc = tuples_by_path(n_paths, n_ec, off, ids, n_tuples, tuples, tn, t)) return rc;
+    size_t lo = 0;
+    while (lo < t.size() && t[lo].path < path) lo++;
+    size_t hi = lo;
+    while (hi < t.size() && t[hi].path == path) hi++;
+    std::vector<double> D;
+    std::vector<int64_t> diff;
+    depth_of(t, lo, hi, off, ids, alpha, path, path_len, D, diff);
+    std::copy(D.begin(), D.end(), depth);
+    return GROOT_OK;
+}
+
+extern "C" int groot_host_calls_from_table(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                           const double *alpha, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads,
+                                           double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines, uint64_t *n_called)
+{
+    if (!ix) return set_error(GROOT_E_INVALID, "null argument");
+    const uint32_t n = ix->n_paths;
+    std::vector<const char *> name_ptr(n);
+    std::vector<uint32_t> name_len(n);
+    for (uint32_t p = 0; p < n; p++) {
+        name_ptr[p] = ix->path_names + ix->path_name_off[p];
+        name_len[p] = ix->path_name_off[p + 1] - ix->path_name_off[p];
+    }
+    return write_calls(n, name_ptr.data(), name_len.data(), ix->path_len, n_ec, off, ids, count, alpha, n_tuples, tuples, tn, min_reads, call_depth, cov_cutoff,
+                       out_path, n_lines, n_called);
+}
+
+extern "C" int groot_host_report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
+                                       uint64_t *n_called, uint64_t *n_tuples)
+{
+    std::vector<uint64_t> read_ref;
+    std::vector<std::string> names;
+    std::vector<std::array<uint32_t, 4>> recs;
+    std::vector<uint32_t> lens;
+    if (int rc = report_bam(bam_path, 0.97, 0, nullptr, nullptr, nullptr, nullptr, &read_ref, &names, &recs, &lens)) return rc;
+    // S(read) as report_abundance builds it, and the read's EC
+    EcMap m;
+    std::vector<std::vector<uint32_t>> set_of;
+    std::vector<uint32_t> v;
+    for (size_t i = 0; i < read_ref.size();) {
+        size_t j = i;
+        v.clear();
+        while (j < read_ref.size() && read_ref[j] >> 32 == read_ref[i] >> 32) v.push_back((uint32_t)read_ref[j++]);
+        const uint32_t rd = (uint32_t)(read_ref[i] >> 32);
+        if (set_of.size() <= rd) set_of.resize((size_t)rd + 1);
+        set_of[rd] = v;
+        m[v]++;
+        i = j;
+    }
+    std::map<std::vector<uint32_t>, uint32_t> index;
+    std::vector<uint64_t> off{0}, count;
+    std::vector<uint32_t> ids;
+    for (const auto &kv : m) {
+        const uint32_t i = (uint32_t)index.size();
+        index[kv.first] = i;
+        ids.insert(ids.end(), kv.first.begin(), kv.first.end());
+        off.push_back(ids.size());
+        count.push_back(kv.second);
+    }
+    std::vector<uint32_t> ec_of(set_of.size(), 0);
+    for (size_t r = 0; r < set_of.size(); r++)
+        if (!set_of[r].empty()) ec_of[r] = index[set_of[r]];
+    std::vector<Tuple> t;
+    t.reserve(recs.size());
+    for (const auto &r : recs) t.push_back(Tuple{ec_of[r[0]], r[1], r[2], r[3], 1});
+    tuples_canonical(t);
+    std::vector<uint32_t> tup(4 * t.size());
+    std::vector<uint64_t> tn(t.size());
+    for (size_t i = 0; i < t.size(); i++) {
+        tup[4 * i] = t[i].ec; tup[4 * i + 1] = t[i].path; tup[4 * i + 2] = t[i].pos; tup[4 * i + 3] = t[i].last;
+        tn[i] = t[i].n;
+    }
+    if (n_tuples) *n_tuples = t.size();
+    std::vector<const char *> name_ptr(names.size());
+    for (size_t r = 0; r < names.size(); r++) name_ptr[r] = names[r].c_str();
+    return write_calls((uint32_t)names.size(), name_ptr.data(), nullptr, lens.data(), m.size(), off.data(), ids.data(), count.data(), nullptr, t.size(), tup.data(),
+                       tn.data(), min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called);
 }

@@ -433,6 +433,40 @@ class Aligner:
     def ec_reset(self):
         self._check(lib().groot_hip_ec_reset(self._h))
 
+    # ---- assigned coverage (groot_hip_acov_*) ------------------------------------------------------
+    def acov_enable(self, on=True):
+        """group every record by (EC of its read, path, Pos, last) from now on (include/groot_hip.h, "assigned coverage"); switches
+        equivalence classes on.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_acov_enable(self._h, C.c_int(1 if on else 0)))
+
+    def acov(self):
+        """(off, ids, count, tuples uint32[n, 4], n uint64[n]): the ctx's ECs as ecs() gives them and the assigned-coverage table,
+        tuple = (EC index, path, Pos, last), ascending: the input of host.acov_merge / host.calls_from_table"""
+        ne, ni, nt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        z = C.c_uint64(0)
+        self._check(lib().groot_hip_acov_export(self._h, None, None, None, None, None, z, z, z, C.byref(ne), C.byref(ni), C.byref(nt)))
+        off = np.zeros(ne.value + 1, dtype=np.uint64)
+        ids = np.zeros(max(ni.value, 1), dtype=np.uint32)
+        cnt = np.zeros(max(ne.value, 1), dtype=np.uint64)
+        tup = np.zeros((max(nt.value, 1), 4), dtype=np.uint32)
+        tn = np.zeros(max(nt.value, 1), dtype=np.uint64)
+        if ne.value or nt.value:
+            me, mi, mt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+            self._check(lib().groot_hip_acov_export(self._h, _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32), _ffi.as_ptr(cnt, C.c_uint64),
+                                                    _ffi.as_ptr(tup, C.c_uint32), _ffi.as_ptr(tn, C.c_uint64), C.c_uint64(ne.value), C.c_uint64(ni.value),
+                                                    C.c_uint64(nt.value), C.byref(me), C.byref(mi), C.byref(mt)))
+            assert (me.value, mi.value, mt.value) == (ne.value, ni.value, nt.value)
+        return off, ids[:ni.value], cnt[:ne.value], tup[:nt.value], tn[:nt.value]
+
+    def acov_stats(self):
+        """{"records", "tuples", "slots", "grows", "slow_records", "launches"} (groot_hip_acov_stats); zeros while off, but for launches"""
+        v = [C.c_uint64(0) for _ in range(6)]
+        self._check(lib().groot_hip_acov_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("records", "tuples", "slots", "grows", "slow_records", "launches"), (x.value for x in v)))
+
+    def acov_reset(self):
+        self._check(lib().groot_hip_acov_reset(self._h))
+
     # ---- paired-end reads (groot_hip_pairs_*) ------------------------------------------------------
     def pairs_enable(self, on=True):
         """reads 2i and 2i+1 of every batch are the mates of one fragment: shared reads and equivalence classes count units

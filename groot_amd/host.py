@@ -538,6 +538,74 @@ def report_abundance(bam_path, min_reads=1.0, out_path=None):
     return rows
 
 
+def _tuple_arrays(tuples, tn):
+    tuples = np.ascontiguousarray(tuples, dtype=np.uint32).reshape(-1, 4)
+    tn = np.ascontiguousarray(tn, dtype=np.uint64)
+    if len(tuples) != len(tn):
+        raise ValueError("one count per tuple")
+    return tuples, tn
+
+
+def acov_merge(n_paths, exports):
+    """groot_host_acov_merge: exports = [(off, ids, count, tuples, tn), ...] as device.Aligner.acov() gives them -> one table
+    (off, ids, count, tuples[n, 4], tn) with canonical ECs and ascending tuples"""
+    ex = [_ec_arrays(o, i, c) + _tuple_arrays(t, n) for o, i, c, t, n in exports]
+    k = len(ex)
+
+    def ptrs(j, ct):
+        return (C.c_void_p * max(k, 1))(*[C.cast(_ffi.as_ptr(e[j], ct), C.c_void_p).value or 0 for e in ex])
+
+    n_ec = np.array([len(e[2]) for e in ex], dtype=np.uint64)
+    n_tp = np.array([len(e[4]) for e in ex], dtype=np.uint64)
+    o = np.zeros(int(n_ec.sum()) + 1, dtype=np.uint64)
+    i = np.zeros(max(sum(len(e[1]) for e in ex), 1), dtype=np.uint32)
+    c = np.zeros(max(int(n_ec.sum()), 1), dtype=np.uint64)
+    t = np.zeros((max(int(n_tp.sum()), 1), 4), dtype=np.uint32)
+    tn = np.zeros(max(int(n_tp.sum()), 1), dtype=np.uint64)
+    ne, nt = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().groot_host_acov_merge(C.c_uint32(n_paths), C.c_uint32(k), ptrs(0, C.c_uint64), ptrs(1, C.c_uint32), ptrs(2, C.c_uint64),
+                                       _ffi.as_ptr(n_ec, C.c_uint64), ptrs(3, C.c_uint32), ptrs(4, C.c_uint64), _ffi.as_ptr(n_tp, C.c_uint64),
+                                       _ffi.as_ptr(o, C.c_uint64), _ffi.as_ptr(i, C.c_uint32), _ffi.as_ptr(c, C.c_uint64), _ffi.as_ptr(t, C.c_uint32),
+                                       _ffi.as_ptr(tn, C.c_uint64), C.byref(ne), C.byref(nt)))
+    return o[:ne.value + 1].copy(), i[:int(o[ne.value])].copy(), c[:ne.value].copy(), t[:nt.value].copy(), tn[:nt.value].copy()
+
+
+def acov_depth(n_paths, off, ids, alpha, tuples, tn, path, path_len):
+    """groot_host_acov_depth: D_p[path_len] (float64) of one path from a table with canonical ECs and alpha[n_paths]"""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+    tuples, tn = _tuple_arrays(tuples, tn)
+    d = np.zeros(max(path_len, 1), dtype=np.float64)
+    _check(lib().groot_host_acov_depth(C.c_uint32(n_paths), C.c_uint64(len(off) - 1), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                       _ffi.as_ptr(alpha, C.c_double), C.c_uint64(len(tn)), _ffi.as_ptr(tuples, C.c_uint32), _ffi.as_ptr(tn, C.c_uint64),
+                                       C.c_uint32(path), C.c_uint32(path_len), _ffi.as_ptr(d, C.c_double)))
+    return d[:path_len]
+
+
+def calls_from_table(index, off, ids, count, tuples, tn, out_path, alpha=None, min_reads=1.0, call_depth=1.0, cov_cutoff=0.97):
+    """groot_host_calls_from_table: writes the calls file of a table with canonical ECs (acov_merge); alpha None = the EM over the
+    ECs.  Returns (lines, called)."""
+    off, ids, count = _ec_arrays(off, ids, count)
+    tuples, tn = _tuple_arrays(tuples, tn)
+    if alpha is not None:
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+    nl, nc = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().groot_host_calls_from_table(C.byref(index.view), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                             _ffi.as_ptr(count, C.c_uint64), None if alpha is None else _ffi.as_ptr(alpha, C.c_double),
+                                             C.c_uint64(len(tn)), _ffi.as_ptr(tuples, C.c_uint32), _ffi.as_ptr(tn, C.c_uint64), C.c_double(min_reads),
+                                             C.c_double(call_depth), C.c_double(cov_cutoff), out_path.encode(), C.byref(nl), C.byref(nc)))
+    return nl.value, nc.value
+
+
+def report_calls(bam_path, out_path, min_reads=1.0, call_depth=1.0, cov_cutoff=0.97):
+    """groot_host_report_calls: the calls file from a BAM.  Returns (lines, called, tuples)."""
+    nl, nc, nt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().groot_host_report_calls(bam_path.encode(), C.c_double(min_reads), C.c_double(call_depth), C.c_double(cov_cutoff), out_path.encode(),
+                                         C.byref(nl), C.byref(nc), C.byref(nt)))
+    return nl.value, nc.value, nt.value
+
+
 def _ec_arrays(off, ids, count):
     off = np.ascontiguousarray(off, dtype=np.uint64)
     ids = np.ascontiguousarray(ids, dtype=np.uint32)

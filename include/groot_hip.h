@@ -346,6 +346,45 @@ int groot_hip_ec_reset(groot_ctx *ctx);
  * in more than one under GROOT_TEST_SHARED_SLOW), times the table grew.  Waits for everything in flight.  GROOT_E_STATE when off. */
 int groot_hip_ec_stats(groot_ctx *ctx, uint64_t *reads, uint64_t *distinct, uint64_t *slow_reads, uint64_t *grows);
 
+/* ---- assigned coverage ---------------------------------------------------------------------------------------------
+ * The pileup of the reads the abundance EM assigns to each path: every record of read r on path p gets the weight of r's posterior
+ * on p.  The definition (README.md, DESIGN.md 13, groot_host.h and the tests quote it):
+ *
+ *   S(r), equivalence classes (ECs), their canonical order and alpha = groot_host_em over the run's ECs: exactly as for --abundance.
+ *   For an EC e (ascending path IDs) and p in e:   w(e,p) = alpha[p] / denom(e),  denom(e) = sum of alpha[q], q in e, in ID order;
+ *                                                  w(e,p) = 0.0 where the EM skips e (denom < 2^-52).  Double, no FMA contraction.
+ *   A record of read r on path p with an M op of M bases at Pos covers [Pos, last], last = min(Pos + M, path_len(p) - 1), both ends
+ *   included: the interval `report` piles up.  EVERY record counts (both strands, primary and secondary), as in the report.
+ *   The assigned-coverage table of a run is the multiset of records grouped by (e = EC of S(r), p, Pos, last):  n(e,p,Pos,last), integers.
+ *   Per path p, per EC e holding p:  d_e[x] = number of records of (e,p,.,.) covering base x   (integers).
+ *   Assigned depth:  D_p[x] = sum over the ECs holding p, in canonical EC order, of (double)d_e[x] * w(e,p).
+ *   A base is covered when D_p[x] >= callDepth (default 1.0).  breadth = covered / path_len;  depth = (sum of D_p[x] in x order) / path_len.
+ *
+ * Only the integer table is computed on the device (kernels_acov.hpp); everything in floating point happens once, on the host, in a
+ * fixed order (groot_host_calls_from_table), so the result depends on neither the batch size, the pipeline depth, the first-pass
+ * variant nor the number of ctxs or GPUs.  The table is a run-wide open-addressing table in HBM keyed by (serial of the EC's slot in
+ * the EC table, path, Pos, last), 16 bytes a key and a u64 count, that grows as it fills (a batch whose keys found no room adds
+ * nothing and is counted again at collect, after the growth: no count is lost or doubled).  Reads in more than 4 graphs are grouped
+ * on the host at collect, as their ECs are.  Counted once exactly as the other counters are.  Not with pairing (GROOT_E_UNSUPPORTED,
+ * from whichever of the two enables comes second).  Off by default: then nothing is launched and no device memory is taken. */
+/* Switch on (an empty table of 2^20 slots, 24 MB; equivalence classes are switched on if they are off, and stay on) or off (freed;
+ * groot_hip_ec_enable(ctx, 0) switches it off too).  Only while nothing is in flight. */
+int groot_hip_acov_enable(groot_ctx *ctx, int on);
+/* The ctx's ECs since enable / reset exactly as groot_hip_ec_export gives them (canonical order, CSR: ec_off[cap_ec + 1],
+ * ec_ids[cap_ids], ec_count[cap_ec]) and the table: tuple i = tuples[4 i .. 4 i + 4) = (EC index into that list, path, Pos, last),
+ * n[i] its records; the tuples ascend.  *n_ec / *n_ids / *n_tuples = the sizes; call with all three caps 0 to get them
+ * (GROOT_E_NOSPACE when an array is too small).  Waits for everything in flight.  GROOT_E_STATE when off.  (Tuples count from
+ * groot_hip_acov_enable / _reset, ECs from groot_hip_ec_enable / _reset: enable both before the first batch for a consistent pair.) */
+int groot_hip_acov_export(groot_ctx *ctx, uint64_t *ec_off, uint32_t *ec_ids, uint64_t *ec_count, uint32_t *tuples, uint64_t *n,
+                          uint64_t cap_ec, uint64_t cap_ids, uint64_t cap_tuples, uint64_t *n_ec, uint64_t *n_ids, uint64_t *n_tuples);
+/* Empties the table (after waiting for everything in flight); groot_hip_ec_reset does this too.  No-op when off. */
+int groot_hip_acov_reset(groot_ctx *ctx);
+/* Since enable / reset: records in the table (the sum of n), distinct tuples, slots of the device table, times it grew, records
+ * grouped on the host (slow-path reads); all zero while off.  launches: kernels launched for assigned coverage since the ctx was
+ * opened -- it does not move while the feature is off.  Waits for everything in flight. */
+int groot_hip_acov_stats(groot_ctx *ctx, uint64_t *records, uint64_t *tuples, uint64_t *slots, uint64_t *grows, uint64_t *slow_records,
+                         uint64_t *launches);
+
 /* ---- paired-end reads -------------------------------------------------------------------------------------------------
  * With pairing on, reads 2i and 2i+1 of a batch are the mates of fragment i.  The index is batch-relative: read_id - first_read_id;
  * first_read_id may be odd.  Let A = S(r_2i) and B = S(r_2i+1), S(r) exactly as above.

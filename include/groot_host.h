@@ -355,6 +355,44 @@ int groot_host_abundance_boot_from_ecs(const groot_index_view *idx, uint64_t n_e
 int groot_host_report_abundance_boot(const char *bam_path, double min_reads, uint32_t n_boot, uint64_t seed, uint32_t threads, const char *out_path,
                                      uint64_t *n_lines);
 
+/* ---- calls: assigned coverage, the EM-weighted pileup per path ------------------------------------------------------------
+ * The pileup of the reads the abundance EM assigns to each path: every record of read r on path p gets the weight of r's posterior on
+ * p, and a line says whether the assigned evidence covers the path.  The definition (groot_hip.h, README.md, DESIGN.md 13, the tests):
+ *
+ *   S(r), equivalence classes (ECs), their canonical order and alpha = groot_host_em over the run's ECs: exactly as for --abundance.
+ *   For an EC e (ascending path IDs) and p in e:   w(e,p) = alpha[p] / denom(e),  denom(e) = sum of alpha[q], q in e, in ID order;
+ *                                                  w(e,p) = 0.0 where the EM skips e (denom < 2^-52).  Double, no FMA contraction.
+ *   A record of read r on path p with an M op of M bases at Pos covers [Pos, last], last = min(Pos + M, path_len(p) - 1), both ends
+ *   included: the interval `report` piles up.  EVERY record counts (both strands, primary and secondary), as in the report.
+ *   The assigned-coverage table of a run is the multiset of records grouped by (e = EC of S(r), p, Pos, last):  n(e,p,Pos,last), integers.
+ *   Per path p, per EC e holding p:  d_e[x] = number of records of (e,p,.,.) covering base x   (integers).
+ *   Assigned depth:  D_p[x] = sum over the ECs holding p, in canonical EC order, of (double)d_e[x] * w(e,p).
+ *   A base is covered when D_p[x] >= callDepth (default 1.0).  breadth = covered / path_len;  depth = (sum of D_p[x] in x order) / path_len.
+ *
+ * A table is (ECs as CSR in canonical order, tuples[4 n] = (EC index, path, Pos, last) ascending, tn[n] = records), as
+ * groot_hip_acov_export hands it out.  The library is built without -march, so no product and sum are contracted. */
+/* The exports of n_ctx contexts (arrays of n_ctx pointers / sizes; ECs in any order, tuples naming ECs by their index in the same
+ * export) -> one table: ECs canonical as groot_host_ecs_canonical gives them, tuples renumbered, equal keys summed, ascending.  The
+ * outputs need room for the sums of the inputs' sizes (out_off one more); *n_ec_out / *n_tuples_out = what was written. */
+int groot_host_acov_merge(uint32_t n_paths, uint32_t n_ctx, const uint64_t *const *ec_off, const uint32_t *const *ec_ids, const uint64_t *const *ec_count,
+                          const uint64_t *n_ec, const uint32_t *const *tuples, const uint64_t *const *tn, const uint64_t *n_tuples, uint64_t *out_off,
+                          uint32_t *out_ids, uint64_t *out_count, uint32_t *out_tuples, uint64_t *out_tn, uint64_t *n_ec_out, uint64_t *n_tuples_out);
+/* D_p of one path from a table (canonical ECs) and alpha[n_paths]: depth[path_len].  GROOT_E_INVALID for a tuple whose EC is outside
+ * the list or whose path is not in its EC. */
+int groot_host_acov_depth(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const double *alpha, uint64_t n_tuples,
+                          const uint32_t *tuples, const uint64_t *tn, uint32_t path, uint32_t path_len, double *depth);
+/* The calls file: one line per line of the abundance file (alpha >= min_reads, BAM header order; empty without ECs),
+ * "name \t em_reads (%.2f) \t length \t depth (%.2f) \t breadth (%.4f) \t cigar \t called": cigar = the covered (M) / uncovered (D) runs as
+ * the report writes them, called = 1 when breadth >= cov_cutoff.  ECs canonical (groot_host_acov_merge); alpha[n_paths], or NULL =
+ * groot_host_em over the ECs with GROOT_EM_MIN_ITER / GROOT_EM_MAX_ITER.  out_path NULL = stdout; *n_lines / *n_called may be NULL. */
+int groot_host_calls_from_table(const groot_index_view *idx, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                const double *alpha, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads, double call_depth,
+                                double cov_cutoff, const char *out_path, uint64_t *n_lines, uint64_t *n_called);
+/* The same file from a BAM, a read being one QNAME (groot_host_report_abundance's grouping), through the same writer: byte for byte
+ * what the device path writes whenever read names are unique.  *n_tuples (may be NULL) = distinct tuples of the table. */
+int groot_host_report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
+                            uint64_t *n_called, uint64_t *n_tuples);
+
 #ifdef __cplusplus
 }
 #endif
