@@ -1,0 +1,1016 @@
+// counters.hip -- the counters that run behind every batch's order stage, and their C ABI (include/groot_hip.h): report coverage
+// (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
+// paired-end units, and the bootstrap replicates of the abundance EM (kernels_boot.hpp).  One of the five translation units of
+// libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cstring>
+#include <iterator>
+#include <map>
+#include <tuple>
+#include <vector>
+
+#include "counters.hpp"
+#include "ctx.hpp"
+#include "kernels_acov.hpp"
+#include "kernels_boot.hpp"
+#include "kernels_cov.hpp"
+#include "kernels_ec.hpp"
+#include "kernels_shared.hpp"
+
+using namespace groot;
+
+// workgroups of a grid-stride launch over n items
+static uint32_t grid_for(uint32_t n)
+{
+    return std::max<uint32_t>(1u, std::min<uint32_t>((n + kBlock - 1) / kBlock, 2048u));
+}
+
+// ---- the position tables' one device copy (Counters::d_*) ----
+static bool pos_wanted(const Counters &k) { return k.cov_on || k.sh_on || k.ec_on || k.acov_on; }
+
+static void pos_release(Counters &k)
+{
+    for (auto *b : {&k.d_np_off, &k.d_gpo, &k.d_len}) b->release();
+    k.d_np.release();
+}
+
+// for a counter that comes on: there already when another one is on
+static hipError_t pos_acquire(Counters &k)
+{
+    if (pos_wanted(k)) return hipSuccess;
+    hipError_t e = upload(k.d_np_off, k.h_np_off.data(), k.h_np_off.size());
+    if (e == hipSuccess) e = upload(k.d_gpo, k.h_gpo.data(), k.h_gpo.size());
+    if (e == hipSuccess) e = upload(k.d_len, k.h_len.data(), k.h_len.size());
+    if (e == hipSuccess) e = upload(k.d_np, k.h_np.data(), k.h_np.size());
+    if (e != hipSuccess) pos_release(k);
+    return e;
+}
+
+// ---- equivalence classes (kernels_ec.hpp) ----
+hipError_t EcBufs::alloc(uint32_t slots, uint32_t pw, hipStream_t st)
+{
+    cap = slots;
+    hipError_t e = claim.alloc(cap);
+    if (e == hipSuccess) e = graph.alloc((size_t)cap * kSharedSegs);
+    if (e == hipSuccess) e = mask.alloc((size_t)cap * kSharedSegs * pw);
+    if (e == hipSuccess) e = cnt.alloc(cap);
+    if (e == hipSuccess) e = serial.alloc(cap);
+    if (e == hipSuccess) e = hipMemsetAsync(claim.p, 0, (size_t)cap * sizeof(uint32_t), st);
+    return e;
+}
+EcTable EcBufs::table() const { return EcTable{claim.p, graph.p, mask.p, cnt.p, serial.p, cap - 1}; }
+void EcBufs::swap(EcBufs &o)
+{
+    std::swap(cap, o.cap);
+    claim.swap(o.claim); graph.swap(o.graph); mask.swap(o.mask); cnt.swap(o.cnt); serial.swap(o.serial);
+}
+void EcBufs::release()
+{
+    for (auto *b : {&claim, &graph, &serial}) b->release();
+    mask.release(); cnt.release();
+    cap = 0;
+}
+
+// Before a batch's merge: each batch adds at most n_reads keys, so the table must keep >= 2 x (the fill read back at the newest
+// collect + n_reads of every batch launched and not collected, this one included) slots -- else it doubles, rehashed in tail-stream
+// order.  (Growth is rare -- a handful of times per run -- so the old buffers are freed behind a wait for the tail stream.)
+static int ec_reserve(groot_ctx *c, Slot *s)
+{
+    Counters &k = c->ct;
+    uint64_t pending = s->n_reads;
+    for (Slot *x : c->inflight)
+        if (x != s && x->state == Slot::IN_FLIGHT) pending += x->n_reads;
+    const uint64_t need = 2 * (k.ec_fill_known + pending);
+    if (k.ec.cap >= need) return GROOT_OK;
+    uint64_t cap = k.ec.cap;
+    while (cap < need) cap *= 2;
+    if (cap > (1ull << 31)) return fail(c, GROOT_E_NOSPACE, "equivalence classes: the table would need %llu slots", (unsigned long long)cap);
+    const uint32_t pw = std::max<uint32_t>(c->pw_view, 1u);
+    EcBufs grown;
+    hipError_t e = grown.alloc((uint32_t)cap, pw, c->tstream);
+    if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "equivalence classes: growing the table to %llu slots: %s", (unsigned long long)cap, hipGetErrorString(e));
+    hipLaunchKernelGGL(ec_rehash_kernel, dim3(grid_for(k.ec.cap)), dim3(kBlock), 0, c->tstream, k.ec.table(), k.ec.cap, grown.table(), pw, ++k.ec_epoch);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
+    k.ec.swap(grown);
+    k.ec_grows++;
+    return GROOT_OK;
+}
+
+// S(r) of the records trav[0..n) (one read): global path IDs, ascending, each once
+static void ec_set_of(const groot_ctx *c, const groot_trav *trav, const uint64_t *mask, size_t n, std::vector<uint32_t> &ids)
+{
+    const uint32_t pw = c->pw_view, n_paths = (uint32_t)c->ct.h_len.size();
+    ids.clear();
+    for (size_t t = 0; t < n; t++)
+        for (uint32_t w = 0; w < pw; w++)
+            for (uint64_t m = mask[t * pw + w]; m; m &= m - 1) {
+                const uint64_t id = (uint64_t)c->ct.h_gpo[trav[t].graph_id] + w * 64 + (uint32_t)__builtin_ctzll(m);
+                if (id < n_paths) ids.push_back((uint32_t)id);
+            }
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+}
+
+// ---- assigned coverage (kernels_acov.hpp) ----
+hipError_t AcovBufs::alloc(uint32_t slots, hipStream_t st)
+{
+    cap = slots;
+    hipError_t e = k0.alloc(cap);
+    if (e == hipSuccess) e = k1.alloc(cap);
+    if (e == hipSuccess) e = cnt.alloc(cap);
+    if (e == hipSuccess) e = hipMemsetAsync(k0.p, 0, (size_t)cap * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(k1.p, 0xFF, (size_t)cap * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, (size_t)cap * sizeof(unsigned long long), st);
+    return e;
+}
+AcovTable AcovBufs::table() const { return AcovTable{k0.p, k1.p, cnt.p, cap - 1}; }
+void AcovBufs::swap(AcovBufs &o)
+{
+    std::swap(cap, o.cap);
+    k0.swap(o.k0); k1.swap(o.k1); cnt.swap(o.cnt);
+}
+void AcovBufs::release()
+{
+    for (auto *b : {&k0, &k1, &cnt}) b->release();
+    cap = 0;
+}
+
+// the claim and the add phase of slot s's batch on the tail stream; both read nothing but what the slot owns and the ctx's tables
+static int acov_count(groot_ctx *c, Slot *s)
+{
+    Counters &k = c->ct;
+    AcovArgs a{};
+    a.trav = s->d_trav.p; a.mask = s->d_mask.p; a.seq_off = s->off(); a.ctr = s->d_ctr.p;
+    a.node_np_off = k.d_np_off.p; a.np = k.d_np.p; a.graph_path_off = k.d_gpo.p; a.path_len = k.d_len.p;
+    a.read_ser = s->ct.d_acov_ser.p; a.state = s->ct.d_acov_state.p; a.fill = k.acov_fill.p;
+    a.cap = s->trav_cap; a.pw = c->pw_view; a.first_read_id = s->first_read_id; a.n_paths = (uint32_t)k.h_len.size();
+    const dim3 g(grid_for(s->trav_cap));
+    hipLaunchKernelGGL(acov_count_kernel<false>, g, dim3(kBlock), 0, c->tstream, a, k.acov.table());
+    hipLaunchKernelGGL(acov_count_kernel<true>, g, dim3(kBlock), 0, c->tstream, a, k.acov.table());
+    k.acov_launches += 2;
+    HIP_TRY(c, hipGetLastError());
+    return GROOT_OK;
+}
+
+// behind the batch's ec_merge_kernel and before shared_expand_kernel clears the per-batch table (tail stream)
+static int acov_launch(groot_ctx *c, Slot *s, const SharedArgs &sa)
+{
+    HIP_TRY(c, s->ct.d_acov_ser.reserve(std::max<uint32_t>(c->prm.max_batch_reads, 1u)));
+    HIP_TRY(c, s->ct.d_acov_state.reserve(1));
+    HIP_TRY(c, hipMemsetAsync(s->ct.d_acov_state.p, 0, sizeof(uint32_t), c->tstream));
+    hipLaunchKernelGGL(acov_serial_kernel, dim3(grid_for(s->trav_cap)), dim3(kBlock), 0, c->tstream, sa, c->ct.acov_tab_ser.p, s->ct.d_acov_ser.p);
+    c->ct.acov_launches++;
+    return acov_count(c, s);
+}
+
+// `factor` times the slots, every key and count moved over; everything launched on the tail stream has ended when this returns
+static int acov_grow(groot_ctx *c, uint32_t factor)
+{
+    Counters &k = c->ct;
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
+    const uint64_t cap = (uint64_t)factor * k.acov.cap;
+    if (cap > (1ull << 31)) return fail(c, GROOT_E_NOSPACE, "assigned coverage: the table would need %llu slots", (unsigned long long)cap);
+    AcovBufs grown;
+    hipError_t e = grown.alloc((uint32_t)cap, c->tstream);
+    if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "assigned coverage: growing the table to %llu slots: %s", (unsigned long long)cap, hipGetErrorString(e));
+    hipLaunchKernelGGL(acov_rehash_kernel, dim3(grid_for(k.acov.cap)), dim3(kBlock), 0, c->tstream, k.acov.table(), k.acov.cap, grown.table(), k.acov_err.p);
+    k.acov_launches++;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
+    uint32_t err = 0;
+    HIP_TRY(c, hipMemcpy(&err, k.acov_err.p, sizeof err, hipMemcpyDeviceToHost));
+    if (err) return fail(c, GROOT_E_DEVICE, "assigned coverage: a key did not fit the grown table");
+    k.acov.swap(grown);
+    k.acov_grows++;
+    return GROOT_OK;
+}
+
+// At collect, while slot s still owns its records and its reads' serials: a batch whose claim phase ran out of room added nothing;
+// the table grows fourfold and both phases run again until the claim goes through.  A table more than half full is doubled.
+// refetch: the copies enqueue made are stale (the batch was redone).
+static int acov_collect(groot_ctx *c, Slot *s, bool refetch)
+{
+    auto fetch = [&]() -> int {
+        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->acov_state, s->ct.d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->acov_fill, c->ct.acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return GROOT_OK;
+    };
+    if (refetch)
+        if (int rc = fetch()) return rc;
+    for (;;) {
+        const uint32_t st = s->ct.h_status.p->acov_state, fill = s->ct.h_status.p->acov_fill;
+        if (st > 1) return fail(c, GROOT_E_DEVICE, "assigned coverage: a claimed key was not found in the table");
+        if (!st && 2ull * fill <= c->ct.acov.cap) return GROOT_OK;
+        if (int rc = acov_grow(c, st ? 4u : 2u)) return rc;
+        if (!st) continue;
+        HIP_TRY(c, hipMemsetAsync(s->ct.d_acov_state.p, 0, sizeof(uint32_t), c->tstream));
+        if (int rc = acov_count(c, s)) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
+        c->ct.acov_redone++;
+        if (int rc = fetch()) return rc;
+    }
+}
+
+// the records of one slow-path read (trav[0..n), its path sets, its S(r) = ids) into acov_host; m_len = the read's length
+static void acov_fold_host(groot_ctx *c, const groot_trav *trav, const uint64_t *mask, size_t n, const std::vector<uint32_t> &ids, uint64_t read_len)
+{
+    const uint32_t pw = c->pw_view, n_paths = (uint32_t)c->ct.h_len.size();
+    auto &tab = c->ct.acov_host[ids];
+    for (size_t t = 0; t < n; t++) {
+        const groot_trav &tr = trav[t];
+        const uint64_t m = read_len - ((tr.flags & GROOT_TRAV_START_CLIP) ? 1u : 0u) - ((tr.flags & GROOT_TRAV_END_CLIP) ? 1u : 0u);
+        const uint32_t g0 = c->ct.h_gpo[tr.graph_id];
+        for (uint32_t j = c->ct.h_np_off[tr.node]; j < c->ct.h_np_off[tr.node + 1]; j++) {
+            const uint2 e = c->ct.h_np[j];
+            if (!((mask[t * pw + (e.x >> 6)] >> (e.x & 63)) & 1ull)) continue;
+            const uint32_t gp = g0 + e.x;
+            if (gp >= n_paths) continue;
+            const uint64_t len = c->ct.h_len[gp], pos = (uint64_t)e.y + tr.offset;
+            if (len == 0 || pos > 0xFFFFFFFEull) continue;
+            const uint64_t last = std::min<uint64_t>(pos + m, len - 1);
+            tab[{gp, (uint32_t)pos, (uint32_t)last}]++;
+            c->ct.acov_slow_records++;
+        }
+    }
+}
+
+// At collect, while slot s still owns its records: the table's fill, and the exact S(r) of the batch's slow-path reads into ec_host.
+// refetch: the copies enqueue made are stale (the batch was redone).
+static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
+{
+    if (refetch) {
+        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->ec_slow, s->ct.d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->ec_fill, c->ct.ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    const uint32_t n_slow = s->ct.h_status.p->ec_slow;
+    c->ct.ec_fill_known = std::max<uint64_t>(c->ct.ec_fill_known, s->ct.h_status.p->ec_fill);
+    if (!n_slow) return GROOT_OK;
+    // per unit (first, end) traversal; in paired mode (first, end of the even mate's records, end): the unit is a fragment, and its
+    // set the intersection of the two mates' sets, when the middle differs from the end
+    const size_t sw = c->ct.pairs_on ? 3 : 2;
+    std::vector<uint32_t> span(sw * (size_t)n_slow);
+    HIP_TRY(c, hipMemcpy(span.data(), s->ct.d_ec_slow.p + 1, span.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t pw = c->pw_view;
+    // few reads: their records one by one; many (GROOT_TEST_SHARED_SLOW): the range that holds them all in one copy
+    uint32_t lo = ~0u, hi = 0;
+    for (uint32_t i = 0; i < n_slow; i++) { lo = std::min(lo, span[sw * i]); hi = std::max(hi, span[sw * i + sw - 1]); }
+    const bool whole = n_slow > 32;
+    std::vector<groot_trav> tr;
+    std::vector<uint64_t> mk;
+    if (whole) {
+        tr.resize(hi - lo); mk.resize((size_t)(hi - lo) * pw);
+        HIP_TRY(c, hipMemcpy(tr.data(), s->d_trav.p + lo, tr.size() * sizeof(groot_trav), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)lo * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    std::vector<uint32_t> ids, ids_a, ids_b;
+    std::vector<uint64_t> offs;            // assigned coverage: the batch's read offsets (a record's M op is the read's length less its clips)
+    if (c->ct.acov_on) {
+        offs.resize((size_t)s->n_reads + 1);
+        HIP_TRY(c, hipMemcpy(offs.data(), s->off(), offs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    for (uint32_t i = 0; i < n_slow; i++) {
+        const uint32_t t0 = span[sw * i], tm = span[sw * i + sw - 2], t1 = span[sw * i + sw - 1];
+        if (!whole) {
+            tr.resize(t1 - t0); mk.resize((size_t)(t1 - t0) * pw);
+            HIP_TRY(c, hipMemcpy(tr.data(), s->d_trav.p + t0, tr.size() * sizeof(groot_trav), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)t0 * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        }
+        const size_t o = whole ? t0 - lo : 0;
+        if (c->ct.pairs_on && tm != t1) {
+            ec_set_of(c, tr.data() + o, mk.data() + o * pw, tm - t0, ids_a);
+            ec_set_of(c, tr.data() + o + (tm - t0), mk.data() + (o + (tm - t0)) * pw, t1 - tm, ids_b);
+            ids.clear();
+            std::set_intersection(ids_a.begin(), ids_a.end(), ids_b.begin(), ids_b.end(), std::back_inserter(ids));
+        } else {
+            ec_set_of(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids);
+        }
+        if (c->ct.acov_on && !ids.empty() && t1 > t0) {
+            const uint32_t r = tr[o].read_id - s->first_read_id;
+            acov_fold_host(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids, offs[r + 1] - offs[r]);
+        }
+        if (!ids.empty()) c->ct.ec_host[ids]++;
+    }
+    c->ct.ec_slow_reads += n_slow;
+    return GROOT_OK;
+}
+
+// ---- the pipeline's hooks (counters.hpp) ---------------------------------------------------------------------------
+namespace groot {
+
+void counters_init(groot_ctx *c, const groot_index_view *v)
+{
+    Counters &k = c->ct;
+    // (a view without graphs -- the sketch engine of `index --gpu` -- may carry no offset arrays at all)
+    if (v->node_np_off) k.h_np_off.assign(v->node_np_off, v->node_np_off + v->n_nodes + 1); else k.h_np_off.assign(v->n_nodes + 1, 0);
+    if (v->graph_path_off) k.h_gpo.assign(v->graph_path_off, v->graph_path_off + v->n_graphs + 1); else k.h_gpo.assign(v->n_graphs + 1, 0);
+    k.h_len.assign(v->path_len, v->path_len + v->n_paths);
+    k.h_np.resize(v->n_np);
+    for (uint64_t j = 0; j < v->n_np; j++) k.h_np[j] = make_uint2(v->np_path[j], v->np_pos[j]);
+    k.h_cov_base.assign(v->n_paths + 1, 0);
+    for (uint32_t p = 0; p < v->n_paths; p++) k.h_cov_base[p + 1] = k.h_cov_base[p] + v->path_len[p] + 1;
+}
+
+int counters_launch(groot_ctx *c, Slot *s)
+{
+    Counters &k = c->ct;
+    const dim3 g(grid_for(s->trav_cap));
+    if (k.cov_on) {   // (reads the slot's records and read offsets only: the next batch's seed stage need not wait for it)
+        CovArgs ca{};
+        ca.trav = s->d_trav.p; ca.mask = s->d_mask.p; ca.seq_off = s->off(); ca.ctr = s->d_ctr.p;
+        ca.node_np_off = k.d_np_off.p; ca.np = k.d_np.p; ca.graph_path_off = k.d_gpo.p; ca.path_len = k.d_len.p; ca.slot_base = k.cov_base.p;
+        ca.starts = k.cov_starts.p; ca.ends = k.cov_ends.p;
+        ca.cap = s->trav_cap; ca.pw = c->pw_view; ca.first_read_id = s->first_read_id;
+        hipLaunchKernelGGL(cov_count_kernel, g, dim3(kBlock), 0, c->tstream, ca);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (k.sh_on || k.ec_on) {    // (the same: slot data and the ctx's own buffers, in tail-stream order)
+        SharedArgs sa{};
+        sa.trav = s->d_trav.p; sa.mask = s->d_mask.p; sa.ctr = s->d_ctr.p; sa.graph_path_off = k.d_gpo.p;
+        sa.set_graph = k.sh_set_graph.p; sa.set_mask = k.sh_set_mask.p; sa.tab_rep = k.sh_tab_rep.p; sa.tab_cnt = k.sh_tab_cnt.p;
+        sa.slow = k.sh_slow.p; sa.batch = k.sh_batch.p; sa.tri = k.sh_tri.p; sa.stats = k.sh_stats.p;
+        sa.cap = s->trav_cap; sa.pw = c->pw_view; sa.first_read_id = s->first_read_id; sa.n_paths = (uint32_t)k.h_len.size();
+        sa.max_segs = c->kn.shared_slow ? 1u : kSharedSegs;
+        sa.pairs = k.sh_on;
+        sa.slow_cap = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+        uint32_t tab = 1;                  // this batch's part of the table: >= 2 n_reads slots
+        while (tab < 2u * std::max<uint32_t>(s->n_reads, 1u)) tab <<= 1;
+        sa.tab_mask = tab - 1;
+        const dim3 gt(grid_for(tab));      // the merge and the expansion: one item per slot of that part
+        const bool paired = k.pairs_on;
+        if (paired) hipLaunchKernelGGL(shared_gather_paired_kernel, g, dim3(kBlock), 0, c->tstream, sa);
+        else hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->tstream, sa);
+        hipLaunchKernelGGL(shared_insert_kernel, g, dim3(kBlock), 0, c->tstream, sa);
+        if (k.sh_on && paired) hipLaunchKernelGGL(shared_slow_kernel<true>, dim3(256), dim3(kBlock), 0, c->tstream, sa);
+        else if (k.sh_on) hipLaunchKernelGGL(shared_slow_kernel<false>, dim3(256), dim3(kBlock), 0, c->tstream, sa);
+        if (k.ec_on) {
+            if (int rc = ec_reserve(c, s)) return rc;
+            HIP_TRY(c, s->ct.d_ec_slow.reserve(1 + (paired ? 3 : 2) * (size_t)c->prm.max_batch_reads));
+            HIP_TRY(c, s->ct.h_status.reserve(1));
+            if (paired) hipLaunchKernelGGL(ec_merge_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p, nullptr);
+            else hipLaunchKernelGGL(ec_merge_kernel<false>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p,
+                                    k.acov_on ? k.acov_tab_ser.p : nullptr);
+            if (k.acov_on)
+                if (int rc = acov_launch(c, s, sa)) return rc;
+        }
+        if (paired) hipLaunchKernelGGL(shared_expand_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, tab);
+        else hipLaunchKernelGGL(shared_expand_kernel<false>, gt, dim3(kBlock), 0, c->tstream, sa, tab);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return GROOT_OK;
+}
+
+int counters_fetch(groot_ctx *c, Slot *s)
+{
+    if (!c->ct.ec_on) return GROOT_OK;
+    CounterStatus *h = s->ct.h_status.p;
+    HIP_TRY(c, hipMemcpyAsync(&h->ec_slow, s->ct.d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    HIP_TRY(c, hipMemcpyAsync(&h->ec_fill, c->ct.ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    if (c->ct.acov_on) {
+        HIP_TRY(c, hipMemcpyAsync(&h->acov_state, s->ct.d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+        HIP_TRY(c, hipMemcpyAsync(&h->acov_fill, c->ct.acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    }
+    return GROOT_OK;
+}
+
+int counters_collect(groot_ctx *c, Slot *s, bool redone)
+{
+    if (!c->ct.ec_on || !s->n_reads) return GROOT_OK;
+    if (int rc = ec_collect(c, s, redone)) return rc;
+    return c->ct.acov_on ? acov_collect(c, s, redone) : GROOT_OK;
+}
+
+} // namespace groot
+
+// ---------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+
+// ---- report coverage (kernels_cov.hpp) ------------------------------------------------------------------------------
+int groot_hip_coverage_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "coverage can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!on) {
+        k.cov_base.release(); k.cov_starts.release(); k.cov_ends.release();
+        k.cov_on = false;
+        if (!pos_wanted(k)) pos_release(k);
+        return GROOT_OK;
+    }
+    if (k.cov_on) return GROOT_OK;
+    const uint64_t slots = k.h_cov_base.back();
+    auto undo = [&](int rc) { k.cov_on = true; groot_hip_coverage_enable(c, 0); return rc; };
+    hipError_t e = pos_acquire(k);
+    if (e == hipSuccess) e = upload(k.cov_base, k.h_cov_base.data(), k.h_cov_base.size());
+    if (e == hipSuccess) e = k.cov_starts.alloc(slots);
+    if (e == hipSuccess) e = k.cov_ends.alloc(slots);
+    if (e == hipSuccess) e = hipMemset(k.cov_starts.p, 0, std::max<uint64_t>(slots, 1) * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(k.cov_ends.p, 0, std::max<uint64_t>(slots, 1) * sizeof(unsigned long long));
+    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "coverage: %s", hipGetErrorString(e)));
+    k.cov_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_coverage_export(groot_ctx *c, uint64_t *records, uint64_t *depth)
+{
+    if (!c || (!c->ct.h_len.empty() && (!records || !depth))) return GROOT_E_INVALID;
+    if (!c->ct.cov_on) return fail(c, GROOT_E_STATE, "coverage is not enabled (groot_hip_coverage_enable)");
+    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo, if they need one)
+    const uint64_t slots = c->ct.h_cov_base.back();
+    std::vector<uint64_t> st(slots), en(slots);
+    if (slots) {
+        HIP_TRY(c, hipMemcpy(st.data(), c->ct.cov_starts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(en.data(), c->ct.cov_ends.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    uint64_t at = 0;
+    for (size_t p = 0; p < c->ct.h_len.size(); p++) {
+        const uint64_t b = c->ct.h_cov_base[p], len = c->ct.h_len[p];
+        uint64_t n = 0, d = 0;
+        for (uint64_t i = 0; i < len; i++) {
+            n += st[b + i];
+            d += st[b + i] - en[b + i];
+            depth[at++] = d;
+        }
+        records[p] = n + st[b + len];
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_coverage_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.cov_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    const uint64_t slots = std::max<uint64_t>(c->ct.h_cov_base.back(), 1);
+    HIP_TRY(c, hipMemset(c->ct.cov_starts.p, 0, slots * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->ct.cov_ends.p, 0, slots * sizeof(unsigned long long)));
+    return GROOT_OK;
+}
+
+// ---- shared reads (kernels_shared.hpp) -------------------------------------------------------------------------------
+static uint64_t shared_tri_size(uint64_t n_paths) { return n_paths * (n_paths + 1) / 2; }
+
+// the per-batch buffers shared reads and equivalence classes both use (allocated while either is on)
+static void sh_common_release(groot_ctx *c)
+{
+    for (auto *b : {&c->ct.sh_set_graph, &c->ct.sh_tab_rep, &c->ct.sh_tab_cnt, &c->ct.sh_slow, &c->ct.sh_batch}) b->release();
+    c->ct.sh_set_mask.release(); c->ct.sh_stats.release();
+    if (!pos_wanted(c->ct)) pos_release(c->ct);
+}
+
+static hipError_t sh_common_alloc(groot_ctx *c)
+{
+    if (c->ct.sh_on || c->ct.ec_on) return hipSuccess;
+    const uint32_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    const uint64_t tab = c->ct.sh_tab_cap;
+    hipError_t e = pos_acquire(c->ct);
+    if (e == hipSuccess) e = c->ct.sh_set_graph.alloc((size_t)R * kSharedSegs);
+    if (e == hipSuccess) e = c->ct.sh_set_mask.alloc((size_t)R * kSharedSegs * std::max<uint32_t>(c->pw_view, 1u));
+    if (e == hipSuccess) e = c->ct.sh_tab_rep.alloc(tab);
+    if (e == hipSuccess) e = c->ct.sh_tab_cnt.alloc(tab);
+    if (e == hipSuccess) e = c->ct.sh_slow.alloc(R);
+    if (e == hipSuccess) e = c->ct.sh_batch.alloc(kSharedBatch);
+    if (e == hipSuccess) e = c->ct.sh_stats.alloc(kSharedStats);
+    if (e == hipSuccess) e = hipMemset(c->ct.sh_tab_rep.p, 0xFF, tab * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->ct.sh_tab_cnt.p, 0, tab * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->ct.sh_batch.p, 0, kSharedBatch * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(c->ct.sh_stats.p, 0, kSharedStats * sizeof(unsigned long long));
+    return e;
+}
+
+static int sh_table_size(groot_ctx *c, const char *what)
+{
+    const uint32_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    uint64_t tab = 1;
+    while (tab < 2ull * R) tab <<= 1;
+    if (tab > (1ull << 31)) return fail(c, GROOT_E_UNSUPPORTED, "%s: max_batch_reads=%u is above 2^30", what, R);
+    c->ct.sh_tab_cap = (uint32_t)tab;
+    return GROOT_OK;
+}
+
+int groot_hip_shared_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "shared reads can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!on) {
+        c->ct.sh_tri.release();
+        c->ct.sh_on = false;
+        if (!c->ct.ec_on) sh_common_release(c);
+        return GROOT_OK;
+    }
+    if (c->ct.sh_on) return GROOT_OK;
+    const uint64_t n_paths = c->ct.h_len.size(), tri = shared_tri_size(n_paths);
+    if (tri * sizeof(uint64_t) > GROOT_SHARED_MAX_BYTES)
+        return fail(c, GROOT_E_UNSUPPORTED, "shared reads: %llu paths need a %llu MiB pair table, above the bound of %llu MiB", (unsigned long long)n_paths,
+                    (unsigned long long)(tri * sizeof(uint64_t) >> 20), (unsigned long long)(GROOT_SHARED_MAX_BYTES >> 20));
+    if (!c->ct.ec_on)
+        if (int rc = sh_table_size(c, "shared reads")) return rc;
+    auto undo = [&](int rc) { c->ct.sh_on = true; groot_hip_shared_enable(c, 0); return rc; };
+    hipError_t e = sh_common_alloc(c);
+    if (e == hipSuccess) e = c->ct.sh_tri.alloc(tri);
+    if (e == hipSuccess) e = hipMemset(c->ct.sh_tri.p, 0, std::max<uint64_t>(tri, 1) * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(c->ct.sh_stats.p, 0, kSharedStats * sizeof(unsigned long long));
+    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "shared reads: %s", hipGetErrorString(e)));
+    c->ct.sh_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_shared_export(groot_ctx *c, uint32_t *pa, uint32_t *pb, uint64_t *count, uint64_t cap, uint64_t *n_pairs)
+{
+    if (!c || !n_pairs || (cap && (!pa || !pb || !count))) return GROOT_E_INVALID;
+    if (!c->ct.sh_on) return fail(c, GROOT_E_STATE, "shared reads are not enabled (groot_hip_shared_enable)");
+    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo, if they need one)
+    const uint64_t P = c->ct.h_len.size(), tri = shared_tri_size(P);
+    std::vector<uint64_t> t(tri);
+    if (tri) HIP_TRY(c, hipMemcpy(t.data(), c->ct.sh_tri.p, tri * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t n = 0, i = 0;
+    for (uint64_t x = 0; x < P; x++)
+        for (uint64_t y = x; y < P; y++, i++) {
+            if (!t[i]) continue;
+            if (n < cap) { pa[n] = (uint32_t)x; pb[n] = (uint32_t)y; count[n] = t[i]; }
+            n++;
+        }
+    *n_pairs = n;
+    return GROOT_OK;
+}
+
+int groot_hip_shared_stats(groot_ctx *c, uint64_t *reads, uint64_t *distinct_sets, uint64_t *slow_reads)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.sh_on) return fail(c, GROOT_E_STATE, "shared reads are not enabled (groot_hip_shared_enable)");
+    if (int rc = drain(c)) return rc;
+    uint64_t st[kSharedPairStats];
+    HIP_TRY(c, hipMemcpy(st, c->ct.sh_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    if (reads) *reads = st[0];
+    if (distinct_sets) *distinct_sets = st[1];
+    if (slow_reads) *slow_reads = st[2];
+    return GROOT_OK;
+}
+
+int groot_hip_shared_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.sh_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemset(c->ct.sh_tri.p, 0, std::max<uint64_t>(shared_tri_size(c->ct.h_len.size()), 1) * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->ct.sh_stats.p, 0, kSharedStats * sizeof(unsigned long long)));
+    return GROOT_OK;
+}
+
+// ---- equivalence classes (kernels_ec.hpp) ---------------------------------------------------------------------------
+int groot_hip_ec_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "equivalence classes can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!on) {
+        if (c->ct.acov_on)
+            if (int rc = groot_hip_acov_enable(c, 0)) return rc;     // (its tuples are keyed by this table's serials)
+        c->ct.ec.release(); c->ct.ec_fill.release();
+        c->ct.ec_host.clear();
+        c->ct.ec_on = false;
+        if (!c->ct.sh_on) sh_common_release(c);
+        return GROOT_OK;
+    }
+    if (c->ct.ec_on) return GROOT_OK;
+    if (!c->ct.sh_on)
+        if (int rc = sh_table_size(c, "equivalence classes")) return rc;
+    uint32_t cap = 1;
+    while (cap < (c->kn.ec_slots ? std::max<uint32_t>(c->kn.ec_slots, 2u) : (1u << 16))) cap <<= 1;
+    auto undo = [&](int rc) { c->ct.ec_on = true; groot_hip_ec_enable(c, 0); return rc; };
+    hipError_t e = sh_common_alloc(c);
+    if (e == hipSuccess) e = c->ct.ec.alloc(cap, std::max<uint32_t>(c->pw_view, 1u), c->tstream);
+    if (e == hipSuccess) e = c->ct.ec_fill.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(c->ct.ec_fill.p, 0, sizeof(uint32_t), c->tstream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->tstream);
+    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "equivalence classes: %s", hipGetErrorString(e)));
+    c->ct.ec_fill_known = c->ct.ec_grows = c->ct.ec_slow_reads = 0;
+    c->ct.ec_host.clear();
+    c->ct.ec_on = true;
+    return GROOT_OK;
+}
+
+// the device table and the host map merged: S -> reads, in canonical order (lexicographic on the ascending ID lists)
+// by_serial (optional): the ID list of every slot of the device table, by the slot's serial
+static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &out, std::vector<std::vector<uint32_t>> *by_serial = nullptr)
+{
+    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo and their slow-path reads)
+    uint32_t fill = 0;
+    HIP_TRY(c, hipMemcpy(&fill, c->ct.ec_fill.p, sizeof fill, hipMemcpyDeviceToHost));
+    out = c->ct.ec_host;
+    if (!fill) return GROOT_OK;
+    const uint32_t pw = std::max<uint32_t>(c->pw_view, 1u);
+    DevBuf<uint32_t> g, n, ser;
+    DevBuf<uint64_t> m;
+    DevBuf<unsigned long long> cnt;
+    HIP_TRY(c, ser.alloc(fill));
+    HIP_TRY(c, g.alloc((size_t)fill * kSharedSegs));
+    HIP_TRY(c, m.alloc((size_t)fill * kSharedSegs * pw));
+    HIP_TRY(c, cnt.alloc(fill));
+    HIP_TRY(c, n.alloc(1));
+    HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->tstream));
+    hipLaunchKernelGGL(ec_export_kernel, dim3(grid_for(c->ct.ec.cap)), dim3(kBlock), 0, c->tstream, c->ct.ec.table(), c->ct.ec.cap, pw, g.p, m.p, cnt.p, ser.p, n.p, fill);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->tstream));
+    uint32_t got = 0;
+    HIP_TRY(c, hipMemcpy(&got, n.p, sizeof got, hipMemcpyDeviceToHost));
+    if (got != fill) return fail(c, GROOT_E_DEVICE, "equivalence classes: %u keys in a table that counted %u", got, fill);
+    std::vector<uint32_t> hg((size_t)fill * kSharedSegs);
+    std::vector<uint64_t> hm((size_t)fill * kSharedSegs * pw), hc(fill);
+    HIP_TRY(c, hipMemcpy(hg.data(), g.p, hg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hm.data(), m.p, hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hc.data(), cnt.p, hc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> hs(fill);
+    HIP_TRY(c, hipMemcpy(hs.data(), ser.p, hs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (by_serial) by_serial->assign(fill, {});
+    std::vector<groot_trav> tr;
+    std::vector<uint64_t> mk;
+    std::vector<uint32_t> ids;
+    for (uint32_t i = 0; i < fill; i++) {
+        // a key = one pseudo-record per segment: (graph, OR of its path sets)
+        tr.clear(); mk.clear();
+        for (uint32_t k = 0; k < kSharedSegs && hg[(size_t)i * kSharedSegs + k] != kSharedEmpty; k++) {
+            groot_trav t{};
+            t.graph_id = hg[(size_t)i * kSharedSegs + k];
+            tr.push_back(t);
+            for (uint32_t w = 0; w < pw; w++) mk.push_back(hm[((size_t)i * kSharedSegs + k) * pw + w]);
+        }
+        ec_set_of(c, tr.data(), mk.data(), tr.size(), ids);
+        if (!ids.empty() && hc[i]) out[ids] += hc[i];
+        if (by_serial && hs[i] < fill) (*by_serial)[hs[i]] = ids;
+    }
+    return GROOT_OK;
+}
+
+// the classes of m as a CSR: off[e] .. off[e + 1] of ids are the path IDs of class e, count[e] its reads (the caller has checked the room)
+static void write_ecs(const std::map<std::vector<uint32_t>, uint64_t> &m, uint64_t *off, uint32_t *ids, uint64_t *count)
+{
+    uint64_t e = 0, at = 0;
+    if (off) off[0] = 0;
+    for (const auto &kv : m) {
+        for (uint32_t x : kv.first) ids[at++] = x;
+        count[e] = kv.second;
+        off[++e] = at;
+    }
+}
+
+int groot_hip_ec_export(groot_ctx *c, uint64_t *off, uint32_t *ids, uint64_t *count, uint64_t cap_ec, uint64_t cap_ids, uint64_t *n_ec, uint64_t *n_ids)
+{
+    if (!c || !n_ec || !n_ids || (cap_ec && (!off || !count)) || (cap_ids && !ids)) return GROOT_E_INVALID;
+    if (!c->ct.ec_on) return fail(c, GROOT_E_STATE, "equivalence classes are not enabled (groot_hip_ec_enable)");
+    std::map<std::vector<uint32_t>, uint64_t> m;
+    if (int rc = ec_gather(c, m)) return rc;
+    uint64_t ni = 0;
+    for (const auto &kv : m) ni += kv.first.size();
+    *n_ec = m.size();
+    *n_ids = ni;
+    if (!cap_ec && !cap_ids) return GROOT_OK;
+    if (cap_ec < m.size() || cap_ids < ni)
+        return fail(c, GROOT_E_NOSPACE, "equivalence classes: room for %llu classes / %llu IDs, %llu / %llu needed", (unsigned long long)cap_ec,
+                    (unsigned long long)cap_ids, (unsigned long long)m.size(), (unsigned long long)ni);
+    write_ecs(m, off, ids, count);
+    return GROOT_OK;
+}
+
+int groot_hip_ec_stats(groot_ctx *c, uint64_t *reads, uint64_t *distinct, uint64_t *slow_reads, uint64_t *grows)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.ec_on) return fail(c, GROOT_E_STATE, "equivalence classes are not enabled (groot_hip_ec_enable)");
+    std::map<std::vector<uint32_t>, uint64_t> m;
+    if (int rc = ec_gather(c, m)) return rc;
+    uint64_t r = 0;
+    for (const auto &kv : m) r += kv.second;
+    if (reads) *reads = r;
+    if (distinct) *distinct = m.size();
+    if (slow_reads) *slow_reads = c->ct.ec_slow_reads;
+    if (grows) *grows = c->ct.ec_grows;
+    return GROOT_OK;
+}
+
+int groot_hip_ec_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.ec_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemset(c->ct.ec.claim.p, 0, (size_t)c->ct.ec.cap * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(c->ct.ec_fill.p, 0, sizeof(uint32_t)));
+    c->ct.ec_fill_known = c->ct.ec_grows = c->ct.ec_slow_reads = 0;
+    c->ct.ec_host.clear();
+    if (c->ct.pairs_on) HIP_TRY(c, hipMemset(c->ct.sh_stats.p + kSharedPairStats, 0, (kSharedStats - kSharedPairStats) * sizeof(unsigned long long)));
+    return groot_hip_acov_reset(c);     // (the serials start again: its tuples would name other classes)
+}
+
+// ---- assigned coverage (kernels_acov.hpp; the definition is in groot_hip.h) ------------------------------------------------
+int groot_hip_acov_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "assigned coverage can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!on) {
+        c->ct.acov.release();
+        for (auto *b : {&c->ct.acov_fill, &c->ct.acov_err, &c->ct.acov_tab_ser}) b->release();
+        c->ct.acov_host.clear();
+        c->ct.acov_on = false;
+        return GROOT_OK;
+    }
+    if (c->ct.acov_on) return GROOT_OK;
+    if (c->ct.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "assigned coverage with paired-end units is not supported");
+    if (int rc = groot_hip_ec_enable(c, 1)) return rc;
+    uint32_t cap = 1;
+    while (cap < (c->kn.acov_slots ? std::max<uint32_t>(c->kn.acov_slots, 2u) : (1u << 20))) cap <<= 1;
+    auto undo = [&](int rc) { c->ct.acov_on = true; groot_hip_acov_enable(c, 0); return rc; };
+    hipError_t e = c->ct.acov.alloc(cap, c->tstream);
+    if (e == hipSuccess) e = c->ct.acov_fill.alloc(1);
+    if (e == hipSuccess) e = c->ct.acov_err.alloc(1);
+    if (e == hipSuccess) e = c->ct.acov_tab_ser.alloc(c->ct.sh_tab_cap);
+    if (e == hipSuccess) e = hipMemsetAsync(c->ct.acov_fill.p, 0, sizeof(uint32_t), c->tstream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->ct.acov_err.p, 0, sizeof(uint32_t), c->tstream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->tstream);
+    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "assigned coverage: %s", hipGetErrorString(e)));
+    c->ct.acov_grows = c->ct.acov_slow_records = c->ct.acov_redone = 0;
+    c->ct.acov_host.clear();
+    c->ct.acov_on = true;
+    return GROOT_OK;
+}
+
+namespace {
+struct AcovTuple {
+    uint32_t ec, path, pos, last;
+    uint64_t n;
+    bool operator<(const AcovTuple &o) const { return std::tie(ec, path, pos, last) < std::tie(o.ec, o.path, o.pos, o.last); }
+    bool same_key(const AcovTuple &o) const { return ec == o.ec && path == o.path && pos == o.pos && last == o.last; }
+};
+}
+
+// the ctx's ECs in canonical order and its tuples, EC = index into that list, ascending, equal keys of the device table and the host
+// map summed
+static int acov_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &ecs, std::vector<AcovTuple> &out)
+{
+    std::vector<std::vector<uint32_t>> by_serial;
+    if (int rc = ec_gather(c, ecs, &by_serial)) return rc;
+    out.clear();
+    std::map<std::vector<uint32_t>, uint32_t> index;
+    for (const auto &kv : ecs) { const uint32_t i = (uint32_t)index.size(); index[kv.first] = i; }
+    uint32_t fill = 0;
+    HIP_TRY(c, hipMemcpy(&fill, c->ct.acov_fill.p, sizeof fill, hipMemcpyDeviceToHost));
+    if (fill) {
+        std::vector<uint32_t> ser_idx(by_serial.size(), ~0u);
+        for (size_t i = 0; i < by_serial.size(); i++) {
+            auto it = index.find(by_serial[i]);
+            if (it != index.end()) ser_idx[i] = it->second;
+        }
+        DevBuf<unsigned long long> key, cnt;
+        DevBuf<uint32_t> n;
+        HIP_TRY(c, key.alloc(2 * (size_t)fill));
+        HIP_TRY(c, cnt.alloc(fill));
+        HIP_TRY(c, n.alloc(1));
+        HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->tstream));
+        hipLaunchKernelGGL(acov_export_kernel, dim3(grid_for(c->ct.acov.cap)), dim3(kBlock), 0, c->tstream, c->ct.acov.table(), c->ct.acov.cap, key.p, cnt.p, n.p, fill);
+        c->ct.acov_launches++;
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
+        uint32_t got = 0;
+        HIP_TRY(c, hipMemcpy(&got, n.p, sizeof got, hipMemcpyDeviceToHost));
+        if (got > fill) return fail(c, GROOT_E_DEVICE, "assigned coverage: %u tuples in a table that counted %u", got, fill);
+        std::vector<uint64_t> hk(2 * (size_t)got), hc(got);
+        if (got) {
+            HIP_TRY(c, hipMemcpy(hk.data(), key.p, hk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(hc.data(), cnt.p, hc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        }
+        out.reserve(got);
+        for (uint32_t i = 0; i < got; i++) {
+            const uint64_t ser = (hk[2 * (size_t)i] >> 32) - 1;
+            if (ser >= ser_idx.size() || ser_idx[ser] == ~0u) return fail(c, GROOT_E_DEVICE, "assigned coverage: a tuple names class %llu, which the table of classes does not hold", (unsigned long long)ser);
+            out.push_back(AcovTuple{ser_idx[ser], (uint32_t)hk[2 * (size_t)i], (uint32_t)(hk[2 * (size_t)i + 1] >> 32), (uint32_t)hk[2 * (size_t)i + 1], hc[i]});
+        }
+    }
+    for (const auto &kv : c->ct.acov_host) {
+        auto it = index.find(kv.first);
+        if (it == index.end()) return fail(c, GROOT_E_DEVICE, "assigned coverage: the host map holds a class the table of classes does not");
+        for (const auto &t : kv.second) out.push_back(AcovTuple{it->second, t.first[0], t.first[1], t.first[2], t.second});
+    }
+    std::sort(out.begin(), out.end());
+    size_t w = 0;
+    for (size_t i = 0; i < out.size(); i++) {
+        if (w && out[w - 1].same_key(out[i])) out[w - 1].n += out[i].n;
+        else out[w++] = out[i];
+    }
+    out.resize(w);
+    return GROOT_OK;
+}
+
+int groot_hip_acov_export(groot_ctx *c, uint64_t *ec_off, uint32_t *ec_ids, uint64_t *ec_count, uint32_t *tuples, uint64_t *n, uint64_t cap_ec, uint64_t cap_ids,
+                          uint64_t cap_tuples, uint64_t *n_ec, uint64_t *n_ids, uint64_t *n_tuples)
+{
+    if (!c || !n_ec || !n_ids || !n_tuples || (cap_ec && (!ec_off || !ec_count)) || (cap_ids && !ec_ids) || (cap_tuples && (!tuples || !n))) return GROOT_E_INVALID;
+    if (!c->ct.acov_on) return fail(c, GROOT_E_STATE, "assigned coverage is not enabled (groot_hip_acov_enable)");
+    std::map<std::vector<uint32_t>, uint64_t> m;
+    std::vector<AcovTuple> tp;
+    if (int rc = acov_gather(c, m, tp)) return rc;
+    uint64_t ni = 0;
+    for (const auto &kv : m) ni += kv.first.size();
+    *n_ec = m.size();
+    *n_ids = ni;
+    *n_tuples = tp.size();
+    if (!cap_ec && !cap_ids && !cap_tuples) return GROOT_OK;
+    if (cap_ec < m.size() || cap_ids < ni || cap_tuples < tp.size())
+        return fail(c, GROOT_E_NOSPACE, "assigned coverage: room for %llu classes / %llu IDs / %llu tuples, %llu / %llu / %llu needed", (unsigned long long)cap_ec,
+                    (unsigned long long)cap_ids, (unsigned long long)cap_tuples, (unsigned long long)m.size(), (unsigned long long)ni, (unsigned long long)tp.size());
+    write_ecs(m, ec_off, ec_ids, ec_count);
+    for (size_t i = 0; i < tp.size(); i++) {
+        tuples[4 * i] = tp[i].ec; tuples[4 * i + 1] = tp[i].path; tuples[4 * i + 2] = tp[i].pos; tuples[4 * i + 3] = tp[i].last;
+        n[i] = tp[i].n;
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_acov_stats(groot_ctx *c, uint64_t *records, uint64_t *tuples, uint64_t *slots, uint64_t *grows, uint64_t *slow_records, uint64_t *launches)
+{
+    if (!c) return GROOT_E_INVALID;
+    uint64_t r = 0, nt = 0;
+    if (c->ct.acov_on) {
+        std::map<std::vector<uint32_t>, uint64_t> m;
+        std::vector<AcovTuple> tp;
+        if (int rc = acov_gather(c, m, tp)) return rc;
+        for (const auto &t : tp) r += t.n;
+        nt = tp.size();
+    }
+    if (records) *records = r;
+    if (tuples) *tuples = nt;
+    if (slots) *slots = c->ct.acov_on ? c->ct.acov.cap : 0;
+    if (grows) *grows = c->ct.acov_on ? c->ct.acov_grows : 0;
+    if (slow_records) *slow_records = c->ct.acov_on ? c->ct.acov_slow_records : 0;
+    if (launches) *launches = c->ct.acov_launches;
+    return GROOT_OK;
+}
+
+int groot_hip_acov_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.acov_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemset(c->ct.acov.k0.p, 0, (size_t)c->ct.acov.cap * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->ct.acov.k1.p, 0xFF, (size_t)c->ct.acov.cap * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->ct.acov.cnt.p, 0, (size_t)c->ct.acov.cap * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->ct.acov_fill.p, 0, sizeof(uint32_t)));
+    c->ct.acov_grows = c->ct.acov_slow_records = c->ct.acov_redone = 0;
+    c->ct.acov_host.clear();
+    return GROOT_OK;
+}
+
+// ---- paired-end reads (the kPaired kernels of kernels_shared.hpp; the definition is in groot_hip.h) -------------------------
+int groot_hip_pairs_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "pairing can only be switched while nothing is in flight");
+    if (on && c->ct.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assigned coverage are not supported");
+    c->ct.pairs_on = on != 0;
+    if (c->ct.sh_on || c->ct.ec_on) {     // (else there is nothing to zero: sh_common_alloc zeroes the counts when either comes on)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipMemset(c->ct.sh_stats.p + kSharedPairStats, 0, (kSharedStats - kSharedPairStats) * sizeof(unsigned long long)));
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_pairs_stats(groot_ctx *c, uint64_t *joined, uint64_t *split, uint64_t *single)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.pairs_on) return fail(c, GROOT_E_STATE, "pairing is not enabled (groot_hip_pairs_enable)");
+    if (int rc = drain(c)) return rc;
+    uint64_t st[kSharedStats] = {};
+    if (c->ct.sh_on || c->ct.ec_on) HIP_TRY(c, hipMemcpy(st, c->ct.sh_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    if (joined) *joined = st[kSharedPairStats];
+    if (split) *split = st[kSharedPairStats + 1];
+    if (single) *single = st[kSharedPairStats + 2];
+    return GROOT_OK;
+}
+
+// ---- bootstrap replicates of the abundance EM (kernels_boot.hpp; the contract is in groot_host.h) ---------------------------
+namespace {
+struct DeviceGuard {         // the calling thread's current device, put back on return
+    int prev = -1;
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
+};
+constexpr size_t kBootChunkBytes = 256u << 20;      // device memory of one chunk of replicates (counts + alpha)
+constexpr uint32_t kBootDrawGroups = 2048;          // workgroups of one boot_resample_kernel launch, about
+} // namespace
+
+int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_boot,
+                           uint64_t seed, uint64_t n_draws, uint32_t min_iter, uint32_t max_iter, uint64_t *boot_count, double *alpha, uint32_t *iterations)
+{
+    if ((n_ec && (!off || !count)) || (n_paths && !alpha)) return fail(nullptr, GROOT_E_INVALID, "null argument");
+    if (n_boot == 0) return fail(nullptr, GROOT_E_INVALID, "no bootstrap replicates");
+    if (max_iter < min_iter)
+        return fail(nullptr, GROOT_E_INVALID, "number of EM iterations (%u) must be greater than minimum iterations (%u)", max_iter, min_iter);
+    if (max_iter < 1) return fail(nullptr, GROOT_E_INVALID, "no EM iterations were ran");
+    if (n_ec >= 0xFFFFFFFFull || (n_ec && off[n_ec] >= 0xFFFFFFFFull))
+        return fail(nullptr, GROOT_E_UNSUPPORTED, "bootstrap on the device: 2^32 ECs or path IDs and more");
+    const uint32_t ne = (uint32_t)n_ec;
+    std::vector<uint64_t> cum((size_t)ne + 1, 0);
+    std::vector<uint32_t> ec_off((size_t)ne + 1, 0), path_off((size_t)n_paths + 1, 0);
+    for (uint32_t e = 0; e < ne; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return fail(nullptr, GROOT_E_INVALID, "EC %u: bad offsets", e);
+        for (uint64_t i = off[e]; i < off[e + 1]; i++) {
+            if (ids[i] >= n_paths) return fail(nullptr, GROOT_E_INVALID, "EC %u holds path %u of %u", e, ids[i], n_paths);
+            path_off[ids[i] + 1]++;
+        }
+        ec_off[e + 1] = ec_off[e] + (uint32_t)(off[e + 1] - off[e]);
+        cum[e + 1] = cum[e] + count[e];
+        if (cum[e + 1] < cum[e]) return fail(nullptr, GROOT_E_INVALID, "the EC counts sum to 2^64 or more");
+    }
+    const uint64_t total = cum[ne];
+    if (ne && total == 0) return fail(nullptr, GROOT_E_INVALID, "bootstrap over ECs without reads");
+    if (n_draws == 0) n_draws = total;
+    // path -> EC, CSR: the ECs are visited in order, so every path's list ascends (an ID an EC names twice is listed twice, as the host adds it twice)
+    const uint32_t nnz = ec_off[ne];
+    for (uint32_t p = 0; p < n_paths; p++) path_off[p + 1] += path_off[p];
+    std::vector<uint32_t> ec_ids(std::max<uint32_t>(nnz, 1u)), path_ecs(std::max<uint32_t>(nnz, 1u)), at(path_off.begin(), path_off.end() - 1);
+    for (uint32_t e = 0; e < ne; e++)
+        for (uint64_t i = off[e]; i < off[e + 1]; i++) {
+            ec_ids[ec_off[e] + (i - off[e])] = ids[i];
+            path_ecs[at[ids[i]]++] = e;
+        }
+
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(nullptr, GROOT_E_DEVICE, "no HIP device");
+    if (device < 0 || device >= n_dev) return fail(nullptr, GROOT_E_DEVICE, "device %d of %d", device, n_dev);
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    HIP_TRY(nullptr, hipSetDevice(device));
+    int lds_max = 0, n_cu = 0;
+    HIP_TRY(nullptr, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    HIP_TRY(nullptr, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+    n_cu = std::max(n_cu, 1);
+    StreamGuard sg;
+    HIP_TRY(nullptr, hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    hipStream_t st = sg.s;
+
+    const size_t per_rep = ((size_t)ne + n_paths) * 8;
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)n_boot, (size_t)65535, kBootChunkBytes / std::max<size_t>(per_rep, 1)}));
+    DevBuf<uint64_t> d_cum;
+    DevBuf<uint32_t> d_ec_off, d_ec_ids, d_path_off, d_path_ecs, d_it;
+    DevBuf<unsigned long long> d_cnt;
+    DevBuf<double> d_alpha, d_scratch;
+    HIP_TRY(nullptr, d_cum.alloc(cum.size()));
+    HIP_TRY(nullptr, d_ec_off.alloc(ec_off.size()));
+    HIP_TRY(nullptr, d_ec_ids.alloc(ec_ids.size()));
+    HIP_TRY(nullptr, d_path_off.alloc(path_off.size()));
+    HIP_TRY(nullptr, d_path_ecs.alloc(path_ecs.size()));
+    HIP_TRY(nullptr, d_cnt.alloc((size_t)chunk * ne));
+    HIP_TRY(nullptr, d_alpha.alloc((size_t)chunk * n_paths));
+    HIP_TRY(nullptr, d_it.alloc(chunk));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_cum.p, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_ec_off.p, ec_off.data(), ec_off.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_ec_ids.p, ec_ids.data(), ec_ids.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_path_off.p, path_off.data(), path_off.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_path_ecs.p, path_ecs.data(), path_ecs.size() * 4, hipMemcpyHostToDevice, st));
+
+    // LDS or global memory: the cumulative table and the histogram of the draws; alpha and norm of the EM
+    const size_t draw_lds = ((size_t)ne + 1) * 8 + (size_t)ne * 4, em_lds = per_rep;
+    const bool draw_in_lds = draw_lds <= (size_t)lds_max, em_in_lds = em_lds <= (size_t)lds_max;
+    if (draw_in_lds && draw_lds > 48 * 1024)
+        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_resample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)draw_lds));
+    if (em_in_lds && em_lds > 48 * 1024)
+        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_em_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
+    const uint32_t em_grid = std::min<uint32_t>(chunk, (uint32_t)n_cu);
+    if (!em_in_lds) HIP_TRY(nullptr, d_scratch.alloc((size_t)em_grid * ((size_t)ne + n_paths)));
+
+    constexpr uint64_t kChunkDraws = (uint64_t)kBootDrawBlock * kBootDrawsPerThread;
+    const uint64_t draw_chunks = (n_draws + kChunkDraws - 1) / kChunkDraws;
+    for (uint32_t b0 = 0; b0 < n_boot; b0 += chunk) {
+        const uint32_t nb = std::min(chunk, n_boot - b0);
+        if (ne) {
+            HIP_TRY(nullptr, hipMemsetAsync(d_cnt.p, 0, (size_t)nb * ne * 8, st));
+            if (draw_chunks) {
+                BootDrawArgs da{d_cum.p, d_cnt.p, total, n_draws, seed, ne, b0};
+                const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(draw_chunks, (kBootDrawGroups + nb - 1) / nb)), nb);
+                if (draw_in_lds) hipLaunchKernelGGL(boot_resample_kernel<true>, grid, dim3(kBootDrawBlock), draw_lds, st, da);
+                else hipLaunchKernelGGL(boot_resample_kernel<false>, grid, dim3(kBootDrawBlock), 0, st, da);
+                HIP_TRY(nullptr, hipGetLastError());
+            }
+        }
+        BootEmArgs ea{d_ec_off.p, d_ec_ids.p, d_path_off.p, d_path_ecs.p, d_cnt.p, d_alpha.p, d_it.p, d_scratch.p, 1.0 / (double)n_paths, n_paths, ne, nb, min_iter, max_iter};
+        const dim3 grid(std::min<uint32_t>(nb, em_grid));
+        if (em_in_lds) hipLaunchKernelGGL(boot_em_kernel<true>, grid, dim3(kBootEmBlock), em_lds, st, ea);
+        else hipLaunchKernelGGL(boot_em_kernel<false>, grid, dim3(kBootEmBlock), 0, st, ea);
+        HIP_TRY(nullptr, hipGetLastError());
+        if (boot_count && ne) HIP_TRY(nullptr, hipMemcpyAsync(boot_count + (size_t)b0 * ne, d_cnt.p, (size_t)nb * ne * 8, hipMemcpyDeviceToHost, st));
+        if (n_paths) HIP_TRY(nullptr, hipMemcpyAsync(alpha + (size_t)b0 * n_paths, d_alpha.p, (size_t)nb * n_paths * 8, hipMemcpyDeviceToHost, st));
+        if (iterations) HIP_TRY(nullptr, hipMemcpyAsync(iterations + b0, d_it.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(nullptr, hipStreamSynchronize(st));
+    }
+    return GROOT_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,408 @@
+// ctx.hpp -- the ctx of libgroot_hip.so as its translation units see it: the buffer types, one batch in flight (Slot), the work sets and
+// groot_ctx itself, with the state of the counters behind the order stage (counters.hip) as ONE member each of the ctx and of a slot.
+// Internal to groot_hip.hip (pipeline + C ABI) and counters.hip; the calls between the two are at the end and in counters.hpp.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <atomic>
+#include <cstdlib>
+#include <deque>
+#include <map>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "device_types.hpp"
+
+using namespace groot;
+
+
+// ---------------------------------------------------------------------------------------------
+// ctx
+// ---------------------------------------------------------------------------------------------
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    hipError_t alloc(size_t count)
+    {
+        release();
+        n = count;
+        return hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
+    }
+    hipError_t reserve(size_t count) { return count <= n && p ? hipSuccess : alloc(count); }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    ~DevBuf() { release(); }
+};
+
+// page-locked host memory: the only kind hipMemcpyAsync really overlaps with kernels
+template <class T> struct PinBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    hipError_t alloc(size_t count)
+    {
+        release();
+        n = count;
+        return hipHostMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault);
+    }
+    hipError_t reserve(size_t count) { return count <= n && p ? hipSuccess : alloc(count); }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    ~PinBuf() { release(); }
+};
+
+// The environment switches of the shipped library, read when a ctx is opened (everything else that used to be tunable from the
+// environment was an experiment and went in round 4: DESIGN.md "Removed").  The three NO_* switch a tier of the seed stage off (tests
+// compare the tiers with each other and with the CPU checker); TEST_SMALL_BUFFERS starts every growable buffer and list too small, so that
+// a test batch walks the grow-and-redo and the fall-back paths; OPEN_STATS prints where groot_hip_open spent its time.
+struct Knobs {
+    bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false,
+         shared_slow = false, serial_tail = false;
+    uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
+    uint32_t acov_slots = 0;               // GROOT_TEST_ACOV_SLOTS: initial slots of the assigned-coverage table (0 = the default)
+    static Knobs read()
+    {
+        Knobs k;
+        k.no_outcome_table = getenv("GROOT_NO_OUTCOME_TABLE") != nullptr; k.no_text_table = getenv("GROOT_NO_TEXT_TABLE") != nullptr;
+        k.no_sig = getenv("GROOT_NO_SIG") != nullptr;                     k.force_rccl = getenv("GROOT_FORCE_RCCL") != nullptr;
+        k.small_buffers = getenv("GROOT_TEST_SMALL_BUFFERS") != nullptr;  k.open_stats = getenv("GROOT_OPEN_STATS") != nullptr;
+        k.poison = getenv("GROOT_TEST_POISON") != nullptr;
+        k.lean = getenv("GROOT_LEAN") != nullptr;                         // the node-by-node first pass (kernels_lean.hpp) instead of the path-text one
+        k.no_path = getenv("GROOT_NO_PATH_PASS") != nullptr;              // no first pass: align_kernel alone
+        k.shared_slow = getenv("GROOT_TEST_SHARED_SLOW") != nullptr;      // shared reads: every read in more than one graph takes the slow path
+        k.serial_tail = getenv("GROOT_SERIAL_TAIL") != nullptr;           // the tail of the align stage stays on the walk stream (no tail stream: the A/B baseline)
+        if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
+        if (const char *e = getenv("GROOT_TEST_ACOV_SLOTS")) k.acov_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
+        return k;
+    }
+};
+
+// ---- the counters behind the order stage (counters.hip) ----
+namespace groot {
+struct EcTable;
+struct AcovTable;
+} // namespace groot
+
+// The run-wide table of equivalence classes (kernels_ec.hpp): its buffers for cap slots (a power of two).  Growth allocates a second
+// one, rehashes into it and swaps.
+struct EcBufs {
+    uint32_t cap = 0;
+    DevBuf<uint32_t> claim, graph;
+    DevBuf<uint64_t> mask;
+    DevBuf<unsigned long long> cnt;
+    DevBuf<uint32_t> serial;               // [cap] the serial of every claimed slot (EcTable::serial)
+    hipError_t alloc(uint32_t slots, uint32_t pw, hipStream_t st);   // free (no slot claimed; the memset is enqueued on st); pw words per path set
+    EcTable table() const;
+    void swap(EcBufs &o);
+    void release();
+};
+
+// The run-wide table of assigned coverage (kernels_acov.hpp), likewise
+struct AcovBufs {
+    uint32_t cap = 0;
+    DevBuf<unsigned long long> k0, k1, cnt;
+    hipError_t alloc(uint32_t slots, hipStream_t st);                // free (k0 = 0, k1 = all ones, no counts; the memsets are enqueued on st)
+    AcovTable table() const;
+    void swap(AcovBufs &o);
+    void release();
+};
+
+// what the host reads back of a batch's counting kernels (copied behind them, ahead of the DeviceCounters)
+struct CounterStatus {
+    uint32_t ec_slow;                      // equivalence classes: the batch's slow-path reads
+    uint32_t ec_fill;                      // ... and the table's fill behind this batch's merge
+    uint32_t acov_state;                   // assigned coverage: SlotCounters::d_acov_state[0]
+    uint32_t acov_fill;                    // ... and its table's fill
+};
+
+struct SlotCounters {
+    DevBuf<uint32_t> d_ec_slow;            // equivalence classes: the batch's slow-path reads (ec_merge_kernel), read at collect
+    PinBuf<CounterStatus> h_status;
+    DevBuf<uint32_t> d_acov_ser;           // assigned coverage: the EC serial of every read of the batch (acov_serial_kernel); the counting kernels read it, also when collect repeats them
+    DevBuf<uint32_t> d_acov_state;         // [0] 1 = the batch's claim phase ran out of room (its add phase then did nothing), 2 = a key went missing
+};
+
+struct Counters {
+    // The per-node path-position tables, kept on the host from open (a few MB).  ONE device copy serves report coverage, shared reads,
+    // equivalence classes and assigned coverage: uploaded when the first of them comes on, released when the last goes off.
+    std::vector<uint32_t> h_np_off, h_gpo, h_len;        // node_np_off, graph_path_off, path_len
+    std::vector<uint2> h_np;                             // (path, position) of every entry
+    DevBuf<uint32_t> d_np_off, d_gpo, d_len;
+    DevBuf<uint2> d_np;
+    // report coverage (groot_hip_coverage_*, kernels_cov.hpp): off until enabled, then cov_count_kernel runs behind every batch's
+    // order stage.  The device holds the counters only while on.
+    bool cov_on = false;
+    std::vector<uint64_t> h_cov_base;      // first slot of every path, + the total
+    DevBuf<uint64_t> cov_base;
+    DevBuf<unsigned long long> cov_starts, cov_ends;
+    // shared reads (groot_hip_shared_*, kernels_shared.hpp): off until enabled, then four kernels behind every batch's order stage count,
+    // for every pair of paths a <= b, the reads with records on both.  Nothing on the device while off.
+    bool sh_on = false;
+    uint32_t sh_tab_cap = 0;               // slots of the set table: a power of two >= 2 max_batch_reads
+    DevBuf<uint32_t> sh_set_graph, sh_tab_rep, sh_tab_cnt, sh_slow, sh_batch;
+    DevBuf<uint64_t> sh_set_mask;
+    DevBuf<unsigned long long> sh_tri, sh_stats;
+    // equivalence classes (groot_hip_ec_*, kernels_ec.hpp): the gather and insert kernels of shared reads run while either is on, and
+    // ec_merge_kernel folds each batch's distinct sets into a run-wide table; slow-path reads are folded on the host at collect
+    bool ec_on = false;
+    bool pairs_on = false;                 // groot_hip_pairs_enable: reads 2i, 2i+1 of a batch are one fragment (the kPaired kernels of kernels_shared.hpp)
+    EcBufs ec;
+    uint32_t ec_epoch = 0;                 // epoch of the newest launch on the table
+    DevBuf<uint32_t> ec_fill;
+    uint64_t ec_fill_known = 0;            // the fill read back at the newest collect
+    uint64_t ec_grows = 0, ec_slow_reads = 0;
+    std::map<std::vector<uint32_t>, uint64_t> ec_host;   // the exact S(r) of slow-path reads -> reads
+    // assigned coverage (groot_hip_acov_*, kernels_acov.hpp): the run's records grouped by (EC serial, path, Pos, last) in a run-wide
+    // open-addressing table; needs equivalence classes on.  Slow-path reads are grouped on the host at collect (ec_collect).
+    bool acov_on = false;
+    AcovBufs acov;
+    DevBuf<uint32_t> acov_fill, acov_err, acov_tab_ser;
+    uint64_t acov_grows = 0, acov_slow_records = 0, acov_redone = 0;
+    uint64_t acov_launches = 0;            // kernels launched for it since open (stays put while it is off)
+    std::map<std::vector<uint32_t>, std::map<std::array<uint32_t, 3>, uint64_t>> acov_host;   // S(r) -> (path, Pos, last) -> records, of slow-path reads
+};
+
+// One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the
+// kernels of batch b); everything the kernels only use between themselves is shared by all slots (one compute stream).
+struct Slot {
+    enum State { FREE, ACQUIRED, IN_FLIGHT, D2H_ISSUED, COLLECTED };
+    State state = FREE;
+    uint64_t ticket = 0;
+    uint32_t n_reads = 0, first_read_id = 0, max_len = 0;
+    uint32_t set = 0;                      // groot_ctx::ws the batch runs through
+    uint32_t uniform_len = 0;              // IN_PACKED16: every read has this length (0 = lengths differ): no length array on the wire
+    bool mixed_len = false;                // the reads are known to differ in length (the align stage then refills its wavefronts earlier)
+    bool text_used = false;                // text_lookup_kernel ran first (the list behind it goes through the full-width kernel)
+    bool sig_used = false;                 // the signature kernel ran in front of the full-width kernel for this batch
+    uint32_t packed_q = 0;                 // SeedArgs::packed_q of the batch's signature kernel (0: it left no codes)
+    bool lean_used = false;                // align_lean_kernel ran in front of align_kernel for this batch
+    bool path_used = false;                // align_path_kernel ran in front of align_kernel for this batch
+    uint32_t path_reads = 0;               // ... and finished this many reads
+    float path_ms = 0;                     // ... in this time (profiling on: the pass, which also appends the list of the reads it leaves)
+    bool one_len = false;                  // the reads are known to have max_len bases each, or the caller said so (submit_device with max_len)
+    uint64_t n_bases = 0, n_exc = 0;
+    enum Input { IN_ASCII, IN_PACKED, IN_PACKED16, IN_DEVICE } input = IN_ASCII;
+    const uint8_t *ext_seq = nullptr;      // IN_DEVICE
+    const uint64_t *ext_off = nullptr;
+    // pinned staging (inputs)
+    PinBuf<uint8_t> h_bases;               // ASCII or packed bases
+    PinBuf<uint16_t> h_len;
+    PinBuf<uint64_t> h_off, h_exc_pos;
+    PinBuf<uint8_t> h_exc_byte;
+    // HBM inputs
+    DevBuf<uint16_t> d_len;
+    DevBuf<uint32_t> d_packed;
+    bool exc_at_home = false;                      // the batch's exception list is read from the pinned staging by the kernel that applies it
+    DevBuf<uint8_t> d_seq, d_exc_byte;
+    DevBuf<uint64_t> d_off, d_exc_pos;
+    // outputs
+    uint32_t trav_cap = 0;
+    DevBuf<groot_trav> d_trav;
+    DevBuf<uint64_t> d_mask;
+    DevBuf<DeviceCounters> d_ctr;
+    PinBuf<DeviceCounters> h_ctr;
+    PinBuf<groot_trav> h_trav;                     // what collect hands out (expanded on the host from h_ctrav when the records travel packed)
+    DevBuf<groot_ctrav> d_ctrav;                   // 12-byte records for the copy-out
+    PinBuf<groot_ctrav> h_ctrav;
+    PinBuf<uint8_t> h_mask;                        // COMPACT path sets: ceil(paths(graph) / 8) bytes per traversal
+    PinBuf<uint32_t> h_ckpt;                       // offset into h_mask of every 256th traversal
+    DevBuf<uint8_t> d_cmask;                       // the compact copy the copy-out takes (host-result mode)
+    DevBuf<uint32_t> d_mwords, d_moff, d_ckpt;
+    uint32_t n_trav = 0, copied = 0;               // records of the batch / records the copy-out enqueued at submit covers
+    uint64_t n_mask_bytes = 0, copied_bytes = 0;
+    bool host_results = false;             // the traversal records of this batch are in h_trav / h_mask
+    hipEvent_t ev_seed = nullptr;          // behind the batch's seed stage on the compute stream: its align stage waits for it
+    hipEvent_t ev_walk = nullptr;          // behind the batch's first pass (which appends the list of the reads it leaves) on the walk stream: its tail waits for it
+    hipEvent_t ev_h2d0 = nullptr, ev_h2d = nullptr, ev_compute = nullptr, ev_ctr = nullptr, ev_d2h0 = nullptr, ev_d2h = nullptr;
+    hipEvent_t ev[14]{};                   // [7..8] around the first seed kernel, [9..10] around order_first_kernel, [11] start of the align stage (align stream), [12] behind the list pass
+                                           // [0..6] stage boundaries on the compute stream (profiling)
+    groot_counts counts{};
+    int status = GROOT_OK;
+    std::string status_msg;
+    groot_stage_ms ms{};
+    SlotCounters ct;                       // what the counters behind the order stage keep per batch (counters.hip)
+    const uint8_t *seq() const { return input == IN_DEVICE ? ext_seq : d_seq.p; }
+    const uint64_t *off() const { return input == IN_DEVICE ? ext_off : d_off.p; }
+};
+
+// One of the two sets of buffers a batch's seed stage fills for its align and order stages (groot_ctx::ws)
+struct WorkSet {
+    DevBuf<uint32_t> seed_count, seed_win, perm, perm_count, trav_cnt, tab_idx;
+    DevBuf<uint32_t> perm2;                              // the reads the first pass left (LeanArgs::left); their number is ovf_cnt[kOvfShards + 2]
+    DevBuf<uint4> packed;                                // SeedArgs::packed
+    DevBuf<ReadRec> read_rec;
+    DevBuf<uint4> vitem, split_list;                     // AlignArgs::vitem, sort_seed_lists_kernel
+    DevBuf<uint32_t> vcount;                             // [0] items, [1] split reads of the batch
+    DevBuf<groot_trav> trav_first;
+    DevBuf<uint64_t> mask_first, sketches;
+    // records beyond a read's first (both passes of the align stage append, order_ovf_kernel reads): per set, since the first pass of batch b+1
+    // (walk stream) runs beside align_kernel and the order stage of batch b (tail stream); groot_ctx::ovf_cap slots per shard
+    DevBuf<groot_trav> ovf_trav;
+    DevBuf<uint64_t> ovf_mask;
+    DevBuf<uint32_t> ovf_cnt;
+    hipEvent_t ev_free = nullptr;          // on the tail stream behind the order stage of the batch that used the set last
+    bool used = false;
+    Slot *owner = nullptr;                 // whose seeds / sketches the set holds
+    uint64_t ticket = 0;
+};
+
+struct groot_ctx {
+    int device = 0;
+    std::string err;
+    groot_params prm{};
+    Knobs kn;
+    uint32_t s = 0, k = 0, max_k = 0, l_max = 0, pw_view = 0, pw = 0, n_windows = 0, max_q = 0, band_hash_bits = 0;
+    hipEvent_t h2d_last = nullptr;         // the copy-in of the newest host-fed batch (its slot's event)
+    Slot *newest = nullptr;                // the newest submitted batch (groot_hip_redo_status)
+    hipEvent_t last_compute = nullptr;     // behind the order stage of the newest batch, on the tail stream (groot_hip_stream_join)
+    // stream: seed stage (the caller's, if given); astream: the walk stream (first pass of the align stage, which appends the list of what it leaves);
+    // tstream: the tail stream (align_kernel, order stage, host-copy and counting kernels) -- astream itself under GROOT_SERIAL_TAIL=1
+    hipStream_t own_stream = nullptr, stream = nullptr, astream = nullptr, tstream = nullptr, own_tstream = nullptr, h2d_stream = nullptr, d2h_stream = nullptr;
+    bool profiling = false;
+
+    // index in HBM
+    DevBuf<uint32_t> graph_win_end;
+    DevBuf<uint4> cn_pre;                  // DeviceIndex::cn_pre
+    DevBuf<uint64_t> node_l2b;             // DeviceIndex::node_l2b
+    DevBuf<uint32_t> win_prefix, edges, win_graph, cn_node,
+        band_keys, band_ids;
+    DevBuf<ExactEntry> band_hash;
+    DevBuf<uint8_t> band_sig;
+    DevBuf<uint32_t> band_run;
+    DevBuf<uint8_t> bases, q_k, q_l;
+    DevBuf<uint16_t> q_min_eq;
+    DevBuf<uint64_t> win_sketch;
+    DevBuf<unsigned char> node_rec;
+    DevBuf<LeanExt> lean_ext;
+    DevBuf<LeanNode> lean_nodes;           // first pass of the align stage (kernels_lean.hpp): nodes, graph bases and ContainedNodes prefixes at 2 bits per base
+    DevBuf<uint32_t> bases2;
+    DevBuf<uint4> cn_pre2;
+    DevBuf<uint8_t> win_ok;
+    DevBuf<uint4> lean_stk;                // LeanArgs::stk (align stream)
+    bool lean = false;                     // the first pass is align_lean_kernel (GROOT_LEAN=1)
+    bool path = false;                     // the first pass is align_path_kernel (the default; pw == 3)
+    DevBuf<uint4> path_node, path_hold;    // LeanArgs::path_* (kernels_path.hpp)
+    DevBuf<uint32_t> path_text, path_tag, path_nodes;
+    DevBuf<uint64_t> path_tab;
+    DevBuf<WinRec> win_rec;
+    DevBuf<ExactEntry> exact;
+    DevBuf<SigEntry> sig;                  // sketch_sig_kernel: signature index + window texts (absent: that kernel is not used)
+    DevBuf<uint4> sig_dir;
+    DevBuf<uint8_t> win_text, win_nodes;
+    DevBuf<uint32_t> sig_info;             // per window-text string: verdict byte, or where its tabulated outcome is (DeviceIndex::sig_info)
+    DevBuf<uint4> out_tab;                 // AlignRead outcomes of the window-text strings (DeviceIndex::out_tab)
+    std::vector<uint32_t> h_out_tab;       // the host's copy (groot_hip_read_seeds: seed windows of reads the text lookup answered)
+    uint64_t out_strings = 0, out_tabulated = 0, out_entries = 0;   // strings that confirm reads / of them tabulated / table entries
+    double out_build_ms = 0, open_ms = 0;
+    uint32_t incr_cap = kIncrCap;
+    bool tab_capture = false;              // the capture pass of groot_hip_open is running (align stage records the IncrementSubPath windows)
+    DevBuf<uint32_t> tab_idx, tab_hist, incr_cnt, incr_win;
+    DevBuf<uint4> text_tab;                // text_lookup_kernel: strings with a tabulated outcome, keyed by their bases
+    uint64_t text_entries = 0;
+    uint32_t batches_without_text = 0, text_retry_gap = 8;   // the lookup is tried again after this many batches without it; the gap doubles (up to 256) while it keeps missing
+    double text_hit_frac = 1.0;            // share of the latest batch's reads the outcome table answered: picks the first kernel of the seed stage
+    std::vector<uint16_t> h_q_min_eq;      // host copy of DeviceIndex::q_min_eq: which seed kernel a batch of one read length gets
+    uint32_t sig_disabled = 0;             // windows whose text did not reproduce Key.Sketch (they cannot confirm reads)
+    DeviceIndex dix{};
+
+    // groot_hip_open_flags(GROOT_OPEN_BACKGROUND): the prefix tables and the signature index are built on a thread of its own while the
+    // first batches already run (through the full-width kernel, without the seed stage's verdicts: same results, a little slower);
+    // what it builds is described in bg_dix and moves into dix between two batches (install_background)
+    std::thread bg;
+    std::atomic<int> bg_state{0};          // 0 nothing pending, 1 running, 2 finished, 3 failed, 4 abandoned
+    std::atomic<bool> bg_cancel{false};    // groot_hip_open_abandon / groot_hip_close: the builder stops at its next checkpoint
+    int bg_rc = 0;
+    std::string bg_err;
+    DeviceIndex bg_dix{};
+    uint32_t bg_seed_slots = 0, bg_max_read_len = 0;   // what the builder thread may know of the ctx's mutable state: copies taken before it starts
+    hipStream_t bg_stream = nullptr;
+    DevBuf<unsigned long long> bg_shards;
+    // where the table builders of groot_hip_open work: the ctx's own index description / compute stream / shard counters, or the
+    // background thread's
+    DeviceIndex *build_dix = nullptr;
+    hipStream_t build_stream = nullptr;
+    unsigned long long *build_shards = nullptr;
+
+    // pipeline
+    std::vector<std::unique_ptr<Slot>> slots;
+    std::deque<Slot *> inflight;           // submission order: IN_FLIGHT / D2H_ISSUED
+    uint64_t next_ticket = 1;
+    Slot *waited = nullptr;                // the batch groot_hip_wait collected (released by the next submit / wait)
+    double todo_frac = 1.0;                // share of the latest finished batch's reads that the first seed kernel left to the list pass
+    double lean_left_frac = 1.0;           // share of the latest finished batch's reads that the first pass of the align stage left to the second
+    uint32_t n_cu = 256;
+    double dfs_frac = 1.0;                 // share of the latest finished batch's reads that needed the align stage's graph walk (the rest: no seeds / tabulated outcomes)
+    double trav_per_read = 1.25;           // traversal records per read of the latest finished batch: sizes the next copy-out
+    double bytes_per_trav = 0;             // compact path-set bytes per traversal, likewise (0 = not seen yet: 8 * path_words)
+    bool packed_travs = false;             // the copy-out sends 12-byte records (batches of at most 2^24 reads), collect expands them
+    std::vector<uint32_t> h_node_graph;    // graph of every node (the expansion)
+    DevBuf<uint8_t> graph_words;           // ceil(paths / 8) per graph: BYTES of a traversal's compact path set
+    std::vector<uint8_t> h_graph_words;
+    // What the seed stage of a batch leaves for its align and order stages lives in one of TWO work sets, taken in turn: the seed
+    // stage of batch b+1 (compute stream) runs beside the align + order stages of batch b (align stream) -- the reference's sketching
+    // minions and graph minions run side by side too (boss.go:134-203, graphminion.go:46-102).  Hashing is VALU-issue bound, the
+    // graph walk waits on dependent loads: they want different resources.
+    WorkSet ws[2];
+    uint32_t next_set = 0;
+
+    // shared work buffers: used on ONE of the three streams only, inside one stage
+    uint32_t seed_slots = 0;
+    DevBuf<uint32_t> sort_key, sort_key_out, perm_in, todo_list, todo_count;   // seed stage
+    DevBuf<uint32_t> long_list, long_count;              // SeedArgs::long_list (seed stage)
+    uint32_t vcap = 0;
+    uint32_t lsh_defer_rows = 0, lsh_cap = 0;   // SeedArgs::lsh_defer_rows
+    DevBuf<unsigned long long> seed_shards;
+    DevBuf<uint32_t> lsh_list, lsh_count;  // reads on the LSH-Forest branch with many candidate rows + their sketches, for lsh_heavy_kernel (seed stage)
+    DevBuf<uint64_t> lsh_sketch;
+    DevBuf<char> sort_tmp, in_tmp;         // rocprim scratch of the seed stage / of the input decoding (compute stream)
+    uint32_t ovf_cap = 0;
+    DevBuf<uint32_t> trav_off;             // order stage (tail stream)
+    DevBuf<char> scan_tmp;                 // rocprim scratch of the order stage (tail stream)
+    // DFS stacks
+    uint32_t align_threads = 0, stk_depth = 0;
+    DevBuf<uint64_t> stk_hdr, stk_mask;
+    // IncrementSubPath call counts: [rows][n_windows], one row per kmerCount that occurred
+    DevBuf<uint32_t> attempts, q_row, q_seen, q_of_row, q_nrows;
+    uint32_t *attempts_ptr = nullptr;      // own buffer or the caller's (groot_hip_attempts_layout)
+    uint32_t att_cap = 0;                  // rows the table can hold
+    bool att_external = false;
+    Counters ct;                           // report coverage, shared reads, equivalence classes, assigned coverage, pairing (counters.hip)
+};
+
+#define HIP_TRY(ctx, expr)                                                                             \
+    do {                                                                                                \
+        hipError_t e__ = (expr);                                                                        \
+        if (e__ != hipSuccess) return fail(ctx, GROOT_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e__)); \
+    } while (0)
+
+template <class T> static hipError_t upload(DevBuf<T> &d, const T *src, size_t n, size_t pad = 0)
+{
+    hipError_t e = d.alloc(n + pad);
+    if (e != hipSuccess) return e;
+    if (pad) {
+        e = hipMemset(d.p, 0, (n + pad) * sizeof(T));
+        if (e != hipSuccess) return e;
+    }
+    if (n) e = hipMemcpy(d.p, src, n * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
+
+// what counters.hip needs of the pipeline (groot_hip.hip)
+namespace groot {
+int fail(groot_ctx *ctx, int code, const char *fmt, ...);   // sets the ctx's (no ctx: the thread's) error text, returns code
+int drain(groot_ctx *c);                                    // everything submitted has finished on the device (results stay collectable)
+bool idle(const groot_ctx *c);                              // nothing is in flight
+} // namespace groot

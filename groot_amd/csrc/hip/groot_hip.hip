@@ -1,4 +1,5 @@
-// groot_hip.hip -- libgroot_hip.so: ctx management + the C ABI of include/groot_hip.h.
+// groot_hip.hip -- libgroot_hip.so: ctx management (ctx.hpp), the batch pipeline and the C ABI of include/groot_hip.h; the counters behind the
+// order stage and their part of the ABI are counters.hip, reached through the hooks of counters.hpp.
 // gfx950 only; no CPU fallback anywhere in this library.
 #include <cstring>   // before rocprim: its texture iterator calls host memset
 
@@ -26,333 +27,13 @@
 
 #include "../common/cpus.hpp"
 #include "../common/view_check.hpp"
-#include "kernels_boot.hpp"
-#include "kernels_cov.hpp"
-#include "kernels_ec.hpp"
-#include "kernels_acov.hpp"
+#include "counters.hpp"
+#include "ctx.hpp"
 #include "kernels_misc.hpp"
 #include "kernels_path.hpp"
-#include "kernels_shared.hpp"
 #include "launch.hpp"
 
 using namespace groot;
-
-// ---------------------------------------------------------------------------------------------
-// ctx
-// ---------------------------------------------------------------------------------------------
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count)
-    {
-        release();
-        n = count;
-        return hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-    }
-    hipError_t reserve(size_t count) { return count <= n && p ? hipSuccess : alloc(count); }
-    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~DevBuf() { release(); }
-};
-
-// page-locked host memory: the only kind hipMemcpyAsync really overlaps with kernels
-template <class T> struct PinBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count)
-    {
-        release();
-        n = count;
-        return hipHostMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault);
-    }
-    hipError_t reserve(size_t count) { return count <= n && p ? hipSuccess : alloc(count); }
-    void release()
-    {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~PinBuf() { release(); }
-};
-
-// The environment switches of the shipped library, read when a ctx is opened (everything else that used to be tunable from the
-// environment was an experiment and went in round 4: DESIGN.md "Removed").  The three NO_* switch a tier of the seed stage off (tests
-// compare the tiers with each other and with the CPU checker); TEST_SMALL_BUFFERS starts every growable buffer and list too small, so that
-// a test batch walks the grow-and-redo and the fall-back paths; OPEN_STATS prints where groot_hip_open spent its time.
-struct Knobs {
-    bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false,
-         shared_slow = false, serial_tail = false;
-    uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
-    uint32_t acov_slots = 0;               // GROOT_TEST_ACOV_SLOTS: initial slots of the assigned-coverage table (0 = the default)
-    static Knobs read()
-    {
-        Knobs k;
-        k.no_outcome_table = getenv("GROOT_NO_OUTCOME_TABLE") != nullptr; k.no_text_table = getenv("GROOT_NO_TEXT_TABLE") != nullptr;
-        k.no_sig = getenv("GROOT_NO_SIG") != nullptr;                     k.force_rccl = getenv("GROOT_FORCE_RCCL") != nullptr;
-        k.small_buffers = getenv("GROOT_TEST_SMALL_BUFFERS") != nullptr;  k.open_stats = getenv("GROOT_OPEN_STATS") != nullptr;
-        k.poison = getenv("GROOT_TEST_POISON") != nullptr;
-        k.lean = getenv("GROOT_LEAN") != nullptr;                         // the node-by-node first pass (kernels_lean.hpp) instead of the path-text one
-        k.no_path = getenv("GROOT_NO_PATH_PASS") != nullptr;              // no first pass: align_kernel alone
-        k.shared_slow = getenv("GROOT_TEST_SHARED_SLOW") != nullptr;      // shared reads: every read in more than one graph takes the slow path
-        k.serial_tail = getenv("GROOT_SERIAL_TAIL") != nullptr;           // the tail of the align stage stays on the walk stream (no tail stream: the A/B baseline)
-        if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
-        if (const char *e = getenv("GROOT_TEST_ACOV_SLOTS")) k.acov_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
-        return k;
-    }
-};
-
-// One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the
-// kernels of batch b); everything the kernels only use between themselves is shared by all slots (one compute stream).
-struct Slot {
-    enum State { FREE, ACQUIRED, IN_FLIGHT, D2H_ISSUED, COLLECTED };
-    State state = FREE;
-    uint64_t ticket = 0;
-    uint32_t n_reads = 0, first_read_id = 0, max_len = 0;
-    uint32_t set = 0;                      // groot_ctx::ws the batch runs through
-    uint32_t uniform_len = 0;              // IN_PACKED16: every read has this length (0 = lengths differ): no length array on the wire
-    bool mixed_len = false;                // the reads are known to differ in length (the align stage then refills its wavefronts earlier)
-    bool text_used = false;                // text_lookup_kernel ran first (the list behind it goes through the full-width kernel)
-    bool sig_used = false;                 // the signature kernel ran in front of the full-width kernel for this batch
-    uint32_t packed_q = 0;                 // SeedArgs::packed_q of the batch's signature kernel (0: it left no codes)
-    bool lean_used = false;                // align_lean_kernel ran in front of align_kernel for this batch
-    bool path_used = false;                // align_path_kernel ran in front of align_kernel for this batch
-    uint32_t path_reads = 0;               // ... and finished this many reads
-    float path_ms = 0;                     // ... in this time (profiling on: the pass, which also appends the list of the reads it leaves)
-    bool one_len = false;                  // the reads are known to have max_len bases each, or the caller said so (submit_device with max_len)
-    uint64_t n_bases = 0, n_exc = 0;
-    enum Input { IN_ASCII, IN_PACKED, IN_PACKED16, IN_DEVICE } input = IN_ASCII;
-    const uint8_t *ext_seq = nullptr;      // IN_DEVICE
-    const uint64_t *ext_off = nullptr;
-    // pinned staging (inputs)
-    PinBuf<uint8_t> h_bases;               // ASCII or packed bases
-    PinBuf<uint16_t> h_len;
-    PinBuf<uint64_t> h_off, h_exc_pos;
-    PinBuf<uint8_t> h_exc_byte;
-    // HBM inputs
-    DevBuf<uint16_t> d_len;
-    DevBuf<uint32_t> d_packed;
-    bool exc_at_home = false;                      // the batch's exception list is read from the pinned staging by the kernel that applies it
-    DevBuf<uint8_t> d_seq, d_exc_byte;
-    DevBuf<uint64_t> d_off, d_exc_pos;
-    // outputs
-    uint32_t trav_cap = 0;
-    DevBuf<groot_trav> d_trav;
-    DevBuf<uint64_t> d_mask;
-    DevBuf<DeviceCounters> d_ctr;
-    PinBuf<DeviceCounters> h_ctr;
-    PinBuf<groot_trav> h_trav;                     // what collect hands out (expanded on the host from h_ctrav when the records travel packed)
-    DevBuf<groot_ctrav> d_ctrav;                   // 12-byte records for the copy-out
-    PinBuf<groot_ctrav> h_ctrav;
-    PinBuf<uint8_t> h_mask;                        // COMPACT path sets: ceil(paths(graph) / 8) bytes per traversal
-    PinBuf<uint32_t> h_ckpt;                       // offset into h_mask of every 256th traversal
-    DevBuf<uint8_t> d_cmask;                       // the compact copy the copy-out takes (host-result mode)
-    DevBuf<uint32_t> d_mwords, d_moff, d_ckpt;
-    uint32_t n_trav = 0, copied = 0;               // records of the batch / records the copy-out enqueued at submit covers
-    uint64_t n_mask_bytes = 0, copied_bytes = 0;
-    bool host_results = false;             // the traversal records of this batch are in h_trav / h_mask
-    hipEvent_t ev_seed = nullptr;          // behind the batch's seed stage on the compute stream: its align stage waits for it
-    hipEvent_t ev_walk = nullptr;          // behind the batch's first pass (which appends the list of the reads it leaves) on the walk stream: its tail waits for it
-    hipEvent_t ev_h2d0 = nullptr, ev_h2d = nullptr, ev_compute = nullptr, ev_ctr = nullptr, ev_d2h0 = nullptr, ev_d2h = nullptr;
-    hipEvent_t ev[14]{};                   // [7..8] around the first seed kernel, [9..10] around order_first_kernel, [11] start of the align stage (align stream), [12] behind the list pass
-                                           // [0..6] stage boundaries on the compute stream (profiling)
-    groot_counts counts{};
-    int status = GROOT_OK;
-    std::string status_msg;
-    groot_stage_ms ms{};
-    DevBuf<uint32_t> d_ec_slow;            // equivalence classes: the batch's slow-path reads (ec_merge_kernel), read at collect
-    PinBuf<uint32_t> h_ec;                 // [0] their number, [1] the table's fill behind this batch's merge; assigned coverage: [2] d_acov_state[0], [3] its table's fill
-    DevBuf<uint32_t> d_acov_ser;           // assigned coverage: the EC serial of every read of the batch (acov_serial_kernel); the counting kernels read it, also when collect repeats them
-    DevBuf<uint32_t> d_acov_state;         // [0] 1 = the batch's claim phase ran out of room (its add phase then did nothing), 2 = a key went missing
-    const uint8_t *seq() const { return input == IN_DEVICE ? ext_seq : d_seq.p; }
-    const uint64_t *off() const { return input == IN_DEVICE ? ext_off : d_off.p; }
-};
-
-// One of the two sets of buffers a batch's seed stage fills for its align and order stages (groot_ctx::ws)
-struct WorkSet {
-    DevBuf<uint32_t> seed_count, seed_win, perm, perm_count, trav_cnt, tab_idx;
-    DevBuf<uint32_t> perm2;                              // the reads the first pass left (LeanArgs::left); their number is ovf_cnt[kOvfShards + 2]
-    DevBuf<uint4> packed;                                // SeedArgs::packed
-    DevBuf<ReadRec> read_rec;
-    DevBuf<uint4> vitem, split_list;                     // AlignArgs::vitem, sort_seed_lists_kernel
-    DevBuf<uint32_t> vcount;                             // [0] items, [1] split reads of the batch
-    DevBuf<groot_trav> trav_first;
-    DevBuf<uint64_t> mask_first, sketches;
-    // records beyond a read's first (both passes of the align stage append, order_ovf_kernel reads): per set, since the first pass of batch b+1
-    // (walk stream) runs beside align_kernel and the order stage of batch b (tail stream); groot_ctx::ovf_cap slots per shard
-    DevBuf<groot_trav> ovf_trav;
-    DevBuf<uint64_t> ovf_mask;
-    DevBuf<uint32_t> ovf_cnt;
-    hipEvent_t ev_free = nullptr;          // on the tail stream behind the order stage of the batch that used the set last
-    bool used = false;
-    Slot *owner = nullptr;                 // whose seeds / sketches the set holds
-    uint64_t ticket = 0;
-};
-
-struct groot_ctx {
-    int device = 0;
-    std::string err;
-    groot_params prm{};
-    Knobs kn;
-    uint32_t s = 0, k = 0, max_k = 0, l_max = 0, pw_view = 0, pw = 0, n_windows = 0, max_q = 0, band_hash_bits = 0;
-    hipEvent_t h2d_last = nullptr;         // the copy-in of the newest host-fed batch (its slot's event)
-    Slot *newest = nullptr;                // the newest submitted batch (groot_hip_redo_status)
-    hipEvent_t last_compute = nullptr;     // behind the order stage of the newest batch, on the tail stream (groot_hip_stream_join)
-    // stream: seed stage (the caller's, if given); astream: the walk stream (first pass of the align stage, which appends the list of what it leaves);
-    // tstream: the tail stream (align_kernel, order stage, host-copy and counting kernels) -- astream itself under GROOT_SERIAL_TAIL=1
-    hipStream_t own_stream = nullptr, stream = nullptr, astream = nullptr, tstream = nullptr, own_tstream = nullptr, h2d_stream = nullptr, d2h_stream = nullptr;
-    bool profiling = false;
-
-    // index in HBM
-    DevBuf<uint32_t> graph_win_end;
-    DevBuf<uint4> cn_pre;                  // DeviceIndex::cn_pre
-    DevBuf<uint64_t> node_l2b;             // DeviceIndex::node_l2b
-    DevBuf<uint32_t> win_prefix, edges, win_graph, cn_node,
-        band_keys, band_ids;
-    DevBuf<ExactEntry> band_hash;
-    DevBuf<uint8_t> band_sig;
-    DevBuf<uint32_t> band_run;
-    DevBuf<uint8_t> bases, q_k, q_l;
-    DevBuf<uint16_t> q_min_eq;
-    DevBuf<uint64_t> win_sketch;
-    DevBuf<unsigned char> node_rec;
-    DevBuf<LeanExt> lean_ext;
-    DevBuf<LeanNode> lean_nodes;           // first pass of the align stage (kernels_lean.hpp): nodes, graph bases and ContainedNodes prefixes at 2 bits per base
-    DevBuf<uint32_t> bases2;
-    DevBuf<uint4> cn_pre2;
-    DevBuf<uint8_t> win_ok;
-    DevBuf<uint4> lean_stk;                // LeanArgs::stk (align stream)
-    bool lean = false;                     // the first pass is align_lean_kernel (GROOT_LEAN=1)
-    bool path = false;                     // the first pass is align_path_kernel (the default; pw == 3)
-    DevBuf<uint4> path_node, path_hold;    // LeanArgs::path_* (kernels_path.hpp)
-    DevBuf<uint32_t> path_text, path_tag, path_nodes;
-    DevBuf<uint64_t> path_tab;
-    DevBuf<WinRec> win_rec;
-    DevBuf<ExactEntry> exact;
-    DevBuf<SigEntry> sig;                  // sketch_sig_kernel: signature index + window texts (absent: that kernel is not used)
-    DevBuf<uint4> sig_dir;
-    DevBuf<uint8_t> win_text, win_nodes;
-    DevBuf<uint32_t> sig_info;             // per window-text string: verdict byte, or where its tabulated outcome is (DeviceIndex::sig_info)
-    DevBuf<uint4> out_tab;                 // AlignRead outcomes of the window-text strings (DeviceIndex::out_tab)
-    std::vector<uint32_t> h_out_tab;       // the host's copy (groot_hip_read_seeds: seed windows of reads the text lookup answered)
-    uint64_t out_strings = 0, out_tabulated = 0, out_entries = 0;   // strings that confirm reads / of them tabulated / table entries
-    double out_build_ms = 0, open_ms = 0;
-    uint32_t incr_cap = kIncrCap;
-    bool tab_capture = false;              // the capture pass of groot_hip_open is running (align stage records the IncrementSubPath windows)
-    DevBuf<uint32_t> tab_idx, tab_hist, incr_cnt, incr_win;
-    DevBuf<uint4> text_tab;                // text_lookup_kernel: strings with a tabulated outcome, keyed by their bases
-    uint64_t text_entries = 0;
-    uint32_t batches_without_text = 0, text_retry_gap = 8;   // the lookup is tried again after this many batches without it; the gap doubles (up to 256) while it keeps missing
-    double text_hit_frac = 1.0;            // share of the latest batch's reads the outcome table answered: picks the first kernel of the seed stage
-    std::vector<uint16_t> h_q_min_eq;      // host copy of DeviceIndex::q_min_eq: which seed kernel a batch of one read length gets
-    uint32_t sig_disabled = 0;             // windows whose text did not reproduce Key.Sketch (they cannot confirm reads)
-    DeviceIndex dix{};
-
-    // groot_hip_open_flags(GROOT_OPEN_BACKGROUND): the prefix tables and the signature index are built on a thread of its own while the
-    // first batches already run (through the full-width kernel, without the seed stage's verdicts: same results, a little slower);
-    // what it builds is described in bg_dix and moves into dix between two batches (install_background)
-    std::thread bg;
-    std::atomic<int> bg_state{0};          // 0 nothing pending, 1 running, 2 finished, 3 failed, 4 abandoned
-    std::atomic<bool> bg_cancel{false};    // groot_hip_open_abandon / groot_hip_close: the builder stops at its next checkpoint
-    int bg_rc = 0;
-    std::string bg_err;
-    DeviceIndex bg_dix{};
-    uint32_t bg_seed_slots = 0, bg_max_read_len = 0;   // what the builder thread may know of the ctx's mutable state: copies taken before it starts
-    hipStream_t bg_stream = nullptr;
-    DevBuf<unsigned long long> bg_shards;
-    // where the table builders of groot_hip_open work: the ctx's own index description / compute stream / shard counters, or the
-    // background thread's
-    DeviceIndex *build_dix = nullptr;
-    hipStream_t build_stream = nullptr;
-    unsigned long long *build_shards = nullptr;
-
-    // pipeline
-    std::vector<std::unique_ptr<Slot>> slots;
-    std::deque<Slot *> inflight;           // submission order: IN_FLIGHT / D2H_ISSUED
-    uint64_t next_ticket = 1;
-    Slot *waited = nullptr;                // the batch groot_hip_wait collected (released by the next submit / wait)
-    double todo_frac = 1.0;                // share of the latest finished batch's reads that the first seed kernel left to the list pass
-    double lean_left_frac = 1.0;           // share of the latest finished batch's reads that the first pass of the align stage left to the second
-    uint32_t n_cu = 256;
-    double dfs_frac = 1.0;                 // share of the latest finished batch's reads that needed the align stage's graph walk (the rest: no seeds / tabulated outcomes)
-    double trav_per_read = 1.25;           // traversal records per read of the latest finished batch: sizes the next copy-out
-    double bytes_per_trav = 0;             // compact path-set bytes per traversal, likewise (0 = not seen yet: 8 * path_words)
-    bool packed_travs = false;             // the copy-out sends 12-byte records (batches of at most 2^24 reads), collect expands them
-    std::vector<uint32_t> h_node_graph;    // graph of every node (the expansion)
-    DevBuf<uint8_t> graph_words;           // ceil(paths / 8) per graph: BYTES of a traversal's compact path set
-    std::vector<uint8_t> h_graph_words;
-    // What the seed stage of a batch leaves for its align and order stages lives in one of TWO work sets, taken in turn: the seed
-    // stage of batch b+1 (compute stream) runs beside the align + order stages of batch b (align stream) -- the reference's sketching
-    // minions and graph minions run side by side too (boss.go:134-203, graphminion.go:46-102).  Hashing is VALU-issue bound, the
-    // graph walk waits on dependent loads: they want different resources.
-    WorkSet ws[2];
-    uint32_t next_set = 0;
-
-    // shared work buffers: used on ONE of the three streams only, inside one stage
-    uint32_t seed_slots = 0;
-    DevBuf<uint32_t> sort_key, sort_key_out, perm_in, todo_list, todo_count;   // seed stage
-    DevBuf<uint32_t> long_list, long_count;              // SeedArgs::long_list (seed stage)
-    uint32_t vcap = 0;
-    uint32_t lsh_defer_rows = 0, lsh_cap = 0;   // SeedArgs::lsh_defer_rows
-    DevBuf<unsigned long long> seed_shards;
-    DevBuf<uint32_t> lsh_list, lsh_count;  // reads on the LSH-Forest branch with many candidate rows + their sketches, for lsh_heavy_kernel (seed stage)
-    DevBuf<uint64_t> lsh_sketch;
-    DevBuf<char> sort_tmp, in_tmp;         // rocprim scratch of the seed stage / of the input decoding (compute stream)
-    uint32_t ovf_cap = 0;
-    DevBuf<uint32_t> trav_off;             // order stage (tail stream)
-    DevBuf<char> scan_tmp;                 // rocprim scratch of the order stage (tail stream)
-    // DFS stacks
-    uint32_t align_threads = 0, stk_depth = 0;
-    DevBuf<uint64_t> stk_hdr, stk_mask;
-    // IncrementSubPath call counts: [rows][n_windows], one row per kmerCount that occurred
-    DevBuf<uint32_t> attempts, q_row, q_seen, q_of_row, q_nrows;
-    uint32_t *attempts_ptr = nullptr;      // own buffer or the caller's (groot_hip_attempts_layout)
-    uint32_t att_cap = 0;                  // rows the table can hold
-    bool att_external = false;
-    // report coverage (groot_hip_coverage_*, kernels_cov.hpp): off until enabled, then cov_count_kernel runs behind every batch's
-    // order stage.  The host keeps the position tables from open (a few MB); the device holds them and the counters only while on.
-    bool cov_on = false;
-    std::vector<uint32_t> h_cov_np_off, h_cov_gpo, h_cov_len;
-    std::vector<uint2> h_cov_np;
-    std::vector<uint64_t> h_cov_base;      // first slot of every path, + the total
-    DevBuf<uint32_t> cov_np_off, cov_gpo, cov_len;
-    DevBuf<uint2> cov_np;
-    DevBuf<uint64_t> cov_base;
-    DevBuf<unsigned long long> cov_starts, cov_ends;
-    // shared reads (groot_hip_shared_*, kernels_shared.hpp): off until enabled, then four kernels behind every batch's order stage count,
-    // for every pair of paths a <= b, the reads with records on both.  Nothing on the device while off.
-    bool sh_on = false;
-    uint32_t sh_tab_cap = 0;               // slots of the set table: a power of two >= 2 max_batch_reads
-    DevBuf<uint32_t> sh_gpo, sh_set_graph, sh_tab_rep, sh_tab_cnt, sh_slow, sh_batch;
-    DevBuf<uint64_t> sh_set_mask;
-    DevBuf<unsigned long long> sh_tri, sh_stats;
-    // equivalence classes (groot_hip_ec_*, kernels_ec.hpp): the gather and insert kernels of shared reads run while either is on, and
-    // ec_merge_kernel folds each batch's distinct sets into a run-wide table; slow-path reads are folded on the host at collect
-    bool ec_on = false;
-    bool pairs_on = false;                 // groot_hip_pairs_enable: reads 2i, 2i+1 of a batch are one fragment (the kPaired kernels of kernels_shared.hpp)
-    uint32_t ec_cap = 0, ec_epoch = 0;     // slots (a power of two) / epoch of the newest launch on the table
-    DevBuf<uint32_t> ec_claim, ec_graph, ec_fill;
-    DevBuf<uint64_t> ec_mask;
-    DevBuf<unsigned long long> ec_cnt;
-    uint64_t ec_fill_known = 0;            // the fill read back at the newest collect
-    uint64_t ec_grows = 0, ec_slow_reads = 0;
-    std::map<std::vector<uint32_t>, uint64_t> ec_host;   // the exact S(r) of slow-path reads -> reads
-    DevBuf<uint32_t> ec_serial;            // [ec_cap] the serial of every claimed slot (EcTable::serial)
-    // assigned coverage (groot_hip_acov_*, kernels_acov.hpp): the run's records grouped by (EC serial, path, Pos, last) in a run-wide
-    // open-addressing table; needs equivalence classes on.  Slow-path reads are grouped on the host at collect (ec_collect).
-    bool acov_on = false;
-    uint32_t acov_cap = 0;                 // slots (a power of two)
-    DevBuf<unsigned long long> acov_k0, acov_k1, acov_cnt;
-    DevBuf<uint32_t> acov_fill, acov_err, acov_tab_ser, acov_np_off, acov_len;
-    DevBuf<uint2> acov_np;
-    uint64_t acov_grows = 0, acov_slow_records = 0, acov_redone = 0;
-    uint64_t acov_launches = 0;            // kernels launched for it since open (stays put while it is off)
-    std::map<std::vector<uint32_t>, std::map<std::array<uint32_t, 3>, uint64_t>> acov_host;   // S(r) -> (path, Pos, last) -> records, of slow-path reads
-};
 
 // A ctx drives five HIP streams at once -- seed stage, walk (first pass of the align stage), tail (align_kernel + order stage), copy-in,
 // copy-out -- beside whatever the host process uses itself.  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share one
@@ -365,7 +46,9 @@ static thread_local std::string g_open_err;
 
 static thread_local bool tl_background = false;       // this thread is a ctx's background builder
 
-static int fail(groot_ctx *ctx, int code, const char *fmt, ...)
+namespace groot {
+
+int fail(groot_ctx *ctx, int code, const char *fmt, ...)
 {
     char buf[1024];
     va_list ap;
@@ -377,23 +60,7 @@ static int fail(groot_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                             \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess) return fail(ctx, GROOT_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-
-template <class T> static hipError_t upload(DevBuf<T> &d, const T *src, size_t n, size_t pad = 0)
-{
-    hipError_t e = d.alloc(n + pad);
-    if (e != hipSuccess) return e;
-    if (pad) {
-        e = hipMemset(d.p, 0, (n + pad) * sizeof(T));
-        if (e != hipSuccess) return e;
-    }
-    if (n) e = hipMemcpy(d.p, src, n * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
+} // namespace groot
 
 // ---------------------------------------------------------------------------------------------
 // LSH Ensemble parameters (github.com/ekzhu/lshensemble v1.1.0: OptimalKL, Containment), computed
@@ -1041,248 +708,6 @@ static int launch_order_stage(groot_ctx *c, Slot *s, bool update_weights)
     return GROOT_OK;
 }
 
-// ---- equivalence classes (kernels_ec.hpp) ----
-static EcTable ec_table(const groot_ctx *c)
-{
-    return EcTable{c->ec_claim.p, c->ec_graph.p, c->ec_mask.p, c->ec_cnt.p, c->ec_serial.p, c->ec_cap - 1};
-}
-
-// the table's buffers for cap slots, free
-static hipError_t ec_alloc(groot_ctx *c, uint32_t cap, DevBuf<uint32_t> &claim, DevBuf<uint32_t> &graph, DevBuf<uint64_t> &mask, DevBuf<unsigned long long> &cnt,
-                           DevBuf<uint32_t> &serial, hipStream_t st)
-{
-    const size_t pw = std::max<uint32_t>(c->pw_view, 1u);
-    hipError_t e = claim.alloc(cap);
-    if (e == hipSuccess) e = graph.alloc((size_t)cap * kSharedSegs);
-    if (e == hipSuccess) e = mask.alloc((size_t)cap * kSharedSegs * pw);
-    if (e == hipSuccess) e = cnt.alloc(cap);
-    if (e == hipSuccess) e = serial.alloc(cap);
-    if (e == hipSuccess) e = hipMemsetAsync(claim.p, 0, (size_t)cap * sizeof(uint32_t), st);
-    return e;
-}
-
-// Before a batch's merge: each batch adds at most n_reads keys, so the table must keep >= 2 x (the fill read back at the newest
-// collect + n_reads of every batch launched and not collected, this one included) slots -- else it doubles, rehashed in tail-stream
-// order.  (Growth is rare -- a handful of times per run -- so the old buffers are freed behind a wait for the tail stream.)
-static int ec_reserve(groot_ctx *c, Slot *s)
-{
-    uint64_t pending = s->n_reads;
-    for (Slot *x : c->inflight)
-        if (x != s && x->state == Slot::IN_FLIGHT) pending += x->n_reads;
-    const uint64_t need = 2 * (c->ec_fill_known + pending);
-    if (c->ec_cap >= need) return GROOT_OK;
-    uint64_t cap = c->ec_cap;
-    while (cap < need) cap *= 2;
-    if (cap > (1ull << 31)) return fail(c, GROOT_E_NOSPACE, "equivalence classes: the table would need %llu slots", (unsigned long long)cap);
-    DevBuf<uint32_t> claim, graph, serial;
-    DevBuf<uint64_t> mask;
-    DevBuf<unsigned long long> cnt;
-    hipError_t e = ec_alloc(c, (uint32_t)cap, claim, graph, mask, cnt, serial, c->tstream);
-    if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "equivalence classes: growing the table to %llu slots: %s", (unsigned long long)cap, hipGetErrorString(e));
-    const EcTable from = ec_table(c), to{claim.p, graph.p, mask.p, cnt.p, serial.p, (uint32_t)cap - 1};
-    hipLaunchKernelGGL(ec_rehash_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
-                       from, c->ec_cap, to, std::max<uint32_t>(c->pw_view, 1u), ++c->ec_epoch);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->tstream));
-    c->ec_claim.swap(claim); c->ec_graph.swap(graph); c->ec_mask.swap(mask); c->ec_cnt.swap(cnt); c->ec_serial.swap(serial);
-    c->ec_cap = (uint32_t)cap;
-    c->ec_grows++;
-    return GROOT_OK;
-}
-
-// S(r) of the records trav[0..n) (one read): global path IDs, ascending, each once
-static void ec_set_of(const groot_ctx *c, const groot_trav *trav, const uint64_t *mask, size_t n, std::vector<uint32_t> &ids)
-{
-    const uint32_t pw = c->pw_view, n_paths = (uint32_t)c->h_cov_len.size();
-    ids.clear();
-    for (size_t t = 0; t < n; t++)
-        for (uint32_t w = 0; w < pw; w++)
-            for (uint64_t m = mask[t * pw + w]; m; m &= m - 1) {
-                const uint64_t id = (uint64_t)c->h_cov_gpo[trav[t].graph_id] + w * 64 + (uint32_t)__builtin_ctzll(m);
-                if (id < n_paths) ids.push_back((uint32_t)id);
-            }
-    std::sort(ids.begin(), ids.end());
-    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-}
-
-// ---- assigned coverage (kernels_acov.hpp) ----
-static AcovTable acov_table(const groot_ctx *c)
-{
-    return AcovTable{c->acov_k0.p, c->acov_k1.p, c->acov_cnt.p, c->acov_cap - 1};
-}
-
-// the table's buffers for cap slots, free (k0 = 0, k1 = all ones, no counts)
-static hipError_t acov_alloc(uint32_t cap, DevBuf<unsigned long long> &k0, DevBuf<unsigned long long> &k1, DevBuf<unsigned long long> &cnt, hipStream_t st)
-{
-    hipError_t e = k0.alloc(cap);
-    if (e == hipSuccess) e = k1.alloc(cap);
-    if (e == hipSuccess) e = cnt.alloc(cap);
-    if (e == hipSuccess) e = hipMemsetAsync(k0.p, 0, (size_t)cap * sizeof(unsigned long long), st);
-    if (e == hipSuccess) e = hipMemsetAsync(k1.p, 0xFF, (size_t)cap * sizeof(unsigned long long), st);
-    if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, (size_t)cap * sizeof(unsigned long long), st);
-    return e;
-}
-
-// the claim and the add phase of slot s's batch on the tail stream; both read nothing but what the slot owns and the ctx's tables
-static int acov_count(groot_ctx *c, Slot *s)
-{
-    AcovArgs a{};
-    a.trav = s->d_trav.p; a.mask = s->d_mask.p; a.seq_off = s->off(); a.ctr = s->d_ctr.p;
-    a.node_np_off = c->acov_np_off.p; a.np = c->acov_np.p; a.graph_path_off = c->sh_gpo.p; a.path_len = c->acov_len.p;
-    a.read_ser = s->d_acov_ser.p; a.state = s->d_acov_state.p; a.fill = c->acov_fill.p;
-    a.cap = s->trav_cap; a.pw = c->pw_view; a.first_read_id = s->first_read_id; a.n_paths = (uint32_t)c->h_cov_len.size();
-    const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
-    hipLaunchKernelGGL(acov_count_kernel<false>, g, dim3(kBlock), 0, c->tstream, a, acov_table(c));
-    hipLaunchKernelGGL(acov_count_kernel<true>, g, dim3(kBlock), 0, c->tstream, a, acov_table(c));
-    c->acov_launches += 2;
-    HIP_TRY(c, hipGetLastError());
-    return GROOT_OK;
-}
-
-// behind the batch's ec_merge_kernel and before shared_expand_kernel clears the per-batch table (tail stream)
-static int acov_launch(groot_ctx *c, Slot *s, const SharedArgs &sa)
-{
-    HIP_TRY(c, s->d_acov_ser.reserve(std::max<uint32_t>(c->prm.max_batch_reads, 1u)));
-    HIP_TRY(c, s->d_acov_state.reserve(1));
-    HIP_TRY(c, hipMemsetAsync(s->d_acov_state.p, 0, sizeof(uint32_t), c->tstream));
-    const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
-    hipLaunchKernelGGL(acov_serial_kernel, g, dim3(kBlock), 0, c->tstream, sa, c->acov_tab_ser.p, s->d_acov_ser.p);
-    c->acov_launches++;
-    return acov_count(c, s);
-}
-
-// `factor` times the slots, every key and count moved over; everything launched on the tail stream has ended when this returns
-static int acov_grow(groot_ctx *c, uint32_t factor)
-{
-    HIP_TRY(c, hipStreamSynchronize(c->tstream));
-    const uint64_t cap = (uint64_t)factor * c->acov_cap;
-    if (cap > (1ull << 31)) return fail(c, GROOT_E_NOSPACE, "assigned coverage: the table would need %llu slots", (unsigned long long)cap);
-    DevBuf<unsigned long long> k0, k1, cnt;
-    hipError_t e = acov_alloc((uint32_t)cap, k0, k1, cnt, c->tstream);
-    if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "assigned coverage: growing the table to %llu slots: %s", (unsigned long long)cap, hipGetErrorString(e));
-    const AcovTable to{k0.p, k1.p, cnt.p, (uint32_t)cap - 1};
-    hipLaunchKernelGGL(acov_rehash_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->acov_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
-                       acov_table(c), c->acov_cap, to, c->acov_err.p);
-    c->acov_launches++;
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->tstream));
-    uint32_t err = 0;
-    HIP_TRY(c, hipMemcpy(&err, c->acov_err.p, sizeof err, hipMemcpyDeviceToHost));
-    if (err) return fail(c, GROOT_E_DEVICE, "assigned coverage: a key did not fit the grown table");
-    c->acov_k0.swap(k0); c->acov_k1.swap(k1); c->acov_cnt.swap(cnt);
-    c->acov_cap = (uint32_t)cap;
-    c->acov_grows++;
-    return GROOT_OK;
-}
-
-// At collect, while slot s still owns its records and its reads' serials: a batch whose claim phase ran out of room added nothing;
-// the table grows fourfold and both phases run again until the claim goes through.  A table more than half full is doubled.
-// refetch: the copies enqueue made are stale (the batch was redone).
-static int acov_collect(groot_ctx *c, Slot *s, bool refetch)
-{
-    auto fetch = [&]() -> int {
-        HIP_TRY(c, hipMemcpy(s->h_ec.p + 2, s->d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(s->h_ec.p + 3, c->acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return GROOT_OK;
-    };
-    if (refetch)
-        if (int rc = fetch()) return rc;
-    for (;;) {
-        const uint32_t st = s->h_ec.p[2], fill = s->h_ec.p[3];
-        if (st > 1) return fail(c, GROOT_E_DEVICE, "assigned coverage: a claimed key was not found in the table");
-        if (!st && 2ull * fill <= c->acov_cap) return GROOT_OK;
-        if (int rc = acov_grow(c, st ? 4u : 2u)) return rc;
-        if (!st) continue;
-        HIP_TRY(c, hipMemsetAsync(s->d_acov_state.p, 0, sizeof(uint32_t), c->tstream));
-        if (int rc = acov_count(c, s)) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->tstream));
-        c->acov_redone++;
-        if (int rc = fetch()) return rc;
-    }
-}
-
-// the records of one slow-path read (trav[0..n), its path sets, its S(r) = ids) into acov_host; m_len = the read's length
-static void acov_fold_host(groot_ctx *c, const groot_trav *trav, const uint64_t *mask, size_t n, const std::vector<uint32_t> &ids, uint64_t read_len)
-{
-    const uint32_t pw = c->pw_view, n_paths = (uint32_t)c->h_cov_len.size();
-    auto &tab = c->acov_host[ids];
-    for (size_t t = 0; t < n; t++) {
-        const groot_trav &tr = trav[t];
-        const uint64_t m = read_len - ((tr.flags & GROOT_TRAV_START_CLIP) ? 1u : 0u) - ((tr.flags & GROOT_TRAV_END_CLIP) ? 1u : 0u);
-        const uint32_t g0 = c->h_cov_gpo[tr.graph_id];
-        for (uint32_t j = c->h_cov_np_off[tr.node]; j < c->h_cov_np_off[tr.node + 1]; j++) {
-            const uint2 e = c->h_cov_np[j];
-            if (!((mask[t * pw + (e.x >> 6)] >> (e.x & 63)) & 1ull)) continue;
-            const uint32_t gp = g0 + e.x;
-            if (gp >= n_paths) continue;
-            const uint64_t len = c->h_cov_len[gp], pos = (uint64_t)e.y + tr.offset;
-            if (len == 0 || pos > 0xFFFFFFFEull) continue;
-            const uint64_t last = std::min<uint64_t>(pos + m, len - 1);
-            tab[{gp, (uint32_t)pos, (uint32_t)last}]++;
-            c->acov_slow_records++;
-        }
-    }
-}
-
-// At collect, while slot s still owns its records: the table's fill, and the exact S(r) of the batch's slow-path reads into ec_host.
-// refetch: the copies enqueue made are stale (the batch was redone).
-static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
-{
-    if (refetch) {
-        HIP_TRY(c, hipMemcpy(s->h_ec.p, s->d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(s->h_ec.p + 1, c->ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    const uint32_t n_slow = s->h_ec.p[0];
-    c->ec_fill_known = std::max<uint64_t>(c->ec_fill_known, s->h_ec.p[1]);
-    if (!n_slow) return GROOT_OK;
-    // per unit (first, end) traversal; in paired mode (first, end of the even mate's records, end): the unit is a fragment, and its
-    // set the intersection of the two mates' sets, when the middle differs from the end
-    const size_t sw = c->pairs_on ? 3 : 2;
-    std::vector<uint32_t> span(sw * (size_t)n_slow);
-    HIP_TRY(c, hipMemcpy(span.data(), s->d_ec_slow.p + 1, span.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const uint32_t pw = c->pw_view;
-    // few reads: their records one by one; many (GROOT_TEST_SHARED_SLOW): the range that holds them all in one copy
-    uint32_t lo = ~0u, hi = 0;
-    for (uint32_t i = 0; i < n_slow; i++) { lo = std::min(lo, span[sw * i]); hi = std::max(hi, span[sw * i + sw - 1]); }
-    const bool whole = n_slow > 32;
-    std::vector<groot_trav> tr;
-    std::vector<uint64_t> mk;
-    if (whole) {
-        tr.resize(hi - lo); mk.resize((size_t)(hi - lo) * pw);
-        HIP_TRY(c, hipMemcpy(tr.data(), s->d_trav.p + lo, tr.size() * sizeof(groot_trav), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)lo * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    std::vector<uint32_t> ids, ids_a, ids_b;
-    std::vector<uint64_t> offs;            // assigned coverage: the batch's read offsets (a record's M op is the read's length less its clips)
-    if (c->acov_on) {
-        offs.resize((size_t)s->n_reads + 1);
-        HIP_TRY(c, hipMemcpy(offs.data(), s->off(), offs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    for (uint32_t i = 0; i < n_slow; i++) {
-        const uint32_t t0 = span[sw * i], tm = span[sw * i + sw - 2], t1 = span[sw * i + sw - 1];
-        if (!whole) {
-            tr.resize(t1 - t0); mk.resize((size_t)(t1 - t0) * pw);
-            HIP_TRY(c, hipMemcpy(tr.data(), s->d_trav.p + t0, tr.size() * sizeof(groot_trav), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(mk.data(), s->d_mask.p + (size_t)t0 * pw, mk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        }
-        const size_t o = whole ? t0 - lo : 0;
-        if (c->pairs_on && tm != t1) {
-            ec_set_of(c, tr.data() + o, mk.data() + o * pw, tm - t0, ids_a);
-            ec_set_of(c, tr.data() + o + (tm - t0), mk.data() + (o + (tm - t0)) * pw, t1 - tm, ids_b);
-            ids.clear();
-            std::set_intersection(ids_a.begin(), ids_a.end(), ids_b.begin(), ids_b.end(), std::back_inserter(ids));
-        } else {
-            ec_set_of(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids);
-        }
-        if (c->acov_on && !ids.empty() && t1 > t0) {
-            const uint32_t r = tr[o].read_id - s->first_read_id;
-            acov_fold_host(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids, offs[r + 1] - offs[r]);
-        }
-        if (!ids.empty()) c->ec_host[ids]++;
-    }
-    c->ec_slow_reads += n_slow;
-    return GROOT_OK;
-}
 
 // sketch+seed -> schedule (compute stream) | align -> order (align stream) for the batch of slot s
 static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
@@ -1319,50 +744,7 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
     if (int rc = launch_order_stage(c, s, update_weights)) return rc;
     if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[5], c->tstream));
     HIP_TRY(c, hipEventRecord(w->ev_free, c->tstream));
-    if (c->cov_on) {   // (reads the slot's records and read offsets only: the next batch's seed stage need not wait for it)
-        CovArgs ca{};
-        ca.trav = s->d_trav.p; ca.mask = s->d_mask.p; ca.seq_off = s->off(); ca.ctr = s->d_ctr.p;
-        ca.node_np_off = c->cov_np_off.p; ca.np = c->cov_np.p; ca.graph_path_off = c->cov_gpo.p; ca.path_len = c->cov_len.p; ca.slot_base = c->cov_base.p;
-        ca.starts = c->cov_starts.p; ca.ends = c->cov_ends.p;
-        ca.cap = s->trav_cap; ca.pw = c->pw_view; ca.first_read_id = s->first_read_id;
-        hipLaunchKernelGGL(cov_count_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream, ca);
-        HIP_TRY(c, hipGetLastError());
-    }
-    if (c->sh_on || c->ec_on) {    // (the same: slot data and the ctx's own buffers, in tail-stream order)
-        SharedArgs sa{};
-        sa.trav = s->d_trav.p; sa.mask = s->d_mask.p; sa.ctr = s->d_ctr.p; sa.graph_path_off = c->sh_gpo.p;
-        sa.set_graph = c->sh_set_graph.p; sa.set_mask = c->sh_set_mask.p; sa.tab_rep = c->sh_tab_rep.p; sa.tab_cnt = c->sh_tab_cnt.p;
-        sa.slow = c->sh_slow.p; sa.batch = c->sh_batch.p; sa.tri = c->sh_tri.p; sa.stats = c->sh_stats.p;
-        sa.cap = s->trav_cap; sa.pw = c->pw_view; sa.first_read_id = s->first_read_id; sa.n_paths = (uint32_t)c->h_cov_len.size();
-        sa.max_segs = c->kn.shared_slow ? 1u : kSharedSegs;
-        sa.pairs = c->sh_on;
-        sa.slow_cap = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-        uint32_t tab = 1;                  // this batch's part of the table: >= 2 n_reads slots
-        while (tab < 2u * std::max<uint32_t>(s->n_reads, 1u)) tab <<= 1;
-        sa.tab_mask = tab - 1;
-        const dim3 g(std::max<uint32_t>(1u, std::min<uint32_t>((s->trav_cap + kBlock - 1) / kBlock, 2048u)));
-        const bool paired = c->pairs_on;
-        if (paired) hipLaunchKernelGGL(shared_gather_paired_kernel, g, dim3(kBlock), 0, c->tstream, sa);
-        else hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->tstream, sa);
-        hipLaunchKernelGGL(shared_insert_kernel, g, dim3(kBlock), 0, c->tstream, sa);
-        if (c->sh_on && paired) hipLaunchKernelGGL(shared_slow_kernel<true>, dim3(256), dim3(kBlock), 0, c->tstream, sa);
-        else if (c->sh_on) hipLaunchKernelGGL(shared_slow_kernel<false>, dim3(256), dim3(kBlock), 0, c->tstream, sa);
-        if (c->ec_on) {
-            if (int rc = ec_reserve(c, s)) return rc;
-            HIP_TRY(c, s->d_ec_slow.reserve(1 + (paired ? 3 : 2) * (size_t)c->prm.max_batch_reads));
-            HIP_TRY(c, s->h_ec.reserve(4));
-            const dim3 gm(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u));
-            if (paired) hipLaunchKernelGGL(ec_merge_kernel<true>, gm, dim3(kBlock), 0, c->tstream, sa, ec_table(c), tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p, nullptr);
-            else hipLaunchKernelGGL(ec_merge_kernel<false>, gm, dim3(kBlock), 0, c->tstream, sa, ec_table(c), tab, ++c->ec_epoch, c->ec_fill.p, s->d_ec_slow.p,
-                                    c->acov_on ? c->acov_tab_ser.p : nullptr);
-            if (c->acov_on)
-                if (int rc = acov_launch(c, s, sa)) return rc;
-        }
-        const dim3 ge(std::min<uint32_t>((tab + kBlock - 1) / kBlock, 2048u));
-        if (paired) hipLaunchKernelGGL(shared_expand_kernel<true>, ge, dim3(kBlock), 0, c->tstream, sa, tab);
-        else hipLaunchKernelGGL(shared_expand_kernel<false>, ge, dim3(kBlock), 0, c->tstream, sa, tab);
-        HIP_TRY(c, hipGetLastError());
-    }
+    if (int rc = counters_launch(c, s)) return rc;   // (reads the slot's records and read offsets and the ctx's own buffers only: the next batch's seed stage need not wait for it)
     w->used = true;
     w->owner = s;
     w->ticket = s->ticket;
@@ -1544,14 +926,7 @@ static int enqueue(groot_ctx *c, Slot *s)
         HIP_TRY(c, hipMemcpyAsync(s->h_ckpt.p, s->d_ckpt.p, ((size_t)s->copied / 256 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
         if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev_d2h, c->d2h_stream));
     }
-    if (c->ec_on) {    // (ahead of the counters: there when they are)
-        HIP_TRY(c, hipMemcpyAsync(s->h_ec.p, s->d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-        HIP_TRY(c, hipMemcpyAsync(s->h_ec.p + 1, c->ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-        if (c->acov_on) {
-            HIP_TRY(c, hipMemcpyAsync(s->h_ec.p + 2, s->d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-            HIP_TRY(c, hipMemcpyAsync(s->h_ec.p + 3, c->acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-        }
-    }
+    if (int rc = counters_fetch(c, s)) return rc;   // (ahead of the counters: there when they are)
     HIP_TRY(c, hipMemcpyAsync(s->h_ctr.p, s->d_ctr.p, sizeof(DeviceCounters), hipMemcpyDeviceToHost, c->d2h_stream));
     HIP_TRY(c, hipEventRecord(s->ev_ctr, c->d2h_stream));
     s->state = Slot::IN_FLIGHT;
@@ -1653,11 +1028,7 @@ static int finish_counters(groot_ctx *c, Slot *s)
         } else h = again;
     }
     s->n_trav = s->n_reads ? h.n_trav : 0;
-    if (c->ec_on && s->n_reads) {
-        if (int rc = ec_collect(c, s, redone)) return rc;
-        if (c->acov_on)
-            if (int rc = acov_collect(c, s, redone)) return rc;
-    }
+    if (int rc = counters_collect(c, s, redone)) return rc;
     groot_counts &o = s->counts;
     o.received = s->n_reads;              // boss.go:194 receivedReads++ for every read
     o.mapped = h.mapped; o.multimapped = h.multimapped; o.alignments = h.alignments; o.seeds = h.seeds;
@@ -1815,7 +1186,9 @@ static int collect_impl(groot_ctx *c, Slot **out)
     return GROOT_OK;
 }
 
-static int drain(groot_ctx *c)     // everything submitted has finished on the device (results stay collectable)
+namespace groot {
+
+int drain(groot_ctx *c)     // everything submitted has finished on the device (results stay collectable)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->inflight.empty()) { if (int rc = progress(c, c->inflight.back())) return rc; }
@@ -1825,6 +1198,13 @@ static int drain(groot_ctx *c)     // everything submitted has finished on the d
     HIP_TRY(c, hipStreamSynchronize(c->d2h_stream));
     return GROOT_OK;
 }
+
+bool idle(const groot_ctx *c)
+{
+    return c->inflight.empty();
+}
+
+} // namespace groot
 
 // ---------------------------------------------------------------------------------------------
 // C ABI
@@ -2809,14 +2189,7 @@ static int open_impl(groot_ctx *c, int device_id, const groot_index_view *v, con
     c->h_node_graph.resize(v->n_nodes);
     for (uint32_t g = 0; g < v->n_graphs; g++)
         for (uint32_t nd = v->graph_node_off[g]; nd < v->graph_node_off[g + 1]; nd++) c->h_node_graph[nd] = g;
-    // (a view without graphs -- the sketch engine of `index --gpu` -- may carry no offset arrays at all)
-    if (v->node_np_off) c->h_cov_np_off.assign(v->node_np_off, v->node_np_off + v->n_nodes + 1); else c->h_cov_np_off.assign(v->n_nodes + 1, 0);
-    if (v->graph_path_off) c->h_cov_gpo.assign(v->graph_path_off, v->graph_path_off + v->n_graphs + 1); else c->h_cov_gpo.assign(v->n_graphs + 1, 0);
-    c->h_cov_len.assign(v->path_len, v->path_len + v->n_paths);
-    c->h_cov_np.resize(v->n_np);
-    for (uint64_t j = 0; j < v->n_np; j++) c->h_cov_np[j] = make_uint2(v->np_path[j], v->np_pos[j]);
-    c->h_cov_base.assign(v->n_paths + 1, 0);
-    for (uint32_t p = 0; p < v->n_paths; p++) c->h_cov_base[p + 1] = c->h_cov_base[p] + v->path_len[p] + 1;
+    counters_init(c, v);
     c->packed_travs = !c->prm.results_on_device && c->prm.max_batch_reads <= (1u << 24);
     {   // windows are numbered graph by graph (canonical seed order): the last window of every graph
         std::vector<uint32_t> end(v->n_graphs, 0);
@@ -3163,11 +2536,6 @@ int groot_hip_open_flags(groot_ctx **out, int device_id, const groot_index_view 
     return GROOT_OK;
 }
 
-static bool idle(const groot_ctx *c)
-{
-    return c->inflight.empty();
-}
-
 int groot_hip_set_stream(groot_ctx *c, void *hip_stream)
 {
     if (!c) return GROOT_E_INVALID;
@@ -3283,7 +2651,7 @@ static int check_exceptions(groot_ctx *c, const uint64_t *exc_pos, uint64_t n_ex
 // paired mode: a batch is whole fragments (checked by every submit before anything else is touched)
 static int pairs_check(groot_ctx *c, uint32_t n_reads)
 {
-    if (c->pairs_on && (n_reads & 1)) return fail(c, GROOT_E_INVALID, "pairing is on: a batch of %u reads is not whole fragments", n_reads);
+    if (c->ct.pairs_on && (n_reads & 1)) return fail(c, GROOT_E_INVALID, "pairing is on: a batch of %u reads is not whole fragments", n_reads);
     return GROOT_OK;
 }
 
@@ -3717,639 +3085,6 @@ int groot_hip_attempts_reset(groot_ctx *c)
     if (!c) return GROOT_E_INVALID;
     if (int rc = drain(c)) return rc;
     if (c->att_cap) HIP_TRY(c, hipMemset(c->attempts_ptr, 0, (size_t)c->att_cap * c->n_windows * sizeof(uint32_t)));
-    return GROOT_OK;
-}
-
-// ---- report coverage (kernels_cov.hpp) ------------------------------------------------------------------------------
-int groot_hip_coverage_enable(groot_ctx *c, int on)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "coverage can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!on) {
-        for (auto *b : {&c->cov_np_off, &c->cov_gpo, &c->cov_len}) b->release();
-        c->cov_np.release(); c->cov_base.release(); c->cov_starts.release(); c->cov_ends.release();
-        c->cov_on = false;
-        return GROOT_OK;
-    }
-    if (c->cov_on) return GROOT_OK;
-    const uint64_t slots = c->h_cov_base.back();
-    HIP_TRY(c, upload(c->cov_np_off, c->h_cov_np_off.data(), c->h_cov_np_off.size()));
-    HIP_TRY(c, upload(c->cov_gpo, c->h_cov_gpo.data(), c->h_cov_gpo.size()));
-    HIP_TRY(c, upload(c->cov_len, c->h_cov_len.data(), c->h_cov_len.size()));
-    HIP_TRY(c, upload(c->cov_np, c->h_cov_np.data(), c->h_cov_np.size()));
-    HIP_TRY(c, upload(c->cov_base, c->h_cov_base.data(), c->h_cov_base.size()));
-    HIP_TRY(c, c->cov_starts.alloc(slots));
-    HIP_TRY(c, c->cov_ends.alloc(slots));
-    HIP_TRY(c, hipMemset(c->cov_starts.p, 0, std::max<uint64_t>(slots, 1) * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(c->cov_ends.p, 0, std::max<uint64_t>(slots, 1) * sizeof(unsigned long long)));
-    c->cov_on = true;
-    return GROOT_OK;
-}
-
-int groot_hip_coverage_export(groot_ctx *c, uint64_t *records, uint64_t *depth)
-{
-    if (!c || (!c->h_cov_len.empty() && (!records || !depth))) return GROOT_E_INVALID;
-    if (!c->cov_on) return fail(c, GROOT_E_STATE, "coverage is not enabled (groot_hip_coverage_enable)");
-    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo, if they need one)
-    const uint64_t slots = c->h_cov_base.back();
-    std::vector<uint64_t> st(slots), en(slots);
-    if (slots) {
-        HIP_TRY(c, hipMemcpy(st.data(), c->cov_starts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(en.data(), c->cov_ends.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    uint64_t at = 0;
-    for (size_t p = 0; p < c->h_cov_len.size(); p++) {
-        const uint64_t b = c->h_cov_base[p], len = c->h_cov_len[p];
-        uint64_t n = 0, d = 0;
-        for (uint64_t i = 0; i < len; i++) {
-            n += st[b + i];
-            d += st[b + i] - en[b + i];
-            depth[at++] = d;
-        }
-        records[p] = n + st[b + len];
-    }
-    return GROOT_OK;
-}
-
-int groot_hip_coverage_reset(groot_ctx *c)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->cov_on) return GROOT_OK;
-    if (int rc = drain(c)) return rc;
-    const uint64_t slots = std::max<uint64_t>(c->h_cov_base.back(), 1);
-    HIP_TRY(c, hipMemset(c->cov_starts.p, 0, slots * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(c->cov_ends.p, 0, slots * sizeof(unsigned long long)));
-    return GROOT_OK;
-}
-
-// ---- shared reads (kernels_shared.hpp) -------------------------------------------------------------------------------
-static uint64_t shared_tri_size(uint64_t n_paths) { return n_paths * (n_paths + 1) / 2; }
-
-// the per-batch buffers shared reads and equivalence classes both use (allocated while either is on)
-static void sh_common_release(groot_ctx *c)
-{
-    for (auto *b : {&c->sh_gpo, &c->sh_set_graph, &c->sh_tab_rep, &c->sh_tab_cnt, &c->sh_slow, &c->sh_batch}) b->release();
-    c->sh_set_mask.release(); c->sh_stats.release();
-}
-
-static hipError_t sh_common_alloc(groot_ctx *c)
-{
-    if (c->sh_on || c->ec_on) return hipSuccess;
-    const uint32_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-    const uint64_t tab = c->sh_tab_cap;
-    hipError_t e = upload(c->sh_gpo, c->h_cov_gpo.data(), c->h_cov_gpo.size());
-    if (e == hipSuccess) e = c->sh_set_graph.alloc((size_t)R * kSharedSegs);
-    if (e == hipSuccess) e = c->sh_set_mask.alloc((size_t)R * kSharedSegs * std::max<uint32_t>(c->pw_view, 1u));
-    if (e == hipSuccess) e = c->sh_tab_rep.alloc(tab);
-    if (e == hipSuccess) e = c->sh_tab_cnt.alloc(tab);
-    if (e == hipSuccess) e = c->sh_slow.alloc(R);
-    if (e == hipSuccess) e = c->sh_batch.alloc(kSharedBatch);
-    if (e == hipSuccess) e = c->sh_stats.alloc(kSharedStats);
-    if (e == hipSuccess) e = hipMemset(c->sh_tab_rep.p, 0xFF, tab * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(c->sh_tab_cnt.p, 0, tab * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(c->sh_batch.p, 0, kSharedBatch * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, kSharedStats * sizeof(unsigned long long));
-    return e;
-}
-
-static int sh_table_size(groot_ctx *c, const char *what)
-{
-    const uint32_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-    uint64_t tab = 1;
-    while (tab < 2ull * R) tab <<= 1;
-    if (tab > (1ull << 31)) return fail(c, GROOT_E_UNSUPPORTED, "%s: max_batch_reads=%u is above 2^30", what, R);
-    c->sh_tab_cap = (uint32_t)tab;
-    return GROOT_OK;
-}
-
-int groot_hip_shared_enable(groot_ctx *c, int on)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "shared reads can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!on) {
-        c->sh_tri.release();
-        c->sh_on = false;
-        if (!c->ec_on) sh_common_release(c);
-        return GROOT_OK;
-    }
-    if (c->sh_on) return GROOT_OK;
-    const uint64_t n_paths = c->h_cov_len.size(), tri = shared_tri_size(n_paths);
-    if (tri * sizeof(uint64_t) > GROOT_SHARED_MAX_BYTES)
-        return fail(c, GROOT_E_UNSUPPORTED, "shared reads: %llu paths need a %llu MiB pair table, above the bound of %llu MiB", (unsigned long long)n_paths,
-                    (unsigned long long)(tri * sizeof(uint64_t) >> 20), (unsigned long long)(GROOT_SHARED_MAX_BYTES >> 20));
-    if (!c->ec_on)
-        if (int rc = sh_table_size(c, "shared reads")) return rc;
-    auto undo = [&](int rc) { c->sh_on = true; groot_hip_shared_enable(c, 0); return rc; };
-    hipError_t e = sh_common_alloc(c);
-    if (e == hipSuccess) e = c->sh_tri.alloc(tri);
-    if (e == hipSuccess) e = hipMemset(c->sh_tri.p, 0, std::max<uint64_t>(tri, 1) * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(c->sh_stats.p, 0, kSharedStats * sizeof(unsigned long long));
-    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "shared reads: %s", hipGetErrorString(e)));
-    c->sh_on = true;
-    return GROOT_OK;
-}
-
-int groot_hip_shared_export(groot_ctx *c, uint32_t *pa, uint32_t *pb, uint64_t *count, uint64_t cap, uint64_t *n_pairs)
-{
-    if (!c || !n_pairs || (cap && (!pa || !pb || !count))) return GROOT_E_INVALID;
-    if (!c->sh_on) return fail(c, GROOT_E_STATE, "shared reads are not enabled (groot_hip_shared_enable)");
-    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo, if they need one)
-    const uint64_t P = c->h_cov_len.size(), tri = shared_tri_size(P);
-    std::vector<uint64_t> t(tri);
-    if (tri) HIP_TRY(c, hipMemcpy(t.data(), c->sh_tri.p, tri * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    uint64_t n = 0, i = 0;
-    for (uint64_t x = 0; x < P; x++)
-        for (uint64_t y = x; y < P; y++, i++) {
-            if (!t[i]) continue;
-            if (n < cap) { pa[n] = (uint32_t)x; pb[n] = (uint32_t)y; count[n] = t[i]; }
-            n++;
-        }
-    *n_pairs = n;
-    return GROOT_OK;
-}
-
-int groot_hip_shared_stats(groot_ctx *c, uint64_t *reads, uint64_t *distinct_sets, uint64_t *slow_reads)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->sh_on) return fail(c, GROOT_E_STATE, "shared reads are not enabled (groot_hip_shared_enable)");
-    if (int rc = drain(c)) return rc;
-    uint64_t st[3];
-    HIP_TRY(c, hipMemcpy(st, c->sh_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    if (reads) *reads = st[0];
-    if (distinct_sets) *distinct_sets = st[1];
-    if (slow_reads) *slow_reads = st[2];
-    return GROOT_OK;
-}
-
-int groot_hip_shared_reset(groot_ctx *c)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->sh_on) return GROOT_OK;
-    if (int rc = drain(c)) return rc;
-    HIP_TRY(c, hipMemset(c->sh_tri.p, 0, std::max<uint64_t>(shared_tri_size(c->h_cov_len.size()), 1) * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(c->sh_stats.p, 0, kSharedStats * sizeof(unsigned long long)));
-    return GROOT_OK;
-}
-
-// ---- equivalence classes (kernels_ec.hpp) ---------------------------------------------------------------------------
-int groot_hip_ec_enable(groot_ctx *c, int on)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "equivalence classes can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!on) {
-        if (c->acov_on)
-            if (int rc = groot_hip_acov_enable(c, 0)) return rc;     // (its tuples are keyed by this table's serials)
-        for (auto *b : {&c->ec_claim, &c->ec_graph, &c->ec_fill, &c->ec_serial}) b->release();
-        c->ec_mask.release(); c->ec_cnt.release();
-        c->ec_host.clear();
-        c->ec_on = false;
-        c->ec_cap = 0;
-        if (!c->sh_on) sh_common_release(c);
-        return GROOT_OK;
-    }
-    if (c->ec_on) return GROOT_OK;
-    if (!c->sh_on)
-        if (int rc = sh_table_size(c, "equivalence classes")) return rc;
-    uint32_t cap = 1;
-    while (cap < (c->kn.ec_slots ? std::max<uint32_t>(c->kn.ec_slots, 2u) : (1u << 16))) cap <<= 1;
-    auto undo = [&](int rc) { c->ec_on = true; groot_hip_ec_enable(c, 0); return rc; };
-    hipError_t e = sh_common_alloc(c);
-    if (e == hipSuccess) e = ec_alloc(c, cap, c->ec_claim, c->ec_graph, c->ec_mask, c->ec_cnt, c->ec_serial, c->tstream);
-    if (e == hipSuccess) e = c->ec_fill.alloc(1);
-    if (e == hipSuccess) e = hipMemsetAsync(c->ec_fill.p, 0, sizeof(uint32_t), c->tstream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->tstream);
-    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "equivalence classes: %s", hipGetErrorString(e)));
-    c->ec_cap = cap;
-    c->ec_fill_known = c->ec_grows = c->ec_slow_reads = 0;
-    c->ec_host.clear();
-    c->ec_on = true;
-    return GROOT_OK;
-}
-
-// the device table and the host map merged: S -> reads, in canonical order (lexicographic on the ascending ID lists)
-// by_serial (optional): the ID list of every slot of the device table, by the slot's serial
-static int ec_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &out, std::vector<std::vector<uint32_t>> *by_serial = nullptr)
-{
-    if (int rc = drain(c)) return rc;     // (the batches in flight through their redo and their slow-path reads)
-    uint32_t fill = 0;
-    HIP_TRY(c, hipMemcpy(&fill, c->ec_fill.p, sizeof fill, hipMemcpyDeviceToHost));
-    out = c->ec_host;
-    if (!fill) return GROOT_OK;
-    const uint32_t pw = std::max<uint32_t>(c->pw_view, 1u);
-    DevBuf<uint32_t> g, n, ser;
-    DevBuf<uint64_t> m;
-    DevBuf<unsigned long long> cnt;
-    HIP_TRY(c, ser.alloc(fill));
-    HIP_TRY(c, g.alloc((size_t)fill * kSharedSegs));
-    HIP_TRY(c, m.alloc((size_t)fill * kSharedSegs * pw));
-    HIP_TRY(c, cnt.alloc(fill));
-    HIP_TRY(c, n.alloc(1));
-    HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->tstream));
-    hipLaunchKernelGGL(ec_export_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->ec_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
-                       ec_table(c), c->ec_cap, pw, g.p, m.p, cnt.p, ser.p, n.p, fill);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->tstream));
-    uint32_t got = 0;
-    HIP_TRY(c, hipMemcpy(&got, n.p, sizeof got, hipMemcpyDeviceToHost));
-    if (got != fill) return fail(c, GROOT_E_DEVICE, "equivalence classes: %u keys in a table that counted %u", got, fill);
-    std::vector<uint32_t> hg((size_t)fill * kSharedSegs);
-    std::vector<uint64_t> hm((size_t)fill * kSharedSegs * pw), hc(fill);
-    HIP_TRY(c, hipMemcpy(hg.data(), g.p, hg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hm.data(), m.p, hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hc.data(), cnt.p, hc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> hs(fill);
-    HIP_TRY(c, hipMemcpy(hs.data(), ser.p, hs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (by_serial) by_serial->assign(fill, {});
-    std::vector<groot_trav> tr;
-    std::vector<uint64_t> mk;
-    std::vector<uint32_t> ids;
-    for (uint32_t i = 0; i < fill; i++) {
-        // a key = one pseudo-record per segment: (graph, OR of its path sets)
-        tr.clear(); mk.clear();
-        for (uint32_t k = 0; k < kSharedSegs && hg[(size_t)i * kSharedSegs + k] != kSharedEmpty; k++) {
-            groot_trav t{};
-            t.graph_id = hg[(size_t)i * kSharedSegs + k];
-            tr.push_back(t);
-            for (uint32_t w = 0; w < pw; w++) mk.push_back(hm[((size_t)i * kSharedSegs + k) * pw + w]);
-        }
-        ec_set_of(c, tr.data(), mk.data(), tr.size(), ids);
-        if (!ids.empty() && hc[i]) out[ids] += hc[i];
-        if (by_serial && hs[i] < fill) (*by_serial)[hs[i]] = ids;
-    }
-    return GROOT_OK;
-}
-
-int groot_hip_ec_export(groot_ctx *c, uint64_t *off, uint32_t *ids, uint64_t *count, uint64_t cap_ec, uint64_t cap_ids, uint64_t *n_ec, uint64_t *n_ids)
-{
-    if (!c || !n_ec || !n_ids || (cap_ec && (!off || !count)) || (cap_ids && !ids)) return GROOT_E_INVALID;
-    if (!c->ec_on) return fail(c, GROOT_E_STATE, "equivalence classes are not enabled (groot_hip_ec_enable)");
-    std::map<std::vector<uint32_t>, uint64_t> m;
-    if (int rc = ec_gather(c, m)) return rc;
-    uint64_t ni = 0;
-    for (const auto &kv : m) ni += kv.first.size();
-    *n_ec = m.size();
-    *n_ids = ni;
-    if (!cap_ec && !cap_ids) return GROOT_OK;
-    if (cap_ec < m.size() || cap_ids < ni)
-        return fail(c, GROOT_E_NOSPACE, "equivalence classes: room for %llu classes / %llu IDs, %llu / %llu needed", (unsigned long long)cap_ec,
-                    (unsigned long long)cap_ids, (unsigned long long)m.size(), (unsigned long long)ni);
-    uint64_t e = 0, at = 0;
-    off[0] = 0;
-    for (const auto &kv : m) {
-        for (uint32_t x : kv.first) ids[at++] = x;
-        count[e] = kv.second;
-        off[++e] = at;
-    }
-    return GROOT_OK;
-}
-
-int groot_hip_ec_stats(groot_ctx *c, uint64_t *reads, uint64_t *distinct, uint64_t *slow_reads, uint64_t *grows)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->ec_on) return fail(c, GROOT_E_STATE, "equivalence classes are not enabled (groot_hip_ec_enable)");
-    std::map<std::vector<uint32_t>, uint64_t> m;
-    if (int rc = ec_gather(c, m)) return rc;
-    uint64_t r = 0;
-    for (const auto &kv : m) r += kv.second;
-    if (reads) *reads = r;
-    if (distinct) *distinct = m.size();
-    if (slow_reads) *slow_reads = c->ec_slow_reads;
-    if (grows) *grows = c->ec_grows;
-    return GROOT_OK;
-}
-
-int groot_hip_ec_reset(groot_ctx *c)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->ec_on) return GROOT_OK;
-    if (int rc = drain(c)) return rc;
-    HIP_TRY(c, hipMemset(c->ec_claim.p, 0, (size_t)c->ec_cap * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemset(c->ec_fill.p, 0, sizeof(uint32_t)));
-    c->ec_fill_known = c->ec_grows = c->ec_slow_reads = 0;
-    c->ec_host.clear();
-    if (c->pairs_on) HIP_TRY(c, hipMemset(c->sh_stats.p + 3, 0, (kSharedStats - 3) * sizeof(unsigned long long)));
-    return groot_hip_acov_reset(c);     // (the serials start again: its tuples would name other classes)
-}
-
-// ---- assigned coverage (kernels_acov.hpp; the definition is in groot_hip.h) ------------------------------------------------
-int groot_hip_acov_enable(groot_ctx *c, int on)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "assigned coverage can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!on) {
-        for (auto *b : {&c->acov_k0, &c->acov_k1, &c->acov_cnt}) b->release();
-        for (auto *b : {&c->acov_fill, &c->acov_err, &c->acov_tab_ser, &c->acov_np_off, &c->acov_len}) b->release();
-        c->acov_np.release();
-        c->acov_host.clear();
-        c->acov_on = false;
-        c->acov_cap = 0;
-        return GROOT_OK;
-    }
-    if (c->acov_on) return GROOT_OK;
-    if (c->pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "assigned coverage with paired-end units is not supported");
-    if (int rc = groot_hip_ec_enable(c, 1)) return rc;
-    uint32_t cap = 1;
-    while (cap < (c->kn.acov_slots ? std::max<uint32_t>(c->kn.acov_slots, 2u) : (1u << 20))) cap <<= 1;
-    auto undo = [&](int rc) { c->acov_on = true; groot_hip_acov_enable(c, 0); return rc; };
-    hipError_t e = acov_alloc(cap, c->acov_k0, c->acov_k1, c->acov_cnt, c->tstream);
-    if (e == hipSuccess) e = c->acov_fill.alloc(1);
-    if (e == hipSuccess) e = c->acov_err.alloc(1);
-    if (e == hipSuccess) e = c->acov_tab_ser.alloc(c->sh_tab_cap);
-    if (e == hipSuccess) e = hipMemsetAsync(c->acov_fill.p, 0, sizeof(uint32_t), c->tstream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->acov_err.p, 0, sizeof(uint32_t), c->tstream);
-    if (e == hipSuccess) e = upload(c->acov_np_off, c->h_cov_np_off.data(), c->h_cov_np_off.size());
-    if (e == hipSuccess) e = upload(c->acov_len, c->h_cov_len.data(), c->h_cov_len.size());
-    if (e == hipSuccess) e = upload(c->acov_np, c->h_cov_np.data(), c->h_cov_np.size());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->tstream);
-    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "assigned coverage: %s", hipGetErrorString(e)));
-    c->acov_cap = cap;
-    c->acov_grows = c->acov_slow_records = c->acov_redone = 0;
-    c->acov_host.clear();
-    c->acov_on = true;
-    return GROOT_OK;
-}
-
-namespace {
-struct AcovTuple {
-    uint32_t ec, path, pos, last;
-    uint64_t n;
-    bool operator<(const AcovTuple &o) const { return std::tie(ec, path, pos, last) < std::tie(o.ec, o.path, o.pos, o.last); }
-    bool same_key(const AcovTuple &o) const { return ec == o.ec && path == o.path && pos == o.pos && last == o.last; }
-};
-}
-
-// the ctx's ECs in canonical order and its tuples, EC = index into that list, ascending, equal keys of the device table and the host
-// map summed
-static int acov_gather(groot_ctx *c, std::map<std::vector<uint32_t>, uint64_t> &ecs, std::vector<AcovTuple> &out)
-{
-    std::vector<std::vector<uint32_t>> by_serial;
-    if (int rc = ec_gather(c, ecs, &by_serial)) return rc;
-    out.clear();
-    std::map<std::vector<uint32_t>, uint32_t> index;
-    for (const auto &kv : ecs) { const uint32_t i = (uint32_t)index.size(); index[kv.first] = i; }
-    uint32_t fill = 0;
-    HIP_TRY(c, hipMemcpy(&fill, c->acov_fill.p, sizeof fill, hipMemcpyDeviceToHost));
-    if (fill) {
-        std::vector<uint32_t> ser_idx(by_serial.size(), ~0u);
-        for (size_t i = 0; i < by_serial.size(); i++) {
-            auto it = index.find(by_serial[i]);
-            if (it != index.end()) ser_idx[i] = it->second;
-        }
-        DevBuf<unsigned long long> key, cnt;
-        DevBuf<uint32_t> n;
-        HIP_TRY(c, key.alloc(2 * (size_t)fill));
-        HIP_TRY(c, cnt.alloc(fill));
-        HIP_TRY(c, n.alloc(1));
-        HIP_TRY(c, hipMemsetAsync(n.p, 0, sizeof(uint32_t), c->tstream));
-        hipLaunchKernelGGL(acov_export_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((c->acov_cap + kBlock - 1) / kBlock, 2048u))), dim3(kBlock), 0, c->tstream,
-                           acov_table(c), c->acov_cap, key.p, cnt.p, n.p, fill);
-        c->acov_launches++;
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->tstream));
-        uint32_t got = 0;
-        HIP_TRY(c, hipMemcpy(&got, n.p, sizeof got, hipMemcpyDeviceToHost));
-        if (got > fill) return fail(c, GROOT_E_DEVICE, "assigned coverage: %u tuples in a table that counted %u", got, fill);
-        std::vector<uint64_t> hk(2 * (size_t)got), hc(got);
-        if (got) {
-            HIP_TRY(c, hipMemcpy(hk.data(), key.p, hk.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(hc.data(), cnt.p, hc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        }
-        out.reserve(got);
-        for (uint32_t i = 0; i < got; i++) {
-            const uint64_t ser = (hk[2 * (size_t)i] >> 32) - 1;
-            if (ser >= ser_idx.size() || ser_idx[ser] == ~0u) return fail(c, GROOT_E_DEVICE, "assigned coverage: a tuple names class %llu, which the table of classes does not hold", (unsigned long long)ser);
-            out.push_back(AcovTuple{ser_idx[ser], (uint32_t)hk[2 * (size_t)i], (uint32_t)(hk[2 * (size_t)i + 1] >> 32), (uint32_t)hk[2 * (size_t)i + 1], hc[i]});
-        }
-    }
-    for (const auto &kv : c->acov_host) {
-        auto it = index.find(kv.first);
-        if (it == index.end()) return fail(c, GROOT_E_DEVICE, "assigned coverage: the host map holds a class the table of classes does not");
-        for (const auto &t : kv.second) out.push_back(AcovTuple{it->second, t.first[0], t.first[1], t.first[2], t.second});
-    }
-    std::sort(out.begin(), out.end());
-    size_t w = 0;
-    for (size_t i = 0; i < out.size(); i++) {
-        if (w && out[w - 1].same_key(out[i])) out[w - 1].n += out[i].n;
-        else out[w++] = out[i];
-    }
-    out.resize(w);
-    return GROOT_OK;
-}
-
-int groot_hip_acov_export(groot_ctx *c, uint64_t *ec_off, uint32_t *ec_ids, uint64_t *ec_count, uint32_t *tuples, uint64_t *n, uint64_t cap_ec, uint64_t cap_ids,
-                          uint64_t cap_tuples, uint64_t *n_ec, uint64_t *n_ids, uint64_t *n_tuples)
-{
-    if (!c || !n_ec || !n_ids || !n_tuples || (cap_ec && (!ec_off || !ec_count)) || (cap_ids && !ec_ids) || (cap_tuples && (!tuples || !n))) return GROOT_E_INVALID;
-    if (!c->acov_on) return fail(c, GROOT_E_STATE, "assigned coverage is not enabled (groot_hip_acov_enable)");
-    std::map<std::vector<uint32_t>, uint64_t> m;
-    std::vector<AcovTuple> tp;
-    if (int rc = acov_gather(c, m, tp)) return rc;
-    uint64_t ni = 0;
-    for (const auto &kv : m) ni += kv.first.size();
-    *n_ec = m.size();
-    *n_ids = ni;
-    *n_tuples = tp.size();
-    if (!cap_ec && !cap_ids && !cap_tuples) return GROOT_OK;
-    if (cap_ec < m.size() || cap_ids < ni || cap_tuples < tp.size())
-        return fail(c, GROOT_E_NOSPACE, "assigned coverage: room for %llu classes / %llu IDs / %llu tuples, %llu / %llu / %llu needed", (unsigned long long)cap_ec,
-                    (unsigned long long)cap_ids, (unsigned long long)cap_tuples, (unsigned long long)m.size(), (unsigned long long)ni, (unsigned long long)tp.size());
-    uint64_t e = 0, at = 0;
-    if (ec_off) ec_off[0] = 0;
-    for (const auto &kv : m) {
-        for (uint32_t x : kv.first) ec_ids[at++] = x;
-        ec_count[e] = kv.second;
-        ec_off[++e] = at;
-    }
-    for (size_t i = 0; i < tp.size(); i++) {
-        tuples[4 * i] = tp[i].ec; tuples[4 * i + 1] = tp[i].path; tuples[4 * i + 2] = tp[i].pos; tuples[4 * i + 3] = tp[i].last;
-        n[i] = tp[i].n;
-    }
-    return GROOT_OK;
-}
-
-int groot_hip_acov_stats(groot_ctx *c, uint64_t *records, uint64_t *tuples, uint64_t *slots, uint64_t *grows, uint64_t *slow_records, uint64_t *launches)
-{
-    if (!c) return GROOT_E_INVALID;
-    uint64_t r = 0, nt = 0;
-    if (c->acov_on) {
-        std::map<std::vector<uint32_t>, uint64_t> m;
-        std::vector<AcovTuple> tp;
-        if (int rc = acov_gather(c, m, tp)) return rc;
-        for (const auto &t : tp) r += t.n;
-        nt = tp.size();
-    }
-    if (records) *records = r;
-    if (tuples) *tuples = nt;
-    if (slots) *slots = c->acov_on ? c->acov_cap : 0;
-    if (grows) *grows = c->acov_on ? c->acov_grows : 0;
-    if (slow_records) *slow_records = c->acov_on ? c->acov_slow_records : 0;
-    if (launches) *launches = c->acov_launches;
-    return GROOT_OK;
-}
-
-int groot_hip_acov_reset(groot_ctx *c)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->acov_on) return GROOT_OK;
-    if (int rc = drain(c)) return rc;
-    HIP_TRY(c, hipMemset(c->acov_k0.p, 0, (size_t)c->acov_cap * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(c->acov_k1.p, 0xFF, (size_t)c->acov_cap * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(c->acov_cnt.p, 0, (size_t)c->acov_cap * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(c->acov_fill.p, 0, sizeof(uint32_t)));
-    c->acov_grows = c->acov_slow_records = c->acov_redone = 0;
-    c->acov_host.clear();
-    return GROOT_OK;
-}
-
-// ---- paired-end reads (the kPaired kernels of kernels_shared.hpp; the definition is in groot_hip.h) -------------------------
-int groot_hip_pairs_enable(groot_ctx *c, int on)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "pairing can only be switched while nothing is in flight");
-    if (on && c->acov_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assigned coverage are not supported");
-    c->pairs_on = on != 0;
-    if (c->sh_on || c->ec_on) {     // (else there is nothing to zero: sh_common_alloc zeroes the counts when either comes on)
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipMemset(c->sh_stats.p + 3, 0, (kSharedStats - 3) * sizeof(unsigned long long)));
-    }
-    return GROOT_OK;
-}
-
-int groot_hip_pairs_stats(groot_ctx *c, uint64_t *joined, uint64_t *split, uint64_t *single)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->pairs_on) return fail(c, GROOT_E_STATE, "pairing is not enabled (groot_hip_pairs_enable)");
-    if (int rc = drain(c)) return rc;
-    uint64_t st[kSharedStats] = {};
-    if (c->sh_on || c->ec_on) HIP_TRY(c, hipMemcpy(st, c->sh_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    if (joined) *joined = st[3];
-    if (split) *split = st[4];
-    if (single) *single = st[5];
-    return GROOT_OK;
-}
-
-// ---- bootstrap replicates of the abundance EM (kernels_boot.hpp; the contract is in groot_host.h) ---------------------------
-namespace {
-struct DeviceGuard {         // the calling thread's current device, put back on return
-    int prev = -1;
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-};
-constexpr size_t kBootChunkBytes = 256u << 20;      // device memory of one chunk of replicates (counts + alpha)
-constexpr uint32_t kBootDrawGroups = 2048;          // workgroups of one boot_resample_kernel launch, about
-} // namespace
-
-int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_boot,
-                           uint64_t seed, uint64_t n_draws, uint32_t min_iter, uint32_t max_iter, uint64_t *boot_count, double *alpha, uint32_t *iterations)
-{
-    if ((n_ec && (!off || !count)) || (n_paths && !alpha)) return fail(nullptr, GROOT_E_INVALID, "null argument");
-    if (n_boot == 0) return fail(nullptr, GROOT_E_INVALID, "no bootstrap replicates");
-    if (max_iter < min_iter)
-        return fail(nullptr, GROOT_E_INVALID, "number of EM iterations (%u) must be greater than minimum iterations (%u)", max_iter, min_iter);
-    if (max_iter < 1) return fail(nullptr, GROOT_E_INVALID, "no EM iterations were ran");
-    if (n_ec >= 0xFFFFFFFFull || (n_ec && off[n_ec] >= 0xFFFFFFFFull))
-        return fail(nullptr, GROOT_E_UNSUPPORTED, "bootstrap on the device: 2^32 ECs or path IDs and more");
-    const uint32_t ne = (uint32_t)n_ec;
-    std::vector<uint64_t> cum((size_t)ne + 1, 0);
-    std::vector<uint32_t> ec_off((size_t)ne + 1, 0), path_off((size_t)n_paths + 1, 0);
-    for (uint32_t e = 0; e < ne; e++) {
-        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return fail(nullptr, GROOT_E_INVALID, "EC %u: bad offsets", e);
-        for (uint64_t i = off[e]; i < off[e + 1]; i++) {
-            if (ids[i] >= n_paths) return fail(nullptr, GROOT_E_INVALID, "EC %u holds path %u of %u", e, ids[i], n_paths);
-            path_off[ids[i] + 1]++;
-        }
-        ec_off[e + 1] = ec_off[e] + (uint32_t)(off[e + 1] - off[e]);
-        cum[e + 1] = cum[e] + count[e];
-        if (cum[e + 1] < cum[e]) return fail(nullptr, GROOT_E_INVALID, "the EC counts sum to 2^64 or more");
-    }
-    const uint64_t total = cum[ne];
-    if (ne && total == 0) return fail(nullptr, GROOT_E_INVALID, "bootstrap over ECs without reads");
-    if (n_draws == 0) n_draws = total;
-    // path -> EC, CSR: the ECs are visited in order, so every path's list ascends (an ID an EC names twice is listed twice, as the host adds it twice)
-    const uint32_t nnz = ec_off[ne];
-    for (uint32_t p = 0; p < n_paths; p++) path_off[p + 1] += path_off[p];
-    std::vector<uint32_t> ec_ids(std::max<uint32_t>(nnz, 1u)), path_ecs(std::max<uint32_t>(nnz, 1u)), at(path_off.begin(), path_off.end() - 1);
-    for (uint32_t e = 0; e < ne; e++)
-        for (uint64_t i = off[e]; i < off[e + 1]; i++) {
-            ec_ids[ec_off[e] + (i - off[e])] = ids[i];
-            path_ecs[at[ids[i]]++] = e;
-        }
-
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(nullptr, GROOT_E_DEVICE, "no HIP device");
-    if (device < 0 || device >= n_dev) return fail(nullptr, GROOT_E_DEVICE, "device %d of %d", device, n_dev);
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    HIP_TRY(nullptr, hipSetDevice(device));
-    int lds_max = 0, n_cu = 0;
-    HIP_TRY(nullptr, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
-    HIP_TRY(nullptr, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
-    n_cu = std::max(n_cu, 1);
-    StreamGuard sg;
-    HIP_TRY(nullptr, hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    hipStream_t st = sg.s;
-
-    const size_t per_rep = ((size_t)ne + n_paths) * 8;
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)n_boot, (size_t)65535, kBootChunkBytes / std::max<size_t>(per_rep, 1)}));
-    DevBuf<uint64_t> d_cum;
-    DevBuf<uint32_t> d_ec_off, d_ec_ids, d_path_off, d_path_ecs, d_it;
-    DevBuf<unsigned long long> d_cnt;
-    DevBuf<double> d_alpha, d_scratch;
-    HIP_TRY(nullptr, d_cum.alloc(cum.size()));
-    HIP_TRY(nullptr, d_ec_off.alloc(ec_off.size()));
-    HIP_TRY(nullptr, d_ec_ids.alloc(ec_ids.size()));
-    HIP_TRY(nullptr, d_path_off.alloc(path_off.size()));
-    HIP_TRY(nullptr, d_path_ecs.alloc(path_ecs.size()));
-    HIP_TRY(nullptr, d_cnt.alloc((size_t)chunk * ne));
-    HIP_TRY(nullptr, d_alpha.alloc((size_t)chunk * n_paths));
-    HIP_TRY(nullptr, d_it.alloc(chunk));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_cum.p, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_ec_off.p, ec_off.data(), ec_off.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_ec_ids.p, ec_ids.data(), ec_ids.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_path_off.p, path_off.data(), path_off.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_path_ecs.p, path_ecs.data(), path_ecs.size() * 4, hipMemcpyHostToDevice, st));
-
-    // LDS or global memory: the cumulative table and the histogram of the draws; alpha and norm of the EM
-    const size_t draw_lds = ((size_t)ne + 1) * 8 + (size_t)ne * 4, em_lds = per_rep;
-    const bool draw_in_lds = draw_lds <= (size_t)lds_max, em_in_lds = em_lds <= (size_t)lds_max;
-    if (draw_in_lds && draw_lds > 48 * 1024)
-        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_resample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)draw_lds));
-    if (em_in_lds && em_lds > 48 * 1024)
-        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_em_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
-    const uint32_t em_grid = std::min<uint32_t>(chunk, (uint32_t)n_cu);
-    if (!em_in_lds) HIP_TRY(nullptr, d_scratch.alloc((size_t)em_grid * ((size_t)ne + n_paths)));
-
-    constexpr uint64_t kChunkDraws = (uint64_t)kBootDrawBlock * kBootDrawsPerThread;
-    const uint64_t draw_chunks = (n_draws + kChunkDraws - 1) / kChunkDraws;
-    for (uint32_t b0 = 0; b0 < n_boot; b0 += chunk) {
-        const uint32_t nb = std::min(chunk, n_boot - b0);
-        if (ne) {
-            HIP_TRY(nullptr, hipMemsetAsync(d_cnt.p, 0, (size_t)nb * ne * 8, st));
-            if (draw_chunks) {
-                BootDrawArgs da{d_cum.p, d_cnt.p, total, n_draws, seed, ne, b0};
-                const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(draw_chunks, (kBootDrawGroups + nb - 1) / nb)), nb);
-                if (draw_in_lds) hipLaunchKernelGGL(boot_resample_kernel<true>, grid, dim3(kBootDrawBlock), draw_lds, st, da);
-                else hipLaunchKernelGGL(boot_resample_kernel<false>, grid, dim3(kBootDrawBlock), 0, st, da);
-                HIP_TRY(nullptr, hipGetLastError());
-            }
-        }
-        BootEmArgs ea{d_ec_off.p, d_ec_ids.p, d_path_off.p, d_path_ecs.p, d_cnt.p, d_alpha.p, d_it.p, d_scratch.p, 1.0 / (double)n_paths, n_paths, ne, nb, min_iter, max_iter};
-        const dim3 grid(std::min<uint32_t>(nb, em_grid));
-        if (em_in_lds) hipLaunchKernelGGL(boot_em_kernel<true>, grid, dim3(kBootEmBlock), em_lds, st, ea);
-        else hipLaunchKernelGGL(boot_em_kernel<false>, grid, dim3(kBootEmBlock), 0, st, ea);
-        HIP_TRY(nullptr, hipGetLastError());
-        if (boot_count && ne) HIP_TRY(nullptr, hipMemcpyAsync(boot_count + (size_t)b0 * ne, d_cnt.p, (size_t)nb * ne * 8, hipMemcpyDeviceToHost, st));
-        if (n_paths) HIP_TRY(nullptr, hipMemcpyAsync(alpha + (size_t)b0 * n_paths, d_alpha.p, (size_t)nb * n_paths * 8, hipMemcpyDeviceToHost, st));
-        if (iterations) HIP_TRY(nullptr, hipMemcpyAsync(iterations + b0, d_it.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(nullptr, hipStreamSynchronize(st));
-    }
     return GROOT_OK;
 }
 

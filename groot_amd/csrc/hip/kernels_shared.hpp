@@ -56,6 +56,7 @@ struct SharedArgs {
 // `batch` and `stats` beyond [3], written in paired mode only (kPaired kernels): fragments joined, split, single; batch[6] = the
 // batch's slow-path fragments (into stats[2] with the slow-path reads)
 constexpr uint32_t kSharedStats = 6, kSharedBatch = 7;
+constexpr uint32_t kSharedPairStats = 3;   // (host) stats[kSharedPairStats .. kSharedStats): the pairing counts -- joined, split, single
 
 __device__ __forceinline__ bool shared_live(const SharedArgs &a) { return !(a.ctr->flags & kCovSkipFlags); }
 
