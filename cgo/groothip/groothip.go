@@ -38,6 +38,7 @@ const (
 	TravStartClip = 2 // 1H before the M op (alignment.go:72-85)
 	TravEndClip   = 4 // 1H after the M op (alignment.go:87-103)
 	TravFirst     = 8 // first traversal of its AlignRead call
+	TravMapq      = 16 // assignment: Reserved holds the MAPQ of the traversal's records
 )
 
 // Counts mirrors groot_counts (the boss counters, boss.go:24-27)
@@ -101,6 +102,9 @@ type Ctx struct {
 	idx    *Index
 	device int
 	params Params
+	// assignment (AssignEnable): kept so that Reopen can hand it to the new ctx
+	assignAlpha   []float64
+	assignMinPost float64
 }
 
 // Params mirrors the fields of groot_params a host sets
@@ -198,6 +202,12 @@ func (c *Ctx) Reopen(maxReadLen int) error {
 			n.Close()
 			return nil, err
 		}
+		if c.assignAlpha != nil {
+			if err := n.AssignEnable(c.assignAlpha, c.assignMinPost); err != nil {
+				n.Close()
+				return nil, err
+			}
+		}
 		return n, nil
 	}
 	bigger, err := reopen(p)
@@ -212,6 +222,101 @@ func (c *Ctx) Reopen(maxReadLen int) error {
 	}
 	c.h, c.params = bigger.h, bigger.params
 	return nil
+}
+
+// AssignStats mirrors groot_assign_stats: the reads with records, how they were classed, the records before and after, the traversals
+// emptied, and (device only) the kernels launched for assignment since the ctx was opened
+type AssignStats struct {
+	Reads, Assigned, Unassigned, Below, Ties, RecordsIn, RecordsKept, TravsEmptied, Launches uint64
+}
+
+// AssignEnable switches assignment on with a copy of alpha (one value per path of the index, em_reads of an abundance file:
+// AbundanceRead) or, with alpha == nil, off (include/groot_hip.h, "assignment"): every batch then keeps, per read, only the records on
+// the path of S(r) with the largest alpha, with a MAPQ from its posterior.  Nothing may be in flight.  Not with AcovEnable or PairsEnable.
+func (c *Ctx) AssignEnable(alpha []float64, minPosterior float64) error {
+	var p *C.double
+	if alpha != nil {
+		if len(alpha) == 0 {
+			return fmt.Errorf("groot_hip_assign_enable: alpha is empty")
+		}
+		p = (*C.double)(unsafe.Pointer(&alpha[0]))
+	}
+	if rc := C.groot_hip_assign_enable(c.h, p, C.uint32_t(len(alpha)), C.double(minPosterior)); rc != 0 {
+		return c.err("groot_hip_assign_enable")
+	}
+	c.assignAlpha, c.assignMinPost = nil, 0
+	if alpha != nil {
+		c.assignAlpha, c.assignMinPost = append([]float64(nil), alpha...), minPosterior
+	}
+	return nil
+}
+
+// AssignBatch returns best (the global path, 0xFFFFFFFF for a read that keeps no record) and mapq of every read of a collected batch;
+// the slices are the ctx's and die with Release
+func (c *Ctx) AssignBatch(r *Result) (best []uint32, mapq []uint8, err error) {
+	var b *C.uint32_t
+	var q *C.uint8_t
+	if rc := C.groot_hip_assign_batch(c.h, C.uint64_t(r.Ticket), &b, &q); rc != 0 {
+		return nil, nil, c.err("groot_hip_assign_batch")
+	}
+	if r.NumReads == 0 {
+		return nil, nil, nil
+	}
+	return (*[1 << 28]uint32)(unsafe.Pointer(b))[:r.NumReads:r.NumReads], (*[1 << 30]uint8)(unsafe.Pointer(q))[:r.NumReads:r.NumReads], nil
+}
+
+// AssignStatsGet returns the counters since AssignEnable or AssignReset (waits for everything in flight)
+func (c *Ctx) AssignStatsGet() (AssignStats, error) {
+	var st C.groot_assign_stats
+	if rc := C.groot_hip_assign_stats(c.h, &st); rc != 0 {
+		return AssignStats{}, c.err("groot_hip_assign_stats")
+	}
+	return AssignStats{uint64(st.reads), uint64(st.assigned), uint64(st.unassigned), uint64(st.below), uint64(st.ties), uint64(st.records_in),
+		uint64(st.records_kept), uint64(st.travs_emptied), uint64(st.launches)}, nil
+}
+
+// AssignReset zeroes the counters (after waiting for everything in flight)
+func (c *Ctx) AssignReset() error {
+	if rc := C.groot_hip_assign_reset(c.h); rc != 0 {
+		return c.err("groot_hip_assign_reset")
+	}
+	return nil
+}
+
+// AbundanceRead reads an abundance file (`align --abundance`, 4 or 8 columns) into alpha: em_reads per path of the index, 0 for the
+// paths the file does not name
+func (idx *Index) AbundanceRead(path string) ([]float64, error) {
+	cp := C.CString(path)
+	defer C.free(unsafe.Pointer(cp))
+	alpha := make([]float64, int(idx.view.n_paths)+1)
+	var named C.uint64_t
+	if rc := C.groot_host_abundance_read(&idx.view, cp, (*C.double)(unsafe.Pointer(&alpha[0])), &named); rc != 0 {
+		return nil, fmt.Errorf("groot_host_abundance_read: %s", C.GoString(C.groot_host_last_error()))
+	}
+	return alpha[:int(idx.view.n_paths)], nil
+}
+
+// AssignTravs is the definition of assignment on the CPU (groot_host_assign_travs): travs (in (read, ord) order) and masks (PathWords
+// words per traversal) are rewritten in place; best and mapq have one entry per read of the batch
+func (idx *Index) AssignTravs(alpha []float64, minPosterior float64, travs []Trav, masks []uint64, firstReadID uint32, numReads int) (best []uint32, mapq []uint8, st AssignStats, err error) {
+	best, mapq = make([]uint32, numReads+1), make([]uint8, numReads+1)
+	var cs C.groot_assign_stats
+	var tp *C.groot_trav
+	var mp *C.uint64_t
+	var ap *C.double
+	if len(travs) > 0 {
+		tp, mp = (*C.groot_trav)(unsafe.Pointer(&travs[0])), (*C.uint64_t)(unsafe.Pointer(&masks[0]))
+	}
+	if len(alpha) > 0 {
+		ap = (*C.double)(unsafe.Pointer(&alpha[0]))
+	}
+	if rc := C.groot_host_assign_travs(&idx.view, ap, C.double(minPosterior), tp, mp, C.uint64_t(len(travs)), C.uint32_t(firstReadID), C.uint32_t(numReads),
+		(*C.uint32_t)(unsafe.Pointer(&best[0])), (*C.uint8_t)(unsafe.Pointer(&mapq[0])), &cs); rc != 0 {
+		return nil, nil, st, fmt.Errorf("groot_host_assign_travs: %s", C.GoString(C.groot_host_last_error()))
+	}
+	st = AssignStats{uint64(cs.reads), uint64(cs.assigned), uint64(cs.unassigned), uint64(cs.below), uint64(cs.ties), uint64(cs.records_in),
+		uint64(cs.records_kept), uint64(cs.travs_emptied), 0}
+	return best[:numReads], mapq[:numReads], st, nil
 }
 
 // Close releases the GPU context

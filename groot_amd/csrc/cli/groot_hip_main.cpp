@@ -70,8 +70,8 @@ void logf(const char *fmt, ...)
 }
 
 struct Args {
-    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out, abundance_out, calls_out;
-    double cov_cutoff = 0.97, abundance_min = 1.0, call_depth = 1.0;
+    std::string cmd, index_dir, msa_dir, log_file = "groot.log", graph_dir, bam_out, bam_file, report_out, shared_out, abundance_out, calls_out, assign_from;
+    double cov_cutoff = 0.97, abundance_min = 1.0, call_depth = 1.0, min_posterior = 0.0;   // --assignFrom <abundance file> [--minPosterior P]
     bool low_cov = false, no_bam = false;
     bool paired = false, interleaved = false;   // --paired / --interleaved: the FASTQ input is fragments (groot_reads_open_paired, groot_hip_pairs_enable)
     uint32_t bootstraps = 0;               // --bootstraps: replicates behind the four bootstrap columns of --abundance (0 = none)
@@ -112,6 +112,7 @@ void usage()
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
             "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0]] [--noBam]\n"
             "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0]]\n"
+            "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
@@ -121,6 +122,11 @@ void usage()
             "                   --calls: with --abundance, per line of the abundance file `name em_reads length depth breadth cigar called`: the pileup of\n"
             "                   the reads the EM assigns to the ARG (a record weighs its read's posterior on that ARG); a base is covered at depth >=\n"
             "                   --callDepth, called = 1 at breadth >= --covCutoff;\n"
+            "                   --assignFrom: a second pass over the same reads with the abundance file of a first (`--abundance a.tsv --noBam`): per read only\n"
+            "                   the records on the ARG with the largest em_reads among those the read lies on are kept (ties: the first in BAM header order),\n"
+            "                   and only when its share of their sum is >= --minPosterior; MAPQ = 3 per halving of the share of the others, 0..60.  The filter\n"
+            "                   runs on the GPU ahead of the BAM writer and of --report, which then covers what was assigned.  Not with --sharedReads,\n"
+            "                   --abundance, --calls, --paired, --interleaved or --noAlign;\n"
             "                   --paired: the -f files are R1,R2[,R1b,R2b...], first with second, third with fourth; --interleaved: the mates alternate in\n"
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
@@ -167,6 +173,13 @@ Args parse(int argc, char **argv)
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--abundanceMin") a.abundance_min = atof(v().c_str());
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootstraps") a.bootstraps = (uint32_t)std::max(0l, atol(v().c_str()));
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootSeed") a.boot_seed = strtoull(v().c_str(), nullptr, 10);
+        else if (a.cmd == "align" && f == "--assignFrom") a.assign_from = v();
+        else if (a.cmd == "align" && f == "--minPosterior") {   // (it decides which reads are kept: a value that is no number is refused, not read as 0)
+            const std::string t = v();
+            char *end = nullptr;
+            a.min_posterior = strtod(t.c_str(), &end);
+            if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "--minPosterior is a number in [0, 1]: %s\n", t.c_str()); exit(1); }
+        }
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--paired") a.paired = true;
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--interleaved") a.interleaved = true;
@@ -374,6 +387,22 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     if (want_ab && a.no_align) { fprintf(stderr, "--abundance needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
     if (a.bootstraps && !want_ab) { fprintf(stderr, "--bootstraps adds columns to the abundance file: it needs --abundance\n"); return 1; }
     const bool want_calls = !a.calls_out.empty();
+    const bool want_assign = !a.assign_from.empty();
+    if (want_assign) {
+        // the counters of S(r) see what assignment leaves of it -- one path per read
+        const struct { bool on; const char *flag, *why; } refused[] = {
+            {want_shared, "--sharedReads", "it counts the reads two ARGs share, and an assigned read lies on one ARG"},
+            {want_ab, "--abundance", "it estimates from every ARG a read lies on, and an assigned read lies on one: run it as the first pass"},
+            {want_calls, "--calls", "it weighs every record of a read, and an assigned read keeps the records on one ARG"},
+            {a.paired, "--paired", "fragments are not assigned yet: the mates would be assigned one by one"},
+            {a.interleaved, "--interleaved", "fragments are not assigned yet: the mates would be assigned one by one"},
+            {a.no_align, "--noAlign", "assignment filters the exact alignments, which it leaves out"},
+        };
+        for (const auto &r : refused)
+            if (r.on) { fprintf(stderr, "--assignFrom cannot be combined with %s: %s\n", r.flag, r.why); return 1; }
+        if (!(a.min_posterior >= 0.0 && a.min_posterior <= 1.0)) { fprintf(stderr, "--minPosterior is a share: %g is not in [0, 1]\n", a.min_posterior); return 1; }
+        if (!is_file(a.assign_from)) { fprintf(stderr, "--assignFrom: no file found at %s\n", a.assign_from.c_str()); return 1; }
+    } else if (a.min_posterior != 0.0) { fprintf(stderr, "--minPosterior is the threshold of --assignFrom: it needs it\n"); return 1; }
     if (want_calls && !want_ab) { fprintf(stderr, "--calls has a line per line of the abundance file: it needs --abundance\n"); return 1; }
     if (want_calls && a.no_align) { fprintf(stderr, "--calls needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
     if (want_calls && (a.paired || a.interleaved)) {
@@ -558,7 +587,25 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         std::vector<uint32_t> ids, tuples;
     };
     std::vector<std::unique_ptr<AcovExport>> acov_exports;
+    // --assignFrom: alpha of the first pass, handed to every ctx with the other switches (cov_enable); the stats of every ctx, summed
+    std::vector<double> assign_alpha;
+    groot_assign_stats assign_total{};
+    if (want_assign) {
+        uint64_t named = 0;
+        assign_alpha.resize(v.n_paths);
+        if (groot_host_abundance_read(&v, a.assign_from.c_str(), assign_alpha.data(), &named)) die("%s", groot_host_last_error());
+        logf("\tassignment: em_reads of %llu ARG(s) read from %s, minimum posterior %g", (unsigned long long)named, a.assign_from.c_str(), a.min_posterior);
+    }
+    const bool want_cov = want_report || want_ab || want_assign;   // a ctx carries switches: set at open and reopen, harvested before it closes
     auto cov_harvest = [&](groot_ctx *ctx) -> int {
+        if (want_assign) {
+            groot_assign_stats st{};
+            if (int rc = groot_hip_assign_stats(ctx, &st)) return rc;
+            std::lock_guard<std::mutex> lk(cov_mu);
+            assign_total.reads += st.reads; assign_total.assigned += st.assigned; assign_total.unassigned += st.unassigned; assign_total.below += st.below;
+            assign_total.ties += st.ties; assign_total.records_in += st.records_in; assign_total.records_kept += st.records_kept;
+            assign_total.travs_emptied += st.travs_emptied;
+        }
         if (frags) {
             uint64_t j = 0, sp = 0, si = 0;
             if (int rc = groot_hip_pairs_stats(ctx, &j, &sp, &si)) return rc;
@@ -613,6 +660,8 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         return 0;
     };
     auto cov_enable = [&](groot_ctx *ctx, int on) -> int {
+        if (want_assign)
+            if (int rc = groot_hip_assign_enable(ctx, on ? assign_alpha.data() : nullptr, v.n_paths, a.min_posterior)) return rc;
         if (frags)
             if (int rc = groot_hip_pairs_enable(ctx, on)) return rc;
         if (want_report)
@@ -638,7 +687,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             });
         for (auto &t : th) t.join();
         for (auto &e : errs) if (!e.empty()) die("%s", e.c_str());
-        if (want_report || want_ab)
+        if (want_cov)
             for (auto &g : gpus) if (cov_enable(g->ctx, 1)) die("%s", groot_hip_last_error(g->ctx));
     }
     logf("\tcontainment threshold: %.2f", a.threshold);
@@ -695,7 +744,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                 if (groot_hip_attempts_export(g.ctx, nullptr, nullptr, 0, &n_rows, &nw)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 std::vector<uint32_t> qv(n_rows), cnt((size_t)n_rows * nw);
                 if (n_rows && groot_hip_attempts_export(g.ctx, qv.data(), cnt.data(), n_rows, &n_rows, &nw)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
-                if ((want_report || want_ab) && cov_harvest(g.ctx)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+                if (want_cov && cov_harvest(g.ctx)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 groot_hip_close(g.ctx);
                 g.ctx = nullptr;
                 g.max_read_len = std::min<uint32_t>(65535, need + need / 2);
@@ -703,7 +752,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                 logf("\tread of %u bases: reopening the GPU context for reads up to %u bases", need, g.max_read_len);
                 if (groot_hip_open_flags(&g.ctx, g.device, &v, &prm, GROOT_OPEN_BACKGROUND)) { fail_with(groot_hip_last_error(nullptr)); return false; }
                 if (n_rows && groot_hip_attempts_import(g.ctx, qv.data(), cnt.data(), n_rows)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
-                if ((want_report || want_ab) && cov_enable(g.ctx, 1)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+                if (want_cov && cov_enable(g.ctx, 1)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
                 return true;
             };
             while (!failed) {
@@ -768,7 +817,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                     const int wrc = groot_bam_write_batch(bam, &v, &it.view, 0, it.res.travs, it.res.masks, it.res.mask_ckpt, it.res.n_travs, &nrec);
                     bam_s += seconds_since(tw);
                     if (wrc) fail_with(groot_host_last_error());
-                    else if (nrec != c.alignments)
+                    else if (nrec != c.alignments && !want_assign)   // (assignment: the counts are the unfiltered run's, the records what it kept)
                         fail_with("internal error: " + std::to_string(nrec) + " records written, " + std::to_string(c.alignments) + " alignments counted");
                 }
                 groot_reads_batch_free(it.batch);
@@ -799,12 +848,17 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     logf("\tnumber of reads sketched: %llu", (unsigned long long)received);                      // sketch.go:321
     const uint64_t bam_bytes = bam ? groot_bam_bytes_written(bam) : 0;
     if (bam && groot_bam_close(bam)) die("%s", groot_host_last_error());
-    if (want_report || want_ab) {
+    if (want_cov) {
         // every batch has been collected: what each ctx counted is final (it is switched off, so a ctx reopened below starts without it)
         for (auto &g : gpus) {
             if (cov_harvest(g->ctx) || cov_enable(g->ctx, 0)) die("%s", groot_hip_last_error(g->ctx));
         }
     }
+    if (want_assign)
+        logf("\tassignment: %llu read(s) with records: %llu assigned (%llu on a tie), %llu unassigned, %llu below the minimum posterior; %llu record(s) in, %llu kept, %llu traversal(s) emptied",
+             (unsigned long long)assign_total.reads, (unsigned long long)assign_total.assigned, (unsigned long long)assign_total.ties, (unsigned long long)assign_total.unassigned,
+             (unsigned long long)assign_total.below, (unsigned long long)assign_total.records_in, (unsigned long long)assign_total.records_kept,
+             (unsigned long long)assign_total.travs_emptied);
     if (frags)
         logf("\tpaired-end input: %llu fragment(s), %llu joined, %llu split, %llu single", (unsigned long long)(received / 2), (unsigned long long)fr_joined,
              (unsigned long long)fr_split, (unsigned long long)fr_single);

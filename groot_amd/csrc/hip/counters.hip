@@ -15,6 +15,7 @@
 #include "counters.hpp"
 #include "ctx.hpp"
 #include "kernels_acov.hpp"
+#include "kernels_assign.hpp"
 #include "kernels_boot.hpp"
 #include "kernels_cov.hpp"
 #include "kernels_ec.hpp"
@@ -314,6 +315,33 @@ void counters_init(groot_ctx *c, const groot_index_view *v)
     for (uint32_t p = 0; p < v->n_paths; p++) k.h_cov_base[p + 1] = k.h_cov_base[p] + v->path_len[p] + 1;
 }
 
+int counters_assign(groot_ctx *c, Slot *s)
+{
+    Counters &k = c->ct;
+    if (!k.asg_on) return GROOT_OK;
+    const size_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    HIP_TRY(c, s->ct.d_best.reserve(R));
+    HIP_TRY(c, s->ct.d_mapq.reserve(R));
+    HIP_TRY(c, s->ct.h_best.reserve(R));
+    HIP_TRY(c, s->ct.h_mapq.reserve(R));
+    if (!s->n_reads) return GROOT_OK;
+    const WorkSet &w = c->ws[s->set];
+    AssignArgs a{};
+    a.trav = s->d_trav.p; a.mask = s->d_mask.p; a.ctr = s->d_ctr.p; a.off = c->trav_off.p; a.cnt = w.trav_cnt.p;
+    a.graph_path_off = k.asg_gpo.p; a.alpha = k.asg_alpha.p; a.best = s->ct.d_best.p; a.mapq = s->ct.d_mapq.p; a.stats = k.asg_stats.p;
+    a.min_post = k.asg_min_post;
+    a.n_reads = s->n_reads; a.cap = s->trav_cap; a.pw = c->pw_view; a.n_paths = (uint32_t)k.h_len.size(); a.n_graphs = (uint32_t)k.h_gpo.size() - 1;
+    // Once per pass, on records the order stage has just written: the filter is not idempotent (a second application would see
+    // S(r) = {best} and give MAPQ 60).  A redo pass rewrites the records first and is filtered here again; the skipped pass was not.
+    const dim3 g(grid_for(s->n_reads));
+    if (a.n_paths <= kAssignLdsPaths && !c->kn.assign_global)
+        hipLaunchKernelGGL(assign_kernel<true>, g, dim3(kBlock), (size_t)a.n_paths * sizeof(double), c->tstream, a);
+    else hipLaunchKernelGGL(assign_kernel<false>, g, dim3(kBlock), 0, c->tstream, a);
+    HIP_TRY(c, hipGetLastError());
+    k.asg_launches++;
+    return GROOT_OK;
+}
+
 int counters_launch(groot_ctx *c, Slot *s)
 {
     Counters &k = c->ct;
@@ -365,6 +393,10 @@ int counters_launch(groot_ctx *c, Slot *s)
 
 int counters_fetch(groot_ctx *c, Slot *s)
 {
+    if (s->ct.assigned && s->n_reads) {   // 5 bytes per read
+        HIP_TRY(c, hipMemcpyAsync(s->ct.h_best.p, s->ct.d_best.p, (size_t)s->n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+        HIP_TRY(c, hipMemcpyAsync(s->ct.h_mapq.p, s->ct.d_mapq.p, (size_t)s->n_reads, hipMemcpyDeviceToHost, c->d2h_stream));
+    }
     if (!c->ct.ec_on) return GROOT_OK;
     CounterStatus *h = s->ct.h_status.p;
     HIP_TRY(c, hipMemcpyAsync(&h->ec_slow, s->ct.d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
@@ -378,6 +410,15 @@ int counters_fetch(groot_ctx *c, Slot *s)
 
 int counters_collect(groot_ctx *c, Slot *s, bool redone)
 {
+    if (s->ct.assigned && s->n_reads && s->ct.h_best.p) {
+        if (s->h_ctr.p->flags & kCovSkipFlags) {           // the batch fails: assign_kernel left its records as they were
+            std::fill(s->ct.h_best.p, s->ct.h_best.p + s->n_reads, kAssignNone);
+            memset(s->ct.h_mapq.p, 0, s->n_reads);
+        } else if (redone) {                               // fetch's copies are those of the skipped pass
+            HIP_TRY(c, hipMemcpy(s->ct.h_best.p, s->ct.d_best.p, (size_t)s->n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(s->ct.h_mapq.p, s->ct.d_mapq.p, (size_t)s->n_reads, hipMemcpyDeviceToHost));
+        }
+    }
     if (!c->ct.ec_on || !s->n_reads) return GROOT_OK;
     if (int rc = ec_collect(c, s, redone)) return rc;
     return c->ct.acov_on ? acov_collect(c, s, redone) : GROOT_OK;
@@ -506,6 +547,7 @@ int groot_hip_shared_enable(groot_ctx *c, int on)
         return GROOT_OK;
     }
     if (c->ct.sh_on) return GROOT_OK;
+    if (c->ct.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "shared reads count S(r), which assignment collapses (groot_hip_assign_enable)");
     const uint64_t n_paths = c->ct.h_len.size(), tri = shared_tri_size(n_paths);
     if (tri * sizeof(uint64_t) > GROOT_SHARED_MAX_BYTES)
         return fail(c, GROOT_E_UNSUPPORTED, "shared reads: %llu paths need a %llu MiB pair table, above the bound of %llu MiB", (unsigned long long)n_paths,
@@ -580,6 +622,7 @@ int groot_hip_ec_enable(groot_ctx *c, int on)
         return GROOT_OK;
     }
     if (c->ct.ec_on) return GROOT_OK;
+    if (c->ct.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "equivalence classes count S(r), which assignment collapses (groot_hip_assign_enable)");
     if (!c->ct.sh_on)
         if (int rc = sh_table_size(c, "equivalence classes")) return rc;
     uint32_t cap = 1;
@@ -865,12 +908,68 @@ int groot_hip_acov_reset(groot_ctx *c)
     return GROOT_OK;
 }
 
+// ---- assignment (kernels_assign.hpp) ---------------------------------------------------------------------------------
+int groot_hip_assign_enable(groot_ctx *c, const double *alpha, uint32_t n_paths, double min_posterior)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "assignment can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!alpha) {
+        k.asg_alpha.release(); k.asg_gpo.release(); k.asg_stats.release();
+        k.asg_on = false;
+        return GROOT_OK;
+    }
+    if (k.sh_on || k.ec_on || k.acov_on || k.pairs_on)
+        return fail(c, GROOT_E_UNSUPPORTED, "assignment collapses S(r): not with shared reads, equivalence classes, assigned coverage or pairing on");
+    if (n_paths != k.h_len.size()) return fail(c, GROOT_E_INVALID, "assignment: alpha has %u values, the index %zu paths", n_paths, k.h_len.size());
+    if (!(min_posterior >= 0.0 && min_posterior <= 1.0)) return fail(c, GROOT_E_INVALID, "assignment: min_posterior %g is not in [0, 1]", min_posterior);
+    for (uint32_t p = 0; p < n_paths; p++)
+        if (!(alpha[p] >= 0.0 && alpha[p] <= 1e300)) return fail(c, GROOT_E_INVALID, "assignment: alpha[%u] = %g is not a finite value in [0, 1e300]", p, alpha[p]);
+    const bool was_on = k.asg_on;
+    auto undo = [&](int rc) { groot_hip_assign_enable(c, nullptr, 0, 0.0); return rc; };
+    hipError_t e = upload(k.asg_alpha, alpha, n_paths);
+    if (e == hipSuccess && !was_on) {
+        e = upload(k.asg_gpo, k.h_gpo.data(), k.h_gpo.size());
+        if (e == hipSuccess) e = k.asg_stats.alloc(kAssignStats);
+        if (e == hipSuccess) e = hipMemset(k.asg_stats.p, 0, kAssignStats * sizeof(unsigned long long));
+    }
+    if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "assignment: %s", hipGetErrorString(e)));
+    k.asg_min_post = min_posterior;
+    k.asg_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_assign_stats(groot_ctx *c, groot_assign_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kAssignStats] = {};
+    if (c->ct.asg_on) {
+        if (int rc = drain(c)) return rc;
+        HIP_TRY(c, hipMemcpy(st, c->ct.asg_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    }
+    out->reads = st[0]; out->assigned = st[1]; out->unassigned = st[2]; out->below = st[3]; out->ties = st[4];
+    out->records_in = st[5]; out->records_kept = st[6]; out->travs_emptied = st[7];
+    out->launches = c->ct.asg_launches;
+    return GROOT_OK;
+}
+
+int groot_hip_assign_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.asg_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemset(c->ct.asg_stats.p, 0, kAssignStats * sizeof(unsigned long long)));
+    return GROOT_OK;
+}
+
 // ---- paired-end reads (the kPaired kernels of kernels_shared.hpp; the definition is in groot_hip.h) -------------------------
 int groot_hip_pairs_enable(groot_ctx *c, int on)
 {
     if (!c) return GROOT_E_INVALID;
     if (!idle(c)) return fail(c, GROOT_E_STATE, "pairing can only be switched while nothing is in flight");
     if (on && c->ct.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assigned coverage are not supported");
+    if (on && c->ct.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assignment are not supported (groot_hip_assign_enable)");
     c->ct.pairs_on = on != 0;
     if (c->ct.sh_on || c->ct.ec_on) {     // (else there is nothing to zero: sh_common_alloc zeroes the counts when either comes on)
         HIP_TRY(c, hipSetDevice(c->device));

@@ -70,7 +70,7 @@ template <class T> struct PinBuf {
 // a test batch walks the grow-and-redo and the fall-back paths; OPEN_STATS prints where groot_hip_open spent its time.
 struct Knobs {
     bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false,
-         shared_slow = false, serial_tail = false;
+         shared_slow = false, serial_tail = false, assign_global = false;
     uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
     uint32_t acov_slots = 0;               // GROOT_TEST_ACOV_SLOTS: initial slots of the assigned-coverage table (0 = the default)
     static Knobs read()
@@ -84,6 +84,7 @@ struct Knobs {
         k.no_path = getenv("GROOT_NO_PATH_PASS") != nullptr;              // no first pass: align_kernel alone
         k.shared_slow = getenv("GROOT_TEST_SHARED_SLOW") != nullptr;      // shared reads: every read in more than one graph takes the slow path
         k.serial_tail = getenv("GROOT_SERIAL_TAIL") != nullptr;           // the tail of the align stage stays on the walk stream (no tail stream: the A/B baseline)
+        k.assign_global = getenv("GROOT_TEST_ASSIGN_GLOBAL") != nullptr;  // assignment: alpha is read from global memory even when it fits in LDS
         if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         if (const char *e = getenv("GROOT_TEST_ACOV_SLOTS")) k.acov_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         return k;
@@ -133,6 +134,11 @@ struct SlotCounters {
     PinBuf<CounterStatus> h_status;
     DevBuf<uint32_t> d_acov_ser;           // assigned coverage: the EC serial of every read of the batch (acov_serial_kernel); the counting kernels read it, also when collect repeats them
     DevBuf<uint32_t> d_acov_state;         // [0] 1 = the batch's claim phase ran out of room (its add phase then did nothing), 2 = a key went missing
+    DevBuf<uint32_t> d_best;               // assignment: best path / MAPQ of every read of the batch (assign_kernel), copied out with the batch
+    DevBuf<uint8_t> d_mapq;
+    PinBuf<uint32_t> h_best;
+    PinBuf<uint8_t> h_mapq;
+    bool assigned = false;                 // the batch went through assign_kernel: h_best / h_mapq are its
 };
 
 struct Counters {
@@ -173,6 +179,14 @@ struct Counters {
     uint64_t acov_grows = 0, acov_slow_records = 0, acov_redone = 0;
     uint64_t acov_launches = 0;            // kernels launched for it since open (stays put while it is off)
     std::map<std::vector<uint32_t>, std::map<std::array<uint32_t, 3>, uint64_t>> acov_host;   // S(r) -> (path, Pos, last) -> records, of slow-path reads
+    // assignment (groot_hip_assign_*, kernels_assign.hpp): assign_kernel rewrites every batch's records inside the order stage, ahead
+    // of everything that reads them.  Nothing on the device while off.
+    bool asg_on = false;
+    double asg_min_post = 0.0;
+    DevBuf<double> asg_alpha;              // [n_paths]
+    DevBuf<uint32_t> asg_gpo;              // graph_path_off (a copy of its own: the position tables above are not needed)
+    DevBuf<unsigned long long> asg_stats;  // [kAssignStats]
+    uint64_t asg_launches = 0;             // kernels launched for it since open (stays put while it is off)
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

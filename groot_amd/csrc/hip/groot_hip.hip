@@ -688,6 +688,10 @@ static int launch_order_stage(groot_ctx *c, Slot *s, bool update_weights)
                        w->ovf_trav.p, w->ovf_mask.p, w->ovf_cnt.p, c->ovf_cap, c->trav_off.p, s->first_read_id, s->d_trav.p,
                        s->d_mask.p, s->trav_cap, c->pw, c->pw_view, s->d_ctr.p, w->vitem.p, n);
     HIP_TRY(c, hipGetLastError());
+    // assignment (groot_hip_assign_enable): the records are complete and nothing has read them yet -- the compact copy-out below, the packed
+    // records, the counters and groot_hip_read_travs all see what it leaves.  It runs once per pass on freshly written records, never twice
+    // on the same ones: the filter is not idempotent.
+    if (int rc = counters_assign(c, s)) return rc;
     if (!c->prm.results_on_device) {
         // compact path sets for the copy-out (kernels.hpp): words per traversal, their exclusive scan, the copy
         const dim3 g((s->trav_cap + kBlock - 1) / kBlock);
@@ -835,6 +839,7 @@ static int enqueue(groot_ctx *c, Slot *s)
     memset(&s->ms, 0, sizeof s->ms);
     s->ticket = c->next_ticket++;
     s->lean_used = s->path_used = false; s->path_reads = 0;   // (an empty batch runs no stage: not what the slot's last batch left)
+    s->ct.assigned = c->ct.asg_on;                            // (likewise, and for a batch that fails ahead of the order stage)
     if (s->n_reads == 0) {      // nothing to run: completes at once
         memset(s->h_ctr.p, 0, sizeof(DeviceCounters));
         HIP_TRY(c, hipEventRecord(s->ev_ctr, c->d2h_stream));
@@ -942,6 +947,7 @@ static void expand_travs(const groot_ctx *c, Slot *s)
     groot_trav *out = s->h_trav.p;
     const uint32_t first = s->first_read_id;
     const uint32_t *node_graph = c->h_node_graph.data();
+    const uint8_t *mapq = s->ct.assigned ? s->ct.h_mapq.p : nullptr;
     auto span = [=](size_t lo, size_t hi) {
         if (lo >= hi) return;
         uint32_t ord = 0, prev = ~0u;
@@ -959,7 +965,8 @@ static void expand_travs(const groot_ctx *c, Slot *s)
             prev = pos;
             groot_trav t;
             t.read_id = first + pos; t.graph_id = node_graph[in[i].node]; t.node = in[i].node; t.offset = in[i].offset;
-            t.ord = (uint16_t)ord; t.flags = (uint8_t)(in[i].read_flags >> 24); t.reserved = 0;
+            t.ord = (uint16_t)ord; t.flags = (uint8_t)(in[i].read_flags >> 24);
+            t.reserved = mapq && (t.flags & GROOT_TRAV_MAPQ) ? mapq[pos] : (uint8_t)0;   // (the 12-byte record carries the flag, the read's MAPQ travels beside it)
             out[i] = t;
         }
     };
@@ -2826,6 +2833,17 @@ int groot_hip_release(groot_ctx *c, uint64_t ticket)
     if (!s) s = slot_by_ticket(c, ticket, Slot::ACQUIRED);     // an acquired batch may be abandoned
     if (!s) return fail(c, GROOT_E_STATE, "ticket %llu is not a collected batch", (unsigned long long)ticket);
     release_slot(c, s);
+    return GROOT_OK;
+}
+
+int groot_hip_assign_batch(groot_ctx *c, uint64_t ticket, const uint32_t **best, const uint8_t **mapq)
+{
+    if (!c) return GROOT_E_INVALID;
+    Slot *s = ticket ? slot_by_ticket(c, ticket, Slot::COLLECTED) : c->waited;
+    if (!s) return fail(c, GROOT_E_STATE, "ticket %llu is not a collected batch", (unsigned long long)ticket);
+    if (!s->ct.assigned) return fail(c, GROOT_E_STATE, "assignment was off when the batch was submitted (groot_hip_assign_enable)");
+    if (best) *best = s->ct.h_best.p;
+    if (mapq) *mapq = s->ct.h_mapq.p;
     return GROOT_OK;
 }
 

@@ -261,7 +261,7 @@ struct RawBuf {
 };
 
 template <class Buf>
-static void format_records(const groot_aln_record *recs, uint64_t i0, uint64_t i1, Buf &buf, std::vector<uint32_t> *starts = nullptr)
+static void format_records(const groot_aln_record *recs, uint64_t i0, uint64_t i1, Buf &buf, std::vector<uint32_t> *starts = nullptr, uint32_t mapq = 30)
 {
     static const Nt16 nt;
     const uint8_t *nt16 = nt.t;
@@ -287,7 +287,7 @@ static void format_records(const groot_aln_record *recs, uint64_t i0, uint64_t i
         w32(body);
         w32(r.ref_id);
         w32(r.pos);
-        w32(((uint32_t)bin << 16) | (30u << 8) | l_name);                     // MAPQ 30 (:143)
+        w32(((uint32_t)bin << 16) | (mapq << 8) | l_name);                    // MAPQ 30 (:143), or the assignment's (groot_trav.reserved)
         w32(((uint32_t)flag << 16) | nc);
         w32(r.seq_len);
         w32((uint32_t)-1);                                                    // next_refID
@@ -459,6 +459,7 @@ static int write_travs_impl(groot_bam *b, const groot_index_view *ix, ReadFn rea
                 }
                 const uint8_t sc = (tr.flags & GROOT_TRAV_START_CLIP) ? 1 : 0, ec = (tr.flags & GROOT_TRAV_END_CLIP) ? 1 : 0;
                 bool first = (tr.flags & GROOT_TRAV_FIRST) != 0;
+                const uint32_t mapq = (tr.flags & GROOT_TRAV_MAPQ) ? tr.reserved : 30u;   // (a structural copy of a record carries its MAPQ along)
                 recs.clear();
                 uint64_t n_here = 0;                                  // records of this traversal so far (structural path: formatted as they come)
                 const uint32_t np0 = ix->node_np_off[tr.node], np1 = ix->node_np_off[tr.node + 1];
@@ -516,7 +517,7 @@ static int write_travs_impl(groot_bam *b, const groot_index_view *ix, ReadFn rea
                         rec.secondary = first ? 0 : 1;                                            // alignment.go:147-149
                         first = false;
                         if (level == kBamStructural) {
-                            format_records(&rec, 0, 1, raw, &starts);
+                            format_records(&rec, 0, 1, raw, &starts, mapq);
                             follow.push_back(0);
                             n_here++;
                             continue;
@@ -528,7 +529,7 @@ static int write_travs_impl(groot_bam *b, const groot_index_view *ix, ReadFn rea
                 nrec[c] += level == kBamStructural ? n_here : recs.size();
                 const uint64_t q1 = bam_stats ? now_ns() : 0;
                 tb += q1 - q0;
-                if (level != kBamStructural) format_records(recs.data(), 0, recs.size(), raw, nullptr);   // rcs/rcq/padq stay valid until here
+                if (level != kBamStructural) format_records(recs.data(), 0, recs.size(), raw, nullptr, mapq);   // rcs/rcq/padq stay valid until here
                 if (bam_stats) tf += now_ns() - q1;
             }
             if (errs[c]) continue;

@@ -1,5 +1,6 @@
 // graphs.cpp -- host steps after the device path: traversal -> record expansion, graph weighting
-// replay, pruning and GFA output.
+// replay, pruning and GFA output; and, at the end, assignment on a traversal list (groot_host_assign_travs: it rewrites what
+// groot_host_expand_alns expands, so it lives beside it).
 //   src/graph/alignment.go:113-156,263-317   records from traversals
 //   src/graph/graph.go:401-451               IncrementSubPath
 //   src/graph/graph.go:455-525               Prune
@@ -246,3 +247,105 @@ int groot_host_save_gfa(const groot_index_view *ix, uint32_t g, const double *kf
 }
 
 } // extern "C"
+
+// ---- assignment: each read to its best allele by EM posterior (groot_host.h "assignment") ------------------------------------
+// The definition itself, read by read over records in (read, ord) order; kernels_assign.hpp computes the same bytes on the device.
+// (x86-64 without -march has no fused multiply-add: the one product and the sums round as written)
+static bool assign_alpha_ok(double v) { return v >= 0.0 && v <= 1e300; }   // (false for a NaN)
+
+extern "C" int groot_host_assign_travs(const groot_index_view *ix, const double *alpha, double min_post, groot_trav *travs, uint64_t *masks, uint64_t n_trav,
+                                       uint32_t first_read_id, uint32_t n_reads, uint32_t *best, uint8_t *mapq, groot_assign_stats *stats)
+{
+    if (!ix || (ix->n_paths && !alpha) || (n_trav && (!travs || !masks))) return set_error(GROOT_E_INVALID, "null argument");
+    if (!(min_post >= 0.0 && min_post <= 1.0)) return set_error(GROOT_E_INVALID, "min_posterior %g is not in [0, 1]", min_post);
+    for (uint32_t p = 0; p < ix->n_paths; p++)
+        if (!assign_alpha_ok(alpha[p])) return set_error(GROOT_E_INVALID, "alpha[%u] = %g is not a finite value in [0, 1e300]", p, alpha[p]);
+    const uint32_t pw = ix->path_words;
+    for (uint64_t t = 0; t < n_trav; t++) {
+        const groot_trav &tr = travs[t];
+        if (tr.graph_id >= ix->n_graphs || (uint32_t)(tr.read_id - first_read_id) >= n_reads)
+            return set_error(GROOT_E_INVALID, "traversal %llu refers outside the index or the batch", (unsigned long long)t);
+        const uint32_t np = ix->graph_path_off[tr.graph_id + 1] - ix->graph_path_off[tr.graph_id];
+        for (uint32_t w = 0; w < pw; w++) {
+            const uint64_t ok = np >= 64 * (w + 1) ? ~0ull : np <= 64 * w ? 0ull : (1ull << (np - 64 * w)) - 1;
+            if (masks[t * pw + w] & ~ok) return set_error(GROOT_E_INVALID, "traversal %llu: a path beyond its graph's", (unsigned long long)t);
+        }
+        if (t && tr.read_id == travs[t - 1].read_id && tr.graph_id < travs[t - 1].graph_id)
+            return set_error(GROOT_E_INVALID, "traversal %llu: the graphs of a read must ascend", (unsigned long long)t);
+        // (read, ord) order: batch positions never fall, so a read's traversals are one run and no read is taken for two
+        if (t && (uint32_t)(tr.read_id - first_read_id) < (uint32_t)(travs[t - 1].read_id - first_read_id))
+            return set_error(GROOT_E_INVALID, "traversal %llu: the reads must come in batch order, each read's traversals together", (unsigned long long)t);
+    }
+    if (best) for (uint32_t r = 0; r < n_reads; r++) best[r] = 0xFFFFFFFFu;
+    if (mapq) memset(mapq, 0, n_reads);
+    groot_assign_stats st{};
+    for (uint64_t t0 = 0; t0 < n_trav;) {
+        uint64_t t1 = t0 + 1;
+        while (t1 < n_trav && travs[t1].read_id == travs[t0].read_id) t1++;
+        st.reads++;
+        // S(r) in ascending global ID: graph by graph (they ascend), the OR of the graph's path sets word by word
+        double denom = 0.0, bestv = -1.0;
+        uint32_t bg = 0, bl = 0, nties = 0;
+        for (uint64_t s = t0; s < t1;) {
+            const uint32_t g = travs[s].graph_id;
+            uint64_t e = s + 1;
+            while (e < t1 && travs[e].graph_id == g) e++;
+            for (uint32_t w = 0; w < pw; w++) {
+                uint64_t m = 0;
+                for (uint64_t t = s; t < e; t++) { m |= masks[t * pw + w]; st.records_in += (uint64_t)__builtin_popcountll(masks[t * pw + w]); }
+                while (m) {
+                    const uint32_t l = w * 64 + (uint32_t)__builtin_ctzll(m);
+                    m &= m - 1;
+                    const double v = alpha[ix->graph_path_off[g] + l];
+                    denom = denom + v;
+                    if (v > bestv) { bestv = v; bg = g; bl = l; nties = 1; }
+                    else if (v == bestv) nties++;
+                }
+            }
+            s = e;
+        }
+        bool keep = false;
+        uint32_t mq = 0;
+        if (bestv < 0.0 || denom == 0.0) st.unassigned++;
+        else if (!(bestv >= min_post * denom)) st.below++;
+        else {
+            keep = true;
+            st.assigned++;
+            if (nties > 1) st.ties++;
+            const double rest = denom - bestv;
+            double sc = 1.0;
+            uint32_t j = 0;
+            for (int k = 1; k <= 20; k++) {
+                sc = sc * 2.0;                       // 2^k: the product below is ldexp(rest, k)
+                if (rest * sc <= denom) j++;
+            }
+            mq = 3 * j;
+        }
+        const uint32_t bw = bl >> 6;
+        const uint64_t bb = 1ull << (bl & 63u);
+        bool first = true;
+        for (uint64_t t = t0; t < t1; t++) {
+            groot_trav &tr = travs[t];
+            uint64_t *mk = masks + t * pw;
+            const bool kept = keep && tr.graph_id == bg && (mk[bw] & bb);
+            for (uint32_t w = 0; w < pw; w++) mk[w] = kept && w == bw ? bb : 0ull;
+            uint8_t fl = tr.flags & (uint8_t)~(GROOT_TRAV_FIRST | GROOT_TRAV_MAPQ);
+            if (kept) {
+                fl |= GROOT_TRAV_MAPQ;
+                if (first) fl |= GROOT_TRAV_FIRST;
+                first = false;
+                st.records_kept++;
+            } else st.travs_emptied++;
+            tr.flags = fl;
+            tr.reserved = kept ? (uint8_t)mq : (uint8_t)0;
+        }
+        const uint32_t r = travs[t0].read_id - first_read_id;
+        if (keep) {
+            if (best) best[r] = ix->graph_path_off[bg] + bl;
+            if (mapq) mapq[r] = (uint8_t)mq;
+        }
+        t0 = t1;
+    }
+    if (stats) *stats = st;
+    return GROOT_OK;
+}

@@ -937,3 +937,60 @@ extern "C" int groot_host_report_calls(const char *bam_path, double min_reads, d
     return write_calls((uint32_t)names.size(), name_ptr.data(), nullptr, lens.data(), m.size(), off.data(), ids.data(), count.data(), nullptr, t.size(), tup.data(),
                        tn.data(), min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called);
 }
+
+// ---- reading an abundance file back (align --assignFrom; groot_host.h "assignment") ------------------------------------------
+extern "C" int groot_host_abundance_read(const groot_index_view *ix, const char *path, double *alpha_out, uint64_t *n_named)
+{
+    if (!ix || !path || (ix->n_paths && !alpha_out)) return set_error(GROOT_E_INVALID, "null argument");
+    const uint32_t n = ix->n_paths;
+    constexpr uint32_t kAmbiguous = 0xFFFFFFFFu;
+    std::unordered_map<std::string, uint32_t> by_name;         // the name as the report prints it -> path (kAmbiguous: two paths share it)
+    for (uint32_t p = 0; p < n; p++) {
+        const char *nm = ix->path_names + ix->path_name_off[p];
+        size_t nl = ix->path_name_off[p + 1] - ix->path_name_off[p];
+        if (nl && nm[0] == '*') { nm++; nl--; }
+        auto ins = by_name.emplace(std::string(nm, nl), p);
+        if (!ins.second) ins.first->second = kAmbiguous;
+    }
+    FILE *f = fopen(path, "r");
+    if (!f) return set_error(GROOT_E_IO, "cannot open %s", path);
+    std::string text;
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    if (bad) return set_error(GROOT_E_IO, "cannot read %s", path);
+    for (uint32_t p = 0; p < n; p++) alpha_out[p] = 0.0;
+    std::vector<uint8_t> seen(n, 0);
+    uint64_t lines = 0, line_no = 0;
+    for (size_t at = 0; at < text.size();) {
+        size_t end = text.find('\n', at);
+        if (end == std::string::npos) end = text.size();
+        std::string line = text.substr(at, end - at);
+        at = end + 1;
+        line_no++;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const size_t t1 = line.find('\t'), t2 = t1 == std::string::npos ? t1 : line.find('\t', t1 + 1);
+        if (t2 == std::string::npos || t2 + 1 >= line.size())
+            return set_error(GROOT_E_FORMAT, "%s line %llu: fewer than 3 columns", path, (unsigned long long)line_no);
+        const std::string name = line.substr(0, t1);
+        size_t t3 = line.find('\t', t2 + 1);
+        if (t3 == std::string::npos) t3 = line.size();
+        const std::string val = line.substr(t2 + 1, t3 - t2 - 1);
+        char *ep = nullptr;
+        const double v = strtod(val.c_str(), &ep);
+        if (val.empty() || ep != val.c_str() + val.size() || !(v >= 0.0 && v <= 1e300))
+            return set_error(GROOT_E_FORMAT, "%s line %llu: em_reads '%s' is not a finite number in [0, 1e300]", path, (unsigned long long)line_no, val.c_str());
+        const auto it = by_name.find(name);
+        if (it == by_name.end()) return set_error(GROOT_E_FORMAT, "%s line %llu: '%s' is not a reference of the index", path, (unsigned long long)line_no, name.c_str());
+        if (it->second == kAmbiguous) return set_error(GROOT_E_FORMAT, "%s line %llu: two references of the index are called '%s'", path, (unsigned long long)line_no, name.c_str());
+        if (seen[it->second]) return set_error(GROOT_E_FORMAT, "%s line %llu: '%s' is given twice", path, (unsigned long long)line_no, name.c_str());
+        seen[it->second] = 1;
+        alpha_out[it->second] = v;
+        lines++;
+    }
+    if (n_named) *n_named = lines;
+    return GROOT_OK;
+}

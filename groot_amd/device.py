@@ -15,7 +15,7 @@ TRAV_DTYPE = np.dtype([("read_id", "<u4"), ("graph_id", "<u4"), ("node", "<u4"),
 ALN_DTYPE = np.dtype([("read_id", "<u4"), ("graph_id", "<u4"), ("path_id", "<u4"), ("ref_id", "<u4"), ("pos", "<u4"),
                       ("start_clip", "u1"), ("end_clip", "u1"), ("rc", "u1"), ("secondary", "u1")])
 SEED_DTYPE = np.dtype([("read_id", "<u4"), ("window_id", "<u4")])
-TRAV_RC, TRAV_START_CLIP, TRAV_END_CLIP, TRAV_FIRST = 1, 2, 4, 8
+TRAV_RC, TRAV_START_CLIP, TRAV_END_CLIP, TRAV_FIRST, TRAV_MAPQ = 1, 2, 4, 8, 16
 
 
 class Params(C.Structure):
@@ -466,6 +466,34 @@ class Aligner:
 
     def acov_reset(self):
         self._check(lib().groot_hip_acov_reset(self._h))
+
+    # ---- assignment (groot_hip_assign_*) -------------------------------------------------------------
+    def assign_enable(self, alpha, min_posterior=0.0):
+        """every batch from now on keeps, per read, only the records on the path of S(r) with the largest alpha (include/groot_hip.h,
+        "assignment"); alpha None switches it off.  Only while nothing is in flight."""
+        if alpha is None:
+            self._check(lib().groot_hip_assign_enable(self._h, None, C.c_uint32(0), C.c_double(0.0)))
+            return
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        self._check(lib().groot_hip_assign_enable(self._h, _ffi.as_ptr(a, C.c_double), C.c_uint32(len(a)), C.c_double(min_posterior)))
+
+    def assign_batch(self, n_reads, ticket=0):
+        """(best uint32[n_reads], mapq uint8[n_reads]) of a collected, unreleased batch, copied (ticket 0: the batch wait() collected)"""
+        b, q = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        self._check(lib().groot_hip_assign_batch(self._h, C.c_uint64(ticket), C.byref(b), C.byref(q)))
+        if not n_reads:
+            return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+        return _ffi._np_view(b, n_reads, np.uint32).copy(), _ffi._np_view(q, n_reads, np.uint8).copy()
+
+    def assign_stats(self):
+        """groot_hip_assign_stats: {"reads", "assigned", "unassigned", "below", "ties", "records_in", "records_kept", "travs_emptied",
+        "launches"}; zeros while off, but for launches"""
+        st = host.AssignStats()
+        self._check(lib().groot_hip_assign_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def assign_reset(self):
+        self._check(lib().groot_hip_assign_reset(self._h))
 
     # ---- paired-end reads (groot_hip_pairs_*) ------------------------------------------------------
     def pairs_enable(self, on=True):

@@ -293,6 +293,12 @@ class ParallelReads:
     __del__ = close
 
 
+class ReadBatch(C.Structure):
+    """groot_read_batch"""
+    _fields_ = [("seq", C.c_void_p), ("qual", C.c_void_p), ("seq_off", C.c_void_p), ("names", C.c_void_p), ("name_off", C.c_void_p),
+                ("n_reads", C.c_uint32), ("first_read_id", C.c_uint32)]
+
+
 class BamWriter:
     """setupBAM + the record collector of theBoss (src/pipeline/boss.go:45-105,225-240)"""
 
@@ -326,6 +332,23 @@ class BamWriter:
             recs[i] = AlnRecord(name, len(name), _ffi.as_ptr(seq, C.c_uint8), _ffi.as_ptr(qual, C.c_uint8), seq_len, int(a["ref_id"]),
                                 int(a["pos"]), int(a["start_clip"]), int(a["end_clip"]), int(a["rc"]), int(a["secondary"]))
         _check(lib().groot_bam_write(self._h, recs, C.c_uint64(len(alns))))
+
+    def set_level(self, level):
+        """groot_bam_set_level: -1 = zlib default, 0..9, -2 = structural"""
+        _check(lib().groot_bam_set_level(self._h, C.c_int(level)))
+
+    def write_travs(self, travs, masks, batch, first_read_id=0):
+        """groot_bam_write_travs: traversal records (device.TRAV_DTYPE) + path sets [n, path_words] of reads held in `batch` (a
+        FastqReader batch dict) -> the number of records written.  MAPQ 30, or `reserved` where a traversal carries TRAV_MAPQ."""
+        t = np.ascontiguousarray(travs)
+        m = np.ascontiguousarray(masks, dtype=np.uint64)
+        arrs = [np.ascontiguousarray(batch[k], dtype=d) for k, d in (("seq", np.uint8), ("qual", np.uint8), ("seq_off", np.uint64), ("names", np.uint8),
+                                                                      ("name_off", np.uint64))]
+        rb = ReadBatch(*[a.ctypes.data for a in arrs], len(arrs[2]) - 1, first_read_id)
+        n = C.c_uint64(0)
+        _check(lib().groot_bam_write_travs(self._h, C.byref(self.index.view), C.byref(rb), t.ctypes.data_as(C.c_void_p), _ffi.as_ptr(m, C.c_uint64),
+                                           C.c_uint64(len(t)), C.byref(n)))
+        return n.value
 
     def close(self):
         if self._h:
@@ -707,3 +730,41 @@ def save_gfa(index, graph, kmer_freq, path_kept, node_removed, total_kmers, file
                                      _ffi.as_ptr(nr, C.c_uint8), C.c_uint64(total_kmers), timestamp.encode() if timestamp else None,
                                      file_name.encode(), C.byref(written)))
     return bool(written.value)
+
+
+# ---- assignment: each read to its best allele by EM posterior (groot_host.h "assignment") ----------------------------------
+class AssignStats(C.Structure):
+    """groot_assign_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "assigned", "unassigned", "below", "ties", "records_in", "records_kept", "travs_emptied", "launches")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def assign_travs(index, alpha, min_posterior, travs, masks, first_read_id, n_reads):
+    """groot_host_assign_travs: the definition on the CPU.  travs (device.TRAV_DTYPE, (read, ord) order) and masks [n, path_words] are
+    copied, not changed -> (travs, masks, best uint32[n_reads], mapq uint8[n_reads], stats dict without "launches")"""
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+    if len(alpha) != index.view.n_paths:
+        raise ValueError("alpha must have n_paths values")
+    t = np.array(travs, copy=True, order="C")
+    if t.dtype.itemsize != 20:
+        raise ValueError("travs must be groot_trav records")
+    m = np.array(masks, dtype=np.uint64, copy=True, order="C").reshape(len(t), index.view.path_words)
+    best = np.zeros(n_reads, dtype=np.uint32)
+    mapq = np.zeros(n_reads, dtype=np.uint8)
+    st = AssignStats()
+    _check(lib().groot_host_assign_travs(C.byref(index.view), _ffi.as_ptr(alpha, C.c_double), C.c_double(min_posterior), t.ctypes.data_as(C.c_void_p),
+                                         _ffi.as_ptr(m, C.c_uint64), C.c_uint64(len(t)), C.c_uint32(first_read_id), C.c_uint32(n_reads),
+                                         _ffi.as_ptr(best, C.c_uint32), _ffi.as_ptr(mapq, C.c_uint8), C.byref(st)))
+    d = st.as_dict()
+    del d["launches"]
+    return t, m, best, mapq, d
+
+
+def abundance_read(index, path):
+    """groot_host_abundance_read: an abundance file (4 or 8 columns) -> (alpha float64[n_paths], lines)"""
+    alpha = np.zeros(index.view.n_paths, dtype=np.float64)
+    n = C.c_uint64(0)
+    _check(lib().groot_host_abundance_read(C.byref(index.view), path.encode(), _ffi.as_ptr(alpha, C.c_double), C.byref(n)))
+    return alpha, n.value

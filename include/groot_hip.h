@@ -385,6 +385,52 @@ int groot_hip_acov_reset(groot_ctx *ctx);
 int groot_hip_acov_stats(groot_ctx *ctx, uint64_t *records, uint64_t *tuples, uint64_t *slots, uint64_t *grows, uint64_t *slow_records,
                          uint64_t *launches);
 
+/* ---- assignment: each read to its best allele by EM posterior --------------------------------------------------------------
+ * `align --assignFrom`: with the alpha of an earlier run's abundance estimate in hand, a batch keeps, per read, only the records on the
+ * path with the largest posterior, decided on the device before anything is copied out.  The definition (groot_host.h, README.md,
+ * DESIGN.md 14 and the tests quote it):
+ *
+ *   Input: alpha[n_paths] (global path = BAM reference order), every value finite and 0 <= alpha[p] <= 1e300; min_post in [0, 1].
+ *   S(r) exactly as for --sharedReads: the global paths carrying at least one record of read r.
+ *   For a read r with records, double precision, no FMA contraction, p running over S(r) in ASCENDING global ID:
+ *       denom = 0.0;  denom = denom + alpha[p]
+ *       best  = the p of S(r) with the largest alpha[p]; among equal values the lowest ID
+ *     unassigned:  denom == 0.0.                                   No record of r is kept.
+ *     below:       not (alpha[best] >= min_post * denom)           (one product, one comparison, no division).  No record of r is kept.
+ *     assigned:    otherwise.  Every record of r on `best` is kept (every traversal whose path set holds best; both strands), nothing else.
+ *       rest = denom - alpha[best]                                 (>= 0: a sum of non-negative terms is never below one of them)
+ *       j    = the number of k in 1..20 with ldexp(rest, k) <= denom   (a product by 2^k is exact; rest == 0 gives 20)
+ *       mapq = 3 * j                                               (0, 3, .., 60: one step per halving of the posterior mass elsewhere)
+ *   What happens to the batch's traversal records, in place, BEFORE anything else reads them:
+ *     the number of traversals, their order, read_id, graph_id, node, offset, ord and the RC / clip flags do not change;
+ *     a kept traversal's path set becomes {best} (every other bit of all its words cleared); a traversal that is not kept gets the EMPTY
+ *     path set (it expands to no record), loses GROOT_TRAV_FIRST and has reserved = 0;
+ *     GROOT_TRAV_FIRST is cleared on all of r's traversals and set on the first kept one in (read, ord) order: an assigned read has exactly
+ *     one primary record, its further records on `best` are secondary;
+ *     kept traversals get GROOT_TRAV_MAPQ (16u, new) and reserved = mapq.
+ *   Per read (batch position): best[r] = the global path, 0xFFFFFFFF when r keeps no record; mapq[r], 0 then.
+ *   groot_counts (mapped, multimapped, alignments, travs, ...), call counts, weights and the GFA are those of the unfiltered run.
+ *
+ * assign_kernel (kernels_assign.hpp) runs on the tail stream right behind the order stage's last scatter, one thread per read, so the
+ * compact copy-out, the packed records, report coverage and groot_hip_read_travs all see the filtered records; the result depends on
+ * alpha and the read's records alone, not on the batch size, the pipeline depth, the first-pass variant or the number of ctxs.  A batch
+ * is filtered, and counted in the stats, once: a pass that collect redoes by its redo, a batch that fails with GROOT_E_NOSPACE not at all
+ * (its records stay unfiltered, best = 0xFFFFFFFF).  Off by default: then no allocation, no launch, no sync. */
+/* Switch on with a copy of alpha[n_paths] (a second call replaces it), or off with alpha == NULL.  Only while nothing is in flight
+ * (GROOT_E_STATE).  GROOT_E_INVALID when n_paths is not the index's or a value or min_posterior is out of range.  GROOT_E_UNSUPPORTED
+ * while shared reads, equivalence classes, assigned coverage or pairing is on -- they count S(r), which assignment collapses --, and from
+ * their enable calls while assignment is on.  Report coverage is allowed and counts the kept records. */
+int groot_hip_assign_enable(groot_ctx *ctx, const double *alpha, uint32_t n_paths, double min_posterior);
+/* best[n_reads] / mapq[n_reads] of a collected, unreleased batch (ticket 0: the batch groot_hip_wait collected), in pinned host memory
+ * that stays valid until the batch is released; either pointer may be NULL.  GROOT_E_STATE when assignment is off or was off when the
+ * batch was submitted. */
+int groot_hip_assign_batch(groot_ctx *ctx, uint64_t ticket, const uint32_t **best, const uint8_t **mapq);
+/* The eight counters since enable / reset (replacing alpha keeps them) plus launches: kernels launched for assignment since the ctx was
+ * opened -- it does not move while the feature is off.  Zeros (but for launches) while off.  Waits for everything in flight. */
+int groot_hip_assign_stats(groot_ctx *ctx, groot_assign_stats *out);
+/* Zeroes the eight counters (after waiting for everything in flight).  No-op when off. */
+int groot_hip_assign_reset(groot_ctx *ctx);
+
 /* ---- paired-end reads -------------------------------------------------------------------------------------------------
  * With pairing on, reads 2i and 2i+1 of a batch are the mates of fragment i.  The index is batch-relative: read_id - first_read_id;
  * first_read_id may be odd.  Let A = S(r_2i) and B = S(r_2i+1), S(r) exactly as above.

@@ -122,6 +122,7 @@ typedef struct groot_trav {
 #define GROOT_TRAV_START_CLIP 2u  /* 1H before the M op (alignment.go:72-85)                          */
 #define GROOT_TRAV_END_CLIP 4u    /* 1H after the M op (alignment.go:87-103)                          */
 #define GROOT_TRAV_FIRST 8u       /* first traversal of its (read, graph) AlignRead call              */
+#define GROOT_TRAV_MAPQ 16u       /* assignment (below): `reserved` holds the MAPQ of the traversal's records */
 
 /* one sam.Record of AlignRead in id form (alignment.go:114-156) */
 typedef struct groot_aln {
@@ -202,6 +203,8 @@ typedef struct groot_read_batch {
     const uint64_t *name_off;      /* [n_reads+1]                                       */
     uint32_t n_reads, first_read_id;
 } groot_read_batch;
+/* MAPQ: 30 (alignment.go:143), or travs[i].reserved for the records of a traversal that carries GROOT_TRAV_MAPQ (assignment); a
+ * traversal with an empty path set writes no record.  The same holds for groot_bam_write_batch. */
 int groot_bam_write_travs(groot_bam *bam, const groot_index_view *idx, const groot_read_batch *batch, const groot_trav *travs,
                           const uint64_t *masks, uint64_t n_trav, uint64_t *n_records);
 int groot_bam_close(groot_bam *bam);
@@ -392,6 +395,54 @@ int groot_host_calls_from_table(const groot_index_view *idx, uint64_t n_ec, cons
  * what the device path writes whenever read names are unique.  *n_tuples (may be NULL) = distinct tuples of the table. */
 int groot_host_report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
                             uint64_t *n_called, uint64_t *n_tuples);
+
+/* ---- assignment: each read to its best allele by EM posterior ------------------------------------------------------------
+ * A second `align` pass keeps, per read, only the records on the path with the largest posterior of a first pass's abundance estimate
+ * (w(e,p) = alpha[p] / denom(e), so the argmax over S(r) is the argmax over alpha), each with a MAPQ derived from that posterior.  The
+ * definition (groot_hip.h, README.md, DESIGN.md 14 and the tests quote it):
+ *
+ *   Input: alpha[n_paths] (global path = BAM reference order), every value finite and 0 <= alpha[p] <= 1e300; min_post in [0, 1].
+ *   S(r) exactly as for --sharedReads: the global paths carrying at least one record of read r.
+ *   For a read r with records, double precision, no FMA contraction, p running over S(r) in ASCENDING global ID:
+ *       denom = 0.0;  denom = denom + alpha[p]
+ *       best  = the p of S(r) with the largest alpha[p]; among equal values the lowest ID
+ *     unassigned:  denom == 0.0.                                   No record of r is kept.
+ *     below:       not (alpha[best] >= min_post * denom)           (one product, one comparison, no division).  No record of r is kept.
+ *     assigned:    otherwise.  Every record of r on `best` is kept (every traversal whose path set holds best; both strands), nothing else.
+ *       rest = denom - alpha[best]                                 (>= 0: a sum of non-negative terms is never below one of them)
+ *       j    = the number of k in 1..20 with ldexp(rest, k) <= denom   (a product by 2^k is exact; rest == 0 gives 20)
+ *       mapq = 3 * j                                               (0, 3, .., 60: one step per halving of the posterior mass elsewhere)
+ *   What happens to the batch's traversal records, in place, BEFORE anything else reads them:
+ *     the number of traversals, their order, read_id, graph_id, node, offset, ord and the RC / clip flags do not change;
+ *     a kept traversal's path set becomes {best} (every other bit of all its words cleared); a traversal that is not kept gets the EMPTY
+ *     path set (it expands to no record), loses GROOT_TRAV_FIRST and has reserved = 0;
+ *     GROOT_TRAV_FIRST is cleared on all of r's traversals and set on the first kept one in (read, ord) order: an assigned read has exactly
+ *     one primary record, its further records on `best` are secondary;
+ *     kept traversals get GROOT_TRAV_MAPQ (16u, new) and reserved = mapq.
+ *   Per read (batch position): best[r] = the global path, 0xFFFFFFFF when r keeps no record; mapq[r], 0 then.
+ *   groot_counts (mapped, multimapped, alignments, travs, ...), call counts, weights and the GFA are those of the unfiltered run.
+ *
+ * The result depends on alpha and the read's records alone.  The library is built without -march: no product and sum are contracted. */
+typedef struct groot_assign_stats {
+    uint64_t reads;        /* reads with records                                                         */
+    uint64_t assigned, unassigned, below;
+    uint64_t ties;         /* assigned reads whose largest alpha is shared by two or more paths of S(r)  */
+    uint64_t records_in;   /* set bits of the path sets before                                           */
+    uint64_t records_kept; /* ... and after: one per kept traversal                                      */
+    uint64_t travs_emptied;
+    uint64_t launches;     /* device only: kernels launched for the feature since the ctx was opened; 0 from the host call */
+} groot_assign_stats;
+/* The definition on the CPU, in place: travs[n_trav] in (read, ord) order with masks[n_trav * path_words]; a read's batch position is
+ * read_id - first_read_id (< n_reads: GROOT_E_INVALID otherwise, as for alpha or min_posterior out of range and a traversal outside
+ * the index; likewise for a list out of order: batch positions that fall, so also a read whose traversals are not one run, or graphs
+ * that fall within a read).  best[n_reads], mapq[n_reads] and stats may be NULL.  libgroot_hip.so computes the same bytes (groot_hip_assign_enable). */
+int groot_host_assign_travs(const groot_index_view *idx, const double *alpha, double min_posterior, groot_trav *travs, uint64_t *masks,
+                            uint64_t n_trav, uint32_t first_read_id, uint32_t n_reads, uint32_t *best, uint8_t *mapq, groot_assign_stats *stats);
+/* Reads an abundance file (4 columns, or 8 with bootstraps): alpha_out[n_paths] = em_reads (column 3, strtod) of the path named in
+ * column 1 -- names as the report prints them, the '*' stripped --, 0 for paths the file does not name; *n_named (may be NULL) = its
+ * lines.  GROOT_E_FORMAT for an unknown name, a name given twice, a name two paths share after stripping, a value that is not a finite
+ * number in [0, 1e300], or a line with fewer than 3 columns; GROOT_E_IO when the file cannot be read. */
+int groot_host_abundance_read(const groot_index_view *idx, const char *path, double *alpha_out, uint64_t *n_named);
 
 #ifdef __cplusplus
 }
