@@ -76,6 +76,7 @@ struct Args {
     bool paired = false, interleaved = false;   // --paired / --interleaved: the FASTQ input is fragments (groot_reads_open_paired, groot_hip_pairs_enable)
     uint32_t bootstraps = 0;               // --bootstraps: replicates behind the four bootstrap columns of --abundance (0 = none)
     uint64_t boot_seed = 1;
+    bool call_support = false;             // --callSupport: three more columns of the calls file from the bootstrap replicates
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
     bool gpu_given = false, write_gob = false;
@@ -111,7 +112,7 @@ void usage()
             "                  [--gpu 0 | --gpus N] [--batch 1048576] [--maxReadLen 512] [--bam out.bam] [--bamLevel -2..9] [--stats f.json]\n"
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
             "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0]] [--noBam]\n"
-            "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0]]\n"
+            "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
@@ -122,6 +123,8 @@ void usage()
             "                   --calls: with --abundance, per line of the abundance file `name em_reads length depth breadth cigar called`: the pileup of\n"
             "                   the reads the EM assigns to the ARG (a record weighs its read's posterior on that ARG); a base is covered at depth >=\n"
             "                   --callDepth, called = 1 at breadth >= --covCutoff;\n"
+            "                   --callSupport: with --calls and --bootstraps, three more columns `support breadth_lo breadth_hi`: the pileup redone with\n"
+            "                   every replicate's estimate and draw counts, on the GPU; support = the share of replicates in which the ARG is called;\n"
             "                   --assignFrom: a second pass over the same reads with the abundance file of a first (`--abundance a.tsv --noBam`): per read only\n"
             "                   the records on the ARG with the largest em_reads among those the read lies on are kept (ties: the first in BAM header order),\n"
             "                   and only when its share of their sum is >= --minPosterior; MAPQ = 3 per halving of the share of the others, 0..60.  The filter\n"
@@ -131,8 +134,8 @@ void usage()
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
-            "                  [--bootstraps B [--bootSeed 1]] [-p N] [--calls c.tsv [--callDepth 1.0]]\n"
-            "                  (BAM from stdin unless --bamFile; --bootstraps: the same columns as align writes, computed on -p host threads)\n",
+            "                  [--bootstraps B [--bootSeed 1]] [-p N] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
+            "                  (BAM from stdin unless --bamFile; --bootstraps, --callSupport: the same columns as align writes, computed on -p host threads)\n",
             groot_host_version());
 }
 
@@ -173,6 +176,7 @@ Args parse(int argc, char **argv)
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--abundanceMin") a.abundance_min = atof(v().c_str());
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootstraps") a.bootstraps = (uint32_t)std::max(0l, atol(v().c_str()));
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootSeed") a.boot_seed = strtoull(v().c_str(), nullptr, 10);
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--callSupport") a.call_support = true;
         else if (a.cmd == "align" && f == "--assignFrom") a.assign_from = v();
         else if (a.cmd == "align" && f == "--minPosterior") {   // (it decides which reads are kept: a value that is no number is refused, not read as 0)
             const std::string t = v();
@@ -410,6 +414,8 @@ int run_align(const Args &a)   // cmd/align.go:54-163
                         "outside the intersection have no weight rule\n");
         return 1;
     }
+    if (a.call_support && !want_calls) { fprintf(stderr, "--callSupport adds columns to the calls file: it needs --calls\n"); return 1; }
+    if (a.call_support && !a.bootstraps) { fprintf(stderr, "--callSupport is computed from the bootstrap replicates: it needs --bootstraps\n"); return 1; }
     if (want_calls && a.cov_cutoff > 1.0) { fprintf(stderr, "supplied coverage cutoff exceeds 1.0 (100%%): %g\n", a.cov_cutoff); return 1; }
     if (a.no_bam && !want_report && !want_ab) { fprintf(stderr, "--noBam without --report would leave no output of the alignments\n"); return 1; }
     if (a.no_bam && !a.bam_out.empty()) { fprintf(stderr, "--noBam and --bam contradict each other\n"); return 1; }
@@ -862,11 +868,14 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     if (frags)
         logf("\tpaired-end input: %llu fragment(s), %llu joined, %llu split, %llu single", (unsigned long long)(received / 2), (unsigned long long)fr_joined,
              (unsigned long long)fr_split, (unsigned long long)fr_single);
+    // the bootstrap's canonical ECs, draw counts and estimates: --callSupport piles up the same replicates
+    std::vector<uint64_t> boot_off, boot_ec_cnt, boot_count;
+    std::vector<uint32_t> boot_ids;
+    std::vector<double> boot_alpha;
     if (want_ab) {
         uint64_t n_lines = 0;
         uint32_t iters = 0;
         auto t_em = std::chrono::steady_clock::now();
-        std::vector<double> boot_alpha;
         if (a.bootstraps) {
             // the replicates: drawn and fitted on the run's first GPU, over the merged ECs in canonical order
             auto t_boot = std::chrono::steady_clock::now();
@@ -876,9 +885,15 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             if (groot_host_ecs_canonical(v.n_paths, ec_cnt.size(), ec_off.data(), ec_ids.data(), ec_cnt.data(), c_off.data(), c_ids.data(), c_cnt.data(), &n_can))
                 die("%s", groot_host_last_error());
             boot_alpha.resize((size_t)a.bootstraps * v.n_paths);
+            if (a.call_support) boot_count.resize((size_t)a.bootstraps * n_can);
             if (groot_hip_em_bootstrap(gpus[0]->device, v.n_paths, n_can, c_off.data(), c_ids.data(), c_cnt.data(), a.bootstraps, a.boot_seed, 0, GROOT_EM_MIN_ITER,
-                                       GROOT_EM_MAX_ITER, nullptr, boot_alpha.data(), its.data()))
+                                       GROOT_EM_MAX_ITER, a.call_support ? boot_count.data() : nullptr, boot_alpha.data(), its.data()))
                 die("%s", groot_hip_last_error(nullptr));
+            if (a.call_support) {
+                boot_off.assign(c_off.begin(), c_off.begin() + n_can + 1);
+                boot_ids.assign(c_ids.begin(), c_ids.begin() + c_off[n_can]);
+                boot_ec_cnt.assign(c_cnt.begin(), c_cnt.begin() + n_can);
+            }
             logf("\tbootstrap: %u replicate(s) of %llu equivalence class(es) on GPU %d (seed %llu), EM of %u to %u iteration(s), %.3f s", a.bootstraps,
                  (unsigned long long)n_can, gpus[0]->device, (unsigned long long)a.boot_seed, *std::min_element(its.begin(), its.end()),
                  *std::max_element(its.begin(), its.end()), seconds_since(t_boot));
@@ -908,9 +923,35 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         std::vector<uint32_t> m_ids(s_ids + 1), m_tup(4 * s_tp + 4);
         uint64_t m_ec = 0, m_tp = 0, n_lines = 0, n_called = 0;
         if (groot_host_acov_merge(v.n_paths, (uint32_t)k, p_off.data(), p_ids.data(), p_cnt.data(), n_ec.data(), p_tup.data(), p_tn.data(), n_tp.data(), m_off.data(),
-                                  m_ids.data(), m_cnt.data(), m_tup.data(), m_tn.data(), &m_ec, &m_tp) ||
-            groot_host_calls_from_table(&v, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), nullptr, m_tp, m_tup.data(), m_tn.data(), a.abundance_min, a.call_depth,
-                                        a.cov_cutoff, a.calls_out.c_str(), &n_lines, &n_called))
+                                  m_ids.data(), m_cnt.data(), m_tup.data(), m_tn.data(), &m_ec, &m_tp))
+            die("%s", groot_host_last_error());
+        if (a.call_support && m_ec) {
+            // the replicates of --bootstraps, piled up on the run's first GPU; the merged table's ECs are the bootstrap's canonical ECs
+            auto t_sup = std::chrono::steady_clock::now();
+            if (m_ec != boot_ec_cnt.size() || !std::equal(boot_off.begin(), boot_off.end(), m_off.begin()) || !std::equal(boot_ids.begin(), boot_ids.end(), m_ids.begin()) ||
+                !std::equal(boot_ec_cnt.begin(), boot_ec_cnt.end(), m_cnt.begin()))
+                die("--callSupport: the equivalence classes of the calls table are not those of the bootstrap");
+            std::vector<double> alpha(v.n_paths);
+            if (groot_host_em(v.n_paths, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER, alpha.data(), nullptr))
+                die("%s", groot_host_last_error());
+            std::vector<uint32_t> sel;
+            for (uint32_t p = 0; p < v.n_paths; p++)
+                if (alpha[p] >= a.abundance_min) sel.push_back(p);
+            std::vector<uint32_t> covered((size_t)a.bootstraps * sel.size() + 1);
+            if (groot_hip_call_support(gpus[0]->device, v.n_paths, v.path_len, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), m_tp, m_tup.data(), m_tn.data(), a.bootstraps,
+                                       boot_count.data(), boot_alpha.data(), a.call_depth, (uint32_t)sel.size(), sel.data(), covered.data()))
+                die("%s", groot_hip_last_error(nullptr));
+            uint64_t rows = 0;
+            uint32_t width = 0;
+            groot_hip_call_support_info(&rows, &width, nullptr);
+            logf("\tcall support: %u replicate(s), %zu path(s), %llu row(s) of u%u on GPU %d in %.3f s", a.bootstraps, sel.size(), (unsigned long long)rows, 8 * width,
+                 gpus[0]->device, seconds_since(t_sup));
+            if (groot_host_calls_support_from_table(&v, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), alpha.data(), m_tp, m_tup.data(), m_tn.data(), a.abundance_min,
+                                                    a.call_depth, a.cov_cutoff, a.bootstraps, a.boot_seed, 1, boot_count.data(), boot_alpha.data(), covered.data(),
+                                                    a.calls_out.c_str(), &n_lines, &n_called))
+                die("%s", groot_host_last_error());
+        } else if (groot_host_calls_from_table(&v, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), nullptr, m_tp, m_tup.data(), m_tn.data(), a.abundance_min, a.call_depth,
+                                               a.cov_cutoff, a.calls_out.c_str(), &n_lines, &n_called))
             die("%s", groot_host_last_error());
         logf("\tcalls: %llu tuple(s) of (class, ARG, interval) from %zu context(s), %llu line(s), %llu called at depth >= %g over >= %.2f of the length, in %.3f s, written to %s",
              (unsigned long long)m_tp, k, (unsigned long long)n_lines, (unsigned long long)n_called, a.call_depth, a.cov_cutoff, seconds_since(t_calls), a.calls_out.c_str());
@@ -1050,6 +1091,8 @@ int run_report(const Args &a)
     logf("i am groot (version %s)", groot_host_version());
     logf("starting the report subcommand");
     logf("checking parameters...");
+    if (a.call_support && a.calls_out.empty()) die("--callSupport adds columns to the calls file: it needs --calls");
+    if (a.call_support && !a.bootstraps) die("--callSupport is computed from the bootstrap replicates: it needs --bootstraps");
     if (a.bam_file.empty()) logf("\tBAM file: using STDIN");
     else {
         if (!is_file(a.bam_file)) die("BAM file does not exist: %s", a.bam_file.c_str());
@@ -1093,7 +1136,11 @@ int run_report(const Args &a)
     if (!a.calls_out.empty()) {
         uint64_t n_called = 0, n_tuples = 0;
         auto t_calls = std::chrono::steady_clock::now();
-        if (groot_host_report_calls(bam, a.abundance_min, a.call_depth, a.cov_cutoff, a.calls_out.c_str(), &n_lines, &n_called, &n_tuples)) die("%s", groot_host_last_error());
+        if (a.call_support ? groot_host_report_calls_support(bam, a.abundance_min, a.call_depth, a.cov_cutoff, a.bootstraps, a.boot_seed, (uint32_t)std::max(1, a.proc),
+                                                             a.calls_out.c_str(), &n_lines, &n_called, &n_tuples)
+                           : groot_host_report_calls(bam, a.abundance_min, a.call_depth, a.cov_cutoff, a.calls_out.c_str(), &n_lines, &n_called, &n_tuples))
+            die("%s", groot_host_last_error());
+        if (a.call_support) logf("\tcall support: %u replicate(s) on %d host thread(s) (seed %llu)", a.bootstraps, std::max(1, a.proc), (unsigned long long)a.boot_seed);
         logf("\tcalls: %llu tuple(s) of (class, ARG, interval), %llu line(s), %llu called at depth >= %g over >= %.2f of the length, in %.3f s, written to %s",
              (unsigned long long)n_tuples, (unsigned long long)n_lines, (unsigned long long)n_called, a.call_depth, a.cov_cutoff, seconds_since(t_calls), a.calls_out.c_str());
     }

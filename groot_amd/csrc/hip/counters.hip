@@ -1,11 +1,12 @@
 // counters.hip -- the counters that run behind every batch's order stage, and their C ABI (include/groot_hip.h): report coverage
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
-// paired-end units, and the bootstrap replicates of the abundance EM (kernels_boot.hpp).  One of the five translation units of
+// paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp).  One of the five translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
+#include <cstdlib>
 #include <cstring>
 #include <iterator>
 #include <map>
@@ -18,6 +19,7 @@
 #include "kernels_assign.hpp"
 #include "kernels_boot.hpp"
 #include "kernels_cov.hpp"
+#include "kernels_csup.hpp"
 #include "kernels_ec.hpp"
 #include "kernels_shared.hpp"
 
@@ -1107,6 +1109,206 @@ int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const ui
         if (boot_count && ne) HIP_TRY(nullptr, hipMemcpyAsync(boot_count + (size_t)b0 * ne, d_cnt.p, (size_t)nb * ne * 8, hipMemcpyDeviceToHost, st));
         if (n_paths) HIP_TRY(nullptr, hipMemcpyAsync(alpha + (size_t)b0 * n_paths, d_alpha.p, (size_t)nb * n_paths * 8, hipMemcpyDeviceToHost, st));
         if (iterations) HIP_TRY(nullptr, hipMemcpyAsync(iterations + b0, d_it.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(nullptr, hipStreamSynchronize(st));
+    }
+    return GROOT_OK;
+}
+
+} // extern "C"
+
+// ---- bootstrap support for the calls (kernels_csup.hpp; the contract is in groot_host.h) -----------------------------------------
+namespace {
+constexpr uint64_t kCsupBytes = 1ull << 30;          // device memory of one chunk of paths' rows (GROOT_TEST_CSUP_BYTES)
+constexpr uint32_t kCsupGroupsPerLaunch = 32;        // groups of kCsupReps replicates in one csup_cover_kernel launch (grid.y)
+struct CsupInfo { uint64_t rows = 0; uint32_t width = 0, chunks = 0; };
+thread_local CsupInfo tl_csup_info;
+
+template <class T>
+int csup_run(hipStream_t st, const std::vector<uint32_t> &chunk_s, const std::vector<uint32_t> &path_row, const std::vector<uint64_t> &row_base,
+             const std::vector<uint32_t> &row_t, CsupFillArgs fa, CsupCoverArgs ca, uint32_t nb, size_t max_entries)
+{
+    DevBuf<T> d;
+    HIP_TRY(nullptr, d.alloc(max_entries));
+    for (size_t c = 0; c + 1 < chunk_s.size(); c++) {
+        const uint32_t s0 = chunk_s[c], s1 = chunk_s[c + 1], r0 = path_row[s0], r1 = path_row[s1];
+        const uint64_t base = row_base[r0], entries = row_base[r1] - base;
+        if (r1 > r0) {
+            HIP_TRY(nullptr, hipMemsetAsync(d.p, 0, entries * sizeof(T), st));
+            fa.chunk_base = base; fa.t0 = row_t[r0]; fa.t1 = row_t[r1];
+            if (fa.t1 > fa.t0) hipLaunchKernelGGL(csup_fill_kernel<T>, dim3(grid_for(fa.t1 - fa.t0)), dim3(kBlock), 0, st, fa, d.p);
+            hipLaunchKernelGGL(csup_scan_kernel<T>, dim3(grid_for(std::min<uint64_t>((uint64_t)(r1 - r0) * 64, 0xFFFFFFFFull))), dim3(kBlock), 0, st, fa.row_base, base,
+                               r0, r1, d.p);
+        }
+        ca.chunk_base = base; ca.s0 = s0;
+        const uint32_t groups = (nb + kCsupReps - 1) / kCsupReps;
+        for (uint32_t g0 = 0; g0 < groups; g0 += kCsupGroupsPerLaunch) {
+            ca.g0 = g0;
+            hipLaunchKernelGGL((csup_cover_kernel<T, kCsupReps>), dim3(s1 - s0, std::min(kCsupGroupsPerLaunch, groups - g0)), dim3(kBlock), 0, st, ca, d.p);
+        }
+        HIP_TRY(nullptr, hipGetLastError());
+    }
+    return GROOT_OK;
+}
+} // namespace
+
+extern "C" {
+
+void groot_hip_call_support_info(uint64_t *rows, uint32_t *width, uint32_t *chunks)
+{
+    if (rows) *rows = tl_csup_info.rows;
+    if (width) *width = tl_csup_info.width;
+    if (chunks) *chunks = tl_csup_info.chunks;
+}
+
+int groot_hip_call_support(int device, uint32_t n_paths, const uint32_t *path_len, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                           uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, uint32_t n_boot, const uint64_t *boot_count, const double *alpha,
+                           double call_depth, uint32_t n_sel, const uint32_t *sel_paths, uint32_t *covered_out)
+{
+    tl_csup_info = CsupInfo{};
+    if ((n_paths && !path_len) || (n_ec && (!off || !count || !boot_count)) || (n_paths && !alpha) || (n_tuples && (!tuples || !tn)) ||
+        (n_sel && (!sel_paths || !covered_out)))
+        return fail(nullptr, GROOT_E_INVALID, "null argument");
+    if (n_boot == 0) return fail(nullptr, GROOT_E_INVALID, "no bootstrap replicates");
+    if (n_ec >= 0xFFFFFFFFull || (n_ec && off[n_ec] >= 0xFFFFFFFFull) || n_tuples >= 0xFFFFFFFFull)
+        return fail(nullptr, GROOT_E_UNSUPPORTED, "call support on the device: 2^32 - 1 ECs, listed IDs or tuples and more");
+    const uint32_t ne = (uint32_t)n_ec;
+    std::vector<uint32_t> ec_off((size_t)ne + 1, 0);
+    for (uint32_t e = 0; e < ne; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return fail(nullptr, GROOT_E_INVALID, "EC %u: bad offsets", e);
+        if (count[e] == 0) return fail(nullptr, GROOT_E_INVALID, "EC %u has no reads", e);
+        for (uint64_t i = off[e]; i < off[e + 1]; i++)
+            if (ids[i] >= n_paths || (i > off[e] && ids[i] <= ids[i - 1])) return fail(nullptr, GROOT_E_INVALID, "EC %u: its IDs do not ascend inside the index", e);
+        ec_off[e + 1] = (uint32_t)off[e + 1];
+    }
+    const uint32_t listed = ne ? ec_off[ne] : 0;
+    if (ne && off[0] != 0) return fail(nullptr, GROOT_E_INVALID, "EC 0: bad offsets");
+    // the selection: sel_of[p] = the path's place in it (a path named twice gets two places: its rows are made twice)
+    for (uint32_t s = 0; s < n_sel; s++)
+        if (sel_paths[s] >= n_paths) return fail(nullptr, GROOT_E_INVALID, "selected path %u of %u", sel_paths[s], n_paths);
+    // the tuples checked, keyed by their listed-ID index (the pair (e, p)), grouped by it
+    struct Rec { uint32_t listed, pos, last; uint64_t n; };
+    std::vector<Rec> recs(n_tuples);
+    std::vector<uint32_t> per_listed((size_t)listed + 1, 0);
+    for (uint64_t i = 0; i < n_tuples; i++) {
+        const uint32_t e = tuples[4 * i], p = tuples[4 * i + 1], pos = tuples[4 * i + 2], last = tuples[4 * i + 3];
+        if (e >= ne) return fail(nullptr, GROOT_E_INVALID, "tuple %llu names EC %u of %u", (unsigned long long)i, e, ne);
+        const uint32_t *lo = ids + off[e], *hi = ids + off[e + 1], *at = std::lower_bound(lo, hi, p);
+        if (p >= n_paths || at == hi || *at != p) return fail(nullptr, GROOT_E_INVALID, "tuple %llu: path %u is not in EC %u", (unsigned long long)i, p, e);
+        if (last >= path_len[p]) return fail(nullptr, GROOT_E_INVALID, "a tuple of path %u ends at %u, the path has %u bases", p, last, path_len[p]);
+        recs[i] = Rec{(uint32_t)(at - ids), pos, last, tn[i]};
+        per_listed[recs[i].listed + 1]++;
+    }
+    for (uint32_t j = 0; j < listed; j++) per_listed[j + 1] += per_listed[j];       // tuples of listed ID j: [per_listed[j], per_listed[j + 1]) once sorted
+    {
+        std::vector<Rec> sorted(recs.size());
+        std::vector<uint32_t> at(per_listed.begin(), per_listed.end() - 1);
+        for (const Rec &r : recs) sorted[at[r.listed]++] = r;
+        recs.swap(sorted);
+    }
+    // path -> its listed IDs in canonical EC order (the CSR of the bootstrap, holding listed indices)
+    std::vector<uint32_t> path_off((size_t)n_paths + 1, 0);
+    for (uint32_t j = 0; j < listed; j++) path_off[ids[j] + 1]++;
+    for (uint32_t p = 0; p < n_paths; p++) path_off[p + 1] += path_off[p];
+    std::vector<uint32_t> path_listed(std::max<uint32_t>(listed, 1u));
+    {
+        std::vector<uint32_t> at(path_off.begin(), path_off.end() - 1);
+        for (uint32_t j = 0; j < listed; j++) path_listed[at[ids[j]]++] = j;
+    }
+    // rows: per selected path, its (e, p) with tuples, in that order; the tuples laid out row by row
+    std::vector<uint32_t> path_row((size_t)n_sel + 1, 0), sel_len(std::max<uint32_t>(n_sel, 1u), 0), row_listed, row_t{0}, t_row, t_pos, t_last;
+    std::vector<uint64_t> row_base{0}, t_n;
+    uint64_t max_sum = 0;
+    for (uint32_t s = 0; s < n_sel; s++) {
+        const uint32_t p = sel_paths[s];
+        sel_len[s] = path_len[p];
+        for (uint32_t k = path_off[p]; k < path_off[p + 1]; k++) {
+            const uint32_t j = path_listed[k];
+            if (per_listed[j] == per_listed[j + 1]) continue;
+            if (row_listed.size() >= 0xFFFFFFFEull || t_row.size() + (per_listed[j + 1] - per_listed[j]) >= 0xFFFFFFFFull)
+                return fail(nullptr, GROOT_E_UNSUPPORTED, "call support on the device: 2^32 - 1 rows or tuples and more");
+            uint64_t sum = 0;
+            for (uint32_t i = per_listed[j]; i < per_listed[j + 1]; i++) {
+                t_row.push_back((uint32_t)row_listed.size()); t_pos.push_back(recs[i].pos); t_last.push_back(recs[i].last); t_n.push_back(recs[i].n);
+                sum = sum + recs[i].n < sum ? ~0ull : sum + recs[i].n;
+            }
+            max_sum = std::max(max_sum, sum);
+            row_listed.push_back(j);
+            row_t.push_back((uint32_t)t_row.size());
+            row_base.push_back(row_base.back() + (uint64_t)path_len[p] + 1);
+        }
+        path_row[s + 1] = (uint32_t)row_listed.size();
+    }
+    const uint32_t n_rows = (uint32_t)row_listed.size();
+    const bool wide = max_sum >= (1ull << 32) || getenv("GROOT_TEST_CSUP_WIDE") != nullptr;
+    const size_t width = wide ? 8 : 4;
+    uint64_t budget = kCsupBytes;
+    if (const char *e = getenv("GROOT_TEST_CSUP_BYTES")) budget = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);
+    // chunks of whole paths under the budget
+    std::vector<uint32_t> chunk_s{0};
+    uint64_t max_entries = 0;
+    for (uint32_t s = 0, s0 = 0; s < n_sel; s++) {
+        const uint64_t with = row_base[path_row[s + 1]] - row_base[path_row[s0]];
+        if (s > s0 && with * width > budget) { chunk_s.push_back(s); s0 = s; }
+        max_entries = std::max(max_entries, row_base[path_row[s + 1]] - row_base[path_row[s0]]);
+        if (s + 1 == n_sel) chunk_s.push_back(n_sel);
+    }
+    tl_csup_info = CsupInfo{n_rows, (uint32_t)width, (uint32_t)chunk_s.size() - 1};
+    if (n_sel == 0) return GROOT_OK;
+
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(nullptr, GROOT_E_DEVICE, "no HIP device");
+    if (device < 0 || device >= n_dev) return fail(nullptr, GROOT_E_DEVICE, "device %d of %d", device, n_dev);
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    HIP_TRY(nullptr, hipSetDevice(device));
+    StreamGuard sg;
+    HIP_TRY(nullptr, hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    hipStream_t st = sg.s;
+
+    DevBuf<uint32_t> d_ec_off, d_ec_ids, d_path_row, d_sel_len, d_row_listed, d_t_row, d_t_pos, d_t_last, d_cov;
+    DevBuf<uint64_t> d_count, d_row_base, d_t_n;
+    DevBuf<unsigned long long> d_bc;
+    DevBuf<double> d_alpha, d_f;
+    auto up = [&](auto &buf, const auto *src, size_t n) -> hipError_t {
+        hipError_t e = buf.alloc(n);
+        if (e == hipSuccess && n) e = hipMemcpyAsync(buf.p, src, n * sizeof(*src), hipMemcpyHostToDevice, st);
+        return e;
+    };
+    HIP_TRY(nullptr, up(d_ec_off, ec_off.data(), ec_off.size()));
+    HIP_TRY(nullptr, up(d_ec_ids, ids, listed));
+    HIP_TRY(nullptr, up(d_count, count, ne));
+    HIP_TRY(nullptr, up(d_path_row, path_row.data(), path_row.size()));
+    HIP_TRY(nullptr, up(d_sel_len, sel_len.data(), n_sel));
+    HIP_TRY(nullptr, up(d_row_listed, row_listed.data(), row_listed.size()));
+    HIP_TRY(nullptr, up(d_row_base, row_base.data(), row_base.size()));
+    HIP_TRY(nullptr, up(d_t_row, t_row.data(), t_row.size()));
+    HIP_TRY(nullptr, up(d_t_pos, t_pos.data(), t_pos.size()));
+    HIP_TRY(nullptr, up(d_t_last, t_last.data(), t_last.size()));
+    HIP_TRY(nullptr, up(d_t_n, t_n.data(), t_n.size()));
+
+    // replicates in chunks that bound the device memory of counts, alpha, f and covered (as the bootstrap's)
+    const size_t per_rep = ((size_t)ne + n_paths + listed) * 8 + (size_t)n_sel * 4;
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)n_boot, (size_t)65535, kBootChunkBytes / std::max<size_t>(per_rep, 1)}));
+    HIP_TRY(nullptr, d_bc.alloc((size_t)chunk * ne));
+    HIP_TRY(nullptr, d_alpha.alloc((size_t)chunk * n_paths));
+    HIP_TRY(nullptr, d_f.alloc((size_t)chunk * listed));
+    HIP_TRY(nullptr, d_cov.alloc((size_t)chunk * n_sel));
+    for (uint32_t b0 = 0; b0 < n_boot; b0 += chunk) {
+        const uint32_t nb = std::min(chunk, n_boot - b0);
+        if (ne) HIP_TRY(nullptr, hipMemcpyAsync(d_bc.p, boot_count + (size_t)b0 * ne, (size_t)nb * ne * 8, hipMemcpyHostToDevice, st));
+        if (n_paths) HIP_TRY(nullptr, hipMemcpyAsync(d_alpha.p, alpha + (size_t)b0 * n_paths, (size_t)nb * n_paths * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(nullptr, hipMemsetAsync(d_cov.p, 0, (size_t)nb * n_sel * 4, st));
+        if (ne) {
+            CsupWeightArgs wa{d_ec_off.p, d_ec_ids.p, d_count.p, d_bc.p, d_alpha.p, d_f.p, ne, n_paths, nb};
+            hipLaunchKernelGGL(csup_weight_kernel, dim3(grid_for((uint32_t)std::min<uint64_t>((uint64_t)nb * ne, 0xFFFFFFFFull))), dim3(kBlock), 0, st, wa);
+            HIP_TRY(nullptr, hipGetLastError());
+        }
+        CsupFillArgs fa{d_t_row.p, d_t_pos.p, d_t_last.p, d_t_n.p, d_row_base.p, 0, 0, 0};
+        CsupCoverArgs ca{d_path_row.p, d_sel_len.p, d_row_listed.p, d_row_base.p, d_f.p, d_cov.p, 0, listed, call_depth, 0, n_sel, nb, 0};
+        if (int rc = wide ? csup_run<uint64_t>(st, chunk_s, path_row, row_base, row_t, fa, ca, nb, max_entries)
+                          : csup_run<uint32_t>(st, chunk_s, path_row, row_base, row_t, fa, ca, nb, max_entries))
+            return rc;
+        HIP_TRY(nullptr, hipMemcpyAsync(covered_out + (size_t)b0 * n_sel, d_cov.p, (size_t)nb * n_sel * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(nullptr, hipStreamSynchronize(st));
     }
     return GROOT_OK;

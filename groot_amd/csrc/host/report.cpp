@@ -721,9 +721,9 @@ double weight_of(const uint64_t *off, const uint32_t *ids, const double *alpha, 
     return alpha[p] / denom;
 }
 
-// D_p of the tuples [lo, hi) of path p (ordered by EC): per EC an integer difference array, then the weighted sum in EC order
-void depth_of(const std::vector<Tuple> &t, size_t lo, size_t hi, const uint64_t *off, const uint32_t *ids, const double *alpha, uint32_t p, uint32_t len,
-              std::vector<double> &D, std::vector<int64_t> &diff)
+// D_p of the tuples [lo, hi) of one path of length len (ordered by EC): per EC an integer difference array, then the weighted sum in
+// EC order, the weight of the group that starts at tuple i being weight(i)
+template <class W> void depth_weighted(const std::vector<Tuple> &t, size_t lo, size_t hi, uint32_t len, std::vector<double> &D, std::vector<int64_t> &diff, W weight)
 {
     D.assign(len, 0.0);
     for (size_t i = lo; i < hi;) {
@@ -734,7 +734,7 @@ void depth_of(const std::vector<Tuple> &t, size_t lo, size_t hi, const uint64_t 
             diff[t[j].pos] += (int64_t)t[j].n;
             diff[std::min<uint64_t>((uint64_t)t[j].last, (uint64_t)len - 1) + 1] -= (int64_t)t[j].n;
         }
-        const double w = weight_of(off, ids, alpha, t[i].ec, p);
+        const double w = weight(i);
         int64_t d = 0;
         for (uint32_t x = 0; x < len; x++) {
             d += diff[x];
@@ -745,12 +745,96 @@ void depth_of(const std::vector<Tuple> &t, size_t lo, size_t hi, const uint64_t 
     }
 }
 
+// D_p with the point estimate's weights w(e, p)
+void depth_of(const std::vector<Tuple> &t, size_t lo, size_t hi, const uint64_t *off, const uint32_t *ids, const double *alpha, uint32_t p, uint32_t len,
+              std::vector<double> &D, std::vector<int64_t> &diff)
+{
+    depth_weighted(t, lo, hi, len, D, diff, [&](size_t i) { return weight_of(off, ids, alpha, t[i].ec, p); });
+}
+
+// groot_host_call_support (groot_host.h "bootstrap support for the calls"): covered_b[p] of every replicate and selected path
+int call_support(uint32_t n_paths, const uint32_t *lens, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint64_t n_tuples,
+                 const uint32_t *tuples, const uint64_t *tn, uint32_t n_boot, const uint64_t *boot_count, const double *boot_alpha, double call_depth,
+                 uint32_t n_sel, const uint32_t *sel, uint32_t threads, uint32_t *covered)
+{
+    if ((n_paths && !lens) || (n_ec && (!off || !count || !boot_count)) || (n_paths && !boot_alpha) || (n_tuples && (!tuples || !tn)) ||
+        (n_sel && (!sel || !covered)))
+        return set_error(GROOT_E_INVALID, "null argument");
+    if (n_boot == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
+    for (uint64_t e = 0; e < n_ec; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
+        if (count[e] == 0) return set_error(GROOT_E_INVALID, "EC %llu has no reads", (unsigned long long)e);
+        for (uint64_t i = off[e]; i < off[e + 1]; i++)
+            if (ids[i] >= n_paths || (i > off[e] && ids[i] <= ids[i - 1])) return set_error(GROOT_E_INVALID, "EC %llu: its IDs do not ascend inside the index", (unsigned long long)e);
+    }
+    for (uint32_t s = 0; s < n_sel; s++)
+        if (sel[s] >= n_paths) return set_error(GROOT_E_INVALID, "selected path %u of %u", sel[s], n_paths);
+    std::vector<Tuple> t;
+    if (int rc = tuples_by_path(n_paths, n_ec, off, ids, n_tuples, tuples, tn, t)) return rc;
+    // per tuple the listed-ID index of its (EC, path); per path its range of tuples
+    std::vector<uint64_t> listed(t.size());
+    std::vector<size_t> first((size_t)n_paths + 1, 0);
+    for (size_t i = 0; i < t.size(); i++) {
+        if (t[i].last >= lens[t[i].path])
+            return set_error(GROOT_E_INVALID, "a tuple of path %u ends at %u, the path has %u bases", t[i].path, t[i].last, lens[t[i].path]);
+        listed[i] = (uint64_t)(std::lower_bound(ids + off[t[i].ec], ids + off[t[i].ec + 1], t[i].path) - ids);
+        first[(size_t)t[i].path + 1]++;
+    }
+    for (uint32_t p = 0; p < n_paths; p++) first[p + 1] += first[p];
+    const uint64_t n_listed = n_ec ? off[n_ec] : 0;
+    const double tolerance = std::nextafter(1.0, 2.0) - 1.0;
+    std::atomic<uint32_t> next_b{0};
+    auto work = [&]() {
+        std::vector<double> f(n_listed), D;
+        std::vector<int64_t> diff;
+        for (uint32_t b; (b = next_b.fetch_add(1)) < n_boot;) {
+            const uint64_t *bc = boot_count + (size_t)b * n_ec;
+            const double *alpha = boot_alpha + (size_t)b * n_paths;
+            for (uint64_t e = 0; e < n_ec; e++) {
+                double denom = 0.0;
+                for (uint64_t i = off[e]; i < off[e + 1]; i++) denom = denom + alpha[ids[i]];
+                const bool skip = bc[e] == 0 || denom < tolerance;
+                const double s = (double)bc[e] / (double)count[e];
+                for (uint64_t i = off[e]; i < off[e + 1]; i++) {
+                    const double w = skip ? 0.0 : alpha[ids[i]] / denom;
+                    f[i] = s * w;
+                }
+            }
+            for (uint32_t k = 0; k < n_sel; k++) {
+                const uint32_t p = sel[k], len = lens[p];
+                depth_weighted(t, first[p], first[(size_t)p + 1], len, D, diff, [&](size_t i) { return f[listed[i]]; });
+                uint32_t c = 0;
+                for (uint32_t x = 0; x < len; x++) c += D[x] >= call_depth ? 1u : 0u;
+                covered[(size_t)b * n_sel + k] = c;
+            }
+        }
+    };
+    const uint32_t nt = std::max(1u, std::min(threads, n_boot));
+    std::vector<std::thread> pool;
+    for (uint32_t i = 1; i < nt; i++) pool.emplace_back(work);
+    work();
+    for (auto &th : pool) th.join();
+    return GROOT_OK;
+}
+
+// the three support columns of the calls file: n replicates; boot_count[n][n_ec] and boot_alpha[n][n_paths] (used when both are given),
+// covered[n][lines]; whatever is NULL is computed here on `threads` host threads
+struct Support {
+    uint32_t n = 0;
+    uint64_t seed = 1;
+    uint32_t threads = 1;
+    const uint64_t *boot_count = nullptr;
+    const double *boot_alpha = nullptr;
+    const uint32_t *covered = nullptr;
+};
+
 // the calls file: a line per line of the abundance file (alpha >= min_reads, header order)
 int write_calls(uint32_t n_paths, const char *const *names, const uint32_t *name_len, const uint32_t *lens, uint64_t n_ec, const uint64_t *off, const uint32_t *ids,
                 const uint64_t *count, const double *alpha_in, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads, double call_depth,
-                double cov_cutoff, const char *out_path, uint64_t *n_lines, uint64_t *n_called)
+                double cov_cutoff, const char *out_path, uint64_t *n_lines, uint64_t *n_called, const Support *sup = nullptr)
 {
     if ((n_ec && (!off || !count)) || (n_tuples && (!tuples || !tn))) return set_error(GROOT_E_INVALID, "null argument");
+    if (sup && sup->n == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
     if (cov_cutoff > 1.0) return set_error(GROOT_E_INVALID, "supplied coverage cutoff exceeds 1.0 (100%%): %g", cov_cutoff);
     for (uint64_t e = 0; e < n_ec; e++) {
         if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
@@ -766,6 +850,33 @@ int write_calls(uint32_t n_paths, const char *const *names, const uint32_t *name
     }
     std::vector<Tuple> t;
     if (int rc = tuples_by_path(n_paths, n_ec, off, ids, n_tuples, tuples, tn, t)) return rc;
+    // with sup: covered[B][lines] of the replicates, over the paths that get a line
+    const uint32_t B = sup && n_ec ? sup->n : 0;
+    std::vector<uint32_t> sel, own_cov, v(B);
+    const uint32_t *cov_b = B ? sup->covered : nullptr;
+    if (B) {
+        for (uint32_t p = 0; p < n_paths; p++)
+            if (alpha[p] >= min_reads) sel.push_back(p);
+        if (!cov_b) {
+            std::vector<uint64_t> own_bc;
+            std::vector<double> own_ba;
+            const uint64_t *bc = sup->boot_count;
+            const double *ba = sup->boot_alpha;
+            if (!bc || !ba) {
+                own_bc.resize((size_t)B * n_ec);
+                own_ba.resize((size_t)B * n_paths);
+                if (int rc = groot_host_em_bootstrap(n_paths, n_ec, off, ids, count, B, sup->seed, 0, GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER, sup->threads,
+                                                     own_bc.data(), own_ba.data(), nullptr))
+                    return rc;
+                bc = own_bc.data(); ba = own_ba.data();
+            }
+            own_cov.resize((size_t)B * sel.size());
+            if (int rc = call_support(n_paths, lens, n_ec, off, ids, count, n_tuples, tuples, tn, B, bc, ba, call_depth, (uint32_t)sel.size(), sel.data(),
+                                      sup->threads, own_cov.data()))
+                return rc;
+            cov_b = own_cov.data();
+        }
+    }
     FILE *out = out_path ? fopen(out_path, "w") : stdout;
     if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
     uint64_t lines = 0, called = 0;
@@ -796,7 +907,20 @@ int write_calls(uint32_t n_paths, const char *const *names, const uint32_t *name
         const char *nm = names[p];
         size_t nl = name_len ? name_len[p] : strlen(nm);
         if (nl && nm[0] == '*') { nm++; nl--; }
-        fprintf(out, "%.*s\t%.2f\t%u\t%.2f\t%.4f\t%s\t%d\n", (int)nl, nm, alpha[p], len, depth, breadth, cigar.c_str(), is_called);
+        fprintf(out, "%.*s\t%.2f\t%u\t%.2f\t%.4f\t%s\t%d", (int)nl, nm, alpha[p], len, depth, breadth, cigar.c_str(), is_called);
+        if (B) {
+            // groot_host.h: support = the share of replicates that call p, the interval from the sorted covered counts
+            uint32_t yes = 0;
+            for (uint32_t b = 0; b < B; b++) {
+                v[b] = cov_b[(size_t)b * sel.size() + lines];
+                const double breadth_b = len ? (double)v[b] / (double)len : 0.0;
+                yes += breadth_b >= cov_cutoff ? 1u : 0u;
+            }
+            std::sort(v.begin(), v.end());
+            const uint32_t q = (uint32_t)((25ull * (B - 1)) / 1000);
+            fprintf(out, "\t%.3f\t%.4f\t%.4f", (double)yes / (double)B, len ? (double)v[q] / (double)len : 0.0, len ? (double)v[B - 1 - q] / (double)len : 0.0);
+        }
+        fputc('\n', out);
         lines++;
         called += is_called;
     }
@@ -870,9 +994,9 @@ extern "C" int groot_host_acov_depth(uint32_t n_paths, uint64_t n_ec, const uint
     return GROOT_OK;
 }
 
-extern "C" int groot_host_calls_from_table(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
-                                           const double *alpha, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads,
-                                           double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines, uint64_t *n_called)
+static int calls_from_table(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, const double *alpha,
+                            uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads, double call_depth, double cov_cutoff,
+                            const char *out_path, uint64_t *n_lines, uint64_t *n_called, const Support *sup)
 {
     if (!ix) return set_error(GROOT_E_INVALID, "null argument");
     const uint32_t n = ix->n_paths;
@@ -883,11 +1007,37 @@ extern "C" int groot_host_calls_from_table(const groot_index_view *ix, uint64_t 
         name_len[p] = ix->path_name_off[p + 1] - ix->path_name_off[p];
     }
     return write_calls(n, name_ptr.data(), name_len.data(), ix->path_len, n_ec, off, ids, count, alpha, n_tuples, tuples, tn, min_reads, call_depth, cov_cutoff,
-                       out_path, n_lines, n_called);
+                       out_path, n_lines, n_called, sup);
 }
 
-extern "C" int groot_host_report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
-                                       uint64_t *n_called, uint64_t *n_tuples)
+extern "C" int groot_host_calls_from_table(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                           const double *alpha, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads,
+                                           double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines, uint64_t *n_called)
+{
+    return calls_from_table(ix, n_ec, off, ids, count, alpha, n_tuples, tuples, tn, min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, nullptr);
+}
+
+extern "C" int groot_host_call_support(uint32_t n_paths, const uint32_t *path_len, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                       uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, uint32_t n_boot, const uint64_t *boot_count,
+                                       const double *alpha, double call_depth, uint32_t n_sel, const uint32_t *sel_paths, uint32_t threads, uint32_t *covered_out)
+{
+    return call_support(n_paths, path_len, n_ec, off, ids, count, n_tuples, tuples, tn, n_boot, boot_count, alpha, call_depth, n_sel, sel_paths, threads,
+                        covered_out);
+}
+
+extern "C" int groot_host_calls_support_from_table(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                                   const double *alpha, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads,
+                                                   double call_depth, double cov_cutoff, uint32_t n_boot, uint64_t seed, uint32_t threads,
+                                                   const uint64_t *boot_count, const double *boot_alpha, const uint32_t *covered, const char *out_path,
+                                                   uint64_t *n_lines, uint64_t *n_called)
+{
+    if (n_boot == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
+    const Support sup{n_boot, seed, threads, boot_count, boot_alpha, covered};
+    return calls_from_table(ix, n_ec, off, ids, count, alpha, n_tuples, tuples, tn, min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, &sup);
+}
+
+static int report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
+                        uint64_t *n_called, uint64_t *n_tuples, const Support *sup)
 {
     std::vector<uint64_t> read_ref;
     std::vector<std::string> names;
@@ -935,7 +1085,21 @@ extern "C" int groot_host_report_calls(const char *bam_path, double min_reads, d
     std::vector<const char *> name_ptr(names.size());
     for (size_t r = 0; r < names.size(); r++) name_ptr[r] = names[r].c_str();
     return write_calls((uint32_t)names.size(), name_ptr.data(), nullptr, lens.data(), m.size(), off.data(), ids.data(), count.data(), nullptr, t.size(), tup.data(),
-                       tn.data(), min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called);
+                       tn.data(), min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, sup);
+}
+
+extern "C" int groot_host_report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
+                                       uint64_t *n_called, uint64_t *n_tuples)
+{
+    return report_calls(bam_path, min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, n_tuples, nullptr);
+}
+
+extern "C" int groot_host_report_calls_support(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, uint32_t n_boot, uint64_t seed,
+                                               uint32_t threads, const char *out_path, uint64_t *n_lines, uint64_t *n_called, uint64_t *n_tuples)
+{
+    if (n_boot == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
+    const Support sup{n_boot, seed, threads, nullptr, nullptr, nullptr};
+    return report_calls(bam_path, min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, n_tuples, &sup);
 }
 
 // ---- reading an abundance file back (align --assignFrom; groot_host.h "assignment") ------------------------------------------

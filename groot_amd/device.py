@@ -129,6 +129,28 @@ def em_bootstrap(n_paths, off, ids, count, n_boot, seed=1, n_draws=0, min_iter=h
     return bc, alpha, its
 
 
+def call_support(n_paths, path_len, off, ids, count, tuples, tn, boot_count, alpha, sel_paths, call_depth=1.0, device=0):
+    """groot_hip_call_support: host.call_support on the device, bit for bit -> covered uint32[n_boot, n_sel]"""
+    path_len, off, ids, count, tuples, tn, n_boot, boot_count, alpha, sel = host._support_arrays(n_paths, path_len, off, ids, count, tuples, tn, boot_count,
+                                                                                                alpha, sel_paths)
+    cov = np.zeros((n_boot, len(sel)), dtype=np.uint32)
+    rc = lib().groot_hip_call_support(C.c_int(device), C.c_uint32(n_paths), _ffi.as_ptr(path_len, C.c_uint32), C.c_uint64(len(count)),
+                                      _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32), _ffi.as_ptr(count, C.c_uint64), C.c_uint64(len(tn)),
+                                      _ffi.as_ptr(tuples, C.c_uint32), _ffi.as_ptr(tn, C.c_uint64), C.c_uint32(n_boot), _ffi.as_ptr(boot_count, C.c_uint64),
+                                      _ffi.as_ptr(alpha, C.c_double), C.c_double(call_depth), C.c_uint32(len(sel)), _ffi.as_ptr(sel, C.c_uint32),
+                                      _ffi.as_ptr(cov, C.c_uint32))
+    if rc < 0:
+        raise GrootError(rc, lib().groot_hip_last_error(None).decode(errors="replace"))
+    return cov
+
+
+def call_support_info():
+    """what this thread's last call_support did: {"rows", "width" (bytes per integer: 4 or 8), "chunks" (of paths)}"""
+    r, w, c = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+    lib().groot_hip_call_support_info(C.byref(r), C.byref(w), C.byref(c))
+    return {"rows": r.value, "width": w.value, "chunks": c.value}
+
+
 class Aligner:
     """One groot_ctx: the replacement for theBoss.mapReads (src/pipeline/boss.go:108-242) on one GPU."""
 

@@ -629,6 +629,75 @@ def report_calls(bam_path, out_path, min_reads=1.0, call_depth=1.0, cov_cutoff=0
     return nl.value, nc.value, nt.value
 
 
+def _support_arrays(n_paths, path_len, off, ids, count, tuples, tn, boot_count, alpha, sel_paths):
+    off, ids, count = _ec_arrays(off, ids, count)
+    tuples, tn = _tuple_arrays(tuples, tn)
+    path_len = np.ascontiguousarray(path_len, dtype=np.uint32)
+    if len(path_len) != n_paths:
+        raise ValueError("path_len must have n_paths values")
+    boot_count = np.ascontiguousarray(boot_count, dtype=np.uint64)
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+    n_boot = alpha.shape[0] if alpha.ndim == 2 else 0
+    if alpha.shape != (n_boot, n_paths) or boot_count.shape != (n_boot, len(count)):
+        raise ValueError("boot_count must be [n_boot, n_ec] and alpha [n_boot, n_paths]")
+    sel = np.ascontiguousarray(sel_paths, dtype=np.uint32).reshape(-1)
+    return path_len, off, ids, count, tuples, tn, n_boot, boot_count, alpha, sel
+
+
+def call_support(n_paths, path_len, off, ids, count, tuples, tn, boot_count, alpha, sel_paths, call_depth=1.0, threads=1):
+    """groot_host_call_support: the covered bases of the paths sel_paths in every bootstrap replicate (boot_count [n_boot, n_ec] and
+    alpha [n_boot, n_paths] as em_bootstrap returns them) -> covered uint32[n_boot, n_sel]"""
+    path_len, off, ids, count, tuples, tn, n_boot, boot_count, alpha, sel = _support_arrays(n_paths, path_len, off, ids, count, tuples, tn, boot_count, alpha,
+                                                                                           sel_paths)
+    cov = np.zeros((n_boot, len(sel)), dtype=np.uint32)
+    _check(lib().groot_host_call_support(C.c_uint32(n_paths), _ffi.as_ptr(path_len, C.c_uint32), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64),
+                                         _ffi.as_ptr(ids, C.c_uint32), _ffi.as_ptr(count, C.c_uint64), C.c_uint64(len(tn)), _ffi.as_ptr(tuples, C.c_uint32),
+                                         _ffi.as_ptr(tn, C.c_uint64), C.c_uint32(n_boot), _ffi.as_ptr(boot_count, C.c_uint64), _ffi.as_ptr(alpha, C.c_double),
+                                         C.c_double(call_depth), C.c_uint32(len(sel)), _ffi.as_ptr(sel, C.c_uint32), C.c_uint32(threads),
+                                         _ffi.as_ptr(cov, C.c_uint32)))
+    return cov
+
+
+def calls_support_from_table(index, off, ids, count, tuples, tn, out_path, n_boot, seed=1, threads=1, alpha=None, boot_count=None, boot_alpha=None,
+                             covered=None, min_reads=1.0, call_depth=1.0, cov_cutoff=0.97):
+    """groot_host_calls_support_from_table: calls_from_table with the three support columns; boot_count / boot_alpha / covered None =
+    computed inside on `threads` host threads.  Returns (lines, called)."""
+    off, ids, count = _ec_arrays(off, ids, count)
+    tuples, tn = _tuple_arrays(tuples, tn)
+
+    def opt(a, dt, ct):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=dt)
+        return a, _ffi.as_ptr(a, ct)
+
+    alpha, p_alpha = opt(alpha, np.float64, C.c_double)
+    boot_count, p_bc = opt(boot_count, np.uint64, C.c_uint64)
+    boot_alpha, p_ba = opt(boot_alpha, np.float64, C.c_double)
+    covered, p_cov = opt(covered, np.uint32, C.c_uint32)
+    if boot_count is not None and boot_count.shape != (n_boot, len(count)):
+        raise ValueError("boot_count must be [n_boot, n_ec]")
+    if boot_alpha is not None and boot_alpha.shape != (n_boot, index.view.n_paths):
+        raise ValueError("boot_alpha must be [n_boot, n_paths]")
+    if covered is not None and (covered.ndim != 2 or covered.shape[0] != n_boot):
+        raise ValueError("covered must be [n_boot, lines]")
+    nl, nc = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().groot_host_calls_support_from_table(C.byref(index.view), C.c_uint64(len(count)), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                                     _ffi.as_ptr(count, C.c_uint64), p_alpha, C.c_uint64(len(tn)), _ffi.as_ptr(tuples, C.c_uint32),
+                                                     _ffi.as_ptr(tn, C.c_uint64), C.c_double(min_reads), C.c_double(call_depth), C.c_double(cov_cutoff),
+                                                     C.c_uint32(n_boot), C.c_uint64(seed), C.c_uint32(threads), p_bc, p_ba, p_cov, out_path.encode(),
+                                                     C.byref(nl), C.byref(nc)))
+    return nl.value, nc.value
+
+
+def report_calls_support(bam_path, out_path, n_boot, seed=1, threads=1, min_reads=1.0, call_depth=1.0, cov_cutoff=0.97):
+    """groot_host_report_calls_support: the calls file of a BAM with the three support columns.  Returns (lines, called, tuples)."""
+    nl, nc, nt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().groot_host_report_calls_support(bam_path.encode(), C.c_double(min_reads), C.c_double(call_depth), C.c_double(cov_cutoff), C.c_uint32(n_boot),
+                                                 C.c_uint64(seed), C.c_uint32(threads), out_path.encode(), C.byref(nl), C.byref(nc), C.byref(nt)))
+    return nl.value, nc.value, nt.value
+
+
 def _ec_arrays(off, ids, count):
     off = np.ascontiguousarray(off, dtype=np.uint64)
     ids = np.ascontiguousarray(ids, dtype=np.uint32)

@@ -476,6 +476,43 @@ int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const ui
                            uint32_t n_boot, uint64_t seed, uint64_t n_draws, uint32_t min_iter, uint32_t max_iter, uint64_t *boot_count,
                            double *alpha, uint32_t *iterations);
 
+/* ---- bootstrap support for the calls: per-replicate breadth ------------------------------------------------------------------
+ * groot_host_call_support (groot_host.h, "bootstrap support for the calls") on the device, covered_out as u32 bit for bit.  Quoted
+ * from there:
+ *
+ *   Inputs: canonical ECs (off, ids, count; count[e] > 0), the assigned-coverage table n(e,p,Pos,last), B >= 1 replicates:
+ *   boot_count[b][e] and alpha_b[n_paths] exactly as groot_host_em_bootstrap / groot_hip_em_bootstrap return them, callDepth, covCutoff.
+ *   d_e[x] for p in e: the number of records of (e,p,.,.) covering base x of p -- integers, as in §13.
+ *   For replicate b, EC e and p in e.  Double precision, no FMA contraction.
+ *       denom_b(e) = 0.0; denom_b(e) = denom_b(e) + alpha_b[q], q over e in ascending ID order
+ *       w_b(e,p)   = alpha_b[p] / denom_b(e);  0.0 when boot_count[b][e] == 0 or denom_b(e) < 2^-52 (the EM's skip)
+ *       s_b(e)     = (double)boot_count[b][e] / (double)count[e]            (one correctly rounded division)
+ *       f_b(e,p)   = s_b(e) * w_b(e,p)                                      (one product)
+ *       D_p^b[x]   = 0.0; D = D + (double)d_e[x] * f_b(e,p), over the ECs that hold p, in canonical EC order
+ *       covered_b[p] = the number of x in [0, path_len(p)) with D_p^b[x] >= callDepth                       (u32: the only thing the device returns)
+ *       called_b[p]  = ((double)covered_b[p] / (double)path_len(p) >= covCutoff), the writer's own expression; path_len 0: breadth 0.0
+ *   Per path over b = 0 .. B-1:   support = (double)(number of b with called_b[p]) / (double)B
+ *       v = covered_b[p] sorted ascending (integers), q = (25 * (B - 1)) / 1000 in integers (§11's rule)
+ *       breadth_lo = (double)v[q] / (double)path_len,  breadth_hi = (double)v[B-1-q] / (double)path_len
+ *   File: every line of the calls file gets three more tab-separated columns, "support (%.3f) \t breadth_lo (%.4f) \t breadth_hi (%.4f)"; the
+ *   lines, their order and their first seven columns are the calls file's, byte for byte.
+ *
+ * Needs no ctx: like groot_hip_em_bootstrap it runs on the device with that ordinal, on a stream and in buffers of its own that are
+ * freed on return, and may be called while ctxs have batches in flight.  Once, on the host: the tuples grouped by (e, p) into dense
+ * rows of path_len + 1 integers, rows of a path in canonical EC order.  On the device (kernels_csup.hpp): csup_fill_kernel adds
+ * +n at Pos and -n at last + 1 with integer atomics (u32 while every row's record sum is below 2^32, u64 otherwise or under
+ * GROOT_TEST_CSUP_WIDE=1) and csup_scan_kernel turns each row into d_e[x]; csup_weight_kernel computes f_b per (replicate, EC);
+ * csup_cover_kernel adds a path's rows in order for 8 replicates at a time and counts the covered bases.  Paths go in chunks of at
+ * most 1 GiB of rows (GROOT_TEST_CSUP_BYTES=<n> sets the budget; a path is never split), replicates in chunks as for the
+ * bootstrap; the result depends on neither.  Arguments and GROOT_E_INVALID as groot_host_call_support (no threads);
+ * GROOT_E_UNSUPPORTED at 2^32 - 1 listed IDs, rows or tuples and more; GROOT_E_DEVICE without that HIP device; the message is
+ * groot_hip_last_error(NULL). */
+int groot_hip_call_support(int device, uint32_t n_paths, const uint32_t *path_len, uint64_t n_ec, const uint64_t *off, const uint32_t *ids,
+                           const uint64_t *count, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, uint32_t n_boot, const uint64_t *boot_count,
+                           const double *alpha, double call_depth, uint32_t n_sel, const uint32_t *sel_paths, uint32_t *covered_out);
+/* What the last groot_hip_call_support of this thread did (for logs and probes): rows, bytes per integer (4 or 8), path chunks. */
+void groot_hip_call_support_info(uint64_t *rows, uint32_t *width, uint32_t *chunks);
+
 /* Fine-grained mirror of Sequence.RunMinHash(k, s, false, nil) (seqio.go:40-68) for a batch of
  * sequences in host memory: out[i*s .. (i+1)*s) = KHF sketch of sequence i.  Only while nothing is in flight. */
 int groot_hip_sketch(groot_ctx *ctx, const uint8_t *seq_concat, const uint64_t *seq_off, uint32_t n, uint64_t *out);

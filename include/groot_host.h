@@ -396,6 +396,51 @@ int groot_host_calls_from_table(const groot_index_view *idx, uint64_t n_ec, cons
 int groot_host_report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
                             uint64_t *n_called, uint64_t *n_tuples);
 
+/* ---- bootstrap support for the calls: per-replicate breadth ----------------------------------------------------------------
+ * How far to trust `called`: the pileup above is redone for every bootstrap replicate of the abundance estimate, and a line says in
+ * which share of the replicates the path is still called, and between which breadths it moves.  The definition (groot_hip.h,
+ * README.md, DESIGN.md 13 and the tests quote it):
+ *
+ *   Inputs: canonical ECs (off, ids, count; count[e] > 0), the assigned-coverage table n(e,p,Pos,last), B >= 1 replicates:
+ *   boot_count[b][e] and alpha_b[n_paths] exactly as groot_host_em_bootstrap / groot_hip_em_bootstrap return them, callDepth, covCutoff.
+ *   d_e[x] for p in e: the number of records of (e,p,.,.) covering base x of p -- integers, as in §13.
+ *   For replicate b, EC e and p in e.  Double precision, no FMA contraction.
+ *       denom_b(e) = 0.0; denom_b(e) = denom_b(e) + alpha_b[q], q over e in ascending ID order
+ *       w_b(e,p)   = alpha_b[p] / denom_b(e);  0.0 when boot_count[b][e] == 0 or denom_b(e) < 2^-52 (the EM's skip)
+ *       s_b(e)     = (double)boot_count[b][e] / (double)count[e]            (one correctly rounded division)
+ *       f_b(e,p)   = s_b(e) * w_b(e,p)                                      (one product)
+ *       D_p^b[x]   = 0.0; D = D + (double)d_e[x] * f_b(e,p), over the ECs that hold p, in canonical EC order
+ *       covered_b[p] = the number of x in [0, path_len(p)) with D_p^b[x] >= callDepth                       (u32: the only thing the device returns)
+ *       called_b[p]  = ((double)covered_b[p] / (double)path_len(p) >= covCutoff), the writer's own expression; path_len 0: breadth 0.0
+ *   Per path over b = 0 .. B-1:   support = (double)(number of b with called_b[p]) / (double)B
+ *       v = covered_b[p] sorted ascending (integers), q = (25 * (B - 1)) / 1000 in integers (§11's rule)
+ *       breadth_lo = (double)v[q] / (double)path_len,  breadth_hi = (double)v[B-1-q] / (double)path_len
+ *   File: every line of the calls file gets three more tab-separated columns, "support (%.3f) \t breadth_lo (%.4f) \t breadth_hi (%.4f)"; the
+ *   lines, their order and their first seven columns are the calls file's, byte for byte.
+ *
+ * s_b(e) is the expectation of resampling the reads of e given how often the replicate drew e; positions inside an EC are not
+ * resampled (a run keeps no per-read positions).  A term with d_e[x] == 0 leaves a non-negative D as it is: (e, p) without tuples
+ * are skipped.  Record sums per (e, p) below 2^63. */
+/* The definition itself, the replicates spread over `threads` (0 = 1): covered_out[n_boot][n_sel], the covered bases of the paths
+ * sel_paths[n_sel] (any paths, any order) in every replicate.  path_len[n_paths]; the table as for groot_host_calls_from_table;
+ * boot_count[n_boot][n_ec], alpha[n_boot][n_paths].  GROOT_E_INVALID: a tuple whose EC is outside the list, whose path is not in its
+ * EC or whose last >= path_len; n_boot = 0; an EC with count 0 or IDs that do not ascend; a selected path outside the index.
+ * groot_hip_call_support computes the same bits on the device. */
+int groot_host_call_support(uint32_t n_paths, const uint32_t *path_len, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                            uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, uint32_t n_boot, const uint64_t *boot_count, const double *alpha,
+                            double call_depth, uint32_t n_sel, const uint32_t *sel_paths, uint32_t threads, uint32_t *covered_out);
+/* groot_host_calls_from_table with the three support columns, through the same writer.  boot_count[n_boot][n_ec] and
+ * boot_alpha[n_boot][n_paths] = the replicates over these ECs with n_draws = 0 and GROOT_EM_MIN_ITER / GROOT_EM_MAX_ITER (used when
+ * both are given; else computed here with groot_host_em_bootstrap(seed, threads)); covered[n_boot][lines] = groot_host_call_support /
+ * groot_hip_call_support over the paths that get a line (alpha >= min_reads, ascending), NULL = computed here on `threads` threads. */
+int groot_host_calls_support_from_table(const groot_index_view *idx, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                                        const double *alpha, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double min_reads,
+                                        double call_depth, double cov_cutoff, uint32_t n_boot, uint64_t seed, uint32_t threads, const uint64_t *boot_count,
+                                        const double *boot_alpha, const uint32_t *covered, const char *out_path, uint64_t *n_lines, uint64_t *n_called);
+/* groot_host_report_calls with the three support columns, the replicates drawn, fitted and piled up on `threads` host threads. */
+int groot_host_report_calls_support(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, uint32_t n_boot, uint64_t seed,
+                                    uint32_t threads, const char *out_path, uint64_t *n_lines, uint64_t *n_called, uint64_t *n_tuples);
+
 /* ---- assignment: each read to its best allele by EM posterior ------------------------------------------------------------
  * A second `align` pass keeps, per read, only the records on the path with the largest posterior of a first pass's abundance estimate
  * (w(e,p) = alpha[p] / denom(e), so the argmax over S(r) is the argmax over alpha), each with a MAPQ derived from that posterior.  The
