@@ -68,3 +68,31 @@ def lib_path(name):
 
 def as_ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
+
+
+# ---- rarefaction curves (groot_host.h / groot_hip.h "rarefaction") ----
+_ECS = [C.c_uint32, C.c_uint64, u64p, u32p, u64p]          # n_paths, n_ec, off, ids, count
+_RAREFY_TAIL = [C.c_uint32, C.c_uint32, u64p, C.c_uint64, C.c_uint32, C.c_uint32]     # n_rep, n_depths, depths, seed, min_iter, max_iter
+_RAREFY_OUT = [u64p, f64p, u32p]                           # rare_count, alpha, iterations
+
+
+def rarefy_host_prototypes(L):
+    """argtypes of the rarefaction entry points of libgroot_host.so"""
+    L.groot_host_rarefy_depths.argtypes = [C.c_uint64, C.c_uint32, u64p]
+    L.groot_host_em_rarefy.argtypes = _ECS + _RAREFY_TAIL + [C.c_uint32] + _RAREFY_OUT
+    L.groot_host_rarefy_from_ecs.argtypes = ([C.POINTER(IndexView)] + _ECS[1:] + [C.c_double, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, u64p, f64p, C.c_int,
+                                             C.c_uint64, u32p, u64p, C.c_double, C.c_double, C.c_uint32, u32p, C.c_char_p, u64p])
+    L.groot_host_report_rarefy.argtypes = [C.c_char_p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_double, C.c_double, C.c_char_p, u64p, u32p]
+    for f in (L.groot_host_rarefy_depths, L.groot_host_em_rarefy, L.groot_host_rarefy_from_ecs, L.groot_host_report_rarefy):
+        f.restype = C.c_int
+
+
+def rarefy_hip_prototypes(L):
+    """argtypes of groot_hip_em_rarefy (libgroot_hip.so)"""
+    L.groot_hip_em_rarefy.argtypes = [C.c_int] + _ECS + _RAREFY_TAIL + _RAREFY_OUT
+    L.groot_hip_em_rarefy.restype = C.c_int
+
+
+def opt_ptr(arr, ctype):
+    """as_ptr, or a NULL pointer for None"""
+    return None if arr is None else as_ptr(arr, ctype)

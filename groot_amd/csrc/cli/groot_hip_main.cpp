@@ -77,6 +77,9 @@ struct Args {
     uint32_t bootstraps = 0;               // --bootstraps: replicates behind the four bootstrap columns of --abundance (0 = none)
     uint64_t boot_seed = 1;
     bool call_support = false;             // --callSupport: three more columns of the calls file from the bootstrap replicates
+    std::string rarefy_out;                // --rarefy: the rarefaction curve of --abundance (and --calls): nested subsamples without replacement
+    uint32_t rarefy_steps = GROOT_RAREFY_STEPS, rarefy_reps = GROOT_RAREFY_REPS;
+    uint64_t rarefy_seed = 1;
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
     bool gpu_given = false, write_gob = false;
@@ -113,6 +116,7 @@ void usage()
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
             "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0]] [--noBam]\n"
             "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
+            "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
@@ -125,6 +129,10 @@ void usage()
             "                   --callDepth, called = 1 at breadth >= --covCutoff;\n"
             "                   --callSupport: with --calls and --bootstraps, three more columns `support breadth_lo breadth_hi`: the pileup redone with\n"
             "                   every replicate's estimate and draw counts, on the GPU; support = the share of replicates in which the ARG is called;\n"
+            "                   --rarefy: with --abundance, the rarefaction curve `fraction units args_mean args_lo args_hi` (with --calls also\n"
+            "                   `called_mean called_lo called_hi`): the run's reads subsampled without replacement to s/--rarefySteps of its depth,\n"
+            "                   nested, --rarefyReps times (--rarefySeed), the estimate redone at every depth, drawn and fitted on the GPU: a curve\n"
+            "                   that has flattened says the sample was sequenced deeply enough;\n"
             "                   --assignFrom: a second pass over the same reads with the abundance file of a first (`--abundance a.tsv --noBam`): per read only\n"
             "                   the records on the ARG with the largest em_reads among those the read lies on are kept (ties: the first in BAM header order),\n"
             "                   and only when its share of their sum is >= --minPosterior; MAPQ = 3 per halving of the share of the others, 0..60.  The filter\n"
@@ -135,7 +143,9 @@ void usage()
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
             "                  [--bootstraps B [--bootSeed 1]] [-p N] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
-            "                  (BAM from stdin unless --bamFile; --bootstraps, --callSupport: the same columns as align writes, computed on -p host threads)\n",
+            "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
+            "                  (BAM from stdin unless --bamFile; --bootstraps, --callSupport, --rarefy: the same columns as align writes, computed on -p\n"
+            "                  host threads)\n",
             groot_host_version());
 }
 
@@ -177,6 +187,10 @@ Args parse(int argc, char **argv)
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootstraps") a.bootstraps = (uint32_t)std::max(0l, atol(v().c_str()));
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--bootSeed") a.boot_seed = strtoull(v().c_str(), nullptr, 10);
         else if ((a.cmd == "align" || a.cmd == "report") && f == "--callSupport") a.call_support = true;
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--rarefy") a.rarefy_out = v();
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--rarefySteps") a.rarefy_steps = (uint32_t)std::max(0l, atol(v().c_str()));
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--rarefyReps") a.rarefy_reps = (uint32_t)std::max(0l, atol(v().c_str()));
+        else if ((a.cmd == "align" || a.cmd == "report") && f == "--rarefySeed") a.rarefy_seed = strtoull(v().c_str(), nullptr, 10);
         else if (a.cmd == "align" && f == "--assignFrom") a.assign_from = v();
         else if (a.cmd == "align" && f == "--minPosterior") {   // (it decides which reads are kept: a value that is no number is refused, not read as 0)
             const std::string t = v();
@@ -378,6 +392,48 @@ struct Gpu {
     std::deque<WorkItem> pending;     // submitted, in order
 };
 
+// --rarefy of `align`: the drawn depths fitted (and with --calls piled up) on the run's first GPU, over canonical ECs; the file through the host writer
+void rarefy_on_gpu(const Args &a, const groot_index_view &v, int device, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *cnt, bool calls,
+                   uint64_t n_tp, const uint32_t *tup, const uint64_t *tn)
+{
+    auto t0 = std::chrono::steady_clock::now();
+    const uint32_t R = a.rarefy_reps, D = a.rarefy_steps;
+    uint64_t units = 0;
+    for (uint64_t e = 0; e < n_ec; e++) units += cnt[e];
+    std::vector<uint64_t> m(D), drawn;
+    if (groot_host_rarefy_depths(units, D, m.data())) die("%s", groot_host_last_error());
+    for (uint32_t s = 0; s + 1 < D; s++)
+        if (m[s]) drawn.push_back(m[s]);
+    const uint32_t K = (uint32_t)drawn.size();
+    std::vector<uint64_t> rc(calls ? (size_t)R * K * n_ec + 1 : 1);
+    std::vector<double> ra((size_t)R * K * v.n_paths + 1);
+    std::vector<uint32_t> its(std::max<size_t>((size_t)R * K, 1), 0), sel, covered;
+    if (K && groot_hip_em_rarefy(device, v.n_paths, n_ec, off, ids, cnt, R, K, drawn.data(), a.rarefy_seed, GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER,
+                                 calls ? rc.data() : nullptr, ra.data(), its.data()))
+        die("%s", groot_hip_last_error(nullptr));
+    if (K && calls) {
+        // every path detected at some depth of some replicate, ascending: the writer selects the same
+        std::vector<uint8_t> seen(v.n_paths, 0);
+        for (size_t x = 0; x < (size_t)R * K; x++)
+            for (uint32_t p = 0; p < v.n_paths; p++)
+                if (ra[x * v.n_paths + p] >= a.abundance_min) seen[p] = 1;
+        for (uint32_t p = 0; p < v.n_paths; p++)
+            if (seen[p]) sel.push_back(p);
+        covered.resize((size_t)R * K * sel.size() + 1);
+        if (!sel.empty() && groot_hip_call_support(device, v.n_paths, v.path_len, n_ec, off, ids, cnt, n_tp, tup, tn, R * K, rc.data(), ra.data(), a.call_depth,
+                                                   (uint32_t)sel.size(), sel.data(), covered.data()))
+            die("%s", groot_hip_last_error(nullptr));
+    }
+    uint64_t n_lines = 0;
+    if (groot_host_rarefy_from_ecs(&v, n_ec, off, ids, cnt, a.abundance_min, R, D, a.rarefy_seed, 1, calls && K ? rc.data() : nullptr, K ? ra.data() : nullptr,
+                                   calls ? 1 : 0, n_tp, tup, tn, a.call_depth, a.cov_cutoff, (uint32_t)sel.size(), sel.empty() ? nullptr : covered.data(),
+                                   a.rarefy_out.c_str(), &n_lines))
+        die("%s", groot_host_last_error());
+    logf("\trarefaction: %u step(s), %u replicate(s) of %llu unit(s) in %llu equivalence class(es) on GPU %d (seed %llu), EM of %u to %u iteration(s), %llu line(s)%s in %.3f s, written to %s",
+         D, R, (unsigned long long)units, (unsigned long long)n_ec, device, (unsigned long long)a.rarefy_seed, *std::min_element(its.begin(), its.end()),
+         *std::max_element(its.begin(), its.end()), (unsigned long long)n_lines, calls ? " with the called columns" : "", seconds_since(t0), a.rarefy_out.c_str());
+}
+
 int run_align(const Args &a)   // cmd/align.go:54-163
 {
     if (a.index_dir.empty()) { puts("please specify a directory with the index files (--indexDir)"); return 1; }
@@ -395,6 +451,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
     if (want_assign) {
         // the counters of S(r) see what assignment leaves of it -- one path per read
         const struct { bool on; const char *flag, *why; } refused[] = {
+            {!a.rarefy_out.empty(), "--rarefy", "it redoes the estimate of --abundance on subsamples, and an assigned read lies on one ARG: run it with the first pass"},
             {want_shared, "--sharedReads", "it counts the reads two ARGs share, and an assigned read lies on one ARG"},
             {want_ab, "--abundance", "it estimates from every ARG a read lies on, and an assigned read lies on one: run it as the first pass"},
             {want_calls, "--calls", "it weighs every record of a read, and an assigned read keeps the records on one ARG"},
@@ -407,6 +464,9 @@ int run_align(const Args &a)   // cmd/align.go:54-163
         if (!(a.min_posterior >= 0.0 && a.min_posterior <= 1.0)) { fprintf(stderr, "--minPosterior is a share: %g is not in [0, 1]\n", a.min_posterior); return 1; }
         if (!is_file(a.assign_from)) { fprintf(stderr, "--assignFrom: no file found at %s\n", a.assign_from.c_str()); return 1; }
     } else if (a.min_posterior != 0.0) { fprintf(stderr, "--minPosterior is the threshold of --assignFrom: it needs it\n"); return 1; }
+    const bool want_rarefy = !a.rarefy_out.empty();
+    if (want_rarefy && !want_ab) { fprintf(stderr, "--rarefy redoes the estimate of --abundance at every depth: it needs --abundance\n"); return 1; }
+    if (want_rarefy && (!a.rarefy_steps || !a.rarefy_reps)) { fprintf(stderr, "--rarefySteps and --rarefyReps must be at least 1\n"); return 1; }
     if (want_calls && !want_ab) { fprintf(stderr, "--calls has a line per line of the abundance file: it needs --abundance\n"); return 1; }
     if (want_calls && a.no_align) { fprintf(stderr, "--calls needs the exact alignments: it cannot be combined with --noAlign\n"); return 1; }
     if (want_calls && (a.paired || a.interleaved)) {
@@ -905,6 +965,15 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             die("%s", groot_host_last_error());
         logf("\tabundance: %llu equivalence class(es), EM of %u iteration(s) in %.3f s, %llu ARG(s) with at least %g reads written to %s",
              (unsigned long long)ec_cnt.size(), iters, seconds_since(t_em), (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
+        if (want_rarefy && !want_calls) {
+            // the curve of the abundance file alone: over the merged ECs in canonical order, as the bootstrap takes them
+            std::vector<uint64_t> c_off(ec_cnt.size() + 1), c_cnt(ec_cnt.size() + 1);
+            std::vector<uint32_t> c_ids(ec_ids.size() + 1);
+            uint64_t n_can = 0;
+            if (groot_host_ecs_canonical(v.n_paths, ec_cnt.size(), ec_off.data(), ec_ids.data(), ec_cnt.data(), c_off.data(), c_ids.data(), c_cnt.data(), &n_can))
+                die("%s", groot_host_last_error());
+            rarefy_on_gpu(a, v, gpus[0]->device, n_can, c_off.data(), c_ids.data(), c_cnt.data(), false, 0, nullptr, nullptr);
+        }
     }
     if (want_calls) {
         auto t_calls = std::chrono::steady_clock::now();
@@ -955,6 +1024,7 @@ int run_align(const Args &a)   // cmd/align.go:54-163
             die("%s", groot_host_last_error());
         logf("\tcalls: %llu tuple(s) of (class, ARG, interval) from %zu context(s), %llu line(s), %llu called at depth >= %g over >= %.2f of the length, in %.3f s, written to %s",
              (unsigned long long)m_tp, k, (unsigned long long)n_lines, (unsigned long long)n_called, a.call_depth, a.cov_cutoff, seconds_since(t_calls), a.calls_out.c_str());
+        if (want_rarefy) rarefy_on_gpu(a, v, gpus[0]->device, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), true, m_tp, m_tup.data(), m_tn.data());
     }
     if (want_report) {
         uint64_t n_rep = 0;
@@ -1093,6 +1163,8 @@ int run_report(const Args &a)
     logf("checking parameters...");
     if (a.call_support && a.calls_out.empty()) die("--callSupport adds columns to the calls file: it needs --calls");
     if (a.call_support && !a.bootstraps) die("--callSupport is computed from the bootstrap replicates: it needs --bootstraps");
+    if (!a.rarefy_out.empty() && a.abundance_out.empty()) die("--rarefy redoes the estimate of --abundance at every depth: it needs --abundance");
+    if (!a.rarefy_out.empty() && (!a.rarefy_steps || !a.rarefy_reps)) die("--rarefySteps and --rarefyReps must be at least 1");
     if (a.bam_file.empty()) logf("\tBAM file: using STDIN");
     else {
         if (!is_file(a.bam_file)) die("BAM file does not exist: %s", a.bam_file.c_str());
@@ -1143,6 +1215,16 @@ int run_report(const Args &a)
         if (a.call_support) logf("\tcall support: %u replicate(s) on %d host thread(s) (seed %llu)", a.bootstraps, std::max(1, a.proc), (unsigned long long)a.boot_seed);
         logf("\tcalls: %llu tuple(s) of (class, ARG, interval), %llu line(s), %llu called at depth >= %g over >= %.2f of the length, in %.3f s, written to %s",
              (unsigned long long)n_tuples, (unsigned long long)n_lines, (unsigned long long)n_called, a.call_depth, a.cov_cutoff, seconds_since(t_calls), a.calls_out.c_str());
+    }
+    if (!a.rarefy_out.empty()) {
+        auto t_rare = std::chrono::steady_clock::now();
+        uint32_t its[2] = {0, 0};
+        if (groot_host_report_rarefy(bam, a.abundance_min, a.rarefy_reps, a.rarefy_steps, a.rarefy_seed, (uint32_t)std::max(1, a.proc), a.calls_out.empty() ? 0 : 1,
+                                     a.call_depth, a.cov_cutoff, a.rarefy_out.c_str(), &n_lines, its))
+            die("%s", groot_host_last_error());
+        logf("\trarefaction: %u step(s), %u replicate(s) on %d host thread(s) (seed %llu), EM of %u to %u iteration(s), %llu line(s)%s in %.3f s, written to %s",
+             a.rarefy_steps, a.rarefy_reps, std::max(1, a.proc), (unsigned long long)a.rarefy_seed, its[0], its[1], (unsigned long long)n_lines,
+             a.calls_out.empty() ? "" : " with the called columns", seconds_since(t_rare), a.rarefy_out.c_str());
     }
     if (!spool.empty()) unlink(spool.c_str());
     logf("finished");

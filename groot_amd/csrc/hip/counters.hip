@@ -1,6 +1,7 @@
 // counters.hip -- the counters that run behind every batch's order stage, and their C ABI (include/groot_hip.h): report coverage
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
-// paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp).  One of the five translation units of
+// paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
+// draws (kernels_rare.hpp).  One of the five translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include "kernels_cov.hpp"
 #include "kernels_csup.hpp"
 #include "kernels_ec.hpp"
+#include "kernels_rare.hpp"
 #include "kernels_shared.hpp"
 
 using namespace groot;
@@ -1005,6 +1007,125 @@ struct StreamGuard {
 };
 constexpr size_t kBootChunkBytes = 256u << 20;      // device memory of one chunk of replicates (counts + alpha)
 constexpr uint32_t kBootDrawGroups = 2048;          // workgroups of one boot_resample_kernel launch, about
+
+// What groot_hip_em_bootstrap and groot_hip_em_rarefy share: the ECs checked and restated for the kernels, the device and a stream of
+// the call's own, the uploads, the buffers of one chunk of count vectors, and boot_em_kernel over such a chunk.  (Declared in the
+// order the pieces must go in reverse: the buffers are freed before the stream ends and the device is put back.)
+struct EmDevice {
+    DeviceGuard dg;
+    StreamGuard sg;
+    hipStream_t st = nullptr;
+    uint32_t n_paths = 0, ne = 0;
+    uint64_t total = 0;                              // N
+    std::vector<uint64_t> cum;
+    std::vector<uint32_t> ec_off, path_off, ec_ids, path_ecs;
+    DevBuf<uint64_t> d_cum;
+    DevBuf<uint32_t> d_ec_off, d_ec_ids, d_path_off, d_path_ecs, d_it;
+    DevBuf<unsigned long long> d_cnt;               // [chunk][n_ec]
+    DevBuf<double> d_alpha, d_scratch;
+    int lds_max = 0, n_cu = 1;
+    uint32_t chunk = 0, em_grid = 0;                 // count vectors of one chunk; workgroups of boot_em_kernel
+    size_t draw_lds = 0, em_lds = 0;
+    bool draw_in_lds = false, em_in_lds = false;
+
+    size_t per_vector() const { return ((size_t)ne + n_paths) * 8; }
+
+    // the EM's own errors, the limits of the device path, and the host side of the uploads
+    int check(const char *what, uint32_t paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t min_iter, uint32_t max_iter)
+    {
+        if (max_iter < min_iter)
+            return fail(nullptr, GROOT_E_INVALID, "number of EM iterations (%u) must be greater than minimum iterations (%u)", max_iter, min_iter);
+        if (max_iter < 1) return fail(nullptr, GROOT_E_INVALID, "no EM iterations were ran");
+        if (n_ec >= 0xFFFFFFFFull || (n_ec && off[n_ec] >= 0xFFFFFFFFull))
+            return fail(nullptr, GROOT_E_UNSUPPORTED, "%s on the device: 2^32 ECs or path IDs and more", what);
+        n_paths = paths;
+        ne = (uint32_t)n_ec;
+        cum.assign((size_t)ne + 1, 0);
+        ec_off.assign((size_t)ne + 1, 0);
+        path_off.assign((size_t)n_paths + 1, 0);
+        for (uint32_t e = 0; e < ne; e++) {
+            if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return fail(nullptr, GROOT_E_INVALID, "EC %u: bad offsets", e);
+            for (uint64_t i = off[e]; i < off[e + 1]; i++) {
+                if (ids[i] >= n_paths) return fail(nullptr, GROOT_E_INVALID, "EC %u holds path %u of %u", e, ids[i], n_paths);
+                path_off[ids[i] + 1]++;
+            }
+            ec_off[e + 1] = ec_off[e] + (uint32_t)(off[e + 1] - off[e]);
+            cum[e + 1] = cum[e] + count[e];
+            if (cum[e + 1] < cum[e]) return fail(nullptr, GROOT_E_INVALID, "the EC counts sum to 2^64 or more");
+        }
+        total = cum[ne];
+        // path -> EC, CSR: the ECs are visited in order, so every path's list ascends (an ID an EC names twice is listed twice, as the host adds it twice)
+        const uint32_t nnz = ec_off[ne];
+        for (uint32_t p = 0; p < n_paths; p++) path_off[p + 1] += path_off[p];
+        ec_ids.assign(std::max<uint32_t>(nnz, 1u), 0);
+        path_ecs.assign(std::max<uint32_t>(nnz, 1u), 0);
+        std::vector<uint32_t> at(path_off.begin(), path_off.end() - 1);
+        for (uint32_t e = 0; e < ne; e++)
+            for (uint64_t i = off[e]; i < off[e + 1]; i++) {
+                ec_ids[ec_off[e] + (i - off[e])] = ids[i];
+                path_ecs[at[ids[i]]++] = e;
+            }
+        return GROOT_OK;
+    }
+
+    // the device, the stream, the uploads and the buffers of a chunk: at most n_vec count vectors, a multiple of `group` (a chunk never
+    // splits a group of vectors that belong together), within kBootChunkBytes unless one group alone is larger
+    int open(int device, size_t n_vec, uint32_t group)
+    {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(nullptr, GROOT_E_DEVICE, "no HIP device");
+        if (device < 0 || device >= n_dev) return fail(nullptr, GROOT_E_DEVICE, "device %d of %d", device, n_dev);
+        if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+        HIP_TRY(nullptr, hipSetDevice(device));
+        HIP_TRY(nullptr, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+        HIP_TRY(nullptr, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+        n_cu = std::max(n_cu, 1);
+        HIP_TRY(nullptr, hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+        st = sg.s;
+
+        const size_t fit = std::max<size_t>(1, std::min<size_t>({n_vec, (size_t)65535, kBootChunkBytes / std::max<size_t>(per_vector(), 1)}));
+        chunk = (uint32_t)std::max<size_t>(group, fit / group * group);
+        HIP_TRY(nullptr, d_cum.alloc(cum.size()));
+        HIP_TRY(nullptr, d_ec_off.alloc(ec_off.size()));
+        HIP_TRY(nullptr, d_ec_ids.alloc(ec_ids.size()));
+        HIP_TRY(nullptr, d_path_off.alloc(path_off.size()));
+        HIP_TRY(nullptr, d_path_ecs.alloc(path_ecs.size()));
+        HIP_TRY(nullptr, d_cnt.alloc((size_t)chunk * ne));
+        HIP_TRY(nullptr, d_alpha.alloc((size_t)chunk * n_paths));
+        HIP_TRY(nullptr, d_it.alloc(chunk));
+        HIP_TRY(nullptr, hipMemcpyAsync(d_cum.p, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(nullptr, hipMemcpyAsync(d_ec_off.p, ec_off.data(), ec_off.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(nullptr, hipMemcpyAsync(d_ec_ids.p, ec_ids.data(), ec_ids.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(nullptr, hipMemcpyAsync(d_path_off.p, path_off.data(), path_off.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(nullptr, hipMemcpyAsync(d_path_ecs.p, path_ecs.data(), path_ecs.size() * 4, hipMemcpyHostToDevice, st));
+
+        // LDS or global memory: the cumulative table and the histogram of the draws; alpha and norm of the EM
+        draw_lds = ((size_t)ne + 1) * 8 + (size_t)ne * 4;
+        em_lds = per_vector();
+        draw_in_lds = draw_lds <= (size_t)lds_max;
+        em_in_lds = em_lds <= (size_t)lds_max;
+        if (em_in_lds && em_lds > 48 * 1024)
+            HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_em_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
+        em_grid = std::min<uint32_t>(chunk, (uint32_t)n_cu);
+        if (!em_in_lds) HIP_TRY(nullptr, d_scratch.alloc((size_t)em_grid * ((size_t)ne + n_paths)));
+        return GROOT_OK;
+    }
+
+    // the EM of the chunk's first nv count vectors, and their results to the host arrays' vectors v0 .. v0 + nv; waits for them
+    int em_and_fetch(size_t v0, uint32_t nv, uint32_t min_iter, uint32_t max_iter, uint64_t *counts, double *alpha, uint32_t *iterations)
+    {
+        BootEmArgs ea{d_ec_off.p, d_ec_ids.p, d_path_off.p, d_path_ecs.p, d_cnt.p, d_alpha.p, d_it.p, d_scratch.p, 1.0 / (double)n_paths, n_paths, ne, nv, min_iter, max_iter};
+        const dim3 grid(std::min<uint32_t>(nv, em_grid));
+        if (em_in_lds) hipLaunchKernelGGL(boot_em_kernel<true>, grid, dim3(kBootEmBlock), em_lds, st, ea);
+        else hipLaunchKernelGGL(boot_em_kernel<false>, grid, dim3(kBootEmBlock), 0, st, ea);
+        HIP_TRY(nullptr, hipGetLastError());
+        if (counts && ne) HIP_TRY(nullptr, hipMemcpyAsync(counts + v0 * ne, d_cnt.p, (size_t)nv * ne * 8, hipMemcpyDeviceToHost, st));
+        if (n_paths) HIP_TRY(nullptr, hipMemcpyAsync(alpha + v0 * n_paths, d_alpha.p, (size_t)nv * n_paths * 8, hipMemcpyDeviceToHost, st));
+        if (iterations) HIP_TRY(nullptr, hipMemcpyAsync(iterations + v0, d_it.p, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(nullptr, hipStreamSynchronize(st));
+        return GROOT_OK;
+    }
+};
 } // namespace
 
 int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_boot,
@@ -1012,104 +1133,82 @@ int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const ui
 {
     if ((n_ec && (!off || !count)) || (n_paths && !alpha)) return fail(nullptr, GROOT_E_INVALID, "null argument");
     if (n_boot == 0) return fail(nullptr, GROOT_E_INVALID, "no bootstrap replicates");
-    if (max_iter < min_iter)
-        return fail(nullptr, GROOT_E_INVALID, "number of EM iterations (%u) must be greater than minimum iterations (%u)", max_iter, min_iter);
-    if (max_iter < 1) return fail(nullptr, GROOT_E_INVALID, "no EM iterations were ran");
-    if (n_ec >= 0xFFFFFFFFull || (n_ec && off[n_ec] >= 0xFFFFFFFFull))
-        return fail(nullptr, GROOT_E_UNSUPPORTED, "bootstrap on the device: 2^32 ECs or path IDs and more");
-    const uint32_t ne = (uint32_t)n_ec;
-    std::vector<uint64_t> cum((size_t)ne + 1, 0);
-    std::vector<uint32_t> ec_off((size_t)ne + 1, 0), path_off((size_t)n_paths + 1, 0);
-    for (uint32_t e = 0; e < ne; e++) {
-        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return fail(nullptr, GROOT_E_INVALID, "EC %u: bad offsets", e);
-        for (uint64_t i = off[e]; i < off[e + 1]; i++) {
-            if (ids[i] >= n_paths) return fail(nullptr, GROOT_E_INVALID, "EC %u holds path %u of %u", e, ids[i], n_paths);
-            path_off[ids[i] + 1]++;
-        }
-        ec_off[e + 1] = ec_off[e] + (uint32_t)(off[e + 1] - off[e]);
-        cum[e + 1] = cum[e] + count[e];
-        if (cum[e + 1] < cum[e]) return fail(nullptr, GROOT_E_INVALID, "the EC counts sum to 2^64 or more");
-    }
-    const uint64_t total = cum[ne];
-    if (ne && total == 0) return fail(nullptr, GROOT_E_INVALID, "bootstrap over ECs without reads");
-    if (n_draws == 0) n_draws = total;
-    // path -> EC, CSR: the ECs are visited in order, so every path's list ascends (an ID an EC names twice is listed twice, as the host adds it twice)
-    const uint32_t nnz = ec_off[ne];
-    for (uint32_t p = 0; p < n_paths; p++) path_off[p + 1] += path_off[p];
-    std::vector<uint32_t> ec_ids(std::max<uint32_t>(nnz, 1u)), path_ecs(std::max<uint32_t>(nnz, 1u)), at(path_off.begin(), path_off.end() - 1);
-    for (uint32_t e = 0; e < ne; e++)
-        for (uint64_t i = off[e]; i < off[e + 1]; i++) {
-            ec_ids[ec_off[e] + (i - off[e])] = ids[i];
-            path_ecs[at[ids[i]]++] = e;
-        }
-
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(nullptr, GROOT_E_DEVICE, "no HIP device");
-    if (device < 0 || device >= n_dev) return fail(nullptr, GROOT_E_DEVICE, "device %d of %d", device, n_dev);
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    HIP_TRY(nullptr, hipSetDevice(device));
-    int lds_max = 0, n_cu = 0;
-    HIP_TRY(nullptr, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
-    HIP_TRY(nullptr, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
-    n_cu = std::max(n_cu, 1);
-    StreamGuard sg;
-    HIP_TRY(nullptr, hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    hipStream_t st = sg.s;
-
-    const size_t per_rep = ((size_t)ne + n_paths) * 8;
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)n_boot, (size_t)65535, kBootChunkBytes / std::max<size_t>(per_rep, 1)}));
-    DevBuf<uint64_t> d_cum;
-    DevBuf<uint32_t> d_ec_off, d_ec_ids, d_path_off, d_path_ecs, d_it;
-    DevBuf<unsigned long long> d_cnt;
-    DevBuf<double> d_alpha, d_scratch;
-    HIP_TRY(nullptr, d_cum.alloc(cum.size()));
-    HIP_TRY(nullptr, d_ec_off.alloc(ec_off.size()));
-    HIP_TRY(nullptr, d_ec_ids.alloc(ec_ids.size()));
-    HIP_TRY(nullptr, d_path_off.alloc(path_off.size()));
-    HIP_TRY(nullptr, d_path_ecs.alloc(path_ecs.size()));
-    HIP_TRY(nullptr, d_cnt.alloc((size_t)chunk * ne));
-    HIP_TRY(nullptr, d_alpha.alloc((size_t)chunk * n_paths));
-    HIP_TRY(nullptr, d_it.alloc(chunk));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_cum.p, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_ec_off.p, ec_off.data(), ec_off.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_ec_ids.p, ec_ids.data(), ec_ids.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_path_off.p, path_off.data(), path_off.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(nullptr, hipMemcpyAsync(d_path_ecs.p, path_ecs.data(), path_ecs.size() * 4, hipMemcpyHostToDevice, st));
-
-    // LDS or global memory: the cumulative table and the histogram of the draws; alpha and norm of the EM
-    const size_t draw_lds = ((size_t)ne + 1) * 8 + (size_t)ne * 4, em_lds = per_rep;
-    const bool draw_in_lds = draw_lds <= (size_t)lds_max, em_in_lds = em_lds <= (size_t)lds_max;
-    if (draw_in_lds && draw_lds > 48 * 1024)
-        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_resample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)draw_lds));
-    if (em_in_lds && em_lds > 48 * 1024)
-        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_em_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
-    const uint32_t em_grid = std::min<uint32_t>(chunk, (uint32_t)n_cu);
-    if (!em_in_lds) HIP_TRY(nullptr, d_scratch.alloc((size_t)em_grid * ((size_t)ne + n_paths)));
+    EmDevice em;
+    if (int rc = em.check("bootstrap", n_paths, n_ec, off, ids, count, min_iter, max_iter)) return rc;
+    const uint32_t ne = em.ne;
+    if (ne && em.total == 0) return fail(nullptr, GROOT_E_INVALID, "bootstrap over ECs without reads");
+    if (n_draws == 0) n_draws = em.total;
+    if (int rc = em.open(device, n_boot, 1)) return rc;
+    hipStream_t st = em.st;
+    if (em.draw_in_lds && em.draw_lds > 48 * 1024)
+        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)boot_resample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em.draw_lds));
 
     constexpr uint64_t kChunkDraws = (uint64_t)kBootDrawBlock * kBootDrawsPerThread;
     const uint64_t draw_chunks = (n_draws + kChunkDraws - 1) / kChunkDraws;
-    for (uint32_t b0 = 0; b0 < n_boot; b0 += chunk) {
-        const uint32_t nb = std::min(chunk, n_boot - b0);
+    for (uint32_t b0 = 0; b0 < n_boot; b0 += em.chunk) {
+        const uint32_t nb = std::min(em.chunk, n_boot - b0);
         if (ne) {
-            HIP_TRY(nullptr, hipMemsetAsync(d_cnt.p, 0, (size_t)nb * ne * 8, st));
+            HIP_TRY(nullptr, hipMemsetAsync(em.d_cnt.p, 0, (size_t)nb * ne * 8, st));
             if (draw_chunks) {
-                BootDrawArgs da{d_cum.p, d_cnt.p, total, n_draws, seed, ne, b0};
+                BootDrawArgs da{em.d_cum.p, em.d_cnt.p, em.total, n_draws, seed, ne, b0};
                 const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(draw_chunks, (kBootDrawGroups + nb - 1) / nb)), nb);
-                if (draw_in_lds) hipLaunchKernelGGL(boot_resample_kernel<true>, grid, dim3(kBootDrawBlock), draw_lds, st, da);
+                if (em.draw_in_lds) hipLaunchKernelGGL(boot_resample_kernel<true>, grid, dim3(kBootDrawBlock), em.draw_lds, st, da);
                 else hipLaunchKernelGGL(boot_resample_kernel<false>, grid, dim3(kBootDrawBlock), 0, st, da);
                 HIP_TRY(nullptr, hipGetLastError());
             }
         }
-        BootEmArgs ea{d_ec_off.p, d_ec_ids.p, d_path_off.p, d_path_ecs.p, d_cnt.p, d_alpha.p, d_it.p, d_scratch.p, 1.0 / (double)n_paths, n_paths, ne, nb, min_iter, max_iter};
-        const dim3 grid(std::min<uint32_t>(nb, em_grid));
-        if (em_in_lds) hipLaunchKernelGGL(boot_em_kernel<true>, grid, dim3(kBootEmBlock), em_lds, st, ea);
-        else hipLaunchKernelGGL(boot_em_kernel<false>, grid, dim3(kBootEmBlock), 0, st, ea);
+        if (int rc = em.em_and_fetch(b0, nb, min_iter, max_iter, boot_count, alpha, iterations)) return rc;
+    }
+    return GROOT_OK;
+}
+
+// ---- rarefaction: nested subsamples without replacement, the EM at every depth (kernels_rare.hpp; the contract is in groot_host.h) ----
+int groot_hip_em_rarefy(int device, uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_rep,
+                        uint32_t n_depths, const uint64_t *depths, uint64_t seed, uint32_t min_iter, uint32_t max_iter, uint64_t *rare_count, double *alpha,
+                        uint32_t *iterations)
+{
+    if ((n_ec && (!off || !count)) || (n_paths && !alpha) || (n_depths && !depths)) return fail(nullptr, GROOT_E_INVALID, "null argument");
+    if (n_rep == 0) return fail(nullptr, GROOT_E_INVALID, "no rarefaction replicates");
+    if (n_depths == 0) return fail(nullptr, GROOT_E_INVALID, "no rarefaction depths");
+    EmDevice em;
+    if (int rc = em.check("rarefaction", n_paths, n_ec, off, ids, count, min_iter, max_iter)) return rc;
+    const uint32_t ne = em.ne;
+    if (em.total == 0) return fail(nullptr, GROOT_E_INVALID, "rarefaction over ECs without reads");
+    if (em.total >= kRareMaxUnits) return fail(nullptr, GROOT_E_UNSUPPORTED, "rarefaction: 2^62 units and more");
+    for (uint32_t d = 0; d < n_depths; d++) {
+        if (depths[d] == 0 || depths[d] > em.total)
+            return fail(nullptr, GROOT_E_INVALID, "rarefaction depth %u is %llu: not in [1, %llu]", d, (unsigned long long)depths[d], (unsigned long long)em.total);
+        if (d && depths[d] < depths[d - 1]) return fail(nullptr, GROOT_E_INVALID, "rarefaction depth %u is below depth %u", d, d - 1);
+    }
+    // a replicate's depths stay in one chunk (rare_cumsum_kernel adds along them) and in one launch's grid rows
+    if (n_depths > 65535 || (uint64_t)n_depths * em.per_vector() > (4ull << 30) || (uint64_t)n_rep * n_depths > 0xFFFFFFFFull)
+        return fail(nullptr, GROOT_E_UNSUPPORTED, "rarefaction on the device: %u depths of %zu bytes each", n_depths, em.per_vector());
+    if (int rc = em.open(device, (size_t)n_rep * n_depths, n_depths)) return rc;
+    hipStream_t st = em.st;
+    if (em.draw_in_lds && em.draw_lds > 48 * 1024)
+        HIP_TRY(nullptr, hipFuncSetAttribute((const void *)rare_draw_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em.draw_lds));
+    DevBuf<uint64_t> d_depths;
+    HIP_TRY(nullptr, d_depths.alloc(n_depths));
+    HIP_TRY(nullptr, hipMemcpyAsync(d_depths.p, depths, (size_t)n_depths * 8, hipMemcpyHostToDevice, st));
+
+    // grid.x: the chunks of the longest depth interval, about kBootDrawGroups workgroups a launch (a workgroup past its own interval leaves at once)
+    constexpr uint64_t kChunkDraws = (uint64_t)kBootDrawBlock * kBootDrawsPerThread;
+    uint64_t longest = depths[0];
+    for (uint32_t d = 1; d < n_depths; d++) longest = std::max(longest, depths[d] - depths[d - 1]);
+    const uint64_t draw_chunks = (longest + kChunkDraws - 1) / kChunkDraws;
+    const uint32_t reps_per_chunk = em.chunk / n_depths, half_bits = rare_half_bits(em.total);
+    for (uint32_t b0 = 0; b0 < n_rep; b0 += reps_per_chunk) {
+        const uint32_t nb = std::min(reps_per_chunk, n_rep - b0), nv = nb * n_depths;
+        HIP_TRY(nullptr, hipMemsetAsync(em.d_cnt.p, 0, (size_t)nv * ne * 8, st));
+        RareDrawArgs da{em.d_cum.p, d_depths.p, em.d_cnt.p, em.total, seed, ne, n_depths, b0, half_bits};
+        const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(draw_chunks, (kBootDrawGroups + nv - 1) / nv)), nv);
+        if (em.draw_in_lds) hipLaunchKernelGGL(rare_draw_kernel<true>, grid, dim3(kBootDrawBlock), em.draw_lds, st, da);
+        else hipLaunchKernelGGL(rare_draw_kernel<false>, grid, dim3(kBootDrawBlock), 0, st, da);
+        if (n_depths > 1)
+            hipLaunchKernelGGL(rare_cumsum_kernel, dim3(grid_for((uint32_t)std::min<uint64_t>((uint64_t)nb * ne, 0xFFFFFFFFull))), dim3(kBlock), 0, st, em.d_cnt.p, nb,
+                               n_depths, ne);
         HIP_TRY(nullptr, hipGetLastError());
-        if (boot_count && ne) HIP_TRY(nullptr, hipMemcpyAsync(boot_count + (size_t)b0 * ne, d_cnt.p, (size_t)nb * ne * 8, hipMemcpyDeviceToHost, st));
-        if (n_paths) HIP_TRY(nullptr, hipMemcpyAsync(alpha + (size_t)b0 * n_paths, d_alpha.p, (size_t)nb * n_paths * 8, hipMemcpyDeviceToHost, st));
-        if (iterations) HIP_TRY(nullptr, hipMemcpyAsync(iterations + b0, d_it.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(nullptr, hipStreamSynchronize(st));
+        if (int rc = em.em_and_fetch((size_t)b0 * n_depths, nv, min_iter, max_iter, rare_count, alpha, iterations)) return rc;
     }
     return GROOT_OK;
 }

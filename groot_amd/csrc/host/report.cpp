@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "host_common.hpp"
+#include "../common/rare_perm.hpp"
 
 using namespace groot;
 
@@ -1036,14 +1037,19 @@ extern "C" int groot_host_calls_support_from_table(const groot_index_view *ix, u
     return calls_from_table(ix, n_ec, off, ids, count, alpha, n_tuples, tuples, tn, min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, &sup);
 }
 
-static int report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
-                        uint64_t *n_called, uint64_t *n_tuples, const Support *sup)
+namespace {
+// a BAM as a table: reference names and lengths, the canonical ECs of its reads (one QNAME a read) and their tuples
+struct BamTable {
+    std::vector<std::string> names;
+    std::vector<uint32_t> lens, ids, tup;
+    std::vector<uint64_t> off{0}, count, tn;
+};
+
+int bam_table(const char *bam_path, BamTable &b)
 {
     std::vector<uint64_t> read_ref;
-    std::vector<std::string> names;
     std::vector<std::array<uint32_t, 4>> recs;
-    std::vector<uint32_t> lens;
-    if (int rc = report_bam(bam_path, 0.97, 0, nullptr, nullptr, nullptr, nullptr, &read_ref, &names, &recs, &lens)) return rc;
+    if (int rc = report_bam(bam_path, 0.97, 0, nullptr, nullptr, nullptr, nullptr, &read_ref, &b.names, &recs, &b.lens)) return rc;
     // S(read) as report_abundance builds it, and the read's EC
     EcMap m;
     std::vector<std::vector<uint32_t>> set_of;
@@ -1059,14 +1065,12 @@ static int report_calls(const char *bam_path, double min_reads, double call_dept
         i = j;
     }
     std::map<std::vector<uint32_t>, uint32_t> index;
-    std::vector<uint64_t> off{0}, count;
-    std::vector<uint32_t> ids;
     for (const auto &kv : m) {
         const uint32_t i = (uint32_t)index.size();
         index[kv.first] = i;
-        ids.insert(ids.end(), kv.first.begin(), kv.first.end());
-        off.push_back(ids.size());
-        count.push_back(kv.second);
+        b.ids.insert(b.ids.end(), kv.first.begin(), kv.first.end());
+        b.off.push_back(b.ids.size());
+        b.count.push_back(kv.second);
     }
     std::vector<uint32_t> ec_of(set_of.size(), 0);
     for (size_t r = 0; r < set_of.size(); r++)
@@ -1075,17 +1079,26 @@ static int report_calls(const char *bam_path, double min_reads, double call_dept
     t.reserve(recs.size());
     for (const auto &r : recs) t.push_back(Tuple{ec_of[r[0]], r[1], r[2], r[3], 1});
     tuples_canonical(t);
-    std::vector<uint32_t> tup(4 * t.size());
-    std::vector<uint64_t> tn(t.size());
+    b.tup.resize(4 * t.size());
+    b.tn.resize(t.size());
     for (size_t i = 0; i < t.size(); i++) {
-        tup[4 * i] = t[i].ec; tup[4 * i + 1] = t[i].path; tup[4 * i + 2] = t[i].pos; tup[4 * i + 3] = t[i].last;
-        tn[i] = t[i].n;
+        b.tup[4 * i] = t[i].ec; b.tup[4 * i + 1] = t[i].path; b.tup[4 * i + 2] = t[i].pos; b.tup[4 * i + 3] = t[i].last;
+        b.tn[i] = t[i].n;
     }
-    if (n_tuples) *n_tuples = t.size();
-    std::vector<const char *> name_ptr(names.size());
-    for (size_t r = 0; r < names.size(); r++) name_ptr[r] = names[r].c_str();
-    return write_calls((uint32_t)names.size(), name_ptr.data(), nullptr, lens.data(), m.size(), off.data(), ids.data(), count.data(), nullptr, t.size(), tup.data(),
-                       tn.data(), min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, sup);
+    return GROOT_OK;
+}
+} // namespace
+
+static int report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
+                        uint64_t *n_called, uint64_t *n_tuples, const Support *sup)
+{
+    BamTable b;
+    if (int rc = bam_table(bam_path, b)) return rc;
+    if (n_tuples) *n_tuples = b.tn.size();
+    std::vector<const char *> name_ptr(b.names.size());
+    for (size_t r = 0; r < b.names.size(); r++) name_ptr[r] = b.names[r].c_str();
+    return write_calls((uint32_t)b.names.size(), name_ptr.data(), nullptr, b.lens.data(), b.count.size(), b.off.data(), b.ids.data(), b.count.data(), nullptr,
+                       b.tn.size(), b.tup.data(), b.tn.data(), min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, sup);
 }
 
 extern "C" int groot_host_report_calls(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines,
@@ -1100,6 +1113,254 @@ extern "C" int groot_host_report_calls_support(const char *bam_path, double min_
     if (n_boot == 0) return set_error(GROOT_E_INVALID, "no bootstrap replicates");
     const Support sup{n_boot, seed, threads, nullptr, nullptr, nullptr};
     return report_calls(bam_path, min_reads, call_depth, cov_cutoff, out_path, n_lines, n_called, n_tuples, &sup);
+}
+
+// ---- rarefaction curves (groot_host.h "rarefaction curves") --------------------------------------------------------------------
+extern "C" int groot_host_rarefy_depths(uint64_t n_units, uint32_t n_steps, uint64_t *m)
+{
+    if (n_steps == 0 || !m) return set_error(GROOT_E_INVALID, "no rarefaction steps");
+    const uint64_t D = n_steps;
+    for (uint64_t s = 1; s <= D; s++) m[s - 1] = (n_units / D) * s + ((n_units % D) * s) / D;
+    return GROOT_OK;
+}
+
+extern "C" int groot_host_em_rarefy(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_rep,
+                                    uint32_t n_depths, const uint64_t *depths, uint64_t seed, uint32_t min_iter, uint32_t max_iter, uint32_t threads,
+                                    uint64_t *rare_count, double *alpha, uint32_t *iterations)
+{
+    if ((n_ec && (!off || !count)) || (n_paths && !alpha) || (n_depths && !depths)) return set_error(GROOT_E_INVALID, "null argument");
+    if (n_rep == 0) return set_error(GROOT_E_INVALID, "no rarefaction replicates");
+    if (n_depths == 0) return set_error(GROOT_E_INVALID, "no rarefaction depths");
+    if (max_iter < min_iter)
+        return set_error(GROOT_E_INVALID, "number of EM iterations (%u) must be greater than minimum iterations (%u)", max_iter, min_iter);
+    if (max_iter < 1) return set_error(GROOT_E_INVALID, "no EM iterations were ran");
+    std::vector<uint64_t> cum(n_ec + 1, 0);
+    for (uint64_t e = 0; e < n_ec; e++) {
+        if (off[e + 1] < off[e] || (off[e + 1] > off[e] && !ids)) return set_error(GROOT_E_INVALID, "EC %llu: bad offsets", (unsigned long long)e);
+        for (uint64_t i = off[e]; i < off[e + 1]; i++)
+            if (ids[i] >= n_paths) return set_error(GROOT_E_INVALID, "EC %llu holds path %u of %u", (unsigned long long)e, ids[i], n_paths);
+        cum[e + 1] = cum[e] + count[e];
+        if (cum[e + 1] < cum[e]) return set_error(GROOT_E_INVALID, "the EC counts sum to 2^64 or more");
+    }
+    const uint64_t total = cum[n_ec];
+    if (total == 0) return set_error(GROOT_E_INVALID, "rarefaction over ECs without reads");
+    if (total >= groot::kRareMaxUnits) return set_error(GROOT_E_UNSUPPORTED, "rarefaction: 2^62 units and more");
+    for (uint32_t d = 0; d < n_depths; d++) {
+        if (depths[d] == 0 || depths[d] > total)
+            return set_error(GROOT_E_INVALID, "rarefaction depth %u is %llu: not in [1, %llu]", d, (unsigned long long)depths[d], (unsigned long long)total);
+        if (d && depths[d] < depths[d - 1]) return set_error(GROOT_E_INVALID, "rarefaction depth %u is below depth %u", d, d - 1);
+    }
+    const uint32_t h = groot::rare_half_bits(total);
+    std::atomic<uint32_t> next_b{0};
+    std::atomic<int> failed{0};
+    auto work = [&]() {
+        std::vector<uint64_t> run(n_ec);               // the counts of the draws so far: the depths are nested
+        for (uint32_t b; (b = next_b.fetch_add(1)) < n_rep;) {
+            std::fill(run.begin(), run.end(), 0);
+            const uint64_t key = groot::rare_key(seed, b);
+            uint64_t j = 0;
+            for (uint32_t d = 0; d < n_depths; d++) {
+                for (; j < depths[d]; j++) {
+                    const uint64_t t = groot::rare_pi(key, h, total, j);
+                    run[(std::upper_bound(cum.begin(), cum.end(), t) - cum.begin()) - 1]++;     // cum[e] <= t < cum[e + 1]
+                }
+                const size_t v = (size_t)b * n_depths + d;
+                if (rare_count) std::copy(run.begin(), run.end(), rare_count + v * n_ec);
+                if (groot_host_em(n_paths, n_ec, off, ids, run.data(), min_iter, max_iter, alpha + v * n_paths, iterations ? iterations + v : nullptr)) failed = 1;
+            }
+        }
+    };
+    const uint32_t nt = std::max(1u, std::min(threads, n_rep));
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < nt; t++) pool.emplace_back(work);
+    work();
+    for (auto &t : pool) t.join();
+    if (failed) return set_error(GROOT_E_INVALID, "the EM of a rarefaction replicate failed");
+    return GROOT_OK;
+}
+
+namespace {
+
+// what the rarefaction writer gets ready-made (NULL = computed on `threads` host threads), and the calls table when the called columns are wanted
+struct Rarefy {
+    uint32_t n_rep = 0, n_steps = 0;
+    uint64_t seed = 1;
+    uint32_t threads = 1;
+    const uint64_t *rare_count = nullptr;
+    const double *rare_alpha = nullptr;
+    bool calls = false;
+    uint64_t n_tuples = 0;
+    const uint32_t *tuples = nullptr;
+    const uint64_t *tn = nullptr;
+    double call_depth = 1.0, cov_cutoff = 0.97;
+    uint32_t n_sel = 0;
+    const uint32_t *covered = nullptr;
+    uint32_t *iter_range = nullptr;     // [2]: the fewest and the most EM iterations of the replicates computed here
+};
+
+// the rarefaction file over canonical ECs (groot_host.h)
+int write_rarefy(uint32_t n_paths, const uint32_t *lens, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, double min_reads,
+                 const Rarefy &r, const char *out_path, uint64_t *n_lines)
+{
+    if (r.n_rep == 0) return set_error(GROOT_E_INVALID, "no rarefaction replicates");
+    if (r.n_steps == 0) return set_error(GROOT_E_INVALID, "no rarefaction steps");
+    if (r.calls && r.cov_cutoff > 1.0) return set_error(GROOT_E_INVALID, "supplied coverage cutoff exceeds 1.0 (100%%): %g", r.cov_cutoff);
+    if ((n_ec && (!off || !count)) || (r.calls && ((n_paths && !lens) || (r.n_tuples && (!r.tuples || !r.tn))))) return set_error(GROOT_E_INVALID, "null argument");
+    const uint32_t R = r.n_rep, D = r.n_steps;
+    uint64_t N = 0;
+    for (uint64_t e = 0; e < n_ec; e++) N += count[e];
+    std::vector<uint64_t> m(D), drawn;
+    if (int rc = groot_host_rarefy_depths(N, D, m.data())) return rc;
+    for (uint32_t s = 0; s + 1 < D; s++)
+        if (m[s]) drawn.push_back(m[s]);
+    const uint32_t K = (uint32_t)drawn.size();
+    if ((uint64_t)R * K > 0xFFFFFFFFull) return set_error(GROOT_E_INVALID, "rarefaction: %u replicates of %u depths", R, K);
+    // the replicates at the drawn depths
+    std::vector<uint64_t> own_rc;
+    std::vector<double> own_ra;
+    const uint64_t *rc_ = r.rare_count;
+    const double *ra = r.rare_alpha;
+    if (K && !ra) {
+        own_rc.resize((size_t)R * K * n_ec);
+        own_ra.resize((size_t)R * K * n_paths);
+        std::vector<uint32_t> its((size_t)R * K);
+        if (int rc = groot_host_em_rarefy(n_paths, n_ec, off, ids, count, R, K, drawn.data(), r.seed, GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER, r.threads, own_rc.data(),
+                                          own_ra.data(), its.data()))
+            return rc;
+        if (r.iter_range) {
+            r.iter_range[0] = *std::min_element(its.begin(), its.end());
+            r.iter_range[1] = *std::max_element(its.begin(), its.end());
+        }
+        rc_ = own_rc.data(); ra = own_ra.data();
+    }
+    // the number of paths among sel (all paths: sel NULL) that are detected in alpha, and called when cov (covered bases, in sel's order) is given
+    auto tally = [&](const double *alpha, const std::vector<uint32_t> *sel, const uint32_t *cov, uint64_t &args, uint64_t &called) {
+        args = called = 0;
+        const size_t n = sel ? sel->size() : n_paths;
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t p = sel ? (*sel)[i] : (uint32_t)i;
+            if (!(alpha[p] >= min_reads)) continue;
+            args++;
+            if (!cov) continue;
+            const double breadth = lens[p] ? (double)cov[i] / (double)lens[p] : 0.0;
+            called += breadth >= r.cov_cutoff ? 1u : 0u;
+        }
+    };
+    std::vector<uint64_t> args((size_t)R * K, 0), called((size_t)R * K, 0);
+    if (K && r.calls) {
+        std::vector<uint8_t> seen(n_paths, 0);
+        for (size_t v = 0; v < (size_t)R * K; v++)
+            for (uint32_t p = 0; p < n_paths; p++)
+                if (ra[v * n_paths + p] >= min_reads) seen[p] = 1;
+        std::vector<uint32_t> sel;
+        for (uint32_t p = 0; p < n_paths; p++)
+            if (seen[p]) sel.push_back(p);
+        std::vector<uint32_t> own_cov;
+        const uint32_t *cov = r.covered;
+        if (cov && r.n_sel != sel.size()) return set_error(GROOT_E_INVALID, "rarefaction: covered has %u paths a replicate, %zu are detected", r.n_sel, sel.size());
+        if (!cov && !sel.empty()) {
+            if (!rc_) return set_error(GROOT_E_INVALID, "rarefaction: the called columns need rare_count or covered");
+            own_cov.resize((size_t)R * K * sel.size());
+            if (int rc = call_support(n_paths, lens, n_ec, off, ids, count, r.n_tuples, r.tuples, r.tn, R * K, rc_, ra, r.call_depth, (uint32_t)sel.size(), sel.data(),
+                                      r.threads, own_cov.data()))
+                return rc;
+            cov = own_cov.data();
+        }
+        for (size_t v = 0; v < (size_t)R * K; v++) tally(ra + v * n_paths, &sel, sel.empty() ? nullptr : cov + v * sel.size(), args[v], called[v]);
+    } else {
+        for (size_t v = 0; v < (size_t)R * K; v++) tally(ra + v * n_paths, nullptr, nullptr, args[v], called[v]);
+    }
+    // the step s = D: the point estimate, and with calls its pileup through the same code (boot_count = count: f = w)
+    uint64_t args_all = 0, called_all = 0;
+    if (N) {
+        std::vector<double> alpha(n_paths);
+        if (int rc = groot_host_em(n_paths, n_ec, off, ids, count, GROOT_EM_MIN_ITER, GROOT_EM_MAX_ITER, alpha.data(), nullptr)) return rc;
+        if (r.calls) {
+            std::vector<uint32_t> sel;
+            for (uint32_t p = 0; p < n_paths; p++)
+                if (alpha[p] >= min_reads) sel.push_back(p);
+            std::vector<uint32_t> cov(sel.size() + 1);
+            if (!sel.empty())
+                if (int rc = call_support(n_paths, lens, n_ec, off, ids, count, r.n_tuples, r.tuples, r.tn, 1, count, alpha.data(), r.call_depth, (uint32_t)sel.size(),
+                                          sel.data(), 1, cov.data()))
+                    return rc;
+            tally(alpha.data(), &sel, cov.data(), args_all, called_all);
+        } else {
+            tally(alpha.data(), nullptr, nullptr, args_all, called_all);
+        }
+    }
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
+    uint64_t lines = 0;
+    std::vector<uint64_t> v(R);
+    const uint32_t q = (uint32_t)((25ull * (R - 1)) / 1000);
+    // mean (summed in replicate order), v[q] and v[R - 1 - q] of the sorted integers
+    auto columns = [&](const std::vector<uint64_t> &x, uint32_t k) {
+        double s = 0.0;
+        for (uint32_t b = 0; b < R; b++) { v[b] = x[(size_t)b * K + k]; s += (double)v[b]; }
+        std::sort(v.begin(), v.end());
+        fprintf(out, "\t%.2f\t%llu\t%llu", s / (double)R, (unsigned long long)v[q], (unsigned long long)v[R - 1 - q]);
+    };
+    uint32_t k = 0;
+    for (uint32_t s = 1; s <= D; s++) {
+        if (m[s - 1] == 0) continue;
+        fprintf(out, "%.4f\t%llu", (double)s / (double)D, (unsigned long long)m[s - 1]);
+        if (s < D) {
+            columns(args, k);
+            if (r.calls) columns(called, k);
+            k++;
+        } else {
+            fprintf(out, "\t%.2f\t%llu\t%llu", (double)args_all, (unsigned long long)args_all, (unsigned long long)args_all);
+            if (r.calls) fprintf(out, "\t%.2f\t%llu\t%llu", (double)called_all, (unsigned long long)called_all, (unsigned long long)called_all);
+        }
+        fputc('\n', out);
+        lines++;
+    }
+    if (out_path) fclose(out); else fflush(out);
+    if (n_lines) *n_lines = lines;
+    return GROOT_OK;
+}
+
+} // namespace
+
+extern "C" int groot_host_rarefy_from_ecs(const groot_index_view *ix, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, double min_reads,
+                                          uint32_t n_rep, uint32_t n_steps, uint64_t seed, uint32_t threads, const uint64_t *rare_count, const double *rare_alpha,
+                                          int with_calls, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn, double call_depth, double cov_cutoff,
+                                          uint32_t n_sel, const uint32_t *covered, const char *out_path, uint64_t *n_lines)
+{
+    if (!ix || (n_ec && (!off || !count))) return set_error(GROOT_E_INVALID, "null argument");
+    Rarefy r;
+    r.n_rep = n_rep; r.n_steps = n_steps; r.seed = seed; r.threads = threads; r.rare_count = rare_count; r.rare_alpha = rare_alpha;
+    if (with_calls) {
+        r.calls = true; r.n_tuples = n_tuples; r.tuples = tuples; r.tn = tn; r.call_depth = call_depth; r.cov_cutoff = cov_cutoff; r.n_sel = n_sel; r.covered = covered;
+        return write_rarefy(ix->n_paths, ix->path_len, n_ec, off, ids, count, min_reads, r, out_path, n_lines);
+    }
+    EcMap m;
+    if (int rc = canonical_ecs(ix->n_paths, n_ec, off, ids, count, m)) return rc;
+    std::vector<uint64_t> c_off{0}, c_cnt;
+    std::vector<uint32_t> c_ids;
+    for (const auto &kv : m) {
+        c_ids.insert(c_ids.end(), kv.first.begin(), kv.first.end());
+        c_off.push_back(c_ids.size());
+        c_cnt.push_back(kv.second);
+    }
+    return write_rarefy(ix->n_paths, ix->path_len, m.size(), c_off.data(), c_ids.data(), c_cnt.data(), min_reads, r, out_path, n_lines);
+}
+
+extern "C" int groot_host_report_rarefy(const char *bam_path, double min_reads, uint32_t n_rep, uint32_t n_steps, uint64_t seed, uint32_t threads, int with_calls,
+                                        double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines, uint32_t *iter_range)
+{
+    if (n_rep == 0) return set_error(GROOT_E_INVALID, "no rarefaction replicates");
+    if (n_steps == 0) return set_error(GROOT_E_INVALID, "no rarefaction steps");
+    BamTable b;
+    if (int rc = bam_table(bam_path, b)) return rc;
+    Rarefy r;
+    r.n_rep = n_rep; r.n_steps = n_steps; r.seed = seed; r.threads = threads; r.iter_range = iter_range;
+    if (iter_range) iter_range[0] = iter_range[1] = 0;
+    if (with_calls) {
+        r.calls = true; r.n_tuples = b.tn.size(); r.tuples = b.tup.data(); r.tn = b.tn.data(); r.call_depth = call_depth; r.cov_cutoff = cov_cutoff;
+    }
+    return write_rarefy((uint32_t)b.names.size(), b.lens.data(), b.count.size(), b.off.data(), b.ids.data(), b.count.data(), min_reads, r, out_path, n_lines);
 }
 
 // ---- reading an abundance file back (align --assignFrom; groot_host.h "assignment") ------------------------------------------

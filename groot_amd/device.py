@@ -74,6 +74,7 @@ def lib():
         L.groot_hip_last_error.argtypes = [C.c_void_p]
         L.groot_hip_close.argtypes = [C.c_void_p]
         L.groot_hip_close.restype = None
+        _ffi.rarefy_hip_prototypes(L)
         _lib = L
     return _lib
 
@@ -127,6 +128,22 @@ def em_bootstrap(n_paths, off, ids, count, n_boot, seed=1, n_draws=0, min_iter=h
     if rc < 0:
         raise GrootError(rc, lib().groot_hip_last_error(None).decode(errors="replace"))
     return bc, alpha, its
+
+
+def em_rarefy(n_paths, off, ids, count, n_rep, depths, seed=1, min_iter=host.EM_MIN_ITER, max_iter=host.EM_MAX_ITER, device=0):
+    """groot_hip_em_rarefy: host.em_rarefy on the device, bit for bit ->
+    (rare_count uint64[n_rep, n_depths, n_ec], alpha float64[n_rep, n_depths, n_paths], iterations uint32[n_rep, n_depths])"""
+    off, ids, count = host._ec_arrays(off, ids, count)
+    depths = np.ascontiguousarray(depths, dtype=np.uint64).reshape(-1)
+    rc = np.zeros((n_rep, len(depths), len(count)), dtype=np.uint64)
+    alpha = np.zeros((n_rep, len(depths), n_paths), dtype=np.float64)
+    its = np.zeros((n_rep, len(depths)), dtype=np.uint32)
+    err = lib().groot_hip_em_rarefy(device, n_paths, len(count), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32), _ffi.as_ptr(count, C.c_uint64), n_rep,
+                                    len(depths), _ffi.as_ptr(depths, C.c_uint64), seed, min_iter, max_iter, _ffi.as_ptr(rc, C.c_uint64),
+                                    _ffi.as_ptr(alpha, C.c_double), _ffi.as_ptr(its, C.c_uint32))
+    if err < 0:
+        raise GrootError(err, lib().groot_hip_last_error(None).decode(errors="replace"))
+    return rc, alpha, its
 
 
 def call_support(n_paths, path_len, off, ids, count, tuples, tn, boot_count, alpha, sel_paths, call_depth=1.0, device=0):

@@ -33,6 +33,7 @@ def lib():
         L.groot_index_free.restype = None
         L.groot_index_get_view.argtypes = [C.c_void_p, C.POINTER(IndexView)]
         L.groot_index_get_view.restype = None
+        _ffi.rarefy_host_prototypes(L)
         _lib = L
     return _lib
 
@@ -787,6 +788,61 @@ def report_abundance_boot(bam_path, n_boot, seed=1, threads=1, min_reads=1.0, ou
             os.unlink(tmp)
     assert len(rows) == n.value
     return rows
+
+
+# ---- rarefaction curves (groot_host.h "rarefaction curves") ----------------------------------------------------------------
+RAREFY_STEPS, RAREFY_REPS = 10, 20
+
+
+def rarefy_depths(n_units, n_steps=RAREFY_STEPS):
+    """groot_host_rarefy_depths: m_s of the steps s = 1 .. n_steps (zeros included) -> uint64[n_steps]"""
+    m = np.zeros(max(n_steps, 1), dtype=np.uint64)
+    _check(lib().groot_host_rarefy_depths(n_units, n_steps, _ffi.as_ptr(m, C.c_uint64)))
+    return m[:n_steps]
+
+
+def em_rarefy(n_paths, off, ids, count, n_rep, depths, seed=1, min_iter=EM_MIN_ITER, max_iter=EM_MAX_ITER, threads=1):
+    """groot_host_em_rarefy: n_rep nested subsamples without replacement of the ECs' units at the given depths, the EM on each ->
+    (rare_count uint64[n_rep, n_depths, n_ec], alpha float64[n_rep, n_depths, n_paths], iterations uint32[n_rep, n_depths])"""
+    off, ids, count = _ec_arrays(off, ids, count)
+    depths = np.ascontiguousarray(depths, dtype=np.uint64).reshape(-1)
+    rc = np.zeros((n_rep, len(depths), len(count)), dtype=np.uint64)
+    alpha = np.zeros((n_rep, len(depths), n_paths), dtype=np.float64)
+    its = np.zeros((n_rep, len(depths)), dtype=np.uint32)
+    _check(lib().groot_host_em_rarefy(n_paths, len(count), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32), _ffi.as_ptr(count, C.c_uint64), n_rep,
+                                      len(depths), _ffi.as_ptr(depths, C.c_uint64), seed, min_iter, max_iter, threads, _ffi.as_ptr(rc, C.c_uint64),
+                                      _ffi.as_ptr(alpha, C.c_double), _ffi.as_ptr(its, C.c_uint32)))
+    return rc, alpha, its
+
+
+def rarefy_from_ecs(index, off, ids, count, out_path, n_rep=RAREFY_REPS, n_steps=RAREFY_STEPS, seed=1, threads=1, min_reads=1.0, rare_count=None, rare_alpha=None,
+                    tuples=None, tn=None, call_depth=1.0, cov_cutoff=0.97, covered=None):
+    """groot_host_rarefy_from_ecs: writes the rarefaction file of a run's ECs; rare_count / rare_alpha (device.em_rarefy over the canonical
+    ECs at the drawn depths) and covered (device.call_support) None = computed inside on `threads` host threads.  tuples / tn (the
+    table of acov_merge, ECs canonical) add the three called columns.  Returns the number of lines."""
+    off, ids, count = _ec_arrays(off, ids, count)
+    with_calls = tuples is not None
+    if with_calls:
+        tuples, tn = _tuple_arrays(tuples, tn)
+    rare_count = None if rare_count is None else np.ascontiguousarray(rare_count, dtype=np.uint64)
+    rare_alpha = None if rare_alpha is None else np.ascontiguousarray(rare_alpha, dtype=np.float64)
+    covered = None if covered is None else np.ascontiguousarray(covered, dtype=np.uint32)
+    n_sel = 0 if covered is None else (covered.shape[-1] if covered.ndim >= 2 else 0)
+    nl = C.c_uint64(0)
+    _check(lib().groot_host_rarefy_from_ecs(C.byref(index.view), len(count), _ffi.as_ptr(off, C.c_uint64), _ffi.as_ptr(ids, C.c_uint32),
+                                            _ffi.as_ptr(count, C.c_uint64), min_reads, n_rep, n_steps, seed, threads, _ffi.opt_ptr(rare_count, C.c_uint64),
+                                            _ffi.opt_ptr(rare_alpha, C.c_double), 1 if with_calls else 0, len(tn) if with_calls else 0,
+                                            _ffi.opt_ptr(tuples, C.c_uint32), _ffi.opt_ptr(tn, C.c_uint64), call_depth, cov_cutoff, n_sel,
+                                            _ffi.opt_ptr(covered, C.c_uint32), out_path.encode(), C.byref(nl)))
+    return nl.value
+
+
+def report_rarefy(bam_path, out_path, n_rep=RAREFY_REPS, n_steps=RAREFY_STEPS, seed=1, threads=1, min_reads=1.0, calls=False, call_depth=1.0, cov_cutoff=0.97):
+    """groot_host_report_rarefy: the rarefaction file of a BAM (calls=True: with the three called columns).  Returns the number of lines."""
+    nl = C.c_uint64(0)
+    _check(lib().groot_host_report_rarefy(bam_path.encode(), min_reads, n_rep, n_steps, seed, threads, 1 if calls else 0, call_depth, cov_cutoff,
+                                          out_path.encode(), C.byref(nl), None))
+    return nl.value
 
 
 def save_gfa(index, graph, kmer_freq, path_kept, node_removed, total_kmers, file_name, timestamp=None):

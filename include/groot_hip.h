@@ -476,6 +476,39 @@ int groot_hip_em_bootstrap(int device, uint32_t n_paths, uint64_t n_ec, const ui
                            uint32_t n_boot, uint64_t seed, uint64_t n_draws, uint32_t min_iter, uint32_t max_iter, uint64_t *boot_count,
                            double *alpha, uint32_t *iterations);
 
+/* ---- rarefaction: nested subsamples without replacement, the EM at every depth ---------------------------------------------------
+ * groot_host_em_rarefy (groot_host.h, "rarefaction curves") on the device, bit for bit in rare_count, alpha and iterations.  Quoted
+ * from there:
+ *
+ * Input: canonical ECs (off, ids, count; groot_host_ecs_canonical), cum[0] = 0, cum[e+1] = cum[e] + count[e], N = cum[n_ec], 1 <= N < 2^62;
+ * R >= 1 replicates; a 64-bit seed; n_depths >= 1 depths m[0] <= m[1] <= .. with 1 <= m[d] <= N.
+ * Unit i (0 <= i < N) belongs to the EC e with cum[e] <= i < cum[e+1] (an EC with count 0 owns no unit).
+ * sm(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)      (mod 2^64; the
+ *         mixing steps of the bootstrap's draw)
+ * h   = the smallest integer >= 1 with 2^(2h) >= N;  mask = 2^h - 1                       (domain 2^(2h) < 4 N for N > 4)
+ * k_b = sm(seed + (b + 1) * 0x9E3779B97F4A7C15)
+ * pi_b(j), 0 <= j < N:   x = j
+ *     repeat:  L = x >> h;  Rr = x & mask
+ *              for t = 0 .. 5:  F = sm(k_b + (((t << 32) | Rr) + 1) * 0x9E3779B97F4A7C15) >> (64 - h);   (L, Rr) = (Rr, L ^ F)
+ *              x = (L << h) | Rr
+ *     until x < N                                   (cycle walking: a Feistel network is a bijection of [0, 2^(2h)), so pi_b is a
+ *                                                    bijection of [0, N) and the loop ends)
+ * rare_count[b][d][e] = the number of j < m[d] with pi_b(j) in EC e.
+ *
+ * then alpha[b][d] = groot_host_em(n_paths, n_ec, off, ids, rare_count[b][d], min_iter, max_iter), iterations[b][d] its rounds.
+ * Needs no ctx: like groot_hip_em_bootstrap it runs on the device with that ordinal, on a stream and in buffers of its own that are
+ * freed on return, and may be called while ctxs have batches in flight.  On the device (kernels_rare.hpp): rare_draw_kernel, a thread
+ * per draw j, one grid row per (replicate, depth interval [m[d-1], m[d])), counts the interval's units into the row's increments;
+ * rare_cumsum_kernel adds the increments along the depths; boot_em_kernel then fits the n_rep * n_depths count vectors, one workgroup
+ * each.  Replicates go in chunks that bound the device memory taken, as for the bootstrap; the result does not depend on them.
+ * rare_count[n_rep][n_depths][n_ec] and iterations[n_rep][n_depths] may be NULL; alpha[n_rep][n_depths][n_paths].  GROOT_E_INVALID as
+ * groot_host_em_rarefy (n_rep = 0; n_depths = 0; a depth of 0 or above N; depths that descend; N = 0; the EM's errors);
+ * GROOT_E_UNSUPPORTED at N >= 2^62, at 2^32 - 1 ECs or listed IDs and more, above 65 535 depths or 4 GiB for one replicate's depths;
+ * GROOT_E_DEVICE without that HIP device; the message is groot_hip_last_error(NULL). */
+int groot_hip_em_rarefy(int device, uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_rep,
+                        uint32_t n_depths, const uint64_t *depths, uint64_t seed, uint32_t min_iter, uint32_t max_iter, uint64_t *rare_count,
+                        double *alpha, uint32_t *iterations);
+
 /* ---- bootstrap support for the calls: per-replicate breadth ------------------------------------------------------------------
  * groot_host_call_support (groot_host.h, "bootstrap support for the calls") on the device, covered_out as u32 bit for bit.  Quoted
  * from there:

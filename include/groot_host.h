@@ -441,6 +441,69 @@ int groot_host_calls_support_from_table(const groot_index_view *idx, uint64_t n_
 int groot_host_report_calls_support(const char *bam_path, double min_reads, double call_depth, double cov_cutoff, uint32_t n_boot, uint64_t seed,
                                     uint32_t threads, const char *out_path, uint64_t *n_lines, uint64_t *n_called, uint64_t *n_tuples);
 
+/* ---- rarefaction curves: was the sample sequenced deeply enough? -----------------------------------------------------------
+ * The run's units (reads; fragments with pairing) are subsampled WITHOUT replacement to a list of depths, nested, and the abundance
+ * estimate is redone at every depth: a curve of detected ARGs against depth that has flattened says that more reads would turn up
+ * little more.  Nothing but the ECs is needed.  The definition (groot_hip.h, README.md, DESIGN.md 15 and the tests quote it):
+ *
+ * Input: canonical ECs (off, ids, count; groot_host_ecs_canonical), cum[0] = 0, cum[e+1] = cum[e] + count[e], N = cum[n_ec], 1 <= N < 2^62;
+ * R >= 1 replicates; a 64-bit seed; n_depths >= 1 depths m[0] <= m[1] <= .. with 1 <= m[d] <= N.
+ * Unit i (0 <= i < N) belongs to the EC e with cum[e] <= i < cum[e+1] (an EC with count 0 owns no unit).
+ * sm(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)      (mod 2^64; the
+ *         mixing steps of the bootstrap's draw)
+ * h   = the smallest integer >= 1 with 2^(2h) >= N;  mask = 2^h - 1                       (domain 2^(2h) < 4 N for N > 4)
+ * k_b = sm(seed + (b + 1) * 0x9E3779B97F4A7C15)
+ * pi_b(j), 0 <= j < N:   x = j
+ *     repeat:  L = x >> h;  Rr = x & mask
+ *              for t = 0 .. 5:  F = sm(k_b + (((t << 32) | Rr) + 1) * 0x9E3779B97F4A7C15) >> (64 - h);   (L, Rr) = (Rr, L ^ F)
+ *              x = (L << h) | Rr
+ *     until x < N                                   (cycle walking: a Feistel network is a bijection of [0, 2^(2h)), so pi_b is a
+ *                                                    bijection of [0, N) and the loop ends)
+ * rare_count[b][d][e] = the number of j < m[d] with pi_b(j) in EC e.
+ *
+ * Only integers are involved: rare_count depends on (seed, b, count, m[d]) alone -- not on R, the other depths or the number of threads;
+ * its sum over e is m[d]; rare_count[b][d][e] <= rare_count[b][d+1][e] <= count[e] (the depths are nested), and m[d] = N gives count.
+ * The estimate of replicate b at depth d: alpha[b][d] = groot_host_em(n_paths, n_ec, off, ids, rare_count[b][d], min_iter, max_iter),
+ * bit for bit, with its own iteration count.  (The ECs are taken in the order given; the file writers give them in canonical order.)
+ *
+ * The file (--rarefy): one line per depth step s = 1 .. D (D = n_steps), no header; m_s = (N / D) * s + ((N % D) * s) / D in integers, a
+ * step with m_s = 0 is omitted.  "fraction (s/D, %.4f) \t units (m_s) \t args_mean (%.2f) \t args_lo \t args_hi": args of a replicate = the
+ * number of paths with alpha[b][s] >= min_reads (the lines the abundance file would have at that depth); the mean summed in replicate
+ * order; lo and hi = v[q] and v[R-1-q] of the sorted integers, q = (25 * (R - 1)) / 1000 (the bootstrap's rule).  The step s = D is not
+ * drawn: its three values are the point estimate's line count.  With calls three more columns "called_mean (%.2f) \t called_lo \t
+ * called_hi": called = the number of paths with alpha[b][s] >= min_reads and (double)covered / (double)path_len >= cov_cutoff (path_len 0:
+ * breadth 0.0), covered = groot_host_call_support / groot_hip_call_support fed boot_count = rare_count, the rarefied alpha, call_depth and
+ * sel_paths = every path detected (alpha >= min_reads) in at least one drawn (b, s), ascending; the step s = D from count and the point
+ * estimate in the same way, which is the calls file's count of called lines. */
+#define GROOT_RAREFY_STEPS 10
+#define GROOT_RAREFY_REPS 20
+/* m_s of the steps s = 1 .. n_steps into m[n_steps] (zeros included).  GROOT_E_INVALID for n_steps = 0. */
+int groot_host_rarefy_depths(uint64_t n_units, uint32_t n_steps, uint64_t *m);
+/* The definition on the host, the replicates spread over `threads` (0 = 1).  rare_count[n_rep][n_depths][n_ec] (may be NULL),
+ * alpha[n_rep][n_depths][n_paths], iterations[n_rep][n_depths] (may be NULL).  GROOT_E_INVALID: n_rep = 0; n_depths = 0; a depth of 0 or
+ * above N; depths that descend; N = 0; the errors of groot_host_em.  GROOT_E_UNSUPPORTED at N >= 2^62.  groot_hip_em_rarefy computes the
+ * same bits on the device. */
+int groot_host_em_rarefy(uint32_t n_paths, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count, uint32_t n_rep,
+                         uint32_t n_depths, const uint64_t *depths, uint64_t seed, uint32_t min_iter, uint32_t max_iter, uint32_t threads,
+                         uint64_t *rare_count, double *alpha, uint32_t *iterations);
+/* The rarefaction file of a run's ECs (any order without calls: they are made canonical as the abundance writers do; with calls the
+ * canonical ECs and the table of groot_host_acov_merge, as for groot_host_calls_from_table).  The drawn depths are the m_s > 0 of the steps
+ * s < n_steps, n_drawn of them, in step order.  rare_alpha[n_rep][n_drawn][n_paths] and rare_count[n_rep][n_drawn][n_ec] as
+ * groot_hip_em_rarefy returns them over the canonical ECs with GROOT_EM_MIN_ITER / GROOT_EM_MAX_ITER (rare_count is only read with calls
+ * and without covered); rare_alpha NULL = both computed here with groot_host_em_rarefy(seed, threads).  with_calls != 0 adds the three
+ * called columns; covered[n_rep * n_drawn][n_sel] = groot_hip_call_support over sel_paths as defined above, NULL = computed here on
+ * `threads` threads (n_sel is then ignored).  GROOT_E_INVALID: n_rep = 0, n_steps = 0, cov_cutoff > 1 with calls, an n_sel that is not the
+ * number of detected paths.  out_path NULL = stdout; *n_lines may be NULL. */
+int groot_host_rarefy_from_ecs(const groot_index_view *idx, uint64_t n_ec, const uint64_t *off, const uint32_t *ids, const uint64_t *count,
+                               double min_reads, uint32_t n_rep, uint32_t n_steps, uint64_t seed, uint32_t threads, const uint64_t *rare_count,
+                               const double *rare_alpha, int with_calls, uint64_t n_tuples, const uint32_t *tuples, const uint64_t *tn,
+                               double call_depth, double cov_cutoff, uint32_t n_sel, const uint32_t *covered, const char *out_path, uint64_t *n_lines);
+/* The same file from a BAM, a read being one QNAME (groot_host_report_abundance's grouping; with calls the table of
+ * groot_host_report_calls), everything computed on `threads` host threads: byte for byte what the device path writes whenever read
+ * names are unique.  iter_range[2] (may be NULL) = the fewest and the most EM iterations among the drawn (replicate, depth) pairs, 0 0 without any. */
+int groot_host_report_rarefy(const char *bam_path, double min_reads, uint32_t n_rep, uint32_t n_steps, uint64_t seed, uint32_t threads, int with_calls,
+                             double call_depth, double cov_cutoff, const char *out_path, uint64_t *n_lines, uint32_t *iter_range);
+
 /* ---- assignment: each read to its best allele by EM posterior ------------------------------------------------------------
  * A second `align` pass keeps, per read, only the records on the path with the largest posterior of a first pass's abundance estimate
  * (w(e,p) = alpha[p] / denom(e), so the argmax over S(r) is the argmax over alpha), each with a MAPQ derived from that posterior.  The
