@@ -1,7 +1,7 @@
 // counters.hip -- the counters that run behind every batch's order stage, and their C ABI (include/groot_hip.h): report coverage
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
-// draws (kernels_rare.hpp).  One of the five translation units of
+// draws (kernels_rare.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <hip/hip_runtime.h>
 

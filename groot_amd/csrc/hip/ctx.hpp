@@ -1,6 +1,6 @@
 // ctx.hpp -- the ctx of libgroot_hip.so as its translation units see it: the buffer types, one batch in flight (Slot), the work sets and
 // groot_ctx itself, with the state of the counters behind the order stage (counters.hip) as ONE member each of the ctx and of a slot.
-// Internal to groot_hip.hip (pipeline + C ABI) and counters.hip; the calls between the two are at the end and in counters.hpp.
+// Internal to groot_hip.hip (pipeline + C ABI), open.hip (groot_hip_open*) and counters.hip; the calls between them are at the end, in open.hpp and in counters.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -414,7 +414,7 @@ template <class T> static hipError_t upload(DevBuf<T> &d, const T *src, size_t n
     return e;
 }
 
-// what counters.hip needs of the pipeline (groot_hip.hip)
+// what counters.hip and open.hip need of the pipeline (groot_hip.hip); open.hip's further calls: open.hpp
 namespace groot {
 int fail(groot_ctx *ctx, int code, const char *fmt, ...);   // sets the ctx's (no ctx: the thread's) error text, returns code
 int drain(groot_ctx *c);                                    // everything submitted has finished on the device (results stay collectable)

@@ -381,4 +381,63 @@ struct LeanArgs {
 // the read's (up to four) seed windows; odd
 __host__ __device__ inline uint32_t lean_stride_dw(uint32_t max_len) { return (((max_len + 15u) >> 4) + 15u) | 1u; }
 
+// ---- the table hashes the host side (index_tables.hpp) shares with the kernels ----
+#define GROOT_MULTI_SEED 0x90b45d39fb6da1faULL             // MultiHash (kernels_common.hpp)
+// hash of a whole sketch for the exact-match table (host builds the table with the same function)
+__host__ __device__ __forceinline__ uint64_t sketch_hash_step(uint64_t h, uint64_t v)
+{
+    h = (h ^ v) * 0xff51afd7ed558ccdULL;
+    return h ^ (h >> 29);
+}
+#define GROOT_SKETCH_HASH_INIT 0x9E3779B97F4A7C15ULL
+// LSH-Forest rows (DeviceIndex::band_sig): 5 bits per sketch slot, six slots to a dword (bits 30, 31 zero), four dwords = the first 24 slots
+__host__ __device__ __forceinline__ uint32_t sig5(uint64_t v) { return (uint32_t)((v * 0xD6E8FEB86659FD93ULL) >> 59); }
+constexpr uint32_t kRowSlots = 24, kRowBytes = 16;
+// DeviceIndex::node_l2b: the two bits an 8-mer (2 bits per base, base i at bits 2i) sets / tests in a start position's 64-bit set
+__host__ __device__ __forceinline__ uint64_t l2_bloom_bits(uint32_t code16)
+{
+    const uint32_t x = code16 * 0x9E3779B1u;
+    return (1ull << (x >> 26)) | (1ull << ((x >> 20) & 63u));
+}
+#define GROOT_SIG_HASH_INIT 0x2545F4914F6CDD1DULL
+__host__ __device__ __forceinline__ uint64_t sig_hash_step(uint64_t x, uint32_t top27)
+{
+    x = (x ^ top27) * 0x9E3779B97F4A7C15ULL;
+    return x ^ (x >> 29);
+}
+// sketch_sig_kernel's signature covers kSigG of the S sketch slots (round 5): slot 0 -- the smallest canonical ntHash itself, no multiply -- and
+// the kSigG - 1 slots whose MultiHash multipliers i ^ (k * multiSeed) come first in the kernel's running sum h * C0, h * C0 + h, ...
+// (slot i sits at step d = i ^ M5, M5 = (k * multiSeed) & 31).  A window whose sketch equals a read's has the same value in THOSE
+// slots: no table entry -> no seed, as rigorously as with all S slots; an entry is confirmed by text as before, and a read whose
+// entry cannot be confirmed takes the full-width kernel.  The other S - kSigG slots are never computed for reads this kernel decides.
+#ifndef GROOT_SIG_G
+#define GROOT_SIG_G 13
+#endif
+constexpr int kSigG = GROOT_SIG_G;
+// step d of the j-th signature slot (j = 1..): the j-th smallest d for which slot d ^ m5 exists; -1 if the sketch has too few slots
+__host__ __device__ constexpr int sig_step(int j, int s, int m5)
+{
+    int cnt = 0;
+    for (int d = 0; d < 32; d++) {
+        const int i = d ^ m5;
+        if (i >= 1 && i < s && ++cnt == j) return d;
+    }
+    return -1;
+}
+// what the signature keeps of a 64-bit sketch value: the top 24 bits of slot 0 (the kernel tracks the position of the read's smallest
+// k-mer in the low byte of that slot's running minimum), the top 27 of the others (MultiHash's t ^= t >> 27 leaves them alone)
+__host__ __device__ constexpr uint32_t sig_part(int j, uint64_t v) { return j == 0 ? (uint32_t)(v >> 40) : (uint32_t)(v >> 37); }
+__host__ __device__ __forceinline__ uint64_t sig_hash_fin(uint64_t x)
+{
+    x *= 0xff51afd7ed558ccdULL;
+    return x ^ (x >> 32);
+}
+// hash of a string at 2 bits per base, dword by dword (text table; the memo's string sets on the host)
+__host__ __device__ __forceinline__ uint64_t text_hash_step(uint64_t h, uint32_t dw)
+{
+    h = (h ^ dw) * 0x9E3779B97F4A7C15ULL;
+    return h ^ (h >> 29);
+}
+#define GROOT_TEXT_HASH_INIT 0xD6E8FEB86659FD93ULL
+
 } // namespace groot

@@ -7,7 +7,8 @@
 //                                           kernels above leave.                                                thread per read
 //   kernels_align.hpp    align_kernel       K3: the graphMinion loop -- IncrementSubPath call counts, hierarchical exact-match DFS; persistent,
 //                                           per-lane state machine with wave-coherent phase scheduling
-//   kernels_misc.hpp     heavy LSH-Forest reads, seed-list sort / split, call-count rows, ordering of the traversal records, table builders of open
+//   kernels_misc.hpp     heavy LSH-Forest reads, seed-list sort / split, call-count rows, ordering of the traversal records
+//   kernels_open.hpp     the kernels only groot_hip_open launches (open.hip): proof of the window texts, text table, prefix tables
 //
 // Integer / byte work throughout: no MFMA.  Hashing is bound by VALU issue, the graph walk by dependent trips to L2; reads are staged through LDS with
 // coalesced 16-byte loads; the index is reused by every read and stays in L2 / Infinity Cache.  
@@ -26,8 +27,7 @@ namespace groot {
 #define GROOT_SEED_C 0x3193c18562a02b4cULL
 #define GROOT_SEED_G 0x20323ed082572324ULL
 #define GROOT_SEED_T 0x295549f54be24456ULL
-#define GROOT_MULTI_SEED 0x90b45d39fb6da1faULL
-#define GROOT_MULTI_SHIFT 27
+#define GROOT_MULTI_SHIFT 27              // (GROOT_MULTI_SEED: device_types.hpp, with the table hashes the host shares)
 
 __device__ __forceinline__ uint64_t rol64(uint64_t v, unsigned n)
 {
@@ -50,17 +50,6 @@ __device__ __forceinline__ uint64_t seed_tab(unsigned b)
     }
 }
 
-// hash of a whole sketch for the exact-match table (host builds the table with the same function)
-__host__ __device__ __forceinline__ uint64_t sketch_hash_step(uint64_t h, uint64_t v)
-{
-    h = (h ^ v) * 0xff51afd7ed558ccdULL;
-    return h ^ (h >> 29);
-}
-#define GROOT_SKETCH_HASH_INIT 0x9E3779B97F4A7C15ULL
-// one byte of a sketch slot for DeviceIndex::band_sig
-// LSH-Forest rows (DeviceIndex::band_sig): 5 bits per sketch slot, six slots to a dword (bits 30, 31 zero), four dwords = the first 24 slots
-__host__ __device__ __forceinline__ uint32_t sig5(uint64_t v) { return (uint32_t)((v * 0xD6E8FEB86659FD93ULL) >> 59); }
-constexpr uint32_t kRowSlots = 24, kRowBytes = 16;
 // slots whose 5-bit fields agree in one dword of a row and of the read (an UPPER bound: the borrow of the zero-field test may also flag a field
 // of value 1 right above an equal one; fields neither side uses are zero on both and are taken off by the caller)
 __device__ __forceinline__ uint32_t row_same6(uint32_t w, uint32_t r)
@@ -91,12 +80,6 @@ __host__ __device__ __forceinline__ int kmer4_code(uint64_t r8)
         code |= (int)((b >> 1) & 3) << (2 * i);
     }
     return code;
-}
-// DeviceIndex::node_l2b: the two bits an 8-mer (2 bits per base, base i at bits 2i) sets / tests in a start position's 64-bit set
-__host__ __device__ __forceinline__ uint64_t l2_bloom_bits(uint32_t code16)
-{
-    const uint32_t x = code16 * 0x9E3779B1u;
-    return (1ull << (x >> 26)) | (1ull << ((x >> 20) & 63u));
 }
 // 16-bit code of the first 8 bases of r8, or -1 if one of them is not ACGT
 __host__ __device__ __forceinline__ int kmer8_code(uint64_t r8)
@@ -382,51 +365,12 @@ __device__ __forceinline__ void seed_epilogue_tab(const SeedArgs &a, const uint3
     seed_counters(a, r, q, n_hits, true);
 }
 
-// ---- helpers the host side shares with the kernels (table hashes, LDS layouts) ----
-#define GROOT_SIG_HASH_INIT 0x2545F4914F6CDD1DULL
-__host__ __device__ __forceinline__ uint64_t sig_hash_step(uint64_t x, uint32_t top27)
-{
-    x = (x ^ top27) * 0x9E3779B97F4A7C15ULL;
-    return x ^ (x >> 29);
-}
-// sketch_sig_kernel's signature covers kSigG of the S sketch slots (round 5): slot 0 -- the smallest canonical ntHash itself, no multiply -- and
-// the kSigG - 1 slots whose MultiHash multipliers i ^ (k * multiSeed) come first in the kernel's running sum h * C0, h * C0 + h, ...
-// (slot i sits at step d = i ^ M5, M5 = (k * multiSeed) & 31).  A window whose sketch equals a read's has the same value in THOSE
-// slots: no table entry -> no seed, as rigorously as with all S slots; an entry is confirmed by text as before, and a read whose
-// entry cannot be confirmed takes the full-width kernel.  The other S - kSigG slots are never computed for reads this kernel decides.
-#ifndef GROOT_SIG_G
-#define GROOT_SIG_G 13
-#endif
-constexpr int kSigG = GROOT_SIG_G;
-// step d of the j-th signature slot (j = 1..): the j-th smallest d for which slot d ^ m5 exists; -1 if the sketch has too few slots
-__host__ __device__ constexpr int sig_step(int j, int s, int m5)
-{
-    int cnt = 0;
-    for (int d = 0; d < 32; d++) {
-        const int i = d ^ m5;
-        if (i >= 1 && i < s && ++cnt == j) return d;
-    }
-    return -1;
-}
-// what the signature keeps of a 64-bit sketch value: the top 24 bits of slot 0 (the kernel tracks the position of the read's smallest
-// k-mer in the low byte of that slot's running minimum), the top 27 of the others (MultiHash's t ^= t >> 27 leaves them alone)
-__host__ __device__ constexpr uint32_t sig_part(int j, uint64_t v) { return j == 0 ? (uint32_t)(v >> 40) : (uint32_t)(v >> 37); }
-__host__ __device__ __forceinline__ uint64_t sig_hash_fin(uint64_t x)
-{
-    x *= 0xff51afd7ed558ccdULL;
-    return x ^ (x >> 32);
-}
+// ---- LDS layouts (the table hashes the host side shares with the kernels: device_types.hpp) ----
 // LDS: a static 512-byte table ({leaving, entering} base -> 16-byte entries, at strides 16 and 64, see below; static so
 // that its address folds into the ds_read offsets), then dynamic:
 constexpr uint32_t kTextBad = 2048;    // text_lookup_kernel: bytes of its bad-group bit set (one bit per 4 bases of a span of up to 64 KB)
 constexpr uint32_t kSigBad = 0;        // 4096 bits: 16-byte chunks of the span holding a byte other than ACGT
 constexpr uint32_t kSigCodes = 512;    // one dword per 16 bases
-__host__ __device__ __forceinline__ uint64_t text_hash_step(uint64_t h, uint32_t dw)
-{
-    h = (h ^ dw) * 0x9E3779B97F4A7C15ULL;
-    return h ^ (h >> 29);
-}
-#define GROOT_TEXT_HASH_INIT 0xD6E8FEB86659FD93ULL
 constexpr uint32_t kLshHeavyMaxS = 64;   // lsh_heavy_kernel keeps the read's sketch in LDS
 constexpr int kGenericMaxS = 256;      // largest sketch the run-time-sized instance of sketch_seed_kernel handles
 constexpr int kGenericMaxBands = kGenericMaxS;   // ... and the most bands (sketch size / maxK >= 1)

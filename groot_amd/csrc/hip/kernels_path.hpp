@@ -9,7 +9,7 @@ namespace groot {
 // An error-free read spells a stretch of one path's linear text.  Inside a path the DFS (dfsRecursive, alignment.go:196-254) is
 // deterministic at every node boundary where no two out-neighbours of the node share a first base, none starts with an 'N' and the
 // path's next node is one of them: it can only go on into the neighbour whose first base is the read's next base.  So a walk is a chain
-// of SEGMENTS, each one comparison of the read against one path's text (built at open: groot_hip.hip, build_path_tables), from a start
+// of SEGMENTS, each one comparison of the read against one path's text (built at open: index_tables.hpp, build_path_tables), from a start
 // (node, offset) up to the first of: the end of the read, a boundary that is not deterministic (flagged in the text), a mismatch.
 //   * a mismatch inside a node ends the branch, as in the DFS;
 //   * a mismatch on the first base of the path's next node (an unflagged boundary), a flagged boundary and the end of the path's text

@@ -1,5 +1,5 @@
 """Batch after batch through ONE groot_ctx: the statistics of the latest finished batch choose how the next one runs (groot_hip.hip,
-refreshed at collect l.1104-1119): the processing order (radix sort or stream compaction, or the list the text lookup appends itself),
+refreshed at collect l.914-929): the processing order (radix sort or stream compaction, or the list the text lookup appends itself),
 whether a first pass runs and how many workgroups it gets, how large align_kernel's persistent grid is, whether the outcome table's
 text lookup is tried, how much of the results the copy-out behind the kernels takes.  None of that may change a result: every batch of
 these scripted streams equals a fresh oracle run of the same reads -- counters, seeds, every record field, the call-count delta.
@@ -21,16 +21,16 @@ pytestmark = pytest.mark.gpu
 # The launch choices of groot_hip.hip as of this module (line numbers of that file):
 HEUR = dict(
     block=256,            # kBlock: lanes per workgroup
-    no_first_pass=0.02,   # dfs_frac below which no first pass runs (l.736-737)
-    sparse=0.05,          # kSparseBelow: stream compaction instead of the radix sort, list mode of the text lookup (l.316, 427-428, 497-510, 567)
-    dense=0.6,            # dfs_frac below which align_kernel's grid is halved and refill is 48 (l.362, 571, 603)
-    shrink=0.25,          # lean_left_frac below which align_kernel's grid is cut to max(want, n_cu) workgroups (l.576-579)
-    spare_blocks=64,      # the first pass's workgroups beyond dfs_frac * 1.05 * n / 256 (l.634)
+    no_first_pass=0.02,   # dfs_frac below which no first pass runs (l.551-552)
+    sparse=0.05,          # kSparseBelow: stream compaction instead of the radix sort, list mode of the text lookup (l.127, 238-239, 309-322, 378)
+    dense=0.6,            # dfs_frac below which align_kernel's grid is halved and refill is 48 (l.173, 382, 414)
+    shrink=0.25,          # lean_left_frac below which align_kernel's grid is cut to max(want, n_cu) workgroups (l.387-390)
+    spare_blocks=64,      # the first pass's workgroups beyond dfs_frac * 1.05 * n / 256 (l.445)
     slack=1.05,
-    left_slack=1.25,      # want = lean_left_frac * 1.25 * n / 64 / 4 + 1 (l.577)
+    left_slack=1.25,      # want = lean_left_frac * 1.25 * n / 64 / 4 + 1 (l.388)
     max_first_len=256,    # kLeanMaxLen (device_types.hpp): longest read the first pass takes
-    text_hit=0.7,         # share of a batch the text lookup answered above which it is used for the next batch (l.429)
-    text_gap=8,           # ... else it is tried again after 8, 16, ... 256 batches (ctx.hpp groot_ctx::text_retry_gap, l.1115)
+    text_hit=0.7,         # share of a batch the text lookup answered above which it is used for the next batch (l.240)
+    text_gap=8,           # ... else it is tried again after 8, 16, ... 256 batches (ctx.hpp groot_ctx::text_retry_gap, l.932)
     text_gap_max=256,
 )
 N_CU = 256                # compute units of an MI355X: the floor of the shrunk grid
@@ -228,26 +228,26 @@ def _mask_bytes(index, travs):
 
 
 def lean_slots(dfs, n):
-    """slots the first pass takes (l.634); the walked reads beyond them go to align_kernel behind the list the pass leaves (l.641-644)"""
+    """slots the first pass takes (l.445); the walked reads beyond them go to align_kernel behind the list the pass leaves (l.452-455)"""
     B = HEUR["block"]
     return min((n + B - 1) // B, int(dfs * HEUR["slack"] * n / B) + HEUR["spare_blocks"]) * B
 
 
 def shrunk_lanes(left, n):
-    """lanes of align_kernel's grid when the batch before left less than HEUR["shrink"] to it (l.576-579), at most"""
+    """lanes of align_kernel's grid when the batch before left less than HEUR["shrink"] to it (l.387-390), at most"""
     want = int(left * HEUR["left_slack"] * n / 64.0 / (HEUR["block"] / 64)) + 1
     return max(want, N_CU) * HEUR["block"]
 
 
 def copy_out(tpr, bpt, n, pw=3):
-    """(records, path-set bytes) the copy-out behind the kernels takes (l.917-921)"""
+    """(records, path-set bytes) the copy-out behind the kernels takes (l.727-731)"""
     margin = 1.0 + max(0.01, 4.0 / np.sqrt(n + 1.0))
     copied = int(n * tpr * margin) + 1024
     return copied, int(copied * (bpt if bpt > 0 else 8.0 * pw) * margin) + 4096
 
 
 class Mirror:
-    """what the ctx remembers of its latest finished batch (l.1104-1119) and what that selects for the next one (l.362-634)"""
+    """what the ctx remembers of its latest finished batch (l.914-929) and what that selects for the next one (l.173-445)"""
 
     def __init__(self, stage, memo=False):
         self.stage, self.memo = stage, memo
@@ -268,7 +268,7 @@ class Mirror:
         return copy_out(self.tpr, self.bpt, n)
 
     def text_try(self):
-        """(l.429; the counter is advanced only when the first operand is false)"""
+        """(l.240; the counter is advanced only when the first operand is false)"""
         if self.text_hit >= HEUR["text_hit"]:
             return True
         return self.without + 1 >= self.text_gap

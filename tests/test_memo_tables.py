@@ -1,4 +1,4 @@
-"""Round 3: the memo of the pipeline's own results (groot_hip.hip build_outcome_table).  Every WindowSize-mer of every indexed
+"""Round 3: the memo of the pipeline's own results (open.hip build_outcome_table).  Every WindowSize-mer of every indexed
 path goes through the ctx's pipeline once at open; at run time a read that equals such a string is answered from the outcome
 table -- found by its bases (text_lookup_kernel) or by its signature (sketch_sig_kernel + sig_info) -- and never reaches the
 align stage.  Whatever the route, seeds / records / counters / IncrementSubPath call counts equal the oracle's
