@@ -22,7 +22,7 @@ $(B)/obj/%.o: $(HIP_DIR)/%.hip $(wildcard $(HIP_DIR)/*.hpp) $(wildcard groot_amd
 $(B)/libgroot_hip.so: $(HIP_OBJ)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(HIP_OBJ)
 
-$(B)/groot-hip: groot_amd/csrc/cli/groot_hip_main.cpp $(B)/libgroot_host.so $(B)/libgroot_hip.so
+$(B)/groot-hip: groot_amd/csrc/cli/groot_hip_main.cpp $(wildcard groot_amd/csrc/cli/*.hpp) $(B)/libgroot_host.so $(B)/libgroot_hip.so
 	g++ -O2 -std=c++17 -Wall -Wextra -Iinclude -o $@ $< -L$(B) -lgroot_hip -lgroot_host -lpthread \
 	    '-Wl,-rpath,$$ORIGIN' -Wl,-rpath-link,$(B) -Wl,-rpath-link,/opt/rocm/lib
 

@@ -1,0 +1,136 @@
+// align: what the contexts count on the device beside the records (--report, --sharedReads, --abundance, --calls, --paired, --assignFrom),
+// added up on the host.  A ctx is harvested before it closes (a reopen in the middle of the stream) and once at the end of the stream.
+#pragma once
+#include "align_plan.hpp"
+
+namespace {
+
+struct AcovExport {                          // --calls: a ctx's ECs and assigned-coverage table, as exported (groot_host_acov_merge)
+    std::vector<uint64_t> off, cnt, tn;
+    std::vector<uint32_t> ids, tuples;
+};
+
+struct Harvested {                           // the sums over every harvest so far
+    std::vector<uint64_t> cov_records, cov_depth;            // --report: records per path, depth per base (groot_hip_coverage_*)
+    std::vector<uint32_t> sh_a, sh_b;                        // --sharedReads: every ctx's nonzero pairs, appended
+    std::vector<uint64_t> sh_n;
+    std::vector<uint64_t> ec_off{0}, ec_cnt;                 // --abundance: the equivalence classes of every ctx, appended (CSR)
+    std::vector<uint32_t> ec_ids;
+    uint64_t fr_joined = 0, fr_split = 0, fr_single = 0;     // --paired / --interleaved: fragments per class
+    std::vector<std::unique_ptr<AcovExport>> acov;           // --calls: one export per harvest
+    groot_assign_stats assign{};                             // --assignFrom
+};
+
+class RunCounters {
+public:
+    // (--assignFrom: alpha of the first pass is read here, and handed to every ctx with the other switches)
+    RunCounters(const Args &a, const AlignPlan &plan, const groot_index_view &v) : a_(a), plan_(plan), v_(v)
+    {
+        for (uint32_t p = 0; p < v.n_paths; p++) cov_slots_ += v.path_len[p];
+        h_.cov_records.resize(plan.report ? v.n_paths : 0);
+        h_.cov_depth.resize(plan.report ? cov_slots_ : 0);
+        if (!plan.assign) return;
+        uint64_t named = 0;
+        assign_alpha_.resize(v.n_paths);
+        if (groot_host_abundance_read(&v, a.assign_from.c_str(), assign_alpha_.data(), &named)) die("%s", groot_host_last_error());
+        logf("\tassignment: em_reads of %llu ARG(s) read from %s, minimum posterior %g", (unsigned long long)named, a.assign_from.c_str(), a.min_posterior);
+    }
+
+    // both: 0, or the status of the library call that failed (groot_hip_last_error(ctx) has the text)
+    int enable(groot_ctx *ctx, int on) const
+    {
+        if (plan_.assign)
+            if (int rc = groot_hip_assign_enable(ctx, on ? assign_alpha_.data() : nullptr, v_.n_paths, a_.min_posterior)) return rc;
+        if (plan_.frags)
+            if (int rc = groot_hip_pairs_enable(ctx, on)) return rc;
+        if (plan_.report)
+            if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
+        if (plan_.shared)
+            if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
+        if (plan_.calls && on)
+            if (int rc = groot_hip_acov_enable(ctx, 1)) return rc;
+        return plan_.abundance ? groot_hip_ec_enable(ctx, on) : 0;     // (off: assigned coverage goes with it)
+    }
+
+    // assign stats, pair stats, acov-or-EC export, coverage, shared pairs: each added under the lock (the mappers harvest side by side)
+    int harvest(groot_ctx *ctx)
+    {
+        if (plan_.assign) {
+            groot_assign_stats st{};
+            if (int rc = groot_hip_assign_stats(ctx, &st)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            groot_assign_stats &t = h_.assign;
+            t.reads += st.reads; t.assigned += st.assigned; t.unassigned += st.unassigned; t.below += st.below;
+            t.ties += st.ties; t.records_in += st.records_in; t.records_kept += st.records_kept;
+            t.travs_emptied += st.travs_emptied;
+        }
+        if (plan_.frags) {
+            uint64_t j = 0, sp = 0, si = 0;
+            if (int rc = groot_hip_pairs_stats(ctx, &j, &sp, &si)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            h_.fr_joined += j; h_.fr_split += sp; h_.fr_single += si;
+        }
+        if (plan_.calls) {
+            uint64_t ne = 0, ni = 0, nt = 0;
+            if (int rc = groot_hip_acov_export(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, &ne, &ni, &nt)) return rc;
+            std::unique_ptr<AcovExport> x(new AcovExport());
+            x->off.resize(ne + 1); x->cnt.resize(ne + 1); x->ids.resize(ni + 1); x->tuples.resize(4 * nt + 4); x->tn.resize(nt + 1);
+            if (ne || nt)
+                if (int rc = groot_hip_acov_export(ctx, x->off.data(), x->ids.data(), x->cnt.data(), x->tuples.data(), x->tn.data(), ne, ni, nt, &ne, &ni, &nt)) return rc;
+            x->cnt.resize(ne); x->ids.resize(ni); x->tuples.resize(4 * nt); x->tn.resize(nt);
+            std::lock_guard<std::mutex> lk(mu_);
+            append_ecs(x->off.data(), x->ids.data(), x->cnt.data(), ne, ni);
+            h_.acov.push_back(std::move(x));
+        } else if (plan_.abundance) {
+            uint64_t ne = 0, ni = 0, me = 0, mi = 0;
+            if (int rc = groot_hip_ec_export(ctx, nullptr, nullptr, nullptr, 0, 0, &ne, &ni)) return rc;
+            std::vector<uint64_t> off(ne + 1), cnt(ne);
+            std::vector<uint32_t> ids(ni);
+            if (ne)
+                if (int rc = groot_hip_ec_export(ctx, off.data(), ids.data(), cnt.data(), ne, ni, &me, &mi)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            append_ecs(off.data(), ids.data(), cnt.data(), ne, ni);
+        }
+        if (!plan_.report) return 0;
+        std::vector<uint64_t> r(v_.n_paths), d(cov_slots_);
+        if (int rc = groot_hip_coverage_export(ctx, r.data(), d.data())) return rc;
+        std::lock_guard<std::mutex> lk(mu_);
+        for (size_t i = 0; i < r.size(); i++) h_.cov_records[i] += r[i];
+        for (size_t i = 0; i < d.size(); i++) h_.cov_depth[i] += d[i];
+        if (!plan_.shared) return 0;
+        // --sharedReads: the ctx's nonzero pairs, appended (a read goes to one ctx only: the sums are exact, groot_host_shared_from_counts
+        // adds up repeated pairs)
+        uint64_t n = 0, m = 0;
+        if (int rc = groot_hip_shared_export(ctx, nullptr, nullptr, nullptr, 0, &n)) return rc;
+        std::vector<uint32_t> pa(n), pb(n);
+        std::vector<uint64_t> cnt(n);
+        if (n)
+            if (int rc = groot_hip_shared_export(ctx, pa.data(), pb.data(), cnt.data(), n, &m)) return rc;
+        h_.sh_a.insert(h_.sh_a.end(), pa.begin(), pa.end());
+        h_.sh_b.insert(h_.sh_b.end(), pb.begin(), pb.end());
+        h_.sh_n.insert(h_.sh_n.end(), cnt.begin(), cnt.end());
+        return 0;
+    }
+
+    const Harvested &totals() const { return h_; }   // for the writers, once the mappers are joined
+
+private:
+    // a ctx's n_ec classes over n_ids path ids behind the merged CSR (mu_ held)
+    void append_ecs(const uint64_t *off, const uint32_t *ids, const uint64_t *cnt, uint64_t n_ec, uint64_t n_ids)
+    {
+        const uint64_t base = h_.ec_ids.size();
+        for (uint64_t e = 0; e < n_ec; e++) h_.ec_off.push_back(base + off[e + 1]);
+        h_.ec_ids.insert(h_.ec_ids.end(), ids, ids + n_ids);
+        h_.ec_cnt.insert(h_.ec_cnt.end(), cnt, cnt + n_ec);
+    }
+
+    const Args &a_;
+    const AlignPlan &plan_;
+    const groot_index_view &v_;
+    uint64_t cov_slots_ = 0;
+    std::vector<double> assign_alpha_;
+    std::mutex mu_;
+    Harvested h_;
+};
+
+} // namespace

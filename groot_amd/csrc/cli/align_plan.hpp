@@ -1,0 +1,119 @@
+// align, stages 1 and 2: what the flags ask for (or why they are refused), and the input files and directories.
+#pragma once
+#include "cli_common.hpp"
+
+namespace {
+
+struct AlignPlan {
+    bool report = false, shared = false, abundance = false, calls = false, assign = false, rarefy = false;
+    bool frags = false;      // --paired / --interleaved
+    bool counters = false;   // a ctx carries switches: set at open and reopen, harvested before it closes
+};
+
+__attribute__((format(printf, 1, 2))) int refuse(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    fputc('\n', stderr);
+    return 1;
+}
+
+// Every refusal of the flags, the first failing check first; 1 = refused (message written, nothing else touched: the log is not open yet)
+int plan_align(const Args &a, AlignPlan *p)
+{
+    if (a.index_dir.empty()) { puts("please specify a directory with the index files (--indexDir)"); return 1; }
+    if (a.fasta) return refuse("--fasta is an experimental reference feature that is not supported");
+    p->report = !a.report_out.empty();
+    if (p->report && a.no_align) return refuse("--report needs the exact alignments: it cannot be combined with --noAlign");
+    if (p->report && a.cov_cutoff > 1.0) return refuse("supplied coverage cutoff exceeds 1.0 (100%%): %g", a.cov_cutoff);   // cmd/report.go:95-97
+    p->shared = !a.shared_out.empty();
+    if (p->shared && !p->report) return refuse("--sharedReads lists pairs of reported ARGs: it needs --report");
+    p->abundance = !a.abundance_out.empty();
+    if (p->abundance && a.no_align) return refuse("--abundance needs the exact alignments: it cannot be combined with --noAlign");
+    if (a.bootstraps && !p->abundance) return refuse("--bootstraps adds columns to the abundance file: it needs --abundance");
+    p->calls = !a.calls_out.empty();
+    p->assign = !a.assign_from.empty();
+    p->rarefy = !a.rarefy_out.empty();
+    if (p->assign) {
+        // the counters of S(r) see what assignment leaves of it -- one path per read
+        const struct { bool on; const char *flag, *why; } refused[] = {
+            {p->rarefy, "--rarefy", "it redoes the estimate of --abundance on subsamples, and an assigned read lies on one ARG: run it with the first pass"},
+            {p->shared, "--sharedReads", "it counts the reads two ARGs share, and an assigned read lies on one ARG"},
+            {p->abundance, "--abundance", "it estimates from every ARG a read lies on, and an assigned read lies on one: run it as the first pass"},
+            {p->calls, "--calls", "it weighs every record of a read, and an assigned read keeps the records on one ARG"},
+            {a.paired, "--paired", "fragments are not assigned yet: the mates would be assigned one by one"},
+            {a.interleaved, "--interleaved", "fragments are not assigned yet: the mates would be assigned one by one"},
+            {a.no_align, "--noAlign", "assignment filters the exact alignments, which it leaves out"},
+        };
+        for (const auto &r : refused)
+            if (r.on) return refuse("--assignFrom cannot be combined with %s: %s", r.flag, r.why);
+        if (!(a.min_posterior >= 0.0 && a.min_posterior <= 1.0)) return refuse("--minPosterior is a share: %g is not in [0, 1]", a.min_posterior);
+        if (!is_file(a.assign_from)) return refuse("--assignFrom: no file found at %s", a.assign_from.c_str());
+    } else if (a.min_posterior != 0.0) return refuse("--minPosterior is the threshold of --assignFrom: it needs it");
+    if (p->rarefy && !p->abundance) return refuse("--rarefy redoes the estimate of --abundance at every depth: it needs --abundance");
+    if (p->rarefy && (!a.rarefy_steps || !a.rarefy_reps)) return refuse("--rarefySteps and --rarefyReps must be at least 1");
+    if (p->calls && !p->abundance) return refuse("--calls has a line per line of the abundance file: it needs --abundance");
+    if (p->calls && a.no_align) return refuse("--calls needs the exact alignments: it cannot be combined with --noAlign");
+    if (p->calls && (a.paired || a.interleaved))
+        return refuse("--calls cannot be combined with --paired / --interleaved yet: a fragment's set is the intersection of its mates' sets, and the records "
+                      "outside the intersection have no weight rule");
+    if (a.call_support && !p->calls) return refuse("--callSupport adds columns to the calls file: it needs --calls");
+    if (a.call_support && !a.bootstraps) return refuse("--callSupport is computed from the bootstrap replicates: it needs --bootstraps");
+    if (p->calls && a.cov_cutoff > 1.0) return refuse("supplied coverage cutoff exceeds 1.0 (100%%): %g", a.cov_cutoff);
+    if (a.no_bam && !p->report && !p->abundance) return refuse("--noBam without --report would leave no output of the alignments");
+    if (a.no_bam && !a.bam_out.empty()) return refuse("--noBam and --bam contradict each other");
+    if (a.paired && a.interleaved) return refuse("--paired and --interleaved contradict each other: the mates come in two files or in one");
+    p->frags = a.paired || a.interleaved;
+    if (p->frags && !p->shared && !p->abundance)
+        return refuse("%s changes what --sharedReads and --abundance count, and nothing else: it needs one of them", a.paired ? "--paired" : "--interleaved");
+    if (a.paired && (a.fastq.empty() || a.fastq.size() % 2))
+        return refuse("--paired takes the -f files two at a time (R1,R2[,R1b,R2b...]): %zu file(s) given", a.fastq.size());
+    p->counters = p->report || p->abundance || p->assign;
+    return 0;
+}
+
+struct AlignInputs {
+    std::string gidx, gg, lshe, graph_dir;   // <indexDir>/groot.gidx, or the reference's own groot.gg + groot.lshe; where the GFAs go
+};
+
+// The FASTQ files, the index directory and the graph directory (created here), with the log lines of cmd/align.go:165-197
+AlignInputs check_inputs(const Args &a)
+{
+    logf("checking parameters...");
+    for (auto &f : a.fastq) {
+        if (!is_file(f)) die("no file found at %s", f.c_str());
+        static const char *exts[] = {"fastq", "fq", "fasta", "fna", "fa"};   // misc.CheckExt (cmd/align.go:175)
+        std::string base = f;
+        if (base.size() > 3 && base.compare(base.size() - 3, 3, ".gz") == 0) base.resize(base.size() - 3);
+        size_t dot = base.rfind('.');
+        bool ok = false;
+        for (auto e : exts) ok |= dot != std::string::npos && base.substr(dot + 1) == e;
+        if (!ok) die("file does not have recognised extension: %s", f.c_str());
+    }
+    if (a.fastq.empty()) logf("\tinput file: using STDIN");
+    if (!is_dir(a.index_dir)) die("no directory found at %s", a.index_dir.c_str());
+    AlignInputs in;
+    in.gidx = a.index_dir + "/groot.gidx";
+    // an index directory of the reference itself (cmd/align.go:181-182: groot.gg + groot.lshe) is read through the gob reader
+    in.gg = a.index_dir + "/groot.gg";
+    in.lshe = a.index_dir + "/groot.lshe";
+    if (!is_file(in.gidx) && !(is_file(in.gg) && is_file(in.lshe))) die("no file found at %s (nor groot.gg + groot.lshe)", in.gidx.c_str());
+    in.graph_dir = a.graph_dir;
+    if (in.graph_dir.empty()) {   // cmd/align.go:24: ./groot-graphs-<timestamp>
+        char ts[32];
+        time_t now = time(nullptr);
+        struct tm tmv;
+        localtime_r(&now, &tmv);
+        strftime(ts, sizeof ts, "%Y%m%d%H%M%S", &tmv);
+        in.graph_dir = std::string("./groot-graphs-") + ts;
+    }
+    make_dir(in.graph_dir);
+    logf("\tminimum k-mer coverage: %.0f", a.min_kmer_cov);
+    logf("\tprocessors: %d", a.proc);
+    for (auto &f : a.fastq) logf("\tinput file: %s", f.c_str());
+    return in;
+}
+
+} // namespace

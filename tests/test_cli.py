@@ -219,6 +219,35 @@ def test_reads_longer_than_the_context_was_opened_for(cli, argannot_index, tmp_p
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("bad", ["short_read", "bad_header"])
+@pytest.mark.parametrize("outputs", ["bam", "report"])
+def test_a_failing_batch_ends_the_run_with_its_message(cli, argannot_index, tmp_path, bad, outputs):
+    """A batch that fails in the middle of the stream ends the run: the writer hands the tickets it still holds back, the mappers of both
+    contexts finish, the threads are joined, and the process leaves on its own with the message of what failed.  short_read: a read shorter than
+    k, which the library answers in collect with GROOT_E_SHORT_READ (a mapper's path; tests/test_gpu_parity.py has it at the library level);
+    bad_header: a record whose name line has no '@', which the FASTQ parser refuses (the producer's path)."""
+    idx_dir = tmp_path / "idx"
+    idx_dir.mkdir()
+    argannot_index.save(str(idx_dir / "groot.gidx"))
+    short = read_fastq(os.path.join(DATA, "full-argannot-perfect-reads-small.fq.gz"))[:400]
+    fq = tmp_path / "bad.fq"
+    with open(fq, "wb") as f:
+        for i, (n, s, q) in enumerate(short):
+            f.write(b"@" + n + b"\n" + s + b"\n+\n" + q + b"\n")
+            if i == 250:
+                f.write((b"@tiny\n" if bad == "short_read" else b"tiny\n") + s[:20] + b"\n+\n" + q[:20] + b"\n")
+    out = ["--bam", str(tmp_path / "o.bam")] if outputs == "bam" else ["--noBam", "--report", str(tmp_path / "r.tsv"), "--abundance", str(tmp_path / "a.tsv")]
+    r = subprocess.run([cli, "align", "-i", str(idx_dir), "-f", str(fq), "--log", str(tmp_path / "a.log"), "-g", str(tmp_path / "g"), "--batch", "128",
+                        "--ctxPerGpu", "2", "--depth", "2", "-p", "2"] + out, cwd=REPO, capture_output=True, timeout=120)
+    err = r.stderr.decode()
+    print(r.returncode, err)
+    assert r.returncode == 1, err
+    assert ("k size is greater than sequence length" if bad == "short_read" else "read ID in fastq file does not begin with @") in err
+    assert "internal error" not in err
+    assert not os.path.exists(str(tmp_path / "r.tsv")) and not os.path.exists(str(tmp_path / "a.tsv"))
+
+
+@pytest.mark.gpu
 def test_bench_multi_rank_code_path(argannot_index, tmp_path):
     """bench.py as the driver launches it for N>1 (torch.distributed.run, one rank per GPU).  This box has one GPU, so both
     ranks share it and talk over gloo (GROOT_BENCH_TEST_SAME_DEVICE): the sharding, barriers, the all-reduce of the call-count
