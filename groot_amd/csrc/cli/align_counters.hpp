@@ -1,4 +1,4 @@
-// align: what the contexts count on the device beside the records (--report, --sharedReads, --abundance, --calls, --paired, --assignFrom),
+// align: what the contexts count on the device beside the records (--report, --sharedReads, --abundance, --calls, --paired, --assignFrom, --variants),
 // added up on the host.  A ctx is harvested before it closes (a reopen in the middle of the stream) and once at the end of the stream.
 #pragma once
 #include "align_plan.hpp"
@@ -19,6 +19,8 @@ struct Harvested {                           // the sums over every harvest so f
     uint64_t fr_joined = 0, fr_split = 0, fr_single = 0;     // --paired / --interleaved: fragments per class
     std::vector<std::unique_ptr<AcovExport>> acov;           // --calls: one export per harvest
     groot_assign_stats assign{};                             // --assignFrom
+    std::vector<uint64_t> res_depth, res_alt;                // --variants: rescued depth per base, A / C / G / T counts per base (groot_hip_rescue_*)
+    groot_rescue_stats rescue{};
 };
 
 class RunCounters {
@@ -27,8 +29,10 @@ public:
     RunCounters(const Args &a, const AlignPlan &plan, const groot_index_view &v) : a_(a), plan_(plan), v_(v)
     {
         for (uint32_t p = 0; p < v.n_paths; p++) cov_slots_ += v.path_len[p];
-        h_.cov_records.resize(plan.report ? v.n_paths : 0);
-        h_.cov_depth.resize(plan.report ? cov_slots_ : 0);
+        h_.cov_records.resize(plan.coverage ? v.n_paths : 0);
+        h_.cov_depth.resize(plan.coverage ? cov_slots_ : 0);
+        h_.res_depth.resize(plan.variants ? cov_slots_ : 0);
+        h_.res_alt.resize(plan.variants ? 4 * cov_slots_ : 0);
         if (!plan.assign) return;
         uint64_t named = 0;
         assign_alpha_.resize(v.n_paths);
@@ -43,8 +47,10 @@ public:
             if (int rc = groot_hip_assign_enable(ctx, on ? assign_alpha_.data() : nullptr, v_.n_paths, a_.min_posterior)) return rc;
         if (plan_.frags)
             if (int rc = groot_hip_pairs_enable(ctx, on)) return rc;
-        if (plan_.report)
+        if (plan_.coverage)
             if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
+        if (plan_.variants)
+            if (int rc = groot_hip_rescue_enable(ctx, &v_, on ? (uint32_t)a_.rescue : 0u)) return rc;
         if (plan_.shared)
             if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
         if (plan_.calls && on)
@@ -52,7 +58,7 @@ public:
         return plan_.abundance ? groot_hip_ec_enable(ctx, on) : 0;     // (off: assigned coverage goes with it)
     }
 
-    // assign stats, pair stats, acov-or-EC export, coverage, shared pairs: each added under the lock (the mappers harvest side by side)
+    // assign stats, pair stats, acov-or-EC export, rescue, coverage, shared pairs: each added under the lock (the mappers harvest side by side)
     int harvest(groot_ctx *ctx)
     {
         if (plan_.assign) {
@@ -91,7 +97,19 @@ public:
             std::lock_guard<std::mutex> lk(mu_);
             append_ecs(off.data(), ids.data(), cnt.data(), ne, ni);
         }
-        if (!plan_.report) return 0;
+        if (plan_.variants) {
+            groot_rescue_stats st{};
+            std::vector<uint64_t> d(cov_slots_), al(4 * cov_slots_);
+            if (int rc = groot_hip_rescue_stats(ctx, &st)) return rc;
+            if (int rc = groot_hip_rescue_export(ctx, d.data(), al.data())) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            groot_rescue_stats &t = h_.rescue;
+            t.candidates += st.candidates; t.rescued += st.rescued; t.exact += st.exact; t.placements += st.placements;
+            t.too_short += st.too_short; t.non_acgt += st.non_acgt; t.launches += st.launches; t.text_paths = st.text_paths;
+            for (size_t i = 0; i < d.size(); i++) h_.res_depth[i] += d[i];
+            for (size_t i = 0; i < al.size(); i++) h_.res_alt[i] += al[i];
+        }
+        if (!plan_.coverage) return 0;
         std::vector<uint64_t> r(v_.n_paths), d(cov_slots_);
         if (int rc = groot_hip_coverage_export(ctx, r.data(), d.data())) return rc;
         std::lock_guard<std::mutex> lk(mu_);

@@ -272,4 +272,18 @@ void write_stats(const Stream &s, const RunTimes &t, uint64_t bam_bytes)
     fclose(sf);
 }
 
+// --variants: the summed rescue tables beside the exact depth of report coverage, and the run's stats in the log
+void write_variants(const Args &a, const groot_index_view &v, const Harvested &h)
+{
+    uint64_t n = 0;
+    if (groot_host_variants_write(&v, h.res_depth.data(), h.res_alt.data(), h.cov_depth.data(), (uint64_t)a.variant_min_reads, a.variant_min_share,
+                                  a.variants_out.c_str(), &n))
+        die("%s", groot_host_last_error());
+    const groot_rescue_stats &r = h.rescue;
+    logf("\tvariants: %llu unaligned read(s) tried with up to %ld substitution(s): %llu rescued (%llu without one) in %llu placement(s); left out: %llu too short, %llu not "
+         "A/C/G/T; %llu line(s) written to %s (at least %lld read(s), share %g)",
+         (unsigned long long)r.candidates, a.rescue, (unsigned long long)r.rescued, (unsigned long long)r.exact, (unsigned long long)r.placements,
+         (unsigned long long)r.too_short, (unsigned long long)r.non_acgt, (unsigned long long)n, a.variants_out.c_str(), a.variant_min_reads, a.variant_min_share);
+}
+
 } // namespace

@@ -5,7 +5,8 @@
 namespace {
 
 struct AlignPlan {
-    bool report = false, shared = false, abundance = false, calls = false, assign = false, rarefy = false;
+    bool report = false, shared = false, abundance = false, calls = false, assign = false, rarefy = false, variants = false;
+    bool coverage = false;   // report coverage is counted: --report, or --variants for its exact depth
     bool frags = false;      // --paired / --interleaved
     bool counters = false;   // a ctx carries switches: set at open and reopen, harvested before it closes
 };
@@ -70,7 +71,17 @@ int plan_align(const Args &a, AlignPlan *p)
         return refuse("%s changes what --sharedReads and --abundance count, and nothing else: it needs one of them", a.paired ? "--paired" : "--interleaved");
     if (a.paired && (a.fastq.empty() || a.fastq.size() % 2))
         return refuse("--paired takes the -f files two at a time (R1,R2[,R1b,R2b...]): %zu file(s) given", a.fastq.size());
-    p->counters = p->report || p->abundance || p->assign;
+    // --variants: checked behind everything above
+    p->variants = !a.variants_out.empty();
+    if (p->variants && a.no_align) return refuse("--variants rescues the reads the exact alignments leave out: it cannot be combined with --noAlign");
+    if (p->variants && p->assign) return refuse("--variants cannot be combined with --assignFrom: assignment rewrites the records that tell which reads are unaligned");
+    if (a.rescue_given && !p->variants) return refuse("--rescue is the number of substitutions --variants allows: it needs it");
+    if (a.variant_min_given && !p->variants) return refuse("--variantMinReads and --variantMinShare are the thresholds of --variants: they need it");
+    if (p->variants && (a.rescue < 1 || a.rescue > 3)) return refuse("--rescue allows 1, 2 or 3 substitutions: %ld", a.rescue);
+    if (p->variants && a.variant_min_reads < 0) return refuse("--variantMinReads is a number of reads: %lld", a.variant_min_reads);
+    if (p->variants && !(a.variant_min_share >= 0.0 && a.variant_min_share <= 1.0)) return refuse("--variantMinShare is a share: %g is not in [0, 1]", a.variant_min_share);
+    p->coverage = p->report || p->variants;
+    p->counters = p->report || p->abundance || p->assign || p->variants;
     return 0;
 }
 

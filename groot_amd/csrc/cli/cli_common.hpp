@@ -66,6 +66,11 @@ struct Args {
     std::string rarefy_out;                // --rarefy: the rarefaction curve of --abundance (and --calls): nested subsamples without replacement
     uint32_t rarefy_steps = GROOT_RAREFY_STEPS, rarefy_reps = GROOT_RAREFY_REPS;
     uint64_t rarefy_seed = 1;
+    std::string variants_out;              // --variants: what the reads without an exact alignment, rescued with up to --rescue substitutions, say differs
+    long rescue = 2;                       // --rescue M (1..3)
+    long long variant_min_reads = 2;       // --variantMinReads N
+    double variant_min_share = 0.1;        // --variantMinShare S
+    bool rescue_given = false, variant_min_given = false;
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
     bool gpu_given = false, write_gob = false;

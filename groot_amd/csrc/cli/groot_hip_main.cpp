@@ -37,6 +37,7 @@ void usage()
             "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
+            "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
@@ -57,6 +58,10 @@ void usage()
             "                   and only when its share of their sum is >= --minPosterior; MAPQ = 3 per halving of the share of the others, 0..60.  The filter\n"
             "                   runs on the GPU ahead of the BAM writer and of --report, which then covers what was assigned.  Not with --sharedReads,\n"
             "                   --abundance, --calls, --paired, --interleaved or --noAlign;\n"
+            "                   --variants: the reads WITHOUT an exact alignment are laid ungapped on the ARGs with up to --rescue (1..3) substitutions, on the\n"
+            "                   GPU; `name pos ref alt alt_reads rescued_depth exact_depth share` for every base where at least --variantMinReads rescued reads\n"
+            "                   show another base and they are at least --variantMinShare of the depth there.  The BAM and every other file stay as they are.\n"
+            "                   Not with --assignFrom or --noAlign;\n"
             "                   --paired: the -f files are R1,R2[,R1b,R2b...], first with second, third with fourth; --interleaved: the mates alternate in\n"
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
@@ -117,6 +122,15 @@ Args parse(int argc, char **argv)
             char *end = nullptr;
             a.min_posterior = strtod(t.c_str(), &end);
             if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "--minPosterior is a number in [0, 1]: %s\n", t.c_str()); exit(1); }
+        }
+        else if (a.cmd == "align" && f == "--variants") a.variants_out = v();
+        else if (a.cmd == "align" && (f == "--rescue" || f == "--variantMinReads" || f == "--variantMinShare")) {   // (numbers that decide what is reported: refused when they are none)
+            const std::string t = v();
+            char *end = nullptr;
+            if (f == "--rescue") { a.rescue = strtol(t.c_str(), &end, 10); a.rescue_given = true; }
+            else if (f == "--variantMinReads") { a.variant_min_reads = strtoll(t.c_str(), &end, 10); a.variant_min_given = true; }
+            else { a.variant_min_share = strtod(t.c_str(), &end); a.variant_min_given = true; }
+            if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
         }
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
         else if (ar && f == "--paired") a.paired = true;
@@ -304,6 +318,7 @@ int run_align(const Args &a)
     if (plan.abundance) boot = write_abundance(a, plan, v, h, first_device);
     if (plan.calls) write_calls(a, plan, v, h, first_device, boot);
     if (plan.report) write_report(a, plan, v, h);
+    if (plan.variants) write_variants(a, v, h);
     t.stream_s = seconds_since(t_stream);
     auto t_post = std::chrono::steady_clock::now();
     if (s.mapped_reads == 0) logf("no reads could be mapped to the reference graphs");           // sketch.go:328-334

@@ -1,7 +1,7 @@
 // counters.hip -- the counters that run behind every batch's order stage, and their C ABI (include/groot_hip.h): report coverage
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
-// draws (kernels_rare.hpp).  One of the six translation units of
+// draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <hip/hip_runtime.h>
 
@@ -22,7 +22,9 @@
 #include "kernels_cov.hpp"
 #include "kernels_csup.hpp"
 #include "kernels_ec.hpp"
+#include "index_tables.hpp"
 #include "kernels_rare.hpp"
+#include "kernels_rescue.hpp"
 #include "kernels_shared.hpp"
 
 using namespace groot;
@@ -391,6 +393,19 @@ int counters_launch(groot_ctx *c, Slot *s)
         if (paired) hipLaunchKernelGGL(shared_expand_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, tab);
         else hipLaunchKernelGGL(shared_expand_kernel<false>, gt, dim3(kBlock), 0, c->tstream, sa, tab);
         HIP_TRY(c, hipGetLastError());
+    }
+    if (k.res_on) {   // (the slot's reads, the order stage's scan -- both the tail stream's until the next batch's order stage -- and the ctx's own buffers)
+        RescueArgs ra{};
+        ra.seq = s->seq(); ra.seq_off = s->off(); ra.ctr = s->d_ctr.p; ra.trav_off = c->trav_off.p;
+        ra.rbuf = k.res_rbuf.p; ra.rcap = k.res_rcap; ra.cand = k.res_cand.p; ra.n_cand = k.res_ncand.p;
+        ra.text = k.res_text.p; ra.tag = k.res_tag.p; ra.path = k.res_path.p; ra.tab = k.res_tab.p; ra.occ = k.res_occ.p; ra.slot_base = k.res_base.p;
+        ra.starts = k.res_starts.p; ra.ends = k.res_ends.p; ra.alt = k.res_alt.p; ra.stats = k.res_stats.p;
+        ra.tab_mask = (uint32_t)k.res_tab.n - 1u; ra.n_reads = s->n_reads; ra.max_mismatch = k.res_m;
+        HIP_TRY(c, hipMemsetAsync(k.res_ncand.p, 0, sizeof(uint32_t), c->tstream));
+        hipLaunchKernelGGL(rescue_pack_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+        hipLaunchKernelGGL(rescue_count_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+        HIP_TRY(c, hipGetLastError());
+        k.res_launches += 2;
     }
     return GROOT_OK;
 }
@@ -926,6 +941,7 @@ int groot_hip_assign_enable(groot_ctx *c, const double *alpha, uint32_t n_paths,
     }
     if (k.sh_on || k.ec_on || k.acov_on || k.pairs_on)
         return fail(c, GROOT_E_UNSUPPORTED, "assignment collapses S(r): not with shared reads, equivalence classes, assigned coverage or pairing on");
+    if (k.res_on) return fail(c, GROOT_E_UNSUPPORTED, "assignment rewrites the records mismatch rescue tells the unaligned reads by (groot_hip_rescue_enable)");
     if (n_paths != k.h_len.size()) return fail(c, GROOT_E_INVALID, "assignment: alpha has %u values, the index %zu paths", n_paths, k.h_len.size());
     if (!(min_posterior >= 0.0 && min_posterior <= 1.0)) return fail(c, GROOT_E_INVALID, "assignment: min_posterior %g is not in [0, 1]", min_posterior);
     for (uint32_t p = 0; p < n_paths; p++)
@@ -992,6 +1008,135 @@ int groot_hip_pairs_stats(groot_ctx *c, uint64_t *joined, uint64_t *split, uint6
     if (joined) *joined = st[kSharedPairStats];
     if (split) *split = st[kSharedPairStats + 1];
     if (single) *single = st[kSharedPairStats + 2];
+    return GROOT_OK;
+}
+
+// ---- mismatch rescue (kernels_rescue.hpp) --------------------------------------------------------------------------------
+static void rescue_release(Counters &k)
+{
+    for (auto *b : {&k.res_text, &k.res_tag, &k.res_cand, &k.res_ncand}) b->release();
+    for (auto *b : {&k.res_rbuf, &k.res_starts, &k.res_ends, &k.res_alt, &k.res_stats}) b->release();
+    k.res_path.release(); k.res_tab.release(); k.res_occ.release(); k.res_base.release();
+    k.res_on = false; k.res_m = 0; k.res_rcap = 0;
+}
+
+static hipError_t rescue_zero(Counters &k)
+{
+    const uint64_t slots = std::max<uint64_t>(k.h_cov_base.back(), 1);
+    hipError_t e = hipMemset(k.res_starts.p, 0, slots * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(k.res_ends.p, 0, slots * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(k.res_alt.p, 0, 4 * slots * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(k.res_stats.p, 0, kRescueStats * sizeof(unsigned long long));
+    return e;
+}
+
+int groot_hip_rescue_enable(groot_ctx *c, const groot_index_view *idx, uint32_t max_mismatch)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "mismatch rescue can only be switched while nothing is in flight");
+    if (max_mismatch > kRescueMaxMismatch) return fail(c, GROOT_E_INVALID, "mismatch rescue: %u mismatches, at most %u are supported", max_mismatch, kRescueMaxMismatch);
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!max_mismatch) {
+        rescue_release(k);
+        return GROOT_OK;
+    }
+    if (k.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "mismatch rescue tells the unaligned reads by their records, which assignment rewrites (groot_hip_assign_enable)");
+    const bool same_index = idx && idx->n_paths == k.h_len.size() && (size_t)idx->n_nodes + 1 == k.h_np_off.size() && std::equal(k.h_len.begin(), k.h_len.end(), idx->path_len);
+    if (idx && !same_index) return fail(c, GROOT_E_INVALID, "mismatch rescue: not the index the ctx was opened with");
+    if (k.res_on) {                        // another M: the tables do not depend on it, the counts do
+        if (max_mismatch != k.res_m) {
+            hipError_t e = rescue_zero(k);
+            if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "mismatch rescue: %s", hipGetErrorString(e));
+            k.res_m = max_mismatch;
+        }
+        return GROOT_OK;
+    }
+    if (!idx) return fail(c, GROOT_E_INVALID, "mismatch rescue: the tables are built from the index the ctx was opened with, and none was given");
+    RescueTables rt;
+    if (!build_rescue_tables(idx, rt))
+        return fail(c, GROOT_E_UNSUPPORTED, "mismatch rescue: path texts of %zu bases are beyond 32-bit bit offsets", rt.n_bases);
+    const uint64_t slots = k.h_cov_base.back(), R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    k.res_rcap = c->prm.max_batch_bases / 32 + R + 2;
+    hipError_t e = upload(k.res_text, rt.text.data(), rt.text.size());
+    if (e == hipSuccess) e = upload(k.res_tag, rt.tag.data(), rt.tag.size());
+    if (e == hipSuccess) e = upload(k.res_path, rt.path.data(), rt.path.size());
+    if (e == hipSuccess) e = upload(k.res_tab, rt.tab.data(), rt.tab.size());
+    if (e == hipSuccess) e = upload(k.res_occ, rt.occ.data(), rt.occ.size());
+    if (e == hipSuccess) e = upload(k.res_base, k.h_cov_base.data(), k.h_cov_base.size());
+    if (e == hipSuccess) e = k.res_rbuf.alloc(2 * k.res_rcap);
+    if (e == hipSuccess) e = k.res_cand.alloc(R);
+    if (e == hipSuccess) e = k.res_ncand.alloc(1);
+    if (e == hipSuccess) e = k.res_starts.alloc(slots);
+    if (e == hipSuccess) e = k.res_ends.alloc(slots);
+    if (e == hipSuccess) e = k.res_alt.alloc(4 * slots);
+    if (e == hipSuccess) e = k.res_stats.alloc(kRescueStats);
+    if (e == hipSuccess) e = rescue_zero(k);
+    if (e != hipSuccess) {
+        rescue_release(k);
+        return fail(c, GROOT_E_DEVICE, "mismatch rescue: %s", hipGetErrorString(e));
+    }
+    k.res_text_paths = rt.n_text_paths;
+    k.res_m = max_mismatch;
+    k.res_on = true;
+    return GROOT_OK;
+}
+
+// the run's stats; GROOT_E_DEVICE when a batch's candidates did not fit the 2-bit buffer (a device-resident batch above max_batch_bases)
+static int rescue_fetch_stats(groot_ctx *c, uint64_t (&st)[kRescueStats])
+{
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemcpy(st, c->ct.res_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    if (st[6]) return fail(c, GROOT_E_DEVICE, "mismatch rescue: %llu reads of batches with more than max_batch_bases bases were left out", (unsigned long long)st[6]);
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_export(groot_ctx *c, uint64_t *depth, uint64_t *alt)
+{
+    // (h_cov_base.back() = sum of (path_len + 1): above the number of paths exactly when some path has a base, and then there is something to write)
+    const bool any_base = c && c->ct.h_cov_base.back() > c->ct.h_len.size();
+    if (!c || (any_base && (!depth || !alt))) return GROOT_E_INVALID;
+    if (!c->ct.res_on) return fail(c, GROOT_E_STATE, "mismatch rescue is not enabled (groot_hip_rescue_enable)");
+    uint64_t stats[kRescueStats];
+    if (int rc = rescue_fetch_stats(c, stats)) return rc;
+    const uint64_t slots = c->ct.h_cov_base.back();
+    std::vector<uint64_t> st(slots), en(slots), al(4 * slots);
+    if (slots) {
+        HIP_TRY(c, hipMemcpy(st.data(), c->ct.res_starts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(en.data(), c->ct.res_ends.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(al.data(), c->ct.res_alt.p, 4 * slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    uint64_t at = 0;
+    for (size_t p = 0; p < c->ct.h_len.size(); p++) {
+        const uint64_t b = c->ct.h_cov_base[p], len = c->ct.h_len[p];
+        uint64_t d = 0;
+        for (uint64_t i = 0; i < len; i++, at++) {
+            d += st[b + i] - en[b + i];
+            depth[at] = d;
+            for (uint32_t x = 0; x < 4; x++) alt[4 * at + x] = al[4 * (b + i) + x];
+        }
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_stats(groot_ctx *c, groot_rescue_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kRescueStats] = {};
+    if (c->ct.res_on)
+        if (int rc = rescue_fetch_stats(c, st)) return rc;
+    out->candidates = st[0]; out->rescued = st[1]; out->exact = st[2]; out->placements = st[3]; out->too_short = st[4]; out->non_acgt = st[5];
+    out->text_paths = c->ct.res_on ? c->ct.res_text_paths : 0;
+    out->launches = c->ct.res_launches;
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.res_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, rescue_zero(c->ct));
     return GROOT_OK;
 }
 

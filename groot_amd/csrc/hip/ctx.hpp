@@ -187,6 +187,18 @@ struct Counters {
     DevBuf<uint32_t> asg_gpo;              // graph_path_off (a copy of its own: the position tables above are not needed)
     DevBuf<unsigned long long> asg_stats;  // [kAssignStats]
     uint64_t asg_launches = 0;             // kernels launched for it since open (stays put while it is off)
+    // mismatch rescue (groot_hip_rescue_*, kernels_rescue.hpp): rescue_pack_kernel and rescue_count_kernel behind every batch's order
+    // stage place the reads without a record on the path texts with up to res_m substitutions.  Nothing on the device while off.
+    bool res_on = false;
+    uint32_t res_m = 0, res_text_paths = 0;
+    DevBuf<uint32_t> res_text, res_tag, res_cand, res_ncand;
+    DevBuf<uint4> res_path, res_tab;       // RescueTables (index_tables.hpp)
+    DevBuf<uint2> res_occ;
+    DevBuf<uint64_t> res_base;             // h_cov_base
+    DevBuf<unsigned long long> res_rbuf;   // [2][res_rcap] the batch's candidates at 2 bits per base (tail stream: one batch at a time)
+    uint64_t res_rcap = 0;
+    DevBuf<unsigned long long> res_starts, res_ends, res_alt, res_stats;   // report coverage's layout; alt: four per slot
+    uint64_t res_launches = 0;             // kernels launched for it since open (stays put while it is off)
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

@@ -440,4 +440,14 @@ __host__ __device__ __forceinline__ uint64_t text_hash_step(uint64_t h, uint32_t
 }
 #define GROOT_TEXT_HASH_INIT 0xD6E8FEB86659FD93ULL
 
+// ---- mismatch rescue (kernels_rescue.hpp; the host builds the 16-mer table with the same function: index_tables.hpp) ----
+constexpr uint32_t kRescueAnchor = 16;     // bases of an anchor: one dword at 2 bits per base, the exact key of the table
+constexpr uint32_t kRescueMaxMismatch = 3;
+__host__ __device__ __forceinline__ uint32_t rescue_hash(uint32_t key)
+{
+    uint64_t h = ((uint64_t)key ^ 0x9E3779B97F4A7C15ULL) * 0xff51afd7ed558ccdULL;
+    h ^= h >> 29;
+    return (uint32_t)(h ^ (h >> 32));
+}
+
 } // namespace groot

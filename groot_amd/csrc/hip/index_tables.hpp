@@ -116,6 +116,8 @@ struct PathTables {
     std::vector<uint64_t> tab;         // LeanArgs::path_tab (three words per entry)
     uint32_t n_text_paths = 0;
     size_t n_bases = 0;
+    // per global path (not uploaded; build_rescue_tables reads them): where its text starts (kEmpty: it has none), its bases, the Position of its first node
+    std::vector<uint32_t> path_at, path_bases, path_first;
 };
 // false: the paths' texts are not bit_addressable32: no first pass against path text
 inline bool build_path_tables(const groot_index_view *v, const std::vector<uint32_t> &gnode, PathTables &pt)
@@ -167,6 +169,7 @@ inline bool build_path_tables(const groot_index_view *v, const std::vector<uint3
     }
     pt.n_bases = total;
     if (!bit_addressable32(total)) return false;
+    pt.path_at.assign(v->n_paths, kEmpty); pt.path_bases.assign(v->n_paths, 0); pt.path_first.assign(v->n_paths, 0);
     pt.text.assign(total / 16 + 20, 0);
     pt.tag.assign(total / 16 + 20, 0);
     pt.node.assign((size_t)v->n_nodes * 2, make_uint4(kEmpty, 0, 0, 0));
@@ -177,6 +180,7 @@ inline bool build_path_tables(const groot_index_view *v, const std::vector<uint3
         const auto &L = pl[p];
         const uint32_t n = (uint32_t)L.size(), nbase = (uint32_t)pt.nodes.size(), tbase = (uint32_t)(pt.tab.size() / 3);
         const uint32_t tend = (uint32_t)(at + (L.back().first + nlen(L.back().second) - L.front().first));
+        pt.path_at[p] = (uint32_t)at; pt.path_bases[p] = tend - (uint32_t)at; pt.path_first[p] = L.front().first;
         uint32_t levels = 1;
         while ((2ull << (levels - 1)) <= n) levels++;
         pt.tab.resize(pt.tab.size() + (size_t)3 * levels * n, 0);
@@ -204,6 +208,85 @@ inline bool build_path_tables(const groot_index_view *v, const std::vector<uint3
     }
     if (pt.nodes.empty()) pt.nodes.push_back(0);
     if (pt.tab.empty()) pt.tab.assign(3, 0);
+    return true;
+}
+
+// ---- mismatch rescue (kernels_rescue.hpp): the path texts once more, and an exact table of their 16-mers ----
+// tab: open addressing over the distinct 16-mers of all texts that hold no 'N' (mask = tab.size() - 1, slot = rescue_hash(key) & mask, linear
+// probing): {key = the 16 bases at 2 bits each, first occurrence in occ, occurrences, 0}; occurrences == 0: the slot is free.  The key is the
+// whole 16-mer, so a hit is never a false positive.  occ: {global path, offset of the 16-mer in the text array}, a key's occurrences back to
+// back, ascending by (path, offset).  path: per global path {start of its text in the text array (kEmpty: no text), its bases (those inside path_len),
+// Position of its first node, 0}.
+struct RescueTables {
+    std::vector<uint32_t> text;            // PathTables::text
+    std::vector<uint32_t> tag;             // laid out like it; bit 0 of a base's two: the graph has no A/C/G/T there ('N').  (PathTables::tag cannot
+                                           // say so for a node's first base, where it holds the boundary flags.)
+    std::vector<uint4> path, tab;
+    std::vector<uint2> occ;
+    uint32_t n_text_paths = 0;
+    size_t n_bases = 0, n_kmers = 0;
+};
+// the 16 bases from base i of a 2-bit text as one dword
+inline uint32_t get32(const uint32_t *words, size_t i)
+{
+    const uint64_t two = (uint64_t)words[i >> 4] | ((uint64_t)words[(i >> 4) + 1] << 32);
+    return (uint32_t)(two >> (2 * (i & 15)));
+}
+// false: the paths' texts are not bit_addressable32 (no rescue on such an index)
+inline bool build_rescue_tables(const groot_index_view *v, RescueTables &rt)
+{
+    PathTables pt;
+    if (!build_path_tables(v, build_node_graph(v), pt)) return false;
+    rt.text.swap(pt.text);
+    rt.tag.assign(rt.text.size(), 0);
+    {
+        size_t at = 0, nd = 0;             // pt.nodes lists the nodes of the paths with a text, path after path
+        for (uint32_t p = 0; p < v->n_paths; p++) {
+            if (pt.path_at[p] == kEmpty) continue;
+            for (const size_t end = at + pt.path_bases[p]; at < end; nd++) {
+                const uint32_t n = pt.nodes[nd];
+                for (uint32_t i = v->node_seq_off[n]; i < v->node_seq_off[n + 1]; i++, at++)
+                    if (code_of(v->bases[i]) < 0) put2(rt.tag.data(), at, 1u);
+            }
+        }
+    }
+    rt.n_text_paths = pt.n_text_paths; rt.n_bases = pt.n_bases;
+    rt.path.assign(v->n_paths, make_uint4(kEmpty, 0, 0, 0));
+    // every 16-mer without an 'N' as key << 32 | its number in (path, offset) order; sorted, a key's occurrences are neighbours in that order
+    std::vector<uint64_t> all;
+    std::vector<uint2> where;
+    for (uint32_t p = 0; p < v->n_paths; p++) {
+        if (pt.path_at[p] == kEmpty) continue;
+        const uint32_t at = pt.path_at[p], n = pt.path_bases[p];
+        // (bases past path_len, were a view to claim fewer than its nodes spell, take no placement: the dense tables end at path_len)
+        const uint32_t first = pt.path_first[p], inside = v->path_len[p] > first ? std::min(n, v->path_len[p] - first) : 0u;
+        rt.path[p] = make_uint4(at, inside, first, 0);
+        uint32_t clean = 0;                 // bases since the last 'N'
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t tg = (rt.tag[(at + i) >> 4] >> (2 * ((at + i) & 15))) & 3u;
+            clean = tg ? 0 : clean + 1;
+            if (clean < kRescueAnchor) continue;
+            const uint32_t s = at + i + 1 - kRescueAnchor;
+            all.push_back((uint64_t)get32(rt.text.data(), s) << 32 | where.size());
+            where.push_back(make_uint2(p, s));
+        }
+    }
+    std::sort(all.begin(), all.end());
+    for (size_t i = 0; i < all.size(); i++)
+        if (i == 0 || (all[i] >> 32) != (all[i - 1] >> 32)) rt.n_kmers++;
+    uint32_t cap = 16;
+    while (cap < 2 * (uint64_t)rt.n_kmers) cap <<= 1;
+    rt.tab.assign(cap, make_uint4(0, 0, 0, 0));
+    rt.occ.resize(std::max<size_t>(all.size(), 1), make_uint2(0, 0));
+    for (size_t i = 0; i < all.size();) {
+        size_t j = i;
+        while (j < all.size() && (all[j] >> 32) == (all[i] >> 32)) { rt.occ[j] = where[(uint32_t)all[j]]; j++; }
+        const uint32_t key = (uint32_t)(all[i] >> 32);
+        uint32_t slot = rescue_hash(key) & (cap - 1);
+        while (rt.tab[slot].z) slot = (slot + 1) & (cap - 1);
+        rt.tab[slot] = make_uint4(key, (uint32_t)i, (uint32_t)(j - i), 0);
+        i = j;
+    }
     return true;
 }
 

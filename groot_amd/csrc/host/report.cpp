@@ -406,6 +406,63 @@ extern "C" int groot_host_shared_from_counts(const groot_index_view *ix, const u
     return write_shared(name_ptr.data(), name_len.data(), reported, pairs, out_path, n_lines);
 }
 
+// ---- variants: what the rescued reads say differs from the index (groot_hip_rescue_export) ----------------------------------
+extern "C" int groot_host_variants_write(const groot_index_view *ix, const uint64_t *rescued_depth, const uint64_t *alt, const uint64_t *exact_depth,
+                                         uint64_t min_reads, double min_share, const char *out_path, uint64_t *n_lines)
+{
+    if (!ix || (ix->n_paths && (!rescued_depth || !alt || !exact_depth))) return set_error(GROOT_E_INVALID, "null argument");
+    if (!(min_share >= 0.0 && min_share <= 1.0)) return set_error(GROOT_E_INVALID, "minimum share %g is not in [0, 1]", min_share);
+    // the nodes of every path with a count, by global path
+    std::vector<uint64_t> base(ix->n_paths + 1, 0);
+    for (uint32_t p = 0; p < ix->n_paths; p++) base[p + 1] = base[p] + ix->path_len[p];
+    std::vector<uint8_t> wanted(ix->n_paths, 0);
+    for (uint32_t p = 0; p < ix->n_paths; p++)
+        for (uint64_t i = 4 * base[p]; i < 4 * base[p + 1] && !wanted[p]; i++) wanted[p] = alt[i] != 0;
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> on(ix->n_paths);      // (Position, node)
+    for (uint32_t g = 0; g < ix->n_graphs; g++)
+        for (uint32_t n = ix->graph_node_off[g]; n < ix->graph_node_off[g + 1]; n++)
+            for (uint32_t i = ix->node_np_off[n]; i < ix->node_np_off[n + 1]; i++) {
+                const uint64_t gp = (uint64_t)ix->graph_path_off[g] + ix->np_path[i];
+                if (gp < ix->n_paths && wanted[gp]) on[gp].push_back({ix->np_pos[i], n});
+            }
+    // (a kept placement adds to the depth of every base it adds an alt to: tables that say otherwise are refused before anything is written)
+    for (uint64_t i = 0; i < base[ix->n_paths]; i++)
+        for (uint32_t b = 0; b < 4; b++)
+            if (alt[4 * i + b] > rescued_depth[i] || rescued_depth[i] + exact_depth[i] < rescued_depth[i])
+                return set_error(GROOT_E_INVALID, "base %llu of the tables: %llu alt read(s) at a rescued depth of %llu", (unsigned long long)i,
+                                 (unsigned long long)alt[4 * i + b], (unsigned long long)rescued_depth[i]);
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
+    uint64_t lines = 0;
+    std::string ref;
+    for (uint32_t p = 0; p < ix->n_paths; p++) {
+        if (!wanted[p]) continue;
+        const uint32_t len = ix->path_len[p];
+        ref.assign(len, 'N');                                                      // the path's bases by path coordinate
+        for (const auto &pn : on[p])
+            for (uint32_t j = ix->node_seq_off[pn.second]; j < ix->node_seq_off[pn.second + 1]; j++) {
+                const uint64_t y = (uint64_t)pn.first + (j - ix->node_seq_off[pn.second]);
+                if (y < len) ref[y] = (char)ix->bases[j];
+            }
+        const char *nm = ix->path_names + ix->path_name_off[p];
+        size_t nl = ix->path_name_off[p + 1] - ix->path_name_off[p];
+        if (nl && nm[0] == '*') { nm++; nl--; }                                    // as the report prints it
+        for (uint32_t y = 0; y < len; y++)
+            for (uint32_t b = 0; b < 4; b++) {
+                const uint64_t n = alt[4 * (base[p] + y) + b], rd = rescued_depth[base[p] + y], ed = exact_depth[base[p] + y];
+                if (!n || n < min_reads) continue;
+                const double share = (double)n / (double)(rd + ed);
+                if (!(share >= min_share)) continue;
+                fprintf(out, "%.*s\t%u\t%c\t%c\t%llu\t%llu\t%llu\t%.4f\n", (int)nl, nm, y + 1, ref[y], "ACGT"[b], (unsigned long long)n, (unsigned long long)rd,
+                        (unsigned long long)ed, share);
+                lines++;
+            }
+    }
+    if (out_path) fclose(out); else fflush(out);
+    if (n_lines) *n_lines = lines;
+    return GROOT_OK;
+}
+
 // ---- abundance: EM over equivalence classes ---------------------------------------------------------------------------------
 // src/em/em.go NewEM / Run / Return (lines 29-158), restated in double precision without FMA contraction (the library is built
 // without -march), over ECs in canonical order: the reference iterates a Go map, so its sums are not reproducible.

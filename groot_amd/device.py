@@ -546,6 +546,30 @@ class Aligner:
         self._check(lib().groot_hip_pairs_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("joined", "split", "single"), (x.value for x in v)))
 
+    # ---- mismatch rescue of unaligned reads (groot_hip_rescue_*) ------------------------------------
+    def rescue_enable(self, max_mismatch=2):
+        """from now on, lay every read without a record on the path texts with up to max_mismatch (1..3) substitutions and pile up
+        where it lies and what differs (include/groot_hip.h, "mismatch rescue"); 0 switches it off.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_rescue_enable(self._h, C.byref(self.index.view), C.c_uint32(max_mismatch)))
+
+    def rescue(self):
+        """(depth[sum of path_len], alt[sum of path_len, 4]) as uint64 over every batch since enable / reset: rescued depth and the
+        A, C, G, T counts of the mismatching bases, per path base.  Waits for everything in flight."""
+        n = int(self.index.arrays["path_len"].astype(np.uint64).sum())
+        depth, alt = np.zeros(n, dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        self._check(lib().groot_hip_rescue_export(self._h, _ffi.as_ptr(depth, C.c_uint64), _ffi.as_ptr(alt, C.c_uint64)))
+        return depth, alt
+
+    def rescue_stats(self):
+        """groot_hip_rescue_stats: {"candidates", "rescued", "exact", "placements", "too_short", "non_acgt", "text_paths", "launches"};
+        zeros while off, but for launches"""
+        v = (C.c_uint64 * 8)()
+        self._check(lib().groot_hip_rescue_stats(self._h, v))
+        return dict(zip(("candidates", "rescued", "exact", "placements", "too_short", "non_acgt", "text_paths", "launches"), (int(x) for x in v)))
+
+    def rescue_reset(self):
+        self._check(lib().groot_hip_rescue_reset(self._h))
+
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):
         seq = np.ascontiguousarray(seq_concat, dtype=np.uint8)

@@ -402,6 +402,21 @@ def report(bam_path, cov_cutoff=0.97, low_cov=False, out_path=None):
     return [(r[0], int(r[1]), int(r[2]), r[3]) for r in rows]
 
 
+def variants_write(index, rescued_depth, alt, exact_depth, out_path, min_reads=2, min_share=0.1):
+    """the variants file (groot_host_variants_write) from device.Aligner.rescue() -- summed over the ctxs -- and the depth of
+    device.Aligner.coverage(); returns the lines written"""
+    n_bases = int(index.arrays["path_len"].astype(np.uint64).sum())
+    rd = np.ascontiguousarray(rescued_depth, dtype=np.uint64)
+    al = np.ascontiguousarray(alt, dtype=np.uint64)
+    ed = np.ascontiguousarray(exact_depth, dtype=np.uint64)
+    if rd.shape != (n_bases,) or al.size != 4 * n_bases or ed.shape != (n_bases,):
+        raise ValueError("rescued depth / alt / exact depth do not match the index")
+    n = C.c_uint64(0)
+    _check(lib().groot_host_variants_write(C.byref(index.view), _ffi.as_ptr(rd, C.c_uint64), _ffi.as_ptr(al, C.c_uint64), _ffi.as_ptr(ed, C.c_uint64),
+                                           C.c_uint64(min_reads), C.c_double(min_share), os.fsencode(out_path), C.byref(n)))
+    return n.value
+
+
 def report_coverage(index, records, depth, cov_cutoff=0.97, low_cov=False, out_path=None):
     """the report of `report` from counts instead of a BAM (groot_host_report_coverage): records[n_paths] and depth[sum of
     path_len] as uint64, e.g. device.Aligner.coverage(); same rows as `report` on the BAM whose records they count"""

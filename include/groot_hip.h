@@ -457,6 +457,53 @@ int groot_hip_pairs_enable(groot_ctx *ctx, int on);
  * Waits for everything in flight.  GROOT_E_STATE when pairing is off. */
 int groot_hip_pairs_stats(groot_ctx *ctx, uint64_t *joined, uint64_t *split, uint64_t *single);
 
+/* ---- mismatch rescue of unaligned reads ---------------------------------------------------------------------------------
+ * The aligner is exact-match (AlignRead): a read with one sequencing error, or across the one SNP by which a sample's allele differs
+ * from every indexed one, leaves no record, so no counter above sees it.  With rescue on, two kernels behind every batch's order stage
+ * (kernels_rescue.hpp) lay the reads WITHOUT a record ungapped on the paths' linear texts with up to M substitutions and pile up where
+ * they lie and what differs.  Records, BAM, weights and every other counter stay what they are.  The definition, all of it integers:
+ *
+ *   M = max mismatches, 1 <= M <= 3.   A = 16 (anchor length in bases).
+ *   Text of path p: the concatenation of its nodes' sequences in Position order, for the paths build_path_tables gives a text
+ *   (non-empty nodes, no gap or overlap, joined by OutEdges); path coordinate x = Position of the path's first node + offset in the text.
+ *   A read r of a batch is a CANDIDATE when: the batch pass is counted (the kCovSkipFlags rule of the other counters), r has NO traversal
+ *   record, every base of r is A/C/G/T (nothing of it on the exception list), and len(r) >= A * (M + 1).
+ *   A PLACEMENT of r is (p, strand, x): the oriented read (r, or its reverse complement for strand = 1) laid ungapped on
+ *   text_p[x .. x + len), entirely inside the text (0 <= x, x + len <= path_len(p)), with no 'N' of the path in the window, and
+ *   Hamming distance d <= M.   (len >= A(M+1) leaves at least one of the disjoint blocks [0,16), [16,32), .. of the oriented read error-free, so
+ *   every placement holds an exact 16-mer anchor: the anchor search loses none.)
+ *   d*(r) = the smallest d over r's placements.  r is RESCUED when it has a placement; its KEPT placements are all those with d = d*
+ *   (every path, both strands, every x: as the aligner keeps every multimapper).  A placement is counted once, however many blocks anchor it.
+ *   Per kept placement:   rdepth[p][x .. x + len - 1] += 1;   for every mismatching base at path coordinate y:  alt[p][y][b] += 1, b = the
+ *   base the oriented read has there (path strand: a strand-1 read contributes the complement of what the FASTQ says).
+ *   Stats: candidates, rescued, rescued with d* = 0, kept placements, reads left out as too short / non-ACGT.
+ *
+ * Read closely: 'N' stands for any byte of the graph other than A, C, G, T; a read without a record that is both non-ACGT and too short
+ * counts as non-ACGT; b is indexed A, C, G, T = 0..3.  The tables depend on the reads and the index alone: not on batch size, pipeline
+ * depth, first-pass variant, results_on_device, or how the reads are spread over ctxs (the merge of several ctxs is a sum).  A batch
+ * is counted once, by the rule of report coverage.  With pairing on, mates are rescued one by one.  Independent of coverage, shared
+ * reads, equivalence classes and assigned coverage; refused with assignment, whichever is enabled second (GROOT_E_UNSUPPORTED):
+ * assignment rewrites the records that tell which reads are unaligned.  Off by default: then no allocation, launch or sync. */
+typedef struct groot_rescue_stats {
+    uint64_t candidates, rescued, exact /* rescued with d* = 0 */, placements /* kept */, too_short, non_acgt;
+    uint64_t text_paths; /* paths with a text (0 while off) */
+    uint64_t launches;   /* kernels launched for rescue since open, whether it is on now or not */
+} groot_rescue_stats;
+/* max_mismatch 1..3: on (0: off, everything freed; above 3: GROOT_E_INVALID).  The first time it comes on, the path texts and an exact
+ * table of their 16-mers are built from `idx` on the host and uploaded -- `idx` must be the view the ctx was opened with (GROOT_E_INVALID);
+ * it is only read during the call (no call retains a caller pointer), and may be NULL to switch off or to change M.  Counters start at
+ * zero; another M while on zeroes them.  Device memory: 48 bytes per path base, the texts and the table (about 20 bytes per path base),
+ * max_batch_bases / 2 + 20 max_batch_reads bytes of work space.  Only while nothing is in flight (GROOT_E_STATE).  GROOT_E_UNSUPPORTED
+ * when the texts are beyond 32-bit bit offsets. */
+int groot_hip_rescue_enable(groot_ctx *ctx, const groot_index_view *idx, uint32_t max_mismatch);
+/* depth[sum of path_len] = rdepth, alt[4 * sum of path_len] with path p at sum_{q<p} path_len[q], global path order; paths without a
+ * text stay zero.  Waits for everything in flight (redoing what needs a redo).  GROOT_E_STATE when rescue is off. */
+int groot_hip_rescue_export(groot_ctx *ctx, uint64_t *depth, uint64_t *alt);
+/* Since enable / reset, counted once exactly as the tables are; zeros while off, but for launches.  Waits for everything in flight. */
+int groot_hip_rescue_stats(groot_ctx *ctx, groot_rescue_stats *out);
+/* Zeroes tables and stats (after waiting for everything in flight).  No-op when off. */
+int groot_hip_rescue_reset(groot_ctx *ctx);
+
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
  * the device, bit for bit in boot_count, alpha and iterations.  Quoted from there: draw j (0 <= j < n_draws; n_draws = 0 means N, the sum

@@ -292,6 +292,17 @@ int groot_host_shared_from_counts(const groot_index_view *idx, const uint64_t *r
 int groot_host_report_shared(const char *bam_path, double cov_cutoff, int low_cov, const char *report_out, const char *shared_out,
                              uint64_t *n_reported, uint64_t *n_lines);
 
+/* Variants (mismatch rescue, defined at groot_hip_rescue_enable in groot_hip.h): what the reads the exact aligner left unaligned say
+ * differs from the indexed alleles.  rescued_depth[sum of path_len] and alt[4 * sum of path_len] (A, C, G, T per base) are the summed
+ * groot_hip_rescue_export of every ctx, exact_depth the depth of groot_hip_coverage_export, path p at sum_{q<p} path_len[q].  One line
+ *     name \t pos (1-based) \t ref \t alt \t alt_reads \t rescued_depth \t exact_depth \t share
+ * per (path, position, alt base) with alt_reads >= max(min_reads, 1) and share = alt_reads / (rescued_depth + exact_depth) >= min_share
+ * (one division in double, printed %.4f), ascending by global path, position and A, C, G, T; the name as the report prints it (the '*'
+ * stripped), ref the path's base there.  out_path NULL = stdout; *n_lines = lines written.  GROOT_E_INVALID for an alt count above
+ * the rescued depth of its base (no table of the device has one: a kept placement adds to the depth wherever it adds an alt). */
+int groot_host_variants_write(const groot_index_view *idx, const uint64_t *rescued_depth, const uint64_t *alt, const uint64_t *exact_depth,
+                              uint64_t min_reads, double min_share, const char *out_path, uint64_t *n_lines);
+
 /* ---- abundance by EM over equivalence classes ----------------------------------------------------------------------
  * ECs as defined at groot_hip_ec_enable in groot_hip.h (distinct non-empty S(r), ascending path IDs, in CSR form: EC i is
  * ids[off[i] .. off[i+1]) with count[i] reads).  groot_host_em restates src/em/em.go NewEM / Run / Return (lines 29-158) in double
