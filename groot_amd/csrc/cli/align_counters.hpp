@@ -1,4 +1,4 @@
-// align: what the contexts count on the device beside the records (--report, --sharedReads, --abundance, --calls, --paired, --assignFrom, --variants),
+// align: what the contexts count on the device beside the records (--report, --sharedReads, --abundance, --calls, --paired, --assignFrom, --variants, --indels),
 // added up on the host.  A ctx is harvested before it closes (a reopen in the middle of the stream) and once at the end of the stream.
 #pragma once
 #include "align_plan.hpp"
@@ -21,6 +21,9 @@ struct Harvested {                           // the sums over every harvest so f
     groot_assign_stats assign{};                             // --assignFrom
     std::vector<uint64_t> res_depth, res_alt;                // --variants: rescued depth per base, A / C / G / T counts per base (groot_hip_rescue_*)
     groot_rescue_stats rescue{};
+    std::vector<uint64_t> gap_depth;                         // --indels: gap depth per base, the events of every ctx merged by key (groot_hip_gap_*)
+    std::map<std::array<uint32_t, 5>, uint64_t> gap_events;  // (path, pos, type, len, seq) -> reads: ascending as the export is
+    groot_gap_stats gap{};
 };
 
 class RunCounters {
@@ -31,8 +34,9 @@ public:
         for (uint32_t p = 0; p < v.n_paths; p++) cov_slots_ += v.path_len[p];
         h_.cov_records.resize(plan.coverage ? v.n_paths : 0);
         h_.cov_depth.resize(plan.coverage ? cov_slots_ : 0);
-        h_.res_depth.resize(plan.variants ? cov_slots_ : 0);
-        h_.res_alt.resize(plan.variants ? 4 * cov_slots_ : 0);
+        h_.res_depth.resize(plan.rescue ? cov_slots_ : 0);
+        h_.res_alt.resize(plan.rescue ? 4 * cov_slots_ : 0);
+        h_.gap_depth.resize(plan.indels ? cov_slots_ : 0);
         if (!plan.assign) return;
         uint64_t named = 0;
         assign_alpha_.resize(v.n_paths);
@@ -49,8 +53,10 @@ public:
             if (int rc = groot_hip_pairs_enable(ctx, on)) return rc;
         if (plan_.coverage)
             if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
-        if (plan_.variants)
+        if (plan_.rescue)
             if (int rc = groot_hip_rescue_enable(ctx, &v_, on ? (uint32_t)a_.rescue : 0u)) return rc;
+        if (plan_.indels && on)     // (off: gapped rescue goes with rescue)
+            if (int rc = groot_hip_gap_enable(ctx, (uint32_t)a_.rescue_gap, (uint64_t)a_.gap_event_slots)) return rc;
         if (plan_.shared)
             if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
         if (plan_.calls && on)
@@ -58,7 +64,7 @@ public:
         return plan_.abundance ? groot_hip_ec_enable(ctx, on) : 0;     // (off: assigned coverage goes with it)
     }
 
-    // assign stats, pair stats, acov-or-EC export, rescue, coverage, shared pairs: each added under the lock (the mappers harvest side by side)
+    // assign stats, pair stats, acov-or-EC export, gapped rescue, rescue, coverage, shared pairs: each added under the lock (the mappers harvest side by side)
     int harvest(groot_ctx *ctx)
     {
         if (plan_.assign) {
@@ -97,7 +103,21 @@ public:
             std::lock_guard<std::mutex> lk(mu_);
             append_ecs(off.data(), ids.data(), cnt.data(), ne, ni);
         }
-        if (plan_.variants) {
+        if (plan_.indels) {         // (a table that dropped events fails here, with the reason: no indels file is written)
+            groot_gap_stats st{};
+            uint64_t n = 0;
+            if (int rc = groot_hip_gap_stats(ctx, &st)) return rc;
+            std::vector<uint64_t> d(cov_slots_);
+            std::vector<groot_gap_event> ev(st.events);
+            if (int rc = groot_hip_gap_export(ctx, d.data(), ev.data(), ev.size(), &n)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            groot_gap_stats &t = h_.gap;
+            t.candidates += st.candidates; t.rescued += st.rescued; t.placements += st.placements; t.del_placements += st.del_placements;
+            t.ins_placements += st.ins_placements; t.too_short += st.too_short; t.launches += st.launches; t.event_slots = st.event_slots;
+            for (size_t i = 0; i < d.size(); i++) h_.gap_depth[i] += d[i];
+            for (uint64_t i = 0; i < n; i++) h_.gap_events[{ev[i].path, ev[i].pos, ev[i].type, ev[i].len, ev[i].seq}] += ev[i].reads;
+        }
+        if (plan_.rescue) {
             groot_rescue_stats st{};
             std::vector<uint64_t> d(cov_slots_), al(4 * cov_slots_);
             if (int rc = groot_hip_rescue_stats(ctx, &st)) return rc;

@@ -286,4 +286,25 @@ void write_variants(const Args &a, const groot_index_view &v, const Harvested &h
          (unsigned long long)r.too_short, (unsigned long long)r.non_acgt, (unsigned long long)n, a.variants_out.c_str(), a.variant_min_reads, a.variant_min_share);
 }
 
+// --indels: the merged events beside the three depths, and the run's stats in the log
+void write_indels(const Args &a, const groot_index_view &v, const Harvested &h)
+{
+    std::vector<groot_gap_event> ev;
+    ev.reserve(h.gap_events.size());
+    for (const auto &kv : h.gap_events) {
+        groot_gap_event e{};
+        e.path = kv.first[0]; e.pos = kv.first[1]; e.type = (uint8_t)kv.first[2]; e.len = (uint8_t)kv.first[3]; e.seq = (uint16_t)kv.first[4]; e.reads = kv.second;
+        ev.push_back(e);
+    }
+    uint64_t n = 0;
+    if (groot_host_indels_write(&v, ev.data(), ev.size(), h.gap_depth.data(), h.res_depth.data(), h.cov_depth.data(), (uint64_t)a.variant_min_reads, a.variant_min_share,
+                                a.indels_out.c_str(), &n))
+        die("%s", groot_host_last_error());
+    const groot_gap_stats &g = h.gap;
+    logf("\tindels: %llu read(s) left by up to %ld substitution(s) tried with one gap of up to %ld base(s): %llu rescued in %llu placement(s) (%llu DEL, %llu INS), %zu distinct "
+         "event(s); left out: %llu too short; %llu line(s) written to %s (at least %lld read(s), share %g)",
+         (unsigned long long)g.candidates, a.rescue, a.rescue_gap, (unsigned long long)g.rescued, (unsigned long long)g.placements, (unsigned long long)g.del_placements,
+         (unsigned long long)g.ins_placements, ev.size(), (unsigned long long)g.too_short, (unsigned long long)n, a.indels_out.c_str(), a.variant_min_reads, a.variant_min_share);
+}
+
 } // namespace

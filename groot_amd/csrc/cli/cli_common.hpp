@@ -2,6 +2,7 @@
 // their kernels_*.hpp.  Here: what every subcommand shares -- the log (Go's log.LstdFlags), die, the parsed flags, small file helpers.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
@@ -71,6 +72,10 @@ struct Args {
     long long variant_min_reads = 2;       // --variantMinReads N
     double variant_min_share = 0.1;        // --variantMinShare S
     bool rescue_given = false, variant_min_given = false;
+    std::string indels_out;                // --indels: the gaps that the reads neither aligned nor rescued show, placed with one gap of up to --rescueGap bases
+    long rescue_gap = 3;                   // --rescueGap G (1..8)
+    long long gap_event_slots = 0;         // --gapEventSlots N (a power of two; 0: the library's default)
+    bool rescue_gap_given = false, gap_slots_given = false;
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
     bool gpu_given = false, write_gob = false;

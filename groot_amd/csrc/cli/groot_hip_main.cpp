@@ -38,6 +38,7 @@ void usage()
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
+            "                  [--indels i.tsv [--rescueGap 3] [--gapEventSlots 4194304] [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
@@ -62,6 +63,10 @@ void usage()
             "                   GPU; `name pos ref alt alt_reads rescued_depth exact_depth share` for every base where at least --variantMinReads rescued reads\n"
             "                   show another base and they are at least --variantMinShare of the depth there.  The BAM and every other file stay as they are.\n"
             "                   Not with --assignFrom or --noAlign;\n"
+            "                   --indels: the reads that stay unplaced even so are laid on the ARGs with ONE gap of up to --rescueGap (1..8) bases and up to --rescue\n"
+            "                   substitutions, on the GPU; `name pos type len seq reads gap_depth rescued_depth exact_depth share` for every deletion or insertion\n"
+            "                   that at least --variantMinReads of them show and that is at least --variantMinShare of the depth at pos, the base before the gap.\n"
+            "                   With or without --variants; --gapEventSlots: the slots of the event table on the GPU, a power of two (a run that fills it fails);\n"
             "                   --paired: the -f files are R1,R2[,R1b,R2b...], first with second, third with fourth; --interleaved: the mates alternate in\n"
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
@@ -130,6 +135,14 @@ Args parse(int argc, char **argv)
             if (f == "--rescue") { a.rescue = strtol(t.c_str(), &end, 10); a.rescue_given = true; }
             else if (f == "--variantMinReads") { a.variant_min_reads = strtoll(t.c_str(), &end, 10); a.variant_min_given = true; }
             else { a.variant_min_share = strtod(t.c_str(), &end); a.variant_min_given = true; }
+            if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
+        }
+        else if (a.cmd == "align" && f == "--indels") a.indels_out = v();
+        else if (a.cmd == "align" && (f == "--rescueGap" || f == "--gapEventSlots")) {
+            const std::string t = v();
+            char *end = nullptr;
+            if (f == "--rescueGap") { a.rescue_gap = strtol(t.c_str(), &end, 10); a.rescue_gap_given = true; }
+            else { a.gap_event_slots = strtoll(t.c_str(), &end, 10); a.gap_slots_given = true; }
             if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
         }
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
@@ -319,6 +332,7 @@ int run_align(const Args &a)
     if (plan.calls) write_calls(a, plan, v, h, first_device, boot);
     if (plan.report) write_report(a, plan, v, h);
     if (plan.variants) write_variants(a, v, h);
+    if (plan.indels) write_indels(a, v, h);
     t.stream_s = seconds_since(t_stream);
     auto t_post = std::chrono::steady_clock::now();
     if (s.mapped_reads == 0) logf("no reads could be mapped to the reference graphs");           // sketch.go:328-334

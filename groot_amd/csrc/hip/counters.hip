@@ -1,7 +1,7 @@
 // counters.hip -- the counters that run behind every batch's order stage, and their C ABI (include/groot_hip.h): report coverage
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
-// draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp).  One of the six translation units of
+// draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,7 @@
 #include "kernels_ec.hpp"
 #include "index_tables.hpp"
 #include "kernels_rare.hpp"
+#include "kernels_gap.hpp"
 #include "kernels_rescue.hpp"
 #include "kernels_shared.hpp"
 
@@ -403,7 +404,18 @@ int counters_launch(groot_ctx *c, Slot *s)
         ra.tab_mask = (uint32_t)k.res_tab.n - 1u; ra.n_reads = s->n_reads; ra.max_mismatch = k.res_m;
         HIP_TRY(c, hipMemsetAsync(k.res_ncand.p, 0, sizeof(uint32_t), c->tstream));
         hipLaunchKernelGGL(rescue_pack_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
-        hipLaunchKernelGGL(rescue_count_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+        if (!k.gap_on) hipLaunchKernelGGL(rescue_count_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+        else {
+            GapArgs ga{};
+            ra.gcand = k.gap_cand.p; ra.n_gcand = k.gap_ncand.p; ra.gstats = k.gap_stats.p;
+            ga.r = ra; ga.gcand = k.gap_cand.p; ga.n_gcand = k.gap_ncand.p;
+            ga.starts = k.gap_starts.p; ga.ends = k.gap_ends.p; ga.ev_key = k.gap_key.p; ga.ev_cnt = k.gap_cnt.p; ga.stats = k.gap_stats.p;
+            ga.ev_mask = k.gap_slots - 1; ga.max_gap = k.gap_g;
+            HIP_TRY(c, hipMemsetAsync(k.gap_ncand.p, 0, sizeof(uint32_t), c->tstream));
+            hipLaunchKernelGGL(rescue_count_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+            hipLaunchKernelGGL(rescue_gap_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
+            k.gap_launches++;
+        }
         HIP_TRY(c, hipGetLastError());
         k.res_launches += 2;
     }
@@ -1012,8 +1024,28 @@ int groot_hip_pairs_stats(groot_ctx *c, uint64_t *joined, uint64_t *split, uint6
 }
 
 // ---- mismatch rescue (kernels_rescue.hpp) --------------------------------------------------------------------------------
+static void gap_release(Counters &k)
+{
+    for (auto *b : {&k.gap_cand, &k.gap_ncand}) b->release();
+    for (auto *b : {&k.gap_starts, &k.gap_ends, &k.gap_key, &k.gap_cnt, &k.gap_stats}) b->release();
+    k.gap_on = false; k.gap_g = 0; k.gap_slots = 0;
+}
+
+static hipError_t gap_zero(Counters &k)
+{
+    if (!k.gap_on) return hipSuccess;
+    const uint64_t slots = std::max<uint64_t>(k.h_cov_base.back(), 1);
+    hipError_t e = hipMemset(k.gap_starts.p, 0, slots * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(k.gap_ends.p, 0, slots * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(k.gap_key.p, 0, k.gap_slots * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(k.gap_cnt.p, 0, k.gap_slots * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(k.gap_stats.p, 0, kGapStats * sizeof(unsigned long long));
+    return e;
+}
+
 static void rescue_release(Counters &k)
 {
+    gap_release(k);                        // (gapped rescue looks at what rescue leaves: off with it)
     for (auto *b : {&k.res_text, &k.res_tag, &k.res_cand, &k.res_ncand}) b->release();
     for (auto *b : {&k.res_rbuf, &k.res_starts, &k.res_ends, &k.res_alt, &k.res_stats}) b->release();
     k.res_path.release(); k.res_tab.release(); k.res_occ.release(); k.res_base.release();
@@ -1027,6 +1059,7 @@ static hipError_t rescue_zero(Counters &k)
     if (e == hipSuccess) e = hipMemset(k.res_ends.p, 0, slots * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(k.res_alt.p, 0, 4 * slots * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(k.res_stats.p, 0, kRescueStats * sizeof(unsigned long long));
+    if (e == hipSuccess) e = gap_zero(k);  // (derived from the same reads)
     return e;
 }
 
@@ -1137,6 +1170,124 @@ int groot_hip_rescue_reset(groot_ctx *c)
     if (!c->ct.res_on) return GROOT_OK;
     if (int rc = drain(c)) return rc;
     HIP_TRY(c, rescue_zero(c->ct));
+    return GROOT_OK;
+}
+
+// ---- gapped rescue (kernels_gap.hpp) ---------------------------------------------------------------------------------------
+int groot_hip_gap_enable(groot_ctx *c, uint32_t max_gap, uint64_t event_slots)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "gapped rescue can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!max_gap) {
+        gap_release(k);
+        return GROOT_OK;
+    }
+    if (!k.res_on) return fail(c, GROOT_E_STATE, "gapped rescue looks at the reads mismatch rescue leaves, and that is off (groot_hip_rescue_enable)");
+    if (max_gap > kGapMax) return fail(c, GROOT_E_INVALID, "gapped rescue: a gap of %u bases, at most %u are supported", max_gap, kGapMax);
+    if (event_slots & (event_slots - 1)) return fail(c, GROOT_E_INVALID, "gapped rescue: event_slots %llu is not a power of two", (unsigned long long)event_slots);
+    if (!event_slots) event_slots = 1ull << 22;
+    if (k.gap_on && event_slots == k.gap_slots) {      // another G: the buffers stay, the counts start over
+        if (max_gap != k.gap_g) {
+            hipError_t e = gap_zero(k);
+            if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "gapped rescue: %s", hipGetErrorString(e));
+            k.gap_g = max_gap;
+        }
+        return GROOT_OK;
+    }
+    gap_release(k);
+    const uint64_t slots = k.h_cov_base.back();
+    hipError_t e = k.gap_cand.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
+    if (e == hipSuccess) e = k.gap_ncand.alloc(1);
+    if (e == hipSuccess) e = k.gap_starts.alloc(slots);
+    if (e == hipSuccess) e = k.gap_ends.alloc(slots);
+    if (e == hipSuccess) e = k.gap_key.alloc(event_slots);
+    if (e == hipSuccess) e = k.gap_cnt.alloc(event_slots);
+    if (e == hipSuccess) e = k.gap_stats.alloc(kGapStats);
+    if (e == hipSuccess) {
+        k.gap_on = true; k.gap_g = max_gap; k.gap_slots = event_slots;
+        e = gap_zero(k);
+    }
+    if (e != hipSuccess) {
+        gap_release(k);
+        return fail(c, GROOT_E_DEVICE, "gapped rescue: %s", hipGetErrorString(e));
+    }
+    return GROOT_OK;
+}
+
+int groot_hip_gap_export(groot_ctx *c, uint64_t *gdepth, groot_gap_event *events, uint64_t cap, uint64_t *n_events)
+{
+    const bool any_base = c && c->ct.h_cov_base.back() > c->ct.h_len.size();
+    if (!c || !n_events || (any_base && !gdepth) || (cap && !events)) return GROOT_E_INVALID;
+    *n_events = 0;
+    Counters &k = c->ct;
+    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gapped rescue is not enabled (groot_hip_gap_enable)");
+    uint64_t rst[kRescueStats], st[kGapStats];
+    if (int rc = rescue_fetch_stats(c, rst)) return rc;
+    HIP_TRY(c, hipMemcpy(st, k.gap_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    *n_events = st[6];
+    if (st[7])
+        return fail(c, GROOT_E_NOSPACE, "gapped rescue: %llu events found no room in a table of event_slots = %llu: give groot_hip_gap_enable a larger one",
+                    (unsigned long long)st[7], (unsigned long long)k.gap_slots);
+    if (cap < st[6]) return fail(c, GROOT_E_INVALID, "gapped rescue: %llu distinct events, room for %llu", (unsigned long long)st[6], (unsigned long long)cap);
+    const uint64_t slots = k.h_cov_base.back();
+    std::vector<uint64_t> s0(slots), s1(slots), key(k.gap_slots), cnt(k.gap_slots);
+    if (slots) {
+        HIP_TRY(c, hipMemcpy(s0.data(), k.gap_starts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(s1.data(), k.gap_ends.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(c, hipMemcpy(key.data(), k.gap_key.p, k.gap_slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(cnt.data(), k.gap_cnt.p, k.gap_slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t at = 0;
+    for (size_t p = 0; p < k.h_len.size(); p++) {
+        const uint64_t b = k.h_cov_base[p], len = k.h_len[p];
+        uint64_t d = 0;
+        for (uint64_t i = 0; i < len; i++, at++) {
+            d += s0[b + i] - s1[b + i];
+            gdepth[at] = d;
+        }
+    }
+    uint64_t n = 0;
+    for (uint64_t i = 0; i < k.gap_slots; i++) {
+        if (!key[i]) continue;
+        if (n == st[6]) return fail(c, GROOT_E_DEVICE, "gapped rescue: more keys in the table than the %llu claimed", (unsigned long long)st[6]);
+        const uint64_t slot = key[i] & ((1ull << 40) - 1);
+        const size_t p = (size_t)(std::upper_bound(k.h_cov_base.begin(), k.h_cov_base.end(), slot) - k.h_cov_base.begin()) - 1;
+        groot_gap_event &e = events[n++];
+        e.path = (uint32_t)p; e.pos = (uint32_t)(slot - k.h_cov_base[p]);
+        e.type = (uint8_t)((key[i] >> 40) & 1u); e.len = (uint8_t)(((key[i] >> 41) & 7u) + 1u); e.seq = (uint16_t)(key[i] >> 44);
+        e.reserved = 0; e.reads = cnt[i];
+    }
+    if (n != st[6]) return fail(c, GROOT_E_DEVICE, "gapped rescue: %llu keys in the table, %llu claimed", (unsigned long long)n, (unsigned long long)st[6]);
+    std::sort(events, events + n, [](const groot_gap_event &a, const groot_gap_event &b) {      // the table's order is not deterministic, this one is
+        return std::make_tuple(a.path, a.pos, a.type, a.len, a.seq) < std::make_tuple(b.path, b.pos, b.type, b.len, b.seq);
+    });
+    return GROOT_OK;
+}
+
+int groot_hip_gap_stats(groot_ctx *c, groot_gap_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kGapStats] = {};
+    if (c->ct.gap_on) {
+        uint64_t rst[kRescueStats];
+        if (int rc = rescue_fetch_stats(c, rst)) return rc;
+        HIP_TRY(c, hipMemcpy(st, c->ct.gap_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    }
+    out->candidates = st[0]; out->rescued = st[1]; out->placements = st[2]; out->del_placements = st[3]; out->ins_placements = st[4];
+    out->too_short = st[5]; out->events = st[6]; out->dropped = st[7];
+    out->event_slots = c->ct.gap_on ? c->ct.gap_slots : 0;
+    out->launches = c->ct.gap_launches;
+    return GROOT_OK;
+}
+
+int groot_hip_gap_reset(groot_ctx *c)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!c->ct.gap_on) return GROOT_OK;
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, gap_zero(c->ct));
     return GROOT_OK;
 }
 

@@ -199,6 +199,14 @@ struct Counters {
     uint64_t res_rcap = 0;
     DevBuf<unsigned long long> res_starts, res_ends, res_alt, res_stats;   // report coverage's layout; alt: four per slot
     uint64_t res_launches = 0;             // kernels launched for it since open (stays put while it is off)
+    // gapped rescue (groot_hip_gap_*, kernels_gap.hpp): needs mismatch rescue on.  rescue_count_kernel<true> hands on the candidates it left
+    // unplaced, rescue_gap_kernel behind it places them with one gap of up to gap_g bases.  Nothing on the device while off.
+    bool gap_on = false;
+    uint32_t gap_g = 0;
+    uint64_t gap_slots = 0;                // slots of the event table: a power of two, fixed at enable
+    DevBuf<uint32_t> gap_cand, gap_ncand;
+    DevBuf<unsigned long long> gap_starts, gap_ends, gap_key, gap_cnt, gap_stats;   // report coverage's layout; the event table
+    uint64_t gap_launches = 0;             // rescue_gap_kernel launches since open (stays put while it is off)
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

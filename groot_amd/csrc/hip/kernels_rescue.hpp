@@ -14,6 +14,8 @@
 //                      so every placement counts once without a sort.  Sweep 1 keeps the smallest distance d*, sweep 2 adds the placements
 //                      at d* to the dense tables with plain atomicAdd: starts / ends in report coverage's layout (path_len + 1 slots per
 //                      path), alt as four counters (A, C, G, T) per slot.
+//                      rescue_count_kernel<true> (gapped rescue on: kernels_gap.hpp) also hands on the candidates it leaves unplaced;
+//                      <false> is the kernel without that, and the only one launched while gapped rescue is off.
 // Integer sums only: the tables do not depend on the order of the candidates, of the wavefronts or of the batches.
 #pragma once
 
@@ -42,6 +44,9 @@ struct RescueArgs {
     const uint64_t *slot_base;     // [n_paths] first slot of global path p: sum_{q<p} (path_len[q] + 1)
     unsigned long long *starts, *ends, *alt, *stats;
     uint32_t tab_mask, n_reads, max_mismatch;
+    // gapped rescue (kernels_gap.hpp; rescue_count_kernel<true> only): the candidates left unplaced that are long enough for a gap
+    uint32_t *gcand, *n_gcand;     // [n_reads] the gap candidates handed on, their number
+    unsigned long long *gstats;    // GapArgs::stats
 };
 
 // the workgroup's sums of up to kRescueStats per-thread counts, one atomic each per wavefront
@@ -142,55 +147,95 @@ __device__ __forceinline__ uint32_t rescue_distance(const RescueArgs &a, const u
     return d;
 }
 
-__global__ __launch_bounds__(kBlock) void rescue_count_kernel(RescueArgs a)
+// the placements of candidate r: sweep 1 keeps the smallest distance, sweep 2 adds the placements at it to the tables.  -> d*, M + 1 when
+// there is no placement; hit: one of its blocks is in the table at all
+__device__ __forceinline__ uint32_t rescue_place(const RescueArgs &a, uint32_t r, uint32_t &len, uint32_t (&st)[4], bool &hit)
 {
-    if (a.ctr->flags & kCovSkipFlags) return;
-    const uint32_t n = min(*a.n_cand, a.n_reads), M = a.max_mismatch;
+    const uint32_t M = a.max_mismatch;
     const uint64_t off0 = a.seq_off[0];
-    uint32_t st[4] = {0, 0, 0, 0};         // candidates, rescued, rescued at 0, kept placements
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        const uint32_t r = a.cand[i];
-        const uint64_t o = a.seq_off[r];
-        const uint32_t len = (uint32_t)(a.seq_off[r + 1] - o), nb = len / kRescueAnchor;
-        const uint64_t w0 = ((o - off0) >> 5) + r;
-        st[0]++;
-        uint32_t best = M + 1u;
-        for (uint32_t sweep = 0; sweep < 2u && (sweep == 0 || best <= M); sweep++)
-            for (uint32_t strand = 0; strand < 2u; strand++) {
-                const unsigned long long *rd = a.rbuf + strand * a.rcap + w0;
-                for (uint32_t j = 0; j < nb; j++) {
-                    const uint32_t key = (uint32_t)(rd[j >> 1] >> (32u * (j & 1u)));
-                    uint32_t slot = rescue_hash(key) & a.tab_mask;
-                    uint4 e = a.tab[slot];
-                    while (e.z && e.x != key) { slot = (slot + 1u) & a.tab_mask; e = a.tab[slot]; }
-                    for (uint32_t q = e.y; q < e.y + e.z; q++) {
-                        const uint2 oc = a.occ[q];
-                        const uint4 pi = a.path[oc.x];                  // {text start, bases inside path_len, first Position, 0}
-                        const uint32_t rel = oc.y - pi.x;
-                        if (rel < kRescueAnchor * j || rel - kRescueAnchor * j + len > pi.y) continue;      // the read would hang over an end of the path
-                        const uint32_t to = rel - kRescueAnchor * j, g = pi.x + to;
-                        const uint32_t d = rescue_distance(a, rd, len, g, j, sweep ? best : min(best, M));
-                        if (sweep == 0) { best = min(best, d); continue; }
-                        if (d != best) continue;
-                        st[3]++;
-                        const uint64_t at = a.slot_base[oc.x] + pi.z + to;
-                        atomicAdd(a.starts + at, 1ull);
-                        atomicAdd(a.ends + at + len, 1ull);
-                        for (uint32_t k = 0; d && k < ((len + 31u) >> 5); k++) {
-                            bool nn;
-                            for (unsigned long long m = rescue_diff(a, rd, len, g, k, nn); m; m &= m - 1) {
-                                const uint32_t bit = (uint32_t)__ffsll(m) - 1u, code = (uint32_t)(rd[k] >> bit) & 3u;
-                                atomicAdd(a.alt + 4u * (at + 32u * k + (bit >> 1)) + (code ^ (code >> 1)), 1ull);      // A C T G -> A C G T
-                            }
+    const uint64_t o = a.seq_off[r];
+    len = (uint32_t)(a.seq_off[r + 1] - o);
+    const uint32_t nb = len / kRescueAnchor;
+    const uint64_t w0 = ((o - off0) >> 5) + r;
+    st[0]++;
+    uint32_t best = M + 1u;
+    for (uint32_t sweep = 0; sweep < 2u && (sweep == 0 || best <= M); sweep++)
+        for (uint32_t strand = 0; strand < 2u; strand++) {
+            const unsigned long long *rd = a.rbuf + strand * a.rcap + w0;
+            for (uint32_t j = 0; j < nb; j++) {
+                const uint32_t key = (uint32_t)(rd[j >> 1] >> (32u * (j & 1u)));
+                uint32_t slot = rescue_hash(key) & a.tab_mask;
+                uint4 e = a.tab[slot];
+                while (e.z && e.x != key) { slot = (slot + 1u) & a.tab_mask; e = a.tab[slot]; }
+                hit |= e.z != 0;
+                for (uint32_t q = e.y; q < e.y + e.z; q++) {
+                    const uint2 oc = a.occ[q];
+                    const uint4 pi = a.path[oc.x];                  // {text start, bases inside path_len, first Position, 0}
+                    const uint32_t rel = oc.y - pi.x;
+                    if (rel < kRescueAnchor * j || rel - kRescueAnchor * j + len > pi.y) continue;      // the read would hang over an end of the path
+                    const uint32_t to = rel - kRescueAnchor * j, g = pi.x + to;
+                    const uint32_t d = rescue_distance(a, rd, len, g, j, sweep ? best : min(best, M));
+                    if (sweep == 0) { best = min(best, d); continue; }
+                    if (d != best) continue;
+                    st[3]++;
+                    const uint64_t at = a.slot_base[oc.x] + pi.z + to;
+                    atomicAdd(a.starts + at, 1ull);
+                    atomicAdd(a.ends + at + len, 1ull);
+                    for (uint32_t k = 0; d && k < ((len + 31u) >> 5); k++) {
+                        bool nn;
+                        for (unsigned long long m = rescue_diff(a, rd, len, g, k, nn); m; m &= m - 1) {
+                            const uint32_t bit = (uint32_t)__ffsll(m) - 1u, code = (uint32_t)(rd[k] >> bit) & 3u;
+                            atomicAdd(a.alt + 4u * (at + 32u * k + (bit >> 1)) + (code ^ (code >> 1)), 1ull);      // A C T G -> A C G T
                         }
                     }
                 }
             }
-        if (best <= M) st[1]++;
-        if (best == 0) st[2]++;
+        }
+    return best;
+}
+
+// kGap: a candidate that stays unplaced and has len >= A (M + 3) joins the gap candidates (one ballot and one atomic per wavefront), if
+// one of its blocks had a table hit at all: a gapped placement needs an occurrence of a block.  The gap stats count by the definition.
+template <bool kGap> __global__ __launch_bounds__(kBlock) void rescue_count_kernel(RescueArgs a)
+{
+    if (a.ctr->flags & kCovSkipFlags) return;
+    const uint32_t n = min(*a.n_cand, a.n_reads), M = a.max_mismatch;
+    uint32_t st[4] = {0, 0, 0, 0};         // candidates, rescued, rescued at 0, kept placements
+    uint32_t gst[2] = {0, 0};              // gap candidates, too short for a gap
+    for (uint32_t i0 = blockIdx.x * kBlock; i0 < n; i0 += gridDim.x * kBlock) {      // (uniform per wavefront: the ballot below)
+        const uint32_t i = i0 + threadIdx.x, r = i < n ? a.cand[i] : 0u;
+        bool hand_on = false;
+        if (i < n) {
+            uint32_t len;
+            bool hit = false;
+            const uint32_t best = rescue_place(a, r, len, st, hit);
+            if (best <= M) st[1]++;
+            if (best == 0) st[2]++;
+            if (kGap && best > M) {
+                const bool long_enough = len >= kRescueAnchor * (M + 3u);
+                gst[0] += long_enough;
+                gst[1] += !long_enough;
+                hand_on = hit && long_enough;
+            }
+        }
+        if (kGap) {
+            const unsigned long long cb = __ballot(hand_on);
+            if (cb) {
+                const unsigned lane = threadIdx.x & 63u;
+                const int first = __ffsll(cb) - 1;
+                uint32_t at = 0;
+                if ((int)lane == first) at = atomicAdd(a.n_gcand, (uint32_t)__popcll(cb));
+                at = __shfl(at, first);
+                if (hand_on) a.gcand[at + (uint32_t)__popcll(cb & ((1ull << lane) - 1ull))] = r;
+            }
+        }
     }
     const uint32_t where[4] = {0, 1, 2, 3};
     rescue_add_stats(a.stats, st, where);
+    if (kGap) {
+        const uint32_t gwhere[2] = {0, 5};
+        rescue_add_stats(a.gstats, gst, gwhere);
+    }
 }
 
 } // namespace groot

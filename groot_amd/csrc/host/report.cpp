@@ -463,6 +463,62 @@ extern "C" int groot_host_variants_write(const groot_index_view *ix, const uint6
     return GROOT_OK;
 }
 
+// ---- indels: the gaps the gap-rescued reads show against the index (groot_hip_gap_export) -----------------------------------
+extern "C" int groot_host_indels_write(const groot_index_view *ix, const groot_gap_event *events, uint64_t n_events, const uint64_t *gdepth,
+                                       const uint64_t *rescued_depth, const uint64_t *exact_depth, uint64_t min_reads, double min_share,
+                                       const char *out_path, uint64_t *n_lines)
+{
+    if (!ix || (n_events && !events) || (ix->n_paths && (!gdepth || !rescued_depth || !exact_depth))) return set_error(GROOT_E_INVALID, "null argument");
+    if (!(min_share >= 0.0 && min_share <= 1.0)) return set_error(GROOT_E_INVALID, "minimum share %g is not in [0, 1]", min_share);
+    std::vector<uint64_t> base(ix->n_paths + 1, 0);
+    for (uint32_t p = 0; p < ix->n_paths; p++) base[p + 1] = base[p] + ix->path_len[p];
+    std::vector<uint8_t> wanted(ix->n_paths, 0);
+    for (uint64_t i = 0; i < n_events; i++) {
+        const groot_gap_event &e = events[i];
+        if (e.path >= ix->n_paths || e.type > GROOT_GAP_INS || e.len < 1 || e.len > 8 || (uint64_t)e.pos + (e.type == GROOT_GAP_DEL ? e.len : 0) >= ix->path_len[e.path] ||
+            (e.type == GROOT_GAP_DEL ? e.seq != 0 : (e.seq >> (2 * e.len)) != 0))
+            return set_error(GROOT_E_INVALID, "event %llu: path %u, pos %u, type %u, len %u, seq %u is none of the index", (unsigned long long)i, e.path, e.pos, e.type, e.len, e.seq);
+        const uint64_t at = base[e.path] + e.pos;
+        if (e.reads > gdepth[at] || gdepth[at] + rescued_depth[at] < gdepth[at] || gdepth[at] + rescued_depth[at] + exact_depth[at] < exact_depth[at])
+            return set_error(GROOT_E_INVALID, "event %llu: %llu read(s) at a gap depth of %llu", (unsigned long long)i, (unsigned long long)e.reads, (unsigned long long)gdepth[at]);
+        wanted[e.path] = 1;
+    }
+    std::vector<std::string> ref(ix->n_paths);                                         // the bases of every path with an event, by path coordinate
+    for (uint32_t p = 0; p < ix->n_paths; p++)
+        if (wanted[p]) ref[p].assign(ix->path_len[p], 'N');
+    for (uint32_t g = 0; g < ix->n_graphs; g++)
+        for (uint32_t n = ix->graph_node_off[g]; n < ix->graph_node_off[g + 1]; n++)
+            for (uint32_t i = ix->node_np_off[n]; i < ix->node_np_off[n + 1]; i++) {
+                const uint64_t gp = (uint64_t)ix->graph_path_off[g] + ix->np_path[i];
+                if (gp >= ix->n_paths || !wanted[gp]) continue;
+                for (uint32_t j = ix->node_seq_off[n]; j < ix->node_seq_off[n + 1]; j++) {
+                    const uint64_t y = (uint64_t)ix->np_pos[i] + (j - ix->node_seq_off[n]);
+                    if (y < ix->path_len[gp]) ref[gp][y] = (char)ix->bases[j];
+                }
+            }
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) return set_error(GROOT_E_IO, "cannot create %s", out_path);
+    uint64_t lines = 0;
+    for (uint64_t i = 0; i < n_events; i++) {
+        const groot_gap_event &e = events[i];
+        const uint64_t at = base[e.path] + e.pos, gd = gdepth[at], rd = rescued_depth[at], ed = exact_depth[at];
+        if (!e.reads || e.reads < min_reads) continue;
+        const double share = (double)e.reads / (double)(gd + rd + ed);
+        if (!(share >= min_share)) continue;
+        char seq[9] = {0};
+        for (uint32_t j = 0; j < e.len; j++) seq[j] = e.type == GROOT_GAP_DEL ? ref[e.path][e.pos + 1 + j] : "ACGT"[(e.seq >> (2 * j)) & 3];
+        const char *nm = ix->path_names + ix->path_name_off[e.path];
+        size_t nl = ix->path_name_off[e.path + 1] - ix->path_name_off[e.path];
+        if (nl && nm[0] == '*') { nm++; nl--; }                                        // as the report prints it
+        fprintf(out, "%.*s\t%u\t%s\t%u\t%s\t%llu\t%llu\t%llu\t%llu\t%.4f\n", (int)nl, nm, e.pos + 1, e.type == GROOT_GAP_DEL ? "DEL" : "INS", (unsigned)e.len, seq,
+                (unsigned long long)e.reads, (unsigned long long)gd, (unsigned long long)rd, (unsigned long long)ed, share);
+        lines++;
+    }
+    if (out_path) fclose(out); else fflush(out);
+    if (n_lines) *n_lines = lines;
+    return GROOT_OK;
+}
+
 // ---- abundance: EM over equivalence classes ---------------------------------------------------------------------------------
 // src/em/em.go NewEM / Run / Return (lines 29-158), restated in double precision without FMA contraction (the library is built
 // without -march), over ECs in canonical order: the reference iterates a Go map, so its sums are not reproducible.

@@ -15,6 +15,9 @@ TRAV_DTYPE = np.dtype([("read_id", "<u4"), ("graph_id", "<u4"), ("node", "<u4"),
 ALN_DTYPE = np.dtype([("read_id", "<u4"), ("graph_id", "<u4"), ("path_id", "<u4"), ("ref_id", "<u4"), ("pos", "<u4"),
                       ("start_clip", "u1"), ("end_clip", "u1"), ("rc", "u1"), ("secondary", "u1")])
 SEED_DTYPE = np.dtype([("read_id", "<u4"), ("window_id", "<u4")])
+GAP_EVENT_DTYPE = host.GAP_EVENT_DTYPE                     # groot_gap_event
+GAP_DEL, GAP_INS = 0, 1
+GAP_STATS = ("candidates", "rescued", "placements", "del_placements", "ins_placements", "too_short", "events", "dropped", "event_slots", "launches")
 TRAV_RC, TRAV_START_CLIP, TRAV_END_CLIP, TRAV_FIRST, TRAV_MAPQ = 1, 2, 4, 8, 16
 
 
@@ -569,6 +572,32 @@ class Aligner:
 
     def rescue_reset(self):
         self._check(lib().groot_hip_rescue_reset(self._h))
+
+    # ---- gapped rescue of the reads mismatch rescue leaves (groot_hip_gap_*) --------------------------
+    def gap_enable(self, max_gap=3, event_slots=0):
+        """reads that mismatch rescue leaves unplaced are laid on the path texts with one gap of up to `max_gap` bases (include/groot_hip.h,
+        "gapped rescue"); 0 switches it off.  Needs rescue_enable first.  event_slots: a power of two, 0 for the default of 2^22."""
+        self._check(lib().groot_hip_gap_enable(self._h, C.c_uint32(max_gap), C.c_uint64(event_slots)))
+
+    def gap(self):
+        """(gdepth[sum of path_len] as uint64, events as GAP_EVENT_DTYPE ascending by (path, pos, type, len, seq)) over every batch
+        since enable / reset"""
+        gdepth = np.zeros(int(self.index.arrays["path_len"].astype(np.int64).sum()), dtype=np.uint64)
+        n = C.c_uint64(0)
+        cap = int(self.gap_stats()["events"])
+        events = np.zeros(cap, dtype=GAP_EVENT_DTYPE)
+        self._check(lib().groot_hip_gap_export(self._h, _ffi.as_ptr(gdepth, C.c_uint64), events.ctypes.data_as(C.c_void_p), C.c_uint64(cap), C.byref(n)))
+        return gdepth, events[:n.value]
+
+    def gap_stats(self):
+        """groot_hip_gap_stats: {"candidates", "rescued", "placements", "del_placements", "ins_placements", "too_short", "events", "dropped",
+        "event_slots", "launches"}"""
+        v = (C.c_uint64 * 10)()
+        self._check(lib().groot_hip_gap_stats(self._h, v))
+        return dict(zip(GAP_STATS, (int(x) for x in v)))
+
+    def gap_reset(self):
+        self._check(lib().groot_hip_gap_reset(self._h))
 
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):

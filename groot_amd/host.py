@@ -417,6 +417,23 @@ def variants_write(index, rescued_depth, alt, exact_depth, out_path, min_reads=2
     return n.value
 
 
+GAP_EVENT_DTYPE = np.dtype([("path", "<u4"), ("pos", "<u4"), ("type", "u1"), ("len", "u1"), ("seq", "<u2"), ("reserved", "<u4"), ("reads", "<u8")])   # groot_gap_event
+
+
+def indels_write(index, events, gdepth, rescued_depth, exact_depth, out_path, min_reads=2, min_share=0.1):
+    """the indels file (groot_host_indels_write) from device.Aligner.gap() -- merged over the ctxs: gdepth summed, events by key -- the
+    depth of device.Aligner.rescue() and the depth of device.Aligner.coverage(); returns the lines written"""
+    n_bases = int(index.arrays["path_len"].astype(np.uint64).sum())
+    ev = np.ascontiguousarray(events, dtype=GAP_EVENT_DTYPE)
+    gd, rd, ed = (np.ascontiguousarray(x, dtype=np.uint64) for x in (gdepth, rescued_depth, exact_depth))
+    if gd.shape != (n_bases,) or rd.shape != (n_bases,) or ed.shape != (n_bases,):
+        raise ValueError("gap depth / rescued depth / exact depth do not match the index")
+    n = C.c_uint64(0)
+    _check(lib().groot_host_indels_write(C.byref(index.view), ev.ctypes.data_as(C.c_void_p), C.c_uint64(len(ev)), _ffi.as_ptr(gd, C.c_uint64), _ffi.as_ptr(rd, C.c_uint64),
+                                         _ffi.as_ptr(ed, C.c_uint64), C.c_uint64(min_reads), C.c_double(min_share), os.fsencode(out_path), C.byref(n)))
+    return n.value
+
+
 def report_coverage(index, records, depth, cov_cutoff=0.97, low_cov=False, out_path=None):
     """the report of `report` from counts instead of a BAM (groot_host_report_coverage): records[n_paths] and depth[sum of
     path_len] as uint64, e.g. device.Aligner.coverage(); same rows as `report` on the BAM whose records they count"""

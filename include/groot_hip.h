@@ -504,6 +504,64 @@ int groot_hip_rescue_stats(groot_ctx *ctx, groot_rescue_stats *out);
 /* Zeroes tables and stats (after waiting for everything in flight).  No-op when off. */
 int groot_hip_rescue_reset(groot_ctx *ctx);
 
+/* ---- gapped rescue of the reads mismatch rescue leaves ------------------------------------------------------------------
+ * Mismatch rescue places reads that differ from a path's text by substitutions only.  A read across a frameshift, or across a codon
+ * deletion or insertion, stays unplaced.  With gapped rescue on (it needs mismatch rescue on), a third kernel behind the two of rescue
+ * (kernels_gap.hpp) lays those reads on the texts with ONE gap of up to G bases and up to M substitutions, and piles up where they lie
+ * and which gaps they show.  Everything else, mismatch rescue's tables included, stays what it is.  The definition, all of it integers:
+ *
+ *   M, A = 16, texts, path coordinates, 'N', CANDIDATE, oriented read, strand: exactly mismatch rescue's.   G = max gap length, 1 <= G <= 8.
+ *   A GAP CANDIDATE is a candidate of mismatch rescue that is NOT rescued (no ungapped placement with d <= M) and has len >= A * (M + 3).
+ *      (A candidate that is rescued ungapped is never looked at here, even if a gapped placement would cost less.)
+ *   A GAPPED PLACEMENT of r is (p, strand, x, type, g, k), 1 <= g <= G, with the oriented read R (len bases) and T = text_p:
+ *      type DEL (g text bases missing from the read):   R[0,k) on T[x, x+k),  R[k,len) on T[x+k+g, x+len+g);   A <= k <= len - A
+ *                                                       occupied window W = T[x, x+len+g)
+ *      type INS (g read bases missing from the text):   R[0,k) on T[x, x+k),  R[k+g,len) on T[x+k, x+len-g);   A <= k <= len - g - A
+ *                                                       occupied window W = T[x, x+len-g);  R[k,k+g) is the inserted sequence
+ *      W lies entirely inside the text's bases inside path_len (mismatch rescue's bound) and holds no 'N' (the deleted bases included).
+ *      d(k) = the number of mismatching bases of the two aligned parts.   (Both flanks are at least A bases: a gap nearer to an end
+ *      than that is not told apart from substitutions at the end, and is left out.)
+ *   For fixed (p, strand, x, type, g):  d = min over the allowed k of d(k);  k* = the SMALLEST k with d(k) = d (the gap is left-aligned);
+ *      the gapped placement of (p, strand, x, type, g) is the one at k*, and it exists when d <= M.    Its cost is e = d + g.
+ *   e*(r) = the smallest e over r's gapped placements.  r is GAP-RESCUED when it has one; its KEPT gapped placements are all those with
+ *      e = e* (every path, both strands, every x, both types, every g).  Each (p, strand, x, type, g) counts once, however it was found.
+ *   Per kept gapped placement, in path coordinates (X = first Position of the path + x):
+ *      gdepth[p][y] += 1 for every text base y an aligned read base lies on:  DEL: [X, X+k*) and [X+k*+g, X+len+g);  INS: [X, X+len-g).
+ *      event (p, pos = X + k* - 1, type, g, seq) += 1.   pos is the last text base before the gap.  seq = the g inserted read bases
+ *      R[k*, k*+g) in path strand for INS (2 bits per base, base i in bits 2i..2i+1, A C G T = 0 1 2 3), 0 for DEL.
+ *      Substitutions of gapped placements are not piled up anywhere.
+ *   Stats: gap candidates, gap-rescued, kept gapped placements, kept DEL placements, kept INS placements, candidates left out as too short
+ *      for a gap (len < A (M + 3)), distinct events, events dropped (table full).
+ *
+ * Why the anchor search loses nothing: len >= A(M+3) gives at least M+3 disjoint 16-base blocks [0,16), [16,32), .. of the oriented read.
+ * Substitutions spoil at most M of them, a DEL cut spoils at most one, the inserted bases of an INS (at most 8) touch at most two.  So at
+ * least one block lies wholly in the part in front of the gap or wholly in the part behind it, error-free, inside a window without 'N':
+ * that block is in the 16-mer table, and the kernel tries every occurrence of every block under both hypotheses.
+ * The tables depend on the reads and the index alone: not on batch size, pipeline depth, first-pass variant, results_on_device, or how the
+ * reads are spread over ctxs; merging several ctxs is a sum (gdepth elementwise, events by key).  A batch is counted once, by the rule
+ * of report coverage.  Off by default: then no allocation, launch or sync, and rescue_count_kernel is the one without the hand-over. */
+/* groot_gap_event, GROOT_GAP_DEL and GROOT_GAP_INS: groot_host.h ("Indels"), whose writer reads them */
+typedef struct groot_gap_stats {
+    uint64_t candidates, rescued, placements /* kept */, del_placements, ins_placements, too_short, events /* distinct */, dropped;
+    uint64_t event_slots; /* slots of the event table (0 while off) */
+    uint64_t launches;    /* rescue_gap_kernel launches since open, whether it is on now or not (not part of groot_rescue_stats.launches) */
+} groot_gap_stats;
+/* max_gap 1..8: on (0: off, everything freed, nothing launched afterwards; above 8: GROOT_E_INVALID).  GROOT_E_STATE when mismatch rescue is
+ * off, or when something is in flight.  event_slots: the slots of the event table, a power of two (0: 2^22 = 64 MB; anything else:
+ * GROOT_E_INVALID); the table does not grow.  Tables start at zero; another G or another event_slots while on zeroes them, and so do
+ * groot_hip_rescue_enable with another M and groot_hip_rescue_reset (they are derived from the same reads); groot_hip_rescue_enable(.., 0)
+ * switches gapped rescue off as well.  Device memory: 16 bytes per path base, 16 bytes per event slot, 4 bytes per read of a batch. */
+int groot_hip_gap_enable(groot_ctx *ctx, uint32_t max_gap, uint64_t event_slots);
+/* gdepth[sum of path_len] laid out as groot_hip_rescue_export's depth; events[0 .. *n_events) ascending by (path, pos, type, len, seq).
+ * *n_events is always set to the number of distinct events; cap below it: GROOT_E_INVALID.  Events were dropped because the table was
+ * full: GROOT_E_NOSPACE, and the message names event_slots.  Waits for everything in flight (redoing what needs a redo).
+ * GROOT_E_STATE when gapped rescue is off. */
+int groot_hip_gap_export(groot_ctx *ctx, uint64_t *gdepth, groot_gap_event *events, uint64_t cap, uint64_t *n_events);
+/* Since enable / reset, counted once exactly as the tables are; zeros while off, but for launches.  Waits for everything in flight. */
+int groot_hip_gap_stats(groot_ctx *ctx, groot_gap_stats *out);
+/* Zeroes the gap tables and stats (after waiting for everything in flight).  No-op when off. */
+int groot_hip_gap_reset(groot_ctx *ctx);
+
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
  * the device, bit for bit in boot_count, alpha and iterations.  Quoted from there: draw j (0 <= j < n_draws; n_draws = 0 means N, the sum

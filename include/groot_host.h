@@ -303,6 +303,30 @@ int groot_host_report_shared(const char *bam_path, double cov_cutoff, int low_co
 int groot_host_variants_write(const groot_index_view *idx, const uint64_t *rescued_depth, const uint64_t *alt, const uint64_t *exact_depth,
                               uint64_t min_reads, double min_share, const char *out_path, uint64_t *n_lines);
 
+/* Indels (gapped rescue, defined at groot_hip_gap_enable in groot_hip.h): the gaps that reads left unplaced by mismatch rescue show
+ * against the indexed alleles.  An event is one (path, position, type, length, inserted sequence) with the kept gapped placements
+ * that show it, as groot_hip_gap_export gives them. */
+#define GROOT_GAP_DEL 0
+#define GROOT_GAP_INS 1
+typedef struct groot_gap_event {
+    uint32_t path, pos;  /* global path; path coordinate of the last text base before the gap */
+    uint8_t type, len;   /* GROOT_GAP_DEL / GROOT_GAP_INS; the gap's bases, 1..8 */
+    uint16_t seq;        /* INS: the inserted bases in path strand, 2 bits each, base i in bits 2i..2i+1, A C G T = 0 1 2 3; DEL: 0 */
+    uint32_t reserved;
+    uint64_t reads;      /* kept gapped placements that show it */
+} groot_gap_event;
+/* events[n_events] are the merged groot_hip_gap_export of every ctx (events by key), gdepth / rescued_depth / exact_depth[sum of path_len]
+ * the summed gdepth of groot_hip_gap_export, depth of groot_hip_rescue_export and depth of groot_hip_coverage_export.  One line
+ *     name \t pos (1-based, the base before the gap) \t type (DEL|INS) \t len \t seq \t reads \t gap_depth \t rescued_depth \t exact_depth \t share
+ * per event with reads >= max(min_reads, 1) and share = reads / (gap_depth + rescued_depth + exact_depth) >= min_share (the three depths
+ * at pos; one division in double, printed %.4f), in the order given (the export's: path, pos, type, len, seq).  seq: the deleted bases
+ * of the path for a DEL, the inserted bases for an INS; the name as the report prints it.  out_path NULL = stdout; *n_lines = lines
+ * written.  GROOT_E_INVALID, before anything is written, for an event outside its path (a DEL's bases included), with a type or length the
+ * device never gives, or with more reads than the gap depth at its pos (every placement that shows an event covers that base). */
+int groot_host_indels_write(const groot_index_view *idx, const groot_gap_event *events, uint64_t n_events, const uint64_t *gdepth,
+                            const uint64_t *rescued_depth, const uint64_t *exact_depth, uint64_t min_reads, double min_share,
+                            const char *out_path, uint64_t *n_lines);
+
 /* ---- abundance by EM over equivalence classes ----------------------------------------------------------------------
  * ECs as defined at groot_hip_ec_enable in groot_hip.h (distinct non-empty S(r), ascending path IDs, in CSR form: EC i is
  * ids[off[i] .. off[i+1]) with count[i] reads).  groot_host_em restates src/em/em.go NewEM / Run / Return (lines 29-158) in double
