@@ -24,6 +24,7 @@ struct Harvested {                           // the sums over every harvest so f
     std::vector<uint64_t> gap_depth;                         // --indels: gap depth per base, the events of every ctx merged by key (groot_hip_gap_*)
     std::map<std::array<uint32_t, 5>, uint64_t> gap_events;  // (path, pos, type, len, seq) -> reads: ascending as the export is
     groot_gap_stats gap{};
+    groot_rescue_ec_stats rescue_ec{};                       // --abundanceRescued: the rescued reads in the classes (groot_hip_rescue_ec_*)
 };
 
 class RunCounters {
@@ -34,8 +35,8 @@ public:
         for (uint32_t p = 0; p < v.n_paths; p++) cov_slots_ += v.path_len[p];
         h_.cov_records.resize(plan.coverage ? v.n_paths : 0);
         h_.cov_depth.resize(plan.coverage ? cov_slots_ : 0);
-        h_.res_depth.resize(plan.rescue ? cov_slots_ : 0);
-        h_.res_alt.resize(plan.rescue ? 4 * cov_slots_ : 0);
+        h_.res_depth.resize(plan.variants || plan.indels ? cov_slots_ : 0);
+        h_.res_alt.resize(plan.variants || plan.indels ? 4 * cov_slots_ : 0);
         h_.gap_depth.resize(plan.indels ? cov_slots_ : 0);
         if (!plan.assign) return;
         uint64_t named = 0;
@@ -61,10 +62,12 @@ public:
             if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
         if (plan_.calls && on)
             if (int rc = groot_hip_acov_enable(ctx, 1)) return rc;
-        return plan_.abundance ? groot_hip_ec_enable(ctx, on) : 0;     // (off: assigned coverage goes with it)
+        if (plan_.abundance)
+            if (int rc = groot_hip_ec_enable(ctx, on)) return rc;        // (off: assigned coverage goes with it, and so do the rescued reads in the classes)
+        return plan_.ab_rescued && on ? groot_hip_rescue_ec_enable(ctx, 1) : 0;
     }
 
-    // assign stats, pair stats, acov-or-EC export, gapped rescue, rescue, coverage, shared pairs: each added under the lock (the mappers harvest side by side)
+    // assign stats, pair stats, acov-or-EC export, rescued reads in the ECs, gapped rescue, rescue, coverage, shared pairs: each added under the lock (the mappers harvest side by side)
     int harvest(groot_ctx *ctx)
     {
         if (plan_.assign) {
@@ -103,6 +106,12 @@ public:
             std::lock_guard<std::mutex> lk(mu_);
             append_ecs(off.data(), ids.data(), cnt.data(), ne, ni);
         }
+        if (plan_.ab_rescued) {
+            groot_rescue_ec_stats st{};
+            if (int rc = groot_hip_rescue_ec_stats(ctx, &st)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            h_.rescue_ec.reads += st.reads; h_.rescue_ec.slow_reads += st.slow_reads; h_.rescue_ec.launches += st.launches; h_.rescue_ec.rows = st.rows;
+        }
         if (plan_.indels) {         // (a table that dropped events fails here, with the reason: no indels file is written)
             groot_gap_stats st{};
             uint64_t n = 0;
@@ -117,7 +126,7 @@ public:
             for (size_t i = 0; i < d.size(); i++) h_.gap_depth[i] += d[i];
             for (uint64_t i = 0; i < n; i++) h_.gap_events[{ev[i].path, ev[i].pos, ev[i].type, ev[i].len, ev[i].seq}] += ev[i].reads;
         }
-        if (plan_.rescue) {
+        if (plan_.variants || plan_.indels) {
             groot_rescue_stats st{};
             std::vector<uint64_t> d(cov_slots_), al(4 * cov_slots_);
             if (int rc = groot_hip_rescue_stats(ctx, &st)) return rc;

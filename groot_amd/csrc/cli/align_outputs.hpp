@@ -98,6 +98,13 @@ Bootstrap write_abundance(const Args &a, const AlignPlan &plan, const groot_inde
         die("%s", groot_host_last_error());
     logf("\tabundance: %llu equivalence class(es), EM of %u iteration(s) in %.3f s, %llu ARG(s) with at least %g reads written to %s",
          (unsigned long long)h.ec_cnt.size(), iters, seconds_since(t_em), (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
+    if (plan.ab_rescued) {
+        uint64_t units = 0;
+        for (uint64_t c : h.ec_cnt) units += c;
+        logf("\tabundance: %llu rescued read(s) counted in the equivalence classes beside %llu read(s) with an exact alignment, placed with up to %ld substitution(s); "
+             "%llu of them on ARGs of more than 4 graphs",
+             (unsigned long long)h.rescue_ec.reads, (unsigned long long)(units - h.rescue_ec.reads), a.rescue, (unsigned long long)h.rescue_ec.slow_reads);
+    }
     if (plan.rarefy && !plan.calls) {
         // the curve of the abundance file alone: over the merged ECs in canonical order, as the bootstrap takes them
         const Ecs c = canonical_ecs(v, h);

@@ -6,7 +6,8 @@ namespace {
 
 struct AlignPlan {
     bool report = false, shared = false, abundance = false, calls = false, assign = false, rarefy = false, variants = false, indels = false;
-    bool rescue = false;     // mismatch rescue runs: --variants or --indels
+    bool rescue = false;     // mismatch rescue runs: --variants, --indels or --abundanceRescued
+    bool ab_rescued = false; // --abundanceRescued: the rescued reads join the equivalence classes
     bool coverage = false;   // report coverage is counted: --report, or --variants / --indels for its exact depth
     bool frags = false;      // --paired / --interleaved
     bool counters = false;   // a ctx carries switches: set at open and reopen, harvested before it closes
@@ -77,9 +78,10 @@ int plan_align(const Args &a, AlignPlan *p)
     if (p->variants && a.no_align) return refuse("--variants rescues the reads the exact alignments leave out: it cannot be combined with --noAlign");
     if (p->variants && p->assign) return refuse("--variants cannot be combined with --assignFrom: assignment rewrites the records that tell which reads are unaligned");
     p->indels = !a.indels_out.empty();
-    p->rescue = p->variants || p->indels;
+    p->ab_rescued = a.abundance_rescued;
+    p->rescue = p->variants || p->indels || p->ab_rescued;
     if (a.rescue_given && !p->rescue) return refuse("--rescue is the number of substitutions --variants allows: it needs it");
-    if (a.variant_min_given && !p->rescue) return refuse("--variantMinReads and --variantMinShare are the thresholds of --variants: they need it");
+    if (a.variant_min_given && !p->variants && !p->indels) return refuse("--variantMinReads and --variantMinShare are the thresholds of --variants: they need it");
     if (p->rescue && (a.rescue < 1 || a.rescue > 3)) return refuse("--rescue allows 1, 2 or 3 substitutions: %ld", a.rescue);
     if (p->rescue && a.variant_min_reads < 0) return refuse("--variantMinReads is a number of reads: %lld", a.variant_min_reads);
     if (p->rescue && !(a.variant_min_share >= 0.0 && a.variant_min_share <= 1.0)) return refuse("--variantMinShare is a share: %g is not in [0, 1]", a.variant_min_share);
@@ -90,7 +92,13 @@ int plan_align(const Args &a, AlignPlan *p)
     if (p->indels && (a.rescue_gap < 1 || a.rescue_gap > 8)) return refuse("--rescueGap allows a gap of 1 to 8 bases: %ld", a.rescue_gap);
     if (p->indels && a.gap_slots_given && (a.gap_event_slots < 1 || (a.gap_event_slots & (a.gap_event_slots - 1))))
         return refuse("--gapEventSlots is a number of table slots, a power of two: %lld", a.gap_event_slots);
-    p->coverage = p->report || p->rescue;
+    // --abundanceRescued: checked behind everything above
+    if (p->ab_rescued && !p->abundance) return refuse("--abundanceRescued adds the rescued reads to the classes --abundance estimates from: it needs --abundance");
+    if (p->ab_rescued && p->calls) return refuse("--abundanceRescued cannot be combined with --calls: its pileup weighs records, and a rescued read has none");
+    if (p->ab_rescued && p->frags)
+        return refuse("--abundanceRescued cannot be combined with %s yet: mates are rescued one by one, and a fragment's set has no rule for them",
+                      a.paired ? "--paired" : "--interleaved");
+    p->coverage = p->report || p->variants || p->indels;
     p->counters = p->report || p->abundance || p->assign || p->rescue;
     return 0;
 }

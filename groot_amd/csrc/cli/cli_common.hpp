@@ -72,6 +72,7 @@ struct Args {
     long long variant_min_reads = 2;       // --variantMinReads N
     double variant_min_share = 0.1;        // --variantMinShare S
     bool rescue_given = false, variant_min_given = false;
+    bool abundance_rescued = false;          // --abundanceRescued: the reads mismatch rescue places join the equivalence classes of --abundance
     std::string indels_out;                // --indels: the gaps that the reads neither aligned nor rescued show, placed with one gap of up to --rescueGap bases
     long rescue_gap = 3;                   // --rescueGap G (1..8)
     long long gap_event_slots = 0;         // --gapEventSlots N (a power of two; 0: the library's default)

@@ -33,8 +33,8 @@ void usage()
             "  groot-hip align -i <indexDir> -f <fastq>[,<fastq>...] [-t 0.99] [-c 1.0] [-g <graphDir>] [--noAlign] [-p N] [--log F]\n"
             "                  [--gpu 0 | --gpus N] [--batch 1048576] [--maxReadLen 512] [--bam out.bam] [--bamLevel -2..9] [--stats f.json]\n"
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
-            "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0]] [--noBam]\n"
-            "                  [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
+            "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0] [--abundanceRescued [--rescue 2]]]\n"
+            "                  [--noBam] [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
@@ -43,6 +43,9 @@ void usage()
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
             "                   --abundance: `name reads em_reads fraction` per ARG with em_reads >= --abundanceMin, by EM over the reads' path sets;\n"
+            "                   --abundanceRescued: with --abundance, a read WITHOUT an exact alignment that mismatch rescue places with up to --rescue (1..3)\n"
+            "                   substitutions counts too, with the set of ARGs it was placed on: `reads` then counts the reads that lie on the ARG exactly or\n"
+            "                   rescued, and the EM, --bootstraps and --rarefy see them all.  Not with --calls, --paired or --interleaved;\n"
             "                   --bootstraps: with --abundance, four more columns `boot_mean boot_sd boot_lo boot_hi` from B replicates of the reads\n"
             "                   resampled with replacement (--bootSeed), each with its own EM, drawn and fitted on the GPU;\n"
             "                   --calls: with --abundance, per line of the abundance file `name em_reads length depth breadth cigar called`: the pileup of\n"
@@ -113,6 +116,7 @@ Args parse(int argc, char **argv)
         else if (ar && f == "--abundance") a.abundance_out = v();
         else if (ar && f == "--calls") a.calls_out = v();
         else if (ar && f == "--callDepth") a.call_depth = atof(v().c_str());
+        else if (a.cmd == "align" && f == "--abundanceRescued") a.abundance_rescued = true;
         else if (ar && f == "--abundanceMin") a.abundance_min = atof(v().c_str());
         else if (ar && f == "--bootstraps") a.bootstraps = (uint32_t)std::max(0l, atol(v().c_str()));
         else if (ar && f == "--bootSeed") a.boot_seed = strtoull(v().c_str(), nullptr, 10);

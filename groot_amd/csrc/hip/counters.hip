@@ -1,7 +1,8 @@
 // counters.hip -- the counters that run behind every batch's order stage, and their C ABI (include/groot_hip.h): report coverage
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
-// draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp).  One of the six translation units of
+// draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp), rescued reads in the equivalence
+// classes (kernels_rescue_ec.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <hip/hip_runtime.h>
 
@@ -26,6 +27,7 @@
 #include "kernels_rare.hpp"
 #include "kernels_gap.hpp"
 #include "kernels_rescue.hpp"
+#include "kernels_rescue_ec.hpp"
 #include "kernels_shared.hpp"
 
 using namespace groot;
@@ -85,6 +87,8 @@ void EcBufs::release()
 // Before a batch's merge: each batch adds at most n_reads keys, so the table must keep >= 2 x (the fill read back at the newest
 // collect + n_reads of every batch launched and not collected, this one included) slots -- else it doubles, rehashed in tail-stream
 // order.  (Growth is rare -- a handful of times per run -- so the old buffers are freed behind a wait for the tail stream.)
+// With rescued reads in the ECs (kernels_rescue_ec.hpp) a batch has a second merge, and the bound holds for both together: a rescued
+// read has no record, so the reads with a record and the rescued ones are at most n_reads, and so are their distinct sets.
 static int ec_reserve(groot_ctx *c, Slot *s)
 {
     Counters &k = c->ct;
@@ -306,6 +310,36 @@ static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
     return GROOT_OK;
 }
 
+// ---- rescued reads in the equivalence classes (kernels_rescue_ec.hpp) ----
+// At collect: the bitmaps of the batch's slow rescued reads, each as an ascending ID list into ec_host, the way ec_collect folds the
+// exact slow reads.  refetch: the copy enqueue made is stale (the batch was redone).
+static int rec_collect(groot_ctx *c, Slot *s, bool refetch)
+{
+    Counters &k = c->ct;
+    if (!s->ct.d_rec_slow.p) return GROOT_OK;      // (launched before the feature came on)
+    if (refetch) HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t n_slow = s->ct.h_status.p->rec_slow;
+    if (!n_slow) return GROOT_OK;
+    if (n_slow > k.rec_rows)
+        return fail(c, GROOT_E_NOSPACE, "rescued reads in the equivalence classes: a batch has %u rescued reads whose sets lie in more graphs than a row holds, and room for "
+                    "the bitmaps of %u (GROOT_TEST_RESCUE_EC_ROWS)", n_slow, k.rec_rows);
+    std::vector<uint64_t> bits((size_t)n_slow * k.rec_bw);
+    HIP_TRY(c, hipMemcpy(bits.data(), s->ct.d_rec_bits.p, bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const uint32_t n_paths = (uint32_t)k.h_len.size();
+    std::vector<uint32_t> ids;
+    for (uint32_t i = 0; i < n_slow; i++) {
+        ids.clear();
+        for (uint32_t w = 0; w < k.rec_bw; w++)
+            for (uint64_t m = bits[(size_t)i * k.rec_bw + w]; m; m &= m - 1) {
+                const uint32_t id = w * 64 + (uint32_t)__builtin_ctzll(m);
+                if (id < n_paths) ids.push_back(id);
+            }
+        if (!ids.empty()) k.ec_host[ids]++;
+    }
+    k.rec_slow += n_slow;
+    return GROOT_OK;
+}
+
 // ---- the pipeline's hooks (counters.hpp) ---------------------------------------------------------------------------
 namespace groot {
 
@@ -362,8 +396,9 @@ int counters_launch(groot_ctx *c, Slot *s)
         hipLaunchKernelGGL(cov_count_kernel, g, dim3(kBlock), 0, c->tstream, ca);
         HIP_TRY(c, hipGetLastError());
     }
+    SharedArgs sa{};
+    uint32_t tab = 1;                      // this batch's part of the table: >= 2 n_reads slots
     if (k.sh_on || k.ec_on) {    // (the same: slot data and the ctx's own buffers, in tail-stream order)
-        SharedArgs sa{};
         sa.trav = s->d_trav.p; sa.mask = s->d_mask.p; sa.ctr = s->d_ctr.p; sa.graph_path_off = k.d_gpo.p;
         sa.set_graph = k.sh_set_graph.p; sa.set_mask = k.sh_set_mask.p; sa.tab_rep = k.sh_tab_rep.p; sa.tab_cnt = k.sh_tab_cnt.p;
         sa.slow = k.sh_slow.p; sa.batch = k.sh_batch.p; sa.tri = k.sh_tri.p; sa.stats = k.sh_stats.p;
@@ -371,7 +406,6 @@ int counters_launch(groot_ctx *c, Slot *s)
         sa.max_segs = c->kn.shared_slow ? 1u : kSharedSegs;
         sa.pairs = k.sh_on;
         sa.slow_cap = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-        uint32_t tab = 1;                  // this batch's part of the table: >= 2 n_reads slots
         while (tab < 2u * std::max<uint32_t>(s->n_reads, 1u)) tab <<= 1;
         sa.tab_mask = tab - 1;
         const dim3 gt(grid_for(tab));      // the merge and the expansion: one item per slot of that part
@@ -404,7 +438,12 @@ int counters_launch(groot_ctx *c, Slot *s)
         ra.tab_mask = (uint32_t)k.res_tab.n - 1u; ra.n_reads = s->n_reads; ra.max_mismatch = k.res_m;
         HIP_TRY(c, hipMemsetAsync(k.res_ncand.p, 0, sizeof(uint32_t), c->tstream));
         hipLaunchKernelGGL(rescue_pack_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
-        if (!k.gap_on) hipLaunchKernelGGL(rescue_count_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+        if (k.rec_on) {      // (the rows and the per-batch table are free: shared_expand_kernel, above on this stream, has cleared them)
+            ra.path_bit = k.rec_path_bit.p; ra.set_graph = sa.set_graph; ra.set_mask = sa.set_mask; ra.dstar = k.rec_dstar.p;
+            ra.pw = sa.pw; ra.max_segs = sa.max_segs;
+        }
+        if (!k.gap_on && k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+        else if (!k.gap_on) hipLaunchKernelGGL(rescue_count_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
         else {
             GapArgs ga{};
             ra.gcand = k.gap_cand.p; ra.n_gcand = k.gap_ncand.p; ra.gstats = k.gap_stats.p;
@@ -412,12 +451,28 @@ int counters_launch(groot_ctx *c, Slot *s)
             ga.starts = k.gap_starts.p; ga.ends = k.gap_ends.p; ga.ev_key = k.gap_key.p; ga.ev_cnt = k.gap_cnt.p; ga.stats = k.gap_stats.p;
             ga.ev_mask = k.gap_slots - 1; ga.max_gap = k.gap_g;
             HIP_TRY(c, hipMemsetAsync(k.gap_ncand.p, 0, sizeof(uint32_t), c->tstream));
-            hipLaunchKernelGGL(rescue_count_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+            if (k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+            else hipLaunchKernelGGL(rescue_count_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
             hipLaunchKernelGGL(rescue_gap_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
             k.gap_launches++;
         }
         HIP_TRY(c, hipGetLastError());
         k.res_launches += 2;
+        if (k.rec_on) {      // (ec_reserve above has made room for this merge too: its bound is over both)
+            RescueEcArgs ea{};
+            ea.r = ra; ea.s = sa;
+            HIP_TRY(c, s->ct.d_rec_bits.reserve((size_t)k.rec_rows * k.rec_bw));
+            HIP_TRY(c, s->ct.d_rec_slow.reserve(1));
+            HIP_TRY(c, hipMemsetAsync(s->ct.d_rec_slow.p, 0, sizeof(uint32_t), c->tstream));
+            ea.bits = s->ct.d_rec_bits.p; ea.n_slow = s->ct.d_rec_slow.p; ea.stats = k.rec_stats.p;
+            ea.rows = k.rec_rows; ea.bw = k.rec_bw;
+            const dim3 gc(grid_for(s->n_reads));
+            hipLaunchKernelGGL(rescue_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
+            hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
+            hipLaunchKernelGGL(rescue_ec_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p);
+            HIP_TRY(c, hipGetLastError());
+            k.rec_launches += 3;
+        }
     }
     return GROOT_OK;
 }
@@ -436,6 +491,7 @@ int counters_fetch(groot_ctx *c, Slot *s)
         HIP_TRY(c, hipMemcpyAsync(&h->acov_state, s->ct.d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
         HIP_TRY(c, hipMemcpyAsync(&h->acov_fill, c->ct.acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     }
+    if (c->ct.rec_on) HIP_TRY(c, hipMemcpyAsync(&h->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     return GROOT_OK;
 }
 
@@ -452,6 +508,8 @@ int counters_collect(groot_ctx *c, Slot *s, bool redone)
     }
     if (!c->ct.ec_on || !s->n_reads) return GROOT_OK;
     if (int rc = ec_collect(c, s, redone)) return rc;
+    if (c->ct.rec_on)
+        if (int rc = rec_collect(c, s, redone)) return rc;
     return c->ct.acov_on ? acov_collect(c, s, redone) : GROOT_OK;
 }
 
@@ -523,6 +581,13 @@ int groot_hip_coverage_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ct.cov_starts.p, 0, slots * sizeof(unsigned long long)));
     HIP_TRY(c, hipMemset(c->ct.cov_ends.p, 0, slots * sizeof(unsigned long long)));
     return GROOT_OK;
+}
+
+// rescued reads in the equivalence classes go off (with mismatch rescue, or with the classes): nothing of it stays on the device
+static void rec_release(Counters &k)
+{
+    k.rec_path_bit.release(); k.rec_dstar.release(); k.rec_stats.release();
+    k.rec_on = false; k.rec_rows = k.rec_bw = 0; k.rec_slow = 0;
 }
 
 // ---- shared reads (kernels_shared.hpp) -------------------------------------------------------------------------------
@@ -646,6 +711,7 @@ int groot_hip_ec_enable(groot_ctx *c, int on)
     if (!on) {
         if (c->ct.acov_on)
             if (int rc = groot_hip_acov_enable(c, 0)) return rc;     // (its tuples are keyed by this table's serials)
+        rec_release(c->ct);                                          // (the rescued reads' sets have no table to go to)
         c->ct.ec.release(); c->ct.ec_fill.release();
         c->ct.ec_host.clear();
         c->ct.ec_on = false;
@@ -777,6 +843,10 @@ int groot_hip_ec_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ct.ec_fill.p, 0, sizeof(uint32_t)));
     c->ct.ec_fill_known = c->ct.ec_grows = c->ct.ec_slow_reads = 0;
     c->ct.ec_host.clear();
+    if (c->ct.rec_on) {                    // (the rescued reads are counted with the classes they are in)
+        HIP_TRY(c, hipMemset(c->ct.rec_stats.p, 0, kRescueEcStats * sizeof(unsigned long long)));
+        c->ct.rec_slow = 0;
+    }
     if (c->ct.pairs_on) HIP_TRY(c, hipMemset(c->ct.sh_stats.p + kSharedPairStats, 0, (kSharedStats - kSharedPairStats) * sizeof(unsigned long long)));
     return groot_hip_acov_reset(c);     // (the serials start again: its tuples would name other classes)
 }
@@ -796,6 +866,7 @@ int groot_hip_acov_enable(groot_ctx *c, int on)
     }
     if (c->ct.acov_on) return GROOT_OK;
     if (c->ct.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "assigned coverage with paired-end units is not supported");
+    if (c->ct.rec_on) return fail(c, GROOT_E_UNSUPPORTED, "assigned coverage weighs records, and a rescued read in the equivalence classes has none (groot_hip_rescue_ec_enable)");
     if (int rc = groot_hip_ec_enable(c, 1)) return rc;
     uint32_t cap = 1;
     while (cap < (c->kn.acov_slots ? std::max<uint32_t>(c->kn.acov_slots, 2u) : (1u << 20))) cap <<= 1;
@@ -1002,6 +1073,7 @@ int groot_hip_pairs_enable(groot_ctx *c, int on)
     if (!idle(c)) return fail(c, GROOT_E_STATE, "pairing can only be switched while nothing is in flight");
     if (on && c->ct.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assigned coverage are not supported");
     if (on && c->ct.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assignment are not supported (groot_hip_assign_enable)");
+    if (on && c->ct.rec_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with rescued reads in the equivalence classes are not supported: mates are rescued one by one (groot_hip_rescue_ec_enable)");
     c->ct.pairs_on = on != 0;
     if (c->ct.sh_on || c->ct.ec_on) {     // (else there is nothing to zero: sh_common_alloc zeroes the counts when either comes on)
         HIP_TRY(c, hipSetDevice(c->device));
@@ -1046,6 +1118,7 @@ static hipError_t gap_zero(Counters &k)
 static void rescue_release(Counters &k)
 {
     gap_release(k);                        // (gapped rescue looks at what rescue leaves: off with it)
+    rec_release(k);                        // (and so do the rescued reads in the equivalence classes)
     for (auto *b : {&k.res_text, &k.res_tag, &k.res_cand, &k.res_ncand}) b->release();
     for (auto *b : {&k.res_rbuf, &k.res_starts, &k.res_ends, &k.res_alt, &k.res_stats}) b->release();
     k.res_path.release(); k.res_tab.release(); k.res_occ.release(); k.res_base.release();
@@ -1288,6 +1361,58 @@ int groot_hip_gap_reset(groot_ctx *c)
     if (!c->ct.gap_on) return GROOT_OK;
     if (int rc = drain(c)) return rc;
     HIP_TRY(c, gap_zero(c->ct));
+    return GROOT_OK;
+}
+
+// ---- rescued reads in the equivalence classes (kernels_rescue_ec.hpp; the definition is in groot_hip.h) ---------------------
+int groot_hip_rescue_ec_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!on) {
+        rec_release(k);
+        return GROOT_OK;
+    }
+    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: mismatch rescue is off (groot_hip_rescue_enable)");
+    if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: equivalence classes are off (groot_hip_ec_enable)");
+    if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with paired-end units are not supported: mates are rescued one by one");
+    if (k.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with assigned coverage are not supported: a rescued read has no record to weigh");
+    if (k.rec_on) return GROOT_OK;
+    const uint32_t n_paths = (uint32_t)k.h_len.size(), R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    std::vector<uint2> pb(n_paths);
+    for (uint32_t g = 0; g + 1 < k.h_gpo.size(); g++)
+        for (uint32_t p = k.h_gpo[g]; p < std::min(k.h_gpo[g + 1], n_paths); p++) pb[p] = make_uint2(g, p - k.h_gpo[g]);
+    k.rec_bw = std::max<uint32_t>((n_paths + 63u) / 64u, 1u);
+    // a batch has at most max_batch_reads slow rescued reads; below that, what the byte budget holds (GROOT_RESCUE_EC_BYTES per slot)
+    k.rec_rows = c->kn.rescue_ec_rows ? c->kn.rescue_ec_rows : (uint32_t)std::max<uint64_t>(GROOT_RESCUE_EC_BYTES / (8ull * k.rec_bw), 1);
+    k.rec_rows = std::min(k.rec_rows, R);
+    hipError_t e = upload(k.rec_path_bit, pb.data(), pb.size());
+    if (e == hipSuccess) e = k.rec_dstar.alloc(R);
+    if (e == hipSuccess) e = k.rec_stats.alloc(kRescueEcStats);
+    if (e == hipSuccess) e = hipMemset(k.rec_stats.p, 0, kRescueEcStats * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        rec_release(k);
+        return fail(c, GROOT_E_DEVICE, "rescued reads in the equivalence classes: %s", hipGetErrorString(e));
+    }
+    k.rec_slow = 0;
+    k.rec_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_ec_stats(groot_ctx *c, groot_rescue_ec_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kRescueEcStats] = {};
+    if (c->ct.rec_on) {
+        if (int rc = drain(c)) return rc;
+        HIP_TRY(c, hipMemcpy(st, c->ct.rec_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    }
+    out->slow_reads = c->ct.rec_on ? c->ct.rec_slow : 0;
+    out->reads = st[0] + out->slow_reads;
+    out->rows = c->ct.rec_on ? c->ct.rec_rows : 0;
+    out->launches = c->ct.rec_launches;
     return GROOT_OK;
 }
 

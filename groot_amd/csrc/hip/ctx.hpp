@@ -73,6 +73,7 @@ struct Knobs {
          shared_slow = false, serial_tail = false, assign_global = false;
     uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
     uint32_t acov_slots = 0;               // GROOT_TEST_ACOV_SLOTS: initial slots of the assigned-coverage table (0 = the default)
+    uint32_t rescue_ec_rows = 0;           // GROOT_TEST_RESCUE_EC_ROWS: bitmaps of slow rescued reads per batch (0 = from the byte budget)
     static Knobs read()
     {
         Knobs k;
@@ -87,6 +88,7 @@ struct Knobs {
         k.assign_global = getenv("GROOT_TEST_ASSIGN_GLOBAL") != nullptr;  // assignment: alpha is read from global memory even when it fits in LDS
         if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         if (const char *e = getenv("GROOT_TEST_ACOV_SLOTS")) k.acov_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
+        if (const char *e = getenv("GROOT_TEST_RESCUE_EC_ROWS")) k.rescue_ec_rows = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         return k;
     }
 };
@@ -127,6 +129,7 @@ struct CounterStatus {
     uint32_t ec_fill;                      // ... and the table's fill behind this batch's merge
     uint32_t acov_state;                   // assigned coverage: SlotCounters::d_acov_state[0]
     uint32_t acov_fill;                    // ... and its table's fill
+    uint32_t rec_slow;                     // rescued reads in the ECs: the batch's slow rescued reads (SlotCounters::d_rec_slow[0])
 };
 
 struct SlotCounters {
@@ -139,6 +142,8 @@ struct SlotCounters {
     PinBuf<uint32_t> h_best;
     PinBuf<uint8_t> h_mapq;
     bool assigned = false;                 // the batch went through assign_kernel: h_best / h_mapq are its
+    DevBuf<unsigned long long> d_rec_bits; // rescued reads in the ECs: [rec_rows][rec_bw] the path bitmaps of the batch's slow rescued reads, read at collect
+    DevBuf<uint32_t> d_rec_slow;           // [0] their number, with or without a bitmap (rescue_ec_slow_kernel)
 };
 
 struct Counters {
@@ -207,6 +212,16 @@ struct Counters {
     DevBuf<uint32_t> gap_cand, gap_ncand;
     DevBuf<unsigned long long> gap_starts, gap_ends, gap_key, gap_cnt, gap_stats;   // report coverage's layout; the event table
     uint64_t gap_launches = 0;             // rescue_gap_kernel launches since open (stays put while it is off)
+    // rescued reads in the equivalence classes (groot_hip_rescue_ec_*, kernels_rescue_ec.hpp): needs mismatch rescue and equivalence classes
+    // on.  rescue_count_ec_kernel also writes every rescued read's path set as a row, three kernels behind it fold the rows into the
+    // table of ECs; the sets in too many graphs come back as bitmaps and are folded on the host at collect.  Nothing on the device while off.
+    bool rec_on = false;
+    uint32_t rec_rows = 0, rec_bw = 0;     // bitmaps per batch (fixed at enable), words per bitmap
+    DevBuf<uint2> rec_path_bit;            // RescueArgs::path_bit
+    DevBuf<uint8_t> rec_dstar;             // RescueArgs::dstar
+    DevBuf<unsigned long long> rec_stats;  // [kRescueEcStats]
+    uint64_t rec_slow = 0;                 // slow rescued reads folded at collect since enable / groot_hip_ec_reset
+    uint64_t rec_launches = 0;             // kernels launched for it since open, rescue_count_ec_kernel not among them (it counts as rescue's)
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

@@ -16,6 +16,8 @@
 //                      path), alt as four counters (A, C, G, T) per slot.
 //                      rescue_count_kernel<true> (gapped rescue on: kernels_gap.hpp) also hands on the candidates it leaves unplaced;
 //                      <false> is the kernel without that, and the only one launched while gapped rescue is off.
+//                      Both are rescue_count_body with a sink that does nothing; rescue_count_ec_kernel (kernels_rescue_ec.hpp: rescued
+//                      reads in the equivalence classes) is the same body with a sink that keeps the paths of the kept placements.
 // Integer sums only: the tables do not depend on the order of the candidates, of the wavefronts or of the batches.
 #pragma once
 
@@ -28,6 +30,7 @@ namespace groot {
 // the batch keeps to max_batch_bases)
 constexpr uint32_t kRescueStats = 8;
 constexpr uint32_t kRescueNone = 0xFFFFFFFFu;
+constexpr uint8_t kRescueUnplaced = 0xFFu;      // RescueArgs::dstar of a candidate that is not rescued
 constexpr unsigned long long kRescueOdd = 0x5555555555555555ull;
 
 struct RescueArgs {
@@ -47,6 +50,19 @@ struct RescueArgs {
     // gapped rescue (kernels_gap.hpp; rescue_count_kernel<true> only): the candidates left unplaced that are long enough for a gap
     uint32_t *gcand, *n_gcand;     // [n_reads] the gap candidates handed on, their number
     unsigned long long *gstats;    // GapArgs::stats
+    // rescued reads in the equivalence classes (kernels_rescue_ec.hpp; rescue_count_ec_kernel and the kernels behind it only)
+    const uint2 *path_bit;         // [n_paths] {graph of global path p, p's bit in that graph's path sets}
+    uint32_t *set_graph;           // SharedArgs::set_graph / set_mask: row r is free behind shared_expand_kernel
+    uint64_t *set_mask;
+    uint8_t *dstar;                // [n_reads] d* of candidate i, kRescueUnplaced when it is not rescued
+    uint32_t pw, max_segs;         // SharedArgs::pw, max_segs
+};
+
+// what rescue_place tells of every kept placement beyond the dense tables: nothing here, the path to the read's set row in
+// kernels_rescue_ec.hpp (RescueRow)
+struct RescueNoSink {
+    __device__ __forceinline__ void kept(const RescueArgs &, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void done(const RescueArgs &, uint32_t, uint32_t, uint32_t) {}
 };
 
 // the workgroup's sums of up to kRescueStats per-thread counts, one atomic each per wavefront
@@ -149,7 +165,8 @@ __device__ __forceinline__ uint32_t rescue_distance(const RescueArgs &a, const u
 
 // the placements of candidate r: sweep 1 keeps the smallest distance, sweep 2 adds the placements at it to the tables.  -> d*, M + 1 when
 // there is no placement; hit: one of its blocks is in the table at all
-__device__ __forceinline__ uint32_t rescue_place(const RescueArgs &a, uint32_t r, uint32_t &len, uint32_t (&st)[4], bool &hit)
+template <class Sink>
+__device__ __forceinline__ uint32_t rescue_place(const RescueArgs &a, uint32_t r, uint32_t &len, uint32_t (&st)[4], bool &hit, Sink &sink)
 {
     const uint32_t M = a.max_mismatch;
     const uint64_t off0 = a.seq_off[0];
@@ -178,6 +195,7 @@ __device__ __forceinline__ uint32_t rescue_place(const RescueArgs &a, uint32_t r
                     if (sweep == 0) { best = min(best, d); continue; }
                     if (d != best) continue;
                     st[3]++;
+                    sink.kept(a, r, oc.x);
                     const uint64_t at = a.slot_base[oc.x] + pi.z + to;
                     atomicAdd(a.starts + at, 1ull);
                     atomicAdd(a.ends + at + len, 1ull);
@@ -196,7 +214,8 @@ __device__ __forceinline__ uint32_t rescue_place(const RescueArgs &a, uint32_t r
 
 // kGap: a candidate that stays unplaced and has len >= A (M + 3) joins the gap candidates (one ballot and one atomic per wavefront), if
 // one of its blocks had a table hit at all: a gapped placement needs an occurrence of a block.  The gap stats count by the definition.
-template <bool kGap> __global__ __launch_bounds__(kBlock) void rescue_count_kernel(RescueArgs a)
+// Sink: RescueNoSink, or RescueRow (kernels_rescue_ec.hpp), which also gets d* of every candidate
+template <bool kGap, class Sink> __device__ __forceinline__ void rescue_count_body(const RescueArgs &a)
 {
     if (a.ctr->flags & kCovSkipFlags) return;
     const uint32_t n = min(*a.n_cand, a.n_reads), M = a.max_mismatch;
@@ -208,7 +227,9 @@ template <bool kGap> __global__ __launch_bounds__(kBlock) void rescue_count_kern
         if (i < n) {
             uint32_t len;
             bool hit = false;
-            const uint32_t best = rescue_place(a, r, len, st, hit);
+            Sink sink{};
+            const uint32_t best = rescue_place(a, r, len, st, hit, sink);
+            sink.done(a, r, i, best);
             if (best <= M) st[1]++;
             if (best == 0) st[2]++;
             if (kGap && best > M) {
@@ -237,5 +258,7 @@ template <bool kGap> __global__ __launch_bounds__(kBlock) void rescue_count_kern
         rescue_add_stats(a.gstats, gst, gwhere);
     }
 }
+
+template <bool kGap> __global__ __launch_bounds__(kBlock) void rescue_count_kernel(RescueArgs a) { rescue_count_body<kGap, RescueNoSink>(a); }
 
 } // namespace groot

@@ -272,6 +272,21 @@ __global__ __launch_bounds__(kBlock) void shared_gather_paired_kernel(SharedArgs
     block_add(single, &a.batch[5]);
 }
 
+// row r into the batch's table: the first row of a set owns a slot, the others add 1 to its count.  -> r owns its slot
+// (also what kernels_rescue_ec.hpp does with the rows of the rescued reads, behind shared_expand_kernel)
+__device__ __forceinline__ bool shared_insert_row(const SharedArgs &a, uint32_t r)
+{
+    // the table holds at most n_reads owners in >= 2 n_reads slots: the probe ends
+    for (uint32_t slot = (uint32_t)shared_hash(a, r) & a.tab_mask;; slot = (slot + 1) & a.tab_mask) {
+        uint32_t cur = __hip_atomic_load(a.tab_rep + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == kSharedEmpty) {
+            cur = atomicCAS(a.tab_rep + slot, kSharedEmpty, r);
+            if (cur == kSharedEmpty) { atomicAdd(a.tab_cnt + slot, 1u); return true; }
+        }
+        if (same_set(a, cur, r)) { atomicAdd(a.tab_cnt + slot, 1u); return false; }
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void shared_insert_kernel(SharedArgs a)
 {
     if (!shared_live(a)) return;
@@ -281,15 +296,7 @@ __global__ __launch_bounds__(kBlock) void shared_insert_kernel(SharedArgs a)
         if (!read_start(a, t0)) continue;
         const uint32_t r = a.trav[t0].read_id - a.first_read_id;
         if (a.set_graph[(size_t)r * kSharedSegs] == kSharedEmpty) continue;
-        // the table holds at most n_reads owners in >= 2 n_reads slots: the probe ends
-        for (uint32_t slot = (uint32_t)shared_hash(a, r) & a.tab_mask;; slot = (slot + 1) & a.tab_mask) {
-            uint32_t cur = __hip_atomic_load(a.tab_rep + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == kSharedEmpty) {
-                cur = atomicCAS(a.tab_rep + slot, kSharedEmpty, r);
-                if (cur == kSharedEmpty) { atomicAdd(a.tab_cnt + slot, 1u); owned++; break; }
-            }
-            if (same_set(a, cur, r)) { atomicAdd(a.tab_cnt + slot, 1u); break; }
-        }
+        owned += shared_insert_row(a, r);
     }
     block_add(owned, &a.batch[1]);
 }

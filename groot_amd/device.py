@@ -599,6 +599,18 @@ class Aligner:
     def gap_reset(self):
         self._check(lib().groot_hip_gap_reset(self._h))
 
+    # ---- rescued reads in the equivalence classes (groot_hip_rescue_ec_*) -----------------------------
+    def rescue_ec_enable(self, on=True):
+        """from now on a rescued read counts in the equivalence classes with the set of paths it was placed on (include/groot_hip.h,
+        "rescued reads in the equivalence classes").  Needs rescue_enable and ec_enable first.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_rescue_ec_enable(self._h, C.c_int(1 if on else 0)))
+
+    def rescue_ec_stats(self):
+        """groot_hip_rescue_ec_stats: {"reads", "slow_reads", "rows", "launches"}; zeros while off, but for launches"""
+        v = (C.c_uint64 * 4)()
+        self._check(lib().groot_hip_rescue_ec_stats(self._h, v))
+        return dict(zip(("reads", "slow_reads", "rows", "launches"), (int(x) for x in v)))
+
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):
         seq = np.ascontiguousarray(seq_concat, dtype=np.uint8)

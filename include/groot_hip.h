@@ -562,6 +562,41 @@ int groot_hip_gap_stats(groot_ctx *ctx, groot_gap_stats *out);
 /* Zeroes the gap tables and stats (after waiting for everything in flight).  No-op when off. */
 int groot_hip_gap_reset(groot_ctx *ctx);
 
+/* ---- rescued reads in the equivalence classes ---------------------------------------------------------------------------
+ * The equivalence classes count S(r), and the aligner is exact-match: a read with one sequencing error has no record and is in no
+ * class, though mismatch rescue knows where it lies.  With this on, a rescued read is a unit of the classes with the set of paths it
+ * was placed on.  The definition:
+ *
+ *   S(r)   as in "equivalence classes": the global paths with a record of r.
+ *   R(r)   for a read r that is RESCUED under "mismatch rescue" (a candidate with d*(r) <= M): the set of global paths p for which r has
+ *          a KEPT placement (p, strand, x) -- any strand, any x, each p once.  Not defined for any other read.
+ *   S+(r)  = S(r) when r has a record;  R(r) when r is rescued;  empty otherwise.   (The two cases exclude each other: a candidate has
+ *          no record.)
+ *
+ * With the feature on, the run's ECs are the distinct non-empty S+(r) with their read counts; a rescued read and an exact read with
+ * the same set are one EC.  Nothing else changes: records, BAM, GFA, weights, coverage, shared reads, the rescue tables, the gap tables
+ * (a read placed with a gap is in no class), and every stat that exists today.  The ECs depend on the reads and the index alone: not on
+ * batch size, pipeline depth, align-stage variant, results_on_device, or how the reads are spread over ctxs; the merge of several ctxs
+ * is a sum by set.  A pass that collect redoes counts once, a batch under the skip flags of report coverage counts nothing.
+ * Off by default: then no allocation, launch or sync, and rescue_count_kernel is the one of mismatch rescue alone. */
+#define GROOT_RESCUE_EC_BYTES (8ull << 20)   /* per pipeline slot: the bitmaps (n_paths bits each) of a batch's rescued reads in more than 4 graphs */
+typedef struct groot_rescue_ec_stats {
+    uint64_t reads;       /* rescued reads added to the classes since enable / groot_hip_ec_reset */
+    uint64_t slow_reads;  /* those among them whose set lies in more than 4 graphs (1 under GROOT_TEST_SHARED_SLOW): folded on the host from bitmaps */
+    uint64_t rows;        /* bitmaps per batch: min(max_batch_reads, GROOT_RESCUE_EC_BYTES / (8 ceil(n_paths / 64))), or GROOT_TEST_RESCUE_EC_ROWS; 0 while off */
+    uint64_t launches;    /* kernels launched for it since open, whether it is on now or not (rescue_count_ec_kernel counts in groot_rescue_stats.launches) */
+} groot_rescue_ec_stats;
+/* on != 0: on.  Needs mismatch rescue and equivalence classes on (GROOT_E_STATE otherwise), and nothing in flight (GROOT_E_STATE).
+ * GROOT_E_UNSUPPORTED beside pairing or assigned coverage, whichever is enabled second.  Switching mismatch rescue or the equivalence
+ * classes off switches it off too.  groot_hip_rescue_enable with another M and groot_hip_rescue_reset leave the classes alone;
+ * groot_hip_ec_reset zeroes them, the rescued reads in them and these stats.  A batch with more rescued reads in more than 4 graphs than
+ * `rows` fails at collect with GROOT_E_NOSPACE (the message names GROOT_TEST_RESCUE_EC_ROWS): no read is dropped silently.
+ * groot_hip_ec_export and groot_hip_ec_stats then count the rescued reads too (reads, distinct); slow_reads there stays the reads with
+ * a record.  Device memory: 8 bytes per path, 1 byte per read of a batch, `rows` bitmaps per pipeline slot. */
+int groot_hip_rescue_ec_enable(groot_ctx *ctx, int on);
+/* Waits for everything in flight; zeros while off, but for launches. */
+int groot_hip_rescue_ec_stats(groot_ctx *ctx, groot_rescue_ec_stats *out);
+
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
  * the device, bit for bit in boot_count, alpha and iterations.  Quoted from there: draw j (0 <= j < n_draws; n_draws = 0 means N, the sum
