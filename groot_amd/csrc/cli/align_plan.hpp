@@ -8,6 +8,7 @@ struct AlignPlan {
     bool report = false, shared = false, abundance = false, calls = false, assign = false, rarefy = false, variants = false, indels = false;
     bool rescue = false;     // mismatch rescue runs: --variants, --indels or --abundanceRescued
     bool ab_rescued = false; // --abundanceRescued: the rescued reads join the equivalence classes
+    bool calls_rescued = false; // --callsRescued: and their kept placements the pileup of --calls
     bool coverage = false;   // report coverage is counted: --report, or --variants / --indels for its exact depth
     bool frags = false;      // --paired / --interleaved
     bool counters = false;   // a ctx carries switches: set at open and reopen, harvested before it closes
@@ -94,10 +95,17 @@ int plan_align(const Args &a, AlignPlan *p)
         return refuse("--gapEventSlots is a number of table slots, a power of two: %lld", a.gap_event_slots);
     // --abundanceRescued: checked behind everything above
     if (p->ab_rescued && !p->abundance) return refuse("--abundanceRescued adds the rescued reads to the classes --abundance estimates from: it needs --abundance");
-    if (p->ab_rescued && p->calls) return refuse("--abundanceRescued cannot be combined with --calls: its pileup weighs records, and a rescued read has none");
+    if (p->ab_rescued && p->calls && !a.calls_rescued) return refuse("--abundanceRescued cannot be combined with --calls: its pileup weighs records, and a rescued read has none");
     if (p->ab_rescued && p->frags)
         return refuse("--abundanceRescued cannot be combined with %s yet: mates are rescued one by one, and a fragment's set has no rule for them",
                       a.paired ? "--paired" : "--interleaved");
+    // --callsRescued: checked behind everything above
+    if (a.calls_rescued && !(p->calls && p->ab_rescued))
+        return refuse("--callsRescued puts the reads --abundanceRescued adds to the classes into the pileup of --calls: it needs both --calls and --abundanceRescued");
+    if (a.call_slots_given && !a.calls_rescued) return refuse("--callSlots is the size the table of --callsRescued starts with: it needs it");
+    if (a.call_slots_given && (a.call_slots < 1 || a.call_slots > (1ll << 31) || (a.call_slots & (a.call_slots - 1))))
+        return refuse("--callSlots is a number of table slots, a power of two up to 2^31: %lld", a.call_slots);
+    p->calls_rescued = a.calls_rescued;
     p->coverage = p->report || p->variants || p->indels;
     p->counters = p->report || p->abundance || p->assign || p->rescue;
     return 0;

@@ -73,6 +73,9 @@ struct Args {
     double variant_min_share = 0.1;        // --variantMinShare S
     bool rescue_given = false, variant_min_given = false;
     bool abundance_rescued = false;          // --abundanceRescued: the reads mismatch rescue places join the equivalence classes of --abundance
+    bool calls_rescued = false;              // --callsRescued: with --calls and --abundanceRescued, the rescued reads' placements join the pileup
+    long long call_slots = 1ll << 24;        // --callSlots N (a power of two): the slots the assigned-coverage table starts with under --callsRescued
+    bool call_slots_given = false;
     std::string indels_out;                // --indels: the gaps that the reads neither aligned nor rescued show, placed with one gap of up to --rescueGap bases
     long rescue_gap = 3;                   // --rescueGap G (1..8)
     long long gap_event_slots = 0;         // --gapEventSlots N (a power of two; 0: the library's default)

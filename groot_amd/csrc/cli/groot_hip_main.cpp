@@ -35,6 +35,7 @@ void usage()
             "                  [--memo auto|on|off|<MiB>]   (the device's memo of indexed strings; auto: on for inputs of 20 GB and more)\n"
             "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0] [--abundanceRescued [--rescue 2]]]\n"
             "                  [--noBam] [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
+            "                  [--abundanceRescued --calls c.tsv --callsRescued [--callSlots 16777216]]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
@@ -45,7 +46,9 @@ void usage()
             "                   --abundance: `name reads em_reads fraction` per ARG with em_reads >= --abundanceMin, by EM over the reads' path sets;\n"
             "                   --abundanceRescued: with --abundance, a read WITHOUT an exact alignment that mismatch rescue places with up to --rescue (1..3)\n"
             "                   substitutions counts too, with the set of ARGs it was placed on: `reads` then counts the reads that lie on the ARG exactly or\n"
-            "                   rescued, and the EM, --bootstraps and --rarefy see them all.  Not with --calls, --paired or --interleaved;\n"
+            "                   rescued, and the EM, --bootstraps and --rarefy see them all.  Not with --paired or --interleaved, and with --calls only beside\n"
+            "                   --callsRescued: then every placement of a rescued read is a record of the pileup too, over the bases it covers; --callSlots: the\n"
+            "                   slots the pileup's table on the GPU starts with, a power of two (a run whose rescued records find no room fails and says so);\n"
             "                   --bootstraps: with --abundance, four more columns `boot_mean boot_sd boot_lo boot_hi` from B replicates of the reads\n"
             "                   resampled with replacement (--bootSeed), each with its own EM, drawn and fitted on the GPU;\n"
             "                   --calls: with --abundance, per line of the abundance file `name em_reads length depth breadth cigar called`: the pileup of\n"
@@ -147,6 +150,13 @@ Args parse(int argc, char **argv)
             char *end = nullptr;
             if (f == "--rescueGap") { a.rescue_gap = strtol(t.c_str(), &end, 10); a.rescue_gap_given = true; }
             else { a.gap_event_slots = strtoll(t.c_str(), &end, 10); a.gap_slots_given = true; }
+            if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
+        }
+        else if (a.cmd == "align" && f == "--callsRescued") a.calls_rescued = true;
+        else if (a.cmd == "align" && f == "--callSlots") {
+            const std::string t = v();
+            char *end = nullptr;
+            a.call_slots = strtoll(t.c_str(), &end, 10); a.call_slots_given = true;
             if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
         }
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;

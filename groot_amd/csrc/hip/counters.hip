@@ -2,7 +2,7 @@
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
 // draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp), rescued reads in the equivalence
-// classes (kernels_rescue_ec.hpp).  One of the six translation units of
+// classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <hip/hip_runtime.h>
 
@@ -28,6 +28,7 @@
 #include "kernels_gap.hpp"
 #include "kernels_rescue.hpp"
 #include "kernels_rescue_ec.hpp"
+#include "kernels_rescue_acov.hpp"
 #include "kernels_shared.hpp"
 
 using namespace groot;
@@ -326,7 +327,20 @@ static int rec_collect(groot_ctx *c, Slot *s, bool refetch)
     std::vector<uint64_t> bits((size_t)n_slow * k.rec_bw);
     HIP_TRY(c, hipMemcpy(bits.data(), s->ct.d_rec_bits.p, bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     const uint32_t n_paths = (uint32_t)k.h_len.size();
+    // rescued reads in assigned coverage: the log of these reads' kept placements, checked before anything is folded
+    const bool logged = k.rac_on && s->ct.d_rac_nlog.p;
+    std::vector<uint4> log;
+    if (logged) {
+        if (refetch) HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const uint32_t n_log = s->ct.h_status.p->rac_log;
+        if (n_log > k.rac_log_cap)
+            return fail(c, GROOT_E_NOSPACE, "rescued reads in assigned coverage: a batch's rescued reads whose sets lie in more graphs than a row holds have %u kept "
+                        "placements, and the log has room for %u (GROOT_TEST_RESCUE_ACOV_LOG)", n_log, k.rac_log_cap);
+        log.resize(n_log);
+        if (n_log) HIP_TRY(c, hipMemcpy(log.data(), s->ct.d_rac_log.p, log.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+    }
     std::vector<uint32_t> ids;
+    std::vector<std::vector<uint32_t>> row_ids(logged ? n_slow : 0);
     for (uint32_t i = 0; i < n_slow; i++) {
         ids.clear();
         for (uint32_t w = 0; w < k.rec_bw; w++)
@@ -335,8 +349,14 @@ static int rec_collect(groot_ctx *c, Slot *s, bool refetch)
                 if (id < n_paths) ids.push_back(id);
             }
         if (!ids.empty()) k.ec_host[ids]++;
+        if (logged) row_ids[i] = ids;
     }
     k.rec_slow += n_slow;
+    for (const uint4 &e : log) {           // (bitmap row, path, X, last): into the host map under the row's ID list, as ec_collect folds the exact slow reads' records
+        if (e.x >= n_slow || row_ids[e.x].empty()) return fail(c, GROOT_E_DEVICE, "rescued reads in assigned coverage: a logged placement names bitmap %u of %u", e.x, n_slow);
+        k.acov_host[row_ids[e.x]][{e.y, e.z, e.w}]++;
+        k.rac_host_records++;
+    }
     return GROOT_OK;
 }
 
@@ -467,9 +487,25 @@ int counters_launch(groot_ctx *c, Slot *s)
             ea.bits = s->ct.d_rec_bits.p; ea.n_slow = s->ct.d_rec_slow.p; ea.stats = k.rec_stats.p;
             ea.rows = k.rec_rows; ea.bw = k.rec_bw;
             const dim3 gc(grid_for(s->n_reads));
-            hipLaunchKernelGGL(rescue_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
-            hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
-            hipLaunchKernelGGL(rescue_ec_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p);
+            if (!k.rac_on) {
+                hipLaunchKernelGGL(rescue_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
+                hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
+                hipLaunchKernelGGL(rescue_ec_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p);
+            } else {     // rescued reads in assigned coverage (kernels_rescue_acov.hpp): claim and add in one pass, here and never at collect
+                RescueAcovArgs aa{};
+                HIP_TRY(c, s->ct.d_rac_log.reserve(std::max<uint32_t>(k.rac_log_cap, 1u)));
+                HIP_TRY(c, s->ct.d_rac_nlog.reserve(1));
+                HIP_TRY(c, hipMemsetAsync(s->ct.d_rac_nlog.p, 0, sizeof(uint32_t), c->tstream));
+                aa.e = ea; aa.tab_ser = k.acov_tab_ser.p; aa.cand_ser = k.rac_cand_ser.p; aa.fill = k.acov_fill.p; aa.stats = k.rac_stats.p;
+                aa.log = s->ct.d_rac_log.p; aa.n_log = s->ct.d_rac_nlog.p; aa.log_cap = k.rac_log_cap;
+                hipLaunchKernelGGL(rescue_acov_slow_kernel, gc, dim3(kBlock), 0, c->tstream, aa);
+                hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
+                hipLaunchKernelGGL(rescue_acov_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, k.acov_tab_ser.p);
+                hipLaunchKernelGGL(rescue_acov_serial_kernel, gc, dim3(kBlock), 0, c->tstream, aa);
+                hipLaunchKernelGGL(rescue_acov_clear_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, tab);
+                hipLaunchKernelGGL(rescue_acov_kernel, gc, dim3(kBlock), 0, c->tstream, aa, k.acov.table());
+                k.rac_launches += 3;
+            }
             HIP_TRY(c, hipGetLastError());
             k.rec_launches += 3;
         }
@@ -492,6 +528,7 @@ int counters_fetch(groot_ctx *c, Slot *s)
         HIP_TRY(c, hipMemcpyAsync(&h->acov_fill, c->ct.acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     }
     if (c->ct.rec_on) HIP_TRY(c, hipMemcpyAsync(&h->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    if (c->ct.rac_on) HIP_TRY(c, hipMemcpyAsync(&h->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     return GROOT_OK;
 }
 
@@ -588,6 +625,9 @@ static void rec_release(Counters &k)
 {
     k.rec_path_bit.release(); k.rec_dstar.release(); k.rec_stats.release();
     k.rec_on = false; k.rec_rows = k.rec_bw = 0; k.rec_slow = 0;
+    // (and with it the rescued reads in assigned coverage, which are keyed by these classes)
+    k.rac_cand_ser.release(); k.rac_stats.release();
+    k.rac_on = false; k.rac_log_cap = 0; k.rac_host_records = 0;
 }
 
 // ---- shared reads (kernels_shared.hpp) -------------------------------------------------------------------------------
@@ -858,6 +898,7 @@ int groot_hip_acov_enable(groot_ctx *c, int on)
     if (!idle(c)) return fail(c, GROOT_E_STATE, "assigned coverage can only be switched while nothing is in flight");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!on) {
+        if (c->ct.rac_on) rec_release(c->ct);     // (the rescued reads in it go, and the rescued classes that came on with them)
         c->ct.acov.release();
         for (auto *b : {&c->ct.acov_fill, &c->ct.acov_err, &c->ct.acov_tab_ser}) b->release();
         c->ct.acov_host.clear();
@@ -959,6 +1000,13 @@ int groot_hip_acov_export(groot_ctx *c, uint64_t *ec_off, uint32_t *ec_ids, uint
     std::map<std::vector<uint32_t>, uint64_t> m;
     std::vector<AcovTuple> tp;
     if (int rc = acov_gather(c, m, tp)) return rc;
+    if (c->ct.rac_on) {                    // (behind the drain of acov_gather)
+        uint64_t st[kRescueAcovStats] = {};
+        HIP_TRY(c, hipMemcpy(st, c->ct.rac_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+        if (st[kRescueAcovDropped])
+            return fail(c, GROOT_E_NOSPACE, "assigned coverage: %llu rescued records found no room in a table of %u slots, which grows between batches only: start it "
+                        "larger (min_slots of groot_hip_rescue_acov_enable, align --callSlots)", (unsigned long long)st[kRescueAcovDropped], c->ct.acov.cap);
+    }
     uint64_t ni = 0;
     for (const auto &kv : m) ni += kv.first.size();
     *n_ec = m.size();
@@ -1007,6 +1055,10 @@ int groot_hip_acov_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ct.acov_fill.p, 0, sizeof(uint32_t)));
     c->ct.acov_grows = c->ct.acov_slow_records = c->ct.acov_redone = 0;
     c->ct.acov_host.clear();
+    if (c->ct.rac_on) {                    // (the rescued records are counted with the table they are in)
+        HIP_TRY(c, hipMemset(c->ct.rac_stats.p, 0, kRescueAcovStats * sizeof(unsigned long long)));
+        c->ct.rac_host_records = 0;
+    }
     return GROOT_OK;
 }
 
@@ -1365,20 +1417,10 @@ int groot_hip_gap_reset(groot_ctx *c)
 }
 
 // ---- rescued reads in the equivalence classes (kernels_rescue_ec.hpp; the definition is in groot_hip.h) ---------------------
-int groot_hip_rescue_ec_enable(groot_ctx *c, int on)
+// rescue, the classes, no pairing: checked by the caller
+static int rec_alloc(groot_ctx *c)
 {
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
     Counters &k = c->ct;
-    if (!on) {
-        rec_release(k);
-        return GROOT_OK;
-    }
-    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: mismatch rescue is off (groot_hip_rescue_enable)");
-    if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: equivalence classes are off (groot_hip_ec_enable)");
-    if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with paired-end units are not supported: mates are rescued one by one");
-    if (k.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with assigned coverage are not supported: a rescued read has no record to weigh");
     if (k.rec_on) return GROOT_OK;
     const uint32_t n_paths = (uint32_t)k.h_len.size(), R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
     std::vector<uint2> pb(n_paths);
@@ -1398,6 +1440,73 @@ int groot_hip_rescue_ec_enable(groot_ctx *c, int on)
     }
     k.rec_slow = 0;
     k.rec_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_ec_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!on) {
+        rec_release(k);
+        return GROOT_OK;
+    }
+    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: mismatch rescue is off (groot_hip_rescue_enable)");
+    if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: equivalence classes are off (groot_hip_ec_enable)");
+    if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with paired-end units are not supported: mates are rescued one by one");
+    if (k.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with assigned coverage are not supported: a rescued read has no record to weigh");
+    return rec_alloc(c);
+}
+
+// ---- rescued reads in assigned coverage (kernels_rescue_acov.hpp; the definition is in groot_hip.h) --------------------------
+int groot_hip_rescue_acov_enable(groot_ctx *c, int on, uint64_t min_slots)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!on) {
+        if (k.rac_on) rec_release(k);      // (the rescued classes came on with it and cannot stay beside assigned coverage without it)
+        return GROOT_OK;
+    }
+    if (min_slots & (min_slots - 1)) return fail(c, GROOT_E_INVALID, "rescued reads in assigned coverage: min_slots = %llu is not a power of two", (unsigned long long)min_slots);
+    if (min_slots > (1ull << 31)) return fail(c, GROOT_E_INVALID, "rescued reads in assigned coverage: min_slots = %llu, at most 2^31 are supported", (unsigned long long)min_slots);
+    if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in assigned coverage with paired-end units are not supported: mates are rescued one by one");
+    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: mismatch rescue is off (groot_hip_rescue_enable)");
+    if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: equivalence classes are off (groot_hip_ec_enable)");
+    if (!k.acov_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: assigned coverage is off (groot_hip_acov_enable)");
+    if (k.acov.cap < min_slots)
+        if (int rc = acov_grow(c, (uint32_t)(min_slots / k.acov.cap))) return rc;
+    if (k.rac_on) return GROOT_OK;
+    if (int rc = rec_alloc(c)) return rc;
+    k.rac_log_cap = c->kn.rescue_acov_log ? c->kn.rescue_acov_log : (uint32_t)(GROOT_RESCUE_ACOV_BYTES / sizeof(uint4));
+    hipError_t e = k.rac_cand_ser.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
+    if (e == hipSuccess) e = k.rac_stats.alloc(kRescueAcovStats);
+    if (e == hipSuccess) e = hipMemset(k.rac_stats.p, 0, kRescueAcovStats * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        rec_release(k);
+        return fail(c, GROOT_E_DEVICE, "rescued reads in assigned coverage: %s", hipGetErrorString(e));
+    }
+    k.rac_host_records = 0;
+    k.rac_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_acov_stats(groot_ctx *c, groot_rescue_acov_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kRescueAcovStats] = {};
+    if (c->ct.rac_on) {
+        if (int rc = drain(c)) return rc;
+        HIP_TRY(c, hipMemcpy(st, c->ct.rac_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    }
+    out->host_records = c->ct.rac_on ? c->ct.rac_host_records : 0;
+    out->records = st[0] + out->host_records;
+    out->dropped = st[kRescueAcovDropped];
+    out->log_rows = c->ct.rac_on ? c->ct.rac_log_cap : 0;
+    out->launches = c->ct.rac_launches;
     return GROOT_OK;
 }
 

@@ -74,6 +74,7 @@ struct Knobs {
     uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
     uint32_t acov_slots = 0;               // GROOT_TEST_ACOV_SLOTS: initial slots of the assigned-coverage table (0 = the default)
     uint32_t rescue_ec_rows = 0;           // GROOT_TEST_RESCUE_EC_ROWS: bitmaps of slow rescued reads per batch (0 = from the byte budget)
+    uint32_t rescue_acov_log = 0;          // GROOT_TEST_RESCUE_ACOV_LOG: logged placements of slow rescued reads per batch (0 = from the byte budget)
     static Knobs read()
     {
         Knobs k;
@@ -89,6 +90,7 @@ struct Knobs {
         if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         if (const char *e = getenv("GROOT_TEST_ACOV_SLOTS")) k.acov_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         if (const char *e = getenv("GROOT_TEST_RESCUE_EC_ROWS")) k.rescue_ec_rows = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
+        if (const char *e = getenv("GROOT_TEST_RESCUE_ACOV_LOG")) k.rescue_acov_log = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 28);
         return k;
     }
 };
@@ -130,6 +132,7 @@ struct CounterStatus {
     uint32_t acov_state;                   // assigned coverage: SlotCounters::d_acov_state[0]
     uint32_t acov_fill;                    // ... and its table's fill
     uint32_t rec_slow;                     // rescued reads in the ECs: the batch's slow rescued reads (SlotCounters::d_rec_slow[0])
+    uint32_t rac_log;                      // rescued reads in assigned coverage: the kept placements of those reads (SlotCounters::d_rac_nlog[0])
 };
 
 struct SlotCounters {
@@ -144,6 +147,8 @@ struct SlotCounters {
     bool assigned = false;                 // the batch went through assign_kernel: h_best / h_mapq are its
     DevBuf<unsigned long long> d_rec_bits; // rescued reads in the ECs: [rec_rows][rec_bw] the path bitmaps of the batch's slow rescued reads, read at collect
     DevBuf<uint32_t> d_rec_slow;           // [0] their number, with or without a bitmap (rescue_ec_slow_kernel)
+    DevBuf<uint4> d_rac_log;               // rescued reads in assigned coverage: [rac_log_cap] (bitmap row, path, X, last) of those reads' kept placements, read at collect
+    DevBuf<uint32_t> d_rac_nlog;           // [0] their number, logged or not (rescue_acov_slow_kernel)
 };
 
 struct Counters {
@@ -222,6 +227,15 @@ struct Counters {
     DevBuf<unsigned long long> rec_stats;  // [kRescueEcStats]
     uint64_t rec_slow = 0;                 // slow rescued reads folded at collect since enable / groot_hip_ec_reset
     uint64_t rec_launches = 0;             // kernels launched for it since open, rescue_count_ec_kernel not among them (it counts as rescue's)
+    // rescued reads in assigned coverage (groot_hip_rescue_acov_*, kernels_rescue_acov.hpp): needs mismatch rescue, equivalence classes and
+    // assigned coverage on, and switches the rescued reads in the ECs on itself.  Every kept placement of a rescued read is a record of the
+    // assigned-coverage table; those of the reads with a bitmap come back in a log and are folded on the host at collect.
+    bool rac_on = false;
+    uint32_t rac_log_cap = 0;              // log entries per batch (fixed at enable)
+    DevBuf<uint32_t> rac_cand_ser;         // RescueAcovArgs::cand_ser (tail stream: one batch at a time, as the candidates are)
+    DevBuf<unsigned long long> rac_stats;  // [kRescueAcovStats]
+    uint64_t rac_host_records = 0;         // rescued records folded on the host since enable / groot_hip_acov_reset
+    uint64_t rac_launches = 0;             // kernels launched for it since open; the two that take the place of rec's count there
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

@@ -19,6 +19,8 @@
 // rescue_ec_merge_kernel   one thread per slot of that table: the owner's set into the run-wide table (ec_add, under an epoch of its
 //                          own: the batch's rescued sets are distinct within the launch, as ec_merge_kernel's are), then the slot is
 //                          cleared.  It writes neither the slot's list of exact slow reads nor assigned coverage's serials.
+// rescue_ec_slow_kernel and rescue_ec_merge_kernel are bodies with a sink / a switch that does nothing here; kernels_rescue_acov.hpp (rescued
+// reads in assigned coverage) instantiates them with a placement log and with the serials kept.
 // Integer sums only, and every kernel reads the pass's status word first: a pass collect redoes, or a batch that fails, adds nothing.
 #pragma once
 
@@ -84,8 +86,8 @@ struct RescueEcArgs {
     uint32_t rows, bw;             // bitmaps, words each: ceil(n_paths / 64)
 };
 
-// the kept placements of candidate read r at distance d = d*(r): f(global path) once per placement (rescue_place's second sweep without
-// the tables)
+// the kept placements of candidate read r at distance d = d*(r): f(global path, text offset of the read's first base) once per placement
+// (rescue_place's second sweep without the tables)
 template <class F> __device__ __forceinline__ void rescue_each_kept(const RescueArgs &a, uint32_t r, uint32_t d, F &&f)
 {
     const uint64_t o = a.seq_off[r];
@@ -103,7 +105,7 @@ template <class F> __device__ __forceinline__ void rescue_each_kept(const Rescue
                 const uint4 pi = a.path[oc.x];
                 const uint32_t rel = oc.y - pi.x;
                 if (rel < kRescueAnchor * j || rel - kRescueAnchor * j + len > pi.y) continue;
-                if (rescue_distance(a, rd, len, pi.x + rel - kRescueAnchor * j, j, d) == d) f(oc.x);
+                if (rescue_distance(a, rd, len, pi.x + rel - kRescueAnchor * j, j, d) == d) f(oc.x, rel - kRescueAnchor * j);
             }
         }
     }
@@ -112,7 +114,13 @@ template <class F> __device__ __forceinline__ void rescue_each_kept(const Rescue
 // candidate i of the batch is rescued: its row is written and dstar[i] holds d*
 __device__ __forceinline__ bool rescue_ec_rescued(const RescueEcArgs &a, uint32_t i) { return a.r.dstar[i] != kRescueUnplaced; }
 
-__global__ __launch_bounds__(kBlock) void rescue_ec_slow_kernel(RescueEcArgs a)
+// what rescue_ec_slow_body tells of every kept placement beyond the bitmap: nothing here, the placement to the slot's log in
+// kernels_rescue_acov.hpp (RescueAcovLog)
+struct RescueNoLog {
+    __device__ __forceinline__ void kept(const RescueEcArgs &, uint32_t, uint32_t, uint32_t, uint32_t) const {}
+};
+
+template <class Log> __device__ __forceinline__ void rescue_ec_slow_body(const RescueEcArgs &a, const Log &log)
 {
     if (!shared_live(a.s)) return;
     const uint32_t n = min(*a.r.n_cand, a.r.n_reads);
@@ -123,11 +131,15 @@ __global__ __launch_bounds__(kBlock) void rescue_ec_slow_kernel(RescueEcArgs a)
         if (row >= a.rows) continue;                        // no bitmap left: the count tells the host, which fails the batch
         unsigned long long *b = a.bits + (size_t)row * a.bw;
         for (uint32_t w = 0; w < a.bw; w++) b[w] = 0;
-        rescue_each_kept(a.r, r, a.r.dstar[i], [&](uint32_t p) {
-            if (p < a.s.n_paths) b[p >> 6] |= 1ull << (p & 63u);
+        rescue_each_kept(a.r, r, a.r.dstar[i], [&](uint32_t p, uint32_t to) {
+            if (p >= a.s.n_paths) return;
+            b[p >> 6] |= 1ull << (p & 63u);
+            log.kept(a, r, row, p, to);
         });
     }
 }
+
+__global__ __launch_bounds__(kBlock) void rescue_ec_slow_kernel(RescueEcArgs a) { rescue_ec_slow_body(a, RescueNoLog{}); }
 
 __global__ __launch_bounds__(kBlock) void rescue_ec_insert_kernel(RescueEcArgs a)
 {
@@ -146,17 +158,25 @@ __global__ __launch_bounds__(kBlock) void rescue_ec_insert_kernel(RescueEcArgs a
     rescue_add_stats(a.stats, st, where);
 }
 
-// one thread per slot of the batch's table (tab_size slots)
-__global__ __launch_bounds__(kBlock) void rescue_ec_merge_kernel(SharedArgs a, EcTable t, uint32_t tab_size, uint32_t epoch, uint32_t *fill)
+// one thread per slot of the batch's table (tab_size slots).  tab_ser (rescued reads in assigned coverage: kernels_rescue_acov.hpp) gets
+// the serial of every occupied slot's EC, and the slots then stay as they are for the probe behind this launch, which clears them
+template <bool kKeep>
+__device__ __forceinline__ void rescue_ec_merge_body(const SharedArgs &a, const EcTable &t, uint32_t tab_size, uint32_t epoch, uint32_t *fill, uint32_t *tab_ser)
 {
     if (!shared_live(a)) return;
     for (uint32_t slot = blockIdx.x * kBlock + threadIdx.x; slot < tab_size; slot += gridDim.x * kBlock) {
         const uint32_t r = a.tab_rep[slot];
         if (r == kSharedEmpty) continue;
-        ec_add(t, a.set_graph + (size_t)r * kSharedSegs, a.set_mask + (size_t)r * kSharedSegs * a.pw, a.pw, a.tab_cnt[slot], epoch, true, fill, 0);
+        const uint32_t ser = ec_add(t, a.set_graph + (size_t)r * kSharedSegs, a.set_mask + (size_t)r * kSharedSegs * a.pw, a.pw, a.tab_cnt[slot], epoch, true, fill, 0);
+        if (kKeep) { tab_ser[slot] = ser; continue; }
         a.tab_rep[slot] = kSharedEmpty;
         a.tab_cnt[slot] = 0;
     }
+}
+
+__global__ __launch_bounds__(kBlock) void rescue_ec_merge_kernel(SharedArgs a, EcTable t, uint32_t tab_size, uint32_t epoch, uint32_t *fill)
+{
+    rescue_ec_merge_body<false>(a, t, tab_size, epoch, fill, nullptr);
 }
 
 } // namespace groot

@@ -611,6 +611,19 @@ class Aligner:
         self._check(lib().groot_hip_rescue_ec_stats(self._h, v))
         return dict(zip(("reads", "slow_reads", "rows", "launches"), (int(x) for x in v)))
 
+    # ---- rescued reads in assigned coverage (groot_hip_rescue_acov_*) -----------------------------------
+    def rescue_acov_enable(self, on=True, min_slots=0):
+        """from now on every kept placement of a rescued read is a record of the assigned-coverage table (include/groot_hip.h, "rescued
+        reads in assigned coverage").  Needs rescue_enable, ec_enable and acov_enable first and switches the rescued reads in the classes on
+        itself.  min_slots: 0 or a power of two, the table's slots at least.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_rescue_acov_enable(self._h, C.c_int(1 if on else 0), C.c_uint64(min_slots)))
+
+    def rescue_acov_stats(self):
+        """groot_hip_rescue_acov_stats: {"records", "host_records", "dropped", "log_rows", "launches"}; zeros while off, but for launches"""
+        v = (C.c_uint64 * 5)()
+        self._check(lib().groot_hip_rescue_acov_stats(self._h, v))
+        return dict(zip(("records", "host_records", "dropped", "log_rows", "launches"), (int(x) for x in v)))
+
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):
         seq = np.ascontiguousarray(seq_concat, dtype=np.uint8)

@@ -597,6 +597,51 @@ int groot_hip_rescue_ec_enable(groot_ctx *ctx, int on);
 /* Waits for everything in flight; zeros while off, but for launches. */
 int groot_hip_rescue_ec_stats(groot_ctx *ctx, groot_rescue_ec_stats *out);
 
+/* ---- rescued reads in assigned coverage ----------------------------------------------------------------------------------
+ * The assigned-coverage table piles up records, and a rescued read has none: with the rescued reads in the classes alone, the EM would
+ * see them and the pileup would not.  With this on, every kept placement of a rescued read is a record of the table.  The definition:
+ *
+ *   S+(r), R(r), d*(r), kept placement (p, strand, x), path coordinate X: exactly as in "mismatch rescue" and "rescued reads in the equivalence
+ *   classes".  ECs, canonical order, alpha, w(e,p): exactly as for --abundance --abundanceRescued (the run's ECs are the distinct non-empty S+(r)).
+ *   A kept placement (p, strand, x) of a rescued read r of length len is one RESCUED RECORD of r on p covering [X, X + len - 1], both ends
+ *   included -- the bases on which rescue's rdepth grows for that placement, and in the coordinate the exact records' Pos uses.  Every kept
+ *   placement counts: both strands, every x, several on one path.  (An exact record covers [Pos, min(Pos + M, path_len - 1)], the report's
+ *   interval, one base more than the read where the path allows: that stays.  The two kinds are not made alike.)
+ *   The assigned-coverage table of a run with the feature on is the multiset of exact records AND rescued records grouped by
+ *   (e = EC of S+(r), p, Pos, last): n(e, p, Pos, last), integers.  d_e[x], D_p[x], depth, breadth, cigar, called, --callSupport's and --rarefy's
+ *   columns: computed from that table and those ECs by the existing host and device functions, unchanged.
+ *   Reads placed with a gap (--indels) have no rescued record.  A pass that collect redoes counts once; a batch under kCovSkipFlags counts nothing.
+ *   The table depends on the reads and the index alone: not on batch size, pipeline depth, align stage, --ctxPerGpu or --gpus.
+ *
+ * The exact pileup repeats a batch's claim and add at collect when the table was full; a rescued batch cannot be replayed (its inputs
+ * are the ctx's, one batch at a time), so its records are claimed and added in one pass over the whole table.  The table grows at collect,
+ * between batches: when the rescued records of the batches in flight find no room in the table as it stands, they are counted in `dropped`
+ * and groot_hip_acov_export fails with GROOT_E_NOSPACE until groot_hip_acov_reset: start the table larger (min_slots).  No read is dropped
+ * silently.  Off by default: then no allocation, launch or sync, and every kernel launched is the one launched without this feature. */
+#define GROOT_RESCUE_ACOV_BYTES (8ull << 20)   /* per pipeline slot: the log (16 bytes a placement) of the kept placements of a batch's rescued reads in more than 4 graphs */
+typedef struct groot_rescue_acov_stats {
+    uint64_t records;       /* rescued records added to the table since enable / groot_hip_acov_reset, the host's among them */
+    uint64_t host_records;  /* those of reads whose set lies in more than 4 graphs (1 under GROOT_TEST_SHARED_SLOW): folded on the host from the log */
+    uint64_t dropped;       /* rescued records that found no room in the table: groot_hip_acov_export fails while this is not 0 */
+    uint64_t log_rows;      /* log entries per batch: GROOT_RESCUE_ACOV_BYTES / 16, or GROOT_TEST_RESCUE_ACOV_LOG; 0 while off */
+    uint64_t launches;      /* kernels launched for it since open, whether it is on now or not; the two that take the place of a kernel of the
+                               rescued reads in the classes count in groot_rescue_ec_stats.launches */
+} groot_rescue_acov_stats;
+/* on != 0: on.  Needs mismatch rescue, equivalence classes and assigned coverage on (GROOT_E_STATE otherwise, with the reason), and
+ * nothing in flight (GROOT_E_STATE); GROOT_E_UNSUPPORTED beside pairing.  It switches the rescued reads in the equivalence classes on
+ * itself: the one way in which they and assigned coverage run together (groot_hip_rescue_ec_enable and groot_hip_acov_enable keep refusing
+ * each other).  min_slots: 0, or a power of two (GROOT_E_INVALID otherwise): the table is grown to at least that many slots, also when the
+ * feature is on already (it counts among groot_hip_acov_stats' grows).  on == 0 switches it and the rescued reads in the classes off;
+ * so does switching mismatch rescue, the equivalence classes, the rescued reads in them or assigned coverage off.
+ * groot_hip_acov_reset and groot_hip_ec_reset (which calls it) zero the table, the rescued records in it, `dropped` and these stats.
+ * groot_hip_rescue_enable with another M and groot_hip_rescue_reset leave the table alone, as they leave the classes alone.
+ * A batch whose rescued reads in more than 4 graphs have more kept placements than `log_rows` fails at collect with GROOT_E_NOSPACE (the
+ * message names GROOT_TEST_RESCUE_ACOV_LOG).  groot_hip_acov_export / _stats then count the rescued records too (records, tuples);
+ * slow_records there stays the exact records.  Device memory: 4 bytes per read of a batch, `log_rows` entries per pipeline slot. */
+int groot_hip_rescue_acov_enable(groot_ctx *ctx, int on, uint64_t min_slots);
+/* Waits for everything in flight; zeros while off, but for launches. */
+int groot_hip_rescue_acov_stats(groot_ctx *ctx, groot_rescue_acov_stats *out);
+
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
  * the device, bit for bit in boot_count, alpha and iterations.  Quoted from there: draw j (0 <= j < n_draws; n_draws = 0 means N, the sum
