@@ -96,6 +96,51 @@ def test_window_with_an_N_and_window_over_the_end():
     assert _brute(L20 + b"A" + R20[:19]).placements(read) == []
 
 
+P72 = b"TGGTGTTAACCTTACTATACTCCCGCTCCGGGGTTTGGCTCATATGAACAAGTCTTTGCGCCCATAAATGTA"
+U100 = b"GCCAGTGAGCTTAGTTGGAGCAAGGGGTGCGGAAGCGCAACTCCGTCGCGCGGGTAGCCAACTACTTAAGACCTAGGATTCTGTTGCAGATTAGAACTTG"
+W16 = b"ACGTCAGTGCATGACT"             # no base twice in a row, around the period's end neither: a one-base gap in it does not move
+
+
+def test_read_that_fills_a_short_path_exactly():
+    """a path of 72 bases.  An 80-base read with 8 inserted bases behind its first 40 has W = the whole path: x = 0, d = 0, e = 8, k* = 40 (the
+    last inserted base G is not the T in front of the cut, so the gap does not move left), event (0, 39, INS, 8, GATTACAG).  A 64-base
+    read that lacks bases 40 .. 47 fills it as well.  On the path's first 71 bases, or on its last 71, neither has a placement: every
+    window of a read of 80 bases is at least 72 long, and the DEL read's only window with d <= 3 is the 72"""
+    ins, dele = P72[:40] + b"GATTACAG" + P72[40:], P72[:40] + P72[48:]
+    assert (len(P72), len(ins), len(dele)) == (72, 80, 64)
+    b = _brute(P72, m_max=3)
+    assert keep(b.placements(ins), 1, 8) == (8, [(0, 0, 0, INS, 8, 0, 40)]) and keep(b.placements(ins), 3, 7) == (None, [])
+    assert event_of((0, 0, 0, INS, 8, 0, 40), ins) == (0, 39, INS, 8, 2 | 3 << 4 | 3 << 6 | 1 << 10 | 2 << 14)
+    assert keep(b.placements(dele), 1, 8) == (8, [(0, 0, 0, DEL, 8, 0, 40)])
+    for short in (P72[:71], P72[1:]):
+        assert _brute(short, m_max=3).placements(ins) == [] and _brute(short, m_max=3).placements(dele) == []
+
+
+def test_shifted_copies_in_a_repeat_longer_than_the_read():
+    """T = L20 (W16 x 8) R20.  The read is T[24, 125) without base 74: 100 bases inside the repeat.  One period to the right the repeat
+    spells the same 101 bases (40 + 101 <= 148), two periods to the right the window would run into R20, one to the left into L20: x = 24
+    and x = 40 are kept, each d = 0, e = 1, k* = 50, events at pos 73 and 89"""
+    t = L20 + W16 * 8 + R20
+    read = t[24:74] + t[75:125]
+    e, kept = keep(_brute(t, m_max=3).placements(read), 2, 3)
+    assert e == 1 and sorted(kept) == [(0, 0, 24, DEL, 1, 0, 50), (0, 0, 40, DEL, 1, 0, 50)]
+    assert [event_of(x, read) for x in sorted(kept)] == [(0, 73, DEL, 1, 0), (0, 89, DEL, 1, 0)]
+
+
+def test_three_mismatches_and_one_clean_block():
+    """M = 3: a read of 96 bases is six blocks.  TT inserted behind base 47 lies in blocks 2 and 3, substitutions at 5, 20 and 70 spoil
+    blocks 0, 1 and 4: block 5 alone is clean.  d = 3, e = 3 + 2 under M = 3; nothing under M = 2, whatever G"""
+    sub = lambda s, at: bytes(b"ACGT"[(b"ACGT".index(c) + 1) % 4] if i in at else c for i, c in enumerate(s))
+    read = sub(U100[:47] + b"TT" + U100[47:94], (5, 20, 70))
+    b = _brute(U100, m_max=3)
+    assert len(read) == 96 and keep(b.placements(read), 3, 3) == (5, [(0, 0, 0, INS, 2, 3, 47)])
+    assert keep(b.placements(read), 2, 8) == (None, []) and keep(b.placements(read), 3, 1) == (None, [])
+    assert event_of((0, 0, 0, INS, 2, 3, 47), read) == (0, 46, INS, 2, 3 | 3 << 2)
+    blocks = [read[16 * i:16 * i + 16] for i in range(6)]
+    assert [blocks[i] == U100[16 * i:16 * i + 16] for i in range(3)] == [False] * 3            # in front of the gap
+    assert [blocks[i] == U100[16 * i - 2:16 * i + 14] for i in range(3, 6)] == [False, False, True]      # behind it
+
+
 # ---- the inputs of tests/test_gap_rescue.py ----------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
