@@ -57,6 +57,8 @@ public:
             if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
         if (plan_.rescue)
             if (int rc = groot_hip_rescue_enable(ctx, &v_, on ? (uint32_t)a_.rescue : 0u)) return rc;
+        if (plan_.rescued_bam && on)    // (off: the rescued records go with rescue)
+            if (int rc = groot_hip_rescue_rec_enable(ctx, a_.rescued_bam_slots_given ? (uint64_t)a_.rescued_bam_slots : 16ull * std::max<uint32_t>(a_.batch, 1u))) return rc;
         if (plan_.indels && on)     // (off: gapped rescue goes with rescue)
             if (int rc = groot_hip_gap_enable(ctx, (uint32_t)a_.rescue_gap, (uint64_t)a_.gap_event_slots)) return rc;
         if (plan_.shared)

@@ -9,6 +9,7 @@ struct AlignPlan {
     bool rescue = false;     // mismatch rescue runs: --variants, --indels or --abundanceRescued
     bool ab_rescued = false; // --abundanceRescued: the rescued reads join the equivalence classes
     bool calls_rescued = false; // --callsRescued: and their kept placements the pileup of --calls
+    bool rescued_bam = false;   // --rescuedBam: the kept placements of the rescued reads as BAM records in a file of their own
     bool coverage = false;   // report coverage is counted: --report, or --variants / --indels for its exact depth
     bool frags = false;      // --paired / --interleaved
     bool counters = false;   // a ctx carries switches: set at open and reopen, harvested before it closes
@@ -80,7 +81,8 @@ int plan_align(const Args &a, AlignPlan *p)
     if (p->variants && p->assign) return refuse("--variants cannot be combined with --assignFrom: assignment rewrites the records that tell which reads are unaligned");
     p->indels = !a.indels_out.empty();
     p->ab_rescued = a.abundance_rescued;
-    p->rescue = p->variants || p->indels || p->ab_rescued;
+    p->rescued_bam = !a.rescued_bam_out.empty();
+    p->rescue = p->variants || p->indels || p->ab_rescued || p->rescued_bam;
     if (a.rescue_given && !p->rescue) return refuse("--rescue is the number of substitutions --variants allows: it needs it");
     if (a.variant_min_given && !p->variants && !p->indels) return refuse("--variantMinReads and --variantMinShare are the thresholds of --variants: they need it");
     if (p->rescue && (a.rescue < 1 || a.rescue > 3)) return refuse("--rescue allows 1, 2 or 3 substitutions: %ld", a.rescue);
@@ -106,6 +108,12 @@ int plan_align(const Args &a, AlignPlan *p)
     if (a.call_slots_given && (a.call_slots < 1 || a.call_slots > (1ll << 31) || (a.call_slots & (a.call_slots - 1))))
         return refuse("--callSlots is a number of table slots, a power of two up to 2^31: %lld", a.call_slots);
     p->calls_rescued = a.calls_rescued;
+    // --rescuedBam: checked behind everything above
+    if (p->rescued_bam && a.no_align) return refuse("--rescuedBam holds the reads the exact alignments leave out: it cannot be combined with --noAlign");
+    if (p->rescued_bam && p->assign) return refuse("--rescuedBam cannot be combined with --assignFrom: assignment rewrites the records that tell which reads are unaligned");
+    if (a.rescued_bam_slots_given && !p->rescued_bam) return refuse("--rescuedBamSlots is the room for the records of --rescuedBam: it needs it");
+    if (a.rescued_bam_slots_given && a.rescued_bam_slots < 1) return refuse("--rescuedBamSlots is a number of records per batch, at least 1: %lld", a.rescued_bam_slots);
+    if (p->rescued_bam && a.rescued_bam_out == a.bam_out) return refuse("--rescuedBam and --bam name the same file: %s", a.bam_out.c_str());
     p->coverage = p->report || p->variants || p->indels;
     p->counters = p->report || p->abundance || p->assign || p->rescue;
     return 0;

@@ -17,6 +17,8 @@ struct WorkItem {
     // filled by the mapper
     int gpu = -1;
     groot_batch_result res{};
+    const groot_rescue_record *rr = nullptr;   // --rescuedBam: the batch's rescued records, in the ctx's pinned memory until the ticket is released
+    uint64_t n_rr = 0;
 };
 
 template <class T> struct BoundedQueue {
@@ -84,6 +86,8 @@ struct Stream {
     uint32_t memo_budget = GROOT_MEMO_OFF;
     std::unique_ptr<RunCounters> counters;
     groot_bam *bam = nullptr;
+    groot_bam *rescued_bam = nullptr;                 // --rescuedBam
+    uint64_t rescued_records = 0, rescued_reads = 0;  // ... what went into it
     std::vector<std::unique_ptr<Gpu>> gpus;
     std::atomic<bool> gpus_ready{false};
     BoundedQueue<WorkItem> parsed{kParsedAhead};
@@ -263,6 +267,8 @@ bool Stream::collect_one(Gpu &g)
     n_batches++;
     // the reference's panics (short read, RevComplement on a byte > 'T') and over-long reads end the run
     if (rc) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+    // (asked for here: the ctx is the mapper's, the writer only reads the pinned memory the pointer names)
+    if (plan.rescued_bam && groot_hip_rescue_rec_batch(g.ctx, w.res.ticket, &w.rr, &w.n_rr)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
     g.inflight--; g.held++;
     w.gpu = g.index;
     mapped.push(std::move(w));
@@ -346,6 +352,15 @@ void Stream::writer()
                 if (wrc) fail_with(groot_host_last_error());
                 else if (nrec != c.alignments && !plan.assign)   // (assignment: the counts are the unfiltered run's, the records what it kept)
                     fail_with("internal error: " + std::to_string(nrec) + " records written, " + std::to_string(c.alignments) + " alignments counted");
+            }
+            if (rescued_bam && it.n_rr && !failed) {   // right behind the main BAM's batch, in input order
+                uint64_t nrec = 0;
+                auto tw = std::chrono::steady_clock::now();
+                const int wrc = groot_bam_write_rescued(rescued_bam, &v, &it.view, it.rr, it.n_rr, &nrec);
+                bam_s += seconds_since(tw);
+                if (wrc) fail_with(groot_host_last_error());
+                rescued_records += nrec;
+                for (uint64_t i = 0; i < nrec; i++) rescued_reads += i == 0 || it.rr[i].read != it.rr[i - 1].read;
             }
             hand_back(it);
         }

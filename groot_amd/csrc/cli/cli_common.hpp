@@ -80,6 +80,9 @@ struct Args {
     long rescue_gap = 3;                   // --rescueGap G (1..8)
     long long gap_event_slots = 0;         // --gapEventSlots N (a power of two; 0: the library's default)
     bool rescue_gap_given = false, gap_slots_given = false;
+    std::string rescued_bam_out;           // --rescuedBam: a BAM of its own with one record per kept placement of every read mismatch rescue places
+    long long rescued_bam_slots = 0;       // --rescuedBamSlots N: room for that many of them per batch and pipeline slot (0: 16 per read of --batch)
+    bool rescued_bam_slots_given = false;
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
     bool gpu_given = false, write_gob = false;

@@ -40,6 +40,7 @@ void usage()
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
             "                  [--indels i.tsv [--rescueGap 3] [--gapEventSlots 4194304] [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
+            "                  [--rescuedBam r.bam [--rescue 2] [--rescuedBamSlots N]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
@@ -73,6 +74,11 @@ void usage()
             "                   substitutions, on the GPU; `name pos type len seq reads gap_depth rescued_depth exact_depth share` for every deletion or insertion\n"
             "                   that at least --variantMinReads of them show and that is at least --variantMinShare of the depth at pos, the base before the gap.\n"
             "                   With or without --variants; --gapEventSlots: the slots of the event table on the GPU, a power of two (a run that fills it fails);\n"
+            "                   --rescuedBam: a BAM of its own with one record per placement of every read WITHOUT an exact alignment that mismatch rescue\n"
+            "                   places with up to --rescue (1..3) substitutions: FLAG 0x10 for the reverse strand, 0x100 on a read's further placements, CIGAR\n"
+            "                   <len>M, NM and MD tags; the main BAM and every other file stay as they are.  --rescuedBamSlots: room for that many records per\n"
+            "                   batch on the GPU, 16 per read of --batch unless given (a batch with more fails the run and says so).  Not with --assignFrom or\n"
+            "                   --noAlign;\n"
             "                   --paired: the -f files are R1,R2[,R1b,R2b...], first with second, third with fourth; --interleaved: the mates alternate in\n"
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
@@ -157,6 +163,13 @@ Args parse(int argc, char **argv)
             const std::string t = v();
             char *end = nullptr;
             a.call_slots = strtoll(t.c_str(), &end, 10); a.call_slots_given = true;
+            if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
+        }
+        else if (a.cmd == "align" && f == "--rescuedBam") a.rescued_bam_out = v();
+        else if (a.cmd == "align" && f == "--rescuedBamSlots") {
+            const std::string t = v();
+            char *end = nullptr;
+            a.rescued_bam_slots = strtoll(t.c_str(), &end, 10); a.rescued_bam_slots_given = true;
             if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
         }
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
@@ -307,6 +320,7 @@ int run_align(const Args &a)
     t.load_s = seconds_since(t0);
     if (!a.no_align && !a.no_bam && groot_bam_open(a.bam_out.empty() ? nullptr : a.bam_out.c_str(), &v, nullptr, &s.bam)) die("%s", groot_host_last_error());
     if (s.bam) { groot_bam_set_threads(s.bam, s.cores); if (groot_bam_set_level(s.bam, a.bam_level)) die("%s", groot_host_last_error()); }
+    if (plan.rescued_bam && groot_bam_open(a.rescued_bam_out.c_str(), &v, nullptr, &s.rescued_bam)) die("%s", groot_host_last_error());
 
     logf("now streaming reads...");                                                              // 6. stream
     auto t_stream = std::chrono::steady_clock::now();
@@ -327,6 +341,11 @@ int run_align(const Args &a)
     logf("\tnumber of reads sketched: %llu", (unsigned long long)s.received);                    // sketch.go:321
     const uint64_t bam_bytes = s.bam ? groot_bam_bytes_written(s.bam) : 0;
     if (s.bam && groot_bam_close(s.bam)) die("%s", groot_host_last_error());
+    if (s.rescued_bam) {
+        if (groot_bam_close(s.rescued_bam)) die("%s", groot_host_last_error());
+        logf("\trescued reads: %llu record(s) of %llu read(s) written to %s (up to %ld substitution(s))", (unsigned long long)s.rescued_records,
+             (unsigned long long)s.rescued_reads, a.rescued_bam_out.c_str(), a.rescue);
+    }
     if (plan.counters)                                                                           // 7. harvest
         // every batch has been collected: what each ctx counted is final (it is switched off, so a ctx reopened below starts without it)
         for (auto &g : s.gpus)

@@ -2,12 +2,16 @@
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
 // draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp), rescued reads in the equivalence
-// classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp).  One of the six translation units of
+// classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp), rescued records (kernels_rescue_rec.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
+#include <cstring>   // before rocprim: its texture iterator calls host memset
+
 #include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <array>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
@@ -29,6 +33,7 @@
 #include "kernels_rescue.hpp"
 #include "kernels_rescue_ec.hpp"
 #include "kernels_rescue_acov.hpp"
+#include "kernels_rescue_rec.hpp"
 #include "kernels_shared.hpp"
 
 using namespace groot;
@@ -360,6 +365,67 @@ static int rec_collect(groot_ctx *c, Slot *s, bool refetch)
     return GROOT_OK;
 }
 
+// ---- rescued records (kernels_rescue_rec.hpp) ----
+struct KeptToU64 {
+    __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
+};
+
+// Behind the count kernel on the tail stream: every read's segment by a scan over the reads (its last output is the batch's total, which
+// stays with the slot), then the records themselves.
+static int rr_launch(groot_ctx *c, Slot *s, const RescueArgs &ra)
+{
+    Counters &k = c->ct;
+    HIP_TRY(c, s->ct.d_rr_rec.reserve((size_t)k.rr_slots * kRescueRecWords));
+    HIP_TRY(c, s->ct.d_rr_total.reserve(1));
+    HIP_TRY(c, s->ct.h_status.reserve(1));
+    const size_t n = (size_t)s->n_reads + 1;
+    auto in = rocprim::make_transform_iterator(k.rr_kept.p, KeptToU64());
+    size_t tmp_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_bytes, in, k.rr_off.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->tstream));
+    if (tmp_bytes > c->scan_tmp.n) {
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
+        HIP_TRY(c, c->scan_tmp.alloc(tmp_bytes + tmp_bytes / 4));
+    }
+    HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tmp_bytes, in, k.rr_off.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->tstream));
+    HIP_TRY(c, hipMemcpyAsync(s->ct.d_rr_total.p, k.rr_off.p + s->n_reads, sizeof(uint64_t), hipMemcpyDeviceToDevice, c->tstream));
+    RescueRecArgs a{};
+    a.r = ra; a.off = k.rr_off.p; a.rec = s->ct.d_rr_rec.p; a.cap = k.rr_slots;
+    hipLaunchKernelGGL(rescue_rec_emit_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, a);
+    HIP_TRY(c, hipGetLastError());
+    k.rr_launches += 2;
+    return GROOT_OK;
+}
+
+// At collect: as many records as the batch has, into the slot's pinned memory.  A batch with more than the slot has room for fails alone
+// (its other results stay readable).  refetch: the total enqueue copied is that of the skipped pass.
+static int rr_collect(groot_ctx *c, Slot *s, bool refetch)
+{
+    Counters &k = c->ct;
+    s->ct.rr_n = 0;
+    if (!s->ct.rr || !s->n_reads || !s->ct.d_rr_total.p || !k.rr_on) return GROOT_OK;
+    if (refetch) HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rr_total, s->ct.d_rr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const uint64_t n = s->ct.h_status.p->rr_total;
+    if (!n) return GROOT_OK;
+    if (n > k.rr_slots) {
+        k.rr_failed++;
+        if (s->status == GROOT_OK) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "rescued records: a batch has %llu records, and a pipeline slot has room for %llu (slots_per_batch of groot_hip_rescue_rec_enable)",
+                     (unsigned long long)n, (unsigned long long)k.rr_slots);
+            s->status = GROOT_E_NOSPACE;
+            s->status_msg = buf;
+        }
+        return GROOT_OK;
+    }
+    HIP_TRY(c, s->ct.h_rr_rec.reserve(n + n / 4));
+    HIP_TRY(c, hipMemcpy(s->ct.h_rr_rec.p, s->ct.d_rr_rec.p, n * sizeof(groot_rescue_record), hipMemcpyDeviceToHost));
+    s->ct.rr_n = n;
+    k.rr_records += n;
+    const groot_rescue_record *h = s->ct.h_rr_rec.p;
+    for (uint64_t i = 0; i < n; i++) k.rr_reads += i == 0 || h[i].read != h[i - 1].read;
+    return GROOT_OK;
+}
+
 // ---- the pipeline's hooks (counters.hpp) ---------------------------------------------------------------------------
 namespace groot {
 
@@ -462,7 +528,15 @@ int counters_launch(groot_ctx *c, Slot *s)
             ra.path_bit = k.rec_path_bit.p; ra.set_graph = sa.set_graph; ra.set_mask = sa.set_mask; ra.dstar = k.rec_dstar.p;
             ra.pw = sa.pw; ra.max_segs = sa.max_segs;
         }
-        if (!k.gap_on && k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+        if (k.rr_on) {       // rescued records (kernels_rescue_rec.hpp): the count kernel also leaves every read's kept placements, zero for a read that is no candidate
+            ra.n_kept = k.rr_kept.p; ra.rec_d = k.rr_d.p;
+            HIP_TRY(c, hipMemsetAsync(k.rr_kept.p, 0, ((size_t)s->n_reads + 1) * sizeof(uint32_t), c->tstream));
+        }
+        const dim3 gr(grid_for(s->n_reads));
+        if (!k.gap_on && k.rr_on) {
+            if (k.rec_on) hipLaunchKernelGGL((rescue_count_rec_kernel<false, true>), gr, dim3(kBlock), 0, c->tstream, ra);
+            else hipLaunchKernelGGL((rescue_count_rec_kernel<false, false>), gr, dim3(kBlock), 0, c->tstream, ra);
+        } else if (!k.gap_on && k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
         else if (!k.gap_on) hipLaunchKernelGGL(rescue_count_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
         else {
             GapArgs ga{};
@@ -471,13 +545,17 @@ int counters_launch(groot_ctx *c, Slot *s)
             ga.starts = k.gap_starts.p; ga.ends = k.gap_ends.p; ga.ev_key = k.gap_key.p; ga.ev_cnt = k.gap_cnt.p; ga.stats = k.gap_stats.p;
             ga.ev_mask = k.gap_slots - 1; ga.max_gap = k.gap_g;
             HIP_TRY(c, hipMemsetAsync(k.gap_ncand.p, 0, sizeof(uint32_t), c->tstream));
-            if (k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+            if (k.rr_on && k.rec_on) hipLaunchKernelGGL((rescue_count_rec_kernel<true, true>), gr, dim3(kBlock), 0, c->tstream, ra);
+            else if (k.rr_on) hipLaunchKernelGGL((rescue_count_rec_kernel<true, false>), gr, dim3(kBlock), 0, c->tstream, ra);
+            else if (k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
             else hipLaunchKernelGGL(rescue_count_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
             hipLaunchKernelGGL(rescue_gap_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
             k.gap_launches++;
         }
         HIP_TRY(c, hipGetLastError());
         k.res_launches += 2;
+        if (k.rr_on)
+            if (int rc = rr_launch(c, s, ra)) return rc;
         if (k.rec_on) {      // (ec_reserve above has made room for this merge too: its bound is over both)
             RescueEcArgs ea{};
             ea.r = ra; ea.s = sa;
@@ -519,6 +597,8 @@ int counters_fetch(groot_ctx *c, Slot *s)
         HIP_TRY(c, hipMemcpyAsync(s->ct.h_best.p, s->ct.d_best.p, (size_t)s->n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
         HIP_TRY(c, hipMemcpyAsync(s->ct.h_mapq.p, s->ct.d_mapq.p, (size_t)s->n_reads, hipMemcpyDeviceToHost, c->d2h_stream));
     }
+    if (s->ct.rr && s->n_reads && c->ct.rr_on && s->ct.d_rr_total.p)
+        HIP_TRY(c, hipMemcpyAsync(&s->ct.h_status.p->rr_total, s->ct.d_rr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->d2h_stream));
     if (!c->ct.ec_on) return GROOT_OK;
     CounterStatus *h = s->ct.h_status.p;
     HIP_TRY(c, hipMemcpyAsync(&h->ec_slow, s->ct.d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
@@ -543,6 +623,7 @@ int counters_collect(groot_ctx *c, Slot *s, bool redone)
             HIP_TRY(c, hipMemcpy(s->ct.h_mapq.p, s->ct.d_mapq.p, (size_t)s->n_reads, hipMemcpyDeviceToHost));
         }
     }
+    if (int rc = rr_collect(c, s, redone)) return rc;
     if (!c->ct.ec_on || !s->n_reads) return GROOT_OK;
     if (int rc = ec_collect(c, s, redone)) return rc;
     if (c->ct.rec_on)
@@ -1167,6 +1248,19 @@ static hipError_t gap_zero(Counters &k)
     return e;
 }
 
+// rescued records off: the ctx's work space, every slot's records and the counts since enable (the launches stay)
+static void rr_release(groot_ctx *c)
+{
+    Counters &k = c->ct;
+    k.rr_kept.release(); k.rr_off.release(); k.rr_d.release();
+    for (auto &s : c->slots) {
+        s->ct.d_rr_rec.release(); s->ct.d_rr_total.release(); s->ct.h_rr_rec.release();
+        s->ct.rr = false; s->ct.rr_n = 0;
+    }
+    k.rr_on = false; k.rr_slots = 0;
+    k.rr_records = k.rr_reads = k.rr_failed = 0;
+}
+
 static void rescue_release(Counters &k)
 {
     gap_release(k);                        // (gapped rescue looks at what rescue leaves: off with it)
@@ -1196,6 +1290,7 @@ int groot_hip_rescue_enable(groot_ctx *c, const groot_index_view *idx, uint32_t 
     HIP_TRY(c, hipSetDevice(c->device));
     Counters &k = c->ct;
     if (!max_mismatch) {
+        rr_release(c);                     // (the rescued records are rescue's placements: off with it)
         rescue_release(k);
         return GROOT_OK;
     }
@@ -1522,6 +1617,52 @@ int groot_hip_rescue_ec_stats(groot_ctx *c, groot_rescue_ec_stats *out)
     out->reads = st[0] + out->slow_reads;
     out->rows = c->ct.rec_on ? c->ct.rec_rows : 0;
     out->launches = c->ct.rec_launches;
+    return GROOT_OK;
+}
+
+// ---- rescued records (kernels_rescue_rec.hpp; the definition is in groot_hip.h) ------------------------------------------------
+static_assert(sizeof(groot_rescue_record) == kRescueRecWords * sizeof(uint32_t) && offsetof(groot_rescue_record, mm) == 12 && offsetof(groot_rescue_record, strand) == 18 &&
+              offsetof(groot_rescue_record, d) == 19, "rescue_rec_emit_kernel writes groot_rescue_record as five dwords");
+
+int groot_hip_rescue_rec_enable(groot_ctx *c, uint64_t slots_per_batch)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "rescued records can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!slots_per_batch) {
+        rr_release(c);
+        return GROOT_OK;
+    }
+    if (k.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued records come from mismatch rescue, which tells the unaligned reads by their records, and assignment rewrites those (groot_hip_assign_enable)");
+    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued records are the placements of mismatch rescue, and that is off (groot_hip_rescue_enable)");
+    if (slots_per_batch > (1ull << 40) / sizeof(groot_rescue_record)) return fail(c, GROOT_E_INVALID, "rescued records: slots_per_batch %llu is beyond 2^40 bytes", (unsigned long long)slots_per_batch);
+    if (k.rr_on && slots_per_batch == k.rr_slots) return GROOT_OK;
+    rr_release(c);
+    const size_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    hipError_t e = k.rr_kept.alloc(R + 1);
+    if (e == hipSuccess) e = k.rr_off.alloc(R + 1);
+    if (e == hipSuccess) e = k.rr_d.alloc(R);
+    for (auto &s : c->slots) {             // (now, and not at the first launch: no room is an error of this call)
+        if (e == hipSuccess) e = s->ct.d_rr_rec.alloc((size_t)slots_per_batch * kRescueRecWords);
+        if (e == hipSuccess) e = s->ct.d_rr_total.alloc(1);
+    }
+    if (e != hipSuccess) {
+        rr_release(c);
+        return fail(c, GROOT_E_DEVICE, "rescued records: %s", hipGetErrorString(e));
+    }
+    k.rr_slots = slots_per_batch;
+    k.rr_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_rec_stats(groot_ctx *c, groot_rescue_rec_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    const Counters &k = c->ct;
+    out->records = k.rr_on ? k.rr_records : 0; out->reads = k.rr_on ? k.rr_reads : 0; out->failed = k.rr_on ? k.rr_failed : 0;
+    out->slots = k.rr_on ? k.rr_slots : 0;
+    out->launches = k.rr_launches;
     return GROOT_OK;
 }
 

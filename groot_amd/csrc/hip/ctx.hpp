@@ -133,6 +133,7 @@ struct CounterStatus {
     uint32_t acov_fill;                    // ... and its table's fill
     uint32_t rec_slow;                     // rescued reads in the ECs: the batch's slow rescued reads (SlotCounters::d_rec_slow[0])
     uint32_t rac_log;                      // rescued reads in assigned coverage: the kept placements of those reads (SlotCounters::d_rac_nlog[0])
+    uint64_t rr_total;                     // rescued records: the batch's records (SlotCounters::d_rr_total[0])
 };
 
 struct SlotCounters {
@@ -149,6 +150,11 @@ struct SlotCounters {
     DevBuf<uint32_t> d_rec_slow;           // [0] their number, with or without a bitmap (rescue_ec_slow_kernel)
     DevBuf<uint4> d_rac_log;               // rescued reads in assigned coverage: [rac_log_cap] (bitmap row, path, X, last) of those reads' kept placements, read at collect
     DevBuf<uint32_t> d_rac_nlog;           // [0] their number, logged or not (rescue_acov_slow_kernel)
+    DevBuf<uint32_t> d_rr_rec;             // rescued records: [rr_slots][5 dwords] the batch's records (rescue_rec_emit_kernel), copied out at collect
+    DevBuf<uint64_t> d_rr_total;           // [0] their number, whether they found room or not (the scan's last output)
+    PinBuf<groot_rescue_record> h_rr_rec;  // what groot_hip_rescue_rec_batch hands out: as many as the batch has
+    uint64_t rr_n = 0;                     // the batch's records in h_rr_rec
+    bool rr = false;                       // the feature was on when the batch was submitted
 };
 
 struct Counters {
@@ -236,6 +242,16 @@ struct Counters {
     DevBuf<unsigned long long> rac_stats;  // [kRescueAcovStats]
     uint64_t rac_host_records = 0;         // rescued records folded on the host since enable / groot_hip_acov_reset
     uint64_t rac_launches = 0;             // kernels launched for it since open; the two that take the place of rec's count there
+    // rescued records (groot_hip_rescue_rec_*, kernels_rescue_rec.hpp): needs mismatch rescue on.  The count kernel also leaves every
+    // read's number of kept placements, a scan and rescue_rec_emit_kernel behind it write the batch's records into a buffer of the slot,
+    // and collect copies as many as there are into pinned memory.  Nothing on the device while off.
+    bool rr_on = false;
+    uint64_t rr_slots = 0;                 // records per batch (fixed at enable)
+    DevBuf<uint32_t> rr_kept;              // RescueArgs::n_kept (tail stream: one batch at a time, as the candidates are)
+    DevBuf<uint64_t> rr_off;               // RescueRecArgs::off
+    DevBuf<uint8_t> rr_d;                  // RescueArgs::rec_d
+    uint64_t rr_records = 0, rr_reads = 0, rr_failed = 0;   // handed out / rescued reads among them / batches failed for room, since enable
+    uint64_t rr_launches = 0;              // the scan and rescue_rec_emit_kernel since open (rescue_count_rec_kernel counts as rescue's)
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

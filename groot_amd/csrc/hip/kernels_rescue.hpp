@@ -17,7 +17,8 @@
 //                      rescue_count_kernel<true> (gapped rescue on: kernels_gap.hpp) also hands on the candidates it leaves unplaced;
 //                      <false> is the kernel without that, and the only one launched while gapped rescue is off.
 //                      Both are rescue_count_body with a sink that does nothing; rescue_count_ec_kernel (kernels_rescue_ec.hpp: rescued
-//                      reads in the equivalence classes) is the same body with a sink that keeps the paths of the kept placements.
+//                      reads in the equivalence classes) is the same body with a sink that keeps the paths of the kept placements, and
+//                      rescue_count_rec_kernel (kernels_rescue_rec.hpp: rescued records) with one that also counts them per read.
 // Integer sums only: the tables do not depend on the order of the candidates, of the wavefronts or of the batches.
 #pragma once
 
@@ -56,6 +57,9 @@ struct RescueArgs {
     uint64_t *set_mask;
     uint8_t *dstar;                // [n_reads] d* of candidate i, kRescueUnplaced when it is not rescued
     uint32_t pw, max_segs;         // SharedArgs::pw, max_segs
+    // rescued records (kernels_rescue_rec.hpp; the rescue_count_rec kernels and rescue_rec_emit_kernel only)
+    uint32_t *n_kept;              // [n_reads + 1] kept placements of read r (zeroed ahead of the launch), then their exclusive scan in rec_off
+    uint8_t *rec_d;                // [n_reads] d* of candidate i, kRescueUnplaced when it is not rescued (a copy of its own: dstar is there only beside the classes)
 };
 
 // what rescue_place tells of every kept placement beyond the dense tables: nothing here, the path to the read's set row in

@@ -87,8 +87,8 @@ struct RescueEcArgs {
 };
 
 // the kept placements of candidate read r at distance d = d*(r): f(global path, text offset of the read's first base) once per placement
-// (rescue_place's second sweep without the tables)
-template <class F> __device__ __forceinline__ void rescue_each_kept(const RescueArgs &a, uint32_t r, uint32_t d, F &&f)
+// (rescue_place's second sweep without the tables).  rescue_each_kept_strand tells f the strand as well (kernels_rescue_rec.hpp)
+template <class F> __device__ __forceinline__ void rescue_each_kept_strand(const RescueArgs &a, uint32_t r, uint32_t d, F &&f)
 {
     const uint64_t o = a.seq_off[r];
     const uint32_t len = (uint32_t)(a.seq_off[r + 1] - o), nb = len / kRescueAnchor;
@@ -105,10 +105,15 @@ template <class F> __device__ __forceinline__ void rescue_each_kept(const Rescue
                 const uint4 pi = a.path[oc.x];
                 const uint32_t rel = oc.y - pi.x;
                 if (rel < kRescueAnchor * j || rel - kRescueAnchor * j + len > pi.y) continue;
-                if (rescue_distance(a, rd, len, pi.x + rel - kRescueAnchor * j, j, d) == d) f(oc.x, rel - kRescueAnchor * j);
+                if (rescue_distance(a, rd, len, pi.x + rel - kRescueAnchor * j, j, d) == d) f(oc.x, rel - kRescueAnchor * j, strand);
             }
         }
     }
+}
+
+template <class F> __device__ __forceinline__ void rescue_each_kept(const RescueArgs &a, uint32_t r, uint32_t d, F &&f)
+{
+    rescue_each_kept_strand(a, r, d, [&](uint32_t p, uint32_t to, uint32_t) { f(p, to); });
 }
 
 // candidate i of the batch is rescued: its row is written and dstar[i] holds d*

@@ -9,6 +9,7 @@
 #include "host_common.hpp"
 #include "bgzf_struct.hpp"
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -43,6 +44,9 @@ struct groot_bam {
     std::deque<std::vector<std::vector<uint8_t>>> io_q;
     bool io_busy = false, io_stop = false;
     int io_err = 0;
+    // groot_bam_write_rescued: (Position, node) of every path's nodes, ascending, built from the index view at the first call (MD's bases)
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> path_nodes;
+    bool have_path_nodes = false;
 };
 
 // the writer thread: batches of chunks in the order they were queued, gathered writes straight from the workers' buffers
@@ -628,6 +632,104 @@ int groot_bam_write_batch(groot_bam *b, const groot_index_view *ix, const groot_
         return true;
     };
     return write_travs_impl(b, ix, read, travs, masks, mask_ckpt, n_trav, n_records);
+}
+
+// ---- rescued records (groot_hip_rescue_rec_batch) -> BAM records with NM and MD --------------------------------------------------------
+// the base of global path p at path coordinate y: the node of p that covers y (nodes ascending by Position), 'N' where none does
+static char path_base(const groot_bam *b, const groot_index_view *ix, uint32_t p, uint32_t y)
+{
+    const auto &on = b->path_nodes[p];
+    auto it = std::upper_bound(on.begin(), on.end(), std::make_pair(y, UINT32_MAX));
+    if (it == on.begin()) return 'N';
+    --it;
+    const uint32_t n = it->second, at = y - it->first;
+    return at < ix->node_seq_off[n + 1] - ix->node_seq_off[n] ? (char)ix->bases[ix->node_seq_off[n] + at] : 'N';
+}
+
+int groot_bam_write_rescued(groot_bam *b, const groot_index_view *ix, const groot_reads_view *rv, const groot_rescue_record *recs, uint64_t n, uint64_t *n_records)
+{
+    if (n_records) *n_records = 0;
+    if (!b || !ix || !rv || (n && !recs)) return set_error(GROOT_E_INVALID, "null argument");
+    // everything is checked before anything is written: a refused call leaves the stream as it was
+    for (uint64_t i = 0; i < n; i++) {
+        const groot_rescue_record &r = recs[i];
+        if (r.read >= rv->n_reads) return set_error(GROOT_E_INVALID, "rescued record %llu: read %u of a batch of %u", (unsigned long long)i, r.read, rv->n_reads);
+        if (r.path >= ix->n_paths || r.path >= b->n_ref) return set_error(GROOT_E_INVALID, "rescued record %llu: path %u of %u", (unsigned long long)i, r.path, ix->n_paths);
+        const uint32_t len = rv->seq_len[r.read];
+        if (!len || (uint64_t)r.pos + len > ix->path_len[r.path])
+            return set_error(GROOT_E_INVALID, "rescued record %llu: %u bases at %u do not lie inside path %u of %u bases", (unsigned long long)i, len, r.pos, r.path, ix->path_len[r.path]);
+        if (r.strand > 1 || r.d > 3) return set_error(GROOT_E_INVALID, "rescued record %llu: strand %u, distance %u", (unsigned long long)i, r.strand, r.d);
+        for (uint32_t k = 0; k < 3; k++) {
+            const bool ok = k >= r.d ? r.mm[k] == 0xFFFF : r.mm[k] < len && (k == 0 || r.mm[k] > r.mm[k - 1]);
+            if (!ok) return set_error(GROOT_E_INVALID, "rescued record %llu: offset %u of %u is %u in a read of %u bases", (unsigned long long)i, k, r.d, r.mm[k], len);
+        }
+        if (rv->name_len[r.read] > 254) return set_error(GROOT_E_FORMAT, "read name longer than 254 characters");
+    }
+    if (!n) return GROOT_OK;
+    if (!b->have_path_nodes) {
+        b->path_nodes.assign(ix->n_paths, {});
+        for (uint32_t g = 0; g < ix->n_graphs; g++)
+            for (uint32_t nd = ix->graph_node_off[g]; nd < ix->graph_node_off[g + 1]; nd++)
+                for (uint32_t i = ix->node_np_off[nd]; i < ix->node_np_off[nd + 1]; i++) {
+                    const uint64_t gp = (uint64_t)ix->graph_path_off[g] + ix->np_path[i];
+                    if (gp < ix->n_paths) b->path_nodes[gp].push_back({ix->np_pos[i], nd});
+                }
+        for (auto &on : b->path_nodes) std::sort(on.begin(), on.end());
+        b->have_path_nodes = true;
+    }
+    RawBuf raw;
+    std::vector<uint8_t> rcs, rcq, padq;
+    std::string md;
+    for (uint64_t i = 0; i < n; i++) {
+        const groot_rescue_record &r = recs[i];
+        const uint32_t len = rv->seq_len[r.read], ql_have = std::min<uint32_t>(rv->qual_len[r.read], len);
+        const uint8_t *sq = rv->text + rv->seq_pos[r.read], *ql = rv->text + rv->qual_pos[r.read];
+        if (ql_have < len) {                                  // a short quality line is padded to the sequence, as the writer above does
+            padq.assign(len, '!');
+            memcpy(padq.data(), ql, ql_have);
+            ql = padq.data();
+        }
+        if (r.strand) {                                       // oriented as the writer above orients a reverse record (seqio.go:120-133)
+            rcs.resize(len); rcq.resize(len);
+            for (uint32_t j = 0; j < len; j++) {
+                const uint8_t ch = sq[len - 1 - j];
+                rcs[j] = ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'N' ? 'N' : 0;
+                rcq[j] = ql[len - 1 - j];
+            }
+            sq = rcs.data(); ql = rcq.data();
+        }
+        groot_aln_record rec;
+        rec.name = reinterpret_cast<const char *>(rv->text + rv->name_pos[r.read]);
+        rec.name_len = rv->name_len[r.read];
+        rec.seq = sq; rec.qual = ql; rec.seq_len = len;
+        rec.ref_id = r.path; rec.pos = r.pos;
+        rec.start_clip = rec.end_clip = 0;
+        rec.reverse = r.strand;
+        rec.secondary = i > 0 && recs[i - 1].read == r.read;
+        const size_t at = raw.size();
+        format_records(&rec, 0, 1, raw);
+        md.clear();
+        uint32_t from = 0;
+        for (uint32_t k = 0; k < r.d; k++) {
+            md += std::to_string(r.mm[k] - from);
+            md += path_base(b, ix, r.path, r.pos + r.mm[k]);
+            from = r.mm[k] + 1u;
+        }
+        md += std::to_string(len - from);
+        const size_t aux = 4 + 3 + md.size() + 1, end = raw.size();
+        raw.resize(end + aux);
+        uint8_t *p = raw.data() + end;
+        *p++ = 'N'; *p++ = 'M'; *p++ = 'C'; *p++ = r.d;
+        *p++ = 'M'; *p++ = 'D'; *p++ = 'Z';
+        memcpy(p, md.c_str(), md.size() + 1);
+        uint32_t body;
+        memcpy(&body, raw.data() + at, 4);
+        body += (uint32_t)aux;
+        memcpy(raw.data() + at, &body, 4);
+    }
+    if (int rc = put(b, raw.data(), raw.size())) return rc;
+    if (n_records) *n_records = n;
+    return GROOT_OK;
 }
 
 int groot_bam_set_level(groot_bam *b, int level)

@@ -351,6 +351,28 @@ class BamWriter:
                                            C.c_uint64(len(t)), C.byref(n)))
         return n.value
 
+    def write_rescued(self, records, names, seqs, quals):
+        """groot_bam_write_rescued: the rescued records (device.RESCUE_RECORD_DTYPE) of a batch whose reads are given as lists of bytes
+        (name, sequence, quality line as it came) -> the number of records written, each with NM and MD"""
+        n = len(names)
+        text = np.frombuffer(b"".join(x for t in zip(names, seqs, quals) for x in t) or b"\0", dtype=np.uint8)
+        lens = np.array([[len(a), len(s), len(q)] for a, s, q in zip(names, seqs, quals)], dtype=np.int64).reshape(n, 3)
+        at = np.r_[0, np.cumsum(lens.reshape(-1))][:-1].reshape(n, 3)
+        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)
+        keep = dict(seq_len=np.ascontiguousarray(lens[:, 1], dtype=np.uint16), name_pos=u32(at[:, 0]), name_len=u32(lens[:, 0]), seq_pos=u32(at[:, 1]),
+                    qual_pos=u32(at[:, 2]), qual_len=u32(lens[:, 2]))
+        v = ReadsView()
+        v.n_reads, v.max_len, v.n_bases = n, int(lens[:, 1].max()) if n else 0, int(lens[:, 1].sum())
+        v.text = _ffi.as_ptr(text, C.c_uint8)
+        v.seq_len = _ffi.as_ptr(keep["seq_len"], C.c_uint16)
+        for k in ("name_pos", "name_len", "seq_pos", "qual_pos", "qual_len"):
+            setattr(v, k, _ffi.as_ptr(keep[k], C.c_uint32))
+        rec = np.ascontiguousarray(records)
+        assert rec.dtype.itemsize == 20
+        out = C.c_uint64(0)
+        _check(lib().groot_bam_write_rescued(self._h, C.byref(self.index.view), C.byref(v), rec.ctypes.data_as(C.c_void_p), C.c_uint64(len(rec)), C.byref(out)))
+        return out.value
+
     def close(self):
         if self._h:
             h, self._h = self._h, C.c_void_p()

@@ -642,6 +642,56 @@ int groot_hip_rescue_acov_enable(groot_ctx *ctx, int on, uint64_t min_slots);
 /* Waits for everything in flight; zeros while off, but for launches. */
 int groot_hip_rescue_acov_stats(groot_ctx *ctx, groot_rescue_acov_stats *out);
 
+/* ---- rescued records -------------------------------------------------------------------------------------------------------
+ * Mismatch rescue piles its placements up in tables; the placements themselves are gone when the batch is.  With this on, every batch
+ * also hands out one record per kept placement of its rescued reads: what a BAM record of the read needs.  The definition, integers only:
+ *
+ *   Candidate, placement (p, strand, x), d*(r), RESCUED, KEPT placement, path coordinate X = first Position of p + x: exactly as in
+ *   "mismatch rescue".
+ *   A RESCUED RECORD is one kept placement of a rescued read:
+ *       read   = position of r in its batch
+ *       path   = global path p
+ *       pos    = X (0-based, the coordinate an exact record's Pos uses)
+ *       strand = 0 / 1
+ *       d      = d*(r)
+ *       mm[3]  = the offsets i, ascending, in the ORIENTED read (the read for strand 0, its reverse complement for strand 1)
+ *                with oriented[i] != text_p[x + i]; the d first entries are set, the rest are 0xFFFF.
+ *   The rescued records of a batch are ALL kept placements of ALL its rescued reads (every path, both strands, every x, several on one
+ *   path), each once, in ascending (read, path, strand, pos) order.
+ *   A pass that collect redoes yields the records of its redo, once.  A batch under kCovSkipFlags (one that fails with GROOT_E_NOSPACE)
+ *   yields none.  Gap-placed reads (gapped rescue) yield none.
+ *   The list depends on the reads and the index alone: not on batch size, pipeline depth, align stage, results_on_device or the number
+ *   of ctxs (cut a batch in pieces and the pieces' lists, with batch-relative `read`, concatenate to the batch's).
+ *
+ * On the device (kernels_rescue_rec.hpp): the count kernel of rescue also leaves every read's number of kept placements, an exclusive
+ * scan over the batch's reads gives every read its segment, and rescue_rec_emit_kernel -- one thread per rescued read -- walks the
+ * read's kept placements once more, writes them and sorts its segment.  The records live in a buffer of the pipeline slot and are copied
+ * into pinned host memory at collect, as many as the batch has.  Rescue's tables and stats and every other counter stay what they are.
+ * Off by default: then no allocation, launch or sync, and rescue_count_kernel is the one it is without this section. */
+/* groot_rescue_record (20 bytes: read, path, pos, mm[3], strand, d) is declared in groot_host.h, beside the writer that takes it */
+typedef struct groot_rescue_rec_stats {
+    uint64_t records;     /* records handed out (of collected batches that did not fail) since enable */
+    uint64_t reads;       /* rescued reads those records belong to */
+    uint64_t failed;      /* batches that failed for room */
+    uint64_t slots;       /* slots_per_batch (0 while off) */
+    uint64_t launches;    /* the scan and rescue_rec_emit_kernel, launched since open, whether it is on now or not (the count kernel
+                             counts in groot_rescue_stats.launches) */
+} groot_rescue_rec_stats;
+/* slots_per_batch > 0: on, with room for that many records per batch in every pipeline slot (a second call with another value
+ * reallocates, the stats start over); 0: off, everything freed, nothing launched afterwards.  GROOT_E_STATE when mismatch rescue is off
+ * or something is in flight; GROOT_E_UNSUPPORTED while assignment is on, as mismatch rescue itself is, and groot_hip_assign_enable
+ * refuses while rescue is on.  groot_hip_rescue_enable(.., 0) switches it off too.  A batch with more records than slots_per_batch fails
+ * at collect with GROOT_E_NOSPACE, and the message names slots_per_batch: no record is dropped silently; the batch's other results stay
+ * readable, its records do not (groot_hip_rescue_rec_batch gives n = 0), and the next batch is not affected.  Device memory: 13 bytes per
+ * read of a batch, and 20 slots_per_batch bytes per pipeline slot; pinned memory: 20 bytes per record of the largest batch so far, per slot. */
+int groot_hip_rescue_rec_enable(groot_ctx *ctx, uint64_t slots_per_batch);
+/* recs[0 .. *n) of a collected, unreleased batch (ticket 0: the batch groot_hip_wait collected), in pinned host memory that stays valid
+ * until the batch is released; with results_on_device as well.  *n = 0 for an empty or a failed batch.  GROOT_E_STATE when the feature
+ * was off when the batch was submitted. */
+int groot_hip_rescue_rec_batch(groot_ctx *ctx, uint64_t ticket, const groot_rescue_record **recs, uint64_t *n);
+/* Zeros while off, but for launches.  Counts collected batches only; does not wait. */
+int groot_hip_rescue_rec_stats(groot_ctx *ctx, groot_rescue_rec_stats *out);
+
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
  * the device, bit for bit in boot_count, alpha and iterations.  Quoted from there: draw j (0 <= j < n_draws; n_draws = 0 means N, the sum

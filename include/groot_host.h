@@ -259,6 +259,27 @@ void groot_reads_close(groot_reads *r);
 int groot_bam_write_batch(groot_bam *bam, const groot_index_view *idx, const groot_reads_view *reads, uint32_t first_read_id,
                           const groot_trav *travs, const void *masks, const uint32_t *mask_ckpt, uint64_t n_trav, uint64_t *n_records);
 
+/* Rescued records (defined at groot_hip_rescue_rec_enable in groot_hip.h): one kept placement of a read that mismatch rescue placed --
+ * batch-relative read, global path, 0-based path coordinate, strand, the distance d and the d offsets in the ORIENTED read (the read for
+ * strand 0, its reverse complement for strand 1) at which it differs from the path, ascending, the rest 0xFFFF. */
+typedef struct groot_rescue_record {
+    uint32_t read, path, pos;
+    uint16_t mm[3];
+    uint8_t strand, d;
+} groot_rescue_record;   /* 20 bytes */
+/* One BAM record per rescued record of a batch, in list order (groot_hip_rescue_rec_batch: ascending by read, path, strand, pos), through
+ * the record formatter and the BGZF path of the writer above, into a BAM opened with groot_bam_open:
+ *   QNAME the read's name; FLAG 0x10 for strand 1, 0x100 on every record of a read but its first in the list; MAPQ 30; CIGAR <len>M, no
+ *   clips; SEQ / QUAL oriented as a reverse record's are (reverse complement / reversed for strand 1); no mate; and two aux tags that
+ *   the main BAM does not have: NM:i:d (written as a uint8), and MD:Z: the standard string -- the run of matching bases, then for every
+ *   mismatch the PATH's base at pos + mm[i] and the next run, a run of 0 at either end and between neighbours included.
+ * The path's bases come from the index view (a base outside every node of the path reads 'N').  GROOT_E_INVALID, with nothing of the
+ * call written, for a record whose read is not in the batch, whose path is not in the index, that does not lie inside the path
+ * (pos + len > path_len), with strand > 1, d > 3, or with offsets that are not d ascending values below the read's length followed by
+ * 0xFFFF; GROOT_E_FORMAT for a name above 254 characters.  *n_records = records written. */
+int groot_bam_write_rescued(groot_bam *bam, const groot_index_view *idx, const groot_reads_view *reads, const groot_rescue_record *recs,
+                            uint64_t n, uint64_t *n_records);
+
 /* ---- packing reads for groot_hip_submit_packed (include/groot_hip.h) ------------------------------------ */
 /* packed[(n_bases+3)/4]; exceptions (bytes other than A C G T, e.g. N or lower case) in ascending position, at most
  * exc_cap of them: GROOT_E_NOSPACE with *n_exc = the number needed otherwise.  n_threads 0 = all cores. */
