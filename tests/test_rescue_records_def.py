@@ -75,6 +75,41 @@ def test_a_palindrome_on_both_strands_by_hand(case):
     ]
 
 
+def test_a_palindromic_repeat_by_hand(case):
+    """path 0 = U . (ACGT) x 16 . V, first Position 3: the repeat is its own reverse complement, so a read from it lies on both strands.  M = 1.
+    read 0: (ACGT) x 12 with base 5 changed.  Strand 0: the repeat has room for it at s, s + 4 .. s + 16 (s = 3 + 20), offset 5.  Strand 1:
+            the oriented read is (ACGT) x 12 with base 47 - 5 changed, at the same five pos.  ALL of strand 0 comes before strand 1: in
+            (path, pos, strand) order the ten records would alternate.
+    read 1: (CGTA) x 12 with its first base changed.  Strand 0 at s + 1, s + 5, s + 9, s + 13; its reverse complement is (TACG) x 12 with its
+            LAST base changed, at s + 3 .. s + 15: the strands interleave in pos, and the list does not."""
+    u, v = b"GGATCCTTAGGCATTGACCG", b"TTGACCGTAAGC"
+    text = u + b"ACGT" * 16 + v
+    w0, w1 = b"ACGT" * 12, b"CGTA" * 12
+    assert len(text) == 96 and w0[5:6] == b"C" and _rc(b"ACGT" * 16) == b"ACGT" * 16 and _rc(w1) == b"TACG" * 12
+    reads = [w0[:5] + b"A" + w0[6:], b"T" + w1[1:]]
+    assert _rc(reads[0]) == w0[:42] + b"T" + w0[43:] and _rc(reads[1]) == _rc(w1)[:47] + b"A"
+    assert _hand(case, [(text, 3)], [99], reads, 1) == [
+        (0, 0, 23, 0, 1, (5, F, F)),
+        (0, 0, 27, 0, 1, (5, F, F)),
+        (0, 0, 31, 0, 1, (5, F, F)),
+        (0, 0, 35, 0, 1, (5, F, F)),
+        (0, 0, 39, 0, 1, (5, F, F)),
+        (0, 0, 23, 1, 1, (42, F, F)),
+        (0, 0, 27, 1, 1, (42, F, F)),
+        (0, 0, 31, 1, 1, (42, F, F)),
+        (0, 0, 35, 1, 1, (42, F, F)),
+        (0, 0, 39, 1, 1, (42, F, F)),
+        (1, 0, 24, 0, 1, (0, F, F)),
+        (1, 0, 28, 0, 1, (0, F, F)),
+        (1, 0, 32, 0, 1, (0, F, F)),
+        (1, 0, 36, 0, 1, (0, F, F)),
+        (1, 0, 26, 1, 1, (47, F, F)),
+        (1, 0, 30, 1, 1, (47, F, F)),
+        (1, 0, 34, 1, 1, (47, F, F)),
+        (1, 0, 38, 1, 1, (47, F, F)),
+    ]
+
+
 def test_records_hold_every_class(case):
     """every class of record the device test relies on occurs at least FLOOR times in the batch"""
     rec = case.records(2)
@@ -82,6 +117,10 @@ def test_records_hold_every_class(case):
     mm = rec["mm"].astype(np.int64)
     print("records", len(rec), "reads", len(np.unique(rec["read"])))
     assert np.array_equal(rec, np.sort(rec, order=["read", "path", "strand", "pos"]))
+    # this batch cannot tell that order from (read, path, pos, strand): where one read has both strands on one path -- the palindrome of
+    # graph 7 -- they lie at the same pos.  tests/test_rescue_records_shapes.py has the reads that can, and the floor for them
+    other = np.sort(rec, order=["read", "path", "pos", "strand"])
+    print("reads whose records differ under (read, path, pos, strand) order", len(np.unique(rec["read"][rec != other])))
     for d in (0, 1, 2):
         assert int((rec["d"] == d).sum()) >= FLOOR, d
     assert int((case.records(3)["d"] == 3).sum()) >= FLOOR

@@ -184,6 +184,49 @@ def test_library_on_random_records(case, tmp_path):
     assert any(a[3] & 0x100 for a in aux) and any(a[3] & 0x10 for a in aux)
 
 
+def test_library_on_long_and_palindromic_records(tmp_path_factory, native_libs, tmp_path):
+    """the definition's records of tests/rescue_records_shapes_case.py (M = 2) with their own reads through the library's writer, in two
+    calls split at a read boundary: byte for byte the restatement -- MD runs of three digits, SEQ / QUAL of 512 bases reversed, a hundred
+    records of one read of which one is primary, and both strands of one read at one (path, pos)"""
+    import re
+
+    import rescue_records_shapes_case as shapes
+    from rescue_def import path_texts
+    from rescue_records_def import plain
+
+    c = shapes.build(tmp_path_factory)[0]
+    rec = c.records(2)
+    texts = path_texts(c.index)
+    rng = np.random.default_rng(24)
+    names = [b"%s:%d" % (n.encode(), i) for i, n in enumerate(c.names)]
+    quals = [bytes(rng.integers(33, 74, len(r) if i % 5 else len(r) // 2).astype(np.uint8)) for i, r in enumerate(c.reads)]
+    cut = int(np.searchsorted(rec["read"], rec["read"][len(rec) // 2]))
+    assert 0 < cut < len(rec) and rec["read"][cut - 1] != rec["read"][cut]
+    out = str(tmp_path / "shapes.bam")
+    w = host.BamWriter(out, c.index, date="2020-01-01T00:00:00Z")
+    want = b""
+    for part in (rec[:cut], rec[cut:]):
+        assert w.write_rescued(part, names, c.reads, quals) == len(part)
+        want += records_py(names, c.reads, quals, plain(part), lambda p, y: texts[p][0][y - texts[p][1]])
+    w.close()
+    records = split_bam(out)[2]
+    assert records == want
+    aux = aux_of(records)
+    assert len(aux) == len(rec)
+    length = {n.decode(): len(r) for n, r in zip(names, c.reads)}
+    assert max(int(x) for a in aux for x in re.findall(r"\d+", a[4]["MD"])) >= 256
+    assert any(a[3] & 0x10 and length[a[0]] == 512 and a[4]["NM"] for a in aux)
+    flags = {}
+    for a in aux:
+        flags.setdefault(a[0], []).append(a[3])
+    most = max(flags.values(), key=len)
+    assert len(most) >= 100 and all(sum(not f & 0x100 for f in v) == 1 and not v[0] & 0x100 for v in flags.values())
+    at = {}
+    for a in aux:
+        at.setdefault(a[:3], set()).add(a[3] & 0x10)
+    assert sum(len(v) == 2 for v in at.values()) >= 10
+
+
 def test_library_refuses_what_the_program_refuses(case, tmp_path):
     w = host.BamWriter(str(tmp_path / "x.bam"), case.index, date="2020-01-01T00:00:00Z")
     L = 40
