@@ -61,6 +61,8 @@ public:
             if (int rc = groot_hip_rescue_rec_enable(ctx, a_.rescued_bam_slots_given ? (uint64_t)a_.rescued_bam_slots : 16ull * std::max<uint32_t>(a_.batch, 1u))) return rc;
         if (plan_.indels && on)     // (off: gapped rescue goes with rescue)
             if (int rc = groot_hip_gap_enable(ctx, (uint32_t)a_.rescue_gap, (uint64_t)a_.gap_event_slots)) return rc;
+        if (plan_.rescued_bam_gaps && on)   // behind gapped rescue (off: the gapped records go with it)
+            if (int rc = groot_hip_gap_rec_enable(ctx, a_.gap_record_slots_given ? (uint64_t)a_.gap_record_slots : 4ull * std::max<uint32_t>(a_.batch, 1u))) return rc;
         if (plan_.shared)
             if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
         if (plan_.calls && on)

@@ -10,6 +10,7 @@ struct AlignPlan {
     bool ab_rescued = false; // --abundanceRescued: the rescued reads join the equivalence classes
     bool calls_rescued = false; // --callsRescued: and their kept placements the pileup of --calls
     bool rescued_bam = false;   // --rescuedBam: the kept placements of the rescued reads as BAM records in a file of their own
+    bool rescued_bam_gaps = false; // --rescuedBamGaps: and the kept placements of the gap-rescued reads with them
     bool coverage = false;   // report coverage is counted: --report, or --variants / --indels for its exact depth
     bool frags = false;      // --paired / --interleaved
     bool counters = false;   // a ctx carries switches: set at open and reopen, harvested before it closes
@@ -114,6 +115,12 @@ int plan_align(const Args &a, AlignPlan *p)
     if (a.rescued_bam_slots_given && !p->rescued_bam) return refuse("--rescuedBamSlots is the room for the records of --rescuedBam: it needs it");
     if (a.rescued_bam_slots_given && a.rescued_bam_slots < 1) return refuse("--rescuedBamSlots is a number of records per batch, at least 1: %lld", a.rescued_bam_slots);
     if (p->rescued_bam && a.rescued_bam_out == a.bam_out) return refuse("--rescuedBam and --bam name the same file: %s", a.bam_out.c_str());
+    // --rescuedBamGaps: checked behind everything above
+    p->rescued_bam_gaps = a.rescued_bam_gaps;
+    if (p->rescued_bam_gaps && !p->rescued_bam) return refuse("--rescuedBamGaps adds the gap-placed reads to the file of --rescuedBam: it needs it");
+    if (p->rescued_bam_gaps && !p->indels) return refuse("--rescuedBamGaps writes the placements of gapped rescue, which --indels switches on: it needs it");
+    if (a.gap_record_slots_given && !p->rescued_bam_gaps) return refuse("--gapRecordSlots is the room for the records of --rescuedBamGaps: it needs it");
+    if (a.gap_record_slots_given && a.gap_record_slots < 1) return refuse("--gapRecordSlots is a number of records per batch, at least 1: %lld", a.gap_record_slots);
     p->coverage = p->report || p->variants || p->indels;
     p->counters = p->report || p->abundance || p->assign || p->rescue;
     return 0;

@@ -19,6 +19,8 @@ struct WorkItem {
     groot_batch_result res{};
     const groot_rescue_record *rr = nullptr;   // --rescuedBam: the batch's rescued records, in the ctx's pinned memory until the ticket is released
     uint64_t n_rr = 0;
+    const groot_gap_record *gr = nullptr;      // --rescuedBamGaps: and its gapped records, likewise
+    uint64_t n_gr = 0;
 };
 
 template <class T> struct BoundedQueue {
@@ -88,6 +90,7 @@ struct Stream {
     groot_bam *bam = nullptr;
     groot_bam *rescued_bam = nullptr;                 // --rescuedBam
     uint64_t rescued_records = 0, rescued_reads = 0;  // ... what went into it
+    uint64_t gapped_records = 0, gapped_reads = 0;    // --rescuedBamGaps: the gapped records among them, and their reads
     std::vector<std::unique_ptr<Gpu>> gpus;
     std::atomic<bool> gpus_ready{false};
     BoundedQueue<WorkItem> parsed{kParsedAhead};
@@ -266,9 +269,14 @@ bool Stream::collect_one(Gpu &g)
     collect_wait_us += (uint64_t)(seconds_since(tc) * 1e6);
     n_batches++;
     // the reference's panics (short read, RevComplement on a byte > 'T') and over-long reads end the run
+    if (rc == GROOT_E_NOSPACE && plan.rescued_bam_gaps && strstr(groot_hip_last_error(g.ctx), "groot_hip_gap_rec_enable")) {
+        fail_with(std::string(groot_hip_last_error(g.ctx)) + ": give --gapRecordSlots a larger value");
+        return false;
+    }
     if (rc) { fail_with(groot_hip_last_error(g.ctx)); return false; }
     // (asked for here: the ctx is the mapper's, the writer only reads the pinned memory the pointer names)
     if (plan.rescued_bam && groot_hip_rescue_rec_batch(g.ctx, w.res.ticket, &w.rr, &w.n_rr)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
+    if (plan.rescued_bam_gaps && groot_hip_gap_rec_batch(g.ctx, w.res.ticket, &w.gr, &w.n_gr)) { fail_with(groot_hip_last_error(g.ctx)); return false; }
     g.inflight--; g.held++;
     w.gpu = g.index;
     mapped.push(std::move(w));
@@ -353,14 +361,21 @@ void Stream::writer()
                 else if (nrec != c.alignments && !plan.assign)   // (assignment: the counts are the unfiltered run's, the records what it kept)
                     fail_with("internal error: " + std::to_string(nrec) + " records written, " + std::to_string(c.alignments) + " alignments counted");
             }
-            if (rescued_bam && it.n_rr && !failed) {   // right behind the main BAM's batch, in input order
+            if (rescued_bam && (it.n_rr || it.n_gr) && !failed) {   // right behind the main BAM's batch, in input order
                 uint64_t nrec = 0;
                 auto tw = std::chrono::steady_clock::now();
-                const int wrc = groot_bam_write_rescued(rescued_bam, &v, &it.view, it.rr, it.n_rr, &nrec);
+                // (--rescuedBamGaps: the batch's gapped records merged in by read; without it the call and the bytes it always made)
+                const int wrc = plan.rescued_bam_gaps ? groot_bam_write_rescued_gapped(rescued_bam, &v, &it.view, it.rr, it.n_rr, it.gr, it.n_gr, &nrec)
+                                                      : groot_bam_write_rescued(rescued_bam, &v, &it.view, it.rr, it.n_rr, &nrec);
                 bam_s += seconds_since(tw);
                 if (wrc) fail_with(groot_host_last_error());
-                rescued_records += nrec;
-                for (uint64_t i = 0; i < nrec; i++) rescued_reads += i == 0 || it.rr[i].read != it.rr[i - 1].read;
+                else {
+                    rescued_records += nrec;
+                    for (uint64_t i = 0; i < it.n_rr; i++) rescued_reads += i == 0 || it.rr[i].read != it.rr[i - 1].read;
+                    uint64_t gr_reads = 0;
+                    for (uint64_t i = 0; i < it.n_gr; i++) gr_reads += i == 0 || it.gr[i].read != it.gr[i - 1].read;
+                    gapped_records += it.n_gr; gapped_reads += gr_reads; rescued_reads += gr_reads;
+                }
             }
             hand_back(it);
         }

@@ -83,6 +83,9 @@ struct Args {
     std::string rescued_bam_out;           // --rescuedBam: a BAM of its own with one record per kept placement of every read mismatch rescue places
     long long rescued_bam_slots = 0;       // --rescuedBamSlots N: room for that many of them per batch and pipeline slot (0: 16 per read of --batch)
     bool rescued_bam_slots_given = false;
+    bool rescued_bam_gaps = false;         // --rescuedBamGaps: the file of --rescuedBam also holds the reads gapped rescue (--indels) places, with I / D CIGARs
+    long long gap_record_slots = 0;        // --gapRecordSlots N: room for that many of their records per batch and pipeline slot (0: 4 per read of --batch)
+    bool gap_record_slots_given = false;
     std::vector<std::string> fastq;
     int proc = 1, gpu = 0, gpus = 0, ctx_per_gpu = 1, bam_level = -1;
     bool gpu_given = false, write_gob = false;

@@ -40,7 +40,7 @@ void usage()
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
             "                  [--indels i.tsv [--rescueGap 3] [--gapEventSlots 4194304] [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
-            "                  [--rescuedBam r.bam [--rescue 2] [--rescuedBamSlots N]]\n"
+            "                  [--rescuedBam r.bam [--rescue 2] [--rescuedBamSlots N] [--rescuedBamGaps [--gapRecordSlots N]]]\n"
             "                  (BAM goes to stdout unless --bam; --gpus N shards the reads over N GPUs, index replicated;\n"
             "                   --report: the lines of `report` for this run, counted on the GPU; --noBam: no BAM at all (with --report or --abundance);\n"
             "                   --sharedReads: `nameA nameB reads` for every pair of reported ARGs with reads in common;\n"
@@ -78,7 +78,10 @@ void usage()
             "                   places with up to --rescue (1..3) substitutions: FLAG 0x10 for the reverse strand, 0x100 on a read's further placements, CIGAR\n"
             "                   <len>M, NM and MD tags; the main BAM and every other file stay as they are.  --rescuedBamSlots: room for that many records per\n"
             "                   batch on the GPU, 16 per read of --batch unless given (a batch with more fails the run and says so).  Not with --assignFrom or\n"
-            "                   --noAlign;\n"
+            "                   --noAlign;  --rescuedBamGaps (with --indels): the file also holds the reads gapped rescue places with one deletion or\n"
+            "                   insertion of up to --rescueGap bases, one record per placement, merged with the others in read order: CIGAR <k>M<g>D<n>M or\n"
+            "                   <k>M<g>I<n>M, NM = substitutions + gap bases, MD with ^ and the deleted bases.  --gapRecordSlots: room for that many of\n"
+            "                   those records per batch on the GPU, 4 per read of --batch unless given (a batch with more fails the run and names the flag);\n"
             "                   --paired: the -f files are R1,R2[,R1b,R2b...], first with second, third with fourth; --interleaved: the mates alternate in\n"
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
@@ -170,6 +173,13 @@ Args parse(int argc, char **argv)
             const std::string t = v();
             char *end = nullptr;
             a.rescued_bam_slots = strtoll(t.c_str(), &end, 10); a.rescued_bam_slots_given = true;
+            if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
+        }
+        else if (a.cmd == "align" && f == "--rescuedBamGaps") a.rescued_bam_gaps = true;
+        else if (a.cmd == "align" && f == "--gapRecordSlots") {
+            const std::string t = v();
+            char *end = nullptr;
+            a.gap_record_slots = strtoll(t.c_str(), &end, 10); a.gap_record_slots_given = true;
             if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
         }
         else if (a.cmd == "align" && f == "--noBam") a.no_bam = true;
@@ -345,6 +355,9 @@ int run_align(const Args &a)
         if (groot_bam_close(s.rescued_bam)) die("%s", groot_host_last_error());
         logf("\trescued reads: %llu record(s) of %llu read(s) written to %s (up to %ld substitution(s))", (unsigned long long)s.rescued_records,
              (unsigned long long)s.rescued_reads, a.rescued_bam_out.c_str(), a.rescue);
+        if (plan.rescued_bam_gaps)
+            logf("\tgap-placed reads: %llu record(s) of %llu read(s) among them (one gap of up to %ld base(s))", (unsigned long long)s.gapped_records,
+                 (unsigned long long)s.gapped_reads, a.rescue_gap);
     }
     if (plan.counters)                                                                           // 7. harvest
         // every batch has been collected: what each ctx counted is final (it is switched off, so a ctx reopened below starts without it)

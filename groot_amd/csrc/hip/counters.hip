@@ -2,7 +2,7 @@
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
 // draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp), rescued reads in the equivalence
-// classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp), rescued records (kernels_rescue_rec.hpp).  One of the six translation units of
+// classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp), rescued records (kernels_rescue_rec.hpp), gapped records (kernels_gap_rec.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <cstring>   // before rocprim: its texture iterator calls host memset
 
@@ -34,6 +34,7 @@
 #include "kernels_rescue_ec.hpp"
 #include "kernels_rescue_acov.hpp"
 #include "kernels_rescue_rec.hpp"
+#include "kernels_gap_rec.hpp"
 #include "kernels_shared.hpp"
 
 using namespace groot;
@@ -426,6 +427,56 @@ static int rr_collect(groot_ctx *c, Slot *s, bool refetch)
     return GROOT_OK;
 }
 
+// ---- gapped records (kernels_gap_rec.hpp) ----
+// Behind rescue_gap_rec_kernel on the tail stream: as rr_launch, over the reads' kept gapped placements.
+static int gr_launch(groot_ctx *c, Slot *s, const GapRecArgs &ga)
+{
+    Counters &k = c->ct;
+    const size_t n = (size_t)s->n_reads + 1;
+    auto in = rocprim::make_transform_iterator(k.gr_kept.p, KeptToU64());
+    size_t tmp_bytes = 0;
+    HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_bytes, in, k.gr_off.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->tstream));
+    if (tmp_bytes > c->scan_tmp.n) {
+        HIP_TRY(c, hipStreamSynchronize(c->tstream));
+        HIP_TRY(c, c->scan_tmp.alloc(tmp_bytes + tmp_bytes / 4));
+    }
+    HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tmp_bytes, in, k.gr_off.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->tstream));
+    HIP_TRY(c, hipMemcpyAsync(s->ct.d_gr_total.p, k.gr_off.p + s->n_reads, sizeof(uint64_t), hipMemcpyDeviceToDevice, c->tstream));
+    hipLaunchKernelGGL(gap_rec_emit_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
+    HIP_TRY(c, hipGetLastError());
+    k.gr_launches += 2;
+    return GROOT_OK;
+}
+
+// At collect: as rr_collect.  The batch fails alone; its rescued records (rr_collect ran first) and its other results stay readable.
+static int gr_collect(groot_ctx *c, Slot *s, bool refetch)
+{
+    Counters &k = c->ct;
+    s->ct.gr_n = 0;
+    if (!s->ct.gr || !s->n_reads || !s->ct.d_gr_total.p || !k.gr_on) return GROOT_OK;
+    if (refetch) HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->gr_total, s->ct.d_gr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const uint64_t n = s->ct.h_status.p->gr_total;
+    if (!n) return GROOT_OK;
+    if (n > k.gr_slots) {
+        k.gr_failed++;
+        if (s->status == GROOT_OK) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "gapped records: a batch has %llu records, and a pipeline slot has room for %llu (slots_per_batch of groot_hip_gap_rec_enable)",
+                     (unsigned long long)n, (unsigned long long)k.gr_slots);
+            s->status = GROOT_E_NOSPACE;
+            s->status_msg = buf;
+        }
+        return GROOT_OK;
+    }
+    HIP_TRY(c, s->ct.h_gr_rec.reserve(n + n / 4));
+    HIP_TRY(c, hipMemcpy(s->ct.h_gr_rec.p, s->ct.d_gr_rec.p, n * sizeof(groot_gap_record), hipMemcpyDeviceToHost));
+    s->ct.gr_n = n;
+    k.gr_records += n;
+    const groot_gap_record *h = s->ct.h_gr_rec.p;
+    for (uint64_t i = 0; i < n; i++) k.gr_reads += i == 0 || h[i].read != h[i - 1].read;
+    return GROOT_OK;
+}
+
 // ---- the pipeline's hooks (counters.hpp) ---------------------------------------------------------------------------
 namespace groot {
 
@@ -533,6 +584,7 @@ int counters_launch(groot_ctx *c, Slot *s)
             HIP_TRY(c, hipMemsetAsync(k.rr_kept.p, 0, ((size_t)s->n_reads + 1) * sizeof(uint32_t), c->tstream));
         }
         const dim3 gr(grid_for(s->n_reads));
+        GapRecArgs gra{};
         if (!k.gap_on && k.rr_on) {
             if (k.rec_on) hipLaunchKernelGGL((rescue_count_rec_kernel<false, true>), gr, dim3(kBlock), 0, c->tstream, ra);
             else hipLaunchKernelGGL((rescue_count_rec_kernel<false, false>), gr, dim3(kBlock), 0, c->tstream, ra);
@@ -549,13 +601,22 @@ int counters_launch(groot_ctx *c, Slot *s)
             else if (k.rr_on) hipLaunchKernelGGL((rescue_count_rec_kernel<true, false>), gr, dim3(kBlock), 0, c->tstream, ra);
             else if (k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
             else hipLaunchKernelGGL(rescue_count_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
-            hipLaunchKernelGGL(rescue_gap_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
+            if (k.gr_on) {   // gapped records (kernels_gap_rec.hpp): the gap kernel also leaves every read's kept placements and every gap candidate's e*
+                HIP_TRY(c, s->ct.d_gr_rec.reserve((size_t)k.gr_slots * kGapRecWords));
+                HIP_TRY(c, s->ct.d_gr_total.reserve(1));
+                HIP_TRY(c, s->ct.h_status.reserve(1));
+                gra.g = ga; gra.n_gkept = k.gr_kept.p; gra.gap_e = k.gr_e.p; gra.off = k.gr_off.p; gra.rec = s->ct.d_gr_rec.p; gra.cap = k.gr_slots;
+                HIP_TRY(c, hipMemsetAsync(k.gr_kept.p, 0, ((size_t)s->n_reads + 1) * sizeof(uint32_t), c->tstream));
+                hipLaunchKernelGGL(rescue_gap_rec_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, gra);
+            } else hipLaunchKernelGGL(rescue_gap_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
             k.gap_launches++;
         }
         HIP_TRY(c, hipGetLastError());
         k.res_launches += 2;
         if (k.rr_on)
             if (int rc = rr_launch(c, s, ra)) return rc;
+        if (k.gap_on && k.gr_on)
+            if (int rc = gr_launch(c, s, gra)) return rc;
         if (k.rec_on) {      // (ec_reserve above has made room for this merge too: its bound is over both)
             RescueEcArgs ea{};
             ea.r = ra; ea.s = sa;
@@ -599,6 +660,8 @@ int counters_fetch(groot_ctx *c, Slot *s)
     }
     if (s->ct.rr && s->n_reads && c->ct.rr_on && s->ct.d_rr_total.p)
         HIP_TRY(c, hipMemcpyAsync(&s->ct.h_status.p->rr_total, s->ct.d_rr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    if (s->ct.gr && s->n_reads && c->ct.gr_on && s->ct.d_gr_total.p)
+        HIP_TRY(c, hipMemcpyAsync(&s->ct.h_status.p->gr_total, s->ct.d_gr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->d2h_stream));
     if (!c->ct.ec_on) return GROOT_OK;
     CounterStatus *h = s->ct.h_status.p;
     HIP_TRY(c, hipMemcpyAsync(&h->ec_slow, s->ct.d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
@@ -624,6 +687,7 @@ int counters_collect(groot_ctx *c, Slot *s, bool redone)
         }
     }
     if (int rc = rr_collect(c, s, redone)) return rc;
+    if (int rc = gr_collect(c, s, redone)) return rc;
     if (!c->ct.ec_on || !s->n_reads) return GROOT_OK;
     if (int rc = ec_collect(c, s, redone)) return rc;
     if (c->ct.rec_on)
@@ -1261,6 +1325,19 @@ static void rr_release(groot_ctx *c)
     k.rr_records = k.rr_reads = k.rr_failed = 0;
 }
 
+// gapped records off: as rr_release
+static void gr_release(groot_ctx *c)
+{
+    Counters &k = c->ct;
+    k.gr_kept.release(); k.gr_off.release(); k.gr_e.release();
+    for (auto &s : c->slots) {
+        s->ct.d_gr_rec.release(); s->ct.d_gr_total.release(); s->ct.h_gr_rec.release();
+        s->ct.gr = false; s->ct.gr_n = 0;
+    }
+    k.gr_on = false; k.gr_slots = 0;
+    k.gr_records = k.gr_reads = k.gr_failed = 0;
+}
+
 static void rescue_release(Counters &k)
 {
     gap_release(k);                        // (gapped rescue looks at what rescue leaves: off with it)
@@ -1291,6 +1368,7 @@ int groot_hip_rescue_enable(groot_ctx *c, const groot_index_view *idx, uint32_t 
     Counters &k = c->ct;
     if (!max_mismatch) {
         rr_release(c);                     // (the rescued records are rescue's placements: off with it)
+        gr_release(c);                     // (and the gapped records gapped rescue's, which goes off below)
         rescue_release(k);
         return GROOT_OK;
     }
@@ -1401,6 +1479,7 @@ int groot_hip_gap_enable(groot_ctx *c, uint32_t max_gap, uint64_t event_slots)
     HIP_TRY(c, hipSetDevice(c->device));
     Counters &k = c->ct;
     if (!max_gap) {
+        gr_release(c);                     // (the gapped records are gapped rescue's placements: off with it)
         gap_release(k);
         return GROOT_OK;
     }
@@ -1430,6 +1509,7 @@ int groot_hip_gap_enable(groot_ctx *c, uint32_t max_gap, uint64_t event_slots)
         e = gap_zero(k);
     }
     if (e != hipSuccess) {
+        gr_release(c);
         gap_release(k);
         return fail(c, GROOT_E_DEVICE, "gapped rescue: %s", hipGetErrorString(e));
     }
@@ -1663,6 +1743,52 @@ int groot_hip_rescue_rec_stats(groot_ctx *c, groot_rescue_rec_stats *out)
     out->records = k.rr_on ? k.rr_records : 0; out->reads = k.rr_on ? k.rr_reads : 0; out->failed = k.rr_on ? k.rr_failed : 0;
     out->slots = k.rr_on ? k.rr_slots : 0;
     out->launches = k.rr_launches;
+    return GROOT_OK;
+}
+
+// ---- gapped records (kernels_gap_rec.hpp; the definition is in groot_hip.h) ----------------------------------------------------
+static_assert(sizeof(groot_gap_record) == kGapRecWords * sizeof(uint32_t) && offsetof(groot_gap_record, k) == 12 && offsetof(groot_gap_record, mm) == 14 &&
+              offsetof(groot_gap_record, strand) == 20 && offsetof(groot_gap_record, d) == 21 && offsetof(groot_gap_record, type) == 22 &&
+              offsetof(groot_gap_record, g) == 23, "gap_rec_emit_kernel writes groot_gap_record as six dwords");
+
+int groot_hip_gap_rec_enable(groot_ctx *c, uint64_t slots_per_batch)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "gapped records can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!slots_per_batch) {
+        gr_release(c);
+        return GROOT_OK;
+    }
+    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gapped records are the placements of gapped rescue, and that is off (groot_hip_gap_enable)");
+    if (slots_per_batch > (1ull << 40) / sizeof(groot_gap_record)) return fail(c, GROOT_E_INVALID, "gapped records: slots_per_batch %llu is beyond 2^40 bytes", (unsigned long long)slots_per_batch);
+    if (k.gr_on && slots_per_batch == k.gr_slots) return GROOT_OK;
+    gr_release(c);
+    const size_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+    hipError_t e = k.gr_kept.alloc(R + 1);
+    if (e == hipSuccess) e = k.gr_off.alloc(R + 1);
+    if (e == hipSuccess) e = k.gr_e.alloc(R);
+    for (auto &s : c->slots) {             // (now, and not at the first launch: no room is an error of this call)
+        if (e == hipSuccess) e = s->ct.d_gr_rec.alloc((size_t)slots_per_batch * kGapRecWords);
+        if (e == hipSuccess) e = s->ct.d_gr_total.alloc(1);
+    }
+    if (e != hipSuccess) {
+        gr_release(c);
+        return fail(c, GROOT_E_DEVICE, "gapped records: %s", hipGetErrorString(e));
+    }
+    k.gr_slots = slots_per_batch;
+    k.gr_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_gap_rec_stats(groot_ctx *c, groot_gap_rec_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    const Counters &k = c->ct;
+    out->records = k.gr_on ? k.gr_records : 0; out->reads = k.gr_on ? k.gr_reads : 0; out->failed = k.gr_on ? k.gr_failed : 0;
+    out->slots = k.gr_on ? k.gr_slots : 0;
+    out->launches = k.gr_launches;
     return GROOT_OK;
 }
 

@@ -134,6 +134,7 @@ struct CounterStatus {
     uint32_t rec_slow;                     // rescued reads in the ECs: the batch's slow rescued reads (SlotCounters::d_rec_slow[0])
     uint32_t rac_log;                      // rescued reads in assigned coverage: the kept placements of those reads (SlotCounters::d_rac_nlog[0])
     uint64_t rr_total;                     // rescued records: the batch's records (SlotCounters::d_rr_total[0])
+    uint64_t gr_total;                     // gapped records: the batch's records (SlotCounters::d_gr_total[0])
 };
 
 struct SlotCounters {
@@ -155,6 +156,11 @@ struct SlotCounters {
     PinBuf<groot_rescue_record> h_rr_rec;  // what groot_hip_rescue_rec_batch hands out: as many as the batch has
     uint64_t rr_n = 0;                     // the batch's records in h_rr_rec
     bool rr = false;                       // the feature was on when the batch was submitted
+    DevBuf<uint32_t> d_gr_rec;             // gapped records: [gr_slots][6 dwords] the batch's records (gap_rec_emit_kernel), copied out at collect
+    DevBuf<uint64_t> d_gr_total;           // [0] their number, whether they found room or not (the scan's last output)
+    PinBuf<groot_gap_record> h_gr_rec;     // what groot_hip_gap_rec_batch hands out: as many as the batch has
+    uint64_t gr_n = 0;                     // the batch's records in h_gr_rec
+    bool gr = false;                       // the feature was on when the batch was submitted
 };
 
 struct Counters {
@@ -252,6 +258,16 @@ struct Counters {
     DevBuf<uint8_t> rr_d;                  // RescueArgs::rec_d
     uint64_t rr_records = 0, rr_reads = 0, rr_failed = 0;   // handed out / rescued reads among them / batches failed for room, since enable
     uint64_t rr_launches = 0;              // the scan and rescue_rec_emit_kernel since open (rescue_count_rec_kernel counts as rescue's)
+    // gapped records (groot_hip_gap_rec_*, kernels_gap_rec.hpp): needs gapped rescue on.  rescue_gap_rec_kernel takes rescue_gap_kernel's
+    // place and also leaves every read's number of kept gapped placements, a scan and gap_rec_emit_kernel behind it write the batch's
+    // records into a buffer of the slot, and collect copies as many as there are into pinned memory.  Nothing on the device while off.
+    bool gr_on = false;
+    uint64_t gr_slots = 0;                 // records per batch (fixed at enable)
+    DevBuf<uint32_t> gr_kept;              // GapRecArgs::n_gkept (tail stream: one batch at a time, as the gap candidates are)
+    DevBuf<uint64_t> gr_off;               // GapRecArgs::off
+    DevBuf<uint8_t> gr_e;                  // GapRecArgs::gap_e
+    uint64_t gr_records = 0, gr_reads = 0, gr_failed = 0;   // handed out / gap-rescued reads among them / batches failed for room, since enable
+    uint64_t gr_launches = 0;              // the scan and gap_rec_emit_kernel since open (rescue_gap_rec_kernel counts as gapped rescue's)
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

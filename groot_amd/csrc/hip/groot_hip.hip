@@ -650,6 +650,7 @@ int groot::enqueue(groot_ctx *c, Slot *s)
     s->lean_used = s->path_used = false; s->path_reads = 0;   // (an empty batch runs no stage: not what the slot's last batch left)
     s->ct.assigned = c->ct.asg_on;                            // (likewise, and for a batch that fails ahead of the order stage)
     s->ct.rr = c->ct.rr_on; s->ct.rr_n = 0;                   // (rescued records: an empty batch has none)
+    s->ct.gr = c->ct.gr_on; s->ct.gr_n = 0;                   // (gapped records likewise)
     if (s->n_reads == 0) {      // nothing to run: completes at once
         memset(s->h_ctr.p, 0, sizeof(DeviceCounters));
         HIP_TRY(c, hipEventRecord(s->ev_ctr, c->d2h_stream));
@@ -1401,6 +1402,17 @@ int groot_hip_rescue_rec_batch(groot_ctx *c, uint64_t ticket, const groot_rescue
     if (!s->ct.rr) return fail(c, GROOT_E_STATE, "rescued records were off when the batch was submitted (groot_hip_rescue_rec_enable)");
     *recs = s->ct.rr_n ? s->ct.h_rr_rec.p : nullptr;
     *n = s->ct.rr_n;
+    return GROOT_OK;
+}
+
+int groot_hip_gap_rec_batch(groot_ctx *c, uint64_t ticket, const groot_gap_record **recs, uint64_t *n)
+{
+    if (!c || !recs || !n) return GROOT_E_INVALID;
+    Slot *s = ticket ? slot_by_ticket(c, ticket, Slot::COLLECTED) : c->waited;
+    if (!s) return fail(c, GROOT_E_STATE, "ticket %llu is not a collected batch", (unsigned long long)ticket);
+    if (!s->ct.gr) return fail(c, GROOT_E_STATE, "gapped records were off when the batch was submitted (groot_hip_gap_rec_enable)");
+    *recs = s->ct.gr_n ? s->ct.h_gr_rec.p : nullptr;
+    *n = s->ct.gr_n;
     return GROOT_OK;
 }
 

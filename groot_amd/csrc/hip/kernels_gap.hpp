@@ -14,7 +14,8 @@
 //                      for (d, k*) visits set bits, in ascending order, and a strict `<` keeps the smallest k.  Sweep 1 keeps the smallest
 //                      e = d + g, sweep 2 adds the tuples at e*.  A tuple is reached through (block i, hypothesis h) exactly when block i
 //                      equals the text on h's diagonal and lies in the window W; sweep 2 counts it only through the lowest such (i, h), so
-//                      every tuple counts once without a sort.  gdepth: starts / ends in report coverage's layout with plain atomicAdd (a
+//                      every tuple counts once without a sort (gap_sweep: the walk of either sweep, which the emit kernel of the
+//                      gapped records, kernels_gap_rec.hpp, takes a third time at e*; rescue_gap_body: the kernel with a sink).  gdepth: starts / ends in report coverage's layout with plain atomicAdd (a
 //                      DEL adds two intervals).  Events: an open-addressing table, key claimed with atomicCAS, count with atomicAdd.
 // Integer sums only: the tables do not depend on the order of the candidates, of the wavefronts or of the batches; the table's slot
 // order does, the export sorts.
@@ -124,7 +125,58 @@ __device__ __forceinline__ bool gap_block_in(uint32_t i, uint32_t h, uint32_t in
     return !ins || (h ? i >= 1u : kRescueAnchor * i + kRescueAnchor + g <= len);
 }
 
-__global__ __launch_bounds__(kBlock) void rescue_gap_kernel(GapArgs ga)
+// what a sweep-2 walk tells of every kept tuple beyond the tables: nothing here, their number per read for the gapped records
+// (kernels_gap_rec.hpp)
+struct GapNoSink {
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void kept() {}
+    __device__ __forceinline__ void done(uint32_t, uint32_t, uint32_t, bool) {}
+};
+
+// One sweep over the tuples of the oriented reads at w0 (len bases): occurrence x hypothesis x type x g.  Sweep 0 lowers `best` to the
+// smallest e = d + g.  Sweep 1 calls f(path, its res_path entry, strand, x, ins, g, k*, d, the oriented read) for every tuple at
+// e = best, each once: only through the lowest (block, hypothesis) that reaches it.  rescue_gap_kernel's second sweep and
+// gap_rec_emit_kernel (kernels_gap_rec.hpp) are this one walk: the same tuples in the same order.
+template <class F> __device__ __forceinline__ void gap_sweep(const RescueArgs &a, uint32_t G, uint64_t w0, uint32_t len, uint32_t sweep, uint32_t &best, F &&f)
+{
+    const uint32_t M = a.max_mismatch, nb = len / kRescueAnchor;
+    for (uint32_t strand = 0; strand < 2u; strand++) {
+        const unsigned long long *rd = a.rbuf + strand * a.rcap + w0;
+        for (uint32_t j = 0; j < nb; j++) {
+            const uint32_t key = (uint32_t)(rd[j >> 1] >> (32u * (j & 1u)));
+            uint32_t slot = rescue_hash(key) & a.tab_mask;
+            uint4 e = a.tab[slot];
+            while (e.z && e.x != key) { slot = (slot + 1u) & a.tab_mask; e = a.tab[slot]; }
+            for (uint32_t q = e.y; q < e.y + e.z; q++) {
+                const uint2 oc = a.occ[q];
+                const uint4 pi = a.path[oc.x];                  // {text start, bases inside path_len, first Position, 0}
+                const int t0 = (int)(oc.y - pi.x) - (int)(kRescueAnchor * j);      // x under the hypothesis "in front of the gap"
+                for (uint32_t v = 0; v < 4u * G; v++) {         // hypothesis, type, g
+                    const uint32_t h = v & 1u, ins = (v >> 1) & 1u, g = (v >> 2) + 1u;
+                    if (!gap_block_in(j, h, ins, g, len)) continue;
+                    const int x = t0 - (h ? (ins ? -(int)g : (int)g) : 0);
+                    if (x < 0 || (uint32_t)x + (ins ? len - g : len + g) > pi.y) continue;      // W would hang over an end of the path
+                    if (g > best) continue;                     // e = d + g >= g
+                    uint32_t ks;
+                    const uint32_t d = gap_fit(a, rd, len, pi.x + (uint32_t)x, ins, g, min(M, best - g), ks);
+                    if (d == kRescueNone) continue;
+                    if (sweep == 0) { best = min(best, d + g); continue; }
+                    if (d + g != best) continue;
+                    bool lower = false;                         // a lower (block, hypothesis) reaches the tuple as well: it counts it
+                    for (uint32_t i = 0; i <= j && !lower; i++)
+                        for (uint32_t hh = 0; hh < (i < j ? 2u : h); hh++)
+                            if (gap_block_in(i, hh, ins, g, len) &&
+                                gap_block_at(a, rd, i, (uint32_t)((int)(pi.x + (uint32_t)x + kRescueAnchor * i) + (hh ? (ins ? -(int)g : (int)g) : 0))))
+                                lower = true;
+                    if (lower) continue;
+                    f(oc.x, pi, strand, (uint32_t)x, ins, g, ks, d, rd);
+                }
+            }
+        }
+    }
+}
+
+template <class Sink> __device__ __forceinline__ void rescue_gap_body(const GapArgs &ga, Sink sink)
 {
     const RescueArgs &a = ga.r;
     if (a.ctr->flags & kCovSkipFlags) return;
@@ -134,65 +186,43 @@ __global__ __launch_bounds__(kBlock) void rescue_gap_kernel(GapArgs ga)
     for (uint32_t c = blockIdx.x * kBlock + threadIdx.x; c < n; c += gridDim.x * kBlock) {
         const uint32_t r = ga.gcand[c];
         const uint64_t o = a.seq_off[r];
-        const uint32_t len = (uint32_t)(a.seq_off[r + 1] - o), nb = len / kRescueAnchor;
+        const uint32_t len = (uint32_t)(a.seq_off[r + 1] - o);
         const uint64_t w0 = ((o - off0) >> 5) + r;
         uint32_t best = M + G + 1u;        // e*
+        sink.begin();
         for (uint32_t sweep = 0; sweep < 2u && (sweep == 0 || best <= M + G); sweep++)
-            for (uint32_t strand = 0; strand < 2u; strand++) {
-                const unsigned long long *rd = a.rbuf + strand * a.rcap + w0;
-                for (uint32_t j = 0; j < nb; j++) {
-                    const uint32_t key = (uint32_t)(rd[j >> 1] >> (32u * (j & 1u)));
-                    uint32_t slot = rescue_hash(key) & a.tab_mask;
-                    uint4 e = a.tab[slot];
-                    while (e.z && e.x != key) { slot = (slot + 1u) & a.tab_mask; e = a.tab[slot]; }
-                    for (uint32_t q = e.y; q < e.y + e.z; q++) {
-                        const uint2 oc = a.occ[q];
-                        const uint4 pi = a.path[oc.x];                  // {text start, bases inside path_len, first Position, 0}
-                        const int t0 = (int)(oc.y - pi.x) - (int)(kRescueAnchor * j);      // x under the hypothesis "in front of the gap"
-                        for (uint32_t v = 0; v < 4u * G; v++) {         // hypothesis, type, g
-                            const uint32_t h = v & 1u, ins = (v >> 1) & 1u, g = (v >> 2) + 1u;
-                            if (!gap_block_in(j, h, ins, g, len)) continue;
-                            const int x = t0 - (h ? (ins ? -(int)g : (int)g) : 0);
-                            if (x < 0 || (uint32_t)x + (ins ? len - g : len + g) > pi.y) continue;      // W would hang over an end of the path
-                            if (g > best) continue;                     // e = d + g >= g
-                            uint32_t ks;
-                            const uint32_t d = gap_fit(a, rd, len, pi.x + (uint32_t)x, ins, g, min(M, best - g), ks);
-                            if (d == kRescueNone) continue;
-                            if (sweep == 0) { best = min(best, d + g); continue; }
-                            if (d + g != best) continue;
-                            bool lower = false;                         // a lower (block, hypothesis) reaches the tuple as well: it counts it
-                            for (uint32_t i = 0; i <= j && !lower; i++)
-                                for (uint32_t hh = 0; hh < (i < j ? 2u : h); hh++)
-                                    if (gap_block_in(i, hh, ins, g, len) &&
-                                        gap_block_at(a, rd, i, (uint32_t)((int)(pi.x + (uint32_t)x + kRescueAnchor * i) + (hh ? (ins ? -(int)g : (int)g) : 0))))
-                                        lower = true;
-                            if (lower) continue;
-                            st[1]++;
-                            st[2] += 1u - ins;
-                            st[3] += ins;
-                            const uint64_t at = a.slot_base[oc.x] + pi.z + (uint32_t)x;
-                            atomicAdd(ga.starts + at, 1ull);
-                            uint32_t seq = 0;
-                            if (ins) {
-                                atomicAdd(ga.ends + at + len - g, 1ull);
-                                for (uint32_t i = 0; i < g; i++) {
-                                    const uint32_t code = (uint32_t)(rd[(ks + i) >> 5] >> (2u * ((ks + i) & 31u))) & 3u;
-                                    seq |= (code ^ (code >> 1)) << (2u * i);      // A C T G -> A C G T
-                                }
-                            } else {
-                                atomicAdd(ga.ends + at + ks, 1ull);
-                                atomicAdd(ga.starts + at + ks + g, 1ull);
-                                atomicAdd(ga.ends + at + len + g, 1ull);
-                            }
-                            gap_event_add(ga, gap_event_key(at + ks - 1u, ins, g, seq));
-                        }
+            gap_sweep(a, G, w0, len, sweep, best, [&](uint32_t p, const uint4 &pi, uint32_t, uint32_t x, uint32_t ins, uint32_t g, uint32_t ks, uint32_t, const unsigned long long *rd) {
+                st[1]++;
+                st[2] += 1u - ins;
+                st[3] += ins;
+                sink.kept();
+                const uint64_t at = a.slot_base[p] + pi.z + x;
+                atomicAdd(ga.starts + at, 1ull);
+                uint32_t seq = 0;
+                if (ins) {
+                    atomicAdd(ga.ends + at + len - g, 1ull);
+                    for (uint32_t i = 0; i < g; i++) {
+                        const uint32_t code = (uint32_t)(rd[(ks + i) >> 5] >> (2u * ((ks + i) & 31u))) & 3u;
+                        seq |= (code ^ (code >> 1)) << (2u * i);      // A C T G -> A C G T
                     }
+                } else {
+                    atomicAdd(ga.ends + at + ks, 1ull);
+                    atomicAdd(ga.starts + at + ks + g, 1ull);
+                    atomicAdd(ga.ends + at + len + g, 1ull);
                 }
-            }
+                gap_event_add(ga, gap_event_key(at + ks - 1u, ins, g, seq));
+            });
         if (best <= M + G) st[0]++;
+        sink.done(c, r, best, best <= M + G);
     }
     const uint32_t where[4] = {1, 2, 3, 4};
     rescue_add_stats(ga.stats, st, where);
+}
+
+// the kernel launched while the gapped records are off; rescue_gap_rec_kernel (kernels_gap_rec.hpp) is the same body with a sink
+__global__ __launch_bounds__(kBlock) void rescue_gap_kernel(GapArgs ga)
+{
+    rescue_gap_body(ga, GapNoSink());
 }
 
 } // namespace groot

@@ -646,10 +646,12 @@ static char path_base(const groot_bam *b, const groot_index_view *ix, uint32_t p
     return at < ix->node_seq_off[n + 1] - ix->node_seq_off[n] ? (char)ix->bases[ix->node_seq_off[n] + at] : 'N';
 }
 
-int groot_bam_write_rescued(groot_bam *b, const groot_index_view *ix, const groot_reads_view *rv, const groot_rescue_record *recs, uint64_t n, uint64_t *n_records)
+// both writers: the two lists of a batch merged by read (ng = 0: the rescued records alone, byte for byte what they always were)
+static int write_rescued_impl(groot_bam *b, const groot_index_view *ix, const groot_reads_view *rv, const groot_rescue_record *recs, uint64_t n,
+                              const groot_gap_record *grecs, uint64_t ng, uint64_t *n_records)
 {
     if (n_records) *n_records = 0;
-    if (!b || !ix || !rv || (n && !recs)) return set_error(GROOT_E_INVALID, "null argument");
+    if (!b || !ix || !rv || (n && !recs) || (ng && !grecs)) return set_error(GROOT_E_INVALID, "null argument");
     // everything is checked before anything is written: a refused call leaves the stream as it was
     for (uint64_t i = 0; i < n; i++) {
         const groot_rescue_record &r = recs[i];
@@ -665,7 +667,31 @@ int groot_bam_write_rescued(groot_bam *b, const groot_index_view *ix, const groo
         }
         if (rv->name_len[r.read] > 254) return set_error(GROOT_E_FORMAT, "read name longer than 254 characters");
     }
-    if (!n) return GROOT_OK;
+    for (uint64_t i = 0; i < ng; i++) {
+        const groot_gap_record &r = grecs[i];
+        const unsigned long long at = i;
+        if (r.read >= rv->n_reads) return set_error(GROOT_E_INVALID, "gapped record %llu: read %u of a batch of %u", at, r.read, rv->n_reads);
+        if (r.path >= ix->n_paths || r.path >= b->n_ref) return set_error(GROOT_E_INVALID, "gapped record %llu: path %u of %u", at, r.path, ix->n_paths);
+        if (r.strand > 1 || r.d > 3 || r.type > 1 || r.g < 1 || r.g > 8)
+            return set_error(GROOT_E_INVALID, "gapped record %llu: strand %u, distance %u, type %u, gap %u", at, r.strand, r.d, r.type, r.g);
+        const uint32_t len = rv->seq_len[r.read], ins = r.type, aligned = ins ? (len > r.g ? len - r.g : 0u) : len;
+        const uint64_t span = ins ? aligned : (uint64_t)len + r.g;
+        if (!aligned || (uint64_t)r.pos + span > ix->path_len[r.path])
+            return set_error(GROOT_E_INVALID, "gapped record %llu: %llu bases at %u do not lie inside path %u of %u bases", at, (unsigned long long)span, r.pos, r.path, ix->path_len[r.path]);
+        if (r.k < 16 || r.k > aligned || aligned - r.k < 16)
+            return set_error(GROOT_E_INVALID, "gapped record %llu: %u of %u aligned bases in front of the gap, at least 16 on either side are needed", at, r.k, aligned);
+        for (uint32_t k = 0; k < 3; k++) {
+            const bool ok = k >= r.d ? r.mm[k] == 0xFFFF
+                                     : r.mm[k] < len && (k == 0 || r.mm[k] > r.mm[k - 1]) && !(ins && r.mm[k] >= r.k && r.mm[k] < (uint32_t)r.k + r.g);
+            if (!ok) return set_error(GROOT_E_INVALID, "gapped record %llu: offset %u of %u is %u in a read of %u bases with its gap at %u", at, k, r.d, r.mm[k], len, r.k);
+        }
+        if (rv->name_len[r.read] > 254) return set_error(GROOT_E_FORMAT, "read name longer than 254 characters");
+    }
+    for (uint64_t i = 0, j = 0; i < n && j < ng;) {          // both ascending by read: a read has records of one kind
+        if (recs[i].read == grecs[j].read) return set_error(GROOT_E_INVALID, "read %u has rescued records and gapped records", recs[i].read);
+        if (recs[i].read < grecs[j].read) i++; else j++;
+    }
+    if (!n && !ng) return GROOT_OK;
     if (!b->have_path_nodes) {
         b->path_nodes.assign(ix->n_paths, {});
         for (uint32_t g = 0; g < ix->n_graphs; g++)
@@ -680,16 +706,17 @@ int groot_bam_write_rescued(groot_bam *b, const groot_index_view *ix, const groo
     RawBuf raw;
     std::vector<uint8_t> rcs, rcq, padq;
     std::string md;
-    for (uint64_t i = 0; i < n; i++) {
-        const groot_rescue_record &r = recs[i];
-        const uint32_t len = rv->seq_len[r.read], ql_have = std::min<uint32_t>(rv->qual_len[r.read], len);
-        const uint8_t *sq = rv->text + rv->seq_pos[r.read], *ql = rv->text + rv->qual_pos[r.read];
+    uint32_t prev_read = UINT32_MAX;
+    // the record of `read` on `path` at `pos` with CIGAR <len>M, without aux: -> where it starts in raw
+    auto plain = [&](uint32_t read, uint32_t path, uint32_t pos, uint32_t strand) {
+        const uint32_t len = rv->seq_len[read], ql_have = std::min<uint32_t>(rv->qual_len[read], len);
+        const uint8_t *sq = rv->text + rv->seq_pos[read], *ql = rv->text + rv->qual_pos[read];
         if (ql_have < len) {                                  // a short quality line is padded to the sequence, as the writer above does
             padq.assign(len, '!');
             memcpy(padq.data(), ql, ql_have);
             ql = padq.data();
         }
-        if (r.strand) {                                       // oriented as the writer above orients a reverse record (seqio.go:120-133)
+        if (strand) {                                         // oriented as the writer above orients a reverse record (seqio.go:120-133)
             rcs.resize(len); rcq.resize(len);
             for (uint32_t j = 0; j < len; j++) {
                 const uint8_t ch = sq[len - 1 - j];
@@ -699,37 +726,99 @@ int groot_bam_write_rescued(groot_bam *b, const groot_index_view *ix, const groo
             sq = rcs.data(); ql = rcq.data();
         }
         groot_aln_record rec;
-        rec.name = reinterpret_cast<const char *>(rv->text + rv->name_pos[r.read]);
-        rec.name_len = rv->name_len[r.read];
+        rec.name = reinterpret_cast<const char *>(rv->text + rv->name_pos[read]);
+        rec.name_len = rv->name_len[read];
         rec.seq = sq; rec.qual = ql; rec.seq_len = len;
-        rec.ref_id = r.path; rec.pos = r.pos;
+        rec.ref_id = path; rec.pos = pos;
         rec.start_clip = rec.end_clip = 0;
-        rec.reverse = r.strand;
-        rec.secondary = i > 0 && recs[i - 1].read == r.read;
+        rec.reverse = strand;
+        rec.secondary = read == prev_read;
+        prev_read = read;
         const size_t at = raw.size();
         format_records(&rec, 0, 1, raw);
-        md.clear();
-        uint32_t from = 0;
-        for (uint32_t k = 0; k < r.d; k++) {
-            md += std::to_string(r.mm[k] - from);
-            md += path_base(b, ix, r.path, r.pos + r.mm[k]);
-            from = r.mm[k] + 1u;
-        }
-        md += std::to_string(len - from);
+        return at;
+    };
+    // NM and MD behind the record that starts at `at`
+    auto tags = [&](size_t at, uint32_t nm) {
         const size_t aux = 4 + 3 + md.size() + 1, end = raw.size();
         raw.resize(end + aux);
         uint8_t *p = raw.data() + end;
-        *p++ = 'N'; *p++ = 'M'; *p++ = 'C'; *p++ = r.d;
+        *p++ = 'N'; *p++ = 'M'; *p++ = 'C'; *p++ = (uint8_t)nm;
         *p++ = 'M'; *p++ = 'D'; *p++ = 'Z';
         memcpy(p, md.c_str(), md.size() + 1);
         uint32_t body;
         memcpy(&body, raw.data() + at, 4);
         body += (uint32_t)aux;
         memcpy(raw.data() + at, &body, 4);
+    };
+    uint64_t i = 0, j = 0;
+    while (i < n || j < ng) {
+        if (j >= ng || (i < n && recs[i].read < grecs[j].read)) {
+            const groot_rescue_record &r = recs[i++];
+            const uint32_t len = rv->seq_len[r.read];
+            const size_t at = plain(r.read, r.path, r.pos, r.strand);
+            md.clear();
+            uint32_t from = 0;
+            for (uint32_t k = 0; k < r.d; k++) {
+                md += std::to_string(r.mm[k] - from);
+                md += path_base(b, ix, r.path, r.pos + r.mm[k]);
+                from = r.mm[k] + 1u;
+            }
+            md += std::to_string(len - from);
+            tags(at, r.d);
+            continue;
+        }
+        const groot_gap_record &r = grecs[j++];
+        const uint32_t len = rv->seq_len[r.read], ins = r.type, g = r.g, aligned = ins ? len - g : len;
+        const size_t at = plain(r.read, r.path, r.pos, r.strand);
+        // <len>M -> <k>M<g>D<len-k>M / <k>M<g>I<len-k-g>M: two more operations, and the bin of the reference span
+        const size_t cig = at + 4 + 32 + rv->name_len[r.read] + 1, end = raw.size();
+        raw.resize(end + 8);
+        uint8_t *p = raw.data();
+        memmove(p + cig + 12, p + cig + 4, end - (cig + 4));
+        const uint32_t ops[3] = {(uint32_t)r.k << 4, g << 4 | (ins ? 1u : 2u), (aligned - r.k) << 4};
+        memcpy(p + cig, ops, 12);
+        uint32_t body, bmn, fnc;
+        memcpy(&body, p + at, 4); memcpy(&bmn, p + at + 12, 4); memcpy(&fnc, p + at + 16, 4);
+        body += 8;
+        bmn = (bmn & 0xFFFFu) | (uint32_t)reg2bin(r.pos, (int64_t)r.pos + (ins ? aligned : len + g)) << 16;
+        fnc = (fnc & 0xFFFF0000u) | 3u;
+        memcpy(p + at, &body, 4); memcpy(p + at + 12, &bmn, 4); memcpy(p + at + 16, &fnc, 4);
+        // MD over the aligned bases a = 0 .. aligned: read offset a in front of the gap, a + g behind an insertion; path base pos + a, + g behind a deletion
+        md.clear();
+        uint32_t from = 0;
+        bool gap_done = false;
+        auto deleted = [&]() {
+            md += std::to_string(r.k - from);
+            md += '^';
+            for (uint32_t q = 0; q < g; q++) md += path_base(b, ix, r.path, r.pos + r.k + q);
+            from = r.k;
+        };
+        for (uint32_t k = 0; k < r.d; k++) {
+            const uint32_t behind = r.mm[k] >= r.k, a = behind && ins ? r.mm[k] - g : r.mm[k];
+            if (behind && !ins && !gap_done) { deleted(); gap_done = true; }
+            md += std::to_string(a - from);
+            md += path_base(b, ix, r.path, r.pos + a + (behind && !ins ? g : 0u));
+            from = a + 1u;
+        }
+        if (!ins && !gap_done) deleted();
+        md += std::to_string(aligned - from);
+        tags(at, r.d + g);
     }
     if (int rc = put(b, raw.data(), raw.size())) return rc;
-    if (n_records) *n_records = n;
+    if (n_records) *n_records = n + ng;
     return GROOT_OK;
+}
+
+int groot_bam_write_rescued(groot_bam *b, const groot_index_view *ix, const groot_reads_view *rv, const groot_rescue_record *recs, uint64_t n, uint64_t *n_records)
+{
+    return write_rescued_impl(b, ix, rv, recs, n, nullptr, 0, n_records);
+}
+
+int groot_bam_write_rescued_gapped(groot_bam *b, const groot_index_view *ix, const groot_reads_view *rv, const groot_rescue_record *recs, uint64_t n,
+                                   const groot_gap_record *grecs, uint64_t ng, uint64_t *n_records)
+{
+    return write_rescued_impl(b, ix, rv, recs, n, grecs, ng, n_records);
 }
 
 int groot_bam_set_level(groot_bam *b, int level)

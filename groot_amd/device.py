@@ -17,6 +17,8 @@ ALN_DTYPE = np.dtype([("read_id", "<u4"), ("graph_id", "<u4"), ("path_id", "<u4"
 SEED_DTYPE = np.dtype([("read_id", "<u4"), ("window_id", "<u4")])
 GAP_EVENT_DTYPE = host.GAP_EVENT_DTYPE                     # groot_gap_event
 RESCUE_RECORD_DTYPE = np.dtype([("read", "<u4"), ("path", "<u4"), ("pos", "<u4"), ("mm", "<u2", (3,)), ("strand", "u1"), ("d", "u1")])   # groot_rescue_record
+GAP_RECORD_DTYPE = np.dtype([("read", "<u4"), ("path", "<u4"), ("pos", "<u4"), ("k", "<u2"), ("mm", "<u2", (3,)), ("strand", "u1"), ("d", "u1"), ("type", "u1"),
+                             ("g", "u1")])   # groot_gap_record
 GAP_DEL, GAP_INS = 0, 1
 GAP_STATS = ("candidates", "rescued", "placements", "del_placements", "ins_placements", "too_short", "events", "dropped", "event_slots", "launches")
 TRAV_RC, TRAV_START_CLIP, TRAV_END_CLIP, TRAV_FIRST, TRAV_MAPQ = 1, 2, 4, 8, 16
@@ -645,6 +647,28 @@ class Aligner:
         """groot_hip_rescue_rec_stats: {"records", "reads", "failed", "slots", "launches"}; zeros while off, but for launches"""
         v = (C.c_uint64 * 5)()
         self._check(lib().groot_hip_rescue_rec_stats(self._h, v))
+        return dict(zip(("records", "reads", "failed", "slots", "launches"), (int(x) for x in v)))
+
+    # ---- gapped records (groot_hip_gap_rec_*) --------------------------------------------------------------
+    def gap_rec_enable(self, slots_per_batch):
+        """from now on every batch hands out one record per kept gapped placement of its gap-rescued reads (include/groot_hip.h, "gapped
+        records"), with room for slots_per_batch of them per batch; 0 switches it off.  Needs gap_enable first.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_gap_rec_enable(self._h, C.c_uint64(slots_per_batch)))
+
+    def gap_records(self, ticket=0):
+        """the gapped records of a collected, unreleased batch as GAP_RECORD_DTYPE, copied, in ascending (read, path, strand, pos, type, g)
+        order (ticket 0: the batch wait() collected)"""
+        p, n = C.c_void_p(), C.c_uint64(0)
+        self._check(lib().groot_hip_gap_rec_batch(self._h, C.c_uint64(ticket), C.byref(p), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, dtype=GAP_RECORD_DTYPE)
+        buf = (C.c_uint8 * (n.value * GAP_RECORD_DTYPE.itemsize)).from_address(p.value)
+        return np.frombuffer(buf, dtype=GAP_RECORD_DTYPE).copy()
+
+    def gap_rec_stats(self):
+        """groot_hip_gap_rec_stats: {"records", "reads", "failed", "slots", "launches"}; zeros while off, but for launches"""
+        v = (C.c_uint64 * 5)()
+        self._check(lib().groot_hip_gap_rec_stats(self._h, v))
         return dict(zip(("records", "reads", "failed", "slots", "launches"), (int(x) for x in v)))
 
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------

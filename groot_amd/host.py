@@ -351,9 +351,10 @@ class BamWriter:
                                            C.c_uint64(len(t)), C.byref(n)))
         return n.value
 
-    def write_rescued(self, records, names, seqs, quals):
+    def write_rescued(self, records, names, seqs, quals, gap_records=None):
         """groot_bam_write_rescued: the rescued records (device.RESCUE_RECORD_DTYPE) of a batch whose reads are given as lists of bytes
-        (name, sequence, quality line as it came) -> the number of records written, each with NM and MD"""
+        (name, sequence, quality line as it came) -> the number of records written, each with NM and MD.  gap_records
+        (device.GAP_RECORD_DTYPE, an empty list included): groot_bam_write_rescued_gapped, the two lists merged by read"""
         n = len(names)
         text = np.frombuffer(b"".join(x for t in zip(names, seqs, quals) for x in t) or b"\0", dtype=np.uint8)
         lens = np.array([[len(a), len(s), len(q)] for a, s, q in zip(names, seqs, quals)], dtype=np.int64).reshape(n, 3)
@@ -370,6 +371,12 @@ class BamWriter:
         rec = np.ascontiguousarray(records)
         assert rec.dtype.itemsize == 20
         out = C.c_uint64(0)
+        if gap_records is not None:
+            grec = np.ascontiguousarray(gap_records)
+            assert grec.dtype.itemsize == 24
+            _check(lib().groot_bam_write_rescued_gapped(self._h, C.byref(self.index.view), C.byref(v), rec.ctypes.data_as(C.c_void_p), C.c_uint64(len(rec)),
+                                                        grec.ctypes.data_as(C.c_void_p), C.c_uint64(len(grec)), C.byref(out)))
+            return out.value
         _check(lib().groot_bam_write_rescued(self._h, C.byref(self.index.view), C.byref(v), rec.ctypes.data_as(C.c_void_p), C.c_uint64(len(rec)), C.byref(out)))
         return out.value
 
@@ -947,3 +954,9 @@ def abundance_read(index, path):
     n = C.c_uint64(0)
     _check(lib().groot_host_abundance_read(C.byref(index.view), path.encode(), _ffi.as_ptr(alpha, C.c_double), C.byref(n)))
     return alpha, n.value
+
+
+def bam_write_rescued_gapped(writer, records, gap_records, names, seqs, quals):
+    """groot_bam_write_rescued_gapped on an open BamWriter: one BAM record per entry of both lists of a batch (device.RESCUE_RECORD_DTYPE,
+    device.GAP_RECORD_DTYPE), merged by read -> the number of records written"""
+    return writer.write_rescued(records, names, seqs, quals, gap_records=gap_records)

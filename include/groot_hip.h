@@ -659,7 +659,8 @@ int groot_hip_rescue_acov_stats(groot_ctx *ctx, groot_rescue_acov_stats *out);
  *   The rescued records of a batch are ALL kept placements of ALL its rescued reads (every path, both strands, every x, several on one
  *   path), each once, in ascending (read, path, strand, pos) order.
  *   A pass that collect redoes yields the records of its redo, once.  A batch under kCovSkipFlags (one that fails with GROOT_E_NOSPACE)
- *   yields none.  Gap-placed reads (gapped rescue) yield none.
+ *   yields none.  Gap-placed reads (gapped rescue) yield none, unless the gapped records below are on:
+ *   then they yield those, in a list of their own.
  *   The list depends on the reads and the index alone: not on batch size, pipeline depth, align stage, results_on_device or the number
  *   of ctxs (cut a batch in pieces and the pieces' lists, with batch-relative `read`, concatenate to the batch's).
  *
@@ -691,6 +692,58 @@ int groot_hip_rescue_rec_enable(groot_ctx *ctx, uint64_t slots_per_batch);
 int groot_hip_rescue_rec_batch(groot_ctx *ctx, uint64_t ticket, const groot_rescue_record **recs, uint64_t *n);
 /* Zeros while off, but for launches.  Counts collected batches only; does not wait. */
 int groot_hip_rescue_rec_stats(groot_ctx *ctx, groot_rescue_rec_stats *out);
+
+/* ---- gapped records --------------------------------------------------------------------------------------------------------
+ * Gapped rescue adds its placements to gdepth and the event table; the placements themselves are gone when the batch is.  With this on,
+ * every batch also hands out one record per kept gapped placement of its gap-rescued reads: what a BAM record with an I or D CIGAR
+ * needs.  The definition, integers only:
+ *
+ *   Gap candidate, gapped placement (p, strand, x, type, g, k), d, k*, e = d + g, e*(r), GAP-RESCUED, KEPT gapped placement, oriented read R,
+ *   T = text_p, path coordinate X = first Position of p + x: exactly as in "gapped rescue".
+ *   A GAPPED RECORD is one kept gapped placement of a gap-rescued read:
+ *       read   = position of r in its batch          path = global path p          pos = X (0-based, as an exact record's Pos)
+ *       k      = k* (aligned read bases in front of the gap; the gap is left-aligned as the definition has it)
+ *       strand = 0 / 1      d = its mismatches (<= M <= 3)      type = GROOT_GAP_DEL / GROOT_GAP_INS      g = 1..8
+ *       mm[3]  = the offsets i, ascending, in the ORIENTED read at which an ALIGNED read base differs from the text base it lies on:
+ *                i < k:  R[i] != T[x+i];    DEL, i >= k:  R[i] != T[x+g+i];    INS, i >= k+g:  R[i] != T[x+i-g].
+ *                The inserted bases R[k, k+g) are never listed.  The d first entries are set, the rest are 0xFFFF.
+ *   The gapped records of a batch are ALL kept gapped placements of ALL its gap-rescued reads, each (p, strand, x, type, g) once, in
+ *   ascending (read, path, strand, pos, type, g) order.  (A read has rescued records or gapped records, never both: a gap candidate is
+ *   not rescued.)
+ *   A pass that collect redoes yields the records of its redo, once.  A batch under kCovSkipFlags yields none.
+ *   The list depends on the reads and the index alone: not on batch size, pipeline depth, align stage, results_on_device or the number
+ *   of ctxs (cut a batch in pieces and the pieces' lists, with batch-relative `read`, concatenate to the batch's).
+ *
+ * On the device (kernels_gap_rec.hpp): rescue_gap_rec_kernel -- rescue_gap_kernel's body with a sink -- also leaves every read's number
+ * of kept gapped placements and every gap candidate's e*, an exclusive scan over the batch's reads gives every read its segment, and
+ * gap_rec_emit_kernel -- one thread per gap-rescued read -- walks sweep 2 once more at e*, writes the placements and sorts its segment.
+ * The records live in a buffer of the pipeline slot and are copied into pinned host memory at collect, as many as the batch has.
+ * gdepth, the events, the stats and every other counter stay what they are.  Independent of the rescued records above: either, both or
+ * neither may be on.  Off by default: then no allocation, launch or sync, and rescue_gap_kernel is the one it is without this section. */
+/* groot_gap_record (24 bytes: read, path, pos, k, mm[3], strand, d, type, g) is declared in groot_host.h, beside the writer that takes it */
+typedef struct groot_gap_rec_stats {
+    uint64_t records;     /* records handed out (of collected batches that did not fail) since enable */
+    uint64_t reads;       /* gap-rescued reads those records belong to */
+    uint64_t failed;      /* batches that failed for room */
+    uint64_t slots;       /* slots_per_batch (0 while off) */
+    uint64_t launches;    /* the scan and gap_rec_emit_kernel, launched since open, whether it is on now or not (rescue_gap_rec_kernel
+                             counts in groot_gap_stats.launches) */
+} groot_gap_rec_stats;
+/* slots_per_batch > 0: on, with room for that many records per batch in every pipeline slot (a second call with another value
+ * reallocates, the stats start over); 0: off, everything freed, nothing launched afterwards.  GROOT_E_STATE when gapped rescue is off or
+ * something is in flight; beyond 2^40 bytes GROOT_E_INVALID.  groot_hip_gap_enable(.., 0, ..) and groot_hip_rescue_enable(.., 0) switch
+ * it off too; another G, another M or a reset leaves it on.  A batch with more records than slots_per_batch fails at collect with
+ * GROOT_E_NOSPACE, and the message names slots_per_batch: no record is dropped silently; the batch's other results stay readable, the
+ * rescued records included, its gapped records do not (groot_hip_gap_rec_batch gives n = 0), and the next batch is not affected.  Device
+ * memory: 13 bytes per read of a batch, and 24 slots_per_batch bytes per pipeline slot; pinned memory: 24 bytes per record of the largest
+ * batch so far, per slot. */
+int groot_hip_gap_rec_enable(groot_ctx *ctx, uint64_t slots_per_batch);
+/* recs[0 .. *n) of a collected, unreleased batch (ticket 0: the batch groot_hip_wait collected), in pinned host memory that stays valid
+ * until the batch is released; with results_on_device as well.  *n = 0 for an empty or a failed batch.  GROOT_E_STATE when the feature
+ * was off when the batch was submitted. */
+int groot_hip_gap_rec_batch(groot_ctx *ctx, uint64_t ticket, const groot_gap_record **recs, uint64_t *n);
+/* Zeros while off, but for launches.  Counts collected batches only; does not wait. */
+int groot_hip_gap_rec_stats(groot_ctx *ctx, groot_gap_rec_stats *out);
 
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on

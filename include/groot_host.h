@@ -280,6 +280,29 @@ typedef struct groot_rescue_record {
 int groot_bam_write_rescued(groot_bam *bam, const groot_index_view *idx, const groot_reads_view *reads, const groot_rescue_record *recs,
                             uint64_t n, uint64_t *n_records);
 
+/* Gapped records (defined at groot_hip_gap_rec_enable in groot_hip.h): one kept gapped placement of a read that gapped rescue placed --
+ * as a rescued record, with k aligned read bases in front of one gap of g bases (type: GROOT_GAP_DEL 0 / GROOT_GAP_INS 1), and the d
+ * offsets in the ORIENTED read at which an ALIGNED base differs from the path (never inside an insertion's bases [k, k + g)). */
+typedef struct groot_gap_record {
+    uint32_t read, path, pos;
+    uint16_t k, mm[3];
+    uint8_t strand, d, type, g;
+} groot_gap_record;   /* 24 bytes */
+/* One BAM record per entry of BOTH lists of a batch, merged by `read` (both arrive ascending; a read present in both lists is
+ * GROOT_E_INVALID); with ng = 0 the bytes are exactly those of groot_bam_write_rescued.  A gapped record is written as a rescued one --
+ * QNAME, FLAG 0x10 for strand 1 and 0x100 on every record of a read but its first in the merged list, MAPQ 30, POS = pos, SEQ / QUAL
+ * oriented -- with
+ *   CIGAR <k>M<g>D<len-k>M (DEL) or <k>M<g>I<len-k-g>M (INS); bin = reg2bin over the reference span, len + g (DEL) or len - g (INS);
+ *   NM:i:d + g; MD:Z: the standard string over the aligned bases, runs and the PATH's base at every mismatch; a DEL carries ^ and the
+ *   deleted path bases between the flanks, and a run of 0 behind them when the next aligned base mismatches (31^ACG0T67); an INS skips
+ *   the inserted bases and the matching run goes on across them (50M1I49M with d = 0 gives MD:Z:99).
+ * GROOT_E_INVALID, with nothing of the call written, for what groot_bam_write_rescued refuses in either list, and for a gapped record
+ * whose window (len + g or len - g path bases at pos) does not lie inside the path, with strand > 1, d > 3, type > 1, g outside 1..8,
+ * k below 16 or less than 16 aligned bases behind the gap, or offsets that are not d ascending values below the read's length, outside
+ * [k, k + g) for an INS, followed by 0xFFFF.  *n_records = records written, of both lists. */
+int groot_bam_write_rescued_gapped(groot_bam *bam, const groot_index_view *idx, const groot_reads_view *reads, const groot_rescue_record *recs,
+                                   uint64_t n, const groot_gap_record *grecs, uint64_t ng, uint64_t *n_records);
+
 /* ---- packing reads for groot_hip_submit_packed (include/groot_hip.h) ------------------------------------ */
 /* packed[(n_bases+3)/4]; exceptions (bytes other than A C G T, e.g. N or lower case) in ascending position, at most
  * exc_cap of them: GROOT_E_NOSPACE with *n_exc = the number needed otherwise.  n_threads 0 = all cores. */
