@@ -202,6 +202,12 @@ int main(int argc, char **argv)
            batches, reopened, (unsigned long long)t.received, (unsigned long long)t.mapped, (unsigned long long)t.multimapped,
            (unsigned long long)t.alignments, (unsigned long long)t.travs, (unsigned long long)t.records, (unsigned long long)t.rec_hash,
            (unsigned long long)wh, (unsigned long long)kt_sum, n_rows);
+    /* GapEcEnable / GapEcStats: the gap-placed reads in the classes need gapped rescue and the rescued reads in the classes, which this
+     * run never switched on -- the enable is refused, nothing is allocated or launched, and the stats stay zero */
+    groot_gap_ec_stats gst;
+    if (groot_hip_gap_ec_enable(ctxs[0], 1) != GROOT_E_STATE) DIE("groot_hip_gap_ec_enable without gapped rescue was not refused");
+    if (groot_hip_gap_ec_stats(ctxs[0], &gst)) DIE("groot_hip_gap_ec_stats: %s", groot_hip_last_error(ctxs[0]));
+    if (gst.reads || gst.slow_reads || gst.launches) DIE("groot_hip_gap_ec_stats: counts while the feature is off");
     for (int d = 0; d < n_ctx; d++) groot_hip_close(ctxs[d]);
     groot_index_free(idx);
     return 0;

@@ -397,6 +397,34 @@ func (c *Ctx) PairsStats() (joined, split, single uint64, err error) {
 	return uint64(j), uint64(s), uint64(o), nil
 }
 
+// GapEcStats mirrors groot_gap_ec_stats
+type GapEcStats struct {
+	Reads, SlowReads, Launches uint64
+}
+
+// GapEcEnable switches the gap-placed reads in the equivalence classes on or off (include/groot_hip.h, "gap-placed reads in the
+// equivalence classes"): a read gapped rescue places is then a unit of the classes with the set of paths it was gap-placed on.  Needs
+// gapped rescue and the rescued reads in the classes on.  Nothing may be in flight.
+func (c *Ctx) GapEcEnable(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.groot_hip_gap_ec_enable(c.h, v); rc != 0 {
+		return c.err("groot_hip_gap_ec_enable")
+	}
+	return nil
+}
+
+// GapEcStatsGet returns the gap-rescued reads added to the classes since GapEcEnable or a reset of the classes (waits for everything in flight)
+func (c *Ctx) GapEcStatsGet() (GapEcStats, error) {
+	var st C.groot_gap_ec_stats
+	if rc := C.groot_hip_gap_ec_stats(c.h, &st); rc != 0 {
+		return GapEcStats{}, c.err("groot_hip_gap_ec_stats")
+	}
+	return GapEcStats{uint64(st.reads), uint64(st.slow_reads), uint64(st.launches)}, nil
+}
+
 func (c *Ctx) err(what string) error {
 	return fmt.Errorf("%s: %s", what, C.GoString(C.groot_hip_last_error(c.h)))
 }

@@ -93,6 +93,17 @@ def rarefy_hip_prototypes(L):
     L.groot_hip_em_rarefy.restype = C.c_int
 
 
+# ---- gap-placed reads in the equivalence classes (groot_hip.h) ----
+GAP_EC_STATS = ("reads", "slow_reads", "launches")          # groot_gap_ec_stats, three uint64
+
+
+def gap_ec_prototypes(L):
+    """argtypes of groot_hip_gap_ec_enable / groot_hip_gap_ec_stats (libgroot_hip.so)"""
+    L.groot_hip_gap_ec_enable.argtypes = [C.c_void_p, C.c_int]
+    L.groot_hip_gap_ec_stats.argtypes = [C.c_void_p, u64p]
+    L.groot_hip_gap_ec_enable.restype = L.groot_hip_gap_ec_stats.restype = C.c_int
+
+
 def opt_ptr(arr, ctype):
     """as_ptr, or a NULL pointer for None"""
     return None if arr is None else as_ptr(arr, ctype)

@@ -25,6 +25,7 @@ struct Harvested {                           // the sums over every harvest so f
     std::map<std::array<uint32_t, 5>, uint64_t> gap_events;  // (path, pos, type, len, seq) -> reads: ascending as the export is
     groot_gap_stats gap{};
     groot_rescue_ec_stats rescue_ec{};                       // --abundanceRescued: the rescued reads in the classes (groot_hip_rescue_ec_*)
+    groot_gap_ec_stats gap_ec{};                             // --abundanceGapped: the gap-placed reads in the classes (groot_hip_gap_ec_*)
     groot_rescue_acov_stats rescue_acov{};                   // --callsRescued: their records in the pileup (groot_hip_rescue_acov_*)
 };
 
@@ -70,7 +71,9 @@ public:
         if (plan_.abundance)
             if (int rc = groot_hip_ec_enable(ctx, on)) return rc;        // (off: assigned coverage goes with it, and so do the rescued reads in the classes)
         if (plan_.calls_rescued && on) return groot_hip_rescue_acov_enable(ctx, 1, (uint64_t)a_.call_slots);     // (it switches the rescued reads in the classes on itself)
-        return plan_.ab_rescued && on ? groot_hip_rescue_ec_enable(ctx, 1) : 0;
+        if (plan_.ab_rescued && on)
+            if (int rc = groot_hip_rescue_ec_enable(ctx, 1)) return rc;
+        return plan_.ab_gapped && on ? groot_hip_gap_ec_enable(ctx, 1) : 0;   // behind gapped rescue and the rescued reads in the classes (off: it goes with either)
     }
 
     // assign stats, pair stats, acov-or-EC export, rescued reads in the ECs, gapped rescue, rescue, coverage, shared pairs: each added under the lock (the mappers harvest side by side)
@@ -117,6 +120,12 @@ public:
             if (int rc = groot_hip_rescue_ec_stats(ctx, &st)) return rc;
             std::lock_guard<std::mutex> lk(mu_);
             h_.rescue_ec.reads += st.reads; h_.rescue_ec.slow_reads += st.slow_reads; h_.rescue_ec.launches += st.launches; h_.rescue_ec.rows = st.rows;
+        }
+        if (plan_.ab_gapped) {
+            groot_gap_ec_stats st{};
+            if (int rc = groot_hip_gap_ec_stats(ctx, &st)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            h_.gap_ec.reads += st.reads; h_.gap_ec.slow_reads += st.slow_reads; h_.gap_ec.launches += st.launches;
         }
         if (plan_.calls_rescued) {  // (a table that dropped rescued records has failed above, at the export, with the reason: no calls file is written)
             groot_rescue_acov_stats st{};

@@ -103,8 +103,12 @@ Bootstrap write_abundance(const Args &a, const AlignPlan &plan, const groot_inde
         for (uint64_t c : h.ec_cnt) units += c;
         logf("\tabundance: %llu rescued read(s) counted in the equivalence classes beside %llu read(s) with an exact alignment, placed with up to %ld substitution(s); "
              "%llu of them on ARGs of more than 4 graphs",
-             (unsigned long long)h.rescue_ec.reads, (unsigned long long)(units - h.rescue_ec.reads), a.rescue, (unsigned long long)h.rescue_ec.slow_reads);
+             (unsigned long long)h.rescue_ec.reads, (unsigned long long)(units - h.rescue_ec.reads - h.gap_ec.reads), a.rescue, (unsigned long long)h.rescue_ec.slow_reads);
     }
+    if (plan.ab_gapped)
+        logf("\tabundance: %llu gap-placed read(s) counted in the equivalence classes with them, placed with one deletion or insertion of up to %ld base(s); "
+             "%llu of them on ARGs of more than 4 graphs",
+             (unsigned long long)h.gap_ec.reads, a.rescue_gap, (unsigned long long)h.gap_ec.slow_reads);
     if (plan.rarefy && !plan.calls) {
         // the curve of the abundance file alone: over the merged ECs in canonical order, as the bootstrap takes them
         const Ecs c = canonical_ecs(v, h);

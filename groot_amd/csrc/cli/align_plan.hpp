@@ -8,6 +8,7 @@ struct AlignPlan {
     bool report = false, shared = false, abundance = false, calls = false, assign = false, rarefy = false, variants = false, indels = false;
     bool rescue = false;     // mismatch rescue runs: --variants, --indels or --abundanceRescued
     bool ab_rescued = false; // --abundanceRescued: the rescued reads join the equivalence classes
+    bool ab_gapped = false;  // --abundanceGapped: and so do the gap-placed reads
     bool calls_rescued = false; // --callsRescued: and their kept placements the pileup of --calls
     bool rescued_bam = false;   // --rescuedBam: the kept placements of the rescued reads as BAM records in a file of their own
     bool rescued_bam_gaps = false; // --rescuedBamGaps: and the kept placements of the gap-rescued reads with them
@@ -121,6 +122,13 @@ int plan_align(const Args &a, AlignPlan *p)
     if (p->rescued_bam_gaps && !p->indels) return refuse("--rescuedBamGaps writes the placements of gapped rescue, which --indels switches on: it needs it");
     if (a.gap_record_slots_given && !p->rescued_bam_gaps) return refuse("--gapRecordSlots is the room for the records of --rescuedBamGaps: it needs it");
     if (a.gap_record_slots_given && a.gap_record_slots < 1) return refuse("--gapRecordSlots is a number of records per batch, at least 1: %lld", a.gap_record_slots);
+    // --abundanceGapped: checked behind everything above
+    p->ab_gapped = a.abundance_gapped;
+    if (p->ab_gapped && !p->ab_rescued) return refuse("--abundanceGapped adds the gap-placed reads to the classes beside the reads --abundanceRescued adds: it needs it");
+    if (p->ab_gapped && !p->indels) return refuse("--abundanceGapped counts the reads gapped rescue places, which --indels switches on: it needs it");
+    if (p->ab_gapped && p->calls)
+        return refuse("--abundanceGapped cannot be combined with --calls%s: its pileup has no rule for a gapped record, and a deletion covers two intervals",
+                      p->calls_rescued ? " --callsRescued" : "");
     p->coverage = p->report || p->variants || p->indels;
     p->counters = p->report || p->abundance || p->assign || p->rescue;
     return 0;

@@ -73,6 +73,7 @@ struct Args {
     double variant_min_share = 0.1;        // --variantMinShare S
     bool rescue_given = false, variant_min_given = false;
     bool abundance_rescued = false;          // --abundanceRescued: the reads mismatch rescue places join the equivalence classes of --abundance
+    bool abundance_gapped = false;           // --abundanceGapped: and so do the reads gapped rescue (--indels) places
     bool calls_rescued = false;              // --callsRescued: with --calls and --abundanceRescued, the rescued reads' placements join the pileup
     long long call_slots = 1ll << 24;        // --callSlots N (a power of two): the slots the assigned-coverage table starts with under --callsRescued
     bool call_slots_given = false;

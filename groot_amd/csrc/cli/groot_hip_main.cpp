@@ -36,6 +36,7 @@ void usage()
             "                  [--report r.tsv [--covCutoff 0.97] [--lowCov] [--sharedReads s.tsv]] [--abundance a.tsv [--abundanceMin 1.0] [--abundanceRescued [--rescue 2]]]\n"
             "                  [--noBam] [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
             "                  [--abundanceRescued --calls c.tsv --callsRescued [--callSlots 16777216]]\n"
+            "                  [--abundance a.tsv --abundanceRescued --indels i.tsv --abundanceGapped [--rescueGap 3]]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
@@ -50,6 +51,9 @@ void usage()
             "                   rescued, and the EM, --bootstraps and --rarefy see them all.  Not with --paired or --interleaved, and with --calls only beside\n"
             "                   --callsRescued: then every placement of a rescued read is a record of the pileup too, over the bases it covers; --callSlots: the\n"
             "                   slots the pileup's table on the GPU starts with, a power of two (a run whose rescued records find no room fails and says so);\n"
+            "                   --abundanceGapped: with --abundanceRescued and --indels, a read that gapped rescue places with one deletion or insertion of up\n"
+            "                   to --rescueGap bases counts too, with the set of ARGs it was gap-placed on: `reads`, the EM, --bootstraps and --rarefy see it\n"
+            "                   as they see the others.  Not with --calls, with or without --callsRescued: the pileup has no rule for a gapped record;\n"
             "                   --bootstraps: with --abundance, four more columns `boot_mean boot_sd boot_lo boot_hi` from B replicates of the reads\n"
             "                   resampled with replacement (--bootSeed), each with its own EM, drawn and fitted on the GPU;\n"
             "                   --calls: with --abundance, per line of the abundance file `name em_reads length depth breadth cigar called`: the pileup of\n"
@@ -129,6 +133,7 @@ Args parse(int argc, char **argv)
         else if (ar && f == "--calls") a.calls_out = v();
         else if (ar && f == "--callDepth") a.call_depth = atof(v().c_str());
         else if (a.cmd == "align" && f == "--abundanceRescued") a.abundance_rescued = true;
+        else if (a.cmd == "align" && f == "--abundanceGapped") a.abundance_gapped = true;
         else if (ar && f == "--abundanceMin") a.abundance_min = atof(v().c_str());
         else if (ar && f == "--bootstraps") a.bootstraps = (uint32_t)std::max(0l, atol(v().c_str()));
         else if (ar && f == "--bootSeed") a.boot_seed = strtoull(v().c_str(), nullptr, 10);

@@ -2,7 +2,8 @@
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
 // draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp), rescued reads in the equivalence
-// classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp), rescued records (kernels_rescue_rec.hpp), gapped records (kernels_gap_rec.hpp).  One of the six translation units of
+// classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp), rescued records (kernels_rescue_rec.hpp), gapped records (kernels_gap_rec.hpp),
+// gap-placed reads in the equivalence classes (kernels_gap_ec.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <cstring>   // before rocprim: its texture iterator calls host memset
 
@@ -35,6 +36,7 @@
 #include "kernels_rescue_acov.hpp"
 #include "kernels_rescue_rec.hpp"
 #include "kernels_gap_rec.hpp"
+#include "kernels_gap_ec.hpp"
 #include "kernels_shared.hpp"
 
 using namespace groot;
@@ -95,7 +97,9 @@ void EcBufs::release()
 // collect + n_reads of every batch launched and not collected, this one included) slots -- else it doubles, rehashed in tail-stream
 // order.  (Growth is rare -- a handful of times per run -- so the old buffers are freed behind a wait for the tail stream.)
 // With rescued reads in the ECs (kernels_rescue_ec.hpp) a batch has a second merge, and the bound holds for both together: a rescued
-// read has no record, so the reads with a record and the rescued ones are at most n_reads, and so are their distinct sets.
+// read has no record, so the reads with a record and the rescued ones are at most n_reads, and so are their distinct sets.  The
+// gap-placed reads (kernels_gap_ec.hpp) go through that second merge and change nothing: a gap candidate is a candidate that ended
+// unplaced, so a read is exact, rescued or gap-rescued and never two of them: exact + rescued + gap-rescued <= n_reads.
 static int ec_reserve(groot_ctx *c, Slot *s)
 {
     Counters &k = c->ct;
@@ -366,6 +370,57 @@ static int rec_collect(groot_ctx *c, Slot *s, bool refetch)
     return GROOT_OK;
 }
 
+// ---- gap-placed reads in the equivalence classes (kernels_gap_ec.hpp) ----
+// The batch's slow rescued and slow gap-rescued reads, as the slot's status block has them (refetch: afresh, the batch was redone)
+static int gec_counts(groot_ctx *c, Slot *s, bool refetch, uint32_t &n_r, uint32_t &n_g)
+{
+    if (refetch) {
+        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->gec_slow, s->ct.d_gec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    n_r = s->ct.h_status.p->rec_slow;
+    n_g = s->ct.h_status.p->gec_slow;
+    return GROOT_OK;
+}
+
+// At collect, ahead of rec_collect: the two kinds share the slot's bitmaps, and a batch that needs more fails before either is folded.
+// (More rescued ones alone than there are bitmaps: rec_collect says so, in its own words.)
+static int gec_check(groot_ctx *c, Slot *s, bool refetch)
+{
+    Counters &k = c->ct;
+    if (!s->ct.d_gec_slow.p || !s->ct.d_rec_slow.p) return GROOT_OK;      // (launched before the feature came on)
+    uint32_t n_r, n_g;
+    if (int rc = gec_counts(c, s, refetch, n_r, n_g)) return rc;
+    if (n_r <= k.rec_rows && (uint64_t)n_r + n_g > k.rec_rows)
+        return fail(c, GROOT_E_NOSPACE, "gap-placed reads in the equivalence classes: a batch has %u rescued and %u gap-rescued reads whose sets lie in more graphs than a row "
+                    "holds, and room for the bitmaps of %u (GROOT_TEST_RESCUE_EC_ROWS)", n_r, n_g, k.rec_rows);
+    return GROOT_OK;
+}
+
+// At collect, behind rec_collect: the bitmaps of the batch's slow gap-rescued reads -- the rows behind the rescued reads' -- into ec_host.
+static int gec_collect(groot_ctx *c, Slot *s)
+{
+    Counters &k = c->ct;
+    if (!s->ct.d_gec_slow.p || !s->ct.d_rec_slow.p) return GROOT_OK;
+    const uint32_t n_r = s->ct.h_status.p->rec_slow, n_g = s->ct.h_status.p->gec_slow;      // (gec_check has brought them up to date)
+    if (!n_g) return GROOT_OK;
+    std::vector<uint64_t> bits((size_t)n_g * k.rec_bw);
+    HIP_TRY(c, hipMemcpy(bits.data(), s->ct.d_rec_bits.p + (size_t)n_r * k.rec_bw, bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const uint32_t n_paths = (uint32_t)k.h_len.size();
+    std::vector<uint32_t> ids;
+    for (uint32_t i = 0; i < n_g; i++) {
+        ids.clear();
+        for (uint32_t w = 0; w < k.rec_bw; w++)
+            for (uint64_t m = bits[(size_t)i * k.rec_bw + w]; m; m &= m - 1) {
+                const uint32_t id = w * 64 + (uint32_t)__builtin_ctzll(m);
+                if (id < n_paths) ids.push_back(id);
+            }
+        if (!ids.empty()) k.ec_host[ids]++;
+    }
+    k.gec_slow += n_g;
+    return GROOT_OK;
+}
+
 // ---- rescued records (kernels_rescue_rec.hpp) ----
 struct KeptToU64 {
     __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
@@ -601,14 +656,20 @@ int counters_launch(groot_ctx *c, Slot *s)
             else if (k.rr_on) hipLaunchKernelGGL((rescue_count_rec_kernel<true, false>), gr, dim3(kBlock), 0, c->tstream, ra);
             else if (k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
             else hipLaunchKernelGGL(rescue_count_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
+            gra.g = ga;
             if (k.gr_on) {   // gapped records (kernels_gap_rec.hpp): the gap kernel also leaves every read's kept placements and every gap candidate's e*
                 HIP_TRY(c, s->ct.d_gr_rec.reserve((size_t)k.gr_slots * kGapRecWords));
                 HIP_TRY(c, s->ct.d_gr_total.reserve(1));
                 HIP_TRY(c, s->ct.h_status.reserve(1));
-                gra.g = ga; gra.n_gkept = k.gr_kept.p; gra.gap_e = k.gr_e.p; gra.off = k.gr_off.p; gra.rec = s->ct.d_gr_rec.p; gra.cap = k.gr_slots;
+                gra.n_gkept = k.gr_kept.p; gra.gap_e = k.gr_e.p; gra.off = k.gr_off.p; gra.rec = s->ct.d_gr_rec.p; gra.cap = k.gr_slots;
                 HIP_TRY(c, hipMemsetAsync(k.gr_kept.p, 0, ((size_t)s->n_reads + 1) * sizeof(uint32_t), c->tstream));
-                hipLaunchKernelGGL(rescue_gap_rec_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, gra);
-            } else hipLaunchKernelGGL(rescue_gap_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
+            }
+            if (k.gec_on) {  // gap-placed reads in the classes (kernels_gap_ec.hpp): the gap kernel also writes every gap-rescued read's set row
+                GapEcCountArgs gca{gra, k.gec_e.p};
+                if (k.gr_on) hipLaunchKernelGGL(rescue_gap_ec_kernel<true>, gr, dim3(kBlock), 0, c->tstream, gca);
+                else hipLaunchKernelGGL(rescue_gap_ec_kernel<false>, gr, dim3(kBlock), 0, c->tstream, gca);
+            } else if (k.gr_on) hipLaunchKernelGGL(rescue_gap_rec_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, gra);
+            else hipLaunchKernelGGL(rescue_gap_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
             k.gap_launches++;
         }
         HIP_TRY(c, hipGetLastError());
@@ -626,7 +687,20 @@ int counters_launch(groot_ctx *c, Slot *s)
             ea.bits = s->ct.d_rec_bits.p; ea.n_slow = s->ct.d_rec_slow.p; ea.stats = k.rec_stats.p;
             ea.rows = k.rec_rows; ea.bw = k.rec_bw;
             const dim3 gc(grid_for(s->n_reads));
-            if (!k.rac_on) {
+            if (!k.rac_on && k.gec_on && k.gap_on) {      // the gap-rescued reads' rows between the rescued reads' and the one merge of both
+                GapEcArgs ga{};
+                ga.g = gra.g; ga.s = sa; ga.e = k.gec_e.p; ga.bits = ea.bits; ga.n_rslow = ea.n_slow; ga.stats = k.gec_stats.p;
+                ga.rows = ea.rows; ga.bw = ea.bw;
+                HIP_TRY(c, s->ct.d_gec_slow.reserve(1));
+                HIP_TRY(c, hipMemsetAsync(s->ct.d_gec_slow.p, 0, sizeof(uint32_t), c->tstream));
+                ga.n_gslow = s->ct.d_gec_slow.p;
+                hipLaunchKernelGGL(rescue_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
+                hipLaunchKernelGGL(gap_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
+                hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
+                hipLaunchKernelGGL(gap_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
+                hipLaunchKernelGGL(rescue_ec_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p);
+                k.gec_launches += 2;
+            } else if (!k.rac_on) {
                 hipLaunchKernelGGL(rescue_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
                 hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
                 hipLaunchKernelGGL(rescue_ec_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p);
@@ -671,6 +745,7 @@ int counters_fetch(groot_ctx *c, Slot *s)
         HIP_TRY(c, hipMemcpyAsync(&h->acov_fill, c->ct.acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     }
     if (c->ct.rec_on) HIP_TRY(c, hipMemcpyAsync(&h->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    if (c->ct.gec_on && s->ct.d_gec_slow.p) HIP_TRY(c, hipMemcpyAsync(&h->gec_slow, s->ct.d_gec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     if (c->ct.rac_on) HIP_TRY(c, hipMemcpyAsync(&h->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     return GROOT_OK;
 }
@@ -690,8 +765,12 @@ int counters_collect(groot_ctx *c, Slot *s, bool redone)
     if (int rc = gr_collect(c, s, redone)) return rc;
     if (!c->ct.ec_on || !s->n_reads) return GROOT_OK;
     if (int rc = ec_collect(c, s, redone)) return rc;
+    if (c->ct.rec_on && c->ct.gec_on)
+        if (int rc = gec_check(c, s, redone)) return rc;
     if (c->ct.rec_on)
         if (int rc = rec_collect(c, s, redone)) return rc;
+    if (c->ct.rec_on && c->ct.gec_on)
+        if (int rc = gec_collect(c, s)) return rc;
     return c->ct.acov_on ? acov_collect(c, s, redone) : GROOT_OK;
 }
 
@@ -765,9 +844,17 @@ int groot_hip_coverage_reset(groot_ctx *c)
     return GROOT_OK;
 }
 
+// gap-placed reads in the equivalence classes go off (with gapped rescue, or with the rescued reads in the classes)
+static void gec_release(Counters &k)
+{
+    k.gec_e.release(); k.gec_stats.release();
+    k.gec_on = false; k.gec_slow = 0;
+}
+
 // rescued reads in the equivalence classes go off (with mismatch rescue, or with the classes): nothing of it stays on the device
 static void rec_release(Counters &k)
 {
+    gec_release(k);                        // (the gap-placed reads' rows go through the rescued reads' table and merge)
     k.rec_path_bit.release(); k.rec_dstar.release(); k.rec_stats.release();
     k.rec_on = false; k.rec_rows = k.rec_bw = 0; k.rec_slow = 0;
     // (and with it the rescued reads in assigned coverage, which are keyed by these classes)
@@ -1031,6 +1118,10 @@ int groot_hip_ec_reset(groot_ctx *c)
     if (c->ct.rec_on) {                    // (the rescued reads are counted with the classes they are in)
         HIP_TRY(c, hipMemset(c->ct.rec_stats.p, 0, kRescueEcStats * sizeof(unsigned long long)));
         c->ct.rec_slow = 0;
+    }
+    if (c->ct.gec_on) {                    // (and the gap-placed ones)
+        HIP_TRY(c, hipMemset(c->ct.gec_stats.p, 0, kGapEcStats * sizeof(unsigned long long)));
+        c->ct.gec_slow = 0;
     }
     if (c->ct.pairs_on) HIP_TRY(c, hipMemset(c->ct.sh_stats.p + kSharedPairStats, 0, (kSharedStats - kSharedPairStats) * sizeof(unsigned long long)));
     return groot_hip_acov_reset(c);     // (the serials start again: its tuples would name other classes)
@@ -1480,6 +1571,7 @@ int groot_hip_gap_enable(groot_ctx *c, uint32_t max_gap, uint64_t event_slots)
     Counters &k = c->ct;
     if (!max_gap) {
         gr_release(c);                     // (the gapped records are gapped rescue's placements: off with it)
+        gec_release(k);                    // (and so are the gap-placed reads in the classes)
         gap_release(k);
         return GROOT_OK;
     }
@@ -1510,6 +1602,7 @@ int groot_hip_gap_enable(groot_ctx *c, uint32_t max_gap, uint64_t event_slots)
     }
     if (e != hipSuccess) {
         gr_release(c);
+        gec_release(k);
         gap_release(k);
         return fail(c, GROOT_E_DEVICE, "gapped rescue: %s", hipGetErrorString(e));
     }
@@ -1649,6 +1742,8 @@ int groot_hip_rescue_acov_enable(groot_ctx *c, int on, uint64_t min_slots)
     if (min_slots & (min_slots - 1)) return fail(c, GROOT_E_INVALID, "rescued reads in assigned coverage: min_slots = %llu is not a power of two", (unsigned long long)min_slots);
     if (min_slots > (1ull << 31)) return fail(c, GROOT_E_INVALID, "rescued reads in assigned coverage: min_slots = %llu, at most 2^31 are supported", (unsigned long long)min_slots);
     if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in assigned coverage with paired-end units are not supported: mates are rescued one by one");
+    if (k.gec_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in assigned coverage with gap-placed reads in the equivalence classes are not supported: the pileup has no "
+                              "rule for a gapped record (groot_hip_gap_ec_enable)");
     if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: mismatch rescue is off (groot_hip_rescue_enable)");
     if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: equivalence classes are off (groot_hip_ec_enable)");
     if (!k.acov_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: assigned coverage is off (groot_hip_acov_enable)");
@@ -1789,6 +1884,48 @@ int groot_hip_gap_rec_stats(groot_ctx *c, groot_gap_rec_stats *out)
     out->records = k.gr_on ? k.gr_records : 0; out->reads = k.gr_on ? k.gr_reads : 0; out->failed = k.gr_on ? k.gr_failed : 0;
     out->slots = k.gr_on ? k.gr_slots : 0;
     out->launches = k.gr_launches;
+    return GROOT_OK;
+}
+
+// ---- gap-placed reads in the equivalence classes (kernels_gap_ec.hpp; the definition is in groot_hip.h) ----------------------
+int groot_hip_gap_ec_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!on) {
+        gec_release(k);
+        return GROOT_OK;
+    }
+    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: gapped rescue is off (groot_hip_gap_enable)");
+    if (!k.rec_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: the rescued reads in the equivalence classes are off (groot_hip_rescue_ec_enable)");
+    if (k.rac_on) return fail(c, GROOT_E_UNSUPPORTED, "gap-placed reads in the equivalence classes with rescued reads in assigned coverage are not supported: the pileup has no "
+                              "rule for a gapped record, and a DEL covers two intervals (groot_hip_rescue_acov_enable)");
+    if (k.gec_on) return GROOT_OK;
+    hipError_t e = k.gec_e.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
+    if (e == hipSuccess) e = k.gec_stats.alloc(kGapEcStats);
+    if (e == hipSuccess) e = hipMemset(k.gec_stats.p, 0, kGapEcStats * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        gec_release(k);
+        return fail(c, GROOT_E_DEVICE, "gap-placed reads in the equivalence classes: %s", hipGetErrorString(e));
+    }
+    k.gec_slow = 0;
+    k.gec_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_gap_ec_stats(groot_ctx *c, groot_gap_ec_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kGapEcStats] = {};
+    if (c->ct.gec_on) {
+        if (int rc = drain(c)) return rc;
+        HIP_TRY(c, hipMemcpy(st, c->ct.gec_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    }
+    out->slow_reads = c->ct.gec_on ? c->ct.gec_slow : 0;
+    out->reads = st[0] + out->slow_reads;
+    out->launches = c->ct.gec_launches;
     return GROOT_OK;
 }
 

@@ -135,6 +135,7 @@ struct CounterStatus {
     uint32_t rac_log;                      // rescued reads in assigned coverage: the kept placements of those reads (SlotCounters::d_rac_nlog[0])
     uint64_t rr_total;                     // rescued records: the batch's records (SlotCounters::d_rr_total[0])
     uint64_t gr_total;                     // gapped records: the batch's records (SlotCounters::d_gr_total[0])
+    uint32_t gec_slow;                     // gap-placed reads in the ECs: the batch's slow gap-rescued reads (SlotCounters::d_gec_slow[0])
 };
 
 struct SlotCounters {
@@ -161,6 +162,8 @@ struct SlotCounters {
     PinBuf<groot_gap_record> h_gr_rec;     // what groot_hip_gap_rec_batch hands out: as many as the batch has
     uint64_t gr_n = 0;                     // the batch's records in h_gr_rec
     bool gr = false;                       // the feature was on when the batch was submitted
+    DevBuf<uint32_t> d_gec_slow;           // gap-placed reads in the ECs: [0] the batch's slow gap-rescued reads, with or without a bitmap (gap_ec_slow_kernel);
+                                           // their bitmaps are the rows of d_rec_bits behind the rescued reads'
 };
 
 struct Counters {
@@ -268,6 +271,15 @@ struct Counters {
     DevBuf<uint8_t> gr_e;                  // GapRecArgs::gap_e
     uint64_t gr_records = 0, gr_reads = 0, gr_failed = 0;   // handed out / gap-rescued reads among them / batches failed for room, since enable
     uint64_t gr_launches = 0;              // the scan and gap_rec_emit_kernel since open (rescue_gap_rec_kernel counts as gapped rescue's)
+    // gap-placed reads in the equivalence classes (groot_hip_gap_ec_*, kernels_gap_ec.hpp): needs gapped rescue and the rescued reads in the
+    // ECs on.  rescue_gap_ec_kernel takes the gap kernel's place and also writes every gap-rescued read's path set as a row; two kernels
+    // among those of the rescued reads fold the rows into the table of ECs, the sets in too many graphs come back as bitmaps of the
+    // rescued reads' pool and are folded on the host at collect.  Nothing on the device while off.
+    bool gec_on = false;
+    DevBuf<uint8_t> gec_e;                 // GapEcCountArgs::e (tail stream: one batch at a time, as the gap candidates are)
+    DevBuf<unsigned long long> gec_stats;  // [kGapEcStats]
+    uint64_t gec_slow = 0;                 // slow gap-rescued reads folded at collect since enable / groot_hip_ec_reset
+    uint64_t gec_launches = 0;             // gap_ec_slow_kernel and gap_ec_insert_kernel since open (rescue_gap_ec_kernel counts as gapped rescue's)
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

@@ -125,12 +125,12 @@ __device__ __forceinline__ bool gap_block_in(uint32_t i, uint32_t h, uint32_t in
     return !ins || (h ? i >= 1u : kRescueAnchor * i + kRescueAnchor + g <= len);
 }
 
-// what a sweep-2 walk tells of every kept tuple beyond the tables: nothing here, their number per read for the gapped records
-// (kernels_gap_rec.hpp)
+// what a sweep-2 walk tells of every kept tuple (of read r, on path p) beyond the tables: nothing here, their number per read for the
+// gapped records (kernels_gap_rec.hpp), the path to the read's set row for the gap-placed reads in the classes (kernels_gap_ec.hpp)
 struct GapNoSink {
     __device__ __forceinline__ void begin() {}
-    __device__ __forceinline__ void kept() {}
-    __device__ __forceinline__ void done(uint32_t, uint32_t, uint32_t, bool) {}
+    __device__ __forceinline__ void kept(const RescueArgs &, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void done(const RescueArgs &, uint32_t, uint32_t, uint32_t, bool) {}
 };
 
 // One sweep over the tuples of the oriented reads at w0 (len bases): occurrence x hypothesis x type x g.  Sweep 0 lowers `best` to the
@@ -195,7 +195,7 @@ template <class Sink> __device__ __forceinline__ void rescue_gap_body(const GapA
                 st[1]++;
                 st[2] += 1u - ins;
                 st[3] += ins;
-                sink.kept();
+                sink.kept(a, r, p);
                 const uint64_t at = a.slot_base[p] + pi.z + x;
                 atomicAdd(ga.starts + at, 1ull);
                 uint32_t seq = 0;
@@ -213,7 +213,7 @@ template <class Sink> __device__ __forceinline__ void rescue_gap_body(const GapA
                 gap_event_add(ga, gap_event_key(at + ks - 1u, ins, g, seq));
             });
         if (best <= M + G) st[0]++;
-        sink.done(c, r, best, best <= M + G);
+        sink.done(a, c, r, best, best <= M + G);
     }
     const uint32_t where[4] = {1, 2, 3, 4};
     rescue_add_stats(ga.stats, st, where);

@@ -43,8 +43,8 @@ struct GapRecCount {
     uint8_t *gap_e;
     uint32_t n;
     __device__ __forceinline__ void begin() { n = 0; }
-    __device__ __forceinline__ void kept() { n++; }
-    __device__ __forceinline__ void done(uint32_t c, uint32_t r, uint32_t best, bool rescued)
+    __device__ __forceinline__ void kept(const RescueArgs &, uint32_t, uint32_t) { n++; }
+    __device__ __forceinline__ void done(const RescueArgs &, uint32_t c, uint32_t r, uint32_t best, bool rescued)
     {
         gap_e[c] = rescued ? (uint8_t)best : kGapRecNone;
         if (rescued) n_gkept[r] = n;

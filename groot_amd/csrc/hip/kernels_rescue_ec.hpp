@@ -64,13 +64,19 @@ struct RescueRow {
         val = sm[at * a.pw + word] | bit;
     }
 
-    // behind the sweeps of candidate i (read r): the word in hand written back, the row ended, d* kept
-    __device__ __forceinline__ void done(const RescueArgs &a, uint32_t r, uint32_t i, uint32_t best)
+    // behind the sweeps of read r: the word in hand written back, the row ended
+    __device__ __forceinline__ void end(const RescueArgs &a, uint32_t r)
     {
         uint32_t *sg = a.set_graph + (size_t)r * kSharedSegs;
         if (open) a.set_mask[((size_t)r * kSharedSegs + k) * a.pw + w] = val;
         if (slow || !nseg) sg[0] = kSharedEmpty;
         else for (uint32_t j = nseg; j < kSharedSegs; j++) sg[j] = kSharedEmpty;
+    }
+
+    // behind the sweeps of candidate i (read r): the row ended, d* kept
+    __device__ __forceinline__ void done(const RescueArgs &a, uint32_t r, uint32_t i, uint32_t best)
+    {
+        end(a, r);
         a.dstar[i] = best <= a.max_mismatch ? (uint8_t)best : kRescueUnplaced;
     }
 };

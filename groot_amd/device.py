@@ -81,6 +81,7 @@ def lib():
         L.groot_hip_close.argtypes = [C.c_void_p]
         L.groot_hip_close.restype = None
         _ffi.rarefy_hip_prototypes(L)
+        _ffi.gap_ec_prototypes(L)
         _lib = L
     return _lib
 
@@ -670,6 +671,18 @@ class Aligner:
         v = (C.c_uint64 * 5)()
         self._check(lib().groot_hip_gap_rec_stats(self._h, v))
         return dict(zip(("records", "reads", "failed", "slots", "launches"), (int(x) for x in v)))
+
+    # ---- gap-placed reads in the equivalence classes (groot_hip_gap_ec_*) ---------------------------------
+    def gap_ec_enable(self, on=True):
+        """from now on a gap-rescued read counts in the equivalence classes with the set of paths it was gap-placed on (include/groot_hip.h,
+        "gap-placed reads in the equivalence classes").  Needs gap_enable and rescue_ec_enable first.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_gap_ec_enable(self._h, C.c_int(1 if on else 0)))
+
+    def gap_ec_stats(self):
+        """groot_hip_gap_ec_stats: {"reads", "slow_reads", "launches"}; zeros while off, but for launches"""
+        v = (C.c_uint64 * len(_ffi.GAP_EC_STATS))()
+        self._check(lib().groot_hip_gap_ec_stats(self._h, v))
+        return dict(zip(_ffi.GAP_EC_STATS, (int(x) for x in v)))
 
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):

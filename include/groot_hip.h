@@ -575,7 +575,7 @@ int groot_hip_gap_reset(groot_ctx *ctx);
  *
  * With the feature on, the run's ECs are the distinct non-empty S+(r) with their read counts; a rescued read and an exact read with
  * the same set are one EC.  Nothing else changes: records, BAM, GFA, weights, coverage, shared reads, the rescue tables, the gap tables
- * (a read placed with a gap is in no class), and every stat that exists today.  The ECs depend on the reads and the index alone: not on
+ * (a read placed with a gap is in no class, unless the gap-placed reads in the classes are on: below), and every stat that exists today.  The ECs depend on the reads and the index alone: not on
  * batch size, pipeline depth, align-stage variant, results_on_device, or how the reads are spread over ctxs; the merge of several ctxs
  * is a sum by set.  A pass that collect redoes counts once, a batch under the skip flags of report coverage counts nothing.
  * Off by default: then no allocation, launch or sync, and rescue_count_kernel is the one of mismatch rescue alone. */
@@ -744,6 +744,44 @@ int groot_hip_gap_rec_enable(groot_ctx *ctx, uint64_t slots_per_batch);
 int groot_hip_gap_rec_batch(groot_ctx *ctx, uint64_t ticket, const groot_gap_record **recs, uint64_t *n);
 /* Zeros while off, but for launches.  Counts collected batches only; does not wait. */
 int groot_hip_gap_rec_stats(groot_ctx *ctx, groot_gap_rec_stats *out);
+
+/* ---- gap-placed reads in the equivalence classes ---------------------------------------------------------------------------
+ * The rescued reads in the classes stop at the reads mismatch rescue places.  A read that lies across a frameshift, or across a codon
+ * deletion or insertion, is placed by gapped rescue, and is in no class.  With this on, it is a unit of the classes with the set of
+ * paths it was gap-placed on.  The definition:
+ *
+ *   S(r), R(r), S+(r): as in "rescued reads in the equivalence classes".  Gap candidate, kept gapped placement (p, strand, x, type, g, k*), e*:
+ *   as in "gapped rescue".
+ *   G(r)    for a read r that is GAP-RESCUED (a gap candidate with a kept gapped placement, e*(r) <= M + G): the set of global paths p for
+ *           which r has a kept gapped placement -- any strand, x, type, g; each p once.  Not defined for any other read.
+ *   S++(r)  = S(r) when r has a record;  R(r) when r is rescued ungapped;  G(r) when r is gap-rescued;  empty otherwise.
+ *           (The three exclude each other: a candidate has no record, and a gap candidate is a candidate that ended unplaced.)
+ *   With the feature on the run's ECs are the distinct non-empty S++(r) with their read counts.  Reads of the three kinds with the same set
+ *   are one EC.
+ *
+ * A candidate that is rescued ungapped stays in R(r), even where a gapped placement would cost less (the rule of "gapped rescue").
+ * Nothing else changes: records, BAMs, coverage, shared reads, the rescue and gap tables, events, and every stat that exists today keep
+ * their values.  The ECs depend on the reads and the index alone: not on batch size, pipeline depth, align-stage variant,
+ * results_on_device, or how the reads are spread over ctxs.  A pass that collect redoes counts once, a batch under the skip flags of
+ * report coverage adds nothing.  Off by default: then no allocation, launch or sync, and the gap kernel is the one it is without this
+ * section. */
+typedef struct groot_gap_ec_stats {
+    uint64_t reads;       /* gap-rescued reads added to the classes since enable / groot_hip_ec_reset */
+    uint64_t slow_reads;  /* those among them whose set lies in more than 4 graphs (1 under GROOT_TEST_SHARED_SLOW): folded on the host from
+                             bitmaps of the pool of groot_rescue_ec_stats.rows; groot_rescue_ec_stats.slow_reads stays the ungapped reads' alone */
+    uint64_t launches;    /* gap_ec_slow_kernel and gap_ec_insert_kernel, launched since open, whether it is on now or not (rescue_gap_ec_kernel
+                             counts in groot_gap_stats.launches) */
+} groot_gap_ec_stats;
+/* on != 0: on.  Needs gapped rescue and the rescued reads in the equivalence classes on (GROOT_E_STATE otherwise), and nothing in flight
+ * (GROOT_E_STATE).  GROOT_E_UNSUPPORTED beside the rescued reads in assigned coverage, from whichever enable comes second: the pileup has
+ * no rule for a gapped record, and a DEL covers two intervals.  groot_hip_gap_enable(.., 0, ..), groot_hip_rescue_ec_enable(.., 0),
+ * mismatch rescue off and the equivalence classes off switch it off too; another G or another M leaves the classes alone;
+ * groot_hip_ec_reset zeroes these stats with the classes.  The rescued and the gap-rescued reads of a batch in more than 4 graphs share
+ * the slot's `rows` bitmaps: more of them together fail the batch at collect with GROOT_E_NOSPACE (the message names
+ * GROOT_TEST_RESCUE_EC_ROWS).  Device memory: 1 byte per read of a batch. */
+int groot_hip_gap_ec_enable(groot_ctx *ctx, int on);
+/* Waits for everything in flight; zeros while off, but for launches. */
+int groot_hip_gap_ec_stats(groot_ctx *ctx, groot_gap_ec_stats *out);
 
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
