@@ -70,7 +70,7 @@ template <class T> struct PinBuf {
 // a test batch walks the grow-and-redo and the fall-back paths; OPEN_STATS prints where groot_hip_open spent its time.
 struct Knobs {
     bool no_outcome_table = false, no_text_table = false, no_sig = false, force_rccl = false, small_buffers = false, open_stats = false, poison = false, lean = false, no_path = false,
-         shared_slow = false, serial_tail = false, assign_global = false;
+         shared_slow = false, serial_tail = false, assign_global = false, library_sort = false;
     uint32_t ec_slots = 0;                 // GROOT_TEST_EC_SLOTS: initial slots of the equivalence-class table (0 = the default)
     uint32_t acov_slots = 0;               // GROOT_TEST_ACOV_SLOTS: initial slots of the assigned-coverage table (0 = the default)
     uint32_t rescue_ec_rows = 0;           // GROOT_TEST_RESCUE_EC_ROWS: bitmaps of slow rescued reads per batch (0 = from the byte budget)
@@ -87,6 +87,7 @@ struct Knobs {
         k.shared_slow = getenv("GROOT_TEST_SHARED_SLOW") != nullptr;      // shared reads: every read in more than one graph takes the slow path
         k.serial_tail = getenv("GROOT_SERIAL_TAIL") != nullptr;           // the tail of the align stage stays on the walk stream (no tail stream: the A/B baseline)
         k.assign_global = getenv("GROOT_TEST_ASSIGN_GLOBAL") != nullptr;  // assignment: alpha is read from global memory even when it fits in LDS
+        k.library_sort = getenv("GROOT_LIBRARY_SORT") != nullptr;         // the processing-order sort of every batch through rocprim::radix_sort_pairs (order_sort.hpp: the A/B baseline)
         if (const char *e = getenv("GROOT_TEST_EC_SLOTS")) k.ec_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         if (const char *e = getenv("GROOT_TEST_ACOV_SLOTS")) k.acov_slots = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
         if (const char *e = getenv("GROOT_TEST_RESCUE_EC_ROWS")) k.rescue_ec_rows = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 1ul << 30);
@@ -449,6 +450,7 @@ struct groot_ctx {
     uint64_t next_ticket = 1;
     Slot *waited = nullptr;                // the batch groot_hip_wait collected (released by the next submit / wait)
     double todo_frac = 1.0;                // share of the latest finished batch's reads that the first seed kernel left to the list pass
+    double lsh_frac = -1.0, long_frac = -1.0;   // shares of the latest finished batch's reads on lsh_heavy_kernel's and sort_seed_lists_kernel's lists (negative: no batch yet): their grids
     double lean_left_frac = 1.0;           // share of the latest finished batch's reads that the first pass of the align stage left to the second
     uint32_t n_cu = 256;
     double dfs_frac = 1.0;                 // share of the latest finished batch's reads that needed the align stage's graph walk (the rest: no seeds / tabulated outcomes)
@@ -475,6 +477,11 @@ struct groot_ctx {
     DevBuf<uint32_t> lsh_list, lsh_count;  // reads on the LSH-Forest branch with many candidate rows + their sketches, for lsh_heavy_kernel (seed stage)
     DevBuf<uint64_t> lsh_sketch;
     DevBuf<char> sort_tmp, in_tmp;         // rocprim scratch of the seed stage / of the input decoding (compute stream)
+    // The processing-order sort under the project's own launcher (order_sort.hpp; compute stream): its one scratch block for batches of up to
+    // order_cap reads.  The block's state is all zero between two sorts; order_dirty_* is the sort whose clear is still to be issued (n = 0: none).
+    DevBuf<uint32_t> order_buf;
+    size_t order_cap = 0;
+    uint32_t order_dirty_n = 0, order_dirty_begin = 0, order_dirty_end = 0;
     uint32_t ovf_cap = 0;
     DevBuf<uint32_t> trav_off;             // order stage (tail stream)
     DevBuf<char> scan_tmp;                 // rocprim scratch of the order stage (tail stream)

@@ -40,6 +40,8 @@ struct DeviceCounters {
     unsigned int tab_reads;     // reads the signature kernel answered from the outcome table
     unsigned int lean_reads;    // reads align_lean_kernel finished
     unsigned int path_reads;    // reads align_path_kernel finished
+    unsigned int lsh_reads;     // reads on lsh_heavy_kernel's list (may exceed its capacity) ...
+    unsigned int long_reads;    // ... and on sort_seed_lists_kernel's: they size the two kernels' grids for the next batch (assign_q_rows_kernel writes both)
     unsigned long long dbg[192]; // work counters (only with -DGROOT_WORK_COUNTERS): [e] wave iterations with event e, [32+e] lanes with it,
                                  // [64+b] lanes finishing their read b*2 iterations into the round, [128+b] rounds of that length
 };

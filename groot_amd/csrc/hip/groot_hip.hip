@@ -33,6 +33,7 @@
 #include "kernels_path.hpp"
 #include "launch.hpp"
 #include "open.hpp"
+#include "order_sort.hpp"
 
 using namespace groot;
 
@@ -168,9 +169,31 @@ using OrderSortConfig = rocprim::radix_sort_config<
                                         rocprim::block_radix_rank_algorithm::match>,
     GROOT_SORT_MERGE_LIMIT>;
 
+// Round 28: the grid of a wavefront-per-read kernel over a list whose length the latest finished batch predicts (frac: its share of that batch's reads,
+// negative = no batch has finished yet).  A wavefront per expected read and a quarter more, at least a workgroup per CU, at most `most` -- round 5's grid,
+// which every list of 4 x most / 1.25 reads or more keeps, as does a ctx that has seen no batch: on configs[2] the lists are empty or nearly so and
+// 16 384 workgroups that find nothing cost 0.06 ms of grid dispatch each.  Grid-stride loops: a list longer than predicted is slower, never wrong.
+static uint32_t wave_list_blocks(const groot_ctx *c, const Slot *s, double frac, uint32_t most)
+{
+    if (frac < 0.0) return most;
+    const double want = frac * 1.25 * (double)s->n_reads / (kBlock / 64) + 1.0;
+    return want >= (double)most ? most : std::min(most, std::max<uint32_t>((uint32_t)want, c->n_cu));
+}
+
 // a batch of one read length of which fewer than six reads in ten (but not next to none) are walked, by the latest finished batch: reads with errors --
 // the exact ones seed, the others do not.  The hashing kernels of the next batch are the longer stage there.
 static bool error_batch(const groot_ctx *c, const Slot *s) { return c->dfs_frac >= kSparseBelow && c->dfs_frac < 0.6 && !s->mixed_len; }
+
+// the one fill of the order sort's scratch (order_sort.hpp): zeroes what the latest sort through it dirtied.  On the compute stream, behind that sort.
+static int clear_order_sort(groot_ctx *c)
+{
+    if (!c->order_dirty_n) return GROOT_OK;
+    const order_sort::Scratch sc{c->order_buf.p, c->order_cap};
+    const uint32_t n = c->order_dirty_n;
+    c->order_dirty_n = 0;
+    HIP_TRY(c, order_sort::clear(sc, n, c->order_dirty_begin, c->order_dirty_end, c->stream));
+    return GROOT_OK;
+}
 
 static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
 {
@@ -243,9 +266,9 @@ static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
     if (c->lsh_list.p && !c->prm.keep_sketches) {
         a.lsh_list = c->lsh_list.p; a.lsh_count = c->lsh_count.p; a.lsh_sketch = c->lsh_sketch.p;
         a.lsh_defer_rows = c->lsh_defer_rows; a.lsh_cap = c->lsh_cap;
-        HIP_TRY(c, hipMemsetAsync(c->lsh_count.p, 0, 2 * sizeof(uint32_t), c->stream));
     }
-    HIP_TRY(c, hipMemsetAsync(w->vcount.p, 0, 2 * sizeof(uint32_t), c->stream));
+    // (lsh_count, todo_count, long_count: zero -- assign_q_rows_kernel at the end of the seed stage before left them so; w->vcount: order_ovf_kernel
+    // of the batch that used the work set before did; both were cleared when they were allocated)
     if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[7], c->stream));
     if (s->text_used) {
         a.todo_list = c->todo_list.p;
@@ -253,7 +276,6 @@ static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
         const uint32_t stride_dw = ((s->max_len + 3) / 4 + 1) | 1u;
         a.list_stride_dw = list_lds_stride(stride_dw);
         const size_t lds = kTextBad + (size_t)((a.lds_read_bytes + 15) / 16) * 4 + 96;
-        HIP_TRY(c, hipMemsetAsync(c->todo_count.p, 0, sizeof(uint32_t), c->stream));
         if (list_mode) {       // the reads left for the graph walk are a subset of the lookup's misses: the list pass appends them itself
             a.dfs_list = w->perm.p; a.dfs_count = w->perm_count.p;
             HIP_TRY(c, hipMemsetAsync(w->perm_count.p, 0, sizeof(uint32_t), c->stream));
@@ -268,7 +290,6 @@ static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
         a.todo_count = c->todo_count.p;
         const uint32_t stride_dw = ((s->max_len + 3) / 4 + 1) | 1u;     // the LIST pass copies each read into its lane's LDS slice
         a.list_stride_dw = list_lds_stride(stride_dw);
-        HIP_TRY(c, hipMemsetAsync(c->todo_count.p, 0, sizeof(uint32_t), c->stream));
         // (the reads it decides it also leaves as 2-bit codes for the first pass of the align stage)
         if ((c->lean || c->path) && !c->tab_capture && w->packed.p) { a.packed = w->packed.p; a.packed_q = s->max_len <= 128 ? 2u : 4u; }
         s->packed_q = a.packed ? a.packed_q : 0;
@@ -283,7 +304,7 @@ static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
         if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[8], c->stream));
     }
     // the reads of the LSH-Forest branch with many candidate rows: a wavefront each
-    if (a.lsh_list) hipLaunchKernelGGL(lsh_heavy_kernel, dim3(std::min<uint32_t>(grid.x, GROOT_HEAVY_BLOCKS)), dim3(kBlock), 0, c->stream, a);
+    if (a.lsh_list) hipLaunchKernelGGL(lsh_heavy_kernel, dim3(std::min<uint32_t>(grid.x, wave_list_blocks(c, s, c->lsh_frac, GROOT_HEAVY_BLOCKS))), dim3(kBlock), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[12], c->stream));   // (the list pass behind the first kernel + the heavy LSH-Forest reads)
     // seed lists of more than four windows that are not ascending (LSH-Forest hits come in band order): sorted, a wavefront per read
@@ -295,11 +316,11 @@ static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
         sa.split = c->vcap && !c->tab_capture && !c->prm.no_exact_align;
         sa.vitem = w->vitem.p; sa.vcount = w->vcount.p; sa.vcap = c->vcap; sa.split_list = w->split_list.p;
         sa.ctr = s->d_ctr.p; sa.update_weights = update_weights ? 1 : 0;
-        hipLaunchKernelGGL(sort_seed_lists_kernel, dim3(GROOT_SORTLIST_BLOCKS), dim3(kBlock), 0, c->stream, sa);
+        hipLaunchKernelGGL(sort_seed_lists_kernel, dim3(wave_list_blocks(c, s, c->long_frac, GROOT_SORTLIST_BLOCKS)), dim3(kBlock), 0, c->stream, sa);
     }
     if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[2], c->stream));
     hipLaunchKernelGGL(assign_q_rows_kernel, dim3(1), dim3(64), 0, c->stream, c->q_seen.p, c->q_row.p, c->q_of_row.p, c->q_nrows.p, c->att_cap,
-                       c->max_q, s->d_ctr.p, c->seed_shards.p, c->long_count.p);
+                       c->max_q, s->d_ctr.p, c->seed_shards.p, c->long_count.p, c->todo_count.p, c->lsh_count.p, w->ovf_cnt.p);
     if (a.tab_hist) {
         hipLaunchKernelGGL(fold_tab_hist_kernel, dim3(std::min<uint32_t>((c->n_windows + kBlock - 1) / kBlock, 1024u)), dim3(kBlock), 0, c->stream, c->tab_hist.p,
                            c->attempts_ptr, c->q_row.p, c->dix.w - c->k + 1, c->n_windows, s->d_ctr.p, update_weights ? 1u : 0u);
@@ -327,6 +348,25 @@ static int launch_seed_stage(groot_ctx *c, Slot *s, bool update_weights)
     // (batches of one read length of which fewer than six reads in ten are walked -- reads with errors: the previous batch's first pass is the shorter
     // stage there and the sort does not wait for it; the small blocks cost 0.1 ms alone and 3 % of that workload's rate, so it keeps rocprim's default)
     const bool small_blocks = !error_batch(c, s);
+    // Round 28: the batches that take the onesweep configured above go through the project's own launcher (order_sort.hpp): rocprim's device code, but no
+    // fill between two of its kernels -- the one clear of its scratch is issued by run_batch_async behind ev_seed, beside the first pass.  Batches at or
+    // below GROOT_SORT_MERGE_LIMIT and batches that keep rocprim's default call the library as before; GROOT_LIBRARY_SORT: every batch does.
+    if (small_blocks && !c->kn.library_sort && s->n_reads > GROOT_SORT_MERGE_LIMIT && s->n_reads <= order_sort::kMaxItems) {
+        if (s->n_reads > c->order_cap) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            const size_t cap = (size_t)s->n_reads + s->n_reads / 4;
+            c->order_cap = 0;
+            HIP_TRY(c, c->order_buf.alloc(order_sort::Scratch::bytes(cap) / sizeof(uint32_t)));
+            c->order_cap = cap;
+            c->order_dirty_n = 0;
+            HIP_TRY(c, hipMemsetAsync(c->order_buf.p, 0, order_sort::state_words(cap, order_sort::kMaxPlaces) * sizeof(uint32_t), c->stream));
+        }
+        const order_sort::Scratch sc{c->order_buf.p, c->order_cap};
+        if (int rc = clear_order_sort(c)) return rc;         // (a sort whose clear an error return skipped)
+        c->order_dirty_n = s->n_reads; c->order_dirty_begin = begin_bit; c->order_dirty_end = end_bit;
+        HIP_TRY(c, order_sort::sort_pairs(sc, c->sort_key.p, c->sort_key_out.p, c->perm_in.p, w->perm.p, s->n_reads, begin_bit, end_bit, c->stream));
+        return GROOT_OK;
+    }
     auto sort = [&](void *tmp) {
         return small_blocks ? rocprim::radix_sort_pairs<OrderSortConfig>(tmp, tmp_bytes, c->sort_key.p, c->sort_key_out.p, c->perm_in.p, w->perm.p, s->n_reads,
                                                                          begin_bit, end_bit, c->stream)
@@ -420,8 +460,8 @@ static int launch_align_stage(groot_ctx *c, Slot *s, bool update_weights)
     // beside the first pass of batch b+1.  A batch without a first pass has no walk part: its whole stage goes on the tail stream, so that the
     // persistent align_kernel launches (they share the DFS stacks) stay in order with one another.
     const bool first_pass = s->lean_used || s->path_used;
-    hipStream_t walk = first_pass ? c->astream : c->tstream;
-    HIP_TRY(c, hipMemsetAsync(w->ovf_cnt.p, 0, (kOvfShards + 3) * sizeof(uint32_t), walk));   // + the two chunk cursors + the length of the first pass's list
+    // (w->ovf_cnt -- the shard counts, the two chunk cursors and the length of the first pass's list -- is zero: assign_q_rows_kernel of this batch's seed
+    // stage cleared it, so nothing stands on the walk stream between the wait for ev_seed and the first pass)
     // First pass (kernels_lean.hpp): a thread per read in processing order finishes the reads of one seed window whose walks never branch;
     // the reads it leaves it appends to a list (a wavefront at a time, in the order the wavefronts finish), and align_kernel takes that list.
     const uint32_t lean_stride = lean_stride_dw(s->max_len);
@@ -479,7 +519,7 @@ static int launch_order_stage(groot_ctx *c, Slot *s, bool update_weights)
         HIP_TRY(c, c->scan_tmp.alloc(tmp_bytes + tmp_bytes / 4));
     }
     HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tmp_bytes, w->trav_cnt.p, c->trav_off.p, 0u, n, rocprim::plus<uint32_t>(), c->tstream));
-    hipLaunchKernelGGL(order_total_kernel, dim3(1), dim3(1), 0, c->tstream, c->trav_off.p, w->trav_cnt.p, n, s->d_ctr.p);
+    // (the batch's record count, n_trav: one thread of order_first_kernel writes it)
     OrderTabArgs ot{};
     if (c->dix.out_tab) {
         ot.tab_idx = w->tab_idx.p; ot.out_tab = c->dix.out_tab; ot.stride_q = c->dix.out_stride_q; ot.first_read_id = s->first_read_id;
@@ -496,7 +536,7 @@ static int launch_order_stage(groot_ctx *c, Slot *s, bool update_weights)
                                     c->trav_off.p, w->trav_first.p, w->mask_first.p, n, s->first_read_id, s->d_trav.p, s->d_mask.p, s->trav_cap, c->pw, c->pw_view, s->d_ctr.p);
     hipLaunchKernelGGL(order_ovf_kernel, dim3((c->ovf_cap + kBlock - 1) / kBlock, kOvfShards), dim3(kBlock), 0, c->tstream,
                        w->ovf_trav.p, w->ovf_mask.p, w->ovf_cnt.p, c->ovf_cap, c->trav_off.p, s->first_read_id, s->d_trav.p,
-                       s->d_mask.p, s->trav_cap, c->pw, c->pw_view, s->d_ctr.p, w->vitem.p, n);
+                       s->d_mask.p, s->trav_cap, c->pw, c->pw_view, s->d_ctr.p, w->vitem.p, n, w->vcount.p);
     HIP_TRY(c, hipGetLastError());
     // assignment (groot_hip_assign_enable): the records are complete and nothing has read them yet -- the compact copy-out below, the packed
     // records, the counters and groot_hip_read_travs all see what it leaves.  It runs once per pass on freshly written records, never twice
@@ -546,6 +586,9 @@ static int run_batch_async(groot_ctx *c, Slot *s, bool update_weights)
     if (int rc = launch_seed_stage(c, s, update_weights)) return rc;
     if (c->profiling) HIP_TRY(c, hipEventRecord(s->ev[3], c->stream));
     HIP_TRY(c, hipEventRecord(s->ev_seed, c->stream));
+    // (the order sort's scratch is cleared for the next batch here: behind the last iteration and behind the event the walk stream waits for, so the
+    // fill runs beside the first pass and not between two kernels of the chain)
+    if (int rc = clear_order_sort(c)) return rc;
     // walk + tail streams: graph walk and ordering, beside the seed stage of the next batch.  The stage starts on the walk stream when a first
     // pass runs for this batch (launch_align_stage moves to the tail stream behind it), on the tail stream otherwise.
     s->lean_used = c->lean && !c->tab_capture && s->n_reads && s->max_len <= kLeanMaxLen && c->dfs_frac >= 0.02;
@@ -927,6 +970,7 @@ static int finish_counters(groot_ctx *c, Slot *s)
         c->lean_left_frac = (double)(h.seeded_reads - std::min(h.seeded_reads, first)) / (double)s->n_reads;
     }
     if (s->n_reads && (s->sig_used || s->text_used)) c->todo_frac = (double)h.todo_reads / (double)s->n_reads;
+    if (s->n_reads) { c->lsh_frac = (double)h.lsh_reads / (double)s->n_reads; c->long_frac = (double)h.long_reads / (double)s->n_reads; }
     if (s->n_reads && !c->tab_capture && c->dix.text_tab) {
         c->text_hit_frac = s->text_used ? 1.0 - (double)h.todo_reads / (double)s->n_reads : (double)h.tab_reads / (double)s->n_reads;
         // (a batch that tried the lookup in vain sent all its reads through the list pass: on a stream the memo cannot answer --

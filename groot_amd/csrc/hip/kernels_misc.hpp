@@ -285,12 +285,24 @@ __global__ __launch_bounds__(kBlock) void order_split_kernel(const uint4 *__rest
 // the align stage.  More kmerCounts than rows: kFlagQOverflow, the align stage does nothing, the host grows the table
 // and re-runs the batch.
 __global__ __launch_bounds__(64) void assign_q_rows_kernel(uint32_t *q_seen, uint32_t *q_row, uint32_t *q_of_row, uint32_t *n_rows, uint32_t cap,
-                                                            uint32_t max_q, DeviceCounters *ctr, unsigned long long *shards, uint32_t *long_count)
+                                                            uint32_t max_q, DeviceCounters *ctr, unsigned long long *shards, uint32_t *long_count,
+                                                            uint32_t *todo_count, uint32_t *lsh_count, uint32_t *ovf_cnt)
 {
     // one wavefront: lane i folds shard i of the seed kernels' counters, then the kmerCounts are taken 64 at a time
     if (blockIdx.x) return;
-    if (!threadIdx.x) *long_count = 0;                      // (sort_seed_lists_kernel ran just before: ready for the next batch)
     const uint32_t lane = threadIdx.x;
+    // The last kernel of every seed stage, whichever branch the stage took: it leaves the ctx's list counters at zero for the next batch's
+    // seed stage (no fill in front of that stage's first kernel) and hands the two list lengths on for the next batch's grids.
+    // (sort_seed_lists_kernel, the list pass and lsh_heavy_kernel ran before it on this stream: nobody reads the counters any more)
+    if (!lane) {
+        ctr->long_reads = *long_count;
+        *long_count = 0;
+        *todo_count = 0;
+        if (lsh_count) { ctr->lsh_reads = lsh_count[0]; lsh_count[0] = 0; lsh_count[1] = 0; }
+    }
+    // ... and this batch's own work set gets its overflow counts, chunk cursors and first-pass list length cleared: the batch that used the set
+    // before is through its order stage (the seed stage waited for that), this batch's first pass and align_kernel wait for this stage's end
+    for (uint32_t i = lane; i < kOvfShards + 3; i += 64) ovf_cnt[i] = 0;
     {
         unsigned long long seeds = 0, most = 0, seeded = 0, tabbed = 0;
         for (uint32_t i = lane; i < kSeedShards; i += 64) {
@@ -378,10 +390,9 @@ __global__ __launch_bounds__(kBlock) void fold_tab_hist_kernel(uint32_t *__restr
 
 // ---- ordering: (read, ord) order without a sort -------------------------------------------------
 // off = exclusive scan of trav_cnt (rocprim); record (r, ord) lands at off[r] + ord.
-__global__ void order_total_kernel(const uint32_t *off, const uint32_t *cnt, uint32_t n, DeviceCounters *ctr)
-{
-    if (n) ctr->n_trav = off[n - 1] + cnt[n - 1];
-}
+// The batch's record count, DeviceCounters::n_trav = off[n - 1] + cnt[n - 1], is written by one thread of order_first_kernel's workgroup 0 (round 28:
+// it was a one-thread launch of its own between the scan and this kernel).  Every reader of n_trav is a kernel behind order_first_kernel on the tail
+// stream -- trav_pack_kernel, mask_words_kernel, mask_compact_kernel and the counting kernels -- or the host behind the batch's copy-out.
 
 // tab_idx[r] != kEmpty: the read's records come from the outcome table (DeviceIndex::out_tab) instead of the align stage -- cnt[r]
 // entries from tab_idx[r] on --, and this kernel does what the align stage does for the others: the IncrementSubPath call counts
@@ -403,6 +414,7 @@ __global__ __launch_bounds__(kBlock) void order_first_kernel(const groot_trav *f
     unsigned long long alns = 0, mapped = 0, multimapped = 0, seeds = 0;
     // (a pass whose seed stage ran out of slots / table rows is repeated as a whole: nothing may be counted in it)
     const bool live = !(ctr->flags & (kFlagSeedOverflow | kFlagQOverflow));
+    if (blockIdx.x == 0 && threadIdx.x == 0 && n) ctr->n_trav = off[n - 1] + cnt[n - 1];
     // (grid-stride: the three counter atomics per workgroup below share one line, ~7 ns each -- a few thousand workgroups, not 40 000)
     for (uint32_t r = blockIdx.x * kBlock + threadIdx.x; r < n; r += gridDim.x * kBlock) {
     const uint32_t tw = t.tab_idx ? t.tab_idx[r] : kEmpty;
@@ -482,10 +494,13 @@ __global__ __launch_bounds__(kBlock) void order_first_kernel(const groot_trav *f
 __global__ __launch_bounds__(kBlock) void order_ovf_kernel(const groot_trav *ovf, const uint64_t *ovf_mask, const uint32_t *ovf_cnt,
                                                          uint32_t ovf_cap, const uint32_t *off, uint32_t first_read_id, groot_trav *out,
                                                          uint64_t *mask_out, uint32_t cap, uint32_t pw_in, uint32_t pw_out,
-                                                         DeviceCounters *ctr, const uint4 *vitem, uint32_t n_reads)
+                                                         DeviceCounters *ctr, const uint4 *vitem, uint32_t n_reads, uint32_t *vcount)
 {
     const uint32_t shard = blockIdx.y;
     const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    // (the work set's item counts: split_fix_kernel and order_split_kernel, their last readers, ran before this kernel -- zero for the next batch
+    // that takes the set, whose sort_seed_lists_kernel adds to them)
+    if (!slot && !shard) { vcount[0] = 0; vcount[1] = 0; }
     if (slot >= min(ovf_cnt[shard], ovf_cap)) return;
     const size_t o = (size_t)shard * ovf_cap + slot;
     groot_trav t = ovf[o];

@@ -328,7 +328,7 @@ static int build_outcome_table(groot_ctx *c, const groot_index_view *v, const st
         HIP_TRY(c, hipMemset(c->q_nrows.p, 0, 4));
         if (c->att_cap) HIP_TRY(c, hipMemset(c->attempts_ptr, 0, (size_t)c->att_cap * c->n_windows * sizeof(uint32_t)));
         for (WorkSet &w : c->ws) w.owner = nullptr;
-        c->trav_per_read = 1.25; c->bytes_per_trav = 0; c->dfs_frac = 1.0; c->todo_frac = 1.0;
+        c->trav_per_read = 1.25; c->bytes_per_trav = 0; c->dfs_frac = 1.0; c->todo_frac = 1.0; c->lsh_frac = -1.0; c->long_frac = -1.0;
     }
     if (rc_all) return rc_all;
     lap("pipeline on the strings");
@@ -650,7 +650,10 @@ static int alloc_work_buffers(groot_ctx *c)
     HIP_TRY(c, c->trav_off.alloc(R));
     if (c->lean || c->path) HIP_TRY(c, c->lean_stk.alloc((size_t)R * 4));
     if (c->path) HIP_TRY(c, c->path_hold.alloc((size_t)R * 3 * kPathHold));
-    for (WorkSet &w : c->ws) HIP_TRY(c, w.ovf_cnt.alloc(kOvfShards + 3));
+    for (WorkSet &w : c->ws) {
+        HIP_TRY(c, w.ovf_cnt.alloc(kOvfShards + 3));
+        HIP_TRY(c, hipMemset(w.ovf_cnt.p, 0, (kOvfShards + 3) * sizeof(uint32_t)));
+    }
     if (int rc = alloc_ovf(c, c->kn.small_buffers ? 2u : std::max<uint32_t>(256, R / kOvfShards / 4))) return rc;
     // the align kernel is persistent: exactly the workgroups that are resident at once (GROOT_ALIGN_WAVES per SIMD = per CU)
     int n_cu = 256;
@@ -674,10 +677,12 @@ static int alloc_work_buffers(groot_ctx *c)
         c->lsh_cap = c->kn.small_buffers ? 4u : std::max<uint32_t>(4096, R / 4);   // (small: most heavy reads find the list full and walk their own rows)
         HIP_TRY(c, c->lsh_list.alloc(c->lsh_cap));
         HIP_TRY(c, c->lsh_count.alloc(4));
+        HIP_TRY(c, hipMemset(c->lsh_count.p, 0, 4 * sizeof(uint32_t)));
         HIP_TRY(c, c->lsh_sketch.alloc((size_t)c->lsh_cap * s));
     }
     HIP_TRY(c, c->todo_list.alloc(R));
     HIP_TRY(c, c->todo_count.alloc(1));
+    HIP_TRY(c, hipMemset(c->todo_count.p, 0, sizeof(uint32_t)));
     HIP_TRY(c, c->seed_shards.alloc((size_t)kSeedShards * kSeedShardStride));
     HIP_TRY(c, hipMemset(c->seed_shards.p, 0, (size_t)kSeedShards * kSeedShardStride * sizeof(unsigned long long)));
     HIP_TRY(c, hipDeviceSynchronize());
