@@ -208,6 +208,12 @@ int main(int argc, char **argv)
     if (groot_hip_gap_ec_enable(ctxs[0], 1) != GROOT_E_STATE) DIE("groot_hip_gap_ec_enable without gapped rescue was not refused");
     if (groot_hip_gap_ec_stats(ctxs[0], &gst)) DIE("groot_hip_gap_ec_stats: %s", groot_hip_last_error(ctxs[0]));
     if (gst.reads || gst.slow_reads || gst.launches) DIE("groot_hip_gap_ec_stats: counts while the feature is off");
+    /* GapAcovEnable / GapAcovStats: the gap-placed reads in assigned coverage need gapped rescue and the rescued reads in assigned
+     * coverage, which this run never switched on -- refused, and the stats stay zero */
+    groot_gap_acov_stats gast;
+    if (groot_hip_gap_acov_enable(ctxs[0], 1) != GROOT_E_STATE) DIE("groot_hip_gap_acov_enable without gapped rescue was not refused");
+    if (groot_hip_gap_acov_stats(ctxs[0], &gast)) DIE("groot_hip_gap_acov_stats: %s", groot_hip_last_error(ctxs[0]));
+    if (gast.placements || gast.records || gast.host_records || gast.dropped || gast.launches) DIE("groot_hip_gap_acov_stats: counts while the feature is off");
     for (int d = 0; d < n_ctx; d++) groot_hip_close(ctxs[d]);
     groot_index_free(idx);
     return 0;

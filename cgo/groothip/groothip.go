@@ -425,6 +425,34 @@ func (c *Ctx) GapEcStatsGet() (GapEcStats, error) {
 	return GapEcStats{uint64(st.reads), uint64(st.slow_reads), uint64(st.launches)}, nil
 }
 
+// GapAcovStats mirrors groot_gap_acov_stats
+type GapAcovStats struct {
+	Placements, Records, HostRecords, Dropped, Launches uint64
+}
+
+// GapAcovEnable piles every kept gapped placement of a gap-rescued read up in assigned coverage, two records for a DEL and one for an
+// INS (include/groot_hip.h, "gap-placed reads in assigned coverage").  Needs GapEnable and RescueAcovEnable first; it switches the
+// gap-placed reads in the classes on itself, and off switches both off.  Only while nothing is in flight.
+func (c *Ctx) GapAcovEnable(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.groot_hip_gap_acov_enable(c.h, v); rc != 0 {
+		return c.err("groot_hip_gap_acov_enable")
+	}
+	return nil
+}
+
+// GapAcovStatsGet returns the gapped placements and records piled up since GapAcovEnable or a reset of the table (waits for everything in flight)
+func (c *Ctx) GapAcovStatsGet() (GapAcovStats, error) {
+	var st C.groot_gap_acov_stats
+	if rc := C.groot_hip_gap_acov_stats(c.h, &st); rc != 0 {
+		return GapAcovStats{}, c.err("groot_hip_gap_acov_stats")
+	}
+	return GapAcovStats{uint64(st.placements), uint64(st.records), uint64(st.host_records), uint64(st.dropped), uint64(st.launches)}, nil
+}
+
 func (c *Ctx) err(what string) error {
 	return fmt.Errorf("%s: %s", what, C.GoString(C.groot_hip_last_error(c.h)))
 }

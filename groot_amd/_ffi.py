@@ -104,6 +104,17 @@ def gap_ec_prototypes(L):
     L.groot_hip_gap_ec_enable.restype = L.groot_hip_gap_ec_stats.restype = C.c_int
 
 
+# ---- gap-placed reads in assigned coverage (groot_hip.h) ----
+GAP_ACOV_STATS = ("placements", "records", "host_records", "dropped", "launches")   # groot_gap_acov_stats, five uint64
+
+
+def gap_acov_prototypes(L):
+    """argtypes of groot_hip_gap_acov_enable / groot_hip_gap_acov_stats (libgroot_hip.so)"""
+    L.groot_hip_gap_acov_enable.argtypes = [C.c_void_p, C.c_int]
+    L.groot_hip_gap_acov_stats.argtypes = [C.c_void_p, u64p]
+    L.groot_hip_gap_acov_enable.restype = L.groot_hip_gap_acov_stats.restype = C.c_int
+
+
 def opt_ptr(arr, ctype):
     """as_ptr, or a NULL pointer for None"""
     return None if arr is None else as_ptr(arr, ctype)

@@ -27,6 +27,7 @@ struct Harvested {                           // the sums over every harvest so f
     groot_rescue_ec_stats rescue_ec{};                       // --abundanceRescued: the rescued reads in the classes (groot_hip_rescue_ec_*)
     groot_gap_ec_stats gap_ec{};                             // --abundanceGapped: the gap-placed reads in the classes (groot_hip_gap_ec_*)
     groot_rescue_acov_stats rescue_acov{};                   // --callsRescued: their records in the pileup (groot_hip_rescue_acov_*)
+    groot_gap_acov_stats gap_acov{};                         // --callsGapped: the gap-placed reads' records in the pileup (groot_hip_gap_acov_*)
 };
 
 class RunCounters {
@@ -70,7 +71,10 @@ public:
             if (int rc = groot_hip_acov_enable(ctx, 1)) return rc;
         if (plan_.abundance)
             if (int rc = groot_hip_ec_enable(ctx, on)) return rc;        // (off: assigned coverage goes with it, and so do the rescued reads in the classes)
-        if (plan_.calls_rescued && on) return groot_hip_rescue_acov_enable(ctx, 1, (uint64_t)a_.call_slots);     // (it switches the rescued reads in the classes on itself)
+        if (plan_.calls_rescued && on) {     // (it switches the rescued reads in the classes on itself)
+            if (int rc = groot_hip_rescue_acov_enable(ctx, 1, (uint64_t)a_.call_slots)) return rc;
+            return plan_.calls_gapped ? groot_hip_gap_acov_enable(ctx, 1) : 0;      // (and this one the gap-placed reads in the classes: --abundanceGapped beside --calls)
+        }
         if (plan_.ab_rescued && on)
             if (int rc = groot_hip_rescue_ec_enable(ctx, 1)) return rc;
         return plan_.ab_gapped && on ? groot_hip_gap_ec_enable(ctx, 1) : 0;   // behind gapped rescue and the rescued reads in the classes (off: it goes with either)
@@ -133,6 +137,13 @@ public:
             std::lock_guard<std::mutex> lk(mu_);
             groot_rescue_acov_stats &t = h_.rescue_acov;
             t.records += st.records; t.host_records += st.host_records; t.dropped += st.dropped; t.launches += st.launches; t.log_rows = st.log_rows;
+        }
+        if (plan_.calls_gapped) {   // (gapped records without room have failed the export above as well)
+            groot_gap_acov_stats st{};
+            if (int rc = groot_hip_gap_acov_stats(ctx, &st)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            groot_gap_acov_stats &t = h_.gap_acov;
+            t.placements += st.placements; t.records += st.records; t.host_records += st.host_records; t.dropped += st.dropped; t.launches += st.launches;
         }
         if (plan_.indels) {         // (a table that dropped events fails here, with the reason: no indels file is written)
             groot_gap_stats st{};

@@ -172,6 +172,9 @@ void write_calls(const Args &a, const AlignPlan &plan, const groot_index_view &v
     if (plan.calls_rescued)
         logf("\tcalls: %llu rescued record(s) counted in the pileup, one per placement of a rescued read, %llu of them on ARGs of more than 4 graphs; the table started with %lld slot(s)",
              (unsigned long long)h.rescue_acov.records, (unsigned long long)h.rescue_acov.host_records, a.call_slots);
+    if (plan.calls_gapped)
+        logf("\tcalls: %llu gapped placement(s) of gap-placed reads piled up as %llu record(s), a deletion as two and an insertion as one, %llu of them on ARGs of more than 4 graphs",
+             (unsigned long long)h.gap_acov.placements, (unsigned long long)h.gap_acov.records, (unsigned long long)h.gap_acov.host_records);
     if (plan.rarefy) rarefy_on_gpu(a, v, device, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), true, m_tp, m_tup.data(), m_tn.data());
 }
 

@@ -10,6 +10,7 @@ struct AlignPlan {
     bool ab_rescued = false; // --abundanceRescued: the rescued reads join the equivalence classes
     bool ab_gapped = false;  // --abundanceGapped: and so do the gap-placed reads
     bool calls_rescued = false; // --callsRescued: and their kept placements the pileup of --calls
+    bool calls_gapped = false;  // --callsGapped: and so do the gap-placed reads' (a DEL as two intervals, an INS as one)
     bool rescued_bam = false;   // --rescuedBam: the kept placements of the rescued reads as BAM records in a file of their own
     bool rescued_bam_gaps = false; // --rescuedBamGaps: and the kept placements of the gap-rescued reads with them
     bool coverage = false;   // report coverage is counted: --report, or --variants / --indels for its exact depth
@@ -126,9 +127,14 @@ int plan_align(const Args &a, AlignPlan *p)
     p->ab_gapped = a.abundance_gapped;
     if (p->ab_gapped && !p->ab_rescued) return refuse("--abundanceGapped adds the gap-placed reads to the classes beside the reads --abundanceRescued adds: it needs it");
     if (p->ab_gapped && !p->indels) return refuse("--abundanceGapped counts the reads gapped rescue places, which --indels switches on: it needs it");
-    if (p->ab_gapped && p->calls)
+    if (p->ab_gapped && p->calls && !(a.calls_gapped && p->calls_rescued))     // (--callsGapped is the rule)
         return refuse("--abundanceGapped cannot be combined with --calls%s: its pileup has no rule for a gapped record, and a deletion covers two intervals",
                       p->calls_rescued ? " --callsRescued" : "");
+    // --callsGapped: checked behind everything above
+    if (a.calls_gapped && !p->calls) return refuse("--callsGapped puts the reads --abundanceGapped adds to the classes into the pileup of --calls: it needs --calls");
+    if (a.calls_gapped && !p->calls_rescued) return refuse("--callsGapped piles the gap-placed reads up beside the rescued reads' records: it needs --callsRescued");
+    if (a.calls_gapped && !p->ab_gapped) return refuse("--callsGapped piles up the reads --abundanceGapped adds to the classes: it needs it");
+    p->calls_gapped = a.calls_gapped;
     p->coverage = p->report || p->variants || p->indels;
     p->counters = p->report || p->abundance || p->assign || p->rescue;
     return 0;

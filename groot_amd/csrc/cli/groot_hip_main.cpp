@@ -37,6 +37,7 @@ void usage()
             "                  [--noBam] [--bootstraps B [--bootSeed 1]] [--paired | --interleaved] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
             "                  [--abundanceRescued --calls c.tsv --callsRescued [--callSlots 16777216]]\n"
             "                  [--abundance a.tsv --abundanceRescued --indels i.tsv --abundanceGapped [--rescueGap 3]]\n"
+            "                  [--abundance a.tsv --abundanceRescued --indels i.tsv --abundanceGapped --calls c.tsv --callsRescued --callsGapped]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
@@ -53,7 +54,8 @@ void usage()
             "                   slots the pileup's table on the GPU starts with, a power of two (a run whose rescued records find no room fails and says so);\n"
             "                   --abundanceGapped: with --abundanceRescued and --indels, a read that gapped rescue places with one deletion or insertion of up\n"
             "                   to --rescueGap bases counts too, with the set of ARGs it was gap-placed on: `reads`, the EM, --bootstraps and --rarefy see it\n"
-            "                   as they see the others.  Not with --calls, with or without --callsRescued: the pileup has no rule for a gapped record;\n"
+            "                   as they see the others.  With --calls only beside --callsRescued --callsGapped: then every gapped placement is piled up on\n"
+            "                   the text bases it covers, a deletion as two records around the hole it leaves, an insertion as one;\n"
             "                   --bootstraps: with --abundance, four more columns `boot_mean boot_sd boot_lo boot_hi` from B replicates of the reads\n"
             "                   resampled with replacement (--bootSeed), each with its own EM, drawn and fitted on the GPU;\n"
             "                   --calls: with --abundance, per line of the abundance file `name em_reads length depth breadth cigar called`: the pileup of\n"
@@ -167,6 +169,7 @@ Args parse(int argc, char **argv)
             if (t.empty() || end != t.c_str() + t.size()) { fprintf(stderr, "%s takes a number: %s\n", f.c_str(), t.c_str()); exit(1); }
         }
         else if (a.cmd == "align" && f == "--callsRescued") a.calls_rescued = true;
+        else if (a.cmd == "align" && f == "--callsGapped") a.calls_gapped = true;
         else if (a.cmd == "align" && f == "--callSlots") {
             const std::string t = v();
             char *end = nullptr;

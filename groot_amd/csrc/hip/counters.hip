@@ -3,7 +3,7 @@
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
 // draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp), rescued reads in the equivalence
 // classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp), rescued records (kernels_rescue_rec.hpp), gapped records (kernels_gap_rec.hpp),
-// gap-placed reads in the equivalence classes (kernels_gap_ec.hpp).  One of the six translation units of
+// gap-placed reads in the equivalence classes (kernels_gap_ec.hpp) and in assigned coverage (kernels_gap_acov.hpp).  One of the six translation units of
 // libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
 #include <cstring>   // before rocprim: its texture iterator calls host memset
 
@@ -37,6 +37,7 @@
 #include "kernels_rescue_rec.hpp"
 #include "kernels_gap_rec.hpp"
 #include "kernels_gap_ec.hpp"
+#include "kernels_gap_acov.hpp"
 #include "kernels_shared.hpp"
 
 using namespace groot;
@@ -397,7 +398,27 @@ static int gec_check(groot_ctx *c, Slot *s, bool refetch)
     return GROOT_OK;
 }
 
-// At collect, behind rec_collect: the bitmaps of the batch's slow gap-rescued reads -- the rows behind the rescued reads' -- into ec_host.
+// gap-placed reads in assigned coverage (kernels_gap_acov.hpp).  At collect, ahead of rec_collect: the two kinds share the slot's log,
+// and a batch that needs more fails before either is folded.  (More rescued entries alone than the log holds: rec_collect says so, in
+// its own words.)
+static int gac_check(groot_ctx *c, Slot *s, bool refetch)
+{
+    Counters &k = c->ct;
+    if (!s->ct.d_gac_nlog.p || !s->ct.d_rac_nlog.p) return GROOT_OK;      // (launched before the feature came on)
+    if (refetch) {
+        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->gac_log, s->ct.d_gac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    const uint32_t n_r = s->ct.h_status.p->rac_log, n_g = s->ct.h_status.p->gac_log;
+    if (n_r <= k.rac_log_cap && (uint64_t)n_r + n_g > k.rac_log_cap)
+        return fail(c, GROOT_E_NOSPACE, "gap-placed reads in assigned coverage: a batch's rescued and gap-rescued reads whose sets lie in more graphs than a row holds have "
+                    "%u kept placements and %u gapped records, and the log has room for %u (GROOT_TEST_RESCUE_ACOV_LOG)", n_r, n_g, k.rac_log_cap);
+    return GROOT_OK;
+}
+
+// At collect, behind rec_collect: the bitmaps of the batch's slow gap-rescued reads -- the rows behind the rescued reads' -- into ec_host,
+// and (gap-placed reads in assigned coverage) their log entries -- those behind the rescued reads' -- into acov_host under the ID list
+// of the entry's bitmap.
 static int gec_collect(groot_ctx *c, Slot *s)
 {
     Counters &k = c->ct;
@@ -407,7 +428,15 @@ static int gec_collect(groot_ctx *c, Slot *s)
     std::vector<uint64_t> bits((size_t)n_g * k.rec_bw);
     HIP_TRY(c, hipMemcpy(bits.data(), s->ct.d_rec_bits.p + (size_t)n_r * k.rec_bw, bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     const uint32_t n_paths = (uint32_t)k.h_len.size();
+    const bool logged = k.gac_on && s->ct.d_gac_nlog.p && s->ct.d_rac_nlog.p;
+    std::vector<uint4> log;
+    if (logged) {                          // (gac_check has brought the counts up to date and found them to fit)
+        const uint32_t n_rlog = s->ct.h_status.p->rac_log;
+        log.resize(s->ct.h_status.p->gac_log);
+        if (!log.empty()) HIP_TRY(c, hipMemcpy(log.data(), s->ct.d_rac_log.p + n_rlog, log.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+    }
     std::vector<uint32_t> ids;
+    std::vector<std::vector<uint32_t>> row_ids(logged ? n_g : 0);
     for (uint32_t i = 0; i < n_g; i++) {
         ids.clear();
         for (uint32_t w = 0; w < k.rec_bw; w++)
@@ -416,8 +445,16 @@ static int gec_collect(groot_ctx *c, Slot *s)
                 if (id < n_paths) ids.push_back(id);
             }
         if (!ids.empty()) k.ec_host[ids]++;
+        if (logged) row_ids[i] = ids;
     }
     k.gec_slow += n_g;
+    for (const uint4 &e : log) {           // (bitmap | kGapAcovSecond, path, Pos, last)
+        const uint32_t row = e.x & ~kGapAcovSecond;
+        if (row >= n_g || row_ids[row].empty()) return fail(c, GROOT_E_DEVICE, "gap-placed reads in assigned coverage: a logged record names bitmap %u of %u", row, n_g);
+        k.acov_host[row_ids[row]][{e.y, e.z, e.w}]++;
+        k.gac_host_records++;
+        if (!(e.x & kGapAcovSecond)) k.gac_host_placements++;
+    }
     return GROOT_OK;
 }
 
@@ -700,6 +737,35 @@ int counters_launch(groot_ctx *c, Slot *s)
                 hipLaunchKernelGGL(gap_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
                 hipLaunchKernelGGL(rescue_ec_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p);
                 k.gec_launches += 2;
+            } else if (k.rac_on && k.gac_on) {      // gap-placed reads in assigned coverage (kernels_gap_acov.hpp): both kinds' rows, one merge, both kinds' records
+                RescueAcovArgs aa{};
+                GapAcovArgs ga{};
+                HIP_TRY(c, s->ct.d_rac_log.reserve(std::max<uint32_t>(k.rac_log_cap, 1u)));
+                HIP_TRY(c, s->ct.d_rac_nlog.reserve(1));
+                HIP_TRY(c, s->ct.d_gac_nlog.reserve(1));
+                HIP_TRY(c, s->ct.d_gec_slow.reserve(1));
+                HIP_TRY(c, hipMemsetAsync(s->ct.d_rac_nlog.p, 0, sizeof(uint32_t), c->tstream));
+                HIP_TRY(c, hipMemsetAsync(s->ct.d_gac_nlog.p, 0, sizeof(uint32_t), c->tstream));
+                HIP_TRY(c, hipMemsetAsync(s->ct.d_gec_slow.p, 0, sizeof(uint32_t), c->tstream));
+                aa.e = ea; aa.tab_ser = k.acov_tab_ser.p; aa.cand_ser = k.rac_cand_ser.p; aa.fill = k.acov_fill.p; aa.stats = k.rac_stats.p;
+                aa.log = s->ct.d_rac_log.p; aa.n_log = s->ct.d_rac_nlog.p; aa.log_cap = k.rac_log_cap;
+                ga.e.g = gra.g; ga.e.s = sa; ga.e.e = k.gec_e.p; ga.e.bits = ea.bits; ga.e.n_rslow = ea.n_slow; ga.e.stats = k.gec_stats.p;
+                ga.e.rows = ea.rows; ga.e.bw = ea.bw; ga.e.n_gslow = s->ct.d_gec_slow.p;
+                ga.tab_ser = k.acov_tab_ser.p; ga.gcand_ser = k.gac_cand_ser.p; ga.fill = k.acov_fill.p; ga.stats = k.gac_stats.p;
+                ga.log = aa.log; ga.n_rlog = aa.n_log; ga.n_glog = s->ct.d_gac_nlog.p; ga.log_cap = k.rac_log_cap;
+                hipLaunchKernelGGL(rescue_acov_slow_kernel, gc, dim3(kBlock), 0, c->tstream, aa);
+                hipLaunchKernelGGL(gap_acov_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
+                hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
+                hipLaunchKernelGGL(gap_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ga.e);
+                hipLaunchKernelGGL(rescue_acov_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, k.acov_tab_ser.p);
+                hipLaunchKernelGGL(rescue_acov_serial_kernel, gc, dim3(kBlock), 0, c->tstream, aa);
+                hipLaunchKernelGGL(gap_acov_serial_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
+                hipLaunchKernelGGL(rescue_acov_clear_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, tab);
+                hipLaunchKernelGGL(rescue_acov_kernel, gc, dim3(kBlock), 0, c->tstream, aa, k.acov.table());
+                hipLaunchKernelGGL(gap_acov_kernel, gc, dim3(kBlock), 0, c->tstream, ga, k.acov.table());
+                k.rac_launches += 3;
+                k.gec_launches += 2;
+                k.gac_launches += 4;
             } else if (!k.rac_on) {
                 hipLaunchKernelGGL(rescue_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
                 hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
@@ -747,6 +813,7 @@ int counters_fetch(groot_ctx *c, Slot *s)
     if (c->ct.rec_on) HIP_TRY(c, hipMemcpyAsync(&h->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     if (c->ct.gec_on && s->ct.d_gec_slow.p) HIP_TRY(c, hipMemcpyAsync(&h->gec_slow, s->ct.d_gec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     if (c->ct.rac_on) HIP_TRY(c, hipMemcpyAsync(&h->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    if (c->ct.gac_on && s->ct.d_gac_nlog.p) HIP_TRY(c, hipMemcpyAsync(&h->gac_log, s->ct.d_gac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     return GROOT_OK;
 }
 
@@ -767,6 +834,8 @@ int counters_collect(groot_ctx *c, Slot *s, bool redone)
     if (int rc = ec_collect(c, s, redone)) return rc;
     if (c->ct.rec_on && c->ct.gec_on)
         if (int rc = gec_check(c, s, redone)) return rc;
+    if (c->ct.rec_on && c->ct.gac_on)
+        if (int rc = gac_check(c, s, redone)) return rc;
     if (c->ct.rec_on)
         if (int rc = rec_collect(c, s, redone)) return rc;
     if (c->ct.rec_on && c->ct.gec_on)
@@ -849,6 +918,9 @@ static void gec_release(Counters &k)
 {
     k.gec_e.release(); k.gec_stats.release();
     k.gec_on = false; k.gec_slow = 0;
+    // (and with it the gap-placed reads in assigned coverage, which are keyed by these classes)
+    k.gac_cand_ser.release(); k.gac_stats.release();
+    k.gac_on = false; k.gac_host_records = k.gac_host_placements = 0;
 }
 
 // rescued reads in the equivalence classes go off (with mismatch rescue, or with the classes): nothing of it stays on the device
@@ -1243,6 +1315,13 @@ int groot_hip_acov_export(groot_ctx *c, uint64_t *ec_off, uint32_t *ec_ids, uint
             return fail(c, GROOT_E_NOSPACE, "assigned coverage: %llu rescued records found no room in a table of %u slots, which grows between batches only: start it "
                         "larger (min_slots of groot_hip_rescue_acov_enable, align --callSlots)", (unsigned long long)st[kRescueAcovDropped], c->ct.acov.cap);
     }
+    if (c->ct.gac_on) {
+        uint64_t st[kGapAcovStats] = {};
+        HIP_TRY(c, hipMemcpy(st, c->ct.gac_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+        if (st[kGapAcovDropped])
+            return fail(c, GROOT_E_NOSPACE, "assigned coverage: %llu gapped records found no room in a table of %u slots, which grows between batches only: start it "
+                        "larger (min_slots of groot_hip_rescue_acov_enable, align --callSlots)", (unsigned long long)st[kGapAcovDropped], c->ct.acov.cap);
+    }
     uint64_t ni = 0;
     for (const auto &kv : m) ni += kv.first.size();
     *n_ec = m.size();
@@ -1294,6 +1373,10 @@ int groot_hip_acov_reset(groot_ctx *c)
     if (c->ct.rac_on) {                    // (the rescued records are counted with the table they are in)
         HIP_TRY(c, hipMemset(c->ct.rac_stats.p, 0, kRescueAcovStats * sizeof(unsigned long long)));
         c->ct.rac_host_records = 0;
+    }
+    if (c->ct.gac_on) {                    // (and the gapped ones)
+        HIP_TRY(c, hipMemset(c->ct.gac_stats.p, 0, kGapAcovStats * sizeof(unsigned long long)));
+        c->ct.gac_host_records = c->ct.gac_host_placements = 0;
     }
     return GROOT_OK;
 }
@@ -1742,7 +1825,8 @@ int groot_hip_rescue_acov_enable(groot_ctx *c, int on, uint64_t min_slots)
     if (min_slots & (min_slots - 1)) return fail(c, GROOT_E_INVALID, "rescued reads in assigned coverage: min_slots = %llu is not a power of two", (unsigned long long)min_slots);
     if (min_slots > (1ull << 31)) return fail(c, GROOT_E_INVALID, "rescued reads in assigned coverage: min_slots = %llu, at most 2^31 are supported", (unsigned long long)min_slots);
     if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in assigned coverage with paired-end units are not supported: mates are rescued one by one");
-    if (k.gec_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in assigned coverage with gap-placed reads in the equivalence classes are not supported: the pileup has no "
+    if (k.gec_on && !k.gac_on)             // (beside each other only through groot_hip_gap_acov_enable, which gives the pileup its rule)
+        return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in assigned coverage with gap-placed reads in the equivalence classes are not supported: the pileup has no "
                               "rule for a gapped record (groot_hip_gap_ec_enable)");
     if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: mismatch rescue is off (groot_hip_rescue_enable)");
     if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: equivalence classes are off (groot_hip_ec_enable)");
@@ -1888,20 +1972,10 @@ int groot_hip_gap_rec_stats(groot_ctx *c, groot_gap_rec_stats *out)
 }
 
 // ---- gap-placed reads in the equivalence classes (kernels_gap_ec.hpp; the definition is in groot_hip.h) ----------------------
-int groot_hip_gap_ec_enable(groot_ctx *c, int on)
+// gapped rescue and the rescued classes on: checked by the caller
+static int gec_alloc(groot_ctx *c)
 {
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
     Counters &k = c->ct;
-    if (!on) {
-        gec_release(k);
-        return GROOT_OK;
-    }
-    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: gapped rescue is off (groot_hip_gap_enable)");
-    if (!k.rec_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: the rescued reads in the equivalence classes are off (groot_hip_rescue_ec_enable)");
-    if (k.rac_on) return fail(c, GROOT_E_UNSUPPORTED, "gap-placed reads in the equivalence classes with rescued reads in assigned coverage are not supported: the pileup has no "
-                              "rule for a gapped record, and a DEL covers two intervals (groot_hip_rescue_acov_enable)");
     if (k.gec_on) return GROOT_OK;
     hipError_t e = k.gec_e.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
     if (e == hipSuccess) e = k.gec_stats.alloc(kGapEcStats);
@@ -1915,6 +1989,24 @@ int groot_hip_gap_ec_enable(groot_ctx *c, int on)
     return GROOT_OK;
 }
 
+int groot_hip_gap_ec_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!on) {
+        gec_release(k);
+        return GROOT_OK;
+    }
+    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: gapped rescue is off (groot_hip_gap_enable)");
+    if (!k.rec_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: the rescued reads in the equivalence classes are off (groot_hip_rescue_ec_enable)");
+    if (k.rac_on && !k.gac_on)             // (beside each other only through groot_hip_gap_acov_enable, which gives the pileup its rule)
+        return fail(c, GROOT_E_UNSUPPORTED, "gap-placed reads in the equivalence classes with rescued reads in assigned coverage are not supported: the pileup has no "
+                              "rule for a gapped record, and a DEL covers two intervals (groot_hip_rescue_acov_enable)");
+    return gec_alloc(c);
+}
+
 int groot_hip_gap_ec_stats(groot_ctx *c, groot_gap_ec_stats *out)
 {
     if (!c || !out) return GROOT_E_INVALID;
@@ -1926,6 +2018,49 @@ int groot_hip_gap_ec_stats(groot_ctx *c, groot_gap_ec_stats *out)
     out->slow_reads = c->ct.gec_on ? c->ct.gec_slow : 0;
     out->reads = st[0] + out->slow_reads;
     out->launches = c->ct.gec_launches;
+    return GROOT_OK;
+}
+
+// ---- gap-placed reads in assigned coverage (kernels_gap_acov.hpp; the definition is in groot_hip.h) --------------------------
+int groot_hip_gap_acov_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "gap-placed reads in assigned coverage can only be switched while nothing is in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Counters &k = c->ct;
+    if (!on) {
+        if (k.gac_on) gec_release(k);      // (the gap-placed classes came on with it and cannot stay beside the rescued records without it)
+        return GROOT_OK;
+    }
+    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gap-placed reads in assigned coverage: gapped rescue is off (groot_hip_gap_enable)");
+    if (!k.rac_on) return fail(c, GROOT_E_STATE, "gap-placed reads in assigned coverage: the rescued reads in assigned coverage are off (groot_hip_rescue_acov_enable)");
+    if (k.gac_on) return GROOT_OK;
+    if (int rc = gec_alloc(c)) return rc;  // (rac_on: mismatch rescue, the classes, the rescued classes and assigned coverage are on, pairing is off)
+    hipError_t e = k.gac_cand_ser.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
+    if (e == hipSuccess) e = k.gac_stats.alloc(kGapAcovStats);
+    if (e == hipSuccess) e = hipMemset(k.gac_stats.p, 0, kGapAcovStats * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        gec_release(k);
+        return fail(c, GROOT_E_DEVICE, "gap-placed reads in assigned coverage: %s", hipGetErrorString(e));
+    }
+    k.gac_host_records = k.gac_host_placements = 0;
+    k.gac_on = true;
+    return GROOT_OK;
+}
+
+int groot_hip_gap_acov_stats(groot_ctx *c, groot_gap_acov_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kGapAcovStats] = {};
+    if (c->ct.gac_on) {
+        if (int rc = drain(c)) return rc;
+        HIP_TRY(c, hipMemcpy(st, c->ct.gac_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    }
+    out->host_records = c->ct.gac_on ? c->ct.gac_host_records : 0;
+    out->placements = st[0] + (c->ct.gac_on ? c->ct.gac_host_placements : 0);
+    out->records = st[kGapAcovRecords] + out->host_records;
+    out->dropped = st[kGapAcovDropped];
+    out->launches = c->ct.gac_launches;
     return GROOT_OK;
 }
 

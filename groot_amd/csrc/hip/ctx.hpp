@@ -137,6 +137,7 @@ struct CounterStatus {
     uint64_t rr_total;                     // rescued records: the batch's records (SlotCounters::d_rr_total[0])
     uint64_t gr_total;                     // gapped records: the batch's records (SlotCounters::d_gr_total[0])
     uint32_t gec_slow;                     // gap-placed reads in the ECs: the batch's slow gap-rescued reads (SlotCounters::d_gec_slow[0])
+    uint32_t gac_log;                      // gap-placed reads in assigned coverage: the log entries of those reads (SlotCounters::d_gac_nlog[0])
 };
 
 struct SlotCounters {
@@ -165,6 +166,8 @@ struct SlotCounters {
     bool gr = false;                       // the feature was on when the batch was submitted
     DevBuf<uint32_t> d_gec_slow;           // gap-placed reads in the ECs: [0] the batch's slow gap-rescued reads, with or without a bitmap (gap_ec_slow_kernel);
                                            // their bitmaps are the rows of d_rec_bits behind the rescued reads'
+    DevBuf<uint32_t> d_gac_nlog;           // gap-placed reads in assigned coverage: [0] the log entries of the batch's slow gap-rescued reads, logged or not
+                                           // (gap_acov_slow_kernel); the entries are those of d_rac_log behind the rescued reads'
 };
 
 struct Counters {
@@ -281,6 +284,15 @@ struct Counters {
     DevBuf<unsigned long long> gec_stats;  // [kGapEcStats]
     uint64_t gec_slow = 0;                 // slow gap-rescued reads folded at collect since enable / groot_hip_ec_reset
     uint64_t gec_launches = 0;             // gap_ec_slow_kernel and gap_ec_insert_kernel since open (rescue_gap_ec_kernel counts as gapped rescue's)
+    // gap-placed reads in assigned coverage (groot_hip_gap_acov_*, kernels_gap_acov.hpp): needs gapped rescue and the rescued reads in
+    // assigned coverage on, and switches the gap-placed reads in the ECs on itself.  Every kept gapped placement is two records (DEL) or
+    // one (INS) of the assigned-coverage table; those of the reads with a bitmap come back in the rescued reads' log and are folded on
+    // the host at collect.  gac_on implies gec_on and rac_on; it goes off with either (gec_release).
+    bool gac_on = false;
+    DevBuf<uint32_t> gac_cand_ser;         // GapAcovArgs::gcand_ser (tail stream: one batch at a time, as the gap candidates are)
+    DevBuf<unsigned long long> gac_stats;  // [kGapAcovStats]
+    uint64_t gac_host_records = 0, gac_host_placements = 0;   // folded on the host since enable / groot_hip_acov_reset
+    uint64_t gac_launches = 0;             // the four kernels of kernels_gap_acov.hpp since open
 };
 
 // One batch in flight.  Inputs and outputs are per slot (copy-in of batch b+1 and copy-out of batch b-1 overlap the

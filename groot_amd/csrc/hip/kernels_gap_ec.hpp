@@ -72,7 +72,13 @@ struct GapEcArgs {
     uint32_t rows, bw;
 };
 
-__global__ __launch_bounds__(kBlock) void gap_ec_slow_kernel(GapEcArgs a)
+// what gap_ec_slow_body tells of every kept tuple beyond the bitmap: nothing here, the tuple's intervals to the slot's log in
+// kernels_gap_acov.hpp (GapAcovLog); `at` is the read's bitmap among the gap-rescued reads' (behind the rescued reads' in the pool)
+struct GapNoLog {
+    __device__ __forceinline__ void kept(const GapEcArgs &, uint32_t, uint32_t, const uint4 &, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) const {}
+};
+
+template <class Log> __device__ __forceinline__ void gap_ec_slow_body(const GapEcArgs &a, const Log &log)
 {
     if (!shared_live(a.s)) return;
     const RescueArgs &ra = a.g.r;
@@ -91,12 +97,15 @@ __global__ __launch_bounds__(kBlock) void gap_ec_slow_kernel(GapEcArgs a)
         const uint64_t o = ra.seq_off[r];
         const uint32_t len = (uint32_t)(ra.seq_off[r + 1] - o);
         const uint64_t w0 = ((o - off0) >> 5) + r;
-        gap_sweep(ra, G, w0, len, 1u, best, [&](uint32_t p, const uint4 &, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const unsigned long long *) {
+        gap_sweep(ra, G, w0, len, 1u, best, [&](uint32_t p, const uint4 &pi, uint32_t, uint32_t x, uint32_t ins, uint32_t g, uint32_t ks, uint32_t, const unsigned long long *) {
             if (p >= a.s.n_paths) return;
             b[p >> 6] |= 1ull << (p & 63u);
+            log.kept(a, at, p, pi, x, ins, g, ks, len);
         });
     }
 }
+
+__global__ __launch_bounds__(kBlock) void gap_ec_slow_kernel(GapEcArgs a) { gap_ec_slow_body(a, GapNoLog{}); }
 
 __global__ __launch_bounds__(kBlock) void gap_ec_insert_kernel(GapEcArgs a)
 {

@@ -82,6 +82,7 @@ def lib():
         L.groot_hip_close.restype = None
         _ffi.rarefy_hip_prototypes(L)
         _ffi.gap_ec_prototypes(L)
+        _ffi.gap_acov_prototypes(L)
         _lib = L
     return _lib
 
@@ -683,6 +684,19 @@ class Aligner:
         v = (C.c_uint64 * len(_ffi.GAP_EC_STATS))()
         self._check(lib().groot_hip_gap_ec_stats(self._h, v))
         return dict(zip(_ffi.GAP_EC_STATS, (int(x) for x in v)))
+
+    # ---- gap-placed reads in assigned coverage (groot_hip_gap_acov_*) --------------------------------------
+    def gap_acov_enable(self, on=True):
+        """from now on every kept gapped placement of a gap-rescued read is piled up in assigned coverage: two records for a DEL, one for
+        an INS (include/groot_hip.h, "gap-placed reads in assigned coverage").  Needs gap_enable and rescue_acov_enable first, and switches
+        the gap-placed reads in the classes on itself; off switches both off.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_gap_acov_enable(self._h, C.c_int(1 if on else 0)))
+
+    def gap_acov_stats(self):
+        """groot_hip_gap_acov_stats: {"placements", "records", "host_records", "dropped", "launches"}; zeros while off, but for launches"""
+        v = (C.c_uint64 * len(_ffi.GAP_ACOV_STATS))()
+        self._check(lib().groot_hip_gap_acov_stats(self._h, v))
+        return dict(zip(_ffi.GAP_ACOV_STATS, (int(x) for x in v)))
 
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):

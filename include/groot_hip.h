@@ -774,7 +774,8 @@ typedef struct groot_gap_ec_stats {
 } groot_gap_ec_stats;
 /* on != 0: on.  Needs gapped rescue and the rescued reads in the equivalence classes on (GROOT_E_STATE otherwise), and nothing in flight
  * (GROOT_E_STATE).  GROOT_E_UNSUPPORTED beside the rescued reads in assigned coverage, from whichever enable comes second: the pileup has
- * no rule for a gapped record, and a DEL covers two intervals.  groot_hip_gap_enable(.., 0, ..), groot_hip_rescue_ec_enable(.., 0),
+ * no rule for a gapped record, and a DEL covers two intervals (groot_hip_gap_acov_enable, below, is that rule and switches both on together).
+ * groot_hip_gap_enable(.., 0, ..), groot_hip_rescue_ec_enable(.., 0),
  * mismatch rescue off and the equivalence classes off switch it off too; another G or another M leaves the classes alone;
  * groot_hip_ec_reset zeroes these stats with the classes.  The rescued and the gap-rescued reads of a batch in more than 4 graphs share
  * the slot's `rows` bitmaps: more of them together fail the batch at collect with GROOT_E_NOSPACE (the message names
@@ -782,6 +783,53 @@ typedef struct groot_gap_ec_stats {
 int groot_hip_gap_ec_enable(groot_ctx *ctx, int on);
 /* Waits for everything in flight; zeros while off, but for launches. */
 int groot_hip_gap_ec_stats(groot_ctx *ctx, groot_gap_ec_stats *out);
+
+/* ---- gap-placed reads in assigned coverage -------------------------------------------------------------------------------
+ * The gap-placed reads in the classes vote in the EM, and the rescued reads in assigned coverage stop at the reads mismatch rescue
+ * places: a read placed with a deletion or an insertion is piled up nowhere, and the calls file has a hole of a read length on each side
+ * of an indel the sample carries against every indexed allele.  With this on, every kept gapped placement is piled up on the text bases
+ * gdepth grows on for it.  The definition:
+ *
+ *   S(r), R(r), G(r), S++(r), gap candidate, kept gapped placement (p, strand, x, type, g, k*), e*, X = first Position of p + x, len:
+ *   exactly as in "gapped rescue" and "gap-placed reads in the equivalence classes".  ECs, canonical order, alpha, w(e,p): exactly as for
+ *   --abundance --abundanceRescued --abundanceGapped (the run's ECs are the distinct non-empty S++(r)).
+ *   A kept gapped placement of a gap-rescued read r is
+ *      type DEL:  TWO gapped records of r on p, covering [X, X + k* - 1] and [X + k* + g, X + len + g - 1]
+ *      type INS:  ONE gapped record of r on p, covering [X, X + len - g - 1]
+ *   both ends included: the text bases on which gdepth grows for that placement.  The g deleted text bases of a DEL are covered by neither
+ *   record (the pileup shows the deletion as the hole it is); the g inserted read bases of an INS cover nothing.  Every kept gapped placement
+ *   counts: every path, both strands, every x, both types, every g, each (p, strand, x, type, g) once.
+ *   The assigned-coverage table of a run with the feature on is the multiset of exact records, rescued records AND gapped records
+ *   grouped by (e = EC of S++(r), p, Pos, last): n(e, p, Pos, last).  Everything computed from the table and the ECs (d_e[x], D_p[x], depth,
+ *   breadth, cigar, called, --callSupport's and --rarefy's columns) is computed by the existing host and device functions, unchanged.
+ *   A read that is rescued ungapped keeps its rescued records even where a gapped placement would cost less.  A pass that collect redoes counts
+ *   once; a batch under kCovSkipFlags counts nothing.  The table depends on the reads and the index alone: not on batch size, pipeline depth,
+ *   align stage, results_on_device, --ctxPerGpu or --gpus.
+ *
+ * Off by default: then no allocation, launch or sync, and every kernel launched is the one launched without this section. */
+typedef struct groot_gap_acov_stats {
+    uint64_t placements;    /* kept gapped placements piled up since enable / groot_hip_acov_reset, the host's among them */
+    uint64_t records;       /* gapped records added (DEL two, INS one): placements + the DEL placements among them */
+    uint64_t host_records;  /* those folded on the host from the log (the reads whose set lies in more than 4 graphs, 1 under GROOT_TEST_SHARED_SLOW) */
+    uint64_t dropped;       /* gapped records that found no room: groot_hip_acov_export fails while this or groot_rescue_acov_stats.dropped is not 0 */
+    uint64_t launches;      /* the four launches it adds to a batch's pass (gap_acov_slow_kernel, gap_ec_insert_kernel, gap_acov_serial_kernel,
+                               gap_acov_kernel), since open, whether it is on now or not */
+} groot_gap_acov_stats;
+/* on != 0: on.  Needs gapped rescue and the rescued reads in assigned coverage on (GROOT_E_STATE otherwise, with the reason), and nothing
+ * in flight (GROOT_E_STATE).  It switches the gap-placed reads in the equivalence classes on itself: the one way they and the rescued reads
+ * in assigned coverage run together (groot_hip_gap_ec_enable and groot_hip_rescue_acov_enable keep refusing each other).  on == 0: off, and
+ * the gap-placed reads in the classes with it; the rescued reads in assigned coverage stay.  It also goes off whenever gapped rescue, the
+ * gap-placed classes, the rescued reads in assigned coverage, mismatch rescue, the classes, the rescued classes or assigned coverage goes
+ * off.  Another G, another M and the rescue / gap resets leave the table alone; groot_hip_acov_reset (and groot_hip_ec_reset, which calls
+ * it) zero these stats and the records.  groot_hip_acov_export / _stats count the gapped records in `records` and `tuples`
+ * (slow_records stays the exact records'); groot_hip_gap_ec_stats counts as it does without this.  The log entries of a batch's rescued and
+ * gap-rescued reads in more than 4 graphs share the slot's log (groot_rescue_acov_stats.log_rows): more of them together fail the batch at
+ * collect with GROOT_E_NOSPACE (the message names GROOT_TEST_RESCUE_ACOV_LOG), before either kind is folded.  A gapped record that finds no
+ * room in the table makes groot_hip_acov_export fail with GROOT_E_NOSPACE (min_slots / --callSlots) until groot_hip_acov_reset.
+ * Device memory: 4 bytes per read of a batch. */
+int groot_hip_gap_acov_enable(groot_ctx *ctx, int on);
+/* Waits for everything in flight; zeros while off, but for launches. */
+int groot_hip_gap_acov_stats(groot_ctx *ctx, groot_gap_acov_stats *out);
 
 /* ---- bootstrap replicates of the abundance EM -----------------------------------------------------------------------
  * groot_host_em_bootstrap (groot_host.h, "bootstrap intervals": the resampling by splitmix64 draws, groot_host_em per replicate) on
