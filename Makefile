@@ -11,9 +11,9 @@ $(B)/libgroot_host.so: $(HOST_SRC) groot_amd/csrc/host/host_common.hpp $(wildcar
 	@mkdir -p $(B)
 	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -Iinclude -shared -o $@ $(HOST_SRC) -lpthread -lz
 
-# libgroot_hip.so: six translation units (groot_amd/csrc/hip/launch.hpp) compiled side by side (make -j6)
+# libgroot_hip.so: seven translation units (groot_amd/csrc/hip/launch.hpp) compiled side by side (make -j7)
 HIP_DIR := groot_amd/csrc/hip
-HIP_TU := groot_hip open counters seed_full seed_fast align
+HIP_TU := groot_hip open counters rescue seed_full seed_fast align
 HIP_OBJ := $(addprefix $(B)/obj/,$(addsuffix .o,$(HIP_TU)))
 HIP_FLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-pass-failed -Iinclude -I$(HIP_DIR)
 $(B)/obj/%.o: $(HIP_DIR)/%.hip $(wildcard $(HIP_DIR)/*.hpp) $(wildcard groot_amd/csrc/common/*.hpp) $(wildcard include/*.h)

@@ -1,4 +1,4 @@
-// align.hip -- K3, the graph walk (graphMinion loop + AlignRead hierarchy + DFS).  One of the six translation units of
+// align.hip -- K3, the graph walk (graphMinion loop + AlignRead hierarchy + DFS).  One of the seven translation units of
 // libgroot_hip.so (launch.hpp).
 #include <hip/hip_runtime.h>
 

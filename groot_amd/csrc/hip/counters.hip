@@ -1,14 +1,9 @@
 // counters.hip -- the counters that run behind every batch's order stage, and their C ABI (include/groot_hip.h): report coverage
 // (kernels_cov.hpp), shared reads (kernels_shared.hpp), equivalence classes (kernels_ec.hpp), assigned coverage (kernels_acov.hpp),
 // paired-end units, the bootstrap replicates of the abundance EM (kernels_boot.hpp) and of the calls (kernels_csup.hpp), the rarefaction
-// draws (kernels_rare.hpp), mismatch rescue (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp), rescued reads in the equivalence
-// classes (kernels_rescue_ec.hpp) and in assigned coverage (kernels_rescue_acov.hpp), rescued records (kernels_rescue_rec.hpp), gapped records (kernels_gap_rec.hpp),
-// gap-placed reads in the equivalence classes (kernels_gap_ec.hpp) and in assigned coverage (kernels_gap_acov.hpp).  One of the six translation units of
-// libgroot_hip.so (launch.hpp); the pipeline calls the four hooks of counters.hpp, everything else here is internal.
-#include <cstring>   // before rocprim: its texture iterator calls host memset
-
+// draws (kernels_rare.hpp).  One of the seven translation units of libgroot_hip.so (launch.hpp); the pipeline calls the hooks of
+// counters.hpp, the rescue family (rescue.hip) is reached through those of rescue.hpp, everything else here is internal.
 #include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <array>
@@ -28,25 +23,11 @@
 #include "kernels_cov.hpp"
 #include "kernels_csup.hpp"
 #include "kernels_ec.hpp"
-#include "index_tables.hpp"
 #include "kernels_rare.hpp"
-#include "kernels_gap.hpp"
-#include "kernels_rescue.hpp"
-#include "kernels_rescue_ec.hpp"
-#include "kernels_rescue_acov.hpp"
-#include "kernels_rescue_rec.hpp"
-#include "kernels_gap_rec.hpp"
-#include "kernels_gap_ec.hpp"
-#include "kernels_gap_acov.hpp"
 #include "kernels_shared.hpp"
+#include "rescue.hpp"
 
 using namespace groot;
-
-// workgroups of a grid-stride launch over n items
-static uint32_t grid_for(uint32_t n)
-{
-    return std::max<uint32_t>(1u, std::min<uint32_t>((n + kBlock - 1) / kBlock, 2048u));
-}
 
 // ---- the position tables' one device copy (Counters::d_*) ----
 static bool pos_wanted(const Counters &k) { return k.cov_on || k.sh_on || k.ec_on || k.acov_on; }
@@ -192,7 +173,7 @@ static int acov_launch(groot_ctx *c, Slot *s, const SharedArgs &sa)
 }
 
 // `factor` times the slots, every key and count moved over; everything launched on the tail stream has ended when this returns
-static int acov_grow(groot_ctx *c, uint32_t factor)
+int groot::acov_grow(groot_ctx *c, uint32_t factor)
 {
     Counters &k = c->ct;
     HIP_TRY(c, hipStreamSynchronize(c->tstream));
@@ -322,253 +303,6 @@ static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
     return GROOT_OK;
 }
 
-// ---- rescued reads in the equivalence classes (kernels_rescue_ec.hpp) ----
-// At collect: the bitmaps of the batch's slow rescued reads, each as an ascending ID list into ec_host, the way ec_collect folds the
-// exact slow reads.  refetch: the copy enqueue made is stale (the batch was redone).
-static int rec_collect(groot_ctx *c, Slot *s, bool refetch)
-{
-    Counters &k = c->ct;
-    if (!s->ct.d_rec_slow.p) return GROOT_OK;      // (launched before the feature came on)
-    if (refetch) HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const uint32_t n_slow = s->ct.h_status.p->rec_slow;
-    if (!n_slow) return GROOT_OK;
-    if (n_slow > k.rec_rows)
-        return fail(c, GROOT_E_NOSPACE, "rescued reads in the equivalence classes: a batch has %u rescued reads whose sets lie in more graphs than a row holds, and room for "
-                    "the bitmaps of %u (GROOT_TEST_RESCUE_EC_ROWS)", n_slow, k.rec_rows);
-    std::vector<uint64_t> bits((size_t)n_slow * k.rec_bw);
-    HIP_TRY(c, hipMemcpy(bits.data(), s->ct.d_rec_bits.p, bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    const uint32_t n_paths = (uint32_t)k.h_len.size();
-    // rescued reads in assigned coverage: the log of these reads' kept placements, checked before anything is folded
-    const bool logged = k.rac_on && s->ct.d_rac_nlog.p;
-    std::vector<uint4> log;
-    if (logged) {
-        if (refetch) HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        const uint32_t n_log = s->ct.h_status.p->rac_log;
-        if (n_log > k.rac_log_cap)
-            return fail(c, GROOT_E_NOSPACE, "rescued reads in assigned coverage: a batch's rescued reads whose sets lie in more graphs than a row holds have %u kept "
-                        "placements, and the log has room for %u (GROOT_TEST_RESCUE_ACOV_LOG)", n_log, k.rac_log_cap);
-        log.resize(n_log);
-        if (n_log) HIP_TRY(c, hipMemcpy(log.data(), s->ct.d_rac_log.p, log.size() * sizeof(uint4), hipMemcpyDeviceToHost));
-    }
-    std::vector<uint32_t> ids;
-    std::vector<std::vector<uint32_t>> row_ids(logged ? n_slow : 0);
-    for (uint32_t i = 0; i < n_slow; i++) {
-        ids.clear();
-        for (uint32_t w = 0; w < k.rec_bw; w++)
-            for (uint64_t m = bits[(size_t)i * k.rec_bw + w]; m; m &= m - 1) {
-                const uint32_t id = w * 64 + (uint32_t)__builtin_ctzll(m);
-                if (id < n_paths) ids.push_back(id);
-            }
-        if (!ids.empty()) k.ec_host[ids]++;
-        if (logged) row_ids[i] = ids;
-    }
-    k.rec_slow += n_slow;
-    for (const uint4 &e : log) {           // (bitmap row, path, X, last): into the host map under the row's ID list, as ec_collect folds the exact slow reads' records
-        if (e.x >= n_slow || row_ids[e.x].empty()) return fail(c, GROOT_E_DEVICE, "rescued reads in assigned coverage: a logged placement names bitmap %u of %u", e.x, n_slow);
-        k.acov_host[row_ids[e.x]][{e.y, e.z, e.w}]++;
-        k.rac_host_records++;
-    }
-    return GROOT_OK;
-}
-
-// ---- gap-placed reads in the equivalence classes (kernels_gap_ec.hpp) ----
-// The batch's slow rescued and slow gap-rescued reads, as the slot's status block has them (refetch: afresh, the batch was redone)
-static int gec_counts(groot_ctx *c, Slot *s, bool refetch, uint32_t &n_r, uint32_t &n_g)
-{
-    if (refetch) {
-        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->gec_slow, s->ct.d_gec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    n_r = s->ct.h_status.p->rec_slow;
-    n_g = s->ct.h_status.p->gec_slow;
-    return GROOT_OK;
-}
-
-// At collect, ahead of rec_collect: the two kinds share the slot's bitmaps, and a batch that needs more fails before either is folded.
-// (More rescued ones alone than there are bitmaps: rec_collect says so, in its own words.)
-static int gec_check(groot_ctx *c, Slot *s, bool refetch)
-{
-    Counters &k = c->ct;
-    if (!s->ct.d_gec_slow.p || !s->ct.d_rec_slow.p) return GROOT_OK;      // (launched before the feature came on)
-    uint32_t n_r, n_g;
-    if (int rc = gec_counts(c, s, refetch, n_r, n_g)) return rc;
-    if (n_r <= k.rec_rows && (uint64_t)n_r + n_g > k.rec_rows)
-        return fail(c, GROOT_E_NOSPACE, "gap-placed reads in the equivalence classes: a batch has %u rescued and %u gap-rescued reads whose sets lie in more graphs than a row "
-                    "holds, and room for the bitmaps of %u (GROOT_TEST_RESCUE_EC_ROWS)", n_r, n_g, k.rec_rows);
-    return GROOT_OK;
-}
-
-// gap-placed reads in assigned coverage (kernels_gap_acov.hpp).  At collect, ahead of rec_collect: the two kinds share the slot's log,
-// and a batch that needs more fails before either is folded.  (More rescued entries alone than the log holds: rec_collect says so, in
-// its own words.)
-static int gac_check(groot_ctx *c, Slot *s, bool refetch)
-{
-    Counters &k = c->ct;
-    if (!s->ct.d_gac_nlog.p || !s->ct.d_rac_nlog.p) return GROOT_OK;      // (launched before the feature came on)
-    if (refetch) {
-        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->gac_log, s->ct.d_gac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    const uint32_t n_r = s->ct.h_status.p->rac_log, n_g = s->ct.h_status.p->gac_log;
-    if (n_r <= k.rac_log_cap && (uint64_t)n_r + n_g > k.rac_log_cap)
-        return fail(c, GROOT_E_NOSPACE, "gap-placed reads in assigned coverage: a batch's rescued and gap-rescued reads whose sets lie in more graphs than a row holds have "
-                    "%u kept placements and %u gapped records, and the log has room for %u (GROOT_TEST_RESCUE_ACOV_LOG)", n_r, n_g, k.rac_log_cap);
-    return GROOT_OK;
-}
-
-// At collect, behind rec_collect: the bitmaps of the batch's slow gap-rescued reads -- the rows behind the rescued reads' -- into ec_host,
-// and (gap-placed reads in assigned coverage) their log entries -- those behind the rescued reads' -- into acov_host under the ID list
-// of the entry's bitmap.
-static int gec_collect(groot_ctx *c, Slot *s)
-{
-    Counters &k = c->ct;
-    if (!s->ct.d_gec_slow.p || !s->ct.d_rec_slow.p) return GROOT_OK;
-    const uint32_t n_r = s->ct.h_status.p->rec_slow, n_g = s->ct.h_status.p->gec_slow;      // (gec_check has brought them up to date)
-    if (!n_g) return GROOT_OK;
-    std::vector<uint64_t> bits((size_t)n_g * k.rec_bw);
-    HIP_TRY(c, hipMemcpy(bits.data(), s->ct.d_rec_bits.p + (size_t)n_r * k.rec_bw, bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    const uint32_t n_paths = (uint32_t)k.h_len.size();
-    const bool logged = k.gac_on && s->ct.d_gac_nlog.p && s->ct.d_rac_nlog.p;
-    std::vector<uint4> log;
-    if (logged) {                          // (gac_check has brought the counts up to date and found them to fit)
-        const uint32_t n_rlog = s->ct.h_status.p->rac_log;
-        log.resize(s->ct.h_status.p->gac_log);
-        if (!log.empty()) HIP_TRY(c, hipMemcpy(log.data(), s->ct.d_rac_log.p + n_rlog, log.size() * sizeof(uint4), hipMemcpyDeviceToHost));
-    }
-    std::vector<uint32_t> ids;
-    std::vector<std::vector<uint32_t>> row_ids(logged ? n_g : 0);
-    for (uint32_t i = 0; i < n_g; i++) {
-        ids.clear();
-        for (uint32_t w = 0; w < k.rec_bw; w++)
-            for (uint64_t m = bits[(size_t)i * k.rec_bw + w]; m; m &= m - 1) {
-                const uint32_t id = w * 64 + (uint32_t)__builtin_ctzll(m);
-                if (id < n_paths) ids.push_back(id);
-            }
-        if (!ids.empty()) k.ec_host[ids]++;
-        if (logged) row_ids[i] = ids;
-    }
-    k.gec_slow += n_g;
-    for (const uint4 &e : log) {           // (bitmap | kGapAcovSecond, path, Pos, last)
-        const uint32_t row = e.x & ~kGapAcovSecond;
-        if (row >= n_g || row_ids[row].empty()) return fail(c, GROOT_E_DEVICE, "gap-placed reads in assigned coverage: a logged record names bitmap %u of %u", row, n_g);
-        k.acov_host[row_ids[row]][{e.y, e.z, e.w}]++;
-        k.gac_host_records++;
-        if (!(e.x & kGapAcovSecond)) k.gac_host_placements++;
-    }
-    return GROOT_OK;
-}
-
-// ---- rescued records (kernels_rescue_rec.hpp) ----
-struct KeptToU64 {
-    __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
-};
-
-// Behind the count kernel on the tail stream: every read's segment by a scan over the reads (its last output is the batch's total, which
-// stays with the slot), then the records themselves.
-static int rr_launch(groot_ctx *c, Slot *s, const RescueArgs &ra)
-{
-    Counters &k = c->ct;
-    HIP_TRY(c, s->ct.d_rr_rec.reserve((size_t)k.rr_slots * kRescueRecWords));
-    HIP_TRY(c, s->ct.d_rr_total.reserve(1));
-    HIP_TRY(c, s->ct.h_status.reserve(1));
-    const size_t n = (size_t)s->n_reads + 1;
-    auto in = rocprim::make_transform_iterator(k.rr_kept.p, KeptToU64());
-    size_t tmp_bytes = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_bytes, in, k.rr_off.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->tstream));
-    if (tmp_bytes > c->scan_tmp.n) {
-        HIP_TRY(c, hipStreamSynchronize(c->tstream));
-        HIP_TRY(c, c->scan_tmp.alloc(tmp_bytes + tmp_bytes / 4));
-    }
-    HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tmp_bytes, in, k.rr_off.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->tstream));
-    HIP_TRY(c, hipMemcpyAsync(s->ct.d_rr_total.p, k.rr_off.p + s->n_reads, sizeof(uint64_t), hipMemcpyDeviceToDevice, c->tstream));
-    RescueRecArgs a{};
-    a.r = ra; a.off = k.rr_off.p; a.rec = s->ct.d_rr_rec.p; a.cap = k.rr_slots;
-    hipLaunchKernelGGL(rescue_rec_emit_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, a);
-    HIP_TRY(c, hipGetLastError());
-    k.rr_launches += 2;
-    return GROOT_OK;
-}
-
-// At collect: as many records as the batch has, into the slot's pinned memory.  A batch with more than the slot has room for fails alone
-// (its other results stay readable).  refetch: the total enqueue copied is that of the skipped pass.
-static int rr_collect(groot_ctx *c, Slot *s, bool refetch)
-{
-    Counters &k = c->ct;
-    s->ct.rr_n = 0;
-    if (!s->ct.rr || !s->n_reads || !s->ct.d_rr_total.p || !k.rr_on) return GROOT_OK;
-    if (refetch) HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->rr_total, s->ct.d_rr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    const uint64_t n = s->ct.h_status.p->rr_total;
-    if (!n) return GROOT_OK;
-    if (n > k.rr_slots) {
-        k.rr_failed++;
-        if (s->status == GROOT_OK) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "rescued records: a batch has %llu records, and a pipeline slot has room for %llu (slots_per_batch of groot_hip_rescue_rec_enable)",
-                     (unsigned long long)n, (unsigned long long)k.rr_slots);
-            s->status = GROOT_E_NOSPACE;
-            s->status_msg = buf;
-        }
-        return GROOT_OK;
-    }
-    HIP_TRY(c, s->ct.h_rr_rec.reserve(n + n / 4));
-    HIP_TRY(c, hipMemcpy(s->ct.h_rr_rec.p, s->ct.d_rr_rec.p, n * sizeof(groot_rescue_record), hipMemcpyDeviceToHost));
-    s->ct.rr_n = n;
-    k.rr_records += n;
-    const groot_rescue_record *h = s->ct.h_rr_rec.p;
-    for (uint64_t i = 0; i < n; i++) k.rr_reads += i == 0 || h[i].read != h[i - 1].read;
-    return GROOT_OK;
-}
-
-// ---- gapped records (kernels_gap_rec.hpp) ----
-// Behind rescue_gap_rec_kernel on the tail stream: as rr_launch, over the reads' kept gapped placements.
-static int gr_launch(groot_ctx *c, Slot *s, const GapRecArgs &ga)
-{
-    Counters &k = c->ct;
-    const size_t n = (size_t)s->n_reads + 1;
-    auto in = rocprim::make_transform_iterator(k.gr_kept.p, KeptToU64());
-    size_t tmp_bytes = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp_bytes, in, k.gr_off.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->tstream));
-    if (tmp_bytes > c->scan_tmp.n) {
-        HIP_TRY(c, hipStreamSynchronize(c->tstream));
-        HIP_TRY(c, c->scan_tmp.alloc(tmp_bytes + tmp_bytes / 4));
-    }
-    HIP_TRY(c, rocprim::exclusive_scan(c->scan_tmp.p, tmp_bytes, in, k.gr_off.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->tstream));
-    HIP_TRY(c, hipMemcpyAsync(s->ct.d_gr_total.p, k.gr_off.p + s->n_reads, sizeof(uint64_t), hipMemcpyDeviceToDevice, c->tstream));
-    hipLaunchKernelGGL(gap_rec_emit_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
-    HIP_TRY(c, hipGetLastError());
-    k.gr_launches += 2;
-    return GROOT_OK;
-}
-
-// At collect: as rr_collect.  The batch fails alone; its rescued records (rr_collect ran first) and its other results stay readable.
-static int gr_collect(groot_ctx *c, Slot *s, bool refetch)
-{
-    Counters &k = c->ct;
-    s->ct.gr_n = 0;
-    if (!s->ct.gr || !s->n_reads || !s->ct.d_gr_total.p || !k.gr_on) return GROOT_OK;
-    if (refetch) HIP_TRY(c, hipMemcpy(&s->ct.h_status.p->gr_total, s->ct.d_gr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    const uint64_t n = s->ct.h_status.p->gr_total;
-    if (!n) return GROOT_OK;
-    if (n > k.gr_slots) {
-        k.gr_failed++;
-        if (s->status == GROOT_OK) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "gapped records: a batch has %llu records, and a pipeline slot has room for %llu (slots_per_batch of groot_hip_gap_rec_enable)",
-                     (unsigned long long)n, (unsigned long long)k.gr_slots);
-            s->status = GROOT_E_NOSPACE;
-            s->status_msg = buf;
-        }
-        return GROOT_OK;
-    }
-    HIP_TRY(c, s->ct.h_gr_rec.reserve(n + n / 4));
-    HIP_TRY(c, hipMemcpy(s->ct.h_gr_rec.p, s->ct.d_gr_rec.p, n * sizeof(groot_gap_record), hipMemcpyDeviceToHost));
-    s->ct.gr_n = n;
-    k.gr_records += n;
-    const groot_gap_record *h = s->ct.h_gr_rec.p;
-    for (uint64_t i = 0; i < n; i++) k.gr_reads += i == 0 || h[i].read != h[i - 1].read;
-    return GROOT_OK;
-}
-
 // ---- the pipeline's hooks (counters.hpp) ---------------------------------------------------------------------------
 namespace groot {
 
@@ -658,138 +392,9 @@ int counters_launch(groot_ctx *c, Slot *s)
         else hipLaunchKernelGGL(shared_expand_kernel<false>, gt, dim3(kBlock), 0, c->tstream, sa, tab);
         HIP_TRY(c, hipGetLastError());
     }
-    if (k.res_on) {   // (the slot's reads, the order stage's scan -- both the tail stream's until the next batch's order stage -- and the ctx's own buffers)
-        RescueArgs ra{};
-        ra.seq = s->seq(); ra.seq_off = s->off(); ra.ctr = s->d_ctr.p; ra.trav_off = c->trav_off.p;
-        ra.rbuf = k.res_rbuf.p; ra.rcap = k.res_rcap; ra.cand = k.res_cand.p; ra.n_cand = k.res_ncand.p;
-        ra.text = k.res_text.p; ra.tag = k.res_tag.p; ra.path = k.res_path.p; ra.tab = k.res_tab.p; ra.occ = k.res_occ.p; ra.slot_base = k.res_base.p;
-        ra.starts = k.res_starts.p; ra.ends = k.res_ends.p; ra.alt = k.res_alt.p; ra.stats = k.res_stats.p;
-        ra.tab_mask = (uint32_t)k.res_tab.n - 1u; ra.n_reads = s->n_reads; ra.max_mismatch = k.res_m;
-        HIP_TRY(c, hipMemsetAsync(k.res_ncand.p, 0, sizeof(uint32_t), c->tstream));
-        hipLaunchKernelGGL(rescue_pack_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
-        if (k.rec_on) {      // (the rows and the per-batch table are free: shared_expand_kernel, above on this stream, has cleared them)
-            ra.path_bit = k.rec_path_bit.p; ra.set_graph = sa.set_graph; ra.set_mask = sa.set_mask; ra.dstar = k.rec_dstar.p;
-            ra.pw = sa.pw; ra.max_segs = sa.max_segs;
-        }
-        if (k.rr_on) {       // rescued records (kernels_rescue_rec.hpp): the count kernel also leaves every read's kept placements, zero for a read that is no candidate
-            ra.n_kept = k.rr_kept.p; ra.rec_d = k.rr_d.p;
-            HIP_TRY(c, hipMemsetAsync(k.rr_kept.p, 0, ((size_t)s->n_reads + 1) * sizeof(uint32_t), c->tstream));
-        }
-        const dim3 gr(grid_for(s->n_reads));
-        GapRecArgs gra{};
-        if (!k.gap_on && k.rr_on) {
-            if (k.rec_on) hipLaunchKernelGGL((rescue_count_rec_kernel<false, true>), gr, dim3(kBlock), 0, c->tstream, ra);
-            else hipLaunchKernelGGL((rescue_count_rec_kernel<false, false>), gr, dim3(kBlock), 0, c->tstream, ra);
-        } else if (!k.gap_on && k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
-        else if (!k.gap_on) hipLaunchKernelGGL(rescue_count_kernel<false>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
-        else {
-            GapArgs ga{};
-            ra.gcand = k.gap_cand.p; ra.n_gcand = k.gap_ncand.p; ra.gstats = k.gap_stats.p;
-            ga.r = ra; ga.gcand = k.gap_cand.p; ga.n_gcand = k.gap_ncand.p;
-            ga.starts = k.gap_starts.p; ga.ends = k.gap_ends.p; ga.ev_key = k.gap_key.p; ga.ev_cnt = k.gap_cnt.p; ga.stats = k.gap_stats.p;
-            ga.ev_mask = k.gap_slots - 1; ga.max_gap = k.gap_g;
-            HIP_TRY(c, hipMemsetAsync(k.gap_ncand.p, 0, sizeof(uint32_t), c->tstream));
-            if (k.rr_on && k.rec_on) hipLaunchKernelGGL((rescue_count_rec_kernel<true, true>), gr, dim3(kBlock), 0, c->tstream, ra);
-            else if (k.rr_on) hipLaunchKernelGGL((rescue_count_rec_kernel<true, false>), gr, dim3(kBlock), 0, c->tstream, ra);
-            else if (k.rec_on) hipLaunchKernelGGL(rescue_count_ec_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
-            else hipLaunchKernelGGL(rescue_count_kernel<true>, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ra);
-            gra.g = ga;
-            if (k.gr_on) {   // gapped records (kernels_gap_rec.hpp): the gap kernel also leaves every read's kept placements and every gap candidate's e*
-                HIP_TRY(c, s->ct.d_gr_rec.reserve((size_t)k.gr_slots * kGapRecWords));
-                HIP_TRY(c, s->ct.d_gr_total.reserve(1));
-                HIP_TRY(c, s->ct.h_status.reserve(1));
-                gra.n_gkept = k.gr_kept.p; gra.gap_e = k.gr_e.p; gra.off = k.gr_off.p; gra.rec = s->ct.d_gr_rec.p; gra.cap = k.gr_slots;
-                HIP_TRY(c, hipMemsetAsync(k.gr_kept.p, 0, ((size_t)s->n_reads + 1) * sizeof(uint32_t), c->tstream));
-            }
-            if (k.gec_on) {  // gap-placed reads in the classes (kernels_gap_ec.hpp): the gap kernel also writes every gap-rescued read's set row
-                GapEcCountArgs gca{gra, k.gec_e.p};
-                if (k.gr_on) hipLaunchKernelGGL(rescue_gap_ec_kernel<true>, gr, dim3(kBlock), 0, c->tstream, gca);
-                else hipLaunchKernelGGL(rescue_gap_ec_kernel<false>, gr, dim3(kBlock), 0, c->tstream, gca);
-            } else if (k.gr_on) hipLaunchKernelGGL(rescue_gap_rec_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, gra);
-            else hipLaunchKernelGGL(rescue_gap_kernel, dim3(grid_for(s->n_reads)), dim3(kBlock), 0, c->tstream, ga);
-            k.gap_launches++;
-        }
-        HIP_TRY(c, hipGetLastError());
-        k.res_launches += 2;
-        if (k.rr_on)
-            if (int rc = rr_launch(c, s, ra)) return rc;
-        if (k.gap_on && k.gr_on)
-            if (int rc = gr_launch(c, s, gra)) return rc;
-        if (k.rec_on) {      // (ec_reserve above has made room for this merge too: its bound is over both)
-            RescueEcArgs ea{};
-            ea.r = ra; ea.s = sa;
-            HIP_TRY(c, s->ct.d_rec_bits.reserve((size_t)k.rec_rows * k.rec_bw));
-            HIP_TRY(c, s->ct.d_rec_slow.reserve(1));
-            HIP_TRY(c, hipMemsetAsync(s->ct.d_rec_slow.p, 0, sizeof(uint32_t), c->tstream));
-            ea.bits = s->ct.d_rec_bits.p; ea.n_slow = s->ct.d_rec_slow.p; ea.stats = k.rec_stats.p;
-            ea.rows = k.rec_rows; ea.bw = k.rec_bw;
-            const dim3 gc(grid_for(s->n_reads));
-            if (!k.rac_on && k.gec_on && k.gap_on) {      // the gap-rescued reads' rows between the rescued reads' and the one merge of both
-                GapEcArgs ga{};
-                ga.g = gra.g; ga.s = sa; ga.e = k.gec_e.p; ga.bits = ea.bits; ga.n_rslow = ea.n_slow; ga.stats = k.gec_stats.p;
-                ga.rows = ea.rows; ga.bw = ea.bw;
-                HIP_TRY(c, s->ct.d_gec_slow.reserve(1));
-                HIP_TRY(c, hipMemsetAsync(s->ct.d_gec_slow.p, 0, sizeof(uint32_t), c->tstream));
-                ga.n_gslow = s->ct.d_gec_slow.p;
-                hipLaunchKernelGGL(rescue_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
-                hipLaunchKernelGGL(gap_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
-                hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
-                hipLaunchKernelGGL(gap_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
-                hipLaunchKernelGGL(rescue_ec_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p);
-                k.gec_launches += 2;
-            } else if (k.rac_on && k.gac_on) {      // gap-placed reads in assigned coverage (kernels_gap_acov.hpp): both kinds' rows, one merge, both kinds' records
-                RescueAcovArgs aa{};
-                GapAcovArgs ga{};
-                HIP_TRY(c, s->ct.d_rac_log.reserve(std::max<uint32_t>(k.rac_log_cap, 1u)));
-                HIP_TRY(c, s->ct.d_rac_nlog.reserve(1));
-                HIP_TRY(c, s->ct.d_gac_nlog.reserve(1));
-                HIP_TRY(c, s->ct.d_gec_slow.reserve(1));
-                HIP_TRY(c, hipMemsetAsync(s->ct.d_rac_nlog.p, 0, sizeof(uint32_t), c->tstream));
-                HIP_TRY(c, hipMemsetAsync(s->ct.d_gac_nlog.p, 0, sizeof(uint32_t), c->tstream));
-                HIP_TRY(c, hipMemsetAsync(s->ct.d_gec_slow.p, 0, sizeof(uint32_t), c->tstream));
-                aa.e = ea; aa.tab_ser = k.acov_tab_ser.p; aa.cand_ser = k.rac_cand_ser.p; aa.fill = k.acov_fill.p; aa.stats = k.rac_stats.p;
-                aa.log = s->ct.d_rac_log.p; aa.n_log = s->ct.d_rac_nlog.p; aa.log_cap = k.rac_log_cap;
-                ga.e.g = gra.g; ga.e.s = sa; ga.e.e = k.gec_e.p; ga.e.bits = ea.bits; ga.e.n_rslow = ea.n_slow; ga.e.stats = k.gec_stats.p;
-                ga.e.rows = ea.rows; ga.e.bw = ea.bw; ga.e.n_gslow = s->ct.d_gec_slow.p;
-                ga.tab_ser = k.acov_tab_ser.p; ga.gcand_ser = k.gac_cand_ser.p; ga.fill = k.acov_fill.p; ga.stats = k.gac_stats.p;
-                ga.log = aa.log; ga.n_rlog = aa.n_log; ga.n_glog = s->ct.d_gac_nlog.p; ga.log_cap = k.rac_log_cap;
-                hipLaunchKernelGGL(rescue_acov_slow_kernel, gc, dim3(kBlock), 0, c->tstream, aa);
-                hipLaunchKernelGGL(gap_acov_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
-                hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
-                hipLaunchKernelGGL(gap_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ga.e);
-                hipLaunchKernelGGL(rescue_acov_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, k.acov_tab_ser.p);
-                hipLaunchKernelGGL(rescue_acov_serial_kernel, gc, dim3(kBlock), 0, c->tstream, aa);
-                hipLaunchKernelGGL(gap_acov_serial_kernel, gc, dim3(kBlock), 0, c->tstream, ga);
-                hipLaunchKernelGGL(rescue_acov_clear_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, tab);
-                hipLaunchKernelGGL(rescue_acov_kernel, gc, dim3(kBlock), 0, c->tstream, aa, k.acov.table());
-                hipLaunchKernelGGL(gap_acov_kernel, gc, dim3(kBlock), 0, c->tstream, ga, k.acov.table());
-                k.rac_launches += 3;
-                k.gec_launches += 2;
-                k.gac_launches += 4;
-            } else if (!k.rac_on) {
-                hipLaunchKernelGGL(rescue_ec_slow_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
-                hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
-                hipLaunchKernelGGL(rescue_ec_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p);
-            } else {     // rescued reads in assigned coverage (kernels_rescue_acov.hpp): claim and add in one pass, here and never at collect
-                RescueAcovArgs aa{};
-                HIP_TRY(c, s->ct.d_rac_log.reserve(std::max<uint32_t>(k.rac_log_cap, 1u)));
-                HIP_TRY(c, s->ct.d_rac_nlog.reserve(1));
-                HIP_TRY(c, hipMemsetAsync(s->ct.d_rac_nlog.p, 0, sizeof(uint32_t), c->tstream));
-                aa.e = ea; aa.tab_ser = k.acov_tab_ser.p; aa.cand_ser = k.rac_cand_ser.p; aa.fill = k.acov_fill.p; aa.stats = k.rac_stats.p;
-                aa.log = s->ct.d_rac_log.p; aa.n_log = s->ct.d_rac_nlog.p; aa.log_cap = k.rac_log_cap;
-                hipLaunchKernelGGL(rescue_acov_slow_kernel, gc, dim3(kBlock), 0, c->tstream, aa);
-                hipLaunchKernelGGL(rescue_ec_insert_kernel, gc, dim3(kBlock), 0, c->tstream, ea);
-                hipLaunchKernelGGL(rescue_acov_merge_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, k.acov_tab_ser.p);
-                hipLaunchKernelGGL(rescue_acov_serial_kernel, gc, dim3(kBlock), 0, c->tstream, aa);
-                hipLaunchKernelGGL(rescue_acov_clear_kernel, dim3(grid_for(tab)), dim3(kBlock), 0, c->tstream, sa, tab);
-                hipLaunchKernelGGL(rescue_acov_kernel, gc, dim3(kBlock), 0, c->tstream, aa, k.acov.table());
-                k.rac_launches += 3;
-            }
-            HIP_TRY(c, hipGetLastError());
-            k.rec_launches += 3;
-        }
-    }
-    return GROOT_OK;
+    // the rescue family (rescue.hip); the rows and the per-batch table it writes the rescued reads' sets into are free: shared_expand_kernel,
+    // above on this stream, has cleared them
+    return rescue_launch(c, s, sa, tab);
 }
 
 int counters_fetch(groot_ctx *c, Slot *s)
@@ -798,23 +403,16 @@ int counters_fetch(groot_ctx *c, Slot *s)
         HIP_TRY(c, hipMemcpyAsync(s->ct.h_best.p, s->ct.d_best.p, (size_t)s->n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
         HIP_TRY(c, hipMemcpyAsync(s->ct.h_mapq.p, s->ct.d_mapq.p, (size_t)s->n_reads, hipMemcpyDeviceToHost, c->d2h_stream));
     }
-    if (s->ct.rr && s->n_reads && c->ct.rr_on && s->ct.d_rr_total.p)
-        HIP_TRY(c, hipMemcpyAsync(&s->ct.h_status.p->rr_total, s->ct.d_rr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    if (s->ct.gr && s->n_reads && c->ct.gr_on && s->ct.d_gr_total.p)
-        HIP_TRY(c, hipMemcpyAsync(&s->ct.h_status.p->gr_total, s->ct.d_gr_total.p, sizeof(uint64_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    if (!c->ct.ec_on) return GROOT_OK;
-    CounterStatus *h = s->ct.h_status.p;
-    HIP_TRY(c, hipMemcpyAsync(&h->ec_slow, s->ct.d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    HIP_TRY(c, hipMemcpyAsync(&h->ec_fill, c->ct.ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    if (c->ct.acov_on) {
-        HIP_TRY(c, hipMemcpyAsync(&h->acov_state, s->ct.d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-        HIP_TRY(c, hipMemcpyAsync(&h->acov_fill, c->ct.acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    if (c->ct.ec_on) {
+        CounterStatus *h = s->ct.h_status.p;
+        HIP_TRY(c, hipMemcpyAsync(&h->ec_slow, s->ct.d_ec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+        HIP_TRY(c, hipMemcpyAsync(&h->ec_fill, c->ct.ec_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+        if (c->ct.acov_on) {
+            HIP_TRY(c, hipMemcpyAsync(&h->acov_state, s->ct.d_acov_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+            HIP_TRY(c, hipMemcpyAsync(&h->acov_fill, c->ct.acov_fill.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+        }
     }
-    if (c->ct.rec_on) HIP_TRY(c, hipMemcpyAsync(&h->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    if (c->ct.gec_on && s->ct.d_gec_slow.p) HIP_TRY(c, hipMemcpyAsync(&h->gec_slow, s->ct.d_gec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    if (c->ct.rac_on) HIP_TRY(c, hipMemcpyAsync(&h->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    if (c->ct.gac_on && s->ct.d_gac_nlog.p) HIP_TRY(c, hipMemcpyAsync(&h->gac_log, s->ct.d_gac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    return GROOT_OK;
+    return rescue_fetch(c, s);
 }
 
 int counters_collect(groot_ctx *c, Slot *s, bool redone)
@@ -828,18 +426,10 @@ int counters_collect(groot_ctx *c, Slot *s, bool redone)
             HIP_TRY(c, hipMemcpy(s->ct.h_mapq.p, s->ct.d_mapq.p, (size_t)s->n_reads, hipMemcpyDeviceToHost));
         }
     }
-    if (int rc = rr_collect(c, s, redone)) return rc;
-    if (int rc = gr_collect(c, s, redone)) return rc;
+    if (int rc = rescue_collect_records(c, s, redone)) return rc;
     if (!c->ct.ec_on || !s->n_reads) return GROOT_OK;
     if (int rc = ec_collect(c, s, redone)) return rc;
-    if (c->ct.rec_on && c->ct.gec_on)
-        if (int rc = gec_check(c, s, redone)) return rc;
-    if (c->ct.rec_on && c->ct.gac_on)
-        if (int rc = gac_check(c, s, redone)) return rc;
-    if (c->ct.rec_on)
-        if (int rc = rec_collect(c, s, redone)) return rc;
-    if (c->ct.rec_on && c->ct.gec_on)
-        if (int rc = gec_collect(c, s)) return rc;
+    if (int rc = rescue_collect_classes(c, s, redone)) return rc;
     return c->ct.acov_on ? acov_collect(c, s, redone) : GROOT_OK;
 }
 
@@ -911,27 +501,6 @@ int groot_hip_coverage_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ct.cov_starts.p, 0, slots * sizeof(unsigned long long)));
     HIP_TRY(c, hipMemset(c->ct.cov_ends.p, 0, slots * sizeof(unsigned long long)));
     return GROOT_OK;
-}
-
-// gap-placed reads in the equivalence classes go off (with gapped rescue, or with the rescued reads in the classes)
-static void gec_release(Counters &k)
-{
-    k.gec_e.release(); k.gec_stats.release();
-    k.gec_on = false; k.gec_slow = 0;
-    // (and with it the gap-placed reads in assigned coverage, which are keyed by these classes)
-    k.gac_cand_ser.release(); k.gac_stats.release();
-    k.gac_on = false; k.gac_host_records = k.gac_host_placements = 0;
-}
-
-// rescued reads in the equivalence classes go off (with mismatch rescue, or with the classes): nothing of it stays on the device
-static void rec_release(Counters &k)
-{
-    gec_release(k);                        // (the gap-placed reads' rows go through the rescued reads' table and merge)
-    k.rec_path_bit.release(); k.rec_dstar.release(); k.rec_stats.release();
-    k.rec_on = false; k.rec_rows = k.rec_bw = 0; k.rec_slow = 0;
-    // (and with it the rescued reads in assigned coverage, which are keyed by these classes)
-    k.rac_cand_ser.release(); k.rac_stats.release();
-    k.rac_on = false; k.rac_log_cap = 0; k.rac_host_records = 0;
 }
 
 // ---- shared reads (kernels_shared.hpp) -------------------------------------------------------------------------------
@@ -1055,7 +624,7 @@ int groot_hip_ec_enable(groot_ctx *c, int on)
     if (!on) {
         if (c->ct.acov_on)
             if (int rc = groot_hip_acov_enable(c, 0)) return rc;     // (its tuples are keyed by this table's serials)
-        rec_release(c->ct);                                          // (the rescued reads' sets have no table to go to)
+        rescue_ec_release(c->ct);                                    // (the rescued reads' sets have no table to go to)
         c->ct.ec.release(); c->ct.ec_fill.release();
         c->ct.ec_host.clear();
         c->ct.ec_on = false;
@@ -1187,14 +756,7 @@ int groot_hip_ec_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ct.ec_fill.p, 0, sizeof(uint32_t)));
     c->ct.ec_fill_known = c->ct.ec_grows = c->ct.ec_slow_reads = 0;
     c->ct.ec_host.clear();
-    if (c->ct.rec_on) {                    // (the rescued reads are counted with the classes they are in)
-        HIP_TRY(c, hipMemset(c->ct.rec_stats.p, 0, kRescueEcStats * sizeof(unsigned long long)));
-        c->ct.rec_slow = 0;
-    }
-    if (c->ct.gec_on) {                    // (and the gap-placed ones)
-        HIP_TRY(c, hipMemset(c->ct.gec_stats.p, 0, kGapEcStats * sizeof(unsigned long long)));
-        c->ct.gec_slow = 0;
-    }
+    if (int rc = rescue_ec_reset(c)) return rc;     // (the rescued and the gap-placed reads are counted with the classes they are in)
     if (c->ct.pairs_on) HIP_TRY(c, hipMemset(c->ct.sh_stats.p + kSharedPairStats, 0, (kSharedStats - kSharedPairStats) * sizeof(unsigned long long)));
     return groot_hip_acov_reset(c);     // (the serials start again: its tuples would name other classes)
 }
@@ -1206,7 +768,7 @@ int groot_hip_acov_enable(groot_ctx *c, int on)
     if (!idle(c)) return fail(c, GROOT_E_STATE, "assigned coverage can only be switched while nothing is in flight");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!on) {
-        if (c->ct.rac_on) rec_release(c->ct);     // (the rescued reads in it go, and the rescued classes that came on with them)
+        if (c->ct.rac_on) rescue_ec_release(c->ct);     // (the rescued reads in it go, and the rescued classes that came on with them)
         c->ct.acov.release();
         for (auto *b : {&c->ct.acov_fill, &c->ct.acov_err, &c->ct.acov_tab_ser}) b->release();
         c->ct.acov_host.clear();
@@ -1308,20 +870,7 @@ int groot_hip_acov_export(groot_ctx *c, uint64_t *ec_off, uint32_t *ec_ids, uint
     std::map<std::vector<uint32_t>, uint64_t> m;
     std::vector<AcovTuple> tp;
     if (int rc = acov_gather(c, m, tp)) return rc;
-    if (c->ct.rac_on) {                    // (behind the drain of acov_gather)
-        uint64_t st[kRescueAcovStats] = {};
-        HIP_TRY(c, hipMemcpy(st, c->ct.rac_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-        if (st[kRescueAcovDropped])
-            return fail(c, GROOT_E_NOSPACE, "assigned coverage: %llu rescued records found no room in a table of %u slots, which grows between batches only: start it "
-                        "larger (min_slots of groot_hip_rescue_acov_enable, align --callSlots)", (unsigned long long)st[kRescueAcovDropped], c->ct.acov.cap);
-    }
-    if (c->ct.gac_on) {
-        uint64_t st[kGapAcovStats] = {};
-        HIP_TRY(c, hipMemcpy(st, c->ct.gac_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-        if (st[kGapAcovDropped])
-            return fail(c, GROOT_E_NOSPACE, "assigned coverage: %llu gapped records found no room in a table of %u slots, which grows between batches only: start it "
-                        "larger (min_slots of groot_hip_rescue_acov_enable, align --callSlots)", (unsigned long long)st[kGapAcovDropped], c->ct.acov.cap);
-    }
+    if (int rc = rescue_acov_dropped(c)) return rc;      // (behind the drain of acov_gather)
     uint64_t ni = 0;
     for (const auto &kv : m) ni += kv.first.size();
     *n_ec = m.size();
@@ -1370,15 +919,7 @@ int groot_hip_acov_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ct.acov_fill.p, 0, sizeof(uint32_t)));
     c->ct.acov_grows = c->ct.acov_slow_records = c->ct.acov_redone = 0;
     c->ct.acov_host.clear();
-    if (c->ct.rac_on) {                    // (the rescued records are counted with the table they are in)
-        HIP_TRY(c, hipMemset(c->ct.rac_stats.p, 0, kRescueAcovStats * sizeof(unsigned long long)));
-        c->ct.rac_host_records = 0;
-    }
-    if (c->ct.gac_on) {                    // (and the gapped ones)
-        HIP_TRY(c, hipMemset(c->ct.gac_stats.p, 0, kGapAcovStats * sizeof(unsigned long long)));
-        c->ct.gac_host_records = c->ct.gac_host_placements = 0;
-    }
-    return GROOT_OK;
+    return rescue_acov_reset(c);
 }
 
 // ---- assignment (kernels_assign.hpp) ---------------------------------------------------------------------------------
@@ -1395,7 +936,7 @@ int groot_hip_assign_enable(groot_ctx *c, const double *alpha, uint32_t n_paths,
     }
     if (k.sh_on || k.ec_on || k.acov_on || k.pairs_on)
         return fail(c, GROOT_E_UNSUPPORTED, "assignment collapses S(r): not with shared reads, equivalence classes, assigned coverage or pairing on");
-    if (k.res_on) return fail(c, GROOT_E_UNSUPPORTED, "assignment rewrites the records mismatch rescue tells the unaligned reads by (groot_hip_rescue_enable)");
+    if (rescue_on(c)) return fail(c, GROOT_E_UNSUPPORTED, "assignment rewrites the records mismatch rescue tells the unaligned reads by (groot_hip_rescue_enable)");
     if (n_paths != k.h_len.size()) return fail(c, GROOT_E_INVALID, "assignment: alpha has %u values, the index %zu paths", n_paths, k.h_len.size());
     if (!(min_posterior >= 0.0 && min_posterior <= 1.0)) return fail(c, GROOT_E_INVALID, "assignment: min_posterior %g is not in [0, 1]", min_posterior);
     for (uint32_t p = 0; p < n_paths; p++)
@@ -1463,604 +1004,6 @@ int groot_hip_pairs_stats(groot_ctx *c, uint64_t *joined, uint64_t *split, uint6
     if (joined) *joined = st[kSharedPairStats];
     if (split) *split = st[kSharedPairStats + 1];
     if (single) *single = st[kSharedPairStats + 2];
-    return GROOT_OK;
-}
-
-// ---- mismatch rescue (kernels_rescue.hpp) --------------------------------------------------------------------------------
-static void gap_release(Counters &k)
-{
-    for (auto *b : {&k.gap_cand, &k.gap_ncand}) b->release();
-    for (auto *b : {&k.gap_starts, &k.gap_ends, &k.gap_key, &k.gap_cnt, &k.gap_stats}) b->release();
-    k.gap_on = false; k.gap_g = 0; k.gap_slots = 0;
-}
-
-static hipError_t gap_zero(Counters &k)
-{
-    if (!k.gap_on) return hipSuccess;
-    const uint64_t slots = std::max<uint64_t>(k.h_cov_base.back(), 1);
-    hipError_t e = hipMemset(k.gap_starts.p, 0, slots * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(k.gap_ends.p, 0, slots * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(k.gap_key.p, 0, k.gap_slots * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(k.gap_cnt.p, 0, k.gap_slots * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(k.gap_stats.p, 0, kGapStats * sizeof(unsigned long long));
-    return e;
-}
-
-// rescued records off: the ctx's work space, every slot's records and the counts since enable (the launches stay)
-static void rr_release(groot_ctx *c)
-{
-    Counters &k = c->ct;
-    k.rr_kept.release(); k.rr_off.release(); k.rr_d.release();
-    for (auto &s : c->slots) {
-        s->ct.d_rr_rec.release(); s->ct.d_rr_total.release(); s->ct.h_rr_rec.release();
-        s->ct.rr = false; s->ct.rr_n = 0;
-    }
-    k.rr_on = false; k.rr_slots = 0;
-    k.rr_records = k.rr_reads = k.rr_failed = 0;
-}
-
-// gapped records off: as rr_release
-static void gr_release(groot_ctx *c)
-{
-    Counters &k = c->ct;
-    k.gr_kept.release(); k.gr_off.release(); k.gr_e.release();
-    for (auto &s : c->slots) {
-        s->ct.d_gr_rec.release(); s->ct.d_gr_total.release(); s->ct.h_gr_rec.release();
-        s->ct.gr = false; s->ct.gr_n = 0;
-    }
-    k.gr_on = false; k.gr_slots = 0;
-    k.gr_records = k.gr_reads = k.gr_failed = 0;
-}
-
-static void rescue_release(Counters &k)
-{
-    gap_release(k);                        // (gapped rescue looks at what rescue leaves: off with it)
-    rec_release(k);                        // (and so do the rescued reads in the equivalence classes)
-    for (auto *b : {&k.res_text, &k.res_tag, &k.res_cand, &k.res_ncand}) b->release();
-    for (auto *b : {&k.res_rbuf, &k.res_starts, &k.res_ends, &k.res_alt, &k.res_stats}) b->release();
-    k.res_path.release(); k.res_tab.release(); k.res_occ.release(); k.res_base.release();
-    k.res_on = false; k.res_m = 0; k.res_rcap = 0;
-}
-
-static hipError_t rescue_zero(Counters &k)
-{
-    const uint64_t slots = std::max<uint64_t>(k.h_cov_base.back(), 1);
-    hipError_t e = hipMemset(k.res_starts.p, 0, slots * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(k.res_ends.p, 0, slots * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(k.res_alt.p, 0, 4 * slots * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(k.res_stats.p, 0, kRescueStats * sizeof(unsigned long long));
-    if (e == hipSuccess) e = gap_zero(k);  // (derived from the same reads)
-    return e;
-}
-
-int groot_hip_rescue_enable(groot_ctx *c, const groot_index_view *idx, uint32_t max_mismatch)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "mismatch rescue can only be switched while nothing is in flight");
-    if (max_mismatch > kRescueMaxMismatch) return fail(c, GROOT_E_INVALID, "mismatch rescue: %u mismatches, at most %u are supported", max_mismatch, kRescueMaxMismatch);
-    HIP_TRY(c, hipSetDevice(c->device));
-    Counters &k = c->ct;
-    if (!max_mismatch) {
-        rr_release(c);                     // (the rescued records are rescue's placements: off with it)
-        gr_release(c);                     // (and the gapped records gapped rescue's, which goes off below)
-        rescue_release(k);
-        return GROOT_OK;
-    }
-    if (k.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "mismatch rescue tells the unaligned reads by their records, which assignment rewrites (groot_hip_assign_enable)");
-    const bool same_index = idx && idx->n_paths == k.h_len.size() && (size_t)idx->n_nodes + 1 == k.h_np_off.size() && std::equal(k.h_len.begin(), k.h_len.end(), idx->path_len);
-    if (idx && !same_index) return fail(c, GROOT_E_INVALID, "mismatch rescue: not the index the ctx was opened with");
-    if (k.res_on) {                        // another M: the tables do not depend on it, the counts do
-        if (max_mismatch != k.res_m) {
-            hipError_t e = rescue_zero(k);
-            if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "mismatch rescue: %s", hipGetErrorString(e));
-            k.res_m = max_mismatch;
-        }
-        return GROOT_OK;
-    }
-    if (!idx) return fail(c, GROOT_E_INVALID, "mismatch rescue: the tables are built from the index the ctx was opened with, and none was given");
-    RescueTables rt;
-    if (!build_rescue_tables(idx, rt))
-        return fail(c, GROOT_E_UNSUPPORTED, "mismatch rescue: path texts of %zu bases are beyond 32-bit bit offsets", rt.n_bases);
-    const uint64_t slots = k.h_cov_base.back(), R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-    k.res_rcap = c->prm.max_batch_bases / 32 + R + 2;
-    hipError_t e = upload(k.res_text, rt.text.data(), rt.text.size());
-    if (e == hipSuccess) e = upload(k.res_tag, rt.tag.data(), rt.tag.size());
-    if (e == hipSuccess) e = upload(k.res_path, rt.path.data(), rt.path.size());
-    if (e == hipSuccess) e = upload(k.res_tab, rt.tab.data(), rt.tab.size());
-    if (e == hipSuccess) e = upload(k.res_occ, rt.occ.data(), rt.occ.size());
-    if (e == hipSuccess) e = upload(k.res_base, k.h_cov_base.data(), k.h_cov_base.size());
-    if (e == hipSuccess) e = k.res_rbuf.alloc(2 * k.res_rcap);
-    if (e == hipSuccess) e = k.res_cand.alloc(R);
-    if (e == hipSuccess) e = k.res_ncand.alloc(1);
-    if (e == hipSuccess) e = k.res_starts.alloc(slots);
-    if (e == hipSuccess) e = k.res_ends.alloc(slots);
-    if (e == hipSuccess) e = k.res_alt.alloc(4 * slots);
-    if (e == hipSuccess) e = k.res_stats.alloc(kRescueStats);
-    if (e == hipSuccess) e = rescue_zero(k);
-    if (e != hipSuccess) {
-        rescue_release(k);
-        return fail(c, GROOT_E_DEVICE, "mismatch rescue: %s", hipGetErrorString(e));
-    }
-    k.res_text_paths = rt.n_text_paths;
-    k.res_m = max_mismatch;
-    k.res_on = true;
-    return GROOT_OK;
-}
-
-// the run's stats; GROOT_E_DEVICE when a batch's candidates did not fit the 2-bit buffer (a device-resident batch above max_batch_bases)
-static int rescue_fetch_stats(groot_ctx *c, uint64_t (&st)[kRescueStats])
-{
-    if (int rc = drain(c)) return rc;
-    HIP_TRY(c, hipMemcpy(st, c->ct.res_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    if (st[6]) return fail(c, GROOT_E_DEVICE, "mismatch rescue: %llu reads of batches with more than max_batch_bases bases were left out", (unsigned long long)st[6]);
-    return GROOT_OK;
-}
-
-int groot_hip_rescue_export(groot_ctx *c, uint64_t *depth, uint64_t *alt)
-{
-    // (h_cov_base.back() = sum of (path_len + 1): above the number of paths exactly when some path has a base, and then there is something to write)
-    const bool any_base = c && c->ct.h_cov_base.back() > c->ct.h_len.size();
-    if (!c || (any_base && (!depth || !alt))) return GROOT_E_INVALID;
-    if (!c->ct.res_on) return fail(c, GROOT_E_STATE, "mismatch rescue is not enabled (groot_hip_rescue_enable)");
-    uint64_t stats[kRescueStats];
-    if (int rc = rescue_fetch_stats(c, stats)) return rc;
-    const uint64_t slots = c->ct.h_cov_base.back();
-    std::vector<uint64_t> st(slots), en(slots), al(4 * slots);
-    if (slots) {
-        HIP_TRY(c, hipMemcpy(st.data(), c->ct.res_starts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(en.data(), c->ct.res_ends.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(al.data(), c->ct.res_alt.p, 4 * slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    uint64_t at = 0;
-    for (size_t p = 0; p < c->ct.h_len.size(); p++) {
-        const uint64_t b = c->ct.h_cov_base[p], len = c->ct.h_len[p];
-        uint64_t d = 0;
-        for (uint64_t i = 0; i < len; i++, at++) {
-            d += st[b + i] - en[b + i];
-            depth[at] = d;
-            for (uint32_t x = 0; x < 4; x++) alt[4 * at + x] = al[4 * (b + i) + x];
-        }
-    }
-    return GROOT_OK;
-}
-
-int groot_hip_rescue_stats(groot_ctx *c, groot_rescue_stats *out)
-{
-    if (!c || !out) return GROOT_E_INVALID;
-    uint64_t st[kRescueStats] = {};
-    if (c->ct.res_on)
-        if (int rc = rescue_fetch_stats(c, st)) return rc;
-    out->candidates = st[0]; out->rescued = st[1]; out->exact = st[2]; out->placements = st[3]; out->too_short = st[4]; out->non_acgt = st[5];
-    out->text_paths = c->ct.res_on ? c->ct.res_text_paths : 0;
-    out->launches = c->ct.res_launches;
-    return GROOT_OK;
-}
-
-int groot_hip_rescue_reset(groot_ctx *c)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->ct.res_on) return GROOT_OK;
-    if (int rc = drain(c)) return rc;
-    HIP_TRY(c, rescue_zero(c->ct));
-    return GROOT_OK;
-}
-
-// ---- gapped rescue (kernels_gap.hpp) ---------------------------------------------------------------------------------------
-int groot_hip_gap_enable(groot_ctx *c, uint32_t max_gap, uint64_t event_slots)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "gapped rescue can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    Counters &k = c->ct;
-    if (!max_gap) {
-        gr_release(c);                     // (the gapped records are gapped rescue's placements: off with it)
-        gec_release(k);                    // (and so are the gap-placed reads in the classes)
-        gap_release(k);
-        return GROOT_OK;
-    }
-    if (!k.res_on) return fail(c, GROOT_E_STATE, "gapped rescue looks at the reads mismatch rescue leaves, and that is off (groot_hip_rescue_enable)");
-    if (max_gap > kGapMax) return fail(c, GROOT_E_INVALID, "gapped rescue: a gap of %u bases, at most %u are supported", max_gap, kGapMax);
-    if (event_slots & (event_slots - 1)) return fail(c, GROOT_E_INVALID, "gapped rescue: event_slots %llu is not a power of two", (unsigned long long)event_slots);
-    if (!event_slots) event_slots = 1ull << 22;
-    if (k.gap_on && event_slots == k.gap_slots) {      // another G: the buffers stay, the counts start over
-        if (max_gap != k.gap_g) {
-            hipError_t e = gap_zero(k);
-            if (e != hipSuccess) return fail(c, GROOT_E_DEVICE, "gapped rescue: %s", hipGetErrorString(e));
-            k.gap_g = max_gap;
-        }
-        return GROOT_OK;
-    }
-    gap_release(k);
-    const uint64_t slots = k.h_cov_base.back();
-    hipError_t e = k.gap_cand.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
-    if (e == hipSuccess) e = k.gap_ncand.alloc(1);
-    if (e == hipSuccess) e = k.gap_starts.alloc(slots);
-    if (e == hipSuccess) e = k.gap_ends.alloc(slots);
-    if (e == hipSuccess) e = k.gap_key.alloc(event_slots);
-    if (e == hipSuccess) e = k.gap_cnt.alloc(event_slots);
-    if (e == hipSuccess) e = k.gap_stats.alloc(kGapStats);
-    if (e == hipSuccess) {
-        k.gap_on = true; k.gap_g = max_gap; k.gap_slots = event_slots;
-        e = gap_zero(k);
-    }
-    if (e != hipSuccess) {
-        gr_release(c);
-        gec_release(k);
-        gap_release(k);
-        return fail(c, GROOT_E_DEVICE, "gapped rescue: %s", hipGetErrorString(e));
-    }
-    return GROOT_OK;
-}
-
-int groot_hip_gap_export(groot_ctx *c, uint64_t *gdepth, groot_gap_event *events, uint64_t cap, uint64_t *n_events)
-{
-    const bool any_base = c && c->ct.h_cov_base.back() > c->ct.h_len.size();
-    if (!c || !n_events || (any_base && !gdepth) || (cap && !events)) return GROOT_E_INVALID;
-    *n_events = 0;
-    Counters &k = c->ct;
-    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gapped rescue is not enabled (groot_hip_gap_enable)");
-    uint64_t rst[kRescueStats], st[kGapStats];
-    if (int rc = rescue_fetch_stats(c, rst)) return rc;
-    HIP_TRY(c, hipMemcpy(st, k.gap_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    *n_events = st[6];
-    if (st[7])
-        return fail(c, GROOT_E_NOSPACE, "gapped rescue: %llu events found no room in a table of event_slots = %llu: give groot_hip_gap_enable a larger one",
-                    (unsigned long long)st[7], (unsigned long long)k.gap_slots);
-    if (cap < st[6]) return fail(c, GROOT_E_INVALID, "gapped rescue: %llu distinct events, room for %llu", (unsigned long long)st[6], (unsigned long long)cap);
-    const uint64_t slots = k.h_cov_base.back();
-    std::vector<uint64_t> s0(slots), s1(slots), key(k.gap_slots), cnt(k.gap_slots);
-    if (slots) {
-        HIP_TRY(c, hipMemcpy(s0.data(), k.gap_starts.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(s1.data(), k.gap_ends.p, slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(c, hipMemcpy(key.data(), k.gap_key.p, k.gap_slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(cnt.data(), k.gap_cnt.p, k.gap_slots * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    uint64_t at = 0;
-    for (size_t p = 0; p < k.h_len.size(); p++) {
-        const uint64_t b = k.h_cov_base[p], len = k.h_len[p];
-        uint64_t d = 0;
-        for (uint64_t i = 0; i < len; i++, at++) {
-            d += s0[b + i] - s1[b + i];
-            gdepth[at] = d;
-        }
-    }
-    uint64_t n = 0;
-    for (uint64_t i = 0; i < k.gap_slots; i++) {
-        if (!key[i]) continue;
-        if (n == st[6]) return fail(c, GROOT_E_DEVICE, "gapped rescue: more keys in the table than the %llu claimed", (unsigned long long)st[6]);
-        const uint64_t slot = key[i] & ((1ull << 40) - 1);
-        const size_t p = (size_t)(std::upper_bound(k.h_cov_base.begin(), k.h_cov_base.end(), slot) - k.h_cov_base.begin()) - 1;
-        groot_gap_event &e = events[n++];
-        e.path = (uint32_t)p; e.pos = (uint32_t)(slot - k.h_cov_base[p]);
-        e.type = (uint8_t)((key[i] >> 40) & 1u); e.len = (uint8_t)(((key[i] >> 41) & 7u) + 1u); e.seq = (uint16_t)(key[i] >> 44);
-        e.reserved = 0; e.reads = cnt[i];
-    }
-    if (n != st[6]) return fail(c, GROOT_E_DEVICE, "gapped rescue: %llu keys in the table, %llu claimed", (unsigned long long)n, (unsigned long long)st[6]);
-    std::sort(events, events + n, [](const groot_gap_event &a, const groot_gap_event &b) {      // the table's order is not deterministic, this one is
-        return std::make_tuple(a.path, a.pos, a.type, a.len, a.seq) < std::make_tuple(b.path, b.pos, b.type, b.len, b.seq);
-    });
-    return GROOT_OK;
-}
-
-int groot_hip_gap_stats(groot_ctx *c, groot_gap_stats *out)
-{
-    if (!c || !out) return GROOT_E_INVALID;
-    uint64_t st[kGapStats] = {};
-    if (c->ct.gap_on) {
-        uint64_t rst[kRescueStats];
-        if (int rc = rescue_fetch_stats(c, rst)) return rc;
-        HIP_TRY(c, hipMemcpy(st, c->ct.gap_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    }
-    out->candidates = st[0]; out->rescued = st[1]; out->placements = st[2]; out->del_placements = st[3]; out->ins_placements = st[4];
-    out->too_short = st[5]; out->events = st[6]; out->dropped = st[7];
-    out->event_slots = c->ct.gap_on ? c->ct.gap_slots : 0;
-    out->launches = c->ct.gap_launches;
-    return GROOT_OK;
-}
-
-int groot_hip_gap_reset(groot_ctx *c)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!c->ct.gap_on) return GROOT_OK;
-    if (int rc = drain(c)) return rc;
-    HIP_TRY(c, gap_zero(c->ct));
-    return GROOT_OK;
-}
-
-// ---- rescued reads in the equivalence classes (kernels_rescue_ec.hpp; the definition is in groot_hip.h) ---------------------
-// rescue, the classes, no pairing: checked by the caller
-static int rec_alloc(groot_ctx *c)
-{
-    Counters &k = c->ct;
-    if (k.rec_on) return GROOT_OK;
-    const uint32_t n_paths = (uint32_t)k.h_len.size(), R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-    std::vector<uint2> pb(n_paths);
-    for (uint32_t g = 0; g + 1 < k.h_gpo.size(); g++)
-        for (uint32_t p = k.h_gpo[g]; p < std::min(k.h_gpo[g + 1], n_paths); p++) pb[p] = make_uint2(g, p - k.h_gpo[g]);
-    k.rec_bw = std::max<uint32_t>((n_paths + 63u) / 64u, 1u);
-    // a batch has at most max_batch_reads slow rescued reads; below that, what the byte budget holds (GROOT_RESCUE_EC_BYTES per slot)
-    k.rec_rows = c->kn.rescue_ec_rows ? c->kn.rescue_ec_rows : (uint32_t)std::max<uint64_t>(GROOT_RESCUE_EC_BYTES / (8ull * k.rec_bw), 1);
-    k.rec_rows = std::min(k.rec_rows, R);
-    hipError_t e = upload(k.rec_path_bit, pb.data(), pb.size());
-    if (e == hipSuccess) e = k.rec_dstar.alloc(R);
-    if (e == hipSuccess) e = k.rec_stats.alloc(kRescueEcStats);
-    if (e == hipSuccess) e = hipMemset(k.rec_stats.p, 0, kRescueEcStats * sizeof(unsigned long long));
-    if (e != hipSuccess) {
-        rec_release(k);
-        return fail(c, GROOT_E_DEVICE, "rescued reads in the equivalence classes: %s", hipGetErrorString(e));
-    }
-    k.rec_slow = 0;
-    k.rec_on = true;
-    return GROOT_OK;
-}
-
-int groot_hip_rescue_ec_enable(groot_ctx *c, int on)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    Counters &k = c->ct;
-    if (!on) {
-        rec_release(k);
-        return GROOT_OK;
-    }
-    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: mismatch rescue is off (groot_hip_rescue_enable)");
-    if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: equivalence classes are off (groot_hip_ec_enable)");
-    if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with paired-end units are not supported: mates are rescued one by one");
-    if (k.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with assigned coverage are not supported: a rescued read has no record to weigh");
-    return rec_alloc(c);
-}
-
-// ---- rescued reads in assigned coverage (kernels_rescue_acov.hpp; the definition is in groot_hip.h) --------------------------
-int groot_hip_rescue_acov_enable(groot_ctx *c, int on, uint64_t min_slots)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    Counters &k = c->ct;
-    if (!on) {
-        if (k.rac_on) rec_release(k);      // (the rescued classes came on with it and cannot stay beside assigned coverage without it)
-        return GROOT_OK;
-    }
-    if (min_slots & (min_slots - 1)) return fail(c, GROOT_E_INVALID, "rescued reads in assigned coverage: min_slots = %llu is not a power of two", (unsigned long long)min_slots);
-    if (min_slots > (1ull << 31)) return fail(c, GROOT_E_INVALID, "rescued reads in assigned coverage: min_slots = %llu, at most 2^31 are supported", (unsigned long long)min_slots);
-    if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in assigned coverage with paired-end units are not supported: mates are rescued one by one");
-    if (k.gec_on && !k.gac_on)             // (beside each other only through groot_hip_gap_acov_enable, which gives the pileup its rule)
-        return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in assigned coverage with gap-placed reads in the equivalence classes are not supported: the pileup has no "
-                              "rule for a gapped record (groot_hip_gap_ec_enable)");
-    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: mismatch rescue is off (groot_hip_rescue_enable)");
-    if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: equivalence classes are off (groot_hip_ec_enable)");
-    if (!k.acov_on) return fail(c, GROOT_E_STATE, "rescued reads in assigned coverage: assigned coverage is off (groot_hip_acov_enable)");
-    if (k.acov.cap < min_slots)
-        if (int rc = acov_grow(c, (uint32_t)(min_slots / k.acov.cap))) return rc;
-    if (k.rac_on) return GROOT_OK;
-    if (int rc = rec_alloc(c)) return rc;
-    k.rac_log_cap = c->kn.rescue_acov_log ? c->kn.rescue_acov_log : (uint32_t)(GROOT_RESCUE_ACOV_BYTES / sizeof(uint4));
-    hipError_t e = k.rac_cand_ser.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
-    if (e == hipSuccess) e = k.rac_stats.alloc(kRescueAcovStats);
-    if (e == hipSuccess) e = hipMemset(k.rac_stats.p, 0, kRescueAcovStats * sizeof(unsigned long long));
-    if (e != hipSuccess) {
-        rec_release(k);
-        return fail(c, GROOT_E_DEVICE, "rescued reads in assigned coverage: %s", hipGetErrorString(e));
-    }
-    k.rac_host_records = 0;
-    k.rac_on = true;
-    return GROOT_OK;
-}
-
-int groot_hip_rescue_acov_stats(groot_ctx *c, groot_rescue_acov_stats *out)
-{
-    if (!c || !out) return GROOT_E_INVALID;
-    uint64_t st[kRescueAcovStats] = {};
-    if (c->ct.rac_on) {
-        if (int rc = drain(c)) return rc;
-        HIP_TRY(c, hipMemcpy(st, c->ct.rac_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    }
-    out->host_records = c->ct.rac_on ? c->ct.rac_host_records : 0;
-    out->records = st[0] + out->host_records;
-    out->dropped = st[kRescueAcovDropped];
-    out->log_rows = c->ct.rac_on ? c->ct.rac_log_cap : 0;
-    out->launches = c->ct.rac_launches;
-    return GROOT_OK;
-}
-
-int groot_hip_rescue_ec_stats(groot_ctx *c, groot_rescue_ec_stats *out)
-{
-    if (!c || !out) return GROOT_E_INVALID;
-    uint64_t st[kRescueEcStats] = {};
-    if (c->ct.rec_on) {
-        if (int rc = drain(c)) return rc;
-        HIP_TRY(c, hipMemcpy(st, c->ct.rec_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    }
-    out->slow_reads = c->ct.rec_on ? c->ct.rec_slow : 0;
-    out->reads = st[0] + out->slow_reads;
-    out->rows = c->ct.rec_on ? c->ct.rec_rows : 0;
-    out->launches = c->ct.rec_launches;
-    return GROOT_OK;
-}
-
-// ---- rescued records (kernels_rescue_rec.hpp; the definition is in groot_hip.h) ------------------------------------------------
-static_assert(sizeof(groot_rescue_record) == kRescueRecWords * sizeof(uint32_t) && offsetof(groot_rescue_record, mm) == 12 && offsetof(groot_rescue_record, strand) == 18 &&
-              offsetof(groot_rescue_record, d) == 19, "rescue_rec_emit_kernel writes groot_rescue_record as five dwords");
-
-int groot_hip_rescue_rec_enable(groot_ctx *c, uint64_t slots_per_batch)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "rescued records can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    Counters &k = c->ct;
-    if (!slots_per_batch) {
-        rr_release(c);
-        return GROOT_OK;
-    }
-    if (k.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued records come from mismatch rescue, which tells the unaligned reads by their records, and assignment rewrites those (groot_hip_assign_enable)");
-    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued records are the placements of mismatch rescue, and that is off (groot_hip_rescue_enable)");
-    if (slots_per_batch > (1ull << 40) / sizeof(groot_rescue_record)) return fail(c, GROOT_E_INVALID, "rescued records: slots_per_batch %llu is beyond 2^40 bytes", (unsigned long long)slots_per_batch);
-    if (k.rr_on && slots_per_batch == k.rr_slots) return GROOT_OK;
-    rr_release(c);
-    const size_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-    hipError_t e = k.rr_kept.alloc(R + 1);
-    if (e == hipSuccess) e = k.rr_off.alloc(R + 1);
-    if (e == hipSuccess) e = k.rr_d.alloc(R);
-    for (auto &s : c->slots) {             // (now, and not at the first launch: no room is an error of this call)
-        if (e == hipSuccess) e = s->ct.d_rr_rec.alloc((size_t)slots_per_batch * kRescueRecWords);
-        if (e == hipSuccess) e = s->ct.d_rr_total.alloc(1);
-    }
-    if (e != hipSuccess) {
-        rr_release(c);
-        return fail(c, GROOT_E_DEVICE, "rescued records: %s", hipGetErrorString(e));
-    }
-    k.rr_slots = slots_per_batch;
-    k.rr_on = true;
-    return GROOT_OK;
-}
-
-int groot_hip_rescue_rec_stats(groot_ctx *c, groot_rescue_rec_stats *out)
-{
-    if (!c || !out) return GROOT_E_INVALID;
-    const Counters &k = c->ct;
-    out->records = k.rr_on ? k.rr_records : 0; out->reads = k.rr_on ? k.rr_reads : 0; out->failed = k.rr_on ? k.rr_failed : 0;
-    out->slots = k.rr_on ? k.rr_slots : 0;
-    out->launches = k.rr_launches;
-    return GROOT_OK;
-}
-
-// ---- gapped records (kernels_gap_rec.hpp; the definition is in groot_hip.h) ----------------------------------------------------
-static_assert(sizeof(groot_gap_record) == kGapRecWords * sizeof(uint32_t) && offsetof(groot_gap_record, k) == 12 && offsetof(groot_gap_record, mm) == 14 &&
-              offsetof(groot_gap_record, strand) == 20 && offsetof(groot_gap_record, d) == 21 && offsetof(groot_gap_record, type) == 22 &&
-              offsetof(groot_gap_record, g) == 23, "gap_rec_emit_kernel writes groot_gap_record as six dwords");
-
-int groot_hip_gap_rec_enable(groot_ctx *c, uint64_t slots_per_batch)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "gapped records can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    Counters &k = c->ct;
-    if (!slots_per_batch) {
-        gr_release(c);
-        return GROOT_OK;
-    }
-    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gapped records are the placements of gapped rescue, and that is off (groot_hip_gap_enable)");
-    if (slots_per_batch > (1ull << 40) / sizeof(groot_gap_record)) return fail(c, GROOT_E_INVALID, "gapped records: slots_per_batch %llu is beyond 2^40 bytes", (unsigned long long)slots_per_batch);
-    if (k.gr_on && slots_per_batch == k.gr_slots) return GROOT_OK;
-    gr_release(c);
-    const size_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
-    hipError_t e = k.gr_kept.alloc(R + 1);
-    if (e == hipSuccess) e = k.gr_off.alloc(R + 1);
-    if (e == hipSuccess) e = k.gr_e.alloc(R);
-    for (auto &s : c->slots) {             // (now, and not at the first launch: no room is an error of this call)
-        if (e == hipSuccess) e = s->ct.d_gr_rec.alloc((size_t)slots_per_batch * kGapRecWords);
-        if (e == hipSuccess) e = s->ct.d_gr_total.alloc(1);
-    }
-    if (e != hipSuccess) {
-        gr_release(c);
-        return fail(c, GROOT_E_DEVICE, "gapped records: %s", hipGetErrorString(e));
-    }
-    k.gr_slots = slots_per_batch;
-    k.gr_on = true;
-    return GROOT_OK;
-}
-
-int groot_hip_gap_rec_stats(groot_ctx *c, groot_gap_rec_stats *out)
-{
-    if (!c || !out) return GROOT_E_INVALID;
-    const Counters &k = c->ct;
-    out->records = k.gr_on ? k.gr_records : 0; out->reads = k.gr_on ? k.gr_reads : 0; out->failed = k.gr_on ? k.gr_failed : 0;
-    out->slots = k.gr_on ? k.gr_slots : 0;
-    out->launches = k.gr_launches;
-    return GROOT_OK;
-}
-
-// ---- gap-placed reads in the equivalence classes (kernels_gap_ec.hpp; the definition is in groot_hip.h) ----------------------
-// gapped rescue and the rescued classes on: checked by the caller
-static int gec_alloc(groot_ctx *c)
-{
-    Counters &k = c->ct;
-    if (k.gec_on) return GROOT_OK;
-    hipError_t e = k.gec_e.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
-    if (e == hipSuccess) e = k.gec_stats.alloc(kGapEcStats);
-    if (e == hipSuccess) e = hipMemset(k.gec_stats.p, 0, kGapEcStats * sizeof(unsigned long long));
-    if (e != hipSuccess) {
-        gec_release(k);
-        return fail(c, GROOT_E_DEVICE, "gap-placed reads in the equivalence classes: %s", hipGetErrorString(e));
-    }
-    k.gec_slow = 0;
-    k.gec_on = true;
-    return GROOT_OK;
-}
-
-int groot_hip_gap_ec_enable(groot_ctx *c, int on)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    Counters &k = c->ct;
-    if (!on) {
-        gec_release(k);
-        return GROOT_OK;
-    }
-    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: gapped rescue is off (groot_hip_gap_enable)");
-    if (!k.rec_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: the rescued reads in the equivalence classes are off (groot_hip_rescue_ec_enable)");
-    if (k.rac_on && !k.gac_on)             // (beside each other only through groot_hip_gap_acov_enable, which gives the pileup its rule)
-        return fail(c, GROOT_E_UNSUPPORTED, "gap-placed reads in the equivalence classes with rescued reads in assigned coverage are not supported: the pileup has no "
-                              "rule for a gapped record, and a DEL covers two intervals (groot_hip_rescue_acov_enable)");
-    return gec_alloc(c);
-}
-
-int groot_hip_gap_ec_stats(groot_ctx *c, groot_gap_ec_stats *out)
-{
-    if (!c || !out) return GROOT_E_INVALID;
-    uint64_t st[kGapEcStats] = {};
-    if (c->ct.gec_on) {
-        if (int rc = drain(c)) return rc;
-        HIP_TRY(c, hipMemcpy(st, c->ct.gec_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    }
-    out->slow_reads = c->ct.gec_on ? c->ct.gec_slow : 0;
-    out->reads = st[0] + out->slow_reads;
-    out->launches = c->ct.gec_launches;
-    return GROOT_OK;
-}
-
-// ---- gap-placed reads in assigned coverage (kernels_gap_acov.hpp; the definition is in groot_hip.h) --------------------------
-int groot_hip_gap_acov_enable(groot_ctx *c, int on)
-{
-    if (!c) return GROOT_E_INVALID;
-    if (!idle(c)) return fail(c, GROOT_E_STATE, "gap-placed reads in assigned coverage can only be switched while nothing is in flight");
-    HIP_TRY(c, hipSetDevice(c->device));
-    Counters &k = c->ct;
-    if (!on) {
-        if (k.gac_on) gec_release(k);      // (the gap-placed classes came on with it and cannot stay beside the rescued records without it)
-        return GROOT_OK;
-    }
-    if (!k.gap_on) return fail(c, GROOT_E_STATE, "gap-placed reads in assigned coverage: gapped rescue is off (groot_hip_gap_enable)");
-    if (!k.rac_on) return fail(c, GROOT_E_STATE, "gap-placed reads in assigned coverage: the rescued reads in assigned coverage are off (groot_hip_rescue_acov_enable)");
-    if (k.gac_on) return GROOT_OK;
-    if (int rc = gec_alloc(c)) return rc;  // (rac_on: mismatch rescue, the classes, the rescued classes and assigned coverage are on, pairing is off)
-    hipError_t e = k.gac_cand_ser.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
-    if (e == hipSuccess) e = k.gac_stats.alloc(kGapAcovStats);
-    if (e == hipSuccess) e = hipMemset(k.gac_stats.p, 0, kGapAcovStats * sizeof(unsigned long long));
-    if (e != hipSuccess) {
-        gec_release(k);
-        return fail(c, GROOT_E_DEVICE, "gap-placed reads in assigned coverage: %s", hipGetErrorString(e));
-    }
-    k.gac_host_records = k.gac_host_placements = 0;
-    k.gac_on = true;
-    return GROOT_OK;
-}
-
-int groot_hip_gap_acov_stats(groot_ctx *c, groot_gap_acov_stats *out)
-{
-    if (!c || !out) return GROOT_E_INVALID;
-    uint64_t st[kGapAcovStats] = {};
-    if (c->ct.gac_on) {
-        if (int rc = drain(c)) return rc;
-        HIP_TRY(c, hipMemcpy(st, c->ct.gac_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    }
-    out->host_records = c->ct.gac_on ? c->ct.gac_host_records : 0;
-    out->placements = st[0] + (c->ct.gac_on ? c->ct.gac_host_placements : 0);
-    out->records = st[kGapAcovRecords] + out->host_records;
-    out->dropped = st[kGapAcovDropped];
-    out->launches = c->ct.gac_launches;
     return GROOT_OK;
 }
 

@@ -1,5 +1,5 @@
 // counters.hpp -- how the pipeline (groot_hip.hip) reaches the counters behind the order stage (counters.hip): report coverage, shared
-// reads, equivalence classes, assigned coverage, pairing.  Their state is groot_ctx::ct and Slot::ct (ctx.hpp).
+// reads, equivalence classes, assigned coverage, pairing, and through counters.hip the rescue family (rescue.hip, rescue.hpp).  Their state is groot_ctx::ct and Slot::ct (ctx.hpp).
 #pragma once
 
 #include "groot_hip.h"

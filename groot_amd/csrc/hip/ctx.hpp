@@ -1,6 +1,6 @@
 // ctx.hpp -- the ctx of libgroot_hip.so as its translation units see it: the buffer types, one batch in flight (Slot), the work sets and
-// groot_ctx itself, with the state of the counters behind the order stage (counters.hip) as ONE member each of the ctx and of a slot.
-// Internal to groot_hip.hip (pipeline + C ABI), open.hip (groot_hip_open*) and counters.hip; the calls between them are at the end, in open.hpp and in counters.hpp.
+// groot_ctx itself, with the state of the counters behind the order stage (counters.hip, rescue.hip) as ONE member each of the ctx and of a slot.
+// Internal to groot_hip.hip (pipeline + C ABI), open.hip (groot_hip_open*), counters.hip and rescue.hip; the calls between them are at the end, in open.hpp, in counters.hpp and in rescue.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -96,7 +96,7 @@ struct Knobs {
     }
 };
 
-// ---- the counters behind the order stage (counters.hip) ----
+// ---- the counters behind the order stage (counters.hip, and rescue.hip for the rescue family) ----
 namespace groot {
 struct EcTable;
 struct AcovTable;
@@ -134,10 +134,29 @@ struct CounterStatus {
     uint32_t acov_fill;                    // ... and its table's fill
     uint32_t rec_slow;                     // rescued reads in the ECs: the batch's slow rescued reads (SlotCounters::d_rec_slow[0])
     uint32_t rac_log;                      // rescued reads in assigned coverage: the kept placements of those reads (SlotCounters::d_rac_nlog[0])
-    uint64_t rr_total;                     // rescued records: the batch's records (SlotCounters::d_rr_total[0])
-    uint64_t gr_total;                     // gapped records: the batch's records (SlotCounters::d_gr_total[0])
+    uint64_t rr_total;                     // rescued records: the batch's records (SlotCounters::rr.d_total[0])
+    uint64_t gr_total;                     // gapped records: the batch's records (SlotCounters::gr.d_total[0])
     uint32_t gec_slow;                     // gap-placed reads in the ECs: the batch's slow gap-rescued reads (SlotCounters::d_gec_slow[0])
     uint32_t gac_log;                      // gap-placed reads in assigned coverage: the log entries of those reads (SlotCounters::d_gac_nlog[0])
+};
+
+// One kind of record a batch hands out beside its traversals -- rescued records, gapped records (rescue.hip) -- as the ctx keeps it ...
+struct RecStream {
+    bool on = false;
+    uint64_t slots = 0;                    // records per batch (fixed at enable)
+    DevBuf<uint32_t> kept;                 // [max_batch_reads + 1] every read's kept placements (tail stream: one batch at a time, as the candidates are)
+    DevBuf<uint64_t> off;                  // [max_batch_reads + 1] their exclusive scan: every read's first record, and the batch's total
+    DevBuf<uint8_t> aux;                   // [max_batch_reads] what the count kernel leaves the emit kernel per candidate (d* / e*)
+    uint64_t records = 0, reads = 0, failed = 0;   // handed out / distinct reads among them / batches failed for room, since enable
+    uint64_t launches = 0;                 // the scan and the emit kernel since open (stays put while it is off)
+};
+// ... and as a slot does
+template <class Rec> struct SlotRecStream {
+    DevBuf<uint32_t> d_rec;                // [slots][sizeof(Rec) / 4 dwords] the batch's records (the emit kernel), copied out at collect
+    DevBuf<uint64_t> d_total;              // [0] their number, whether they found room or not (the scan's last output)
+    PinBuf<Rec> h_rec;                     // what the *_rec_batch call hands out: as many as the batch has
+    uint64_t n = 0;                        // the batch's records in h_rec
+    bool on = false;                       // the feature was on when the batch was submitted
 };
 
 struct SlotCounters {
@@ -154,16 +173,8 @@ struct SlotCounters {
     DevBuf<uint32_t> d_rec_slow;           // [0] their number, with or without a bitmap (rescue_ec_slow_kernel)
     DevBuf<uint4> d_rac_log;               // rescued reads in assigned coverage: [rac_log_cap] (bitmap row, path, X, last) of those reads' kept placements, read at collect
     DevBuf<uint32_t> d_rac_nlog;           // [0] their number, logged or not (rescue_acov_slow_kernel)
-    DevBuf<uint32_t> d_rr_rec;             // rescued records: [rr_slots][5 dwords] the batch's records (rescue_rec_emit_kernel), copied out at collect
-    DevBuf<uint64_t> d_rr_total;           // [0] their number, whether they found room or not (the scan's last output)
-    PinBuf<groot_rescue_record> h_rr_rec;  // what groot_hip_rescue_rec_batch hands out: as many as the batch has
-    uint64_t rr_n = 0;                     // the batch's records in h_rr_rec
-    bool rr = false;                       // the feature was on when the batch was submitted
-    DevBuf<uint32_t> d_gr_rec;             // gapped records: [gr_slots][6 dwords] the batch's records (gap_rec_emit_kernel), copied out at collect
-    DevBuf<uint64_t> d_gr_total;           // [0] their number, whether they found room or not (the scan's last output)
-    PinBuf<groot_gap_record> h_gr_rec;     // what groot_hip_gap_rec_batch hands out: as many as the batch has
-    uint64_t gr_n = 0;                     // the batch's records in h_gr_rec
-    bool gr = false;                       // the feature was on when the batch was submitted
+    SlotRecStream<groot_rescue_record> rr; // rescued records: five dwords each (rescue_rec_emit_kernel), handed out by groot_hip_rescue_rec_batch
+    SlotRecStream<groot_gap_record> gr;    // gapped records: six dwords each (gap_rec_emit_kernel), handed out by groot_hip_gap_rec_batch
     DevBuf<uint32_t> d_gec_slow;           // gap-placed reads in the ECs: [0] the batch's slow gap-rescued reads, with or without a bitmap (gap_ec_slow_kernel);
                                            // their bitmaps are the rows of d_rec_bits behind the rescued reads'
     DevBuf<uint32_t> d_gac_nlog;           // gap-placed reads in assigned coverage: [0] the log entries of the batch's slow gap-rescued reads, logged or not
@@ -255,26 +266,11 @@ struct Counters {
     DevBuf<unsigned long long> rac_stats;  // [kRescueAcovStats]
     uint64_t rac_host_records = 0;         // rescued records folded on the host since enable / groot_hip_acov_reset
     uint64_t rac_launches = 0;             // kernels launched for it since open; the two that take the place of rec's count there
-    // rescued records (groot_hip_rescue_rec_*, kernels_rescue_rec.hpp): needs mismatch rescue on.  The count kernel also leaves every
-    // read's number of kept placements, a scan and rescue_rec_emit_kernel behind it write the batch's records into a buffer of the slot,
-    // and collect copies as many as there are into pinned memory.  Nothing on the device while off.
-    bool rr_on = false;
-    uint64_t rr_slots = 0;                 // records per batch (fixed at enable)
-    DevBuf<uint32_t> rr_kept;              // RescueArgs::n_kept (tail stream: one batch at a time, as the candidates are)
-    DevBuf<uint64_t> rr_off;               // RescueRecArgs::off
-    DevBuf<uint8_t> rr_d;                  // RescueArgs::rec_d
-    uint64_t rr_records = 0, rr_reads = 0, rr_failed = 0;   // handed out / rescued reads among them / batches failed for room, since enable
-    uint64_t rr_launches = 0;              // the scan and rescue_rec_emit_kernel since open (rescue_count_rec_kernel counts as rescue's)
-    // gapped records (groot_hip_gap_rec_*, kernels_gap_rec.hpp): needs gapped rescue on.  rescue_gap_rec_kernel takes rescue_gap_kernel's
-    // place and also leaves every read's number of kept gapped placements, a scan and gap_rec_emit_kernel behind it write the batch's
-    // records into a buffer of the slot, and collect copies as many as there are into pinned memory.  Nothing on the device while off.
-    bool gr_on = false;
-    uint64_t gr_slots = 0;                 // records per batch (fixed at enable)
-    DevBuf<uint32_t> gr_kept;              // GapRecArgs::n_gkept (tail stream: one batch at a time, as the gap candidates are)
-    DevBuf<uint64_t> gr_off;               // GapRecArgs::off
-    DevBuf<uint8_t> gr_e;                  // GapRecArgs::gap_e
-    uint64_t gr_records = 0, gr_reads = 0, gr_failed = 0;   // handed out / gap-rescued reads among them / batches failed for room, since enable
-    uint64_t gr_launches = 0;              // the scan and gap_rec_emit_kernel since open (rescue_gap_rec_kernel counts as gapped rescue's)
+    // rescued records (groot_hip_rescue_rec_*, kernels_rescue_rec.hpp; needs mismatch rescue on) and gapped records (groot_hip_gap_rec_*,
+    // kernels_gap_rec.hpp; needs gapped rescue on).  The count kernel / the gap kernel also leaves every read's number of kept placements, a
+    // scan and the emit kernel behind it write the batch's records into a buffer of the slot, and collect copies as many as there are into
+    // pinned memory.  Nothing on the device while off.  (rescue_count_rec_kernel / rescue_gap_rec_kernel count as rescue's / gapped rescue's launches.)
+    RecStream rr, gr;
     // gap-placed reads in the equivalence classes (groot_hip_gap_ec_*, kernels_gap_ec.hpp): needs gapped rescue and the rescued reads in the
     // ECs on.  rescue_gap_ec_kernel takes the gap kernel's place and also writes every gap-rescued read's path set as a row; two kernels
     // among those of the rescued reads fold the rows into the table of ECs, the sets in too many graphs come back as bitmaps of the
@@ -353,7 +349,7 @@ struct Slot {
     int status = GROOT_OK;
     std::string status_msg;
     groot_stage_ms ms{};
-    SlotCounters ct;                       // what the counters behind the order stage keep per batch (counters.hip)
+    SlotCounters ct;                       // what the counters behind the order stage keep per batch (counters.hip, rescue.hip)
     const uint8_t *seq() const { return input == IN_DEVICE ? ext_seq : d_seq.p; }
     const uint64_t *off() const { return input == IN_DEVICE ? ext_off : d_off.p; }
 };
@@ -505,7 +501,7 @@ struct groot_ctx {
     uint32_t *attempts_ptr = nullptr;      // own buffer or the caller's (groot_hip_attempts_layout)
     uint32_t att_cap = 0;                  // rows the table can hold
     bool att_external = false;
-    Counters ct;                           // report coverage, shared reads, equivalence classes, assigned coverage, pairing (counters.hip)
+    Counters ct;                           // report coverage, shared reads, equivalence classes, assigned coverage, pairing (counters.hip); the rescue family (rescue.hip)
 };
 
 #define HIP_TRY(ctx, expr)                                                                             \
@@ -526,7 +522,7 @@ template <class T> static hipError_t upload(DevBuf<T> &d, const T *src, size_t n
     return e;
 }
 
-// what counters.hip and open.hip need of the pipeline (groot_hip.hip); open.hip's further calls: open.hpp
+// what counters.hip, rescue.hip and open.hip need of the pipeline (groot_hip.hip); open.hip's further calls: open.hpp
 namespace groot {
 int fail(groot_ctx *ctx, int code, const char *fmt, ...);   // sets the ctx's (no ctx: the thread's) error text, returns code
 int drain(groot_ctx *c);                                    // everything submitted has finished on the device (results stay collectable)

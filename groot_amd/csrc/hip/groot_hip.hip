@@ -1,5 +1,5 @@
 // groot_hip.hip -- libgroot_hip.so: the batch pipeline of a ctx (ctx.hpp) and the C ABI of include/groot_hip.h.  groot_hip_open* -- the device tables,
-// the work buffers, the memo -- are open.hip (open.hpp); the counters behind the order stage and their part of the ABI are counters.hip, reached
+// the work buffers, the memo -- are open.hip (open.hpp); the counters behind the order stage and their part of the ABI are counters.hip (the rescue family among them: rescue.hip), reached
 // through the hooks of counters.hpp.
 // gfx950 only; no CPU fallback anywhere in this library.
 #include <cstring>   // before rocprim: its texture iterator calls host memset
@@ -692,8 +692,8 @@ int groot::enqueue(groot_ctx *c, Slot *s)
     s->ticket = c->next_ticket++;
     s->lean_used = s->path_used = false; s->path_reads = 0;   // (an empty batch runs no stage: not what the slot's last batch left)
     s->ct.assigned = c->ct.asg_on;                            // (likewise, and for a batch that fails ahead of the order stage)
-    s->ct.rr = c->ct.rr_on; s->ct.rr_n = 0;                   // (rescued records: an empty batch has none)
-    s->ct.gr = c->ct.gr_on; s->ct.gr_n = 0;                   // (gapped records likewise)
+    s->ct.rr.on = c->ct.rr.on; s->ct.rr.n = 0;                 // (rescued records: an empty batch has none)
+    s->ct.gr.on = c->ct.gr.on; s->ct.gr.n = 0;                 // (gapped records likewise)
     if (s->n_reads == 0) {      // nothing to run: completes at once
         memset(s->h_ctr.p, 0, sizeof(DeviceCounters));
         HIP_TRY(c, hipEventRecord(s->ev_ctr, c->d2h_stream));
@@ -1443,9 +1443,9 @@ int groot_hip_rescue_rec_batch(groot_ctx *c, uint64_t ticket, const groot_rescue
     if (!c || !recs || !n) return GROOT_E_INVALID;
     Slot *s = ticket ? slot_by_ticket(c, ticket, Slot::COLLECTED) : c->waited;
     if (!s) return fail(c, GROOT_E_STATE, "ticket %llu is not a collected batch", (unsigned long long)ticket);
-    if (!s->ct.rr) return fail(c, GROOT_E_STATE, "rescued records were off when the batch was submitted (groot_hip_rescue_rec_enable)");
-    *recs = s->ct.rr_n ? s->ct.h_rr_rec.p : nullptr;
-    *n = s->ct.rr_n;
+    if (!s->ct.rr.on) return fail(c, GROOT_E_STATE, "rescued records were off when the batch was submitted (groot_hip_rescue_rec_enable)");
+    *recs = s->ct.rr.n ? s->ct.rr.h_rec.p : nullptr;
+    *n = s->ct.rr.n;
     return GROOT_OK;
 }
 
@@ -1454,9 +1454,9 @@ int groot_hip_gap_rec_batch(groot_ctx *c, uint64_t ticket, const groot_gap_recor
     if (!c || !recs || !n) return GROOT_E_INVALID;
     Slot *s = ticket ? slot_by_ticket(c, ticket, Slot::COLLECTED) : c->waited;
     if (!s) return fail(c, GROOT_E_STATE, "ticket %llu is not a collected batch", (unsigned long long)ticket);
-    if (!s->ct.gr) return fail(c, GROOT_E_STATE, "gapped records were off when the batch was submitted (groot_hip_gap_rec_enable)");
-    *recs = s->ct.gr_n ? s->ct.h_gr_rec.p : nullptr;
-    *n = s->ct.gr_n;
+    if (!s->ct.gr.on) return fail(c, GROOT_E_STATE, "gapped records were off when the batch was submitted (groot_hip_gap_rec_enable)");
+    *recs = s->ct.gr.n ? s->ct.gr.h_rec.p : nullptr;
+    *n = s->ct.gr.n;
     return GROOT_OK;
 }
 

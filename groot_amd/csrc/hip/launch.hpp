@@ -1,5 +1,5 @@
-// launch.hpp -- kernel dispatch by (sketch size, maxK, k) and path words.  libgroot_hip.so is built from six translation units
-// (groot_hip.hip: ctx + batch pipeline + C ABI + the small kernels; open.hip: groot_hip_open* -- device tables (index_tables.hpp), work buffers, memo -- reached through open.hpp; counters.hip: the counters behind the order stage, reached through counters.hpp; seed_full.hip: the full-width hashing kernel; seed_fast.hip: signature kernel,
+// launch.hpp -- kernel dispatch by (sketch size, maxK, k) and path words.  libgroot_hip.so is built from seven translation units
+// (groot_hip.hip: ctx + batch pipeline + C ABI + the small kernels; open.hip: groot_hip_open* -- device tables (index_tables.hpp), work buffers, memo -- reached through open.hpp; counters.hip: the counters behind the order stage, reached through counters.hpp; rescue.hip: the rescue family among them -- mismatch and gapped rescue, their reads in the classes and in assigned coverage, their records -- reached through rescue.hpp; seed_full.hip: the full-width hashing kernel; seed_fast.hip: signature kernel,
 // text lookup, list pass; align.hip: the graph-walk kernels) so that they compile side by side; these are the calls between them.
 #pragma once
 

@@ -1,6 +1,6 @@
 // open.hip -- groot_hip_open*: a new ctx's streams and slots, the device tables (built on the host by index_tables.hpp, uploaded here), the work
 // buffers, and what is built with the device's help: prefix tables, signature index, the memo (outcome table + text table), in the
-// foreground or on the ctx's background thread.  One of the six translation units of libgroot_hip.so (launch.hpp); the calls between
+// foreground or on the ctx's background thread.  One of the seven translation units of libgroot_hip.so (launch.hpp); the calls between
 // this unit and the pipeline (groot_hip.hip) are open.hpp.
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
 // seed_fast.hip -- the seed stage's fast paths: sketch_sig_kernel (27-bit signatures, text confirmation), text_lookup_kernel (reads the
-// memo knows) and the list pass of sketch_seed_kernel behind either.  One of the six translation units of libgroot_hip.so (launch.hpp).
+// memo knows) and the list pass of sketch_seed_kernel behind either.  One of the seven translation units of libgroot_hip.so (launch.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

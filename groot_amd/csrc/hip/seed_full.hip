@@ -1,5 +1,5 @@
 // seed_full.hip -- the instances of sketch_seed_kernel that take a whole batch (K1+K2 full width; `keep_sketches`, groot_hip_sketch,
-// batches the signature kernel is not built for).  One of the six translation units of libgroot_hip.so (launch.hpp).
+// batches the signature kernel is not built for).  One of the seven translation units of libgroot_hip.so (launch.hpp).
 #include <hip/hip_runtime.h>
 
 #include "kernels_sketch.hpp"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # register / spill / scratch figures of every kernel of libgroot_hip.so (gfx950 code object metadata), read from the objects of its
-# six translation units (build/obj/*.o; pass other object files to look at those):  name  scratch  sgprs  sgpr-spills  vgprs  vgpr-spills
+# seven translation units (build/obj/*.o; pass other object files to look at those):  name  scratch  sgprs  sgpr-spills  vgprs  vgpr-spills
 set -e
 B=/opt/rocm/lib/llvm/bin
 for O in ${@:-build/obj/*.o}; do
