@@ -214,6 +214,16 @@ int main(int argc, char **argv)
     if (groot_hip_gap_acov_enable(ctxs[0], 1) != GROOT_E_STATE) DIE("groot_hip_gap_acov_enable without gapped rescue was not refused");
     if (groot_hip_gap_acov_stats(ctxs[0], &gast)) DIE("groot_hip_gap_acov_stats: %s", groot_hip_last_error(ctxs[0]));
     if (gast.placements || gast.records || gast.host_records || gast.dropped || gast.launches) DIE("groot_hip_gap_acov_stats: counts while the feature is off");
+    /* AcovPairsEnable / AcovPairsStats: zero while the rule is off; on, it brings equivalence classes, assigned coverage and pairing with
+     * it, and off again leaves the classes and pairing on */
+    groot_acov_pairs_stats aps;
+    if (groot_hip_acov_pairs_stats(ctxs[0], &aps)) DIE("groot_hip_acov_pairs_stats: %s", groot_hip_last_error(ctxs[0]));
+    if (aps.records || aps.left_out || aps.joined_reads || aps.slow_fragments) DIE("groot_hip_acov_pairs_stats: counts while the feature is off");
+    if (groot_hip_acov_pairs_enable(ctxs[0], 1)) DIE("groot_hip_acov_pairs_enable: %s", groot_hip_last_error(ctxs[0]));
+    uint64_t pj = 1, ps = 1, po = 1;
+    if (groot_hip_pairs_stats(ctxs[0], &pj, &ps, &po) || pj || ps || po) DIE("groot_hip_acov_pairs_enable did not switch pairing on");
+    if (groot_hip_acov_pairs_enable(ctxs[0], 0)) DIE("groot_hip_acov_pairs_enable(0): %s", groot_hip_last_error(ctxs[0]));
+    if (groot_hip_pairs_stats(ctxs[0], &pj, &ps, &po)) DIE("pairing went off with the rule");
     for (int d = 0; d < n_ctx; d++) groot_hip_close(ctxs[d]);
     groot_index_free(idx);
     return 0;

@@ -453,6 +453,34 @@ func (c *Ctx) GapAcovStatsGet() (GapAcovStats, error) {
 	return GapAcovStats{uint64(st.placements), uint64(st.records), uint64(st.host_records), uint64(st.dropped), uint64(st.launches)}, nil
 }
 
+// AcovPairsStats mirrors groot_acov_pairs_stats
+type AcovPairsStats struct {
+	Records, LeftOut, JoinedReads, SlowFragments uint64
+}
+
+// AcovPairsEnable puts the ctx into assigned coverage over fragments (include/groot_hip.h, "assigned coverage over fragments"): it
+// switches on whichever of equivalence classes, assigned coverage and pairing is off, and a record of a joined fragment then counts on
+// the paths of the fragment's set only.  Off: the rule and assigned coverage go, the classes and pairing stay.  Only while nothing is in flight.
+func (c *Ctx) AcovPairsEnable(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.groot_hip_acov_pairs_enable(c.h, v); rc != 0 {
+		return c.err("groot_hip_acov_pairs_enable")
+	}
+	return nil
+}
+
+// AcovPairsStatsGet returns the records piled up and left out under the rule since AcovPairsEnable or a reset of the table (waits for everything in flight)
+func (c *Ctx) AcovPairsStatsGet() (AcovPairsStats, error) {
+	var st C.groot_acov_pairs_stats
+	if rc := C.groot_hip_acov_pairs_stats(c.h, &st); rc != 0 {
+		return AcovPairsStats{}, c.err("groot_hip_acov_pairs_stats")
+	}
+	return AcovPairsStats{uint64(st.records), uint64(st.left_out), uint64(st.joined_reads), uint64(st.slow_fragments)}, nil
+}
+
 func (c *Ctx) err(what string) error {
 	return fmt.Errorf("%s: %s", what, C.GoString(C.groot_hip_last_error(c.h)))
 }

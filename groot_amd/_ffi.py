@@ -115,6 +115,17 @@ def gap_acov_prototypes(L):
     L.groot_hip_gap_acov_enable.restype = L.groot_hip_gap_acov_stats.restype = C.c_int
 
 
+# ---- assigned coverage over fragments (groot_hip.h) ----
+ACOV_PAIRS_STATS = ("records", "left_out", "joined_reads", "slow_fragments")   # groot_acov_pairs_stats, four uint64
+
+
+def acov_pairs_prototypes(L):
+    """argtypes of groot_hip_acov_pairs_enable / groot_hip_acov_pairs_stats (libgroot_hip.so)"""
+    L.groot_hip_acov_pairs_enable.argtypes = [C.c_void_p, C.c_int]
+    L.groot_hip_acov_pairs_stats.argtypes = [C.c_void_p, u64p]
+    L.groot_hip_acov_pairs_enable.restype = L.groot_hip_acov_pairs_stats.restype = C.c_int
+
+
 def opt_ptr(arr, ctype):
     """as_ptr, or a NULL pointer for None"""
     return None if arr is None else as_ptr(arr, ctype)

@@ -28,6 +28,7 @@ struct Harvested {                           // the sums over every harvest so f
     groot_gap_ec_stats gap_ec{};                             // --abundanceGapped: the gap-placed reads in the classes (groot_hip_gap_ec_*)
     groot_rescue_acov_stats rescue_acov{};                   // --callsRescued: their records in the pileup (groot_hip_rescue_acov_*)
     groot_gap_acov_stats gap_acov{};                         // --callsGapped: the gap-placed reads' records in the pileup (groot_hip_gap_acov_*)
+    groot_acov_pairs_stats acov_pairs{};                     // --callsPaired: the records piled up and left out under the rule for fragments (groot_hip_acov_pairs_*)
 };
 
 class RunCounters {
@@ -53,7 +54,7 @@ public:
     {
         if (plan_.assign)
             if (int rc = groot_hip_assign_enable(ctx, on ? assign_alpha_.data() : nullptr, v_.n_paths, a_.min_posterior)) return rc;
-        if (plan_.frags)
+        if (plan_.frags && !(plan_.calls_paired && on))      // (--callsPaired: pairing comes on with assigned coverage, below)
             if (int rc = groot_hip_pairs_enable(ctx, on)) return rc;
         if (plan_.coverage)
             if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
@@ -68,7 +69,7 @@ public:
         if (plan_.shared)
             if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
         if (plan_.calls && on)
-            if (int rc = groot_hip_acov_enable(ctx, 1)) return rc;
+            if (int rc = plan_.calls_paired ? groot_hip_acov_pairs_enable(ctx, 1) : groot_hip_acov_enable(ctx, 1)) return rc;
         if (plan_.abundance)
             if (int rc = groot_hip_ec_enable(ctx, on)) return rc;        // (off: assigned coverage goes with it, and so do the rescued reads in the classes)
         if (plan_.calls_rescued && on) {     // (it switches the rescued reads in the classes on itself)
@@ -97,6 +98,13 @@ public:
             if (int rc = groot_hip_pairs_stats(ctx, &j, &sp, &si)) return rc;
             std::lock_guard<std::mutex> lk(mu_);
             h_.fr_joined += j; h_.fr_split += sp; h_.fr_single += si;
+        }
+        if (plan_.calls_paired) {
+            groot_acov_pairs_stats st{};
+            if (int rc = groot_hip_acov_pairs_stats(ctx, &st)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            groot_acov_pairs_stats &t = h_.acov_pairs;
+            t.records += st.records; t.left_out += st.left_out; t.joined_reads += st.joined_reads; t.slow_fragments += st.slow_fragments;
         }
         if (plan_.calls) {
             uint64_t ne = 0, ni = 0, nt = 0;

@@ -175,6 +175,10 @@ void write_calls(const Args &a, const AlignPlan &plan, const groot_index_view &v
     if (plan.calls_gapped)
         logf("\tcalls: %llu gapped placement(s) of gap-placed reads piled up as %llu record(s), a deletion as two and an insertion as one, %llu of them on ARGs of more than 4 graphs",
              (unsigned long long)h.gap_acov.placements, (unsigned long long)h.gap_acov.records, (unsigned long long)h.gap_acov.host_records);
+    if (plan.calls_paired)
+        logf("\tcalls: %llu record(s) of fragments piled up, %llu left out on ARGs outside their fragment's set; %llu read(s) in joined fragments, %llu fragment(s) on ARGs of more than 4 graphs",
+             (unsigned long long)h.acov_pairs.records, (unsigned long long)h.acov_pairs.left_out, (unsigned long long)h.acov_pairs.joined_reads,
+             (unsigned long long)h.acov_pairs.slow_fragments);
     if (plan.rarefy) rarefy_on_gpu(a, v, device, m_ec, m_off.data(), m_ids.data(), m_cnt.data(), true, m_tp, m_tup.data(), m_tn.data());
 }
 

@@ -11,6 +11,7 @@ struct AlignPlan {
     bool ab_gapped = false;  // --abundanceGapped: and so do the gap-placed reads
     bool calls_rescued = false; // --callsRescued: and their kept placements the pileup of --calls
     bool calls_gapped = false;  // --callsGapped: and so do the gap-placed reads' (a DEL as two intervals, an INS as one)
+    bool calls_paired = false;  // --callsPaired: --calls over fragments (a joined fragment's records count on the paths of its set only)
     bool rescued_bam = false;   // --rescuedBam: the kept placements of the rescued reads as BAM records in a file of their own
     bool rescued_bam_gaps = false; // --rescuedBamGaps: and the kept placements of the gap-rescued reads with them
     bool coverage = false;   // report coverage is counted: --report, or --variants / --indels for its exact depth
@@ -64,7 +65,7 @@ int plan_align(const Args &a, AlignPlan *p)
     if (p->rarefy && (!a.rarefy_steps || !a.rarefy_reps)) return refuse("--rarefySteps and --rarefyReps must be at least 1");
     if (p->calls && !p->abundance) return refuse("--calls has a line per line of the abundance file: it needs --abundance");
     if (p->calls && a.no_align) return refuse("--calls needs the exact alignments: it cannot be combined with --noAlign");
-    if (p->calls && (a.paired || a.interleaved))
+    if (p->calls && (a.paired || a.interleaved) && !a.calls_paired)
         return refuse("--calls cannot be combined with --paired / --interleaved yet: a fragment's set is the intersection of its mates' sets, and the records "
                       "outside the intersection have no weight rule");
     if (a.call_support && !p->calls) return refuse("--callSupport adds columns to the calls file: it needs --calls");
@@ -135,6 +136,10 @@ int plan_align(const Args &a, AlignPlan *p)
     if (a.calls_gapped && !p->calls_rescued) return refuse("--callsGapped piles the gap-placed reads up beside the rescued reads' records: it needs --callsRescued");
     if (a.calls_gapped && !p->ab_gapped) return refuse("--callsGapped piles up the reads --abundanceGapped adds to the classes: it needs it");
     p->calls_gapped = a.calls_gapped;
+    // --callsPaired: checked behind everything above (--assignFrom has refused --calls and --paired, --abundanceRescued and with it --callsRescued have refused --paired)
+    if (a.calls_paired && !p->calls) return refuse("--callsPaired piles up the records of fragments in the file of --calls: it needs --calls");
+    if (a.calls_paired && !p->frags) return refuse("--callsPaired is the rule for the records of fragments: it needs --paired or --interleaved");
+    p->calls_paired = a.calls_paired;
     p->coverage = p->report || p->variants || p->indels;
     p->counters = p->report || p->abundance || p->assign || p->rescue;
     return 0;

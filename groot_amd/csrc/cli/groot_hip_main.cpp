@@ -38,6 +38,7 @@ void usage()
             "                  [--abundanceRescued --calls c.tsv --callsRescued [--callSlots 16777216]]\n"
             "                  [--abundance a.tsv --abundanceRescued --indels i.tsv --abundanceGapped [--rescueGap 3]]\n"
             "                  [--abundance a.tsv --abundanceRescued --indels i.tsv --abundanceGapped --calls c.tsv --callsRescued --callsGapped]\n"
+            "                  [(--paired | --interleaved) --abundance a.tsv --calls c.tsv --callsPaired]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
@@ -90,7 +91,9 @@ void usage()
             "                   those records per batch on the GPU, 4 per read of --batch unless given (a batch with more fails the run and names the flag);\n"
             "                   --paired: the -f files are R1,R2[,R1b,R2b...], first with second, third with fourth; --interleaved: the mates alternate in\n"
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
-            "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order)\n"
+            "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order.  --calls only\n"
+            "                   beside --callsPaired: both mates' records are piled up under the fragment's class, and a record of a fragment whose mates' sets\n"
+            "                   intersect counts on the ARGs of the intersection only -- elsewhere the fragment has no posterior.  Not with --callsRescued)\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
             "                  [--bootstraps B [--bootSeed 1]] [-p N] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
@@ -170,6 +173,7 @@ Args parse(int argc, char **argv)
         }
         else if (a.cmd == "align" && f == "--callsRescued") a.calls_rescued = true;
         else if (a.cmd == "align" && f == "--callsGapped") a.calls_gapped = true;
+        else if (a.cmd == "align" && f == "--callsPaired") a.calls_paired = true;
         else if (a.cmd == "align" && f == "--callSlots") {
             const std::string t = v();
             char *end = nullptr;

@@ -153,9 +153,15 @@ static int acov_count(groot_ctx *c, Slot *s)
     a.node_np_off = k.d_np_off.p; a.np = k.d_np.p; a.graph_path_off = k.d_gpo.p; a.path_len = k.d_len.p;
     a.read_ser = s->ct.d_acov_ser.p; a.state = s->ct.d_acov_state.p; a.fill = k.acov_fill.p;
     a.cap = s->trav_cap; a.pw = c->pw_view; a.first_read_id = s->first_read_id; a.n_paths = (uint32_t)k.h_len.size();
+    a.read_mate = s->ct.d_acov_mate.p; a.pstats = k.acp_stats.p;
     const dim3 g(grid_for(s->trav_cap));
-    hipLaunchKernelGGL(acov_count_kernel<false>, g, dim3(kBlock), 0, c->tstream, a, k.acov.table());
-    hipLaunchKernelGGL(acov_count_kernel<true>, g, dim3(kBlock), 0, c->tstream, a, k.acov.table());
+    if (k.acp_on) {
+        hipLaunchKernelGGL((acov_count_kernel<false, true>), g, dim3(kBlock), 0, c->tstream, a, k.acov.table());
+        hipLaunchKernelGGL((acov_count_kernel<true, true>), g, dim3(kBlock), 0, c->tstream, a, k.acov.table());
+    } else {
+        hipLaunchKernelGGL((acov_count_kernel<false, false>), g, dim3(kBlock), 0, c->tstream, a, k.acov.table());
+        hipLaunchKernelGGL((acov_count_kernel<true, false>), g, dim3(kBlock), 0, c->tstream, a, k.acov.table());
+    }
     k.acov_launches += 2;
     HIP_TRY(c, hipGetLastError());
     return GROOT_OK;
@@ -167,7 +173,13 @@ static int acov_launch(groot_ctx *c, Slot *s, const SharedArgs &sa)
     HIP_TRY(c, s->ct.d_acov_ser.reserve(std::max<uint32_t>(c->prm.max_batch_reads, 1u)));
     HIP_TRY(c, s->ct.d_acov_state.reserve(1));
     HIP_TRY(c, hipMemsetAsync(s->ct.d_acov_state.p, 0, sizeof(uint32_t), c->tstream));
-    hipLaunchKernelGGL(acov_serial_kernel, dim3(grid_for(s->trav_cap)), dim3(kBlock), 0, c->tstream, sa, c->ct.acov_tab_ser.p, s->ct.d_acov_ser.p);
+    if (c->ct.acp_on) {
+        HIP_TRY(c, s->ct.d_acov_mate.reserve(std::max<uint32_t>(c->prm.max_batch_reads, 1u)));
+        hipLaunchKernelGGL(acov_serial_paired_kernel, dim3(grid_for(s->trav_cap)), dim3(kBlock), 0, c->tstream, sa, c->ct.acov_tab_ser.p, s->ct.d_acov_ser.p,
+                           s->ct.d_acov_mate.p, c->ct.acp_stats.p);
+    } else {
+        hipLaunchKernelGGL(acov_serial_kernel, dim3(grid_for(s->trav_cap)), dim3(kBlock), 0, c->tstream, sa, c->ct.acov_tab_ser.p, s->ct.d_acov_ser.p);
+    }
     c->ct.acov_launches++;
     return acov_count(c, s);
 }
@@ -220,14 +232,18 @@ static int acov_collect(groot_ctx *c, Slot *s, bool refetch)
     }
 }
 
-// the records of one slow-path read (trav[0..n), its path sets, its S(r) = ids) into acov_host; m_len = the read's length
-static void acov_fold_host(groot_ctx *c, const groot_trav *trav, const uint64_t *mask, size_t n, const std::vector<uint32_t> &ids, uint64_t read_len)
+// the records of one slow-path unit (trav[0..n), their path sets, the unit's set = ids) into acov_host; offs = the batch's read offsets
+// (a record's M op is its own read's length less its clips).  in_ids: the unit is a joined fragment, and only the records on a path of
+// ids count (the others are left out); else every path of the records is in ids, and nothing is looked up.
+static void acov_fold_host(groot_ctx *c, const Slot *s, const groot_trav *trav, const uint64_t *mask, size_t n, const std::vector<uint32_t> &ids,
+                           const std::vector<uint64_t> &offs, bool in_ids)
 {
     const uint32_t pw = c->pw_view, n_paths = (uint32_t)c->ct.h_len.size();
     auto &tab = c->ct.acov_host[ids];
     for (size_t t = 0; t < n; t++) {
         const groot_trav &tr = trav[t];
-        const uint64_t m = read_len - ((tr.flags & GROOT_TRAV_START_CLIP) ? 1u : 0u) - ((tr.flags & GROOT_TRAV_END_CLIP) ? 1u : 0u);
+        const uint32_t r = tr.read_id - s->first_read_id;
+        const uint64_t m = (offs[r + 1] - offs[r]) - ((tr.flags & GROOT_TRAV_START_CLIP) ? 1u : 0u) - ((tr.flags & GROOT_TRAV_END_CLIP) ? 1u : 0u);
         const uint32_t g0 = c->ct.h_gpo[tr.graph_id];
         for (uint32_t j = c->ct.h_np_off[tr.node]; j < c->ct.h_np_off[tr.node + 1]; j++) {
             const uint2 e = c->ct.h_np[j];
@@ -236,6 +252,7 @@ static void acov_fold_host(groot_ctx *c, const groot_trav *trav, const uint64_t 
             if (gp >= n_paths) continue;
             const uint64_t len = c->ct.h_len[gp], pos = (uint64_t)e.y + tr.offset;
             if (len == 0 || pos > 0xFFFFFFFEull) continue;
+            if (in_ids && !std::binary_search(ids.begin(), ids.end(), gp)) { c->ct.acp_host_left++; continue; }
             const uint64_t last = std::min<uint64_t>(pos + m, len - 1);
             tab[{gp, (uint32_t)pos, (uint32_t)last}]++;
             c->ct.acov_slow_records++;
@@ -294,8 +311,9 @@ static int ec_collect(groot_ctx *c, Slot *s, bool refetch)
             ec_set_of(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids);
         }
         if (c->ct.acov_on && !ids.empty() && t1 > t0) {
-            const uint32_t r = tr[o].read_id - s->first_read_id;
-            acov_fold_host(c, tr.data() + o, mk.data() + o * pw, t1 - t0, ids, offs[r + 1] - offs[r]);
+            const bool fragment = c->ct.pairs_on && tm != t1;
+            acov_fold_host(c, s, tr.data() + o, mk.data() + o * pw, t1 - t0, ids, offs, fragment);
+            c->ct.acp_slow_frags += fragment;
         }
         if (!ids.empty()) c->ct.ec_host[ids]++;
     }
@@ -382,9 +400,9 @@ int counters_launch(groot_ctx *c, Slot *s)
             if (int rc = ec_reserve(c, s)) return rc;
             HIP_TRY(c, s->ct.d_ec_slow.reserve(1 + (paired ? 3 : 2) * (size_t)c->prm.max_batch_reads));
             HIP_TRY(c, s->ct.h_status.reserve(1));
-            if (paired) hipLaunchKernelGGL(ec_merge_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p, nullptr);
-            else hipLaunchKernelGGL(ec_merge_kernel<false>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p,
-                                    k.acov_on ? k.acov_tab_ser.p : nullptr);
+            uint32_t *tab_ser = k.acov_on ? k.acov_tab_ser.p : nullptr;     // (with pairing on: assigned coverage over fragments, the units' serials)
+            if (paired) hipLaunchKernelGGL(ec_merge_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p, tab_ser);
+            else hipLaunchKernelGGL(ec_merge_kernel<false>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p, tab_ser);
             if (k.acov_on)
                 if (int rc = acov_launch(c, s, sa)) return rc;
         }
@@ -769,6 +787,8 @@ int groot_hip_acov_enable(groot_ctx *c, int on)
     HIP_TRY(c, hipSetDevice(c->device));
     if (!on) {
         if (c->ct.rac_on) rescue_ec_release(c->ct);     // (the rescued reads in it go, and the rescued classes that came on with them)
+        c->ct.acp_stats.release();                      // (the rule over fragments goes with it; pairing stays)
+        c->ct.acp_on = false;
         c->ct.acov.release();
         for (auto *b : {&c->ct.acov_fill, &c->ct.acov_err, &c->ct.acov_tab_ser}) b->release();
         c->ct.acov_host.clear();
@@ -919,6 +939,8 @@ int groot_hip_acov_reset(groot_ctx *c)
     HIP_TRY(c, hipMemset(c->ct.acov_fill.p, 0, sizeof(uint32_t)));
     c->ct.acov_grows = c->ct.acov_slow_records = c->ct.acov_redone = 0;
     c->ct.acov_host.clear();
+    if (c->ct.acp_on) HIP_TRY(c, hipMemset(c->ct.acp_stats.p, 0, kAcovPairStats * sizeof(unsigned long long)));
+    c->ct.acp_host_left = c->ct.acp_slow_frags = 0;
     return rescue_acov_reset(c);
 }
 
@@ -983,9 +1005,11 @@ int groot_hip_pairs_enable(groot_ctx *c, int on)
 {
     if (!c) return GROOT_E_INVALID;
     if (!idle(c)) return fail(c, GROOT_E_STATE, "pairing can only be switched while nothing is in flight");
-    if (on && c->ct.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assigned coverage are not supported");
+    if (on && c->ct.acov_on && !c->ct.acp_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assigned coverage are not supported");
     if (on && c->ct.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assignment are not supported (groot_hip_assign_enable)");
     if (on && c->ct.rec_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with rescued reads in the equivalence classes are not supported: mates are rescued one by one (groot_hip_rescue_ec_enable)");
+    if (!on && c->ct.acp_on)              // (assigned coverage over fragments has no meaning without them: the rule and the table go)
+        if (int rc = groot_hip_acov_enable(c, 0)) return rc;
     c->ct.pairs_on = on != 0;
     if (c->ct.sh_on || c->ct.ec_on) {     // (else there is nothing to zero: sh_common_alloc zeroes the counts when either comes on)
         HIP_TRY(c, hipSetDevice(c->device));
@@ -1004,6 +1028,53 @@ int groot_hip_pairs_stats(groot_ctx *c, uint64_t *joined, uint64_t *split, uint6
     if (joined) *joined = st[kSharedPairStats];
     if (split) *split = st[kSharedPairStats + 1];
     if (single) *single = st[kSharedPairStats + 2];
+    return GROOT_OK;
+}
+
+// ---- assigned coverage over fragments (the kPaired kernels of kernels_acov.hpp; the rule is in groot_hip.h) -----------------
+int groot_hip_acov_pairs_enable(groot_ctx *c, int on)
+{
+    if (!c) return GROOT_E_INVALID;
+    if (!idle(c)) return fail(c, GROOT_E_STATE, "assigned coverage over fragments can only be switched while nothing is in flight");
+    Counters &k = c->ct;
+    if (!on) return k.acp_on ? groot_hip_acov_enable(c, 0) : GROOT_OK;     // (equivalence classes and pairing stay)
+    if (k.acp_on) return GROOT_OK;
+    if (k.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "assigned coverage over fragments counts S(r), which assignment collapses (groot_hip_assign_enable)");
+    if (k.rec_on)
+        return fail(c, GROOT_E_UNSUPPORTED, "assigned coverage over fragments with rescued reads in the equivalence classes is not supported: mates are rescued one by one (groot_hip_rescue_ec_enable)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the two enables refuse each other: each is made with the other one off
+    const bool was_acov = k.acov_on, was_pairs = k.pairs_on;
+    k.pairs_on = false;
+    int rc = groot_hip_acov_enable(c, 1);
+    k.pairs_on = was_pairs;
+    if (rc) return rc;
+    hipError_t e = k.acp_stats.alloc(kAcovPairStats);
+    if (e == hipSuccess) e = hipMemset(k.acp_stats.p, 0, kAcovPairStats * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        k.acp_stats.release();
+        if (!was_acov) groot_hip_acov_enable(c, 0);
+        return fail(c, GROOT_E_DEVICE, "assigned coverage over fragments: %s", hipGetErrorString(e));
+    }
+    k.acp_host_left = k.acp_slow_frags = 0;
+    k.acp_on = true;
+    return was_pairs ? GROOT_OK : groot_hip_pairs_enable(c, 1);
+}
+
+int groot_hip_acov_pairs_stats(groot_ctx *c, groot_acov_pairs_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    *out = groot_acov_pairs_stats{};
+    if (!c->ct.acp_on) return GROOT_OK;
+    std::map<std::vector<uint32_t>, uint64_t> m;
+    std::vector<AcovTuple> tp;
+    if (int rc = acov_gather(c, m, tp)) return rc;     // (drains)
+    for (const auto &t : tp) out->records += t.n;
+    uint64_t st[kAcovPairStats];
+    HIP_TRY(c, hipMemcpy(st, c->ct.acp_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    out->left_out = st[0] + c->ct.acp_host_left;
+    out->joined_reads = st[1];
+    out->slow_fragments = c->ct.acp_slow_frags;
     return GROOT_OK;
 }
 

@@ -164,7 +164,9 @@ struct SlotCounters {
     PinBuf<CounterStatus> h_status;
     DevBuf<uint32_t> d_acov_ser;           // assigned coverage: the EC serial of every read of the batch (acov_serial_kernel); the counting kernels read it, also when collect repeats them
     DevBuf<uint32_t> d_acov_state;         // [0] 1 = the batch's claim phase ran out of room (its add phase then did nothing), 2 = a key went missing
-    DevBuf<uint32_t> d_best;               // assignment: best path / MAPQ of every read of the batch (assign_kernel), copied out with the batch
+    DevBuf<uint2> d_acov_mate;             // assigned coverage over fragments: per read of a joined fragment the span of its mate's records (acov_serial_paired_kernel);
+                                           // with d_acov_ser all the rule needs when collect repeats the count (the unit rows are the ctx's, and gone by then)
+    DevBuf<uint32_t> d_best;              // assignment: best path / MAPQ of every read of the batch (assign_kernel), copied out with the batch
     DevBuf<uint8_t> d_mapq;
     PinBuf<uint32_t> h_best;
     PinBuf<uint8_t> h_mapq;
@@ -219,6 +221,11 @@ struct Counters {
     uint64_t acov_grows = 0, acov_slow_records = 0, acov_redone = 0;
     uint64_t acov_launches = 0;            // kernels launched for it since open (stays put while it is off)
     std::map<std::vector<uint32_t>, std::map<std::array<uint32_t, 3>, uint64_t>> acov_host;   // S(r) -> (path, Pos, last) -> records, of slow-path reads
+    // assigned coverage over fragments (groot_hip_acov_pairs_*; the kPaired kernels of kernels_acov.hpp): the one state in which assigned
+    // coverage and pairing are on together.  A record of a joined fragment counts on the paths of the fragment's set only.
+    bool acp_on = false;
+    DevBuf<unsigned long long> acp_stats;  // [kAcovPairStats] records left out on the device, reads of joined fragments
+    uint64_t acp_host_left = 0, acp_slow_frags = 0;   // records left out on the host / joined fragments folded there, since enable / groot_hip_acov_reset
     // assignment (groot_hip_assign_*, kernels_assign.hpp): assign_kernel rewrites every batch's records inside the order stage, ahead
     // of everything that reads them.  Nothing on the device while off.
     bool asg_on = false;

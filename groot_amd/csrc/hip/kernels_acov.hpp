@@ -29,6 +29,14 @@
 // and so do neighbouring reads of one EC at one place.  The k-th record of lane l is compared with the k-th record of lane l - 1; a
 // run of equal keys adds its length once, from its first lane (one ballot and four shuffles per step, no LDS).
 // Every kernel reads the pass's status word first, as the other counters do: a pass collect redoes is not counted.
+//
+// Over fragments (groot_hip_acov_pairs_enable; the rule is in groot_hip.h): the rows are units (shared_gather_paired_kernel), so
+// acov_serial_paired_kernel (a thread per fragment start) gives both mates of a joined fragment the serial of the unit row and leaves
+// each of them the span of its mate's records in read_mate[], which the slot owns as it owns read_ser[].  acov_count_kernel<.., true>
+// counts a record of such a read on path p only when p is in a record of the mate in the same graph (the record's own bit ANDed with
+// the OR of the mate's path sets there, a word at a time); the others are left out and counted in pstats[0] by the add phase, which runs
+// to its end exactly once.  It reads the records, their masks, read_ser[] and read_mate[] and no row of the batch's set table: by the
+// time collect repeats the count, the next batch has overwritten those rows.  kPaired = false drops every branch.
 #pragma once
 
 #include "kernels_shared.hpp"
@@ -57,7 +65,11 @@ struct AcovArgs {
     uint32_t *state;               // [0] of this batch: 1 = the claim ran out of room, 2 = the add missed a key (never met)
     uint32_t *fill;                // claimed slots of the table
     uint32_t cap, pw, first_read_id, n_paths;
+    const uint2 *read_mate;        // kPaired: [n_reads] (first, end) of the mate's records for a read of a joined fragment, (0, 0) for any other
+    unsigned long long *pstats;    // kPaired: [0] records left out, [1] reads of joined fragments (acov_serial_paired_kernel)
 };
+
+constexpr uint32_t kAcovPairStats = 2;
 
 __device__ __forceinline__ uint32_t acov_hash(unsigned long long k0, unsigned long long k1)
 {
@@ -97,7 +109,20 @@ __device__ __forceinline__ uint32_t acov_find(const AcovTable &t, unsigned long 
     return kAcovNone;
 }
 
-// one thread per read start: the serial of the read's EC from the owner slot of its set row (tab_ser: ec_merge_kernel)
+// the serial of the EC of row r of the batch's set table (tab_ser: ec_merge_kernel); kAcovNone for a slow-path unit
+__device__ __forceinline__ uint32_t acov_row_serial(const SharedArgs &a, const uint32_t *tab_ser, uint32_t r)
+{
+    if (a.set_graph[(size_t)r * kSharedSegs] == kSharedEmpty) return kAcovNone;
+    uint32_t slot = (uint32_t)shared_hash(a, r) & a.tab_mask;
+    for (uint32_t i = 0; i <= a.tab_mask; i++, slot = (slot + 1) & a.tab_mask) {
+        const uint32_t cur = a.tab_rep[slot];
+        if (cur == kSharedEmpty) break;        // (insert put every row in: never met)
+        if (cur == r || same_set(a, cur, r)) return tab_ser[slot];
+    }
+    return kAcovNone;
+}
+
+// one thread per read start: the serial of the read's EC from the owner slot of its set row
 __global__ __launch_bounds__(kBlock) void acov_serial_kernel(SharedArgs a, const uint32_t *tab_ser, uint32_t *read_ser)
 {
     if (!shared_live(a)) return;
@@ -105,33 +130,69 @@ __global__ __launch_bounds__(kBlock) void acov_serial_kernel(SharedArgs a, const
     for (uint32_t t0 = blockIdx.x * kBlock + threadIdx.x; t0 < n; t0 += gridDim.x * kBlock) {
         if (!read_start(a, t0)) continue;
         const uint32_t r = a.trav[t0].read_id - a.first_read_id;
-        uint32_t ser = kAcovNone;
-        if (a.set_graph[(size_t)r * kSharedSegs] != kSharedEmpty) {
-            uint32_t slot = (uint32_t)shared_hash(a, r) & a.tab_mask;
-            for (uint32_t i = 0; i <= a.tab_mask; i++, slot = (slot + 1) & a.tab_mask) {
-                const uint32_t cur = a.tab_rep[slot];
-                if (cur == kSharedEmpty) break;        // (insert put every row in: never met)
-                if (cur == r || same_set(a, cur, r)) { ser = tab_ser[slot]; break; }
-            }
-        }
-        read_ser[r] = ser;
+        read_ser[r] = acov_row_serial(a, tab_ser, r);
     }
+}
+
+// the mates' sets intersect: some graph both have records in, with a path in both ORs (what shared_gather_paired_kernel calls joined)
+__device__ __forceinline__ bool frag_joined(const SharedArgs &a, uint32_t t0, uint32_t tm, uint32_t t1)
+{
+    for (uint32_t sa = t0, sb = tm; sa < tm && sb < t1;) {
+        const uint32_t ga = a.trav[sa].graph_id, gb = a.trav[sb].graph_id;
+        if (ga < gb) { sa = seg_end(a, sa, tm); continue; }
+        if (gb < ga) { sb = seg_end(a, sb, t1); continue; }
+        const uint32_t ea = seg_end(a, sa, tm), eb = seg_end(a, sb, t1);
+        for (uint32_t w = 0; w < a.pw; w++)
+            if (seg_or(a, sa, ea, w) & seg_or(a, sb, eb, w)) return true;
+        sa = ea; sb = eb;
+    }
+    return false;
+}
+
+// one thread per fragment start.  Joined: both mates get the serial of the unit row (the even mate's) and the span of the other's
+// records; a joined unit on the slow path leaves kAcovNone to both, and the host counts the fragment.  Split or single: every mate with
+// records as acov_serial_kernel has it, its row being its own.
+__global__ __launch_bounds__(kBlock) void acov_serial_paired_kernel(SharedArgs a, const uint32_t *tab_ser, uint32_t *read_ser, uint2 *read_mate,
+                                                                    unsigned long long *pstats)
+{
+    if (!shared_live(a)) return;
+    const uint32_t n = min(a.ctr->n_trav, a.cap);
+    uint32_t joined = 0;
+    for (uint32_t t0 = blockIdx.x * kBlock + threadIdx.x; t0 < n; t0 += gridDim.x * kBlock) {
+        if (!frag_start(a, t0)) continue;
+        uint32_t tm, t1;
+        frag_span(a, t0, n, tm, t1);
+        const uint32_t r0 = (a.trav[t0].read_id - a.first_read_id) & ~1u;
+        if (tm > t0 && t1 > tm && frag_joined(a, t0, tm, t1)) {
+            read_ser[r0] = read_ser[r0 + 1] = acov_row_serial(a, tab_ser, r0);
+            read_mate[r0] = make_uint2(tm, t1);
+            read_mate[r0 + 1] = make_uint2(t0, tm);
+            joined += 2;
+            continue;
+        }
+        if (tm > t0) { read_ser[r0] = acov_row_serial(a, tab_ser, r0); read_mate[r0] = make_uint2(0, 0); }
+        if (t1 > tm) { read_ser[r0 + 1] = acov_row_serial(a, tab_ser, r0 + 1); read_mate[r0 + 1] = make_uint2(0, 0); }
+    }
+    for (int o = 32; o > 0; o >>= 1) joined += __shfl_down(joined, o, 64);
+    if ((threadIdx.x & 63) == 0 && joined) atomicAdd(pstats + 1, (unsigned long long)joined);
 }
 
 // one lane per traversal, a wavefront over 64 neighbouring ones; step k handles the k-th record (path of the path set, in the
 // order of the first node's list) of every lane that has one
-template <bool kAdd>
+template <bool kAdd, bool kPaired>
 __global__ __launch_bounds__(kBlock) void acov_count_kernel(AcovArgs a, AcovTable t)
 {
     if (a.ctr->flags & kCovSkipFlags) return;
     if (kAdd && a.state[0]) return;
     const uint32_t n = min(a.ctr->n_trav, a.cap), lane = threadIdx.x & 63;
+    uint32_t left = 0;                             // kPaired: records this lane left out
     for (uint32_t tb = blockIdx.x * kBlock + (threadIdx.x & ~63u); tb < n; tb += gridDim.x * kBlock) {
         if (!kAdd && __hip_atomic_load(a.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;     // the table is full: collect grows it and claims again
         const uint32_t tv = tb + lane;
         groot_trav tr{};
         uint32_t ser = kAcovNone, j = 0, j1 = 0, g0 = 0;
-        uint64_t m = 0;
+        uint32_t mf = 0, me = 0, fword = ~0u;      // kPaired: the mate's records [mf, me) of a joined read; the word of their OR in `fw`
+        uint64_t m = 0, fw = 0;
         if (tv < n) {
             tr = a.trav[tv];
             const uint32_t r = tr.read_id - a.first_read_id;
@@ -141,6 +202,7 @@ __global__ __launch_bounds__(kBlock) void acov_count_kernel(AcovArgs a, AcovTabl
                 g0 = a.graph_path_off[tr.graph_id];
                 j = a.node_np_off[tr.node];
                 j1 = a.node_np_off[tr.node + 1];
+                if (kPaired) { const uint2 mt = a.read_mate[r]; mf = mt.x; me = mt.y; }
             }
         }
         const uint64_t *mk = a.mask + (size_t)tv * a.pw;
@@ -154,6 +216,15 @@ __global__ __launch_bounds__(kBlock) void acov_count_kernel(AcovArgs a, AcovTabl
                 if (gp >= a.n_paths) continue;
                 const uint64_t len = a.path_len[gp], pos = (uint64_t)e.y + tr.offset;
                 if (len == 0 || pos > 0xFFFFFFFEull) continue;      // (no such path / Pos: never met; nothing a u32 pair could hold)
+                if (kPaired && me > mf) {          // a joined read: the path must be in the mate's set too
+                    if (fword != (e.x >> 6)) {
+                        fword = e.x >> 6;
+                        fw = 0;
+                        for (uint32_t u = mf; u < me; u++)
+                            if (a.trav[u].graph_id == tr.graph_id) fw |= a.mask[(size_t)u * a.pw + fword];
+                    }
+                    if (!((fw >> (e.x & 63)) & 1ull)) { left += kAdd; continue; }
+                }
                 const uint64_t last = min(pos + m, len - 1);
                 k0 = ((unsigned long long)(ser + 1u) << 32) | gp;
                 k1 = ((unsigned long long)pos << 32) | last;
@@ -177,6 +248,10 @@ __global__ __launch_bounds__(kBlock) void acov_count_kernel(AcovArgs a, AcovTabl
                 }
             }
         }
+    }
+    if (kAdd && kPaired) {
+        for (int o = 32; o > 0; o >>= 1) left += __shfl_down(left, o, 64);
+        if (lane == 0 && left) atomicAdd(a.pstats, (unsigned long long)left);
     }
 }
 

@@ -83,6 +83,7 @@ def lib():
         _ffi.rarefy_hip_prototypes(L)
         _ffi.gap_ec_prototypes(L)
         _ffi.gap_acov_prototypes(L)
+        _ffi.acov_pairs_prototypes(L)
         _lib = L
     return _lib
 
@@ -697,6 +698,20 @@ class Aligner:
         v = (C.c_uint64 * len(_ffi.GAP_ACOV_STATS))()
         self._check(lib().groot_hip_gap_acov_stats(self._h, v))
         return dict(zip(_ffi.GAP_ACOV_STATS, (int(x) for x in v)))
+
+    # ---- assigned coverage over fragments (groot_hip_acov_pairs_*) ------------------------------------------
+    def acov_pairs_enable(self, on=True):
+        """assigned coverage with paired-end units: switches on whichever of equivalence classes, assigned coverage and pairing is off,
+        and the rule that a record of a joined fragment counts on the paths of the fragment's set only (include/groot_hip.h, "assigned
+        coverage over fragments").  Off: the rule and assigned coverage go, equivalence classes and pairing stay.  Only while nothing is
+        in flight."""
+        self._check(lib().groot_hip_acov_pairs_enable(self._h, C.c_int(1 if on else 0)))
+
+    def acov_pairs_stats(self):
+        """groot_hip_acov_pairs_stats: {"records", "left_out", "joined_reads", "slow_fragments"}; zeros while off"""
+        v = (C.c_uint64 * len(_ffi.ACOV_PAIRS_STATS))()
+        self._check(lib().groot_hip_acov_pairs_stats(self._h, v))
+        return dict(zip(_ffi.ACOV_PAIRS_STATS, (int(x) for x in v)))
 
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):

@@ -366,7 +366,7 @@ int groot_hip_ec_stats(groot_ctx *ctx, uint64_t *reads, uint64_t *distinct, uint
  * the EC table, path, Pos, last), 16 bytes a key and a u64 count, that grows as it fills (a batch whose keys found no room adds
  * nothing and is counted again at collect, after the growth: no count is lost or doubled).  Reads in more than 4 graphs are grouped
  * on the host at collect, as their ECs are.  Counted once exactly as the other counters are.  Not with pairing (GROOT_E_UNSUPPORTED,
- * from whichever of the two enables comes second).  Off by default: then nothing is launched and no device memory is taken. */
+ * from whichever of the two enables comes second) but through groot_hip_acov_pairs_enable, below.  Off by default: then nothing is launched and no device memory is taken. */
 /* Switch on (an empty table of 2^20 slots, 24 MB; equivalence classes are switched on if they are off, and stay on) or off (freed;
  * groot_hip_ec_enable(ctx, 0) switches it off too).  Only while nothing is in flight. */
 int groot_hip_acov_enable(groot_ctx *ctx, int on);
@@ -456,6 +456,44 @@ int groot_hip_pairs_enable(groot_ctx *ctx, int on);
  * exactly as the counters are.  joined + 2 split + single = the `reads` of groot_hip_shared_stats = the `reads` of groot_hip_ec_stats.
  * Waits for everything in flight.  GROOT_E_STATE when pairing is off. */
 int groot_hip_pairs_stats(groot_ctx *ctx, uint64_t *joined, uint64_t *split, uint64_t *single);
+
+/* ---- assigned coverage over fragments ------------------------------------------------------------------------------------
+ * `align --calls --callsPaired`: the pileup of --calls with paired-end units.  The rule (README.md, DESIGN.md 24 and the tests quote it):
+ *
+ *   S(r), fragments, A = S(r_2i), B = S(r_2i+1), joined / split / single / none, units, ECs over units, canonical order, alpha, w(e,p):
+ *   exactly as in "paired-end reads"  and "assigned coverage" (DESIGN 13).
+ *   U(r), the UNIT SET of a read r with records:   A n B  when r's fragment is joined (both mates get the same set);
+ *                                                  S(r)   when it is split or single.
+ *   A record of read r on path p COUNTS when p is in U(r); it is then a record of the pileup under e = EC of U(r), covering [Pos, last],
+ *   last = min(Pos + M, path_len(p) - 1), M the record's own M op (its own mate's length less its clips): the interval of DESIGN 13, unchanged.
+ *   A record of a joined fragment on a path outside A n B is LEFT OUT: the unit the EM counted has no posterior there (w(e,p) is defined for
+ *   p in e only), so its weight is zero.  Both mates' records count, each as one record; every strand, primary and secondary, as in DESIGN 13.
+ *   The assigned-coverage table of a run with the feature on is the multiset of counting records grouped by (e, p, Pos, last).
+ *   d_e[x], D_p[x], depth, breadth, cigar, called, --callSupport's and --rarefy's columns: the existing host and device functions on that
+ *   table and those ECs, unchanged.  A pass that collect redoes counts once; a batch under kCovSkipFlags counts nothing.
+ *   The table depends on the reads, their pairing and the index alone: not on batch size, pipeline depth, align stage, --ctxPerGpu or --gpus.
+ *
+ * So with split and single fragments only the table is the unpaired run's, and fragments (r, r) give the unpaired run's ECs with every n
+ * doubled.  On the device (kernels_acov.hpp): ec_merge_kernel<true> leaves the units' serials, acov_serial_paired_kernel (a thread per
+ * fragment) hands both mates of a joined fragment the unit's serial and each the span of the other's records, 8 bytes per read in a
+ * buffer of the batch's slot, and acov_count_kernel<.., true> counts a record on p only when a record of the mate in the same graph
+ * holds p too.  Joined fragments whose set spans more than 4 graphs are folded on the host at collect, as their ECs are. */
+typedef struct groot_acov_pairs_stats {
+    uint64_t records;         /* records that counted since enable / groot_hip_acov_reset, device and host: the sum of n of the table */
+    uint64_t left_out;        /* records left out under the rule (a joined fragment's, on a path outside A n B), device and host */
+    uint64_t joined_reads;    /* reads of joined fragments (two per fragment), whichever path their unit took */
+    uint64_t slow_fragments;  /* joined fragments folded on the host (their set in more than 4 graphs, or in more than one under GROOT_TEST_SHARED_SLOW) */
+} groot_acov_pairs_stats;
+/* on != 0: puts the ctx into "assigned coverage over fragments" -- switches on whichever of equivalence classes, assigned coverage and
+ * pairing is off, and the rule above; the one way in which assigned coverage and pairing run together (groot_hip_acov_enable with
+ * pairing on, and groot_hip_pairs_enable(1) with assigned coverage on and the rule off, keep refusing).  GROOT_E_UNSUPPORTED while
+ * assignment or the rescued reads in the classes (groot_hip_rescue_ec_enable and everything built on it) are on.  on == 0: the rule and
+ * assigned coverage go, equivalence classes and pairing stay; groot_hip_acov_enable(ctx, 0) and groot_hip_pairs_enable(ctx, 0) while the
+ * rule is on do the same (the latter switches pairing off too).  Only while nothing is in flight (GROOT_E_STATE).
+ * groot_hip_acov_export / _reset / _stats keep their meaning; groot_hip_acov_reset zeroes the stats below. */
+int groot_hip_acov_pairs_enable(groot_ctx *ctx, int on);
+/* The four counts; zeros while the rule is off.  Waits for everything in flight. */
+int groot_hip_acov_pairs_stats(groot_ctx *ctx, groot_acov_pairs_stats *out);
 
 /* ---- mismatch rescue of unaligned reads ---------------------------------------------------------------------------------
  * The aligner is exact-match (AlignRead): a read with one sequencing error, or across the one SNP by which a sample's allele differs
