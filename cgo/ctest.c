@@ -224,6 +224,16 @@ int main(int argc, char **argv)
     if (groot_hip_pairs_stats(ctxs[0], &pj, &ps, &po) || pj || ps || po) DIE("groot_hip_acov_pairs_enable did not switch pairing on");
     if (groot_hip_acov_pairs_enable(ctxs[0], 0)) DIE("groot_hip_acov_pairs_enable(0): %s", groot_hip_last_error(ctxs[0]));
     if (groot_hip_pairs_stats(ctxs[0], &pj, &ps, &po)) DIE("pairing went off with the rule");
+    /* RescuePairsEnable / RescuePairsStats: the rescued mates in paired-end units need mismatch rescue, which this run never switched on --
+     * the enable is refused, switching the rule off while it is off is a no-op that leaves pairing on, and the stats stay zero */
+    groot_rescue_pairs_stats rps;
+    if (groot_hip_rescue_pairs_enable(ctxs[0], 1) != GROOT_E_STATE) DIE("groot_hip_rescue_pairs_enable without mismatch rescue was not refused");
+    if (groot_hip_rescue_pairs_enable(ctxs[0], 0)) DIE("groot_hip_rescue_pairs_enable(0): %s", groot_hip_last_error(ctxs[0]));
+    if (groot_hip_pairs_stats(ctxs[0], &pj, &ps, &po)) DIE("pairing went off with groot_hip_rescue_pairs_enable(0)");
+    if (groot_hip_rescue_pairs_stats(ctxs[0], &rps)) DIE("groot_hip_rescue_pairs_stats: %s", groot_hip_last_error(ctxs[0]));
+    if (rps.exact_rescued_joined || rps.exact_rescued_split || rps.rescued_rescued_joined || rps.rescued_rescued_split || rps.single_exact || rps.single_rescued ||
+        rps.rescued_mates || rps.bitmap_units || rps.launches)
+        DIE("groot_hip_rescue_pairs_stats: counts while the feature is off");
     for (int d = 0; d < n_ctx; d++) groot_hip_close(ctxs[d]);
     groot_index_free(idx);
     return 0;

@@ -481,6 +481,37 @@ func (c *Ctx) AcovPairsStatsGet() (AcovPairsStats, error) {
 	return AcovPairsStats{uint64(st.records), uint64(st.left_out), uint64(st.joined_reads), uint64(st.slow_fragments)}, nil
 }
 
+// RescuePairsStats mirrors groot_rescue_pairs_stats
+type RescuePairsStats struct {
+	ExactRescuedJoined, ExactRescuedSplit, RescuedRescuedJoined, RescuedRescuedSplit uint64
+	SingleExact, SingleRescued, RescuedMates, BitmapUnits, Launches                 uint64
+}
+
+// RescuePairsEnable puts the ctx into rescued mates in paired-end units (include/groot_hip.h, "rescued mates in paired-end units"): it
+// switches on whichever of equivalence classes, pairing and the rescued reads in the classes is off, and a fragment's unit is then made of
+// each mate's records or, for a mate mismatch rescue places, of its rescued set.  Needs RescueEnable first.  Off: the rule and the rescued
+// classes go, the classes and pairing stay.  Only while nothing is in flight.
+func (c *Ctx) RescuePairsEnable(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.groot_hip_rescue_pairs_enable(c.h, v); rc != 0 {
+		return c.err("groot_hip_rescue_pairs_enable")
+	}
+	return nil
+}
+
+// RescuePairsStatsGet returns the fragments with a rescued or a lone mate by kind since RescuePairsEnable or EcReset (waits for everything in flight)
+func (c *Ctx) RescuePairsStatsGet() (RescuePairsStats, error) {
+	var st C.groot_rescue_pairs_stats
+	if rc := C.groot_hip_rescue_pairs_stats(c.h, &st); rc != 0 {
+		return RescuePairsStats{}, c.err("groot_hip_rescue_pairs_stats")
+	}
+	return RescuePairsStats{uint64(st.exact_rescued_joined), uint64(st.exact_rescued_split), uint64(st.rescued_rescued_joined), uint64(st.rescued_rescued_split),
+		uint64(st.single_exact), uint64(st.single_rescued), uint64(st.rescued_mates), uint64(st.bitmap_units), uint64(st.launches)}, nil
+}
+
 func (c *Ctx) err(what string) error {
 	return fmt.Errorf("%s: %s", what, C.GoString(C.groot_hip_last_error(c.h)))
 }

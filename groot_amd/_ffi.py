@@ -126,6 +126,18 @@ def acov_pairs_prototypes(L):
     L.groot_hip_acov_pairs_enable.restype = L.groot_hip_acov_pairs_stats.restype = C.c_int
 
 
+# ---- rescued mates in paired-end units (groot_hip.h) ----
+RESCUE_PAIRS_STATS = ("exact_rescued_joined", "exact_rescued_split", "rescued_rescued_joined", "rescued_rescued_split", "single_exact", "single_rescued",
+                      "rescued_mates", "bitmap_units", "launches")   # groot_rescue_pairs_stats, nine uint64
+
+
+def rescue_pairs_prototypes(L):
+    """argtypes of groot_hip_rescue_pairs_enable / groot_hip_rescue_pairs_stats (libgroot_hip.so)"""
+    L.groot_hip_rescue_pairs_enable.argtypes = [C.c_void_p, C.c_int]
+    L.groot_hip_rescue_pairs_stats.argtypes = [C.c_void_p, u64p]
+    L.groot_hip_rescue_pairs_enable.restype = L.groot_hip_rescue_pairs_stats.restype = C.c_int
+
+
 def opt_ptr(arr, ctype):
     """as_ptr, or a NULL pointer for None"""
     return None if arr is None else as_ptr(arr, ctype)

@@ -28,6 +28,7 @@ struct Harvested {                           // the sums over every harvest so f
     groot_gap_ec_stats gap_ec{};                             // --abundanceGapped: the gap-placed reads in the classes (groot_hip_gap_ec_*)
     groot_rescue_acov_stats rescue_acov{};                   // --callsRescued: their records in the pileup (groot_hip_rescue_acov_*)
     groot_gap_acov_stats gap_acov{};                         // --callsGapped: the gap-placed reads' records in the pileup (groot_hip_gap_acov_*)
+    groot_rescue_pairs_stats rescue_pairs{};                 // --rescuedPaired: the fragments with a rescued or a lone mate, by kind (groot_hip_rescue_pairs_*)
     groot_acov_pairs_stats acov_pairs{};                     // --callsPaired: the records piled up and left out under the rule for fragments (groot_hip_acov_pairs_*)
 };
 
@@ -54,7 +55,7 @@ public:
     {
         if (plan_.assign)
             if (int rc = groot_hip_assign_enable(ctx, on ? assign_alpha_.data() : nullptr, v_.n_paths, a_.min_posterior)) return rc;
-        if (plan_.frags && !(plan_.calls_paired && on))      // (--callsPaired: pairing comes on with assigned coverage, below)
+        if (plan_.frags && !((plan_.calls_paired || plan_.rescued_paired) && on))      // (--callsPaired: pairing comes on with assigned coverage, below; --rescuedPaired: with the rescued classes)
             if (int rc = groot_hip_pairs_enable(ctx, on)) return rc;
         if (plan_.coverage)
             if (int rc = groot_hip_coverage_enable(ctx, on)) return rc;
@@ -76,8 +77,8 @@ public:
             if (int rc = groot_hip_rescue_acov_enable(ctx, 1, (uint64_t)a_.call_slots)) return rc;
             return plan_.calls_gapped ? groot_hip_gap_acov_enable(ctx, 1) : 0;      // (and this one the gap-placed reads in the classes: --abundanceGapped beside --calls)
         }
-        if (plan_.ab_rescued && on)
-            if (int rc = groot_hip_rescue_ec_enable(ctx, 1)) return rc;
+        if (plan_.ab_rescued && on)         // (--rescuedPaired: the rule brings the rescued reads in the classes and pairing with it)
+            if (int rc = plan_.rescued_paired ? groot_hip_rescue_pairs_enable(ctx, 1) : groot_hip_rescue_ec_enable(ctx, 1)) return rc;
         return plan_.ab_gapped && on ? groot_hip_gap_ec_enable(ctx, 1) : 0;   // behind gapped rescue and the rescued reads in the classes (off: it goes with either)
     }
 
@@ -132,6 +133,16 @@ public:
             if (int rc = groot_hip_rescue_ec_stats(ctx, &st)) return rc;
             std::lock_guard<std::mutex> lk(mu_);
             h_.rescue_ec.reads += st.reads; h_.rescue_ec.slow_reads += st.slow_reads; h_.rescue_ec.launches += st.launches; h_.rescue_ec.rows = st.rows;
+        }
+        if (plan_.rescued_paired) {
+            groot_rescue_pairs_stats st{};
+            if (int rc = groot_hip_rescue_pairs_stats(ctx, &st)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            groot_rescue_pairs_stats &t = h_.rescue_pairs;
+            t.exact_rescued_joined += st.exact_rescued_joined; t.exact_rescued_split += st.exact_rescued_split;
+            t.rescued_rescued_joined += st.rescued_rescued_joined; t.rescued_rescued_split += st.rescued_rescued_split;
+            t.single_exact += st.single_exact; t.single_rescued += st.single_rescued;
+            t.rescued_mates += st.rescued_mates; t.bitmap_units += st.bitmap_units; t.launches += st.launches;
         }
         if (plan_.ab_gapped) {
             groot_gap_ec_stats st{};

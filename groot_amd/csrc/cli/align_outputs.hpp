@@ -98,7 +98,14 @@ Bootstrap write_abundance(const Args &a, const AlignPlan &plan, const groot_inde
         die("%s", groot_host_last_error());
     logf("\tabundance: %llu equivalence class(es), EM of %u iteration(s) in %.3f s, %llu ARG(s) with at least %g reads written to %s",
          (unsigned long long)h.ec_cnt.size(), iters, seconds_since(t_em), (unsigned long long)n_lines, a.abundance_min, a.abundance_out.c_str());
-    if (plan.ab_rescued) {
+    if (plan.rescued_paired) {
+        const groot_rescue_pairs_stats &r = h.rescue_pairs;
+        logf("\tabundance: %llu rescued mate(s) counted in their fragments, placed with up to %ld substitution(s): exact + rescued %llu joined, %llu split; "
+             "rescued + rescued %llu joined, %llu split; one mate alone %llu exact, %llu rescued; %llu unit(s) on ARGs of more than 4 graphs",
+             (unsigned long long)r.rescued_mates, a.rescue, (unsigned long long)r.exact_rescued_joined, (unsigned long long)r.exact_rescued_split,
+             (unsigned long long)r.rescued_rescued_joined, (unsigned long long)r.rescued_rescued_split, (unsigned long long)r.single_exact,
+             (unsigned long long)r.single_rescued, (unsigned long long)r.bitmap_units);
+    } else if (plan.ab_rescued) {
         uint64_t units = 0;
         for (uint64_t c : h.ec_cnt) units += c;
         logf("\tabundance: %llu rescued read(s) counted in the equivalence classes beside %llu read(s) with an exact alignment, placed with up to %ld substitution(s); "

@@ -74,6 +74,7 @@ struct Args {
     bool rescue_given = false, variant_min_given = false;
     bool abundance_rescued = false;          // --abundanceRescued: the reads mismatch rescue places join the equivalence classes of --abundance
     bool abundance_gapped = false;           // --abundanceGapped: and so do the reads gapped rescue (--indels) places
+    bool rescued_paired = false;             // --rescuedPaired: with --abundanceRescued and --paired / --interleaved, a rescued mate joins its fragment's unit with its rescued set
     bool calls_paired = false;               // --callsPaired: with --calls and --paired / --interleaved, the pileup counts a joined fragment's records on the paths of its set only
     bool calls_gapped = false;               // --callsGapped: with --calls, --callsRescued and --abundanceGapped, the gap-placed reads' placements join the pileup too
     bool calls_rescued = false;              // --callsRescued: with --calls and --abundanceRescued, the rescued reads' placements join the pileup

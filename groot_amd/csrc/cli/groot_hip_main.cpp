@@ -39,6 +39,7 @@ void usage()
             "                  [--abundance a.tsv --abundanceRescued --indels i.tsv --abundanceGapped [--rescueGap 3]]\n"
             "                  [--abundance a.tsv --abundanceRescued --indels i.tsv --abundanceGapped --calls c.tsv --callsRescued --callsGapped]\n"
             "                  [(--paired | --interleaved) --abundance a.tsv --calls c.tsv --callsPaired]\n"
+            "                  [(--paired | --interleaved) --abundance a.tsv --abundanceRescued --rescuedPaired]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
@@ -93,7 +94,10 @@ void usage()
             "                   one stream.  --sharedReads, --abundance and --bootstraps then count fragments, not mates: the mates' path sets intersected,\n"
             "                   or both sets when they do not intersect; the BAM holds the mates as ordinary records in interleaved order.  --calls only\n"
             "                   beside --callsPaired: both mates' records are piled up under the fragment's class, and a record of a fragment whose mates' sets\n"
-            "                   intersect counts on the ARGs of the intersection only -- elsewhere the fragment has no posterior.  Not with --callsRescued)\n"
+            "                   intersect counts on the ARGs of the intersection only -- elsewhere the fragment has no posterior.  Not with --callsRescued.\n"
+            "                   --abundanceRescued only beside --rescuedPaired: a mate without an exact alignment that mismatch rescue places counts in its\n"
+            "                   fragment with the ARGs it was placed on, so an exact mate narrows a rescued one and two rescued mates still make a fragment.\n"
+            "                   Not with --sharedReads, --calls, --abundanceGapped or --assignFrom)\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
             "                  [--bootstraps B [--bootSeed 1]] [-p N] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
@@ -174,6 +178,7 @@ Args parse(int argc, char **argv)
         else if (a.cmd == "align" && f == "--callsRescued") a.calls_rescued = true;
         else if (a.cmd == "align" && f == "--callsGapped") a.calls_gapped = true;
         else if (a.cmd == "align" && f == "--callsPaired") a.calls_paired = true;
+        else if (a.cmd == "align" && f == "--rescuedPaired") a.rescued_paired = true;
         else if (a.cmd == "align" && f == "--callSlots") {
             const std::string t = v();
             char *end = nullptr;

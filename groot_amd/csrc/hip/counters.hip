@@ -391,7 +391,8 @@ int counters_launch(groot_ctx *c, Slot *s)
         sa.tab_mask = tab - 1;
         const dim3 gt(grid_for(tab));      // the merge and the expansion: one item per slot of that part
         const bool paired = k.pairs_on;
-        if (paired) hipLaunchKernelGGL(shared_gather_paired_kernel, g, dim3(kBlock), 0, c->tstream, sa);
+        if (paired && k.rp_on) hipLaunchKernelGGL(shared_gather_paired_kernel<true>, g, dim3(kBlock), 0, c->tstream, sa);     // (rescue_launch makes the units it defers)
+        else if (paired) hipLaunchKernelGGL(shared_gather_paired_kernel<false>, g, dim3(kBlock), 0, c->tstream, sa);
         else hipLaunchKernelGGL(shared_gather_kernel, g, dim3(kBlock), 0, c->tstream, sa);
         hipLaunchKernelGGL(shared_insert_kernel, g, dim3(kBlock), 0, c->tstream, sa);
         if (k.sh_on && paired) hipLaunchKernelGGL(shared_slow_kernel<true>, dim3(256), dim3(kBlock), 0, c->tstream, sa);
@@ -400,6 +401,16 @@ int counters_launch(groot_ctx *c, Slot *s)
             if (int rc = ec_reserve(c, s)) return rc;
             HIP_TRY(c, s->ct.d_ec_slow.reserve(1 + (paired ? 3 : 2) * (size_t)c->prm.max_batch_reads));
             HIP_TRY(c, s->ct.h_status.reserve(1));
+        }
+        if (k.rp_on) {           // rescued mates in paired-end units: the merge and the expansion wait for the units rescue_launch makes -- all of a batch or none
+            HIP_TRY(c, hipGetLastError());
+            if (int rc = rescue_launch(c, s, sa, tab)) return rc;
+            hipLaunchKernelGGL(ec_merge_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p, (uint32_t *)nullptr);
+            hipLaunchKernelGGL(shared_expand_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, tab);
+            HIP_TRY(c, hipGetLastError());
+            return GROOT_OK;
+        }
+        if (k.ec_on) {
             uint32_t *tab_ser = k.acov_on ? k.acov_tab_ser.p : nullptr;     // (with pairing on: assigned coverage over fragments, the units' serials)
             if (paired) hipLaunchKernelGGL(ec_merge_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p, tab_ser);
             else hipLaunchKernelGGL(ec_merge_kernel<false>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p, tab_ser);
@@ -575,6 +586,9 @@ int groot_hip_shared_enable(groot_ctx *c, int on)
     }
     if (c->ct.sh_on) return GROOT_OK;
     if (c->ct.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "shared reads count S(r), which assignment collapses (groot_hip_assign_enable)");
+    if (c->ct.rp_on)
+        return fail(c, GROOT_E_UNSUPPORTED, "shared reads with rescued mates in paired-end units are not supported: the triangle has no rescued reads, and the "
+                    "fragments left to rescue would be missing from it (groot_hip_rescue_pairs_enable)");
     const uint64_t n_paths = c->ct.h_len.size(), tri = shared_tri_size(n_paths);
     if (tri * sizeof(uint64_t) > GROOT_SHARED_MAX_BYTES)
         return fail(c, GROOT_E_UNSUPPORTED, "shared reads: %llu paths need a %llu MiB pair table, above the bound of %llu MiB", (unsigned long long)n_paths,
@@ -1007,9 +1021,10 @@ int groot_hip_pairs_enable(groot_ctx *c, int on)
     if (!idle(c)) return fail(c, GROOT_E_STATE, "pairing can only be switched while nothing is in flight");
     if (on && c->ct.acov_on && !c->ct.acp_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assigned coverage are not supported");
     if (on && c->ct.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with assignment are not supported (groot_hip_assign_enable)");
-    if (on && c->ct.rec_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with rescued reads in the equivalence classes are not supported: mates are rescued one by one (groot_hip_rescue_ec_enable)");
+    if (on && c->ct.rec_on && !c->ct.rp_on) return fail(c, GROOT_E_UNSUPPORTED, "paired-end units with rescued reads in the equivalence classes are not supported: mates are rescued one by one (groot_hip_rescue_ec_enable)");
     if (!on && c->ct.acp_on)              // (assigned coverage over fragments has no meaning without them: the rule and the table go)
         if (int rc = groot_hip_acov_enable(c, 0)) return rc;
+    if (!on && c->ct.rp_on) rescue_ec_release(c->ct);     // (the rescued mates' rule has no meaning without fragments: it and the rescued classes go)
     c->ct.pairs_on = on != 0;
     if (c->ct.sh_on || c->ct.ec_on) {     // (else there is nothing to zero: sh_common_alloc zeroes the counts when either comes on)
         HIP_TRY(c, hipSetDevice(c->device));

@@ -264,6 +264,13 @@ struct Counters {
     DevBuf<unsigned long long> rec_stats;  // [kRescueEcStats]
     uint64_t rec_slow = 0;                 // slow rescued reads folded at collect since enable / groot_hip_ec_reset
     uint64_t rec_launches = 0;             // kernels launched for it since open, rescue_count_ec_kernel not among them (it counts as rescue's)
+    // rescued mates in paired-end units (groot_hip_rescue_pairs_*, kernels_rescue_pairs.hpp): the one state in which pairing and the rescued
+    // reads in the ECs are on together (rp_on implies both, and both imply rp_on).  The gather defers the fragments with records on one mate
+    // only, and three kernels behind rescue_count_ec_kernel make every unit that is not exact + exact.
+    bool rp_on = false;
+    DevBuf<uint8_t> rp_state;              // RescuePairArgs::state (tail stream: one batch at a time, as the candidates are)
+    DevBuf<unsigned long long> rp_stats;   // [2][kRescuePairStats] the totals, and the words of the batch in hand (added to the totals when its bitmaps found room)
+    uint64_t rp_launches = 0;              // the three kernels of kernels_rescue_pairs.hpp since open (stays put while it is off)
     // rescued reads in assigned coverage (groot_hip_rescue_acov_*, kernels_rescue_acov.hpp): needs mismatch rescue, equivalence classes and
     // assigned coverage on, and switches the rescued reads in the ECs on itself.  Every kept placement of a rescued read is a record of the
     // assigned-coverage table; those of the reads with a bitmap come back in a log and are folded on the host at collect.

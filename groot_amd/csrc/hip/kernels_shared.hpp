@@ -217,6 +217,10 @@ __device__ __forceinline__ void gather_read(const SharedArgs &a, uint32_t t0, ui
 // segments whose AND is all zero dropped -- so the row is a canonical key (graphs ascend, no segment is empty, kSharedEmpty ends it).
 // The first max_segs segments of the intersection are written as they are met; a fragment is a slow-path unit only when the
 // intersection itself has more, whatever the mates have alone.
+// kDefer (rescued mates in paired-end units: kernels_rescue_pairs.hpp): a fragment with records on one mate only makes no unit here and is
+// not counted -- that mate's row starts with kSharedEmpty, which shared_insert_kernel skips, and rescue_pair_kernel makes the unit once
+// the other mate's rescued set exists.  <false> is the kernel as it was, and the only one launched while that rule is off.
+template <bool kDefer>
 __global__ __launch_bounds__(kBlock) void shared_gather_paired_kernel(SharedArgs a)
 {
     if (!shared_live(a)) return;
@@ -228,6 +232,10 @@ __global__ __launch_bounds__(kBlock) void shared_gather_paired_kernel(SharedArgs
         frag_span(a, t0, n, tm, t1);
         const uint32_t r0 = (a.trav[t0].read_id - a.first_read_id) & ~1u;     // the even mate's row; r0 + 1 the odd mate's
         if (tm == t0 || t1 == tm) {     // "has records" is decided here, from the traversals: the other mate's row is stale and stays unread
+            if (kDefer) {
+                a.set_graph[(size_t)(tm == t0 ? r0 + 1 : r0) * kSharedSegs] = kSharedEmpty;
+                continue;
+            }
             gather_read(a, t0, t1, tm == t0 ? r0 + 1 : r0);
             single++; units++;
             continue;

@@ -35,6 +35,7 @@
 #include "kernels_gap.hpp"
 #include "kernels_rescue.hpp"
 #include "kernels_rescue_ec.hpp"
+#include "kernels_rescue_pairs.hpp"
 #include "kernels_rescue_acov.hpp"
 #include "kernels_rescue_rec.hpp"
 #include "kernels_gap_rec.hpp"
@@ -80,6 +81,9 @@ void rescue_ec_release(Counters &k)
     gec_release(k);                        // (the gap-placed reads' rows go through the rescued reads' table and merge)
     k.rec_path_bit.release(); k.rec_dstar.release(); k.rec_stats.release();
     k.rec_on = false; k.rec_rows = k.rec_bw = 0; k.rec_slow = 0;
+    // (and with it the rule that lets them stand beside pairing; pairing itself stays)
+    k.rp_state.release(); k.rp_stats.release();
+    k.rp_on = false;
     // (and with it the rescued reads in assigned coverage, which are keyed by these classes)
     k.rac_cand_ser.release(); k.rac_stats.release();
     k.rac_on = false; k.rac_log_cap = 0; k.rac_host_records = 0;
@@ -318,6 +322,16 @@ static int rec_collect(groot_ctx *c, Slot *s, bool refetch)
     CounterStatus &h = *s->ct.h_status.p;
     if (refetch) HIP_TRY(c, hipMemcpy(&h.rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (!h.rec_slow) return GROOT_OK;
+    if (h.rec_slow > k.rec_rows && k.rp_on) {      // the batch fails alone: the device counted nothing of it (rescue_pair_insert_kernel), and the ctx goes on
+        if (s->status == GROOT_OK) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "rescued mates in paired-end units: a batch's units that fit no row need %u bitmaps, and there is room for %u "
+                     "(GROOT_TEST_RESCUE_EC_ROWS)", h.rec_slow, k.rec_rows);
+            s->status = GROOT_E_NOSPACE;
+            s->status_msg = buf;
+        }
+        return GROOT_OK;
+    }
     if (h.rec_slow > k.rec_rows)
         return fail(c, GROOT_E_NOSPACE, "rescued reads in the equivalence classes: a batch has %u rescued reads whose sets lie in more graphs than a row holds, and room for "
                     "the bitmaps of %u (GROOT_TEST_RESCUE_EC_ROWS)", h.rec_slow, k.rec_rows);
@@ -374,7 +388,9 @@ int rescue_launch(groot_ctx *c, Slot *s, const SharedArgs &sa, uint32_t tab)
     ra.tab_mask = (uint32_t)k.res_tab.n - 1u; ra.n_reads = s->n_reads; ra.max_mismatch = k.res_m;
     HIP_TRY(c, hipMemsetAsync(k.res_ncand.p, 0, sizeof(uint32_t), c->tstream));
     hipLaunchKernelGGL(rescue_pack_kernel, gr, blk, 0, c->tstream, ra);
-    if (k.rec_on) {          // (the rows and the per-batch table are free: shared_expand_kernel, launched by counters_launch ahead of this call on this stream, has cleared them)
+    if (k.rec_on) {          // (the rows of the candidates are free, and with the rule of the rescued mates off so is the per-batch table: shared_expand_kernel, launched by
+                             // counters_launch ahead of this call on this stream, has cleared it.  With that rule on the table still holds the units of the fragments with
+                             // records on both mates -- the merge waits behind this call -- and their rows are rows of reads with records, which no candidate shares)
         ra.path_bit = k.rec_path_bit.p; ra.set_graph = sa.set_graph; ra.set_mask = sa.set_mask; ra.dstar = k.rec_dstar.p;
         ra.pw = sa.pw; ra.max_segs = sa.max_segs;
     }
@@ -453,6 +469,20 @@ int rescue_launch(groot_ctx *c, Slot *s, const SharedArgs &sa, uint32_t tab)
         gaa.e.g = gra.g; gaa.e.s = sa; gaa.e.e = k.gec_e.p; gaa.e.bits = ea.bits; gaa.e.n_rslow = ea.n_slow; gaa.e.stats = k.gec_stats.p;
         gaa.e.rows = ea.rows; gaa.e.bw = ea.bw; gaa.e.n_gslow = s->ct.d_gec_slow.p;
     }
+    if (k.rp_on) {           // rescued mates in paired-end units: every unit that is not exact + exact, a thread per fragment (rac, gec and gac are off beside it)
+        RescuePairArgs pa{};
+        // (counters_launch has held the merge and the expansion back: the table still holds the exact + exact fragments' units, whose rows no
+        // candidate shares, and one merge behind this call folds every unit of the batch -- or none, when the bitmaps do not suffice)
+        pa.e = ea; pa.state = k.rp_state.p; pa.total = k.rp_stats.p; pa.stats = k.rp_stats.p + kRescuePairStats; pa.tab_size = tab;
+        HIP_TRY(c, hipMemsetAsync(k.rp_state.p, kRescueUnplaced, std::max<uint32_t>(s->n_reads, 1u), c->tstream));
+        HIP_TRY(c, hipMemsetAsync(pa.stats, 0, kRescuePairStats * sizeof(unsigned long long), c->tstream));
+        hipLaunchKernelGGL(rescue_pair_mark_kernel, gr, blk, 0, c->tstream, pa);
+        hipLaunchKernelGGL(rescue_pair_kernel, dim3(grid_for(s->n_reads / 2u)), blk, 0, c->tstream, pa);
+        hipLaunchKernelGGL(rescue_pair_insert_kernel, dim3(grid_for(std::max(s->n_reads, tab))), blk, 0, c->tstream, pa);
+        HIP_TRY(c, hipGetLastError());
+        k.rp_launches += 3;
+        return GROOT_OK;
+    }
     if (rac) hipLaunchKernelGGL(rescue_acov_slow_kernel, gr, blk, 0, c->tstream, aa);
     else hipLaunchKernelGGL(rescue_ec_slow_kernel, gr, blk, 0, c->tstream, ea);
     if (gac) hipLaunchKernelGGL(gap_acov_slow_kernel, gr, blk, 0, c->tstream, gaa);
@@ -519,6 +549,7 @@ int rescue_ec_reset(groot_ctx *c)
     Counters &k = c->ct;                   // (the rescued and the gap-placed reads are counted with the classes they are in)
     if (k.rec_on) HIP_TRY(c, hipMemset(k.rec_stats.p, 0, kRescueEcStats * sizeof(unsigned long long)));
     if (k.gec_on) HIP_TRY(c, hipMemset(k.gec_stats.p, 0, kGapEcStats * sizeof(unsigned long long)));
+    if (k.rp_on) HIP_TRY(c, hipMemset(k.rp_stats.p, 0, kRescuePairStats * sizeof(unsigned long long)));
     k.rec_slow = k.gec_slow = 0;           // (zero anyway while the part is off)
     return GROOT_OK;
 }
@@ -823,7 +854,7 @@ int groot_hip_rescue_ec_enable(groot_ctx *c, int on)
     }
     if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: mismatch rescue is off (groot_hip_rescue_enable)");
     if (!k.ec_on) return fail(c, GROOT_E_STATE, "rescued reads in the equivalence classes: equivalence classes are off (groot_hip_ec_enable)");
-    if (k.pairs_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with paired-end units are not supported: mates are rescued one by one");
+    if (k.pairs_on && !k.rp_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with paired-end units are not supported: mates are rescued one by one");
     if (k.acov_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued reads in the equivalence classes with assigned coverage are not supported: a rescued read has no record to weigh");
     return rec_alloc(c);
 }
@@ -885,6 +916,77 @@ int groot_hip_rescue_ec_stats(groot_ctx *c, groot_rescue_ec_stats *out)
     out->reads = st[0] + out->slow_reads;
     out->rows = c->ct.rec_on ? c->ct.rec_rows : 0;
     out->launches = c->ct.rec_launches;
+    if (c->ct.rp_on) {                     // the rescued mates that are in a unit, and those of them in a unit that took a bitmap
+        uint64_t pt[kRescuePairStats];
+        HIP_TRY(c, hipMemcpy(pt, c->ct.rp_stats.p, sizeof(pt), hipMemcpyDeviceToHost));
+        out->reads = pt[6];
+        out->slow_reads = pt[8];
+    }
+    return GROOT_OK;
+}
+
+// ---- rescued mates in paired-end units (kernels_rescue_pairs.hpp; the rule is in groot_hip.h) -----------------------------------
+int groot_hip_rescue_pairs_enable(groot_ctx *c, int on)
+{
+    if (int rc = switchable(c, "rescued mates in paired-end units")) return rc;
+    Counters &k = c->ct;
+    if (!on) {
+        if (k.rp_on) rescue_ec_release(k);       // (the rescued classes cannot stay beside pairing without the rule; the classes and pairing stay)
+        return GROOT_OK;
+    }
+    if (k.rp_on) return GROOT_OK;
+    if (k.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued mates in paired-end units count S(r), which assignment collapses (groot_hip_assign_enable)");
+    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued mates in paired-end units: mismatch rescue is off (groot_hip_rescue_enable)");
+    if (k.sh_on)
+        return fail(c, GROOT_E_UNSUPPORTED, "rescued mates in paired-end units with shared reads are not supported: the triangle has no rescued reads, and the "
+                    "fragments left to rescue would be missing from it (groot_hip_shared_enable)");
+    if (k.acp_on)
+        return fail(c, GROOT_E_UNSUPPORTED, "rescued mates in paired-end units with assigned coverage over fragments are not supported: a rescued mate has no "
+                    "record to weigh (groot_hip_acov_pairs_enable)");
+    if (k.acov_on)
+        return fail(c, GROOT_E_UNSUPPORTED, "rescued mates in paired-end units with assigned coverage are not supported: a rescued mate has no record to weigh "
+                    "(groot_hip_acov_enable)");
+    if (k.gec_on)
+        return fail(c, GROOT_E_UNSUPPORTED, "rescued mates in paired-end units with gap-placed reads in the equivalence classes are not supported: the fragment "
+                    "rule knows records and mismatch rescue's sets only (groot_hip_gap_ec_enable)");
+    // the enables of pairing and of the rescued classes refuse each other: each is made with the other one off
+    const bool was_pairs = k.pairs_on, was_ec = k.ec_on, was_rec = k.rec_on;
+    auto undo = [&](int rc) {
+        if (!was_rec) rescue_ec_release(k);
+        if (!was_ec) groot_hip_ec_enable(c, 0);
+        return rc;
+    };
+    k.pairs_on = false;
+    int rc = groot_hip_ec_enable(c, 1);
+    if (!rc) rc = groot_hip_rescue_ec_enable(c, 1);
+    k.pairs_on = was_pairs;
+    if (rc) return undo(rc);
+    hipError_t e = k.rp_state.alloc(std::max<uint32_t>(c->prm.max_batch_reads, 1u));
+    if (e == hipSuccess) e = k.rp_stats.alloc(2 * kRescuePairStats);        // (the totals, and the words of the batch in hand)
+    if (e == hipSuccess) e = hipMemset(k.rp_stats.p, 0, 2 * kRescuePairStats * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        k.rp_state.release(); k.rp_stats.release();
+        return undo(fail(c, GROOT_E_DEVICE, "rescued mates in paired-end units: %s", hipGetErrorString(e)));
+    }
+    k.rp_on = true;
+    if (!was_pairs)
+        if (int rc2 = groot_hip_pairs_enable(c, 1)) {      // (no state with the rule and the rescued classes on and pairing off is left behind)
+            if (was_rec) { k.rp_state.release(); k.rp_stats.release(); k.rp_on = false; }
+            return undo(rc2);
+        }
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_pairs_stats(groot_ctx *c, groot_rescue_pairs_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kRescuePairStats];
+    if (int rc = part_stats(c, c->ct.rp_on, c->ct.rp_stats, st)) return rc;
+    out->exact_rescued_joined = st[0]; out->exact_rescued_split = st[1];
+    out->rescued_rescued_joined = st[2]; out->rescued_rescued_split = st[3];
+    out->single_exact = st[4]; out->single_rescued = st[5];
+    out->rescued_mates = st[6]; out->bitmap_units = st[7];
+    out->launches = c->ct.rp_launches;
     return GROOT_OK;
 }
 
@@ -934,6 +1036,8 @@ int groot_hip_gap_ec_enable(groot_ctx *c, int on)
     }
     if (!k.gap_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: gapped rescue is off (groot_hip_gap_enable)");
     if (!k.rec_on) return fail(c, GROOT_E_STATE, "gap-placed reads in the equivalence classes: the rescued reads in the equivalence classes are off (groot_hip_rescue_ec_enable)");
+    if (k.rp_on) return fail(c, GROOT_E_UNSUPPORTED, "gap-placed reads in the equivalence classes with rescued mates in paired-end units are not supported: the fragment rule "
+                             "knows records and mismatch rescue's sets only (groot_hip_rescue_pairs_enable)");
     if (k.rac_on && !k.gac_on)             // (beside each other only through groot_hip_gap_acov_enable, which gives the pileup its rule)
         return fail(c, GROOT_E_UNSUPPORTED, "gap-placed reads in the equivalence classes with rescued reads in assigned coverage are not supported: the pileup has no "
                               "rule for a gapped record, and a DEL covers two intervals (groot_hip_rescue_acov_enable)");

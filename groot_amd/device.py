@@ -84,6 +84,7 @@ def lib():
         _ffi.gap_ec_prototypes(L)
         _ffi.gap_acov_prototypes(L)
         _ffi.acov_pairs_prototypes(L)
+        _ffi.rescue_pairs_prototypes(L)
         _lib = L
     return _lib
 
@@ -712,6 +713,20 @@ class Aligner:
         v = (C.c_uint64 * len(_ffi.ACOV_PAIRS_STATS))()
         self._check(lib().groot_hip_acov_pairs_stats(self._h, v))
         return dict(zip(_ffi.ACOV_PAIRS_STATS, (int(x) for x in v)))
+
+    # ---- rescued mates in paired-end units (groot_hip_rescue_pairs_*) ----------------------------------------
+    def rescue_pairs_enable(self, on=True):
+        """pairing with the rescued reads in the classes: switches on whichever of equivalence classes, pairing and the rescued reads in the
+        classes is off, and the rule that a fragment's unit is made of each mate's records or, for a mate mismatch rescue places, of its
+        rescued set (include/groot_hip.h, "rescued mates in paired-end units").  Needs rescue_enable first.  Off: the rule and the rescued
+        classes go, equivalence classes and pairing stay.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_rescue_pairs_enable(self._h, C.c_int(1 if on else 0)))
+
+    def rescue_pairs_stats(self):
+        """groot_hip_rescue_pairs_stats: _ffi.RESCUE_PAIRS_STATS as a dict; zeros while off, but for launches"""
+        v = (C.c_uint64 * len(_ffi.RESCUE_PAIRS_STATS))()
+        self._check(lib().groot_hip_rescue_pairs_stats(self._h, v))
+        return dict(zip(_ffi.RESCUE_PAIRS_STATS, (int(x) for x in v)))
 
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):

@@ -624,8 +624,11 @@ typedef struct groot_rescue_ec_stats {
     uint64_t rows;        /* bitmaps per batch: min(max_batch_reads, GROOT_RESCUE_EC_BYTES / (8 ceil(n_paths / 64))), or GROOT_TEST_RESCUE_EC_ROWS; 0 while off */
     uint64_t launches;    /* kernels launched for it since open, whether it is on now or not (rescue_count_ec_kernel counts in groot_rescue_stats.launches) */
 } groot_rescue_ec_stats;
+/* While the rule of "rescued mates in paired-end units" (below) is on, the reads are mates of fragments: `reads` is the rescued mates in a unit
+ * (groot_rescue_pairs_stats.rescued_mates), `slow_reads` those of them in a unit that took a bitmap, and `launches` stays put -- the kernels
+ * that run in its place count in groot_rescue_pairs_stats.launches. */
 /* on != 0: on.  Needs mismatch rescue and equivalence classes on (GROOT_E_STATE otherwise), and nothing in flight (GROOT_E_STATE).
- * GROOT_E_UNSUPPORTED beside pairing or assigned coverage, whichever is enabled second.  Switching mismatch rescue or the equivalence
+ * GROOT_E_UNSUPPORTED beside pairing (the two run together through groot_hip_rescue_pairs_enable alone: below) or assigned coverage, whichever is enabled second.  Switching mismatch rescue or the equivalence
  * classes off switches it off too.  groot_hip_rescue_enable with another M and groot_hip_rescue_reset leave the classes alone;
  * groot_hip_ec_reset zeroes them, the rescued reads in them and these stats.  A batch with more rescued reads in more than 4 graphs than
  * `rows` fails at collect with GROOT_E_NOSPACE (the message names GROOT_TEST_RESCUE_EC_ROWS): no read is dropped silently.
@@ -634,6 +637,54 @@ typedef struct groot_rescue_ec_stats {
 int groot_hip_rescue_ec_enable(groot_ctx *ctx, int on);
 /* Waits for everything in flight; zeros while off, but for launches. */
 int groot_hip_rescue_ec_stats(groot_ctx *ctx, groot_rescue_ec_stats *out);
+
+/* ---- rescued mates in paired-end units -------------------------------------------------------------------------------------
+ * Pairing makes the classes count fragments, and the rescued reads in the classes put the reads with a sequencing error back; the two
+ * enables refuse each other, because a rescued mate's set exists only behind the kernels that make the fragments' units.  With this rule
+ * on they run together (kernels_rescue_pairs.hpp).  The rule:
+ *
+ *   S(r), R(r), S+(r), candidate, rescued, d*, kept placement: exactly as in "mismatch rescue" and "rescued reads in the equivalence classes".
+ *   Fragments, joined / split / single / none, units, ECs over units: exactly as in "paired-end reads" (DESIGN §12), with
+ *       A = S+(r_2i),  B = S+(r_2i+1)
+ *   in place of S(.).  So a mate counts with its records' paths when it has records, with R(r) when mismatch rescue places it, and as
+ *   empty otherwise (no record and: no candidate, or a candidate left unplaced, or placed only with a gap).
+ *     joined:  A n B not empty: one unit, A n B.     split: both non-empty, disjoint: two units, A and B.
+ *     single:  one non-empty: one unit.              none: no unit.
+ *   R(r) is the set at d*(r) and nothing else: a rescued mate whose kept placements miss every path of its partner is SPLIT from it, even where
+ *   a placement at a larger distance would have met one.  Mates are still rescued one by one; no insert size, no orientation.
+ *   The run's ECs are the distinct unit sets with their unit counts; a unit made of exact mates, of rescued mates or of one of each, with the
+ *   same set, is one EC.  joined + 2 split + single = ec_stats.reads.
+ *
+ * A fragment whose mates both have records is what it is under pairing alone; with no rescued mate in the run the classes are those of
+ * pairing and the classes alone; fragments (r, r) give the classes of the unpaired run with the rescued reads in the classes.  Nothing else
+ * changes: records, BAM, coverage, the rescue and gap tables, the rescued and gapped records, and every stat that exists.  A pass that
+ * collect redoes counts once, a batch under the skip flags of report coverage counts nothing.  The classes depend on the reads, their
+ * pairing and the index alone: not on batch size, pipeline depth, align-stage variant, results_on_device, or how the fragments are spread
+ * over ctxs (the merge of several ctxs is a sum by set). */
+typedef struct groot_rescue_pairs_stats {
+    uint64_t exact_rescued_joined, exact_rescued_split;         /* fragments of one mate with records and one rescued mate */
+    uint64_t rescued_rescued_joined, rescued_rescued_split;     /* fragments of two rescued mates */
+    uint64_t single_exact, single_rescued;                      /* fragments with one non-empty mate: it has records / it is rescued */
+    uint64_t rescued_mates;   /* rescued mates in a unit (a joined fragment of two rescued mates has two) */
+    uint64_t bitmap_units;    /* units among the above folded on the host from a bitmap: a mate in more than 4 graphs (1 under GROOT_TEST_SHARED_SLOW) */
+    uint64_t launches;        /* the three kernels of kernels_rescue_pairs.hpp since open, whether the rule is on now or not */
+} groot_rescue_pairs_stats;
+/* on != 0: puts the ctx into "rescued mates in paired-end units" -- switches on whichever of equivalence classes, pairing and the rescued
+ * reads in the classes is off, and the rule above; the one way in which pairing and the rescued classes run together
+ * (groot_hip_rescue_ec_enable with pairing on, and groot_hip_pairs_enable(1) with the rescued classes on and the rule off, keep refusing).
+ * Needs mismatch rescue on (GROOT_E_STATE) and nothing in flight (GROOT_E_STATE).  GROOT_E_UNSUPPORTED, whichever is enabled second, beside
+ * shared reads, assigned coverage in any form, assigned coverage over fragments, the gap-placed reads in the classes, and assignment.
+ * on == 0: the rule and the rescued classes go, equivalence classes and pairing stay; groot_hip_rescue_ec_enable(ctx, 0),
+ * groot_hip_rescue_enable(ctx, .., 0) and groot_hip_ec_enable(ctx, 0) while the rule is on do the same, and so does
+ * groot_hip_pairs_enable(ctx, 0), which switches pairing off too.  groot_hip_ec_reset zeroes the classes and these stats and leaves the
+ * rule on.  While the rule is on, groot_hip_pairs_stats and groot_hip_ec_stats cover the fragments with a rescued mate,
+ * groot_rescue_ec_stats.reads is rescued_mates and .slow_reads those of them in a unit that took a bitmap.  A fragment with a mate that
+ * fits no row takes one bitmap of groot_rescue_ec_stats.rows per non-empty mate; a batch that needs more fails at collect with
+ * GROOT_E_NOSPACE (the message names GROOT_TEST_RESCUE_EC_ROWS) and counts NOTHING: the classes, groot_hip_ec_stats, groot_hip_pairs_stats and
+ * these stats are what they were before it, the fragments whose mates both have records included.  Device memory: 1 byte per read of a batch. */
+int groot_hip_rescue_pairs_enable(groot_ctx *ctx, int on);
+/* Since the rule came on / groot_hip_ec_reset; zeros while it is off, but for launches.  Waits for everything in flight. */
+int groot_hip_rescue_pairs_stats(groot_ctx *ctx, groot_rescue_pairs_stats *out);
 
 /* ---- rescued reads in assigned coverage ----------------------------------------------------------------------------------
  * The assigned-coverage table piles up records, and a rescued read has none: with the rescued reads in the classes alone, the EM would
