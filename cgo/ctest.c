@@ -234,6 +234,15 @@ int main(int argc, char **argv)
     if (rps.exact_rescued_joined || rps.exact_rescued_split || rps.rescued_rescued_joined || rps.rescued_rescued_split || rps.single_exact || rps.single_rescued ||
         rps.rescued_mates || rps.bitmap_units || rps.launches)
         DIE("groot_hip_rescue_pairs_stats: counts while the feature is off");
+    /* RescueAcovPairsEnable / RescueAcovPairsStatsGet: the same for the rescued mates in assigned coverage over fragments -- refused without
+     * mismatch rescue, a min_slots that is no power of two is invalid, off while off is a no-op, and the stats stay zero */
+    groot_rescue_acov_pairs_stats raps;
+    if (groot_hip_rescue_acov_pairs_enable(ctxs[0], 1, 0) != GROOT_E_STATE) DIE("groot_hip_rescue_acov_pairs_enable without mismatch rescue was not refused");
+    if (groot_hip_rescue_acov_pairs_enable(ctxs[0], 1, 3) != GROOT_E_INVALID) DIE("groot_hip_rescue_acov_pairs_enable with min_slots = 3 was not refused");
+    if (groot_hip_rescue_acov_pairs_enable(ctxs[0], 0, 0)) DIE("groot_hip_rescue_acov_pairs_enable(0): %s", groot_hip_last_error(ctxs[0]));
+    if (groot_hip_rescue_acov_pairs_stats(ctxs[0], &raps)) DIE("groot_hip_rescue_acov_pairs_stats: %s", groot_hip_last_error(ctxs[0]));
+    if (raps.exact_records || raps.exact_left_out || raps.rescued_records || raps.rescued_left_out || raps.host_records || raps.dropped || raps.log_rows || raps.launches)
+        DIE("groot_hip_rescue_acov_pairs_stats: counts while the feature is off");
     for (int d = 0; d < n_ctx; d++) groot_hip_close(ctxs[d]);
     groot_index_free(idx);
     return 0;

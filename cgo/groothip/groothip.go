@@ -512,6 +512,38 @@ func (c *Ctx) RescuePairsStatsGet() (RescuePairsStats, error) {
 		uint64(st.single_exact), uint64(st.single_rescued), uint64(st.rescued_mates), uint64(st.bitmap_units), uint64(st.launches)}, nil
 }
 
+// RescueAcovPairsStats mirrors groot_rescue_acov_pairs_stats
+type RescueAcovPairsStats struct {
+	ExactRecords, ExactLeftOut, RescuedRecords, RescuedLeftOut uint64
+	HostRecords, Dropped, LogRows, Launches                    uint64
+}
+
+// RescueAcovPairsEnable puts the ctx into rescued mates in assigned coverage over fragments (include/groot_hip.h, "rescued mates in
+// assigned coverage over fragments"): it switches on whichever of the classes, pairing, the rescued classes, the rescued mates' rule,
+// assigned coverage and its rule over fragments is off, and a record or a kept placement of a mate then counts on the paths of the mate's
+// unit.  Needs RescueEnable first.  minSlots: 0 or a power of two, the table's slots at least.  Off: the rule and assigned coverage go, the
+// classes, pairing and the rescued mates' rule stay.  Only while nothing is in flight.
+func (c *Ctx) RescueAcovPairsEnable(on bool, minSlots uint64) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.groot_hip_rescue_acov_pairs_enable(c.h, v, C.uint64_t(minSlots)); rc != 0 {
+		return c.err("groot_hip_rescue_acov_pairs_enable")
+	}
+	return nil
+}
+
+// RescueAcovPairsStatsGet returns the records of fragments with a rescued mate in the pileup since RescueAcovPairsEnable or AcovReset (waits for everything in flight)
+func (c *Ctx) RescueAcovPairsStatsGet() (RescueAcovPairsStats, error) {
+	var st C.groot_rescue_acov_pairs_stats
+	if rc := C.groot_hip_rescue_acov_pairs_stats(c.h, &st); rc != 0 {
+		return RescueAcovPairsStats{}, c.err("groot_hip_rescue_acov_pairs_stats")
+	}
+	return RescueAcovPairsStats{uint64(st.exact_records), uint64(st.exact_left_out), uint64(st.rescued_records), uint64(st.rescued_left_out),
+		uint64(st.host_records), uint64(st.dropped), uint64(st.log_rows), uint64(st.launches)}, nil
+}
+
 func (c *Ctx) err(what string) error {
 	return fmt.Errorf("%s: %s", what, C.GoString(C.groot_hip_last_error(c.h)))
 }

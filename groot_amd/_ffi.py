@@ -138,6 +138,18 @@ def rescue_pairs_prototypes(L):
     L.groot_hip_rescue_pairs_enable.restype = L.groot_hip_rescue_pairs_stats.restype = C.c_int
 
 
+# ---- rescued mates in assigned coverage over fragments (groot_hip.h) ----
+RESCUE_ACOV_PAIRS_STATS = ("exact_records", "exact_left_out", "rescued_records", "rescued_left_out", "host_records", "dropped", "log_rows",
+                           "launches")   # groot_rescue_acov_pairs_stats, eight uint64
+
+
+def rescue_acov_pairs_prototypes(L):
+    """argtypes of groot_hip_rescue_acov_pairs_enable / groot_hip_rescue_acov_pairs_stats (libgroot_hip.so)"""
+    L.groot_hip_rescue_acov_pairs_enable.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+    L.groot_hip_rescue_acov_pairs_stats.argtypes = [C.c_void_p, u64p]
+    L.groot_hip_rescue_acov_pairs_enable.restype = L.groot_hip_rescue_acov_pairs_stats.restype = C.c_int
+
+
 def opt_ptr(arr, ctype):
     """as_ptr, or a NULL pointer for None"""
     return None if arr is None else as_ptr(arr, ctype)

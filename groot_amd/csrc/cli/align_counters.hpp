@@ -29,6 +29,7 @@ struct Harvested {                           // the sums over every harvest so f
     groot_rescue_acov_stats rescue_acov{};                   // --callsRescued: their records in the pileup (groot_hip_rescue_acov_*)
     groot_gap_acov_stats gap_acov{};                         // --callsGapped: the gap-placed reads' records in the pileup (groot_hip_gap_acov_*)
     groot_rescue_pairs_stats rescue_pairs{};                 // --rescuedPaired: the fragments with a rescued or a lone mate, by kind (groot_hip_rescue_pairs_*)
+    groot_rescue_acov_pairs_stats rescue_acov_pairs{};       // --callsRescuedPaired: the one-pass records of the fragments with a rescued mate (groot_hip_rescue_acov_pairs_*)
     groot_acov_pairs_stats acov_pairs{};                     // --callsPaired: the records piled up and left out under the rule for fragments (groot_hip_acov_pairs_*)
 };
 
@@ -69,6 +70,8 @@ public:
             if (int rc = groot_hip_gap_rec_enable(ctx, a_.gap_record_slots_given ? (uint64_t)a_.gap_record_slots : 4ull * std::max<uint32_t>(a_.batch, 1u))) return rc;
         if (plan_.shared)
             if (int rc = groot_hip_shared_enable(ctx, on)) return rc;
+        if (plan_.calls_rescued_paired && on)      // (the rule brings the classes, pairing, the rescued mates' rule and assigned coverage over fragments with it)
+            return groot_hip_rescue_acov_pairs_enable(ctx, 1, (uint64_t)a_.call_slots);
         if (plan_.calls && on)
             if (int rc = plan_.calls_paired ? groot_hip_acov_pairs_enable(ctx, 1) : groot_hip_acov_enable(ctx, 1)) return rc;
         if (plan_.abundance)
@@ -156,6 +159,14 @@ public:
             std::lock_guard<std::mutex> lk(mu_);
             groot_rescue_acov_stats &t = h_.rescue_acov;
             t.records += st.records; t.host_records += st.host_records; t.dropped += st.dropped; t.launches += st.launches; t.log_rows = st.log_rows;
+        }
+        if (plan_.calls_rescued_paired) {      // (one-pass records without room have failed the export above too)
+            groot_rescue_acov_pairs_stats st{};
+            if (int rc = groot_hip_rescue_acov_pairs_stats(ctx, &st)) return rc;
+            std::lock_guard<std::mutex> lk(mu_);
+            groot_rescue_acov_pairs_stats &t = h_.rescue_acov_pairs;
+            t.exact_records += st.exact_records; t.exact_left_out += st.exact_left_out; t.rescued_records += st.rescued_records; t.rescued_left_out += st.rescued_left_out;
+            t.host_records += st.host_records; t.dropped += st.dropped; t.launches += st.launches; t.log_rows = st.log_rows;
         }
         if (plan_.calls_gapped) {   // (gapped records without room have failed the export above as well)
             groot_gap_acov_stats st{};

@@ -176,7 +176,12 @@ void write_calls(const Args &a, const AlignPlan &plan, const groot_index_view &v
         die("%s", groot_host_last_error());
     logf("\tcalls: %llu tuple(s) of (class, ARG, interval) from %zu context(s), %llu line(s), %llu called at depth >= %g over >= %.2f of the length, in %.3f s, written to %s",
          (unsigned long long)m_tp, k, (unsigned long long)n_lines, (unsigned long long)n_called, a.call_depth, a.cov_cutoff, seconds_since(t_calls), a.calls_out.c_str());
-    if (plan.calls_rescued)
+    if (plan.calls_rescued_paired)
+        logf("\tcalls: fragments with a rescued mate: %llu exact record(s) beside a rescued partner piled up and %llu left out, %llu placement(s) of rescued mates piled up "
+             "and %llu left out on ARGs outside their unit; %llu of them on ARGs of more than 4 graphs; the table started with %lld slot(s)",
+             (unsigned long long)h.rescue_acov_pairs.exact_records, (unsigned long long)h.rescue_acov_pairs.exact_left_out, (unsigned long long)h.rescue_acov_pairs.rescued_records,
+             (unsigned long long)h.rescue_acov_pairs.rescued_left_out, (unsigned long long)h.rescue_acov_pairs.host_records, a.call_slots);
+    else if (plan.calls_rescued)
         logf("\tcalls: %llu rescued record(s) counted in the pileup, one per placement of a rescued read, %llu of them on ARGs of more than 4 graphs; the table started with %lld slot(s)",
              (unsigned long long)h.rescue_acov.records, (unsigned long long)h.rescue_acov.host_records, a.call_slots);
     if (plan.calls_gapped)

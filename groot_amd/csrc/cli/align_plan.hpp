@@ -12,6 +12,7 @@ struct AlignPlan {
     bool calls_rescued = false; // --callsRescued: and their kept placements the pileup of --calls
     bool calls_gapped = false;  // --callsGapped: and so do the gap-placed reads' (a DEL as two intervals, an INS as one)
     bool rescued_paired = false; // --rescuedPaired: --abundanceRescued over fragments (a rescued mate joins its fragment's unit with its rescued set)
+    bool calls_rescued_paired = false; // --callsRescuedPaired: --calls over fragments with rescued mates (a record or placement counts on the paths of its mate's unit)
     bool calls_paired = false;  // --callsPaired: --calls over fragments (a joined fragment's records count on the paths of its set only)
     bool rescued_bam = false;   // --rescuedBam: the kept placements of the rescued reads as BAM records in a file of their own
     bool rescued_bam_gaps = false; // --rescuedBamGaps: and the kept placements of the gap-rescued reads with them
@@ -103,6 +104,8 @@ int plan_align(const Args &a, AlignPlan *p)
     // --abundanceRescued: checked behind everything above
     if (p->ab_rescued && !p->abundance) return refuse("--abundanceRescued adds the rescued reads to the classes --abundance estimates from: it needs --abundance");
     if (p->ab_rescued && p->calls && !a.calls_rescued) return refuse("--abundanceRescued cannot be combined with --calls: its pileup weighs records, and a rescued read has none");
+    if (p->ab_rescued && p->frags && !a.rescued_paired && a.calls_rescued_paired)      // (the one place a missing --rescuedPaired can be told: behind this check it would never be reached)
+        return refuse("--callsRescuedPaired piles up under the units of --rescuedPaired: it needs --rescuedPaired");
     if (p->ab_rescued && p->frags && !a.rescued_paired)
         return refuse("--abundanceRescued cannot be combined with %s yet: mates are rescued one by one, and a fragment's set has no rule for them",
                       a.paired ? "--paired" : "--interleaved");
@@ -146,9 +149,15 @@ int plan_align(const Args &a, AlignPlan *p)
     if (a.rescued_paired && !p->frags) return refuse("--rescuedPaired is the rule for the rescued mates of fragments: it needs --paired or --interleaved");
     if (a.rescued_paired && p->shared)
         return refuse("--rescuedPaired cannot be combined with --sharedReads: its pairs hold no rescued reads, and the fragments with a rescued mate would be missing from them");
-    if (a.rescued_paired && p->calls) return refuse("--rescuedPaired cannot be combined with --calls: its pileup has no rule for a fragment with a rescued mate");
+    if (a.rescued_paired && p->calls && !a.calls_rescued_paired) return refuse("--rescuedPaired cannot be combined with --calls: its pileup has no rule for a fragment with a rescued mate");
     if (a.rescued_paired && p->ab_gapped) return refuse("--rescuedPaired cannot be combined with --abundanceGapped: the rule for fragments knows exact and mismatch-rescued mates only");
     p->rescued_paired = a.rescued_paired;
+    // --callsRescuedPaired: checked behind everything above (it is the rule --rescuedPaired lacked beside --calls, and passes over that refusal alone)
+    if (a.calls_rescued_paired && !p->calls) return refuse("--callsRescuedPaired piles up the fragments with rescued mates in the file of --calls: it needs --calls");
+    if (a.calls_rescued_paired && !p->calls_paired) return refuse("--callsRescuedPaired extends the rule of --callsPaired to rescued mates: it needs --callsPaired");
+    if (a.calls_rescued_paired && !p->calls_rescued) return refuse("--callsRescuedPaired piles up the placements --callsRescued counts, over fragments: it needs --callsRescued");
+    // (--callsPaired has asked for fragments and --callsRescued for --abundanceRescued: a missing --rescuedPaired was refused where those two meet, above)
+    p->calls_rescued_paired = a.calls_rescued_paired;
     p->coverage = p->report || p->variants || p->indels;
     p->counters = p->report || p->abundance || p->assign || p->rescue;
     return 0;

@@ -76,6 +76,7 @@ struct Args {
     bool abundance_gapped = false;           // --abundanceGapped: and so do the reads gapped rescue (--indels) places
     bool rescued_paired = false;             // --rescuedPaired: with --abundanceRescued and --paired / --interleaved, a rescued mate joins its fragment's unit with its rescued set
     bool calls_paired = false;               // --callsPaired: with --calls and --paired / --interleaved, the pileup counts a joined fragment's records on the paths of its set only
+    bool calls_rescued_paired = false;       // --callsRescuedPaired: with --calls, --callsPaired, --callsRescued and --rescuedPaired, the pileup over fragments with rescued mates
     bool calls_gapped = false;               // --callsGapped: with --calls, --callsRescued and --abundanceGapped, the gap-placed reads' placements join the pileup too
     bool calls_rescued = false;              // --callsRescued: with --calls and --abundanceRescued, the rescued reads' placements join the pileup
     long long call_slots = 1ll << 24;        // --callSlots N (a power of two): the slots the assigned-coverage table starts with under --callsRescued

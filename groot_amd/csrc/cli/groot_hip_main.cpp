@@ -40,6 +40,8 @@ void usage()
             "                  [--abundance a.tsv --abundanceRescued --indels i.tsv --abundanceGapped --calls c.tsv --callsRescued --callsGapped]\n"
             "                  [(--paired | --interleaved) --abundance a.tsv --calls c.tsv --callsPaired]\n"
             "                  [(--paired | --interleaved) --abundance a.tsv --abundanceRescued --rescuedPaired]\n"
+            "                  [(--paired | --interleaved) --abundance a.tsv --abundanceRescued --rescuedPaired --calls c.tsv --callsPaired --callsRescued\n"
+            "                   --callsRescuedPaired [--callSlots 16777216]]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
             "                  [--assignFrom a.tsv [--minPosterior 0.0]]\n"
             "                  [--variants v.tsv [--rescue 2] [--variantMinReads 2] [--variantMinShare 0.1]]\n"
@@ -97,7 +99,11 @@ void usage()
             "                   intersect counts on the ARGs of the intersection only -- elsewhere the fragment has no posterior.  Not with --callsRescued.\n"
             "                   --abundanceRescued only beside --rescuedPaired: a mate without an exact alignment that mismatch rescue places counts in its\n"
             "                   fragment with the ARGs it was placed on, so an exact mate narrows a rescued one and two rescued mates still make a fragment.\n"
-            "                   Not with --sharedReads, --calls, --abundanceGapped or --assignFrom)\n"
+            "                   Not with --sharedReads, --calls, --abundanceGapped or --assignFrom.\n"
+            "                   --callsRescuedPaired, beside --calls --callsPaired --callsRescued --rescuedPaired: the calls file over fragments with rescued\n"
+            "                   mates -- a record or a placement of a mate counts on the ARGs of the mate's unit, the fragment's when its mates' sets\n"
+            "                   intersect, and is left out elsewhere.  --callSlots is the room for the records piled up in one pass: the rescued mates'\n"
+            "                   placements and the exact records of a mate joined with a rescued one (a run that drops one fails and names the flag))\n"
             "  groot-hip report [--bamFile x.bam] [-c 0.97] [--lowCov] [--sharedReads s.tsv] [--abundance a.tsv [--abundanceMin 1.0]] [--log F]\n"
             "                  [--bootstraps B [--bootSeed 1]] [-p N] [--calls c.tsv [--callDepth 1.0] [--callSupport]]\n"
             "                  [--rarefy r.tsv [--rarefySteps 10] [--rarefyReps 20] [--rarefySeed 1]]\n"
@@ -179,6 +185,7 @@ Args parse(int argc, char **argv)
         else if (a.cmd == "align" && f == "--callsGapped") a.calls_gapped = true;
         else if (a.cmd == "align" && f == "--callsPaired") a.calls_paired = true;
         else if (a.cmd == "align" && f == "--rescuedPaired") a.rescued_paired = true;
+        else if (a.cmd == "align" && f == "--callsRescuedPaired") a.calls_rescued_paired = true;
         else if (a.cmd == "align" && f == "--callSlots") {
             const std::string t = v();
             char *end = nullptr;

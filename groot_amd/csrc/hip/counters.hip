@@ -181,6 +181,7 @@ static int acov_launch(groot_ctx *c, Slot *s, const SharedArgs &sa)
         hipLaunchKernelGGL(acov_serial_kernel, dim3(grid_for(s->trav_cap)), dim3(kBlock), 0, c->tstream, sa, c->ct.acov_tab_ser.p, s->ct.d_acov_ser.p);
     }
     c->ct.acov_launches++;
+    if (int rc = rescue_acov_pairs_launch(c, s, sa)) return rc;     // (rescued mates in assigned coverage over fragments: while the unit rows are live)
     return acov_count(c, s);
 }
 
@@ -405,7 +406,11 @@ int counters_launch(groot_ctx *c, Slot *s)
         if (k.rp_on) {           // rescued mates in paired-end units: the merge and the expansion wait for the units rescue_launch makes -- all of a batch or none
             HIP_TRY(c, hipGetLastError());
             if (int rc = rescue_launch(c, s, sa, tab)) return rc;
-            hipLaunchKernelGGL(ec_merge_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p, (uint32_t *)nullptr);
+            // (with the rescued mates in assigned coverage over fragments: the units' serials, and the pileup behind that one merge)
+            hipLaunchKernelGGL(ec_merge_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, k.ec.table(), tab, ++k.ec_epoch, k.ec_fill.p, s->ct.d_ec_slow.p,
+                               k.rap_on ? k.acov_tab_ser.p : (uint32_t *)nullptr);
+            if (k.rap_on)
+                if (int rc = acov_launch(c, s, sa)) return rc;
             hipLaunchKernelGGL(shared_expand_kernel<true>, gt, dim3(kBlock), 0, c->tstream, sa, tab);
             HIP_TRY(c, hipGetLastError());
             return GROOT_OK;
@@ -801,6 +806,7 @@ int groot_hip_acov_enable(groot_ctx *c, int on)
     HIP_TRY(c, hipSetDevice(c->device));
     if (!on) {
         if (c->ct.rac_on) rescue_ec_release(c->ct);     // (the rescued reads in it go, and the rescued classes that came on with them)
+        rescue_acov_pairs_release(c->ct);               // (the rescued mates leave it; their rule in the classes stays)
         c->ct.acp_stats.release();                      // (the rule over fragments goes with it; pairing stays)
         c->ct.acp_on = false;
         c->ct.acov.release();

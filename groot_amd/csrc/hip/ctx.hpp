@@ -280,6 +280,17 @@ struct Counters {
     DevBuf<unsigned long long> rac_stats;  // [kRescueAcovStats]
     uint64_t rac_host_records = 0;         // rescued records folded on the host since enable / groot_hip_acov_reset
     uint64_t rac_launches = 0;             // kernels launched for it since open; the two that take the place of rec's count there
+    // rescued mates in assigned coverage over fragments (groot_hip_rescue_acov_pairs_*, kernels_rescue_acov_pairs.hpp): the one state in which
+    // the rescued mates' rule and assigned coverage are on together (rap_on implies rp_on and acp_on, and both imply rap_on; rac_on is off
+    // beside it).  The kept placements, and the exact records of a mate joined with a rescued partner, are claimed and added in one pass
+    // behind the batch's merge; those of the fragments on bitmaps come back in the slot's log and are folded on the host at collect.
+    bool rap_on = false;
+    uint32_t rap_log_cap = 0;              // log entries per batch (fixed at enable)
+    DevBuf<uint32_t> rap_cand_ser;         // RescueAcovArgs::cand_ser (tail stream: one batch at a time, as the candidates are)
+    DevBuf<uint8_t> rap_fclass;            // RescueAcovPairSink::fclass (the same)
+    DevBuf<unsigned long long> rap_stats;  // [kRescueAcovPairStats]
+    uint64_t rap_host[4] = {0, 0, 0, 0};   // exact records counted / left out, rescued records counted / left out on the host since enable / groot_hip_acov_reset
+    uint64_t rap_launches = 0;             // the kernels of kernels_rescue_acov_pairs.hpp since open (stays put while it is off)
     // rescued records (groot_hip_rescue_rec_*, kernels_rescue_rec.hpp; needs mismatch rescue on) and gapped records (groot_hip_gap_rec_*,
     // kernels_gap_rec.hpp; needs gapped rescue on).  The count kernel / the gap kernel also leaves every read's number of kept placements, a
     // scan and the emit kernel behind it write the batch's records into a buffer of the slot, and collect copies as many as there are into

@@ -98,20 +98,29 @@ __global__ __launch_bounds__(kBlock) void rescue_acov_clear_kernel(SharedArgs a,
     }
 }
 
-__global__ __launch_bounds__(kBlock) void rescue_acov_kernel(RescueAcovArgs a, AcovTable t)
+// which placements of a candidate count: all of them here; those on a path of the unit of the mate's fragment in
+// kernels_rescue_acov_pairs.hpp (RescueAcovUnit), which sums the others in `left`
+struct RescueAcovAll {
+    static constexpr bool kFilter = false;
+    __device__ __forceinline__ uint32_t row(uint32_t r) const { return r; }
+    __device__ __forceinline__ bool has(const RescueEcArgs &, uint32_t, uint32_t) const { return true; }
+};
+
+template <class Unit> __device__ __forceinline__ void rescue_acov_body(const RescueAcovArgs &a, const AcovTable &t, const Unit &unit, unsigned long long *left_out)
 {
-    if (!shared_live(a.e.s)) return;
     const RescueArgs &ra = a.e.r;
     const uint32_t n = min(*ra.n_cand, ra.n_reads), n_paths = a.e.s.n_paths;
-    uint32_t added = 0, dropped = 0;
+    uint32_t added = 0, dropped = 0, left = 0;
     for (uint32_t i0 = blockIdx.x * kBlock; i0 < n; i0 += gridDim.x * kBlock) {      // (uniform per wavefront: the shuffles of the stats)
         const uint32_t i = i0 + threadIdx.x;
         if (i >= n) continue;
         const uint32_t ser = a.cand_ser[i];
         if (ser == kAcovNone) continue;
         const uint32_t r = ra.cand[i], len = (uint32_t)(ra.seq_off[r + 1] - ra.seq_off[r]);
+        const uint32_t row = unit.row(r);
         rescue_each_kept(ra, r, ra.dstar[i], [&](uint32_t p, uint32_t to) {
             if (p >= n_paths) return;
+            if (Unit::kFilter && !unit.has(a.e, row, p)) { left++; return; }
             const uint32_t x = rescue_acov_x(ra, p, to);
             const uint32_t s = acov_claim(t, ((unsigned long long)(ser + 1u) << 32) | p, ((unsigned long long)x << 32) | (x + len - 1u), a.fill, ~0u);
             const bool room = s != kAcovNone;                // (both counts without a branch: an early return here costs the kernel 12 bytes of scratch)
@@ -122,6 +131,16 @@ __global__ __launch_bounds__(kBlock) void rescue_acov_kernel(RescueAcovArgs a, A
     }
     const uint32_t st[2] = {added, dropped}, where[2] = {0, kRescueAcovDropped};
     rescue_add_stats(a.stats, st, where);
+    if (Unit::kFilter) {
+        const uint32_t lst[1] = {left}, lwhere[1] = {0};
+        rescue_add_stats(left_out, lst, lwhere);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void rescue_acov_kernel(RescueAcovArgs a, AcovTable t)
+{
+    if (!shared_live(a.e.s)) return;
+    rescue_acov_body(a, t, RescueAcovAll{}, nullptr);
 }
 
 } // namespace groot

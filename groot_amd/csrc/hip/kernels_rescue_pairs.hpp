@@ -160,7 +160,14 @@ __device__ __forceinline__ void pair_mate_bits(const RescuePairArgs &a, const Pa
     }
 }
 
-__global__ __launch_bounds__(kBlock) void rescue_pair_kernel(RescuePairArgs a)
+// what rescue_pair_body tells of every fragment it makes a unit of: nothing here; the fragment's class, and the records of a fragment on
+// bitmaps, to the slot's log in kernels_rescue_acov_pairs.hpp (RescueAcovPairSink)
+struct RescuePairNoSink {
+    __device__ __forceinline__ void rows(uint32_t, bool) const {}
+    __device__ __forceinline__ void bitmaps(const RescuePairArgs &, uint32_t, const PairMate &, const PairMate &, uint32_t, bool) const {}
+};
+
+template <class Sink> __device__ __forceinline__ void rescue_pair_body(const RescuePairArgs &a, const Sink &sink)
 {
     const SharedArgs &s = a.e.s;
     if (!shared_live(s)) return;
@@ -193,6 +200,7 @@ __global__ __launch_bounds__(kBlock) void rescue_pair_kernel(RescuePairArgs a)
             }
             bm_units += two && !joined ? 2u : 1u;
             bm_mates += n_resc;
+            sink.bitmaps(a, f, x, y, row, two && !joined);
         } else {
             if (x.exact) pair_write_row(s, x);
             if (y.exact) pair_write_row(s, y);
@@ -205,6 +213,7 @@ __global__ __launch_bounds__(kBlock) void rescue_pair_kernel(RescuePairArgs a)
                 if (x.any()) a.state[x.r] = kRescuePairUnit;
                 if (y.any()) a.state[y.r] = kRescuePairUnit;
             }
+            sink.rows(f, joined);
         }
         er_j += two && n_resc == 1u && joined;  er_s += two && n_resc == 1u && !joined;
         rr_j += two && n_resc == 2u && joined;  rr_s += two && n_resc == 2u && !joined;
@@ -221,15 +230,17 @@ __global__ __launch_bounds__(kBlock) void rescue_pair_kernel(RescuePairArgs a)
     block_add(one_e + one_r, &s.batch[5]);
 }
 
+__global__ __launch_bounds__(kBlock) void rescue_pair_kernel(RescuePairArgs a) { rescue_pair_body(a, RescuePairNoSink{}); }
+
 // The bitmap demand of the batch is known here (rescue_pair_kernel has ended).  It fits: the rows marked kRescuePairUnit join the units
 // of the exact + exact fragments in the per-batch table, and the batch's counts of the rule go to the totals.  It does not fit: the batch
 // counts NOTHING -- the table (the exact + exact fragments' units, not merged yet), the batch's pairing counts and its slow lists are
 // cleared, so ec_merge_kernel<true> and shared_expand_kernel<true> behind this launch find nothing, and the host fails the batch at collect.
-__global__ __launch_bounds__(kBlock) void rescue_pair_insert_kernel(RescuePairArgs a)
+// (no_room: the batch needs more than the slot holds -- bitmaps here, bitmaps or log entries in kernels_rescue_acov_pairs.hpp)
+__device__ __forceinline__ void rescue_pair_insert_body(const RescuePairArgs &a, bool no_room)
 {
     const SharedArgs &s = a.e.s;
-    if (!shared_live(s)) return;
-    if (*a.e.n_slow > a.e.rows) {
+    if (no_room) {
         for (uint32_t slot = blockIdx.x * kBlock + threadIdx.x; slot < a.tab_size; slot += gridDim.x * kBlock) {
             s.tab_rep[slot] = kSharedEmpty;
             s.tab_cnt[slot] = 0;
@@ -240,6 +251,12 @@ __global__ __launch_bounds__(kBlock) void rescue_pair_insert_kernel(RescuePairAr
     for (uint32_t r = blockIdx.x * kBlock + threadIdx.x; r < a.e.r.n_reads; r += gridDim.x * kBlock)
         if (a.state[r] == kRescuePairUnit) shared_insert_row(s, r);
     if (blockIdx.x == 0 && threadIdx.x < kRescuePairStats) a.total[threadIdx.x] += a.stats[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kBlock) void rescue_pair_insert_kernel(RescuePairArgs a)
+{
+    if (!shared_live(a.e.s)) return;
+    rescue_pair_insert_body(a, *a.e.n_slow > a.e.rows);
 }
 
 } // namespace groot

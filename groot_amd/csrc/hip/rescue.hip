@@ -1,6 +1,7 @@
 // rescue.hip -- the rescue family behind every batch's order stage, and its C ABI (include/groot_hip.h): mismatch rescue
 // (kernels_rescue.hpp), gapped rescue (kernels_gap.hpp), rescued reads in the equivalence classes (kernels_rescue_ec.hpp) and in assigned
-// coverage (kernels_rescue_acov.hpp), gap-placed reads in the classes (kernels_gap_ec.hpp) and in assigned coverage (kernels_gap_acov.hpp),
+// coverage (kernels_rescue_acov.hpp), rescued mates in the fragments' units (kernels_rescue_pairs.hpp) and in assigned coverage over
+// fragments (kernels_rescue_acov_pairs.hpp), gap-placed reads in the classes (kernels_gap_ec.hpp) and in assigned coverage (kernels_gap_acov.hpp),
 // rescued records (kernels_rescue_rec.hpp) and gapped records (kernels_gap_rec.hpp).  One of the seven translation units of
 // libgroot_hip.so (launch.hpp); counters.hip calls the hooks of rescue.hpp, everything else here is internal.
 #include <cstring>   // before rocprim: its texture iterator calls host memset
@@ -37,6 +38,7 @@
 #include "kernels_rescue_ec.hpp"
 #include "kernels_rescue_pairs.hpp"
 #include "kernels_rescue_acov.hpp"
+#include "kernels_rescue_acov_pairs.hpp"
 #include "kernels_rescue_rec.hpp"
 #include "kernels_gap_rec.hpp"
 #include "kernels_gap_ec.hpp"
@@ -75,6 +77,14 @@ static void gec_release(Counters &k)
 }
 
 namespace groot {
+// rescued mates in assigned coverage over fragments go off (with the rescued mates' rule, or with assigned coverage)
+void rescue_acov_pairs_release(Counters &k)
+{
+    k.rap_cand_ser.release(); k.rap_fclass.release(); k.rap_stats.release();
+    k.rap_on = false; k.rap_log_cap = 0;
+    std::fill(k.rap_host, k.rap_host + 4, 0);
+}
+
 // rescued reads in the equivalence classes go off (with mismatch rescue, or with the classes): nothing of it stays on the device
 void rescue_ec_release(Counters &k)
 {
@@ -84,6 +94,7 @@ void rescue_ec_release(Counters &k)
     // (and with it the rule that lets them stand beside pairing; pairing itself stays)
     k.rp_state.release(); k.rp_stats.release();
     k.rp_on = false;
+    rescue_acov_pairs_release(k);          // (and with the rule its part of assigned coverage over fragments; that table itself stays)
     // (and with it the rescued reads in assigned coverage, which are keyed by these classes)
     k.rac_cand_ser.release(); k.rac_stats.release();
     k.rac_on = false; k.rac_log_cap = 0; k.rac_host_records = 0;
@@ -332,6 +343,26 @@ static int rec_collect(groot_ctx *c, Slot *s, bool refetch)
         }
         return GROOT_OK;
     }
+    if (k.rap_on && s->ct.d_rac_nlog.p) {  // rescued mates in assigned coverage over fragments: the fragments on bitmaps have their records in the log
+        if (refetch) HIP_TRY(c, hipMemcpy(&h.rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (h.rac_log > k.rap_log_cap) {   // the batch fails alone, as above (rescue_acov_pair_insert_kernel)
+            if (s->status == GROOT_OK) {
+                char buf[256];
+                snprintf(buf, sizeof buf, "rescued mates in assigned coverage over fragments: a batch's fragments that fit no row have %u records, and the log has "
+                         "room for %u (GROOT_TEST_RESCUE_ACOV_LOG)", h.rac_log, k.rap_log_cap);
+                s->status = GROOT_E_NOSPACE;
+                s->status_msg = buf;
+            }
+            return GROOT_OK;
+        }
+        std::vector<uint64_t> bits((size_t)h.rec_slow * k.rec_bw);
+        std::vector<uint4> log(h.rac_log);
+        HIP_TRY(c, hipMemcpy(bits.data(), s->ct.d_rec_bits.p, bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (h.rac_log) HIP_TRY(c, hipMemcpy(log.data(), s->ct.d_rac_log.p, log.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+        const auto rows = unfold_rows(bits.data(), h.rec_slow, k.rec_bw, (uint32_t)k.h_len.size(), k.ec_host, k.rec_slow);
+        const int64_t bad = fold_log_units(log.data(), log.size(), rows, kRapLogExact, k.acov_host, k.rap_host);
+        return bad < 0 ? GROOT_OK : fail(c, GROOT_E_DEVICE, "rescued mates in assigned coverage over fragments: a logged record names bitmap %u of %u", (uint32_t)bad, h.rec_slow);
+    }
     if (h.rec_slow > k.rec_rows)
         return fail(c, GROOT_E_NOSPACE, "rescued reads in the equivalence classes: a batch has %u rescued reads whose sets lie in more graphs than a row holds, and room for "
                     "the bitmaps of %u (GROOT_TEST_RESCUE_EC_ROWS)", h.rec_slow, k.rec_rows);
@@ -368,6 +399,48 @@ static const void *count_kernel(bool gap, bool rr, bool rec)
     return of[4 * gap + 2 * rr + rec];
 }
 
+// what every kernel of the family reads of slot s's batch and of the ctx's tables (the parts of rescued and gapped records and of gapped
+// rescue are rescue_launch's to add)
+static RescueArgs rescue_args(groot_ctx *c, Slot *s, const SharedArgs &sa)
+{
+    Counters &k = c->ct;
+    RescueArgs ra{};
+    ra.seq = s->seq(); ra.seq_off = s->off(); ra.ctr = s->d_ctr.p; ra.trav_off = c->trav_off.p;
+    ra.rbuf = k.res_rbuf.p; ra.rcap = k.res_rcap; ra.cand = k.res_cand.p; ra.n_cand = k.res_ncand.p;
+    ra.text = k.res_text.p; ra.tag = k.res_tag.p; ra.path = k.res_path.p; ra.tab = k.res_tab.p; ra.occ = k.res_occ.p; ra.slot_base = k.res_base.p;
+    ra.starts = k.res_starts.p; ra.ends = k.res_ends.p; ra.alt = k.res_alt.p; ra.stats = k.res_stats.p;
+    ra.tab_mask = (uint32_t)k.res_tab.n - 1u; ra.n_reads = s->n_reads; ra.max_mismatch = k.res_m;
+    if (k.rec_on) {
+        ra.path_bit = k.rec_path_bit.p; ra.set_graph = sa.set_graph; ra.set_mask = sa.set_mask; ra.dstar = k.rec_dstar.p;
+        ra.pw = sa.pw; ra.max_segs = sa.max_segs;
+    }
+    return ra;
+}
+
+// the rows, the bitmaps and the counts of the rescued reads in the classes, as rescue_launch and rescue_acov_pairs_launch hand them to their kernels
+static RescueEcArgs rescue_ec_args(groot_ctx *c, Slot *s, const RescueArgs &ra, const SharedArgs &sa)
+{
+    Counters &k = c->ct;
+    RescueEcArgs ea{};
+    ea.r = ra; ea.s = sa; ea.bits = s->ct.d_rec_bits.p; ea.n_slow = s->ct.d_rec_slow.p; ea.stats = k.rec_stats.p;
+    ea.rows = k.rec_rows; ea.bw = k.rec_bw;
+    return ea;
+}
+
+// rescued mates in assigned coverage over fragments: what its kernels on both sides of the merge share
+static RescueAcovPairsArgs rescue_acov_pairs_args(groot_ctx *c, Slot *s, const RescueArgs &ra, const SharedArgs &sa)
+{
+    Counters &k = c->ct;
+    RescueAcovPairsArgs p{};
+    p.a.e = rescue_ec_args(c, s, ra, sa);
+    static_assert(kRapDropped == kRapRescued + kRescueAcovDropped, "rescue_acov_body adds {added, dropped} at stats[0] and stats[kRescueAcovDropped]");
+    p.a.tab_ser = k.acov_tab_ser.p; p.a.cand_ser = k.rap_cand_ser.p; p.a.fill = k.acov_fill.p; p.a.stats = k.rap_stats.p + kRapRescued;
+    p.a.log = s->ct.d_rac_log.p; p.a.n_log = s->ct.d_rac_nlog.p; p.a.log_cap = k.rap_log_cap;
+    p.ix = RapIndex{k.d_np_off.p, k.d_np.p, k.d_len.p};
+    p.fclass = k.rap_fclass.p; p.read_ser = s->ct.d_acov_ser.p; p.stats = k.rap_stats.p;
+    return p;
+}
+
 // ---- the hooks of rescue.hpp -------------------------------------------------------------------------------------------------
 namespace groot {
 
@@ -380,20 +453,12 @@ int rescue_launch(groot_ctx *c, Slot *s, const SharedArgs &sa, uint32_t tab)
     Counters &k = c->ct;
     if (!k.res_on) return GROOT_OK;
     const dim3 gr(grid_for(s->n_reads)), gt(grid_for(tab)), blk(kBlock);
-    RescueArgs ra{};
-    ra.seq = s->seq(); ra.seq_off = s->off(); ra.ctr = s->d_ctr.p; ra.trav_off = c->trav_off.p;
-    ra.rbuf = k.res_rbuf.p; ra.rcap = k.res_rcap; ra.cand = k.res_cand.p; ra.n_cand = k.res_ncand.p;
-    ra.text = k.res_text.p; ra.tag = k.res_tag.p; ra.path = k.res_path.p; ra.tab = k.res_tab.p; ra.occ = k.res_occ.p; ra.slot_base = k.res_base.p;
-    ra.starts = k.res_starts.p; ra.ends = k.res_ends.p; ra.alt = k.res_alt.p; ra.stats = k.res_stats.p;
-    ra.tab_mask = (uint32_t)k.res_tab.n - 1u; ra.n_reads = s->n_reads; ra.max_mismatch = k.res_m;
+    RescueArgs ra = rescue_args(c, s, sa);
     HIP_TRY(c, hipMemsetAsync(k.res_ncand.p, 0, sizeof(uint32_t), c->tstream));
     hipLaunchKernelGGL(rescue_pack_kernel, gr, blk, 0, c->tstream, ra);
-    if (k.rec_on) {          // (the rows of the candidates are free, and with the rule of the rescued mates off so is the per-batch table: shared_expand_kernel, launched by
-                             // counters_launch ahead of this call on this stream, has cleared it.  With that rule on the table still holds the units of the fragments with
-                             // records on both mates -- the merge waits behind this call -- and their rows are rows of reads with records, which no candidate shares)
-        ra.path_bit = k.rec_path_bit.p; ra.set_graph = sa.set_graph; ra.set_mask = sa.set_mask; ra.dstar = k.rec_dstar.p;
-        ra.pw = sa.pw; ra.max_segs = sa.max_segs;
-    }
+    // (With the rescued classes on: the rows of the candidates are free, and with the rule of the rescued mates off so is the per-batch table: shared_expand_kernel,
+    // launched by counters_launch ahead of this call on this stream, has cleared it.  With that rule on the table still holds the units of the fragments with
+    // records on both mates -- the merge waits behind this call -- and their rows are rows of reads with records, which no candidate shares)
     if (k.rr.on) {           // rescued records: the count kernel also leaves every read's kept placements, zero for a read that is no candidate
         ra.n_kept = k.rr.kept.p; ra.rec_d = k.rr.aux.p;
         HIP_TRY(c, hipMemsetAsync(k.rr.kept.p, 0, ((size_t)s->n_reads + 1) * sizeof(uint32_t), c->tstream));
@@ -448,8 +513,7 @@ int rescue_launch(groot_ctx *c, Slot *s, const SharedArgs &sa, uint32_t tab)
     HIP_TRY(c, s->ct.d_rec_bits.reserve((size_t)k.rec_rows * k.rec_bw));
     HIP_TRY(c, s->ct.d_rec_slow.reserve(1));
     HIP_TRY(c, hipMemsetAsync(s->ct.d_rec_slow.p, 0, sizeof(uint32_t), c->tstream));
-    ea.r = ra; ea.s = sa; ea.bits = s->ct.d_rec_bits.p; ea.n_slow = s->ct.d_rec_slow.p; ea.stats = k.rec_stats.p;
-    ea.rows = k.rec_rows; ea.bw = k.rec_bw;
+    ea = rescue_ec_args(c, s, ra, sa);
     if (rac) {
         HIP_TRY(c, s->ct.d_rac_log.reserve(std::max<uint32_t>(k.rac_log_cap, 1u)));
         HIP_TRY(c, s->ct.d_rac_nlog.reserve(1));
@@ -477,8 +541,18 @@ int rescue_launch(groot_ctx *c, Slot *s, const SharedArgs &sa, uint32_t tab)
         HIP_TRY(c, hipMemsetAsync(k.rp_state.p, kRescueUnplaced, std::max<uint32_t>(s->n_reads, 1u), c->tstream));
         HIP_TRY(c, hipMemsetAsync(pa.stats, 0, kRescuePairStats * sizeof(unsigned long long), c->tstream));
         hipLaunchKernelGGL(rescue_pair_mark_kernel, gr, blk, 0, c->tstream, pa);
-        hipLaunchKernelGGL(rescue_pair_kernel, dim3(grid_for(s->n_reads / 2u)), blk, 0, c->tstream, pa);
-        hipLaunchKernelGGL(rescue_pair_insert_kernel, dim3(grid_for(std::max(s->n_reads, tab))), blk, 0, c->tstream, pa);
+        if (k.rap_on) {      // ... and in assigned coverage over fragments: every fragment's class, and the records of the fragments on bitmaps into the slot's log
+            HIP_TRY(c, s->ct.d_rac_log.reserve(std::max<uint32_t>(k.rap_log_cap, 1u)));
+            HIP_TRY(c, s->ct.d_rac_nlog.reserve(1));
+            HIP_TRY(c, hipMemsetAsync(s->ct.d_rac_nlog.p, 0, sizeof(uint32_t), c->tstream));
+            HIP_TRY(c, hipMemsetAsync(k.rap_fclass.p, kRapNone, std::max<uint32_t>(s->n_reads / 2u, 1u), c->tstream));
+            const RescueAcovPairSink sink{RapIndex{k.d_np_off.p, k.d_np.p, k.d_len.p}, k.rap_fclass.p, s->ct.d_rac_log.p, s->ct.d_rac_nlog.p, k.rap_log_cap};
+            hipLaunchKernelGGL(rescue_acov_pair_kernel, dim3(grid_for(s->n_reads / 2u)), blk, 0, c->tstream, pa, sink);
+            hipLaunchKernelGGL(rescue_acov_pair_insert_kernel, dim3(grid_for(std::max(s->n_reads, tab))), blk, 0, c->tstream, pa, s->ct.d_rac_nlog.p, k.rap_log_cap);
+        } else {
+            hipLaunchKernelGGL(rescue_pair_kernel, dim3(grid_for(s->n_reads / 2u)), blk, 0, c->tstream, pa);
+            hipLaunchKernelGGL(rescue_pair_insert_kernel, dim3(grid_for(std::max(s->n_reads, tab))), blk, 0, c->tstream, pa);
+        }
         HIP_TRY(c, hipGetLastError());
         k.rp_launches += 3;
         return GROOT_OK;
@@ -506,6 +580,22 @@ int rescue_launch(groot_ctx *c, Slot *s, const SharedArgs &sa, uint32_t tab)
     return GROOT_OK;
 }
 
+// Behind ec_merge_kernel<true> and acov_serial_paired_kernel, ahead of the ordinary count and of shared_expand_kernel<true>: the unit rows and
+// the per-batch table are live, tab_ser[] holds the units' serials.  One pass, here and never at collect.
+int rescue_acov_pairs_launch(groot_ctx *c, Slot *s, const SharedArgs &sa)
+{
+    Counters &k = c->ct;
+    if (!k.rap_on) return GROOT_OK;
+    const RescueAcovPairsArgs p = rescue_acov_pairs_args(c, s, rescue_args(c, s, sa), sa);
+    const dim3 gr(grid_for(s->n_reads)), blk(kBlock);
+    hipLaunchKernelGGL(rescue_acov_pairs_serial_kernel, gr, blk, 0, c->tstream, p);
+    hipLaunchKernelGGL(rescue_acov_pairs_exact_kernel, dim3(grid_for(s->n_reads / 2u)), blk, 0, c->tstream, p, k.acov.table());
+    hipLaunchKernelGGL(rescue_acov_pairs_kernel, gr, blk, 0, c->tstream, p, k.acov.table());
+    HIP_TRY(c, hipGetLastError());
+    k.rap_launches += 3;
+    return GROOT_OK;
+}
+
 int rescue_fetch(groot_ctx *c, Slot *s)
 {
     const Counters &k = c->ct;
@@ -514,7 +604,7 @@ int rescue_fetch(groot_ctx *c, Slot *s)
     CounterStatus *h = s->ct.h_status.p;    // (the classes' words: rec_on, and so the classes, are on with each of the four)
     if (k.rec_on) HIP_TRY(c, hipMemcpyAsync(&h->rec_slow, s->ct.d_rec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     if (k.gec_on && s->ct.d_gec_slow.p) HIP_TRY(c, hipMemcpyAsync(&h->gec_slow, s->ct.d_gec_slow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
-    if (k.rac_on) HIP_TRY(c, hipMemcpyAsync(&h->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
+    if (k.rac_on || k.rap_on) HIP_TRY(c, hipMemcpyAsync(&h->rac_log, s->ct.d_rac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     if (k.gac_on && s->ct.d_gac_nlog.p) HIP_TRY(c, hipMemcpyAsync(&h->gac_log, s->ct.d_gac_nlog.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->d2h_stream));
     return GROOT_OK;
 }
@@ -560,6 +650,8 @@ int rescue_acov_reset(groot_ctx *c)
     if (k.rac_on) HIP_TRY(c, hipMemset(k.rac_stats.p, 0, kRescueAcovStats * sizeof(unsigned long long)));
     if (k.gac_on) HIP_TRY(c, hipMemset(k.gac_stats.p, 0, kGapAcovStats * sizeof(unsigned long long)));
     k.rac_host_records = k.gac_host_records = k.gac_host_placements = 0;
+    if (k.rap_on) HIP_TRY(c, hipMemset(k.rap_stats.p, 0, kRescueAcovPairStats * sizeof(unsigned long long)));
+    std::fill(k.rap_host, k.rap_host + 4, 0);
     return GROOT_OK;
 }
 
@@ -569,6 +661,13 @@ int rescue_acov_dropped(groot_ctx *c)
     uint64_t rst[kRescueAcovStats] = {}, gst[kGapAcovStats] = {};
     if (k.rac_on) HIP_TRY(c, hipMemcpy(rst, k.rac_stats.p, sizeof(rst), hipMemcpyDeviceToHost));
     if (k.gac_on) HIP_TRY(c, hipMemcpy(gst, k.gac_stats.p, sizeof(gst), hipMemcpyDeviceToHost));
+    if (k.rap_on) {
+        uint64_t pst[kRescueAcovPairStats];
+        HIP_TRY(c, hipMemcpy(pst, k.rap_stats.p, sizeof(pst), hipMemcpyDeviceToHost));
+        if (pst[kRapDropped])
+            return fail(c, GROOT_E_NOSPACE, "assigned coverage: %llu records of fragments with a rescued mate found no room in a table of %u slots, which grows between "
+                        "batches only: start it larger (min_slots of groot_hip_rescue_acov_pairs_enable, align --callSlots)", (unsigned long long)pst[kRapDropped], k.acov.cap);
+    }
     const bool res = rst[kRescueAcovDropped] != 0;      // (the rescued records' count first, as ever)
     if (res || gst[kGapAcovDropped])
         return fail(c, GROOT_E_NOSPACE, "assigned coverage: %llu %s records found no room in a table of %u slots, which grows between batches only: start it "
@@ -987,6 +1086,77 @@ int groot_hip_rescue_pairs_stats(groot_ctx *c, groot_rescue_pairs_stats *out)
     out->single_exact = st[4]; out->single_rescued = st[5];
     out->rescued_mates = st[6]; out->bitmap_units = st[7];
     out->launches = c->ct.rp_launches;
+    return GROOT_OK;
+}
+
+// ---- rescued mates in assigned coverage over fragments (kernels_rescue_acov_pairs.hpp; the rule is in groot_hip.h) -------------------
+int groot_hip_rescue_acov_pairs_enable(groot_ctx *c, int on, uint64_t min_slots)
+{
+    if (int rc = switchable(c, "rescued mates in assigned coverage over fragments")) return rc;
+    Counters &k = c->ct;
+    if (!on) return k.rap_on ? groot_hip_acov_enable(c, 0) : GROOT_OK;     // (the rule and its records go with the table; the classes, pairing and the rescued mates' rule stay)
+    if (min_slots & (min_slots - 1)) return fail(c, GROOT_E_INVALID, "rescued mates in assigned coverage over fragments: min_slots = %llu is not a power of two", (unsigned long long)min_slots);
+    if (min_slots > (1ull << 31)) return fail(c, GROOT_E_INVALID, "rescued mates in assigned coverage over fragments: min_slots = %llu, at most 2^31 are supported", (unsigned long long)min_slots);
+    if (!k.res_on) return fail(c, GROOT_E_STATE, "rescued mates in assigned coverage over fragments: mismatch rescue is off (groot_hip_rescue_enable)");
+    if (!k.rap_on) {
+        if (k.asg_on) return fail(c, GROOT_E_UNSUPPORTED, "rescued mates in assigned coverage over fragments count S(r), which assignment collapses (groot_hip_assign_enable)");
+        if (k.sh_on)
+            return fail(c, GROOT_E_UNSUPPORTED, "rescued mates in assigned coverage over fragments with shared reads are not supported: the triangle has no rescued reads "
+                        "(groot_hip_shared_enable)");
+        if (k.gec_on)        // (and with it the gap-placed reads in the pileup, which need them)
+            return fail(c, GROOT_E_UNSUPPORTED, "rescued mates in assigned coverage over fragments with gap-placed reads in the equivalence classes or the pileup are not "
+                        "supported: the fragment rule knows records and mismatch rescue's sets only (groot_hip_gap_ec_enable, groot_hip_gap_acov_enable)");
+        // The enables this one stands on refuse each other: each is made with the other side hidden.  First the rescued mates' rule (the
+        // classes, the rescued classes, pairing), with assigned coverage out of sight; then assigned coverage over fragments, with the
+        // rescued classes out of sight.  The unpaired rule of the rescued records has no meaning over fragments: it goes once both have come
+        // on, the rescued classes stay.  A failure of the first leaves the ctx as it was; one behind it takes assigned coverage off, so that no
+        // state with the rescued mates' rule and assigned coverage on and this rule off is left behind.
+        const bool was_acov = k.acov_on, was_acp = k.acp_on;
+        auto undo = [&](int rc) {
+            const std::string why = c->err;
+            groot_hip_acov_enable(c, 0);
+            c->err = why;
+            return rc;
+        };
+        k.acov_on = k.acp_on = false;
+        int rc = groot_hip_rescue_pairs_enable(c, 1);
+        k.acov_on = was_acov; k.acp_on = was_acp;
+        if (rc) return rc;
+        k.rec_on = false;
+        rc = groot_hip_acov_pairs_enable(c, 1);
+        k.rec_on = true;
+        if (rc) return undo(rc);
+        if (k.rac_on) {
+            k.rac_cand_ser.release(); k.rac_stats.release();
+            k.rac_on = false; k.rac_log_cap = 0; k.rac_host_records = 0;
+        }
+        k.rap_log_cap = c->kn.rescue_acov_log ? c->kn.rescue_acov_log : (uint32_t)(GROOT_RESCUE_ACOV_BYTES / sizeof(uint4));
+        const uint32_t R = std::max<uint32_t>(c->prm.max_batch_reads, 1u);
+        hipError_t e = k.rap_cand_ser.alloc(R);
+        if (e == hipSuccess) e = k.rap_fclass.alloc(R);
+        if (e == hipSuccess) e = k.rap_stats.alloc(kRescueAcovPairStats);
+        if (e == hipSuccess) e = hipMemset(k.rap_stats.p, 0, kRescueAcovPairStats * sizeof(unsigned long long));
+        if (e != hipSuccess) return undo(fail(c, GROOT_E_DEVICE, "rescued mates in assigned coverage over fragments: %s", hipGetErrorString(e)));
+        std::fill(k.rap_host, k.rap_host + 4, 0);
+        k.rap_on = true;
+    }
+    if (k.acov.cap < min_slots)
+        if (int rc = acov_grow(c, (uint32_t)(min_slots / k.acov.cap))) return rc;
+    return GROOT_OK;
+}
+
+int groot_hip_rescue_acov_pairs_stats(groot_ctx *c, groot_rescue_acov_pairs_stats *out)
+{
+    if (!c || !out) return GROOT_E_INVALID;
+    uint64_t st[kRescueAcovPairStats];
+    if (int rc = part_stats(c, c->ct.rap_on, c->ct.rap_stats, st)) return rc;
+    const uint64_t *h = c->ct.rap_host;    // (zero while the rule is off)
+    out->exact_records = st[kRapExact] + h[0]; out->exact_left_out = st[kRapExactLeft] + h[1];
+    out->rescued_records = st[kRapRescued] + h[2]; out->rescued_left_out = st[kRapRescuedLeft] + h[3];
+    out->host_records = h[0] + h[2];
+    out->dropped = st[kRapDropped];
+    out->log_rows = c->ct.rap_on ? c->ct.rap_log_cap : 0;
+    out->launches = c->ct.rap_launches;
     return GROOT_OK;
 }
 

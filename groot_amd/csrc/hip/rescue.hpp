@@ -17,6 +17,8 @@ int rescue_launch(groot_ctx *c, Slot *s, const SharedArgs &sa, uint32_t tab);   
 int rescue_fetch(groot_ctx *c, Slot *s);                        // counters_fetch: the family's status words, on the copy-out stream
 int rescue_collect_records(groot_ctx *c, Slot *s, bool redone); // counters_collect, ahead of ec_collect: the batch's rescued and gapped records into the slot's pinned memory
 int rescue_collect_classes(groot_ctx *c, Slot *s, bool redone); // counters_collect, between ec_collect and acov_collect: the slow rescued and gap-rescued reads' bitmaps and logs into ec_host and acov_host
+int rescue_acov_pairs_launch(groot_ctx *c, Slot *s, const SharedArgs &sa); // acov_launch, between acov_serial_paired_kernel and the count: the one-pass records of the fragments with a rescued mate
+void rescue_acov_pairs_release(Counters &k);                    // groot_hip_acov_enable(0): the rescued mates leave assigned coverage over fragments (their rule in the classes stays)
 void rescue_ec_release(Counters &k);                            // groot_hip_ec_enable(0), groot_hip_acov_enable(0): the family's reads leave the classes, and with them assigned coverage
 int rescue_ec_reset(groot_ctx *c);                              // groot_hip_ec_reset: the counts of the family's reads in the classes start over
 int rescue_acov_reset(groot_ctx *c);                            // groot_hip_acov_reset: the counts of the family's records in assigned coverage start over

@@ -3,6 +3,7 @@
 // coverage.  No HIP runtime call and no ctx: tools/rescue_fold_check.cpp runs both on a CPU under the sanitizers.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstddef>
 #include <cstdint>
@@ -46,6 +47,23 @@ inline int64_t fold_log(const uint4 *log, size_t n_log, const std::vector<std::v
         acov_host[rows[row]][{e.y, e.z, e.w}]++;
         records++;
         if (!(e.x & second)) placements++;
+    }
+    return -1;
+}
+
+// The log of the fragments on bitmaps (rescued mates in assigned coverage over fragments): log[n_log] = (row | exact, path, Pos, last).  An
+// entry whose path is in its row's ID list is one record of acov_host under that list; any other is left out.  count[] gets the exact
+// records counted / left out and the kept placements counted / left out (`exact` is the flag that tells the two kinds apart).
+// -> -1, or the row of the first entry that names no row of `rows` or an empty one (the entries ahead of it are folded, none behind it)
+inline int64_t fold_log_units(const uint4 *log, size_t n_log, const std::vector<std::vector<uint32_t>> &rows, uint32_t exact, AcovHost &acov_host, uint64_t (&count)[4])
+{
+    for (size_t i = 0; i < n_log; i++) {
+        const uint4 &e = log[i];
+        const uint32_t row = e.x & ~exact, kind = (e.x & exact) ? 0u : 2u;
+        if (row >= rows.size() || rows[row].empty()) return row;
+        if (!std::binary_search(rows[row].begin(), rows[row].end(), e.y)) { count[kind + 1]++; continue; }
+        acov_host[rows[row]][{e.y, e.z, e.w}]++;
+        count[kind]++;
     }
     return -1;
 }

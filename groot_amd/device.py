@@ -85,6 +85,7 @@ def lib():
         _ffi.gap_acov_prototypes(L)
         _ffi.acov_pairs_prototypes(L)
         _ffi.rescue_pairs_prototypes(L)
+        _ffi.rescue_acov_pairs_prototypes(L)
         _lib = L
     return _lib
 
@@ -727,6 +728,21 @@ class Aligner:
         v = (C.c_uint64 * len(_ffi.RESCUE_PAIRS_STATS))()
         self._check(lib().groot_hip_rescue_pairs_stats(self._h, v))
         return dict(zip(_ffi.RESCUE_PAIRS_STATS, (int(x) for x in v)))
+
+    # ---- rescued mates in assigned coverage over fragments (groot_hip_rescue_acov_pairs_*) -----------------
+    def rescue_acov_pairs_enable(self, on=True, min_slots=0):
+        """the pileup of --calls over fragments with rescued mates: switches on whichever of the classes, pairing, the rescued classes, the
+        rescued mates' rule, assigned coverage and its rule over fragments is off, and the rule that a record or a kept placement of a mate
+        counts on the paths of the mate's unit (include/groot_hip.h, "rescued mates in assigned coverage over fragments").  Needs
+        rescue_enable first.  min_slots: 0 or a power of two, the table's slots at least.  Off: the rule and assigned coverage go; the
+        classes, pairing and the rescued mates' rule stay.  Only while nothing is in flight."""
+        self._check(lib().groot_hip_rescue_acov_pairs_enable(self._h, C.c_int(1 if on else 0), C.c_uint64(min_slots)))
+
+    def rescue_acov_pairs_stats(self):
+        """groot_hip_rescue_acov_pairs_stats: _ffi.RESCUE_ACOV_PAIRS_STATS as a dict; zeros while off, but for launches"""
+        v = (C.c_uint64 * len(_ffi.RESCUE_ACOV_PAIRS_STATS))()
+        self._check(lib().groot_hip_rescue_acov_pairs_stats(self._h, v))
+        return dict(zip(_ffi.RESCUE_ACOV_PAIRS_STATS, (int(x) for x in v)))
 
     # ---- fine-grained mirror of Sequence.RunMinHash ------------------------------------------
     def sketch(self, seq_concat, seq_off):

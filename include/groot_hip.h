@@ -731,6 +731,63 @@ int groot_hip_rescue_acov_enable(groot_ctx *ctx, int on, uint64_t min_slots);
 /* Waits for everything in flight; zeros while off, but for launches. */
 int groot_hip_rescue_acov_stats(groot_ctx *ctx, groot_rescue_acov_stats *out);
 
+/* ---- rescued mates in assigned coverage over fragments -----------------------------------------------------------------------
+ * "Rescued reads in assigned coverage" is unpaired, "assigned coverage over fragments" knows exact records only, and "rescued mates in
+ * paired-end units" refuses assigned coverage: its pileup had no rule for a fragment with a rescued mate.  This is the rule
+ * (kernels_rescue_acov_pairs.hpp):
+ *
+ *   S(r), R(r), S+(r), candidate, rescued, d*, kept placement (p, strand, x), X, len: exactly as in "mismatch rescue" and "rescued reads in the
+ *   equivalence classes".  Fragments, A = S+(r_2i), B = S+(r_2i+1), joined / split / single / none, units, ECs over units: exactly as in
+ *   "rescued mates in paired-end units" (DESIGN §25).  Canonical order, alpha, w(e,p): as for --abundance over those ECs.
+ *   U(r), the UNIT SET of a mate r with S+(r) non-empty:   A n B when r's fragment is joined (both mates the same set);  S+(r) when split or single.
+ *   An exact record of r on p COUNTS when p is in U(r), covering [Pos, min(Pos + M, path_len(p) - 1)]           (§13 / §24's interval, unchanged).
+ *   A kept placement (p, strand, x) of a rescued mate r COUNTS when p is in U(r), as one rescued record covering [X, X + len - 1]   (§19's interval).
+ *   A record or placement on a path outside U(r) is LEFT OUT (w(e,p) is defined for p in e only).  Every counting one counts once: both mates,
+ *   both strands, every x, several on one path, primary and secondary.  The two interval rules are not made alike.
+ *   The table is the multiset of counting exact AND rescued records grouped by (e = EC of U(r), p, Pos, last): n(e,p,Pos,last), integers.
+ *   A mate placed only with a gap, left unplaced, too short or with a non-ACGT base has the empty set and no record, as in §25.
+ *   A pass that collect redoes counts once; a batch under kCovSkipFlags counts nothing; a batch that fails counts nothing anywhere.
+ *   The table depends on the reads, their pairing and the index alone: not on batch size, pipeline depth, align stage, --ctxPerGpu or --gpus.
+ *
+ * So with no rescued mate in the run the table and the classes are those of assigned coverage over fragments; with split and single
+ * fragments only they are those of the unpaired run with the rescued reads in assigned coverage; fragments (r, r) give that run's classes
+ * with every n doubled.  The exact records whose filter needs exact records only (both mates exact; an exact mate that ends split or single)
+ * are claimed and added by the ordinary count, which collect may repeat.  The kept placements, and the exact records of a mate joined
+ * with a rescued partner, are filtered by a unit row that lives one batch long: they are claimed and added in one pass over the whole
+ * table behind the batch's merge, and what finds no room is counted in `dropped`, on which groot_hip_acov_export fails with
+ * GROOT_E_NOSPACE until groot_hip_acov_reset: start the table larger (min_slots).  A fragment on bitmaps (a mate in more than 4 graphs, 1
+ * under GROOT_TEST_SHARED_SLOW) has no serial on the device: its records of both kinds come back in the slot's log as (bitmap row, p, Pos,
+ * last) and are folded on the host at collect under the ID list of the unit's bitmap -- p in the list, or left out. */
+typedef struct groot_rescue_acov_pairs_stats {
+    uint64_t exact_records, exact_left_out;       /* exact records of a mate joined with a rescued partner, and of the exact mates of fragments on bitmaps: counted / left out */
+    uint64_t rescued_records, rescued_left_out;   /* kept placements of rescued mates in a unit: counted as rescued records / left out */
+    uint64_t host_records;  /* those of exact_records + rescued_records folded on the host from the log */
+    uint64_t dropped;       /* records of either kind that found no room in the table: groot_hip_acov_export fails while this is not 0 */
+    uint64_t log_rows;      /* log entries per batch: GROOT_RESCUE_ACOV_BYTES / 16, or GROOT_TEST_RESCUE_ACOV_LOG; 0 while off */
+    uint64_t launches;      /* the three kernels behind the merge since open, whether the rule is on now or not; the two that take the place of
+                               kernels of the rescued mates' rule count in groot_rescue_pairs_stats.launches */
+} groot_rescue_acov_pairs_stats;
+/* on != 0: puts the ctx into the rule above -- switches on whichever of the classes, pairing, the rescued classes, the rescued mates' rule,
+ * assigned coverage and assigned coverage over fragments is off, then the rule; the unpaired "rescued reads in assigned coverage" goes
+ * off if it was on (the rescued classes stay).  Needs mismatch rescue on (GROOT_E_STATE, with the reason) and nothing in flight
+ * (GROOT_E_STATE).  min_slots: 0, or a power of two (GROOT_E_INVALID otherwise): the table is grown to at least that many slots, also when
+ * the rule is on already.  GROOT_E_UNSUPPORTED, from whichever enable comes second, beside shared reads, assignment, and the gap-placed reads
+ * in the classes or the pileup.  While the rule is off every other refusal is what it was, and no state has the rescued mates' rule and
+ * assigned coverage both on without this rule.
+ * on == 0: the rule, assigned coverage (with its rule over fragments) and the rescued records go; the classes, pairing, the rescued classes
+ * and the rescued mates' rule stay.  groot_hip_acov_enable(ctx, 0) and groot_hip_acov_pairs_enable(ctx, 0) do the same.  Switching the
+ * rescued mates' rule, the rescued classes, the classes, pairing or mismatch rescue off takes this rule with it (and leaves what that
+ * call leaves otherwise: assigned coverage over fragments stays where pairing and the classes do).
+ * groot_hip_acov_reset and groot_hip_ec_reset (which calls it) zero the table, `dropped` and these stats and leave the rule on, as they do
+ * for the rescued reads in assigned coverage and for assigned coverage over fragments; groot_hip_rescue_reset leaves the table alone.
+ * A batch whose fragments on bitmaps have more records than `log_rows`, or need more bitmaps than groot_rescue_ec_stats.rows, fails at collect
+ * with GROOT_E_NOSPACE (the message names GROOT_TEST_RESCUE_ACOV_LOG / GROOT_TEST_RESCUE_EC_ROWS) and counts NOTHING in the classes, the
+ * table or any stat.  groot_acov_pairs_stats.left_out stays the exact + exact fragments' count.  Device memory: 5 bytes per read of a
+ * batch, `log_rows` entries per pipeline slot. */
+int groot_hip_rescue_acov_pairs_enable(groot_ctx *ctx, int on, uint64_t min_slots);
+/* Since the rule came on / groot_hip_acov_reset; zeros while it is off, but for launches.  Waits for everything in flight. */
+int groot_hip_rescue_acov_pairs_stats(groot_ctx *ctx, groot_rescue_acov_pairs_stats *out);
+
 /* ---- rescued records -------------------------------------------------------------------------------------------------------
  * Mismatch rescue piles its placements up in tables; the placements themselves are gone when the batch is.  With this on, every batch
  * also hands out one record per kept placement of its rescued reads: what a BAM record of the read needs.  The definition, integers only:

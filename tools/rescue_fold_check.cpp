@@ -120,10 +120,41 @@ static void check_fold()
     }
 }
 
+// the log of the fragments on bitmaps (rescued mates in assigned coverage over fragments): an entry counts when its path is in its row's list
+static void check_fold_units()
+{
+    const Rows rows{{3, 5}, {}, {7}};
+    {   // no entries: nothing is read (log may be null)
+        AcovHost ac;
+        uint64_t n[4] = {1, 2, 3, 4};
+        CHECK(fold_log_units(nullptr, 0, rows, kSecond, ac, n) == -1 && ac.empty() && n[0] == 1 && n[1] == 2 && n[2] == 3 && n[3] == 4);
+    }
+    {   // row 0 = {3, 5}: an exact record on 3 and a placement on 5 count, an exact record on 4 and placements on 2 and 6 (below, between
+        // and above the list) are left out; the same tuple from both kinds lands in one cell
+        const uint4 log[7] = {{0 | kSecond, 3, 10, 19}, {0, 5, 1, 9}, {0 | kSecond, 4, 10, 19}, {0, 2, 1, 9}, {0, 6, 1, 9}, {0, 3, 10, 19}, {2, 7, 0, 0}};
+        AcovHost ac;
+        uint64_t n[4] = {0, 0, 0, 0};
+        CHECK(fold_log_units(log, 7, rows, kSecond, ac, n) == -1);
+        CHECK((ac == AcovHost{{{3, 5}, {{{3, 10, 19}, 2}, {{5, 1, 9}, 1}}}, {{7}, {{{7, 0, 0}, 1}}}}));
+        CHECK(n[0] == 1 && n[1] == 1 && n[2] == 3 && n[3] == 2);
+    }
+    {   // an entry that names row n, and one that names an empty row with the flag: reported without it, the entries ahead are folded
+        const uint4 log[3] = {{2 | kSecond, 7, 1, 2}, {3, 5, 1, 2}, {2, 7, 1, 2}};
+        AcovHost ac;
+        uint64_t n[4] = {0, 0, 0, 0};
+        CHECK(fold_log_units(log, 3, rows, kSecond, ac, n) == 3);
+        CHECK((ac == AcovHost{{{7}, {{{7, 1, 2}, 1}}}}) && n[0] == 1 && n[1] == 0 && n[2] == 0 && n[3] == 0);
+        const uint4 empty[1] = {{1 | kSecond, 5, 1, 2}};
+        CHECK(fold_log_units(empty, 1, rows, kSecond, ac, n) == 1 && n[0] == 1 && n[1] == 0);
+        CHECK(fold_log_units(empty, 1, Rows{}, kSecond, ac, n) == 1);
+    }
+}
+
 int main()
 {
     check_unfold();
     check_fold();
+    check_fold_units();
     if (failures) { printf("rescue_fold_check: %d checks FAILED\n", failures); return 1; }
     printf("rescue_fold_check: ok\n");
     return 0;
